@@ -209,12 +209,44 @@ def plan_batches(n_steps, F, G):
     return plan                                                                 # that ended on two single-step batches was 5 % slower over all, profiles/r05f_*)
 
 
+def dump_step_outputs(out_dir, records, first, results, segments):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as DIR/<name>.npy (integers as float64, scores as
+    float32).  `records` = the gathered result records of every chunk of the step (all ranks, by chunk index); `results` / `segments` =
+    this rank's DecodingResults of the step (chunks first, first + 1, ...) with their (seek point, segments) from findSeekPointAndSegments."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(records)
+    width = max([len(r["tokens"]) for r in records] + [1])
+    tokens = np.full((n, width), -1.0)
+    for i, r in enumerate(records):
+        tokens[i, :len(r["tokens"])] = r["tokens"]
+    arrays = {"chunk_index": np.array([r["chunk_index"] for r in records], np.float64), "tokens": tokens,
+              "n_tokens": np.array([len(r["tokens"]) for r in records], np.float64),
+              "decoder_steps": np.array([r["steps"] for r in records], np.float64)}
+    for key in ("avg_logprob", "temperature", "compression_ratio", "no_speech_prob"):
+        arrays[key] = np.array([r[key] for r in records], np.float32)
+    # per-token log-probabilities and host segments of this rank's chunks (every chunk at one GPU); log-probs are 0 beyond a chunk's tokens
+    width = max([len(r.tokenLogProbs) for r in results] + [1])
+    logprobs = np.zeros((len(results), width), np.float32)
+    for i, r in enumerate(results):
+        logprobs[i, :len(r.tokenLogProbs)] = r.tokenLogProbs
+    arrays["token_logprobs"] = logprobs
+    arrays["seek_points"] = np.array([seek for seek, _ in segments], np.float64)
+    # one row per segment: chunk index, id, seek, start, end, token offset, token count, average log-prob
+    rows = [(first + i, g.id, g.seek, g.start, g.end, g.token_offset, g.n_tokens, g.avg_logprob)
+            for i, (_, segs) in enumerate(segments) for g in (segs or ())]
+    arrays["segments"] = np.array(rows, np.float64).reshape(-1, 8)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"wrote {len(arrays)} arrays of the last timed step ({n} chunks) to {out_dir}")
+
+
 def run_config(args, model_name, B, F, steps, warmup, world, rank, local_rank, dev, want_roofline, want_cpu, word_timestamps=False,
-               comm=None, scaling="strong", device_batch=None, whole_chip_leg=True):
+               comm=None, scaling="strong", device_batch=None, whole_chip_leg=True, dump_outputs=None):
     """B = chunks per step: in total over the ranks (strong scaling, the default) or per rank (weak).  A rank's share of a step is the
     contiguous block partition_chunks gives it; the shares of up to G consecutive steps are packed into one device batch of at most
     `device_batch` slots (continuous batching: default = B, i.e. G = 1 at one GPU; the headline packs two 64-chunk steps into one 128-slot
-    batch).  The steps of a run are dealt to the F sessions in equal shares (plan_batches)."""
+    batch).  The steps of a run are dealt to the F sessions in equal shares (plan_batches).  With `dump_outputs` rank 0 writes what the last
+    timed step computed to that directory (dump_step_outputs)."""
     import torch
     import torch.distributed as dist
     from whisperkit_amd import api, parallel
@@ -253,10 +285,11 @@ def run_config(args, model_name, B, F, steps, warmup, world, rank, local_rank, d
     st = model.specialTokens
 
     def hot_path(ss, g=1, n0=0):
-        """the rank's chunks of g consecutive steps (run steps n0 .. n0 + g - 1) as ONE device batch; returns (results, [records of step 0, step 1, ...], segments)"""
+        """the rank's chunks of g consecutive steps (run steps n0 .. n0 + g - 1) as ONE device batch; returns (results, [records of step 0, step 1, ...],
+        [(seek point, segments) per result])"""
         nb = g * n_local
         if nb == 0:
-            return [], [np.zeros((0, parallel.RECORD_INTS), np.int32) for _ in range(g)], 0
+            return [], [np.zeros((0, parallel.RECORD_INTS), np.int32) for _ in range(g)], []
         for k in range(g):
             for b, x in enumerate(audio[(n0 + k) % n_sets]):
                 ss.padOrTrim(x, k * n_local + b)       # PCM in host memory -> HBM, inside the timed region (SURVEY 8d)
@@ -264,16 +297,15 @@ def run_config(args, model_name, B, F, steps, warmup, world, rank, local_rank, d
         ss.encodeFeatures(nb)
         ss.prepareDecoderInputs(nb)
         res = ss.decodeText(prompt, opts, batch=nb)
-        nseg = 0
+        segments = []
         for b, r in enumerate(res):
             if word_timestamps:     # findAlignment (SegmentSeeker.swift:340-408): alignment rows of the result tokens -> DTW
                 api.dynamicTimeWarping(ss.getAlignmentWeights(b)[:len(r.tokens)])
-            _, segs = api.findSeekPointAndSegments(r.tokens, r.tokenLogProbs, opts, st, 0, 0, 480000, r.avgLogProb)   # segments on the host
-            nseg += len(segs or ())
+            segments.append(api.findSeekPointAndSegments(r.tokens, r.tokenLogProbs, opts, st, 0, 0, 480000, r.avgLogProb))   # segments on the host
         recs = [np.stack([parallel.pack_record(first + b, res[k * n_local + b].tokens, 0, res[k * n_local + b].steps, res[k * n_local + b].avgLogProb,
                                                res[k * n_local + b].temperature, res[k * n_local + b].compressionRatio) for b in range(n_local)])
                 for k in range(g)]
-        return res, recs, nseg
+        return res, recs, segments
 
     def run_steps(n):
         """n steps as the device batches of plan_batches(n, F, G), F batches in flight: worker f runs its batches on its own session /
@@ -309,7 +341,9 @@ def run_config(args, model_name, B, F, steps, warmup, world, rank, local_rank, d
         gathered = [parallel.gather_records(recs, per_rank_max, device=gdev, comm=comm) for o in out for _, per_step, _ in o for recs in per_step]
         assert len(gathered) == n
         step_dur = [(d / g, d) for p, ds in zip(plan, dur) for g, d in zip(p, ds) for _ in range(g)]      # (a batch's wall time shared by the steps it carries, the step's latency)
-        return out[0][0][0], gathered[-1], step_dur
+        lres, _, lsegs = out[-1][-1]             # the batch that carries the run's last step (gathered[-1]): this rank's share of that step
+        k = (plan[-1][-1] - 1) * n_local
+        return out[0][0][0], gathered[-1], step_dur, (lres[k:k + n_local], lsegs[k:k + n_local])
 
     def fence():
         for ss in sessions:
@@ -326,7 +360,7 @@ def run_config(args, model_name, B, F, steps, warmup, world, rank, local_rank, d
                 hot_path(sessions[f], g)
     fence()
     t0 = time.perf_counter()
-    res, allrecs, durs = run_steps(steps)
+    res, allrecs, durs, last_local = run_steps(steps)
     fence()
     elapsed = time.perf_counter() - t0
     if world > 1:
@@ -337,6 +371,8 @@ def run_config(args, model_name, B, F, steps, warmup, world, rank, local_rank, d
     if rank == 0 and getattr(args, "dump_records", None):
         with open(args.dump_records, "w") as f:
             json.dump([{"chunk_index": r["chunk_index"], "tokens": r["tokens"], "steps": r["steps"], "avg_logprob": r["avg_logprob"]} for r in allrecs], f)
+    if rank == 0 and dump_outputs:
+        dump_step_outputs(dump_outputs, allrecs, first, *last_local)
     log(f"{model_name}: timed region done: {elapsed:.3f} s for {steps} steps of {total} chunks ({n_local} on this rank), {F} batches in flight")
     dec_steps = [r.steps for r in res] if res else [min(args.sample_length, 224) - 1]
     audio_s = total * 30.0 * steps
@@ -572,6 +608,9 @@ def main():
     ap.add_argument("--no-other-configs", action="store_true")
     ap.add_argument("--dump-records", default=None, help="rank 0 writes the gathered result records of the last timed step (chunk index, "
                     "token ids, steps) to this JSON file: the N-rank rehearsal compares them with a 1-rank run (tests/test_gpu_round4.py)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="rank 0 writes what the last timed step of the configuration the result line reports "
+                    "computed (result records of every chunk, per-token log-probs, seek points and segments) as DIR/<name>.npy; the inputs are "
+                    "seeded, so two builds run with the same arguments can be compared output for output (bench_outputs/ is ignored by git)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -634,7 +673,7 @@ def main():
     dev_batch = args.device_batch if args.device_batch > 0 else (256 if args.batch >= 64 else args.batch)
     main_cfg = run_config(args, args.model, args.batch, args.inflight, args.steps, args.warmup, world, rank, local_rank, dev,
                           want_roofline=not args.no_roofline, want_cpu=(world == 1 and not args.no_cpu_baseline), comm=comm, scaling=args.scaling,
-                          device_batch=dev_batch)
+                          device_batch=dev_batch, dump_outputs=args.dump_outputs)
     other = {}
     headline = (args.model, args.batch) == ("large-v3", 64)
     extra = rank == 0 and world == 1 and not args.no_other_configs
