@@ -49,14 +49,21 @@ public final class HIPSession {
     /// slotsPerWorkgroup (wh_session_options, round 6): a workgroup of the absorbed cross-attention streams this many slots one after the other, so a
     /// launch takes ceil(batch / n) x keySplits workgroups whatever the batch (256-slot device batches, 1 split, 2 slots per workgroup = half of the
     /// chip: what bench.py keeps in flight three times); 0 = automatic (1).  Results do not depend on it, bit for bit.
-    public init(model: HIPModel, maxBatch: Int = 1, crossAttention: CrossAttentionMode = .automatic, keySplits: Int = 0, slotsPerWorkgroup: Int = 0) throws {
+    /// encoderPrecision (wh_session_options.encoder_precision): `.float16` = Float16 encoder GEMM operands (the reference's AudioEncoderOutput type,
+    /// the default); `.split` = every rounded encoder operand and the encoder output as a Float16 pair hi | lo, multiplied hi then lo into the same
+    /// fp32 accumulator: end-to-end logits within 1e-3 sigma of fp32 openai/whisper, for about twice the encoder's matrix work and the 24-bit K / V rows
+    /// (369 MB per slot at large-v3; `.automatic` cross-attention resolves to `.keyValueRows`, `.absorbed` throws).
+    public enum EncoderPrecision: Int32 { case float16 = 0, split = 1 }
+    public init(model: HIPModel, maxBatch: Int = 1, crossAttention: CrossAttentionMode = .automatic, keySplits: Int = 0, slotsPerWorkgroup: Int = 0,
+                encoderPrecision: EncoderPrecision = .float16) throws {
         var h: OpaquePointer?
-        if slotsPerWorkgroup > 0 {
+        if slotsPerWorkgroup > 0 || encoderPrecision != .float16 {
             var o = wh_session_options()
             wh_session_options_default(&o)
             o.cross_attention_mode = crossAttention.rawValue
             o.cross_attention_splits = Int32(keySplits)
             o.cross_attention_slots_per_workgroup = Int32(slotsPerWorkgroup)
+            o.encoder_precision = encoderPrecision.rawValue
             try check(wh_session_create_with_options(model.handle, Int32(maxBatch), &o, &h))
         } else {
             try check(wh_session_create_tuned(model.handle, Int32(maxBatch), crossAttention.rawValue, Int32(keySplits), &h))
@@ -68,6 +75,7 @@ public final class HIPSession {
     public var crossAttentionMode: CrossAttentionMode { CrossAttentionMode(rawValue: wh_session_cross_attention_mode(handle)) ?? .automatic }
     public var crossAttentionKeySplits: Int { Int(wh_session_cross_attention_splits(handle)) }
     public var crossAttentionSlotsPerWorkgroup: Int { Int(wh_session_cross_attention_slots_per_workgroup(handle)) }
+    public var encoderPrecision: EncoderPrecision { EncoderPrecision(rawValue: wh_session_encoder_precision(handle)) ?? .float16 }
     public var capturedStepGraphs: Int { Int(wh_session_step_graph_count(handle)) }
 
     /// WhisperKit.transcribeWithOptions(audioArrays:decodeOptionsArray:) (Core/WhisperKit.swift:716-812) on the library's own orchestrator:

@@ -241,16 +241,30 @@ int wh_session_create_tuned(wh_model* m, int max_batch, int cross_attention_mode
                                           A process that keeps several sessions in flight gives every session's cross-attention about half of
                                           the chip (128 workgroups): with 256-slot device batches that is 1 split and 2 slots per workgroup
                                           (bench.py: 2660 -> 2749 audio-s/s against 128-slot batches, profiles/r06i_*).  A slot is processed
-                                          exactly as by a workgroup of its own: results do not depend on this number, bit for bit. */
+                                          exactly as by a workgroup of its own: results do not depend on this number, bit for bit.
+     encoder_precision                    0 (default) Float16 GEMM operands in the encoder, the reference's AudioEncoderOutput type; 1 split:
+                                          every encoder GEMM operand that is rounded today (the mel, GELU(conv1), both LayerNorm outputs, the
+                                          attention output, GELU(fc1)) and the encoder output are kept as a Float16 pair hi | lo, hi = f16(x),
+                                          lo = f16(x - hi), and each GEMM multiplies the weights by hi and then by lo into the same fp32
+                                          accumulator (attention q / k / v / P stay Float16).  The encoder's share of the logits error drops
+                                          from ~1e-2 sigma to ~1e-4 sigma (end to end against fp32 openai/whisper: DESIGN section 6), for twice
+                                          the encoder GEMMs' matrix work - 1.6 - 1.7 x the encoder's time per chunk at large-v3
+                                          (profiles/r07_split_encoder_time.json) - and a second Float16 plane of every rounded activation.  A split session uses the per-layer 24-bit K / V rows: cross_attention_mode
+                                          -1 resolves to 0, and an explicit 1 is WH_ERR_INVALID_ARGUMENT (the absorbed kernel streams the
+                                          Float16 encoder output; a hi | lo stream would double the bytes of the decoder's dominant kernel).
+                                          The rows cost L x 1500 x d x 2 x 3 bytes per slot: 369 MB at large-v3 (32 layers, d = 1280).
+                                          Results stay bit-identical across batch sizes within the mode. */
 typedef struct wh_session_options {
     int32_t cross_attention_mode;
     int32_t cross_attention_splits;
     int32_t cross_attention_slots_per_workgroup;
-    int32_t reserved_[5];
+    int32_t encoder_precision;           /* 0 Float16 operands (default), 1 split hi | lo (above) */
+    int32_t reserved_[4];
 } wh_session_options;
 void wh_session_options_default(wh_session_options* out);
 int wh_session_create_with_options(wh_model* m, int max_batch, const wh_session_options* opt, wh_session** out);
 int wh_session_cross_attention_slots_per_workgroup(const wh_session* s);      /* 0 in K / V-row mode */
+int wh_session_encoder_precision(const wh_session* s);                        /* 0 Float16 operands, 1 split hi | lo (wh_session_options) */
 /* development aid (kernel bring-up, tools/xabs_check.py): the first nbytes of a named decode-step device buffer ("q", "zb_hi", ...);
    nbytes beyond the buffer's size is WH_ERR_INVALID_ARGUMENT */
 int wh_debug_peek(wh_session* s, const char* name, void* out_host, size_t nbytes);
@@ -272,7 +286,7 @@ int wh_set_mel(wh_session* s, int b, const float* mel_host /* [n_mels][3000] */)
 /* AudioEncoding.encodeFeatures (Core/AudioEncoder.swift:50-63) for slots [0, batch) */
 int wh_encode_features(wh_session* s, int batch);
 int wh_get_encoder_output(wh_session* s, int b, float* out_host /* [1500][d] */);
-int wh_set_encoder_output(wh_session* s, int b, const float* enc_host /* [1500][d] */);
+int wh_set_encoder_output(wh_session* s, int b, const float* enc_host /* [1500][d] */);   /* a split session also fills the lo plane */
 
 /* TextDecoding.prepareDecoderInputs + DecodingInputs.reset: project the encoder output to the per-layer
  * cross-attention K/V rows (once per window; K / V-row mode only - the absorbed mode keeps reading the encoder output itself, see
@@ -306,7 +320,7 @@ typedef struct wh_tensor {
     int32_t reserved_;
 } wh_tensor;
 int wh_get_mel_tensor(wh_session* s, int b, wh_tensor* out);                          /* f32 [n_mels][3000], the reference layout */
-int wh_get_encoder_output_tensor(wh_session* s, int b, int dtype, wh_tensor* out);    /* f32 or f16 [1500][d] */
+int wh_get_encoder_output_tensor(wh_session* s, int b, int dtype, wh_tensor* out);    /* f32 or f16 [1500][d]; f16 of a split session: the hi plane */
 int wh_get_logits_tensor(wh_session* s, wh_tensor* out);                              /* f32 [max_batch][n_vocab], step API / T > 0 */
 /* Device-resident hand-off (MLMultiArray outputs of the CoreML stages stay on the accelerator in the reference too): pointers
  * into the session's HBM buffers of slot b, valid until the session rewrites them; consume them on wh_session_stream(s) or after

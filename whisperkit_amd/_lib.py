@@ -55,7 +55,7 @@ class WhDecodingResult(C.Structure):
 
 class WhSessionOptions(C.Structure):
     _fields_ = [("cross_attention_mode", C.c_int32), ("cross_attention_splits", C.c_int32), ("cross_attention_slots_per_workgroup", C.c_int32),
-                ("reserved_", C.c_int32 * 5)]
+                ("encoder_precision", C.c_int32), ("reserved_", C.c_int32 * 4)]
 
 
 class WhTensor(C.Structure):
@@ -146,6 +146,7 @@ SYMBOLS = {
     "wh_session_options_default": (None, [C.POINTER(WhSessionOptions)]),
     "wh_session_create_with_options": (I, [VP, I, C.POINTER(WhSessionOptions), PVP]),
     "wh_session_cross_attention_slots_per_workgroup": (I, [VP]),
+    "wh_session_encoder_precision": (I, [VP]),
     "wh_debug_peek": (I, [VP, C.c_char_p, VP, C.c_size_t]),
     "wh_session_synchronize": (I, [VP]),
     "wh_session_stream": (VP, [VP]),

@@ -446,8 +446,10 @@ class Model:
 class Session:
     """Per-task state for up to `maxBatch` windows in flight (= DecodingInputs x maxBatch, one HIP stream)."""
 
+    ENCODER_PRECISIONS = {None: 0, "f16": 0, "split": 1}
+
     def __init__(self, model: Model, maxBatch: int = 1, crossAttentionMode: Optional[int] = None, crossAttentionSplits: Optional[int] = None,
-                 crossAttentionSlotsPerWorkgroup: Optional[int] = None):
+                 crossAttentionSlotsPerWorkgroup: Optional[int] = None, encoderPrecision: Optional[str] = None):
         """crossAttentionMode: None = the library's choice (absorbed from `xabsAutoMinSlots()` = 28 slots at the widths that support it: the
         choice looks at maxBatch only, so Session(m, 27) and Session(m, 28) run different kernels; both meet the 1e-3 relative logits
         contract), 0 = per-layer cross K / V rows (24-bit: Float16 + 8-bit residual), 1 = weight-absorbed cross-attention over the encoder output (csrc/xabs.hip).
@@ -460,15 +462,26 @@ class Session:
         several sessions share the GPU.
         crossAttentionSlotsPerWorkgroup (wh_session_options, round 6): a workgroup of the absorbed cross-attention streams this many slots one
         after the other, so a launch takes ceil(batch / n) x splits workgroups whatever the batch: 256-slot device batches with 2 slots per
-        workgroup keep the launch at half of the chip (bench.py's headline).  Results do not depend on it, bit for bit."""
+        workgroup keep the launch at half of the chip (bench.py's headline).  Results do not depend on it, bit for bit.
+        encoderPrecision (wh_session_options.encoder_precision): None / "f16" = Float16 GEMM operands in the encoder (the reference's
+        AudioEncoderOutput type; the default, unchanged); "split" = every rounded encoder GEMM operand and the encoder output as a Float16
+        pair hi | lo (hi = f16(x), lo = f16(x - hi)), multiplied hi then lo into the same fp32 accumulator.  It is the mode for "give me the
+        reference model's numbers": end to end from PCM the logits stay within 1e-3 sigma of fp32 openai/whisper on realistic weights
+        (measured per width in profiles/r07_split_encoder_errors.json; the Float16 default sits at 1e-2 - 2e-2 sigma).
+        It costs about twice the encoder's matrix work (encoder ms per chunk: profiles/r07_split_encoder_time.json), a second Float16 plane
+        of every rounded activation, and the 24-bit K / V rows (369 MB per slot at large-v3): crossAttentionMode None resolves to 0 and
+        crossAttentionMode=1 raises WhisperError (the absorbed kernel streams the Float16 encoder output)."""
         self.model, self.lib, self.B = model, model.lib, maxBatch
         self.handle = C.c_void_p()
-        if crossAttentionSlotsPerWorkgroup is not None:
+        if encoderPrecision not in self.ENCODER_PRECISIONS:
+            raise ValueError(f"encoderPrecision {encoderPrecision!r}: expected None, 'f16' or 'split'")
+        if crossAttentionSlotsPerWorkgroup is not None or encoderPrecision is not None:
             o = L.WhSessionOptions()
             self.lib.wh_session_options_default(C.byref(o))
             o.cross_attention_mode = -1 if crossAttentionMode is None else int(crossAttentionMode)
             o.cross_attention_splits = 0 if crossAttentionSplits is None else int(crossAttentionSplits)
-            o.cross_attention_slots_per_workgroup = int(crossAttentionSlotsPerWorkgroup)
+            o.cross_attention_slots_per_workgroup = int(crossAttentionSlotsPerWorkgroup or 0)
+            o.encoder_precision = self.ENCODER_PRECISIONS[encoderPrecision]
             _check(self.lib.wh_session_create_with_options(model.handle, maxBatch, C.byref(o), C.byref(self.handle)))
         elif crossAttentionMode is None and crossAttentionSplits is None:
             _check(self.lib.wh_session_create(model.handle, maxBatch, C.byref(self.handle)))
@@ -490,6 +503,11 @@ class Session:
     @property
     def crossAttentionSlotsPerWorkgroup(self) -> int:
         return int(self.lib.wh_session_cross_attention_slots_per_workgroup(self.handle))
+
+    @property
+    def encoderPrecision(self) -> str:
+        """"f16" (Float16 encoder operands, the default) or "split" (hi | lo pairs; see __init__)"""
+        return {0: "f16", 1: "split"}[int(self.lib.wh_session_encoder_precision(self.handle))]
 
     @property
     def crossAttentionMode(self) -> int:

@@ -22,9 +22,10 @@ constexpr int AT_LD = 72;  // LDS row stride in halves (64 + 8 pad = 144 B)
 // __launch_bounds__(256, 2): two workgroups per CU = at least two waves per SIMD caps the wave at 256 unified registers, which makes
 // the compiler keep the MFMA accumulators in arch VGPRs.  With one wave per SIMD allowed it placed them in AccVGPRs and moved the
 // 64 score / output registers through 200 v_accvgpr_read / write per key tile - on a kernel that is VALU-bound (softmax) already.
+template <bool LO = false>   // LO (split encoder sessions): the output's lo plane f16(o - f16(o)) to out_lo as well
 __global__ __launch_bounds__(256, 2) void encoder_attention_kernel(const f16* __restrict__ q16, const f16* __restrict__ k16,
                                                                 const f16* __restrict__ vt16, f16* __restrict__ out16,
-                                                                int n_head, int d) {
+                                                                int n_head, int d, f16* __restrict__ out_lo) {
     __shared__ __attribute__((aligned(16))) f16 Ks[64 * AT_LD];
     __shared__ __attribute__((aligned(16))) f16 Vs[64 * AT_LD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -130,6 +131,11 @@ __global__ __launch_bounds__(256, 2) void encoder_attention_kernel(const f16* __
             for (int g = 0; g < 4; ++g) {
                 f16x4 pk = {(f16)(o[ct][4 * g] * inv), (f16)(o[ct][4 * g + 1] * inv), (f16)(o[ct][4 * g + 2] * inv), (f16)(o[ct][4 * g + 3] * inv)};
                 *reinterpret_cast<f16x4*>(op + 32 * ct + 8 * g + 4 * half) = pk;
+                if constexpr (LO) {
+                    const f16x4 lo = {(f16)(o[ct][4 * g] * inv - (float)pk[0]), (f16)(o[ct][4 * g + 1] * inv - (float)pk[1]),
+                                      (f16)(o[ct][4 * g + 2] * inv - (float)pk[2]), (f16)(o[ct][4 * g + 3] * inv - (float)pk[3])};
+                    *reinterpret_cast<f16x4*>(out_lo + (op - out16) + 32 * ct + 8 * g + 4 * half) = lo;
+                }
             }
     }
 }
@@ -151,9 +157,10 @@ constexpr int AT_LDK = 72;   // K row stride in halves (144 B)
 constexpr int AT_LDV = 68;   // V^T row stride in halves (136 B)
 constexpr float kLog2e = 1.4426950408889634f;
 
+template <bool LO = false>
 __global__ __launch_bounds__(256, 2) void encoder_attention_v2_kernel(const f16* __restrict__ q16, const f16* __restrict__ k16,
                                                                    const f16* __restrict__ vt16, f16* __restrict__ out16,
-                                                                   int n_head, int d, int n_pairs) {
+                                                                   int n_head, int d, int n_pairs, f16* __restrict__ out_lo) {
     __shared__ __attribute__((aligned(16))) f16 Ks[2][64 * AT_LDK];
     __shared__ __attribute__((aligned(16))) f16 Vs[2][64 * AT_LDV];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -289,20 +296,28 @@ __global__ __launch_bounds__(256, 2) void encoder_attention_v2_kernel(const f16*
             for (int g = 0; g < 4; ++g) {
                 f16x4 pk = {(f16)(o[ct][4 * g] * inv), (f16)(o[ct][4 * g + 1] * inv), (f16)(o[ct][4 * g + 2] * inv), (f16)(o[ct][4 * g + 3] * inv)};
                 *reinterpret_cast<f16x4*>(op + 32 * ct + 8 * g + 4 * half) = pk;
+                if constexpr (LO) {
+                    const f16x4 lo = {(f16)(o[ct][4 * g] * inv - (float)pk[0]), (f16)(o[ct][4 * g + 1] * inv - (float)pk[1]),
+                                      (f16)(o[ct][4 * g + 2] * inv - (float)pk[2]), (f16)(o[ct][4 * g + 3] * inv - (float)pk[3])};
+                    *reinterpret_cast<f16x4*>(out_lo + (op - out16) + 32 * ct + 8 * g + 4 * half) = lo;
+                }
             }
     }
 }
 
-void launch_encoder_attention(const f16* q16, const f16* k16, const f16* vt16, f16* out16, int batch, int n_head, int d, hipStream_t st) {
+void launch_encoder_attention(const f16* q16, const f16* k16, const f16* vt16, f16* out16, int batch, int n_head, int d, hipStream_t st, f16* out_lo) {
     ProfScope ps_(KK_ENC_ATTN, st);
     static const bool v1 = [] { const char* e = getenv("WH_ENC_ATTN_V1"); return e && e[0] == '1'; }();     // A/B knob: the round-2 kernel
     if (v1) {
         dim3 g((kCtx + 127) / 128, n_head, batch);
-        encoder_attention_kernel<<<g, 256, 0, st>>>(q16, k16, vt16, out16, n_head, d);
+        if (out_lo) encoder_attention_kernel<true><<<g, 256, 0, st>>>(q16, k16, vt16, out16, n_head, d, out_lo);
+        else encoder_attention_kernel<false><<<g, 256, 0, st>>>(q16, k16, vt16, out16, n_head, d, nullptr);
         return;
     }
     const int n_pairs = n_head * batch, nqt = (kCtx + 127) / 128;
-    encoder_attention_v2_kernel<<<(unsigned)(((n_pairs + 7) / 8) * 8 * nqt), 256, 0, st>>>(q16, k16, vt16, out16, n_head, d, n_pairs);
+    const unsigned grid = (unsigned)(((n_pairs + 7) / 8) * 8 * nqt);
+    if (out_lo) encoder_attention_v2_kernel<true><<<grid, 256, 0, st>>>(q16, k16, vt16, out16, n_head, d, n_pairs, out_lo);
+    else encoder_attention_v2_kernel<false><<<grid, 256, 0, st>>>(q16, k16, vt16, out16, n_head, d, n_pairs, nullptr);
 }
 
 }  // namespace wh

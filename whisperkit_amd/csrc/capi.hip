@@ -412,7 +412,8 @@ static int dalloc(T** p, size_t n, bool zero = true) {
 }
 #define DALLOC(ptr, n) do { int _r = dalloc(&(ptr), (size_t)(n)); if (_r) { wh_session_destroy(s); return _r; } } while (0)
 
-static int session_create_impl(wh_model* m, int max_batch, int cross_attention_mode, int cross_attention_splits, int slots_per_workgroup, wh_session** out);
+static int session_create_impl(wh_model* m, int max_batch, int cross_attention_mode, int cross_attention_splits, int slots_per_workgroup, wh_session** out,
+                               int encoder_precision = 0);
 extern "C" int wh_session_create(wh_model* m, int max_batch, wh_session** out) { return session_create_impl(m, max_batch, -1, 0, 0, out); }
 extern "C" int wh_session_create_tuned(wh_model* m, int max_batch, int cross_attention_mode, int cross_attention_splits, wh_session** out) {
     wh_session_options o{};
@@ -435,9 +436,16 @@ extern "C" int wh_session_create_with_options(wh_model* m, int max_batch, const 
         return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_create: cross_attention_mode %d (expected -1 auto, 0 K / V rows, 1 absorbed)", cross_attention_mode);
     if (cross_attention_splits < 0 || cross_attention_splits > kXabsSplits)
         return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_create: cross_attention_splits %d (expected 0 auto, 1 .. %d)", cross_attention_splits, kXabsSplits);
+    if (opt->encoder_precision < 0 || opt->encoder_precision > 1)
+        return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_create: encoder_precision %d (expected 0 Float16 operands, 1 split hi | lo)", opt->encoder_precision);
+    if (opt->encoder_precision == 1 && cross_attention_mode == 1)
+        return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_create: encoder_precision 1 (split) needs the K / V-row cross-attention (cross_attention_mode -1 or 0): "
+                         "the absorbed kernel streams the Float16 encoder output, and a hi | lo stream would double its bytes");
     if (cross_attention_mode == 1 && m && !xabs_supported(m->dims.n_text_state, m->dims.n_text_head))
         return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_create: the absorbed cross-attention needs a model width of 512 / 768 / 1024 / 1280 (this model: %d)", m->dims.n_text_state);
-    return session_create_impl(m, max_batch, cross_attention_mode, cross_attention_splits, opt->cross_attention_slots_per_workgroup, out);
+    // a split session resolves the automatic cross-attention choice to the K / V rows (their projection reads the split encoder output)
+    return session_create_impl(m, max_batch, opt->encoder_precision == 1 ? 0 : cross_attention_mode, cross_attention_splits,
+                               opt->cross_attention_slots_per_workgroup, out, opt->encoder_precision);
 }
 extern "C" int wh_session_create_with_mode(wh_model* m, int max_batch, int cross_attention_mode, wh_session** out) {
     return wh_session_create_tuned(m, max_batch, cross_attention_mode, 0, out);
@@ -467,7 +475,8 @@ static hipError_t create_session_stream(hipStream_t* st) {
     for (int i = k * w; i < k * w + w + extra; ++i) { const int c = ((i % n_cu) + n_cu) % n_cu; mask[c >> 5] |= 1u << (c & 31); }
     return hipExtStreamCreateWithCUMask(st, (uint32_t)((n_cu + 31) / 32), mask);
 }
-static int session_create_impl(wh_model* m, int max_batch, int cross_attention_mode, int cross_attention_splits, int slots_per_workgroup, wh_session** out) {
+static int session_create_impl(wh_model* m, int max_batch, int cross_attention_mode, int cross_attention_splits, int slots_per_workgroup, wh_session** out,
+                               int encoder_precision) {
     if (!m || !out) return set_error(WH_ERR_MODELS_UNAVAILABLE, "wh_session_create: model is null");
     if (max_batch < 1 || max_batch > kMaxSessionSlots) return set_error(WH_ERR_INVALID_ARGUMENT, "max_batch %d out of range [1, %d]", max_batch, kMaxSessionSlots);
     WH_HIP(hipSetDevice(m->device));
@@ -484,6 +493,11 @@ static int session_create_impl(wh_model* m, int max_batch, int cross_attention_m
     DALLOC(s->h1, B * kFramesPad * d); DALLOC(s->x, B * kCtx * d); DALLOC(s->xn, B * kCtx * d);
     DALLOC(s->q16, B * kCtx * d); DALLOC(s->k16, B * kCtx * d); DALLOC(s->vt16, B * d * kCtxPad); DALLOC(s->att16, B * kCtx * d);
     DALLOC(s->hmlp, B * kCtx * 4 * d); DALLOC(s->enc16, B * kCtx * d); DALLOC(s->enc32, B * kCtx * d);
+    s->encoder_precision = encoder_precision;
+    if (encoder_precision == 1) {       // lo planes (zero-filled: the padding rows of the time-major conv inputs stay 0 like their hi planes)
+        DALLOC(s->mel_t_lo, B * kFramesPad * D.n_mels); DALLOC(s->h1_lo, B * kFramesPad * d); DALLOC(s->xn_lo, B * kCtx * d);
+        DALLOC(s->att_lo, B * kCtx * d); DALLOC(s->hmlp_lo, B * kCtx * 4 * d); DALLOC(s->enc_lo, B * kCtx * d);
+    }
     // Cross-attention path, fixed per session: the absorbed form (xabs.hip) streams the encoder output instead of per-layer K / V rows;
     // it pays from about kXabsAutoMinSlots slots (three launches per layer instead of one, one workgroup per (slot, key split) and CU;
     // profiles/r04*, r05*).  Both modes meet the 1e-3 relative logits contract against fp32 (the K / V rows carry 19 mantissa bits since round 5: kernels.h hr24).
@@ -557,7 +571,7 @@ extern "C" void wh_session_destroy(wh_session* s) {
     void* ptrs[] = {s->pcm, s->n_valid, s->logspec, s->maxkey, s->mel_t, s->mel_f32, s->h1, s->x, s->xn, s->q16, s->k16, s->vt16, s->att16,
                     s->hmlp, s->enc16, s->enc32, s->cross_k_hi, s->cross_v_hi, s->cross_k_lo, s->cross_v_lo, s->self_k, s->self_v, s->part, s->ticket, s->logits,
                     s->align, s->align_mean, s->seq, s->cfg_dev, s->suppress_dev, s->sup_mask_dev, s->stats, s->tok_out_dev, s->lp_out_dev, s->scratch_logits,
-                    s->beam_owner, s->beam_tok, s->beam_lp};
+                    s->beam_owner, s->beam_tok, s->beam_lp, s->mel_t_lo, s->h1_lo, s->xn_lo, s->att_lo, s->hmlp_lo, s->enc_lo};
     for (void* p : ptrs) if (p) hipFree(p);
     if (s->seq_host) hipHostFree(s->seq_host);
     for (auto& e : s->ev) if (e) hipEventDestroy(e);
@@ -566,6 +580,7 @@ extern "C" void wh_session_destroy(wh_session* s) {
 }
 extern "C" int wh_session_max_batch(const wh_session* s) { return s ? s->B : -1; }
 extern "C" int wh_session_cross_attention_mode(const wh_session* s) { return s ? (s->use_xabs ? 1 : 0) : -1; }
+extern "C" int wh_session_encoder_precision(const wh_session* s) { return s ? s->encoder_precision : -1; }
 extern "C" int wh_session_step_graph_count(const wh_session* s) { return s ? (int)s->graphs.size() : -1; }
 extern "C" int wh_session_cross_attention_splits(const wh_session* s) { return s ? (s->use_xabs ? s->xabs.n_split : 0) : -1; }
 extern "C" int wh_session_cross_attention_slots_per_workgroup(const wh_session* s) { return s ? (s->use_xabs ? s->xabs.spw : 0) : -1; }
@@ -594,6 +609,7 @@ extern "C" int wh_debug_peek(wh_session* s, const char* name, void* out, size_t 
     else if (s->use_xabs && n == "part") { src = s->xabs.part; have = (size_t)kXabsSplits * H * d * B * 4; }
     else if (s->use_xabs && n == "ml") { src = s->xabs.ml; have = (size_t)kXabsSplits * H * B * 8; }
     else if (n == "enc16") { src = s->enc16; have = B * kCtx * d * 2; }
+    else if (s->enc_lo && n == "enc_lo") { src = s->enc_lo; have = B * kCtx * (size_t)s->m->dims.n_audio_state * 2; }
     if (!src) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_peek: no buffer named '%s' in this session", name);
     if (nbytes > have) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_peek: '%s' holds %zu bytes, %zu requested", name, have, nbytes);
     WH_HIP(hipStreamSynchronize(s->st));
@@ -625,7 +641,7 @@ extern "C" int wh_set_audio_device(wh_session* s, int b, const float* pcm_dev, i
 
 extern "C" int wh_log_mel_spectrogram(wh_session* s, int batch) {
     CHECK_SESSION(s); CHECK_BATCH(s, batch);
-    launch_log_mel(s->m->mel, s->pcm, s->n_valid, batch, s->logspec, s->maxkey, s->mel_t, s->mel_f32, s->st);
+    launch_log_mel(s->m->mel, s->pcm, s->n_valid, batch, s->logspec, s->maxkey, s->mel_t, s->mel_f32, s->st, s->mel_t_lo);
     WH_CHECK_LAUNCH();
     return WH_OK;
 }
@@ -643,19 +659,67 @@ extern "C" int wh_set_mel(wh_session* s, int b, const float* mel) {
     const int nm = s->m->dims.n_mels;
     size_t n = (size_t)nm * kFrames;
     WH_HIP(hipMemcpyAsync(s->mel_f32 + b * n, mel, n * 4, hipMemcpyHostToDevice, s->st));
-    launch_mel_import(s->mel_f32 + b * n, nm, 1, s->mel_t + (size_t)b * kFramesPad * nm, s->st);
+    launch_mel_import(s->mel_f32 + b * n, nm, 1, s->mel_t + (size_t)b * kFramesPad * nm, s->st,
+                      s->mel_t_lo ? s->mel_t_lo + (size_t)b * kFramesPad * nm : nullptr);
     WH_CHECK_LAUNCH();
     WH_HIP(hipStreamSynchronize(s->st));
     return WH_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ encoder
+// encoder_precision 1: the launch sequence of wh_encode_features with every Float16 GEMM operand a hi | lo pair (GemmArgs::A_lo) - the mel
+// (written by the mel kernels), GELU(conv1), both LayerNorm outputs, the attention output, GELU(fc1) - and the output's lo plane beside
+// enc16 / enc32 (the cross K / V projection's operand).  q / k / v / P of the attention stay Float16.
+static int encode_features_split(wh_session* s, int batch) {
+    const wh_model* m = s->m;
+    const wh_dims& D = m->dims;
+    const int d = D.n_audio_state, nm = D.n_mels, M = batch * kCtx;
+    hipStream_t st = s->st;
+    GemmArgs g{};
+    g.A = s->mel_t; g.A_lo = s->mel_t_lo; g.W = m->conv1_w; g.bias = m->conv1_b; g.M = batch * kFrames; g.N = d; g.K = 3 * nm; g.lda = nm;
+    g.a_rows_per_batch = kFrames; g.a_batch_stride = (long long)kFramesPad * nm; g.ldc = d; g.out16 = s->h1; g.out16_lo = s->h1_lo; g.rows_per_batch_out = kFrames;
+    g.prof_kind = KK_CONV1;
+    launch_gemm(EPI_CONV1, g, st);
+    g = GemmArgs{};
+    g.A = s->h1; g.A_lo = s->h1_lo; g.W = m->conv2_w; g.bias = m->conv2_b; g.M = M; g.N = d; g.K = 3 * d; g.lda = 2 * d;
+    g.a_rows_per_batch = kCtx; g.a_batch_stride = (long long)kFramesPad * d; g.ldc = d; g.out32 = s->x; g.pos = m->enc_pos; g.rows_per_batch_out = kCtx;
+    g.prof_kind = KK_CONV2;
+    launch_gemm(EPI_CONV2, g, st);
+    for (int l = 0; l < D.n_audio_layer; ++l) {
+        const EncLayerW& w = m->enc[l];
+        launch_layernorm(s->x, w.ln1_g, w.ln1_b, M, d, s->xn, nullptr, st, s->xn_lo);
+        g = GemmArgs{};
+        g.A = s->xn; g.A_lo = s->xn_lo; g.W = w.qkv_w; g.bias = w.qkv_b; g.M = M; g.N = 3 * d; g.K = d; g.lda = d; g.a_rows_per_batch = M; g.ldc = d;
+        g.out16 = s->q16; g.k16 = s->k16; g.vt16 = s->vt16; g.d_model = d; g.rows_per_batch_out = kCtx;
+        g.prof_kind = KK_ENC_QKV;
+        launch_gemm(EPI_QKV_ENC, g, st);
+        launch_encoder_attention(s->q16, s->k16, s->vt16, s->att16, batch, D.n_audio_head, d, st, s->att_lo);
+        g = GemmArgs{};
+        g.A = s->att16; g.A_lo = s->att_lo; g.W = w.o_w; g.bias = w.o_b; g.M = M; g.N = d; g.K = d; g.lda = d; g.a_rows_per_batch = M; g.ldc = d; g.out32 = s->x;
+        g.prof_kind = KK_ENC_O;
+        launch_gemm(EPI_RESID_F32, g, st);
+        launch_layernorm(s->x, w.ln2_g, w.ln2_b, M, d, s->xn, nullptr, st, s->xn_lo);
+        g = GemmArgs{};
+        g.A = s->xn; g.A_lo = s->xn_lo; g.W = w.fc1_w; g.bias = w.fc1_b; g.M = M; g.N = 4 * d; g.K = d; g.lda = d; g.a_rows_per_batch = M; g.ldc = 4 * d;
+        g.out16 = s->hmlp; g.out16_lo = s->hmlp_lo;
+        g.prof_kind = KK_ENC_FC1;
+        launch_gemm(EPI_GELU_F16, g, st);
+        g = GemmArgs{};
+        g.A = s->hmlp; g.A_lo = s->hmlp_lo; g.W = w.fc2_w; g.bias = w.fc2_b; g.M = M; g.N = d; g.K = 4 * d; g.lda = 4 * d; g.a_rows_per_batch = M; g.ldc = d; g.out32 = s->x;
+        g.prof_kind = KK_ENC_FC2;
+        launch_gemm(EPI_RESID_F32, g, st);
+    }
+    launch_layernorm(s->x, m->lnp_g, m->lnp_b, M, d, s->enc16, s->enc32, st, s->enc_lo);
+    WH_CHECK_LAUNCH();
+    return WH_OK;
+}
 extern "C" int wh_encode_features(wh_session* s, int batch) {
     CHECK_SESSION(s); CHECK_BATCH(s, batch);
     const wh_model* m = s->m;
     const wh_dims& D = m->dims;
     const int d = D.n_audio_state, nm = D.n_mels, M = batch * kCtx;
     hipStream_t st = s->st;
+    if (s->encoder_precision == 1) return encode_features_split(s, batch);
     GemmArgs g{};
     // conv1 (k3 s1 p1) + GELU as a GEMM over 3 consecutive rows of the padded time-major mel
     g.A = s->mel_t; g.W = m->conv1_w; g.bias = m->conv1_b; g.M = batch * kFrames; g.N = d; g.K = 3 * nm; g.lda = nm;
@@ -708,7 +772,8 @@ extern "C" int wh_set_encoder_output(wh_session* s, int b, const float* enc) {
     if (!enc) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_set_encoder_output: null input");
     size_t n = (size_t)kCtx * s->m->dims.n_audio_state;
     WH_HIP(hipMemcpyAsync(s->enc32 + b * n, enc, n * 4, hipMemcpyHostToDevice, s->st));
-    launch_f32_to_f16(s->enc32 + b * n, s->enc16 + b * n, n, s->st);
+    if (s->enc_lo) launch_f32_to_f16_split(s->enc32 + b * n, s->enc16 + b * n, s->enc_lo + b * n, n, s->st);
+    else launch_f32_to_f16(s->enc32 + b * n, s->enc16 + b * n, n, s->st);
     WH_CHECK_LAUNCH();
     WH_HIP(hipStreamSynchronize(s->st));
     return WH_OK;
@@ -783,8 +848,8 @@ extern "C" int wh_prepare_decoder_inputs(wh_session* s, int batch) {
     const wh_model* m = s->m;
     const int d = m->dims.n_text_state, L = m->dims.n_text_layer;
     if (!s->use_xabs) {     // (the absorbed cross-attention reads the encoder output itself: no per-layer K / V projection)
-        GemmArgs g{};
-        g.A = s->enc16; g.W = m->ckv_w; g.bias = m->ckv_b; g.M = batch * kCtx; g.N = L * 2 * d; g.K = d; g.lda = d; g.a_rows_per_batch = g.M;
+        GemmArgs g{};      // (enc_lo: the split encoder output's lo plane, null in the default mode)
+        g.A = s->enc16; g.A_lo = s->enc_lo; g.W = m->ckv_w; g.bias = m->ckv_b; g.M = batch * kCtx; g.N = L * 2 * d; g.K = d; g.lda = d; g.a_rows_per_batch = g.M;
         g.ldc = L * 2 * d; g.kv_k_hi = s->cross_k_hi; g.kv_v_hi = s->cross_v_hi; g.kv_k_lo = s->cross_k_lo; g.kv_v_lo = s->cross_v_lo; g.d_model = d; g.max_batch = s->B;
         g.prof_kind = KK_CROSS_KV;
         launch_gemm(EPI_CROSS_KV, g, s->st);

@@ -45,5 +45,16 @@ WH_EPI_FN int vt_read_off(int lane, int it) { return vt_read_col(lane, it) * kRo
 
 static_assert(64 * kRow16 <= kWaveRegion && 32 * kRow32 <= kWaveRegion && 32 * kRowT <= kWaveRegion, "a pass fits the wave's slice");
 
+// ---- operand stages of the split-A form of gemm256_kernel (encoder_precision 1; csrc/gemm.hip), replayed by tests/native/split_stage_check.cpp.
+// BK = 32: an LDS row is the 64-byte K-slice of an operand row (4 chunks of 16 bytes); a stage is [A hi | A lo | W], 256 rows x 64 bytes each.
+// One LDS-DMA piece (512 threads x 16 bytes, lane-linear image) fills 128 rows: thread tid writes slot tid & 3 of row tid >> 2 and fetches
+// the chunk that belongs there; fragment reads find chunk c of row r in slot c ^ split_swz(r).
+constexpr int kSplitStage = 3 * 16384;
+WH_EPI_FN int split_swz(int row) { return (row >> 2) & 3; }
+WH_EPI_FN int split_dma_row(int tid) { return tid >> 2; }                                    // 0 .. 127 within the piece
+WH_EPI_FN int split_dma_chunk(int tid) { return (tid & 3) ^ split_swz(split_dma_row(tid)); } // source chunk of the slot tid & 3
+WH_EPI_FN int split_read_off(int row, int chunk) { return row * 64 + ((chunk ^ split_swz(row)) * 16); }   // byte offset in a 256-row panel
+static_assert(2 * kSplitStage <= 8 * kWaveRegion, "the split stages fit the launch's 128 KB (the staged epilogues' slices)");
+
 }  // namespace epi
 }  // namespace wh

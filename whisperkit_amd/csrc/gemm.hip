@@ -26,7 +26,8 @@ constexpr int LDT = 40;  // LDS row stride in halves (32 + 8 pad)
 
 // Fused epilogue of one wave's TM x TN accumulator tiles.  C layout of v_mfma_f32_32x32x16: col n = lane & 31,
 // row m = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5).  m_wave / n_wave = first row / column of the wave's sub-tile.
-template <int EPI, int TM, int TN>
+// SPLIT (split A operand, encoder_precision 1): EPI_GELU_F16 / EPI_CONV1 also write the lo plane f16(y - f16(y)) of their output to out16_lo.
+template <int EPI, int TM, int TN, bool SPLIT = false>
 __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x16 (&acc)[TM][TN], int m_wave, int n_wave, int lane) {
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
@@ -68,7 +69,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x16 (&acc)[T
                     if constexpr (EPI == EPI_F16) {
                         a.out16[(size_t)m * a.ldc + n] = (f16)x;
                     } else if constexpr (EPI == EPI_GELU_F16) {
-                        a.out16[(size_t)m * a.ldc + n] = (f16)gelu_erf_fast(x);
+                        if constexpr (SPLIT) { f16 h_, l_; split_f16(gelu_erf_fast(x), h_, l_); a.out16[(size_t)m * a.ldc + n] = h_; a.out16_lo[(size_t)m * a.ldc + n] = l_; }
+                        else a.out16[(size_t)m * a.ldc + n] = (f16)gelu_erf_fast(x);
                     } else if constexpr (EPI == EPI_RESID_F32) {
                         a.out32[(size_t)m * a.ldc + n] += x;
                     } else if constexpr (EPI == EPI_F32) {
@@ -88,7 +90,12 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& a, f32x16 (&acc)[T
                         (kv ? a.kv_v_lo : a.kv_k_lo)[o] = lo_;
                     } else if constexpr (EPI == EPI_CONV1) {
                         int bb = m / a.rows_per_batch_out, t = m - bb * a.rows_per_batch_out;
-                        a.out16[((size_t)bb * kFramesPad + t + 1) * a.ldc + n] = (f16)gelu_erf_fast(x);
+                        if constexpr (SPLIT) {
+                            const size_t o = ((size_t)bb * kFramesPad + t + 1) * a.ldc + n;
+                            f16 h_, l_; split_f16(gelu_erf_fast(x), h_, l_); a.out16[o] = h_; a.out16_lo[o] = l_;
+                        } else {
+                            a.out16[((size_t)bb * kFramesPad + t + 1) * a.ldc + n] = (f16)gelu_erf_fast(x);
+                        }
                     } else if constexpr (EPI == EPI_CONV2) {
                         int t = m % a.rows_per_batch_out;
                         a.out32[(size_t)m * a.ldc + n] = gelu_erf_fast(x) + a.pos[(size_t)t * a.ldc + n];
@@ -115,10 +122,19 @@ __device__ __forceinline__ void load_tile_bias(const GemmArgs& a, float4 (&bias)
     }
 }
 
+// f16x4 hi | lo planes of 4 values (split encoder epilogues)
+__device__ __forceinline__ void split_f16x4(float v0, float v1, float v2, float v3, f16x4& hi, f16x4& lo) {
+    f16 h_, l_;
+    split_f16(v0, h_, l_); hi[0] = h_; lo[0] = l_;
+    split_f16(v1, h_, l_); hi[1] = h_; lo[1] = l_;
+    split_f16(v2, h_, l_); hi[2] = h_; lo[2] = l_;
+    split_f16(v3, h_, l_); hi[3] = h_; lo[3] = l_;
+}
+
 // Epilogue for accumulators produced with the operands swapped (mfma(W fragment, A fragment)): the 32 x 32 tile is C^T,
 // so a lane owns ONE output row m = lane & 31 and, per register group, 4 CONSECUTIVE columns n - row-major outputs go
 // out as 8-byte (f16x4) / 16-byte (float4) accesses instead of 2- and 4-byte ones.
-template <int EPI, int TM, int TN, bool BATCH_BIAS = false>
+template <int EPI, int TM, int TN, bool BATCH_BIAS = false, bool SPLIT = false>
 __device__ __forceinline__ void gemm_epilogue_swapped(const GemmArgs& a, f32x16 (&acc)[TM][TN], int m_wave, int n_wave, int lane) {
     float4 tile_bias[2][4];
     if constexpr (BATCH_BIAS) {       // gemm256_kernel, N % 64 == 0: the wave's 64 columns are inside or outside as a whole
@@ -147,8 +163,15 @@ __device__ __forceinline__ void gemm_epilogue_swapped(const GemmArgs& a, f32x16 
                 if constexpr (EPI == EPI_F16) {
                     *reinterpret_cast<f16x4*>(a.out16 + (size_t)m * a.ldc + n) = f16x4{(f16)v0, (f16)v1, (f16)v2, (f16)v3};
                 } else if constexpr (EPI == EPI_GELU_F16) {
-                    *reinterpret_cast<f16x4*>(a.out16 + (size_t)m * a.ldc + n) =
-                        f16x4{(f16)gelu_erf_fast(v0), (f16)gelu_erf_fast(v1), (f16)gelu_erf_fast(v2), (f16)gelu_erf_fast(v3)};
+                    if constexpr (SPLIT) {
+                        f16x4 hi, lo;
+                        split_f16x4(gelu_erf_fast(v0), gelu_erf_fast(v1), gelu_erf_fast(v2), gelu_erf_fast(v3), hi, lo);
+                        *reinterpret_cast<f16x4*>(a.out16 + (size_t)m * a.ldc + n) = hi;
+                        *reinterpret_cast<f16x4*>(a.out16_lo + (size_t)m * a.ldc + n) = lo;
+                    } else {
+                        *reinterpret_cast<f16x4*>(a.out16 + (size_t)m * a.ldc + n) =
+                            f16x4{(f16)gelu_erf_fast(v0), (f16)gelu_erf_fast(v1), (f16)gelu_erf_fast(v2), (f16)gelu_erf_fast(v3)};
+                    }
                 } else if constexpr (EPI == EPI_RESID_F32) {
                     float4* p = reinterpret_cast<float4*>(a.out32 + (size_t)m * a.ldc + n);
                     float4 o = *p;
@@ -170,8 +193,16 @@ __device__ __forceinline__ void gemm_epilogue_swapped(const GemmArgs& a, f32x16 
                     *reinterpret_cast<f16x4*>((kv ? a.kv_v_hi : a.kv_k_hi) + o) = hi4;
                     *reinterpret_cast<char4*>((kv ? a.kv_v_lo : a.kv_k_lo) + o) = lo4;
                 } else if constexpr (EPI == EPI_CONV1) {
-                    *reinterpret_cast<f16x4*>(a.out16 + ((size_t)bb * kFramesPad + t + 1) * a.ldc + n) =
-                        f16x4{(f16)gelu_erf_fast(v0), (f16)gelu_erf_fast(v1), (f16)gelu_erf_fast(v2), (f16)gelu_erf_fast(v3)};
+                    if constexpr (SPLIT) {
+                        const size_t o = ((size_t)bb * kFramesPad + t + 1) * a.ldc + n;
+                        f16x4 hi, lo;
+                        split_f16x4(gelu_erf_fast(v0), gelu_erf_fast(v1), gelu_erf_fast(v2), gelu_erf_fast(v3), hi, lo);
+                        *reinterpret_cast<f16x4*>(a.out16 + o) = hi;
+                        *reinterpret_cast<f16x4*>(a.out16_lo + o) = lo;
+                    } else {
+                        *reinterpret_cast<f16x4*>(a.out16 + ((size_t)bb * kFramesPad + t + 1) * a.ldc + n) =
+                            f16x4{(f16)gelu_erf_fast(v0), (f16)gelu_erf_fast(v1), (f16)gelu_erf_fast(v2), (f16)gelu_erf_fast(v3)};
+                    }
                 } else if constexpr (EPI == EPI_CONV2) {
                     const float4 ps = *reinterpret_cast<const float4*>(a.pos + (size_t)t * a.ldc + n);
                     *reinterpret_cast<float4*>(a.out32 + (size_t)m * a.ldc + n) =
@@ -182,11 +213,14 @@ __device__ __forceinline__ void gemm_epilogue_swapped(const GemmArgs& a, f32x16 
     }
 }
 
-template <int BM, int BN, int EPI>
-__global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmArgs a) {     // (256, 2): accumulators stay in arch VGPRs (no AccVGPR copies)
+// SPLIT: the A operand is a hi | lo pair (a.A / a.A_lo, same layout): a third LDS tile holds the lo rows, and every 16-wide k-step runs
+// mfma(W, A hi) and then mfma(W, A lo) into the same accumulator - gemm256_split_kernel does the same per accumulator, so the two
+// kernels keep giving the same bits.
+template <int BM, int BN, int EPI, bool SPLIT>
+__device__ __forceinline__ void gemm_main(const GemmArgs& a) {
     constexpr int WM = BM / 2, WN = BN / 2, TM = WM / 32, TN = WN / 32;
     constexpr int CA = BM * 4 / 256, CB = BN * 4 / 256;   // 16-byte chunks per thread per tile
-    __shared__ __attribute__((aligned(16))) f16 As[2][BM * LDT];
+    __shared__ __attribute__((aligned(16))) f16 As[SPLIT ? 4 : 2][BM * LDT];     // SPLIT: stages 2 / 3 hold the lo rows
     __shared__ __attribute__((aligned(16))) f16 Bs[2][BN * LDT];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -195,6 +229,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmArgs a) {     //
 
     // per-thread global row pointers (fixed across the K loop)
     const f16* a_ptr[CA];
+    const f16* a_lo_ptr[SPLIT ? CA : 1];
     bool a_ok[CA];
     int a_lds[CA];
 #pragma unroll
@@ -205,6 +240,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmArgs a) {     //
         int mm = a_ok[i] ? m : 0;
         long long off = (long long)(mm / a.a_rows_per_batch) * a.a_batch_stride + (long long)(mm % a.a_rows_per_batch) * a.lda;
         a_ptr[i] = a.A + off + cc * 8;
+        if constexpr (SPLIT) a_lo_ptr[i] = a.A_lo + off + cc * 8;
         a_lds[i] = row * LDT + cc * 8;
     }
     const f16* b_ptr[CB];
@@ -220,11 +256,15 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmArgs a) {     //
     }
     const int kc = (tid & 3) * 8;  // this thread's k offset inside a tile
 
-    uint4 ra[CA], rb[CB];
+    uint4 ra[CA], rb[CB], ral[SPLIT ? CA : 1];
     auto gload = [&](int k0) {
         bool kin = (k0 + kc) < a.K;
 #pragma unroll
         for (int i = 0; i < CA; ++i) ra[i] = (a_ok[i] && kin) ? *reinterpret_cast<const uint4*>(a_ptr[i] + k0) : uint4{0, 0, 0, 0};
+        if constexpr (SPLIT) {
+#pragma unroll
+            for (int i = 0; i < CA; ++i) ral[i] = (a_ok[i] && kin) ? *reinterpret_cast<const uint4*>(a_lo_ptr[i] + k0) : uint4{0, 0, 0, 0};
+        }
 #pragma unroll
         for (int i = 0; i < CB; ++i) rb[i] = (b_ok[i] && kin) ? *reinterpret_cast<const uint4*>(b_ptr[i] + k0) : uint4{0, 0, 0, 0};
     };
@@ -233,6 +273,10 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmArgs a) {     //
         for (int i = 0; i < CA; ++i) *reinterpret_cast<uint4*>(&As[buf][a_lds[i]]) = ra[i];
 #pragma unroll
         for (int i = 0; i < CB; ++i) *reinterpret_cast<uint4*>(&Bs[buf][b_lds[i]]) = rb[i];
+        if constexpr (SPLIT) {
+#pragma unroll
+            for (int i = 0; i < CA; ++i) *reinterpret_cast<uint4*>(&As[2 + buf][a_lds[i]]) = ral[i];
+        }
     };
 
     const int nk = (a.K + BK - 1) / BK;
@@ -262,19 +306,28 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmArgs a) {     //
                 for (int i = 0; i < TM; ++i) af[i] = *reinterpret_cast<const f16x8*>(&As[cur][(wm * WM + i * 32 + fr) * LDT + ks * 16 + fk]);
 #pragma unroll
                 for (int j = 0; j < TN; ++j) bf[j] = *reinterpret_cast<const f16x8*>(&Bs[cur][(wn * WN + j * 32 + fr) * LDT + ks * 16 + fk]);
+                f16x8 afl[SPLIT ? TM : 1];
+                if constexpr (SPLIT) {
+#pragma unroll
+                    for (int i = 0; i < TM; ++i) afl[i] = *reinterpret_cast<const f16x8*>(&As[2 + cur][(wm * WM + i * 32 + fr) * LDT + ks * 16 + fk]);
+                }
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
                     for (int j = 0; j < TN; ++j) {
                         if constexpr (SWAP) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bf[j], af[i], acc[i][j], 0, 0, 0);
                         else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[i], bf[j], acc[i][j], 0, 0, 0);
+                        if constexpr (SPLIT) {
+                            if constexpr (SWAP) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bf[j], afl[i], acc[i][j], 0, 0, 0);
+                            else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(afl[i], bf[j], acc[i][j], 0, 0, 0);
+                        }
                     }
             }
             if (kt + 1 < nk) lstore(cur ^ 1);
             __syncthreads();
         }
-        if constexpr (SWAP) gemm_epilogue_swapped<EPI, TM, TN>(a, acc, m0 + wm * WM, n0 + wn * WN, lane);
-        else gemm_epilogue<EPI, TM, TN>(a, acc, m0 + wm * WM, n0 + wn * WN, lane);
+        if constexpr (SWAP) gemm_epilogue_swapped<EPI, TM, TN, false, SPLIT>(a, acc, m0 + wm * WM, n0 + wn * WN, lane);
+        else gemm_epilogue<EPI, TM, TN, SPLIT>(a, acc, m0 + wm * WM, n0 + wn * WN, lane);
     };
     if constexpr (EPI == EPI_QKV_ENC) {
         if (n0 + wn * WN >= 2 * a.d_model) body(std::false_type{});
@@ -283,6 +336,11 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmArgs a) {     //
         body(std::true_type{});
     }
 }
+
+template <int BM, int BN, int EPI>
+__global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmArgs a) { gemm_main<BM, BN, EPI, false>(a); }    // (256, 2): accumulators stay in arch VGPRs (no AccVGPR copies)
+template <int BM, int BN, int EPI>
+__global__ __launch_bounds__(256, 2) void gemm_split_kernel(const GemmArgs a) { gemm_main<BM, BN, EPI, true>(a); }
 
 // ---------------------------------------------------------------------------------------------- LDS-staged epilogues of gemm256_kernel
 // (round 5; index maps and the reason in epi_stage.h, replayed on the CPU by tests/native/epi_stage_check.cpp).  A wave's 128 x 64 tile
@@ -296,7 +354,9 @@ __device__ __forceinline__ void wave_lds_turn() {      // LDS operations of ONE 
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-template <int EPI>
+// SPLIT (EPI_GELU_F16 of a split encoder): each pass is turned twice through the wave's slice, the hi plane to out16 and then the lo plane
+// f16(y - f16(y)) to out16_lo (y recomputed term for term: the same value).
+template <int EPI, bool SPLIT = false>
 __device__ __forceinline__ void epi_staged_f16(const GemmArgs& a, f32x16 (&acc)[4][2], unsigned char* wl, int mw, int nw, int lane) {
     if (nw >= a.N) return;
     f16* base = a.out16;
@@ -307,29 +367,38 @@ __device__ __forceinline__ void epi_staged_f16(const GemmArgs& a, f32x16 (&acc)[
     }
     float4 bias[2][4];
     load_tile_bias(a, bias, nw, lane);
+    static_assert(!SPLIT || EPI == EPI_GELU_F16, "split output planes: GELU(fc1) only");
 #pragma unroll
     for (int hh = 0; hh < 2; ++hh) {
 #pragma unroll
-        for (int i2 = 0; i2 < 2; ++i2)
+        for (int plane = 0; plane < (SPLIT ? 2 : 1); ++plane) {
 #pragma unroll
-            for (int j = 0; j < 2; ++j)
+            for (int i2 = 0; i2 < 2; ++i2)
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const f32x16& c = acc[2 * hh + i2][j];
-                    const float v0 = c[4 * g] + bias[j][g].x, v1 = c[4 * g + 1] + bias[j][g].y, v2 = c[4 * g + 2] + bias[j][g].z, v3 = c[4 * g + 3] + bias[j][g].w;
-                    f16x4 pk;
-                    if constexpr (EPI == EPI_GELU_F16) pk = f16x4{(f16)gelu_erf_fast(v0), (f16)gelu_erf_fast(v1), (f16)gelu_erf_fast(v2), (f16)gelu_erf_fast(v3)};
-                    else pk = f16x4{(f16)v0, (f16)v1, (f16)v2, (f16)v3};
-                    *reinterpret_cast<f16x4*>(wl + epi::f16_write_off(lane, i2, j, g)) = pk;
-                }
-        wave_lds_turn();
+                for (int j = 0; j < 2; ++j)
 #pragma unroll
-        for (int it = 0; it < 8; ++it) {
-            const int m = mw + hh * 64 + epi::f16_read_row(lane, it);
-            const uint4 v = *reinterpret_cast<const uint4*>(wl + epi::f16_read_off(lane, it));
-            if (m < a.M) *reinterpret_cast<uint4*>(base + (size_t)m * ld + nc + epi::f16_read_col(lane)) = v;
+                    for (int g = 0; g < 4; ++g) {
+                        const f32x16& c = acc[2 * hh + i2][j];
+                        const float v0 = c[4 * g] + bias[j][g].x, v1 = c[4 * g + 1] + bias[j][g].y, v2 = c[4 * g + 2] + bias[j][g].z, v3 = c[4 * g + 3] + bias[j][g].w;
+                        f16x4 pk;
+                        if constexpr (SPLIT) {
+                            f16x4 hi, lo;
+                            split_f16x4(gelu_erf_fast(v0), gelu_erf_fast(v1), gelu_erf_fast(v2), gelu_erf_fast(v3), hi, lo);
+                            pk = plane ? lo : hi;
+                        } else if constexpr (EPI == EPI_GELU_F16) pk = f16x4{(f16)gelu_erf_fast(v0), (f16)gelu_erf_fast(v1), (f16)gelu_erf_fast(v2), (f16)gelu_erf_fast(v3)};
+                        else pk = f16x4{(f16)v0, (f16)v1, (f16)v2, (f16)v3};
+                        *reinterpret_cast<f16x4*>(wl + epi::f16_write_off(lane, i2, j, g)) = pk;
+                    }
+            wave_lds_turn();
+            f16* const dst = SPLIT && plane ? a.out16_lo : base;
+#pragma unroll
+            for (int it = 0; it < 8; ++it) {
+                const int m = mw + hh * 64 + epi::f16_read_row(lane, it);
+                const uint4 v = *reinterpret_cast<const uint4*>(wl + epi::f16_read_off(lane, it));
+                if (m < a.M) *reinterpret_cast<uint4*>(dst + (size_t)m * ld + nc + epi::f16_read_col(lane)) = v;
+            }
+            wave_lds_turn();
         }
-        wave_lds_turn();
     }
 }
 
@@ -423,10 +492,21 @@ constexpr bool kHasStagedEpilogue = EPI == EPI_F16 || EPI == EPI_GELU_F16 || EPI
 // Hazards: tile t is read in slots 4t .. 4t+3 (every X ends with lgkmcnt(0) before its barrier); DMA(t+1) overwrites the stage of
 // tile t-1 from slot 4t on (its last read was slot 4t-1) and every wave has waited for its pieces before b_{4t+3}; the first read
 // of tile t+1 is slot 4t+4.  Both groups execute 4 nk + 1 barriers.
-template <int EPI, int MODE>      // MODE 0: direct epilogues; 1: LDS-staged (kHasStagedEpilogue); 2: direct with the bias fetched in one batch
-__global__ __launch_bounds__(512) void gemm256_kernel(const GemmArgs a) {
+// SPLIT (split A operand, encoder_precision 1): a third operand panel, the lo rows of A, does not fit beside two 64 KB stages (3 x 32 KB per
+// stage at BK = 64 = 192 KB > the CU's 160 KB), so the split form halves the K-tile instead: BK = 32, a stage is [A hi 16 KB | A lo 16 KB |
+// W 16 KB] = 48 KB (96 KB for both; the LDS-staged epilogues still take 8 x 16 KB of the 128 KB the launch asks for).  An LDS row is then the
+// 64-byte K-slice of an operand row (4 chunks of 16 bytes); chunk c of row r lives in slot c ^ ((r >> 2) & 3), which puts every 16-lane group
+// of ds_read_b128 (fragment rows fr = lane & 31, one chunk) on 16 distinct 16-byte slots of the 256-byte bank row (epi_stage.h split_*,
+// replayed by tests/native/split_stage_check.cpp).  A half-tile is ONE 16-wide k-step: X reads 2 W + 4 A hi + 4 A lo fragments, Y issues 8 x 2 MFMAs
+// (per accumulator: W x A hi, then W x A lo - the order of gemm_split_kernel), and the DMA of a K-tile is 6 pieces per wave.  The slot
+// schedule, barriers and hazards are those of the Float16 form with nk = K / 32.  The body is shared; gemm256_kernel (Float16, the names the
+// tests and profiles know) and gemm256_split_kernel are its two entry points.
+template <int EPI, int MODE, bool SPLIT>      // MODE 0: direct epilogues; 1: LDS-staged (kHasStagedEpilogue); 2: direct with the bias fetched in one batch
+__device__ __forceinline__ void gemm256_main(const GemmArgs& a) {
     constexpr int TM = 4, TN = 2;
-    extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];   // [2 stages][A 32 KB | B 32 KB]
+    constexpr int STAGE = SPLIT ? epi::kSplitStage : 65536;     // bytes per LDS stage
+    constexpr int NP = SPLIT ? 6 : 8;                          // LDS-DMA pieces per wave and K-tile
+    extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];   // [2 stages][A 32 KB | B 32 KB]  (SPLIT: [2][A hi 16 KB | A lo 16 KB | B 16 KB])
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 2, wn = wave & 3;
 
@@ -439,25 +519,45 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmArgs a) {
     const int gm = min(tiles_m - first_m, GM), in_g = wg - grp * gsz;
     const int m0 = (first_m + in_g % gm) << 8, n0 = (in_g / gm) << 8;
 
-    const int srow = tid >> 3;
-    const int chunk = (tid & 7) ^ ((tid >> 4) & 7);
-    const f16* src[8];      // pieces 0..3: A rows j*64 + srow, 4..7: W rows
+    const f16* src[NP];     // Float16 form - pieces 0..3: A rows j*64 + srow, 4..7: W rows; SPLIT - 0, 1: A hi rows j*128 + srow, 2, 3: A lo, 4, 5: W
+    if constexpr (SPLIT) {
+        const int srow = epi::split_dma_row(tid);
+        const int chunk = epi::split_dma_chunk(tid);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int m = min(m0 + j * 64 + srow, a.M - 1);
-        src[j] = a.A + (long long)(m / a.a_rows_per_batch) * a.a_batch_stride + (long long)(m % a.a_rows_per_batch) * a.lda + chunk * 8;
-        const int n = min(n0 + j * 64 + srow, a.N - 1);
-        src[4 + j] = a.W + (long long)n * a.K + chunk * 8;
+        for (int j = 0; j < 2; ++j) {
+            const int m = min(m0 + j * 128 + srow, a.M - 1);
+            const long long off = (long long)(m / a.a_rows_per_batch) * a.a_batch_stride + (long long)(m % a.a_rows_per_batch) * a.lda + chunk * 8;
+            src[j] = a.A + off;
+            src[2 + j] = a.A_lo + off;
+            const int n = min(n0 + j * 128 + srow, a.N - 1);
+            src[4 + j] = a.W + (long long)n * a.K + chunk * 8;
+        }
+    } else {
+        const int srow = tid >> 3;
+        const int chunk = (tid & 7) ^ ((tid >> 4) & 7);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int m = min(m0 + j * 64 + srow, a.M - 1);
+            src[j] = a.A + (long long)(m / a.a_rows_per_batch) * a.a_batch_stride + (long long)(m % a.a_rows_per_batch) * a.lda + chunk * 8;
+            const int n = min(n0 + j * 64 + srow, a.N - 1);
+            src[4 + j] = a.W + (long long)n * a.K + chunk * 8;
+        }
     }
     auto piece = [&](int p, int kt) {
-        unsigned char* dst = smem + (kt & 1) * 65536 + wave * 1024 + (p >> 2) * 32768 + (p & 3) * 8192;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[p] + kt * 64),
-                                         (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+        if constexpr (SPLIT) {
+            unsigned char* dst = smem + (kt & 1) * STAGE + wave * 1024 + (p >> 1) * 16384 + (p & 1) * 8192;
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[p] + kt * 32),
+                                             (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+        } else {
+            unsigned char* dst = smem + (kt & 1) * 65536 + wave * 1024 + (p >> 2) * 32768 + (p & 3) * 8192;
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[p] + kt * 64),
+                                             (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+        }
     };
 
-    const int fr = lane & 31, fh = lane >> 5, swz = (fr >> 1) & 7;
-    const int a_row_off = (wm * 128 + fr) * 128, b_row_off = 32768 + (wn * 64 + fr) * 128;
-    const int nk = a.K >> 6;
+    const int fr = lane & 31, fh = lane >> 5, swz = SPLIT ? epi::split_swz(fr) : (fr >> 1) & 7;
+    const int a_row_off = SPLIT ? (wm * 128 + fr) * 64 : (wm * 128 + fr) * 128, b_row_off = SPLIT ? 32768 + (wn * 64 + fr) * 64 : 32768 + (wn * 64 + fr) * 128;
+    const int nk = SPLIT ? a.K >> 5 : a.K >> 6;
 #define PP_BAR() do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_barrier" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define PP_XBAR() do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define PP_VMWAIT() do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); } while (0)
@@ -470,39 +570,70 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmArgs a) {
             for (int j = 0; j < TN; ++j)
 #pragma unroll
                 for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
-        f16x8 af[2][TM], bf[2][TN];
+        f16x8 af[2][TM], bf[2][TN];      // SPLIT: af[0] = A hi, af[1] = A lo, bf[0] = W of the half-tile's one k-step
         auto X = [&](int kt, int h) {
-            const unsigned char* sb = smem + (kt & 1) * 65536;
+            if constexpr (SPLIT) {
+                const unsigned char* sb = smem + (kt & 1) * STAGE;
+                const int slot = ((2 * h + fh) ^ swz) * 16;
 #pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                const int slot = ((2 * (2 * h + s2) + fh) ^ swz) * 16;
+                for (int j = 0; j < TN; ++j) bf[0][j] = *reinterpret_cast<const f16x8*>(sb + b_row_off + j * 2048 + slot);
 #pragma unroll
-                for (int j = 0; j < TN; ++j) bf[s2][j] = *reinterpret_cast<const f16x8*>(sb + b_row_off + j * 4096 + slot);
+                for (int i = 0; i < TM; ++i) af[0][i] = *reinterpret_cast<const f16x8*>(sb + a_row_off + i * 2048 + slot);
 #pragma unroll
-                for (int i = 0; i < TM; ++i) af[s2][i] = *reinterpret_cast<const f16x8*>(sb + a_row_off + i * 4096 + slot);
+                for (int i = 0; i < TM; ++i) af[1][i] = *reinterpret_cast<const f16x8*>(sb + 16384 + a_row_off + i * 2048 + slot);
+            } else {
+                const unsigned char* sb = smem + (kt & 1) * 65536;
+#pragma unroll
+                for (int s2 = 0; s2 < 2; ++s2) {
+                    const int slot = ((2 * (2 * h + s2) + fh) ^ swz) * 16;
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) bf[s2][j] = *reinterpret_cast<const f16x8*>(sb + b_row_off + j * 4096 + slot);
+#pragma unroll
+                    for (int i = 0; i < TM; ++i) af[s2][i] = *reinterpret_cast<const f16x8*>(sb + a_row_off + i * 4096 + slot);
+                }
             }
         };
-        auto Y = [&](auto dma_tag, int dma_kt) {   // 16 MFMAs; DMA: the wave's 8 LDS-DMA pieces of K-tile dma_kt go out among them
+        auto Y = [&](auto dma_tag, int dma_kt) {   // 16 MFMAs; DMA: the wave's LDS-DMA pieces of K-tile dma_kt go out among them
             constexpr bool DMA = decltype(dma_tag)::value;
             __builtin_amdgcn_s_setprio(1);      // the matrix cluster outranks the partner wave's fetch slot
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2)
+            if constexpr (SPLIT) {
 #pragma unroll
                 for (int i = 0; i < TM; ++i) {
 #pragma unroll
                     for (int j = 0; j < TN; ++j) {
-                        if constexpr (SWAP) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bf[s2][j], af[s2][i], acc[i][j], 0, 0, 0);
-                        else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[s2][i], bf[s2][j], acc[i][j], 0, 0, 0);
+#pragma unroll
+                        for (int pl = 0; pl < 2; ++pl) {       // hi, then lo
+                            if constexpr (SWAP) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bf[0][j], af[pl][i], acc[i][j], 0, 0, 0);
+                            else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[pl][i], bf[0][j], acc[i][j], 0, 0, 0);
+                        }
                     }
-                    if constexpr (DMA) { __builtin_amdgcn_sched_barrier(0); piece(s2 * 4 + i, dma_kt); __builtin_amdgcn_sched_barrier(0); }
+                    if constexpr (DMA) {     // pieces 0, 1 | 2, 3 | 4 | 5 after the MFMAs of i = 0 .. 3
+                        __builtin_amdgcn_sched_barrier(0);
+                        if (i < 2) { piece(2 * i, dma_kt); piece(2 * i + 1, dma_kt); }
+                        else piece(2 + i, dma_kt);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
                 }
+            } else {
+#pragma unroll
+                for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+                    for (int i = 0; i < TM; ++i) {
+#pragma unroll
+                        for (int j = 0; j < TN; ++j) {
+                            if constexpr (SWAP) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bf[s2][j], af[s2][i], acc[i][j], 0, 0, 0);
+                            else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[s2][i], bf[s2][j], acc[i][j], 0, 0, 0);
+                        }
+                        if constexpr (DMA) { __builtin_amdgcn_sched_barrier(0); piece(s2 * 4 + i, dma_kt); __builtin_amdgcn_sched_barrier(0); }
+                    }
+            }
             __builtin_amdgcn_s_setprio(0);
         };
         constexpr std::true_type kDma{};
         constexpr std::false_type kNoDma{};
         // prologue: tile 0 (all waves), landed and visible
 #pragma unroll
-        for (int p = 0; p < 8; ++p) piece(p, 0);
+        for (int p = 0; p < NP; ++p) piece(p, 0);
         PP_VMWAIT();
         PP_BAR();
         if (wm == 0) {
@@ -520,7 +651,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmArgs a) {
         } else {
             if (nk > 1) {
 #pragma unroll
-                for (int p = 0; p < 8; ++p) piece(p, 1);
+                for (int p = 0; p < NP; ++p) piece(p, 1);
             }
             PP_BAR();
             for (int t = 0; t + 2 < nk; ++t) {
@@ -541,9 +672,9 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmArgs a) {
             unsigned char* wl = smem + wave * epi::kWaveRegion;
             if constexpr (!SWAP) epi_staged_vt(a, acc, wl, m0 + wm * 128, n0 + wn * 64, lane);
             else if constexpr (EPI == EPI_RESID_F32) epi_staged_resid(a, acc, wl, m0 + wm * 128, n0 + wn * 64, lane);
-            else epi_staged_f16<EPI>(a, acc, wl, m0 + wm * 128, n0 + wn * 64, lane);
-        } else if constexpr (SWAP) gemm_epilogue_swapped<EPI, TM, TN, MODE == 2>(a, acc, m0 + wm * 128, n0 + wn * 64, lane);
-        else gemm_epilogue<EPI, TM, TN>(a, acc, m0 + wm * 128, n0 + wn * 64, lane);
+            else epi_staged_f16<EPI, SPLIT && EPI == EPI_GELU_F16>(a, acc, wl, m0 + wm * 128, n0 + wn * 64, lane);
+        } else if constexpr (SWAP) gemm_epilogue_swapped<EPI, TM, TN, MODE == 2, SPLIT>(a, acc, m0 + wm * 128, n0 + wn * 64, lane);
+        else gemm_epilogue<EPI, TM, TN, SPLIT>(a, acc, m0 + wm * 128, n0 + wn * 64, lane);
     };
 #undef PP_BAR
 #undef PP_XBAR
@@ -555,6 +686,11 @@ __global__ __launch_bounds__(512) void gemm256_kernel(const GemmArgs a) {
         body(std::true_type{});
     }
 }
+
+template <int EPI, int MODE>
+__global__ __launch_bounds__(512) void gemm256_kernel(const GemmArgs a) { gemm256_main<EPI, MODE, false>(a); }
+template <int EPI, int MODE>
+__global__ __launch_bounds__(512) void gemm256_split_kernel(const GemmArgs a) { gemm256_main<EPI, MODE, true>(a); }
 
 // (Round 6, built, measured and rejected, profiles/r06ae_*: gemm256w_kernel - the same tile, stages, LDS image, walk and epilogues with ONE wave per SIMD: 4 waves of 128 x 128
 // wave tiles, the 256 accumulators of a lane in AGPRs, 128 KB instead of 192 KB of fragment reads per K-tile, the next k-step's 8 ds_read_b128 and the wave's 16 LDS-DMA
@@ -754,8 +890,42 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(const GemmArgs a, int n_t
     }
 }
 
+// Split A operand (a.A_lo set, encoder_precision 1): the same kernel choice with gemm_split_kernel / gemm256_split_kernel (BK = 32 there: whole
+// 32-wide K tiles); never the persistent loop (an opt-in experiment of the Float16 form).
+template <int EPI>
+static void launch_split(const GemmArgs& a, hipStream_t st) {
+    const long long tiles256 = (long long)((a.M + 255) / 256) * ((a.N + 255) / 256);
+    static const bool no256 = [] { const char* e = getenv("WH_NO_GEMM256"); return e && e[0] == '1'; }();
+    if (!no256 && tiles256 >= 64 && a.K % 32 == 0 && a.lda % 8 == 0 && a.a_batch_stride % 8 == 0 && a.N % 4 == 0) {
+        static const int epi_mode = [] { const char* e = getenv("WH_GEMM_EPI_MODE"); return e && e[0] >= '0' && e[0] <= '2' ? e[0] - '0' : 1; }();
+        auto go = [&](auto mode_tag) {
+            constexpr int MODE = decltype(mode_tag)::value;
+            static PerDeviceOnce raised;
+            raised.run([] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_split_kernel<EPI, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, 131072); });
+            gemm256_split_kernel<EPI, MODE><<<(unsigned)tiles256, 512, 131072, st>>>(a);
+        };
+        if constexpr (kHasStagedEpilogue<EPI>) {
+            const bool aligned = (((uintptr_t)a.out16 | (uintptr_t)a.out32 | (uintptr_t)a.k16 | (uintptr_t)a.vt16 | (uintptr_t)a.out16_lo) & 15) == 0;
+            const bool shape_ok = aligned && a.N % 64 == 0 && a.M % 4 == 0 && a.ldc % 8 == 0 && a.d_model % 64 == 0;
+            if (shape_ok && epi_mode == 1) { go(std::integral_constant<int, 1>{}); return; }
+            if (shape_ok && epi_mode == 2) { go(std::integral_constant<int, 2>{}); return; }
+        }
+        go(std::integral_constant<int, 0>{});
+        return;
+    }
+    long long tiles128 = (long long)((a.M + 127) / 128) * ((a.N + 127) / 128);
+    if (tiles128 >= 192) {
+        dim3 g((a.N + 127) / 128, (a.M + 127) / 128);
+        gemm_split_kernel<128, 128, EPI><<<g, 256, 0, st>>>(a);
+    } else {
+        dim3 g((a.N + 63) / 64, (a.M + 63) / 64);
+        gemm_split_kernel<64, 64, EPI><<<g, 256, 0, st>>>(a);
+    }
+}
+
 template <int EPI>
 static void launch_epi(const GemmArgs& a, hipStream_t st) {
+    if (a.A_lo) { launch_split<EPI>(a, st); return; }
     // large problems: 256 x 256 x 64 LDS-DMA kernel (needs whole 64-wide K tiles and 16-byte aligned rows)
     const long long tiles256 = (long long)((a.M + 255) / 256) * ((a.N + 255) / 256);
     static const bool no256 = [] { const char* e = getenv("WH_NO_GEMM256"); return e && e[0] == '1'; }();

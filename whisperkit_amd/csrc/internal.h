@@ -71,6 +71,9 @@ struct wh_session {
     float* logspec = nullptr; unsigned* maxkey = nullptr; f16* mel_t = nullptr; float* mel_f32 = nullptr;
     f16* h1 = nullptr; float* x = nullptr; f16* xn = nullptr; f16 *q16 = nullptr, *k16 = nullptr, *vt16 = nullptr, *att16 = nullptr;
     f16* hmlp = nullptr; f16* enc16 = nullptr; float* enc32 = nullptr;
+    // encoder_precision 1 (split): the lo planes f16(x - f16(x)) of every rounded encoder operand and of the output (allocated only then)
+    int encoder_precision = 0;
+    f16 *mel_t_lo = nullptr, *h1_lo = nullptr, *xn_lo = nullptr, *att_lo = nullptr, *hmlp_lo = nullptr, *enc_lo = nullptr;
     // decoder
     f16 *cross_k_hi = nullptr, *cross_v_hi = nullptr;               // K / V-row mode: 24-bit rows (kernels.h hr24), Float16 part ...
     signed char *cross_k_lo = nullptr, *cross_v_lo = nullptr;       // ... and 8-bit residuals

@@ -86,9 +86,17 @@ struct MelTables {
     int n_mels;
 };
 
+// mel_t_lo (split encoder sessions, else null): the lo plane f16(x - f16(x)) of mel_t, same layout
 void launch_log_mel(const MelTables& t, const float* pcm, const int* n_valid, int batch, float* logspec, unsigned* maxkey,
-                    f16* mel_t, float* mel_f32, hipStream_t st);
-void launch_mel_import(const float* mel_f32, int n_mels, int batch, f16* mel_t, hipStream_t st);
+                    f16* mel_t, float* mel_f32, hipStream_t st, f16* mel_t_lo = nullptr);
+void launch_mel_import(const float* mel_f32, int n_mels, int batch, f16* mel_t, hipStream_t st, f16* mel_t_lo = nullptr);
+
+// Split Float16 operand (encoder_precision 1): x ~ hi + lo with hi = f16(x), lo = f16(x - hi) (x - hi is exact in fp32).  22 significant bits
+// where lo is normal; Float16 subnormals bound the absolute error by 2^-25 below that.
+__device__ __forceinline__ void split_f16(float x, f16& hi, f16& lo) {
+    hi = (f16)x;
+    lo = (f16)(x - (float)hi);
+}
 
 // ---------------------------------------------------------------------------------------------- GEMM
 // C[M][N] = A[M][K] * W[N][K]^T (+ bias[N]) with fused epilogues.  A rows may be an overlapping-row view:
@@ -126,17 +134,25 @@ struct GemmArgs {
     f16 *kv_k_hi = nullptr, *kv_v_hi = nullptr;              // EPI_CROSS_KV: the cross-attention key / value rows as hr24 (below): Float16 part ...
     signed char *kv_k_lo = nullptr, *kv_v_lo = nullptr;      // ... and the 8-bit residuals
     int prof_kind = -1;        // KernelKind of this launch (measurement only)
+    // Split A operand (encoder_precision 1): non-null = A_lo holds the lo plane of A in A's layout; every 16-wide k-step multiplies the
+    // weight fragment by the hi and then by the lo fragment into the same accumulator.  EPI_GELU_F16 / EPI_CONV1 then also write the lo
+    // plane of their output to out16_lo (same layout as out16).
+    const f16* A_lo = nullptr;
+    f16* out16_lo = nullptr;
 };
 
 void launch_gemm(GemmEpi epi, const GemmArgs& a, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------------- LayerNorm
 // y = LN(x) * g + b over rows of length d; x fp32 [rows][d]; writes f16 and/or f32
-void launch_layernorm(const float* x, const float* g, const float* b, int rows, int d, f16* y16, float* y32, hipStream_t st);
+// y16_lo (split encoder sessions, else null): the lo plane f16(y - f16(y)) beside y16
+void launch_layernorm(const float* x, const float* g, const float* b, int rows, int d, f16* y16, float* y32, hipStream_t st, f16* y16_lo = nullptr);
 
 // ---------------------------------------------------------------------------------------------- encoder attention
 // q16,k16: [B*1500][d] (q pre-scaled), vt16: [B][H][64][1536]; out16: [B*1500][d]
-void launch_encoder_attention(const f16* q16, const f16* k16, const f16* vt16, f16* out16, int batch, int n_head, int d, hipStream_t st);
+// out_lo (split encoder sessions, else null): the lo plane of the output; q / k / v / P stay Float16
+void launch_encoder_attention(const f16* q16, const f16* k16, const f16* vt16, f16* out16, int batch, int n_head, int d, hipStream_t st,
+                              f16* out_lo = nullptr);
 
 // ---------------------------------------------------------------------------------------------- decoder
 struct DecLayerW {
@@ -338,6 +354,7 @@ void launch_alignment_mean(const float* align, int batch, int n_align, float* ou
 void launch_alignment_postprocess(const float* align, int n_align, float* prob_tmp, float* stat_tmp, int* row_written, int znorm, int median_width,
                                   float* out, hipStream_t st);
 void launch_f32_to_f16(const float* in, f16* out, size_t n, hipStream_t st);
+void launch_f32_to_f16_split(const float* in, f16* hi, f16* lo, size_t n, hipStream_t st);     // split_f16 of every element
 void launch_f16_to_f32(const f16* in, float* out, size_t n, hipStream_t st);
 
 }  // namespace wh

@@ -9,7 +9,7 @@ constexpr int LN_MAXE = 20;  // d <= 1280
 
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, const float* __restrict__ g,
                                                         const float* __restrict__ bta, int rows, int d,
-                                                        f16* __restrict__ y16, float* __restrict__ y32) {
+                                                        f16* __restrict__ y16, float* __restrict__ y32, f16* __restrict__ y16_lo) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int row = blockIdx.x * 4 + wave;
     if (row >= rows) return;
@@ -37,6 +37,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
         if (c < d) {
             float o = (v[i] - mean) * rstd * g[c] + bta[c];
             if (y16) y16[(size_t)row * d + c] = (f16)o;
+            if (y16_lo) y16_lo[(size_t)row * d + c] = (f16)(o - (float)(f16)o);
             if (y32) y32[(size_t)row * d + c] = o;
         }
     }
@@ -45,10 +46,11 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
 // The same row LayerNorm with 16-byte loads and 8-byte Float16 stores (round 6): lane l owns channels 4 l .. 4 l + 3 of every 256-channel group, so a wave instruction
 // moves 1 KB in and 512 B out instead of 256 B / 128 B (the dword / 2-byte form above: 642 us per 256 x 1500 rows of 1280 = 4.6 TB/s).  Same two-pass arithmetic; the
 // lane's partial sums cover different channels than in the scalar form, so results agree to the last bits of the fp32 statistics, not bit for bit.
-template <bool NT>
+// LO (split encoder sessions): also the lo plane f16(y - f16(y)) of the Float16 output, same layout and store form.
+template <bool NT, bool LO = false>
 __global__ __launch_bounds__(256) void layernorm_v4_kernel(const float* __restrict__ x, const float* __restrict__ g,
                                                            const float* __restrict__ bta, int rows, int d,
-                                                           f16* __restrict__ y16, float* __restrict__ y32) {
+                                                           f16* __restrict__ y16, float* __restrict__ y32, f16* __restrict__ y16_lo = nullptr) {
     constexpr int NV = LN_MAXE / 4;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int row = blockIdx.x * 4 + wave;
@@ -88,19 +90,30 @@ __global__ __launch_bounds__(256) void layernorm_v4_kernel(const float* __restri
                 const f16x4 o = {(f16)o0, (f16)o1, (f16)o2, (f16)o3};
                 if constexpr (NT) __builtin_nontemporal_store(o, reinterpret_cast<f16x4*>(y16 + (size_t)row * d + c));
                 else *reinterpret_cast<f16x4*>(y16 + (size_t)row * d + c) = o;
+                if constexpr (LO) {
+                    const f16x4 lo = {(f16)(o0 - (float)o[0]), (f16)(o1 - (float)o[1]), (f16)(o2 - (float)o[2]), (f16)(o3 - (float)o[3])};
+                    if constexpr (NT) __builtin_nontemporal_store(lo, reinterpret_cast<f16x4*>(y16_lo + (size_t)row * d + c));
+                    else *reinterpret_cast<f16x4*>(y16_lo + (size_t)row * d + c) = lo;
+                }
             }
             if (y32) *reinterpret_cast<float4*>(y32 + (size_t)row * d + c) = float4{o0, o1, o2, o3};
         }
     }
 }
 
-void launch_layernorm(const float* x, const float* g, const float* b, int rows, int d, f16* y16, float* y32, hipStream_t st) {
+void launch_layernorm(const float* x, const float* g, const float* b, int rows, int d, f16* y16, float* y32, hipStream_t st, f16* y16_lo) {
     ProfScope ps_(KK_LAYERNORM, st);
     static const int v4 = [] { const char* e = getenv("WH_LN_V4"); return e ? atoi(e) : 2; }();      // 2 (default): non-temporal row loads and Float16 stores (514 -> 488 us per 384 000 rows: each is touched once before 3 GB of other traffic), 1: plain, 0: the scalar form; 1 and 2 give the same bits
     const bool aligned = d % 4 == 0 && (((uintptr_t)x | (uintptr_t)g | (uintptr_t)b | (uintptr_t)y32) % 16) == 0 && ((uintptr_t)y16 % 8) == 0;
+    if (y16_lo) {       // split encoder: y16 must be set
+        if (v4 == 2 && aligned && (uintptr_t)y16_lo % 8 == 0) layernorm_v4_kernel<true, true><<<(rows + 3) / 4, 256, 0, st>>>(x, g, b, rows, d, y16, y32, y16_lo);
+        else if (v4 && aligned && (uintptr_t)y16_lo % 8 == 0) layernorm_v4_kernel<false, true><<<(rows + 3) / 4, 256, 0, st>>>(x, g, b, rows, d, y16, y32, y16_lo);
+        else layernorm_kernel<<<(rows + 3) / 4, 256, 0, st>>>(x, g, b, rows, d, y16, y32, y16_lo);
+        return;
+    }
     if (v4 == 2 && aligned) layernorm_v4_kernel<true><<<(rows + 3) / 4, 256, 0, st>>>(x, g, b, rows, d, y16, y32);
     else if (v4 && aligned) layernorm_v4_kernel<false><<<(rows + 3) / 4, 256, 0, st>>>(x, g, b, rows, d, y16, y32);
-    else layernorm_kernel<<<(rows + 3) / 4, 256, 0, st>>>(x, g, b, rows, d, y16, y32);
+    else layernorm_kernel<<<(rows + 3) / 4, 256, 0, st>>>(x, g, b, rows, d, y16, y32, nullptr);
 }
 
 __global__ void f32_to_f16_kernel(const float* __restrict__ in, f16* __restrict__ out, size_t n) {
@@ -110,6 +123,13 @@ __global__ void f32_to_f16_kernel(const float* __restrict__ in, f16* __restrict_
 __global__ void f16_to_f32_kernel(const f16* __restrict__ in, float* __restrict__ out, size_t n) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = (float)in[i];
+}
+__global__ void f32_to_f16_split_kernel(const float* __restrict__ in, f16* __restrict__ hi, f16* __restrict__ lo, size_t n) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) { f16 h, l; split_f16(in[i], h, l); hi[i] = h; lo[i] = l; }
+}
+void launch_f32_to_f16_split(const float* in, f16* hi, f16* lo, size_t n, hipStream_t st) {
+    f32_to_f16_split_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(in, hi, lo, n);
 }
 void launch_f32_to_f16(const float* in, f16* out, size_t n, hipStream_t st) {
     f32_to_f16_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(in, out, n);

@@ -154,7 +154,8 @@ __global__ __launch_bounds__(256, 2) void mel_power_kernel(const float* __restri
 
 __global__ __launch_bounds__(256) void mel_finalize_kernel(const float* __restrict__ logspec, const unsigned* __restrict__ maxkey,
                                                            int n_mels, f16* __restrict__ mel_t /* [B][3002][n_mels] */,
-                                                           float* __restrict__ mel_f32 /* [B][n_mels][3000] or null */) {
+                                                           float* __restrict__ mel_f32 /* [B][n_mels][3000] or null */,
+                                                           f16* __restrict__ mel_t_lo /* split encoder: lo plane of mel_t, or null */) {
     extern __shared__ __attribute__((aligned(16))) float tile[];   // [n_mels][65]
     const int b = blockIdx.y;
     const int f0 = blockIdx.x * 64;
@@ -175,21 +176,28 @@ __global__ __launch_bounds__(256) void mel_finalize_kernel(const float* __restri
     for (int idx = tid; idx < n_mels * 64; idx += 256) {
         int i = idx / n_mels, m = idx - i * n_mels;
         int f = f0 + i;
-        if (f < kFrames) mel_t[((size_t)b * kFramesPad + f + 1) * n_mels + m] = (f16)tile[m * 65 + i];
+        if (f < kFrames) {
+            const size_t o = ((size_t)b * kFramesPad + f + 1) * n_mels + m;
+            if (mel_t_lo) { f16 hi, lo; split_f16(tile[m * 65 + i], hi, lo); mel_t[o] = hi; mel_t_lo[o] = lo; }
+            else mel_t[o] = (f16)tile[m * 65 + i];
+        }
     }
 }
 
 // [n_mels][3000] f32 (reference layout) -> time-major f16 operand; used by wh_set_mel
-__global__ void mel_import_kernel(const float* __restrict__ mel_f32, int n_mels, f16* __restrict__ mel_t) {
+__global__ void mel_import_kernel(const float* __restrict__ mel_f32, int n_mels, f16* __restrict__ mel_t, f16* __restrict__ mel_t_lo) {
     int b = blockIdx.y;
     int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n_mels * kFrames) return;
     int f = idx / n_mels, m = idx - f * n_mels;
-    mel_t[((size_t)b * kFramesPad + f + 1) * n_mels + m] = (f16)mel_f32[((size_t)b * n_mels + m) * kFrames + f];
+    const size_t o = ((size_t)b * kFramesPad + f + 1) * n_mels + m;
+    const float x = mel_f32[((size_t)b * n_mels + m) * kFrames + f];
+    if (mel_t_lo) { f16 hi, lo; split_f16(x, hi, lo); mel_t[o] = hi; mel_t_lo[o] = lo; }
+    else mel_t[o] = (f16)x;
 }
 
 void launch_log_mel(const MelTables& t, const float* pcm, const int* n_valid, int batch, float* logspec, unsigned* maxkey,
-                    f16* mel_t, float* mel_f32, hipStream_t st) {
+                    f16* mel_t, float* mel_f32, hipStream_t st, f16* mel_t_lo) {
     hipMemsetAsync(maxkey, 0, sizeof(unsigned) * batch, st);
     dim3 g1((kFrames + 16 * FG - 1) / (16 * FG), batch);
     const size_t smem1 = (size_t)(kSpanLds + 16 * LDP) * sizeof(float);   // 55.8 KB: two workgroups per CU
@@ -197,12 +205,12 @@ void launch_log_mel(const MelTables& t, const float* pcm, const int* n_valid, in
     raised.run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&mel_power_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem1); });
     { ProfScope ps_(KK_MEL_POWER, st); mel_power_kernel<<<g1, 256, smem1, st>>>(pcm, n_valid, t.basis_c, t.basis_s, t.filt_c, t.filt_off, t.filt_nnz, t.filt_range, t.n_mels, logspec, maxkey); }
     dim3 g2((kFrames + 63) / 64, batch);
-    { ProfScope ps_(KK_MEL_FINALIZE, st); mel_finalize_kernel<<<g2, 256, t.n_mels * 65 * sizeof(float), st>>>(logspec, maxkey, t.n_mels, mel_t, mel_f32); }
+    { ProfScope ps_(KK_MEL_FINALIZE, st); mel_finalize_kernel<<<g2, 256, t.n_mels * 65 * sizeof(float), st>>>(logspec, maxkey, t.n_mels, mel_t, mel_f32, mel_t_lo); }
 }
 
-void launch_mel_import(const float* mel_f32, int n_mels, int batch, f16* mel_t, hipStream_t st) {
+void launch_mel_import(const float* mel_f32, int n_mels, int batch, f16* mel_t, hipStream_t st, f16* mel_t_lo) {
     dim3 g((n_mels * kFrames + 255) / 256, batch);
-    mel_import_kernel<<<g, 256, 0, st>>>(mel_f32, n_mels, mel_t);
+    mel_import_kernel<<<g, 256, 0, st>>>(mel_f32, n_mels, mel_t, mel_t_lo);
 }
 
 }  // namespace wh
