@@ -55,10 +55,42 @@ class Rig:
         return self.om.new_state(sess.getEncoderOutput(b).astype(np.float16).astype(np.float32))
 
 
-@pytest.fixture(scope="module", params=[("test-small-l2", 0), ("test-large-v3-l2", 0), ("test-small-l2", 1), ("test-large-v3-l2", 1)],
-                ids=["small-kv-rows", "large-v3-kv-rows", "small-absorbed", "large-v3-absorbed"])
+_RIGS = {}
+
+
+def _rig(name, mode):
+    if (name, mode) not in _RIGS:
+        _RIGS[(name, mode)] = Rig(name, seed=11, mode=mode)
+    return _RIGS[(name, mode)]
+
+
+# base / medium (d = 512 / 1024, 8 / 16 heads): the absorbed cross-attention's xabs_attn_kernel<2 | 4, ...> / xabs_vup_kernel<*, 2 | 4> and the
+# decoder projection chunkings of those widths, which the headline widths never launch
+@pytest.fixture(scope="module", params=[("test-small-l2", 0), ("test-large-v3-l2", 0), ("test-small-l2", 1), ("test-large-v3-l2", 1),
+                                        ("test-base-l2", 0), ("test-medium-l2", 0), ("test-base-l2", 1), ("test-medium-l2", 1)],
+                ids=["small-kv-rows", "large-v3-kv-rows", "small-absorbed", "large-v3-absorbed",
+                     "base-kv-rows", "medium-kv-rows", "base-absorbed", "medium-absorbed"])
 def rig(request):
-    return Rig(request.param[0], seed=11, mode=request.param[1])
+    return _rig(*request.param)
+
+
+@pytest.mark.parametrize("name", ["test-base-l2", "test-medium-l2"])
+@pytest.mark.parametrize("splits", [1, 2, 3, 4])
+def test_dims_absorbed_key_splits_teacher_forced(name, splits):
+    """every key-split count of the absorbed form (xabs_vup_kernel<splits, d / 256>) against the oracle at the base / medium widths"""
+    rig = _rig(name, 1)
+    slots = [0, BMAX - 1]
+    s = api.Session(rig.model, len(slots), crossAttentionMode=1, crossAttentionSplits=splits)
+    assert (s.crossAttentionMode, s.crossAttentionSplits) == (1, splits)
+    for b, i in enumerate(slots):
+        s.padOrTrim(rig.xs[i], b)
+    s.logMelSpectrogram(2); s.encodeFeatures(2); s.prepareDecoderInputs(2)
+    states = [rig.oracle_state(s, b) for b in range(2)]
+    for pos, t in [(0, rig.st.startOfTranscriptToken), (1, rig.st.englishToken), (2, rig.st.transcribeToken), (3, 1029), (130, 400)]:
+        got = s.predictLogits([int(t)] * 2, [pos] * 2)
+        for b in range(2):
+            e = float(np.abs(got[b] - states[b].step(int(t), pos)).max())
+            assert e <= 1e-3, (name, splits, b, pos, e)
 
 
 def test_dims_shapes_match_reference_pins(rig):

@@ -75,6 +75,10 @@ MODEL_DIMS: Dict[str, WhisperDims] = {
     "test-tiny-en-l2": WhisperDims(80, 1500, 384, 6, 2, 51864, 448, 384, 6, 2),
     "test-small-l2": WhisperDims(80, 1500, 768, 12, 2, 51865, 448, 768, 12, 2),
     "test-large-v3-l2": WhisperDims(128, 1500, 1280, 20, 2, 51866, 448, 1280, 20, 2),
+    # the base / medium widths (d = 512 / 1024, 8 / 16 heads) with 2 + 2 layers: the absorbed cross-attention instantiations
+    # xabs_attn_kernel<2 | 4, ...> and xabs_vup_kernel<*, 2 | 4> that the headline widths do not reach
+    "test-base-l2": WhisperDims(80, 1500, 512, 8, 2, 51865, 448, 512, 8, 2),
+    "test-medium-l2": WhisperDims(80, 1500, 1024, 16, 2, 51865, 448, 1024, 16, 2),
 }
 
 
