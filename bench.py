@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: audio-seconds per second of the Whisper hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W            (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W [--full]   (N > 1: launched by torch.distributed.run, one rank per GPU)
 
 One "step" = one pass of the whole hot path over one batch of synthetic 30 s chunks, the way SURVEY.md section 8(d) specifies
 it - "PCM in host memory -> token ids + segments on host": padOrTrim from host float32 PCM (wh_set_audio) -> log-mel -> audio
@@ -18,7 +18,7 @@ HIP stream / host thread each: the encoder GEMMs and the projection kernels of o
 in flight 2350 audio-s/s, 128 x 3 2647 - 2660, 256 x 3 with 256 workgroups per launch 2584 - 2692 (profiles/r05a_*, r05d_*), 256 x 3 with two slots per
 workgroup 2749 (profiles/r06i_*).  Weights are random-init (no checkpoints in
 the image), so EOT is never the argmax and the loop runs to the reference's length cap (sampleLength 224 -> 223 decoder forward
-passes per chunk): the decode length is fixed and comparable across runs.  Round 1's configuration (8 chunks per step, 3 in
+passes per chunk): the decode length is fixed and comparable across runs.  With `--full`, round 1's configuration (8 chunks per step, 3 in
 flight) and the other BASELINE configs are measured after the headline and reported under "other_configs", each with its own `roofline`.
 
 N > 1 (configs[3]: "64 x 30 s chunks sharded across 8 x MI355X"): STRONG scaling by default - a step is still 64 chunks in total,
@@ -27,12 +27,19 @@ all-gathered through the C-ABI communicator (wh_comm_*: ncclAllGather over xGMI,
 its shares of up to G consecutive steps into one device batch of at most 256 slots (continuous batching, as at one GPU; never more steps
 than a session's share of the run: plan_batches); `--scaling weak` is the old mode (64 chunks per step AND GPU).
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
+A plain run does only what the headline needs: it sets up, warms up, times the steps, writes `--dump-outputs` and prints ONE JSON
+line (rank 0) with the driver's contract fields (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the session
+geometry in `config` and the medians of the timed steps).  Everything measured beside the headline, in runs of its own, is behind
+`--full` (`"full": true` in the line), where the `--no-*` options drop single legs:
+  `stages`        mel / encoder / cross-K/V / decode split of one device batch, three passes (also `encoder_ms_per_chunk`);
+  `value_single_stream`  the same workload with one device batch in flight (`--no-serial-reference` skips it);
   `roofline`      the dominant kernel of the step, HIP-event timed on the session stream (wh_measure_kernels), against the
-                  HBM or dense-f16-MFMA peak, with the per-kernel table it was picked from;
+                  HBM or dense-f16-MFMA peak, with the per-kernel table it was picked from (`--no-roofline`);
   `cpu_baseline`  the CPU oracle (a port: torch fp32 + the restated WhisperKit loop) on the host cores, rank 0, N == 1 only,
                   on a bounded sample (one chunk: mel + encoder + 16 decoder steps, extrapolated to 223 steps); its first tokens
-                  must equal the GPU's (hard failure otherwise).
+                  must equal the GPU's (hard failure otherwise; `--no-cpu-baseline`);
+  `other_configs` the other BASELINE configurations, N == 1 only (`--no-other-configs`).
+In a plain run these fields are null (`other_configs` empty).
 """
 import argparse
 import ctypes
@@ -240,17 +247,30 @@ def dump_step_outputs(out_dir, records, first, results, segments):
     log(f"wrote {len(arrays)} arrays of the last timed step ({n} chunks) to {out_dir}")
 
 
+def synthetic_audio_sets(first, n_local, n_sets):
+    """host float32 PCM of chunks first .. first + n_local - 1 of audio sets 0 .. n_sets - 1, drawn on a thread pool (numpy releases the
+    GIL; every chunk has its own seed, so the arrays do not depend on the pool; a 256-slot headline run draws 512 chunks of 480 000 samples)"""
+    from concurrent.futures import ThreadPoolExecutor
+    from whisperkit_amd.synth import bench_chunk_seed, synthetic_chunk
+
+    def job(i):     # chunk b of set k = job k * n_local + b
+        return np.ascontiguousarray(synthetic_chunk(bench_chunk_seed(first + i % n_local, i // n_local)), dtype=np.float32)
+    with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as ex:
+        flat = list(ex.map(job, range(n_sets * n_local)))
+    return [flat[k * n_local:(k + 1) * n_local] for k in range(n_sets)]
+
+
 def run_config(args, model_name, B, F, steps, warmup, world, rank, local_rank, dev, want_roofline, want_cpu, word_timestamps=False,
-               comm=None, scaling="strong", device_batch=None, whole_chip_leg=True, dump_outputs=None):
+               comm=None, scaling="strong", device_batch=None, whole_chip_leg=True, dump_outputs=None, want_stages=True, want_serial=True):
     """B = chunks per step: in total over the ranks (strong scaling, the default) or per rank (weak).  A rank's share of a step is the
     contiguous block partition_chunks gives it; the shares of up to G consecutive steps are packed into one device batch of at most
     `device_batch` slots (continuous batching: default = B, i.e. G = 1 at one GPU; the headline packs two 64-chunk steps into one 128-slot
     batch).  The steps of a run are dealt to the F sessions in equal shares (plan_batches).  With `dump_outputs` rank 0 writes what the last
-    timed step computed to that directory (dump_step_outputs)."""
+    timed step computed to that directory (dump_step_outputs).  After the timed region rank 0 runs the legs asked for: the stage split
+    (`want_stages`), the single-stream reference (`want_serial` and args.serial_reference, F > 1), the roofline and the CPU baseline."""
     import torch
     import torch.distributed as dist
     from whisperkit_amd import api, parallel
-    from whisperkit_amd.synth import bench_chunk_seed, synthetic_chunk
 
     model, dims, sd = get_model(model_name, local_rank, keep_sd=want_cpu)
     F = max(1, F)
@@ -276,7 +296,8 @@ def run_config(args, model_name, B, F, steps, warmup, world, rank, local_rank, d
     # weak 9: identical halves let the embedding kernel read one row for two slots) and an N-rank run sees the audio of the 1-rank run step by step.
     # Set 0 is the chunk set of rounds 1 - 5 (seeds 1234 + chunk index): the CPU baseline and tests/test_gpu_fulldepth.py check against it.
     n_sets = max(1, min(AUDIO_SETS, max(steps, warmup, F * G)))
-    audio = [[np.ascontiguousarray(synthetic_chunk(bench_chunk_seed(first + b, k)), dtype=np.float32) for b in range(n_local)] for k in range(n_sets)]
+    log(f"{model_name}: drawing {n_sets} audio set(s) of {n_local} chunks")
+    audio = synthetic_audio_sets(first, n_local, n_sets)
     chunks = audio[0]
     opts = api.DecodingOptions(firstTokenLogProbThreshold=None, logProbThreshold=None, compressionRatioThreshold=None,
                                noSpeechThreshold=None, temperatureFallbackCount=0, sampleLength=args.sample_length,
@@ -387,7 +408,7 @@ def run_config(args, model_name, B, F, steps, warmup, world, rank, local_rank, d
                                if sess.crossAttentionMode == 1 else "per-layer K / V rows"),
            "total": total, "n_local": n_local, "steps_per_batch": G, "slots": slots, "audio_sets": n_sets,
            "median_step_latency_ms": float(np.median(lat)) * 1e3, "median_ms_per_step": float(np.median(durs)) * 1e3 / Fe, "n_median": int(len(durs))}
-    if rank == 0 and F > 1 and args.serial_reference:
+    if rank == 0 and F > 1 and want_serial and args.serial_reference:
         # single-stream reference on rank 0 only: local synchronisation, no collective (the other ranks are not here)
         for ss in sessions:
             ss.synchronize()
@@ -398,7 +419,7 @@ def run_config(args, model_name, B, F, steps, warmup, world, rank, local_rank, d
         out["serial_ms_per_step"] = (time.perf_counter() - s0) / (2 * G) * 1e3
 
     # ---- stage split (rank 0): mel + encoder milliseconds per chunk, decode tokens/s (one full device batch)
-    if rank == 0:
+    if rank == 0 and want_stages:
         ts = []
         nb = slots
         for _ in range(3):
@@ -581,8 +602,10 @@ def main():
     ap.add_argument("--steps", type=int, default=12)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--inflight", type=int, default=3, help="steps (batches of --batch chunks) in flight per GPU, each on its own session / HIP stream")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure what it does not need: the stage split, the single-stream "
+                    "reference, the per-kernel roofline, the CPU baseline and the other BASELINE configurations (each can be dropped with its --no-* option)")
     ap.add_argument("--serial-reference", action=argparse.BooleanOptionalAction, default=True,
-                    help="after the timed region, time the same workload with one step in flight (value_single_stream); --no-serial-reference skips it")
+                    help="with --full: after the timed region, time the same workload with one step in flight (value_single_stream); --no-serial-reference skips it")
     ap.add_argument("--model", default="large-v3")
     ap.add_argument("--batch", type=int, default=64, help="30 s chunks per step (one decode batch = batch / 32 MFMA batch tiles): in total over the GPUs "
                     "with --scaling strong (BASELINE configs[3]: 64 chunks sharded across the GPUs), per GPU with --scaling weak")
@@ -603,9 +626,9 @@ def main():
     ap.add_argument("--dist-backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only to rehearse "
                     "the multi-rank control flow on a box with fewer GPUs than ranks, together with --single-device)")
     ap.add_argument("--single-device", action="store_true", help="rehearsal: every rank uses GPU 0")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the per-kernel roofline")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the other BASELINE configurations")
     ap.add_argument("--dump-records", default=None, help="rank 0 writes the gathered result records of the last timed step (chunk index, "
                     "token ids, steps) to this JSON file: the N-rank rehearsal compares them with a 1-rank run (tests/test_gpu_round4.py)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="rank 0 writes what the last timed step of the configuration the result line reports "
@@ -672,11 +695,11 @@ def main():
         comm_transport = "torch.distributed" if world > 1 else "none"
     dev_batch = args.device_batch if args.device_batch > 0 else (256 if args.batch >= 64 else args.batch)
     main_cfg = run_config(args, args.model, args.batch, args.inflight, args.steps, args.warmup, world, rank, local_rank, dev,
-                          want_roofline=not args.no_roofline, want_cpu=(world == 1 and not args.no_cpu_baseline), comm=comm, scaling=args.scaling,
-                          device_batch=dev_batch, dump_outputs=args.dump_outputs)
+                          want_roofline=args.full and not args.no_roofline, want_cpu=(args.full and world == 1 and not args.no_cpu_baseline), comm=comm,
+                          scaling=args.scaling, device_batch=dev_batch, dump_outputs=args.dump_outputs, want_stages=args.full, want_serial=args.full)
     other = {}
     headline = (args.model, args.batch) == ("large-v3", 64)
-    extra = rank == 0 and world == 1 and not args.no_other_configs
+    extra = args.full and rank == 0 and world == 1 and not args.no_other_configs
 
     def brief_roofline(rf):
         """the dominant kernel's line + the whole-step HBM figure of a secondary configuration (every BASELINE config carries one)"""
@@ -720,6 +743,7 @@ def main():
         B = args.batch
         total, nl, G = main_cfg["total"], main_cfg["n_local"], main_cfg["steps_per_batch"]
         scaling = args.scaling if world > 1 else "strong"
+        stages = main_cfg.get("stages")
         packed = (f"; each GPU packs its {nl}-chunk shares of {G} consecutive steps into one {main_cfg['slots']}-slot device batch" if G > 1 else "")
         out = {
             "metric": "audio-sec/sec (1/RTF), 30 s chunks: host PCM -> log-mel + encoder + greedy decode -> segments",
@@ -744,8 +768,9 @@ def main():
             "value_from_median_step": round(total * 30.0 / (main_cfg["median_ms_per_step"] * 1e-3), 2),
             "value_single_stream": (round(total * 30.0 / (main_cfg["serial_ms_per_step"] * 1e-3), 2)
                                     if main_cfg.get("serial_ms_per_step") else None),
-            "encoder_ms_per_chunk": round(main_cfg["stages"]["encoder_ms_per_chunk"], 4),
-            "stages": {k: (round(v, 4) if isinstance(v, float) else v) for k, v in main_cfg["stages"].items()},
+            "full": args.full,
+            "encoder_ms_per_chunk": round(stages["encoder_ms_per_chunk"], 4) if stages else None,
+            "stages": {k: (round(v, 4) if isinstance(v, float) else v) for k, v in stages.items()} if stages else None,
             "roofline": main_cfg.get("roofline"), "cpu_baseline": main_cfg.get("cpu_baseline"), "other_configs": other,
         }
         print(json.dumps(out), flush=True)

@@ -3,7 +3,7 @@
 # on the whole chip and on a 128- / 64-CU partition (WH_CU_PARTS), with one and with two weight-row tiles per projection workgroup (WH_D32_RT_BT).
 cd ${GRAFT_REPO_ROOT:-.}; export TMPDIR=/tmp; T=${1:-r06t}; OUT=gpurun_out/${T}_chain_on_cus_ab.jsonl; : > $OUT
 run() {
-  env "$@" timeout 500 python bench.py --steps 4 --warmup 4 --inflight 1 --device-batch 256 --cross-attention-splits 1 --cross-attention-slots-per-workgroup 2 --no-cpu-baseline --no-other-configs --no-serial-reference 2>gpurun_out/${T}_last.err | tail -1 | \
+  env "$@" timeout 500 python bench.py --full --steps 4 --warmup 4 --inflight 1 --device-batch 256 --cross-attention-splits 1 --cross-attention-slots-per-workgroup 2 --no-cpu-baseline --no-other-configs --no-serial-reference 2>"$(dirname "$OUT")/${T}_last.err" | tail -1 | \
     python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); k = d['roofline']['kernels']

@@ -4,7 +4,7 @@
 cd ${GRAFT_REPO_ROOT:-.}; export TMPDIR=/tmp; T=${1:-r06g}; OUT=gpurun_out/${T}_encoder_confinement_ab.jsonl; : > $OUT
 run() {  # label, inflight, env...
   L=$1; F=$2; shift 2
-  env "$@" timeout 400 python bench.py --steps 12 --warmup 3 --inflight $F --no-cpu-baseline --no-other-configs --no-roofline --no-serial-reference 2>/dev/null | tail -1 | \
+  env "$@" timeout 400 python bench.py --full --steps 12 --warmup 3 --inflight $F --no-cpu-baseline --no-other-configs --no-roofline --no-serial-reference 2>/dev/null | tail -1 | \
     python -c "import sys, json; d = json.loads(sys.stdin.read()); print(json.dumps({'config': '$L', 'inflight': $F, 'audio_s_per_s': d['value'], 'ms_per_step': d['ms_per_step'], 'encoder_ms_per_chunk': d['encoder_ms_per_chunk']}))" >> $OUT
   tail -1 $OUT
 }
