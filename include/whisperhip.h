@@ -203,8 +203,11 @@ void wh_session_destroy(wh_session* s);
 int wh_session_max_batch(const wh_session* s);
 /* 1: the session's decoder attends over the encoder output directly (weight-absorbed cross-attention: encoder_output_embeds is the
    decoder input in the reference too, Core/Models.swift:986-987), 0: per-layer cross K / V rows (24 bits per element: Float16 + an 8-bit residual) are materialised by
-   wh_prepare_decoder_inputs.  Fixed at creation: automatic = absorbed when the width supports it (512 / 768 / 1024 / 1280) and
-   max_batch >= wh_xabs_auto_min_slots() (28; WH_XABS_MIN_SLOTS), or WH_XABS=0 / 1.  The choice is made from max_batch alone, so
+   wh_prepare_decoder_inputs.  Fixed at creation.  Mode 1 can run at five widths, wh_xabs_supports(): 384 / 512 / 768 / 1024 / 1280.
+   The AUTOMATIC choice (mode -1, wh_session_create) is a narrower predicate: absorbed at 512 / 768 / 1024 / 1280 when
+   max_batch >= wh_xabs_auto_min_slots() (28; WH_XABS_MIN_SLOTS), or WH_XABS=0 / 1.  At 384 (tiny, tiny.en) the absorbed form is opt-in:
+   mode -1 keeps the K / V rows at every max_batch and WH_XABS is ignored there, as before the width had an absorbed kernel; only an
+   explicit cross_attention_mode = 1 selects it.  The choice is made from max_batch alone, so
    Session(m, 27) and Session(m, 28) run different kernels: both modes meet the 1e-3 relative logits contract against the fp32
    model, bit-identity across batch sizes holds within a mode.  Slots that share an encoder output (beam search: beam_size slots per
    audio) need no special request: mode 1 reads the shared tensor with cacheable loads then (the beams of an audio are dispatched back to
@@ -217,6 +220,9 @@ int wh_session_cross_attention_mode(const wh_session* s);
 int wh_xabs_auto_min_slots(void);
 /* the automatic key-split count of an absorbed session of max_batch slots (see wh_session_create_tuned) */
 int wh_xabs_auto_splits(int max_batch);
+/* 1 when a model with this decoder width (n_text_state) and head count can run the absorbed cross-attention (cross_attention_mode = 1):
+   384 x 6, 512 x 8, 768 x 12, 1024 x 16, 1280 x 20 - the five Whisper widths with heads of 64 channels; 0 otherwise.  Host only. */
+int wh_xabs_supports(int n_state, int n_head);
 /* key splits per slot of the absorbed cross-attention (0 in K / V-row mode): slots x splits workgroups, one per CU, stream the
    encoder output; fixed at creation (bench.py prices the kernel's algorithmic bytes with it) */
 int wh_session_cross_attention_splits(const wh_session* s);

@@ -443,6 +443,12 @@ class Model:
             pass
 
 
+def xabsSupports(nState: int, nHead: int) -> bool:
+    """wh_xabs_supports (host only, no GPU): can a model of this decoder width and head count run the weight-absorbed cross-attention
+    (Session(..., crossAttentionMode=1))?  True for 384 x 6, 512 x 8, 768 x 12, 1024 x 16 and 1280 x 20, False otherwise."""
+    return bool(L.load().wh_xabs_supports(int(nState), int(nHead)))
+
+
 class Session:
     """Per-task state for up to `maxBatch` windows in flight (= DecodingInputs x maxBatch, one HIP stream)."""
 
@@ -450,7 +456,8 @@ class Session:
 
     def __init__(self, model: Model, maxBatch: int = 1, crossAttentionMode: Optional[int] = None, crossAttentionSplits: Optional[int] = None,
                  crossAttentionSlotsPerWorkgroup: Optional[int] = None, encoderPrecision: Optional[str] = None):
-        """crossAttentionMode: None = the library's choice (absorbed from `xabsAutoMinSlots()` = 28 slots at the widths that support it: the
+        """crossAttentionMode: None = the library's choice (absorbed from `xabsAutoMinSlots()` = 28 slots at the widths 512 / 768 / 1024 / 1280;
+        at 384 - tiny, tiny.en - always the K / V rows: the absorbed form runs there too, `xabsSupports`, but only when asked for with 1; the
         choice looks at maxBatch only, so Session(m, 27) and Session(m, 28) run different kernels; both meet the 1e-3 relative logits
         contract), 0 = per-layer cross K / V rows (24-bit: Float16 + 8-bit residual), 1 = weight-absorbed cross-attention over the encoder output (csrc/xabs.hip).
         Beam search (decodeTextBeam, DecodingOptions.beamSize) takes the library's choice like any other session: the beams of an audio
@@ -499,6 +506,12 @@ class Session:
         """key splits per slot an absorbed session of maxBatch slots gets when crossAttentionSplits is None: slots x splits within one round of the 256 CUs
         (4 up to 64 slots, 3 up to 85, 2 up to 128, 1 beyond; beam-search callers ask for 4, callers with several sessions in flight for half of it)"""
         return int(L.load().wh_xabs_auto_splits(int(maxBatch)))
+
+    @staticmethod
+    def xabsSupports(nState: int, nHead: int) -> bool:
+        """True when a model of this decoder width and head count can run crossAttentionMode=1: the five Whisper widths 384 / 512 / 768 / 1024 / 1280
+        with heads of 64 channels (6 / 8 / 12 / 16 / 20).  At 384 (tiny, tiny.en) the absorbed form is opt-in: crossAttentionMode=None keeps the K / V rows."""
+        return xabsSupports(nState, nHead)
 
     @property
     def crossAttentionSlotsPerWorkgroup(self) -> int:

@@ -442,7 +442,7 @@ extern "C" int wh_session_create_with_options(wh_model* m, int max_batch, const 
         return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_create: encoder_precision 1 (split) needs the K / V-row cross-attention (cross_attention_mode -1 or 0): "
                          "the absorbed kernel streams the Float16 encoder output, and a hi | lo stream would double its bytes");
     if (cross_attention_mode == 1 && m && !xabs_supported(m->dims.n_text_state, m->dims.n_text_head))
-        return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_create: the absorbed cross-attention needs a model width of 512 / 768 / 1024 / 1280 (this model: %d)", m->dims.n_text_state);
+        return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_create: the absorbed cross-attention needs a model width of 384 / 512 / 768 / 1024 / 1280 (this model: %d)", m->dims.n_text_state);
     // a split session resolves the automatic cross-attention choice to the K / V rows (their projection reads the split encoder output)
     return session_create_impl(m, max_batch, opt->encoder_precision == 1 ? 0 : cross_attention_mode, cross_attention_splits,
                                opt->cross_attention_slots_per_workgroup, out, opt->encoder_precision);
@@ -502,10 +502,16 @@ static int session_create_impl(wh_model* m, int max_batch, int cross_attention_m
     // it pays from about kXabsAutoMinSlots slots (three launches per layer instead of one, one workgroup per (slot, key split) and CU;
     // profiles/r04*, r05*).  Both modes meet the 1e-3 relative logits contract against fp32 (the K / V rows carry 19 mantissa bits since round 5: kernels.h hr24).
     // WH_XABS=0 / 1 forces the choice (A/B, tests), WH_XABS_MIN_SLOTS moves the automatic threshold.
+    // Two predicates: xabs_supported = the path can run (what an explicit cross_attention_mode 1 needs), xabs_auto_width = the automatic
+    // choice and WH_XABS may pick it.  They differ at d = 384 (tiny / tiny.en), where the absorbed form is opt-in: without an explicit
+    // mode such a session keeps the K / V rows at every max_batch.
     {
         const char* e_ = getenv("WH_XABS");       // read per session: a process can hold sessions of both modes (tests, A/B)
-        const int xabs_mode = cross_attention_mode >= 0 ? cross_attention_mode : (e_ ? atoi(e_) : -1);
-        s->use_xabs = xabs_supported((int)d, (int)H) && (xabs_mode < 0 ? max_batch >= wh_xabs_auto_min_slots() : xabs_mode != 0);
+        if (cross_attention_mode >= 0) s->use_xabs = cross_attention_mode != 0 && xabs_supported((int)d, (int)H);
+        else {
+            const int xabs_mode = e_ ? atoi(e_) : -1;
+            s->use_xabs = xabs_auto_width((int)d, (int)H) && (xabs_mode < 0 ? max_batch >= wh_xabs_auto_min_slots() : xabs_mode != 0);
+        }
         if (s->use_xabs) { const int r_ = build_xabs(m); if (r_) { wh_session_destroy(s); return r_; } }
     }
     if (s->use_xabs) {
@@ -586,6 +592,8 @@ extern "C" int wh_session_cross_attention_splits(const wh_session* s) { return s
 extern "C" int wh_session_cross_attention_slots_per_workgroup(const wh_session* s) { return s ? (s->use_xabs ? s->xabs.spw : 0) : -1; }
 // key splits per slot an absorbed session of max_batch slots gets when the caller asks for none (xabs.hip xabs_auto_splits)
 extern "C" int wh_xabs_auto_splits(int max_batch) { return wh::xabs_auto_splits(max_batch); }
+// 1 when a model of this decoder width and head count can run the absorbed cross-attention (cross_attention_mode = 1)
+extern "C" int wh_xabs_supports(int n_state, int n_head) { return wh::xabs_supported(n_state, n_head) ? 1 : 0; }
 // slots from which wh_session_create picks the absorbed cross-attention on its own (models whose width supports it)
 extern "C" int wh_xabs_auto_min_slots(void) {
     const char* e = getenv("WH_XABS_MIN_SLOTS");

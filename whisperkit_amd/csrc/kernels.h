@@ -329,7 +329,8 @@ struct XabsArgs {
     int* gate;                       // cross-attention gate (dec_shared.h, WH_XATT_GATE=1): xabs_qk takes it, xabs_attn's last workgroup returns it
     int spw;                         // xabs_attn: slots per workgroup (round 6): the launch has ceil(batch / spw) x n_split workgroups, each streams its slots one after the other
 };
-bool xabs_supported(int d, int n_head);
+bool xabs_supported(int d, int n_head);     // the path can run: d = 384 / 512 / 768 / 1024 / 1280 with heads of 64 channels
+bool xabs_auto_width(int d, int n_head);    // ... and the automatic choice / WH_XABS may pick it: not at d = 384, where it is opt-in
 void xabs_tile_wk(const f16* Wk, int d, int H, f16* out, hipStream_t st);
 void launch_xabs_qk(const XabsArgs& a, int n_bt, hipStream_t st);
 void launch_xabs_attn(const XabsArgs& a, hipStream_t st);

@@ -13,7 +13,7 @@
 //
 //   xabs_qk     Q'[slot][head][c] = sum_j W_k[h 64 + j][c] q[slot][h 64 + j]     (batch tile = N side, W_k^T tiles pre-tiled at load)
 //   xabs_attn   one workgroup per (slot, key split): the split's encoder rows stream through an LDS ring by LDS-DMA (16-key tiles as
-//               two 8-key half tiles of 20 KB at d = 1280, ring of 7 halves); per tile S^T = enc Q'^T on v_mfma_f32_16x16x32_f16 (the 8 waves split the channels,
+//               two 8-key half tiles of 20 KB at d = 1280, ring of 7 halves); per tile S^T = enc Q'^T on v_mfma_f32_16x16x32_f16 (the 8 waves - 4 at d = 384 - split the channels,
 //               partial tiles meet in LDS), online softmax with a deferred running maximum, P^T (f16) back through LDS,
 //               O'^T += enc^T P^T on v_mfma_f32_32x32x16_f16 with the enc^T operand read by ds_read_b64_tr_b16; the split's
 //               unnormalised O' [head][c] and (m, l) go to a partial buffer
@@ -57,14 +57,15 @@ void xabs_tile_wk(const f16* Wk, int d, int H, f16* out, hipStream_t st) {
 }
 
 // ---------------------------------------------------------------------------------------------- xabs_qk
-// grid (d / 256, H, n_bt), 4 waves, wave w: row tiles (blockIdx.x 4 + w) 2 + {0, 1}.  Output rows of d channels, f16, z ~ hi + lo / 2048:
+// grid (d / (64 WPB), H, n_bt), WPB waves (4; 2 at d = 384, whose 12 row tiles are 3 workgroups of 2 waves), wave w: row tiles
+// (blockIdx.x WPB + w) 2 + {0, 1}.  Output rows of d channels, f16, z ~ hi + lo / 2048:
 //     qf_hi[slot][row 0..15]  = hi of heads 0..15        qf_lo[slot][row 0..15] = lo of heads 0..15
 //     qf_hi[slot][row 16..23] = hi of heads 16..23       qf_hi[slot][row 24..31] = lo of heads 16..23        (NHT = 2 only)
 // i.e. the second head tile of a 20-head model is PACKED: its (at most 8) real heads carry hi and lo in ONE 16-row tile, so the S phase
 // of xabs_attn spends 3 MFMAs per k-step (tile 0 hi, tile 0 lo, tile 1 hi | lo) instead of 4 and keeps 60 instead of 80 fragment
 // registers.  A wave writes whole 128-byte lines; xabs_attn gathers its S-phase B fragments (lane = row | k group << 4, 8 channels
 // ks 32 + 8 kg + 0..7) with 64 contiguous bytes per row and k-step.
-template <int NHT>
+template <int NHT, int WPB = 4>
 __global__ __launch_bounds__(256, 2) void xabs_qk_kernel(const XabsArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int h = blockIdx.y, bt = blockIdx.z;
@@ -86,7 +87,7 @@ __global__ __launch_bounds__(256, 2) void xabs_qk_kernel(const XabsArgs a) {
     }
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-        const int rt = (blockIdx.x * 4 + wave) * 2 + s;
+        const int rt = (blockIdx.x * WPB + wave) * 2 + s;
         const u32x4* wp = reinterpret_cast<const u32x4*>(a.wkT) + ((size_t)(h * RT + rt) * 4) * 64 + lane;
         u32x4 w[4];
 #pragma unroll
@@ -141,7 +142,7 @@ __global__ __launch_bounds__(256, 2) void xabs_qk_kernel(const XabsArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------- S-phase fragments (shared)
-// The Q' slice of one wave (k-steps wave CW + j) as B fragments of v_mfma_f32_16x16x32_f16: tile 0 hi, tile 0 lo, packed tile 1.
+// The Q' slice of one wave (k-steps wave KSW + j) as B fragments of v_mfma_f32_16x16x32_f16: tile 0 hi, tile 0 lo, packed tile 1.
 template <int KSW, int NHT>
 struct XabsQFrag { f16x8 h0[KSW], l0[KSW], p1[NHT == 2 ? KSW : 1]; };
 template <int KSW, int NHT>
@@ -183,20 +184,34 @@ __device__ __forceinline__ void xabs_s_tile(const f16x8 (&af)[KSW], const XabsQF
 constexpr int kXabsHalves = 7;               // LDS ring of half tiles (8 keys): tiles i, i + 1 resident, i + 2 and half of i + 3 in flight
 constexpr int kXabsSpStride = 32 * 17;       // floats per wave partial: [32 heads][16 keys + 1]
 constexpr float kXabsDefer = 8.0f;           // the running maximum moves only when it would grow by more than this (p <= e^8 fits f16)
-__host__ __device__ constexpr int xabs_lds_bytes(int cw) { return kXabsHalves * cw * 4096 + 8 * kXabsSpStride * 4 + 1024 + 128; }
+// ring of half tiles (8 keys x nw ksw 64 bytes) + one partial S tile per wave + P^T + rescale factors
+__host__ __device__ constexpr int xabs_lds_bytes_w(int nw, int ksw) { return kXabsHalves * 8 * nw * ksw * 64 + nw * kXabsSpStride * 4 + 1024 + 128; }
+__host__ __device__ constexpr int xabs_lds_bytes(int cw) { return xabs_lds_bytes_w(8, cw); }
 
 // (Round 5, measured and rejected, profiles/r05b_xabs_attn_l2_prefetch_ab_rejected.jsonl: an L2 PREFETCH ahead of the LDS ring - with every
 // tile request a wave also touched one word of every 128-byte line of the half tile 2 or 3 tiles further on, a `buffer_load_dword ... lds`
 // gather into a landing pad nobody reads, so that the ring's own requests become L2 hits and more than the ring's 60 KB per CU are in
 // flight.  82.2 -> 92.3 us at 64 slots x 2 splits, 150.5 -> 172.5 us at 128 slots x 1 split, 2612 -> 2470 audio-s/s in flight: the CU's
 // share of the stream is not bounded by the bytes it has in flight (latency), the extra requests compete for the same fetch path.)
-template <int CW, int NHT, bool DBG, bool NTL>
-__global__ __launch_bounds__(512, 2) void xabs_attn_kernel(const XabsArgs a) {
-    constexpr int D = CW * 256, ROWB = D * 2, HALF = 8 * ROWB;
+//
+// NW waves split the channels, KSW k-steps (32 channels) each: D = NW KSW 32.  The widths that are multiples of 256 run 8 waves with
+// KSW = D / 256 (xabs_attn_kernel<CW, ...>, NW defaulted: the same code as before the parameter existed); d = 384 = 12 k-steps runs
+// 4 waves of 3 (xabs_attn_kernel<3, 1, ..., 4>): k-steps, P V row tiles and the 1 KB LDS-DMA pieces of a half tile (KSW per wave) then
+// all come out even, and the 4 waves own the softmax of 16 heads (one head tile).  The row size stays a multiple of 256 bytes (768), so
+// every tile row starts at LDS bank 0 and the xswz chunk swizzle decides the banks exactly as at the other widths.  At KSW = 3, NW = 4:
+// 52 864 bytes of LDS (ring 7 x 6 KB), no scratch (registers: DESIGN 3.4).
+template <int KSW, int NHT, bool DBG, bool NTL, int NW = 8>
+__global__ __launch_bounds__(NW * 64, 2) void xabs_attn_kernel(const XabsArgs a) {
+    static_assert(NW == 8 || NW == 4, "the waves split the channels: 8, or 4 at d = 384");
+    static_assert(4 * NW >= 16 * NHT, "4 softmax-owner heads per wave");
+    constexpr int CW = KSW;                  // k-steps = P V row tiles = LDS-DMA pieces per wave and tile
+    constexpr int HWSH = NW == 8 ? 2 : 1, HW = NW / 2;      // waves per half tile (and its log2)
+    constexpr int D = NW * KSW * 32, ROWB = D * 2, HALF = 8 * ROWB;
+    static_assert(HALF == HW * CW * 1024, "a half tile is HW x CW pieces of 1 KB");
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
     float* spart = reinterpret_cast<float*>(smem + kXabsHalves * HALF);
-    f16* pfrag = reinterpret_cast<f16*>(smem + kXabsHalves * HALF + 8 * kXabsSpStride * 4);
-    float* alpha_l = reinterpret_cast<float*>(smem + kXabsHalves * HALF + 8 * kXabsSpStride * 4 + 1024);
+    f16* pfrag = reinterpret_cast<f16*>(smem + kXabsHalves * HALF + NW * kXabsSpStride * 4);
+    float* alpha_l = reinterpret_cast<float*>(smem + kXabsHalves * HALF + NW * kXabsSpStride * 4 + 1024);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // provably wave-uniform: no waterfall loops around the buffer resource / M0
     // workgroup id -> (split, slot): id % 8 is the XCD; an XCD takes whole groups of 4 consecutive slots of one split, whose 32-byte
@@ -223,10 +238,10 @@ __global__ __launch_bounds__(512, 2) void xabs_attn_kernel(const XabsArgs a) {
     const unsigned char* enc = reinterpret_cast<const unsigned char*>(a.enc + (size_t)bc * kCtx * D);
 
     // ---- LDS-DMA: a 16-key tile is two half tiles of 8 keys; half k (= 2 tile + {0, 1}) lives in ring slot k % 7.  Waves 0-3 fetch the
-    // first half of a tile, waves 4-7 the second (CW pieces of 1 KB each per wave and tile): the two halves of a tile can be requested
+    // first half of a tile, waves 4-7 the second (of 4 waves: 0-1 and 2-3; CW pieces of 1 KB each per wave and tile): the two halves of a tile can be requested
     // at different times, so that a freed tile (two slots) is refilled with the second half of tile i + 3 and the first half of
     // tile i + 4 - the fetch pipe of the CU (~11 B / clk: the bound of this kernel) always has a request queued behind the one it waits for.
-    const int half_w = wave >> 2, wq = wave & 3;
+    const int half_w = wave >> HWSH, wq = wave & (HW - 1);
     int p_off[CW];                       // byte offset of this lane's 16 bytes inside a tile's rows (loop-invariant)
 #pragma unroll
     for (int p = 0; p < CW; ++p) {
@@ -276,7 +291,8 @@ __global__ __launch_bounds__(512, 2) void xabs_attn_kernel(const XabsArgs a) {
     if (n > 2) issue(2);
     if (n > 3 && half_w == 0) issue(3);
     if (tid < 32) alpha_l[tid] = 1.0f;
-    pfrag[tid] = (f16)0.0f;
+    if constexpr (NW == 8) pfrag[tid] = (f16)0.0f;
+    else reinterpret_cast<unsigned*>(pfrag)[tid] = 0u;            // 256 lanes clear the 512 entries (heads 16 .. 31 stay 0)
     if (!(s_act && !s_done)) {           // workgroup-uniform: a finished slot streams nothing more
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         continue;
@@ -319,11 +335,11 @@ __global__ __launch_bounds__(512, 2) void xabs_attn_kernel(const XabsArgs a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) wpart[(ht * 16 + (lane & 15)) * 17 + 4 * (lane >> 4) + r] = sreg[ht * 4 + r];
     };
-    // the owner lane of (key, head): sum of the 8 channel-slice partials, online softmax with a deferred running maximum
+    // the owner lane of (key, head): sum of the NW channel-slice partials, online softmax with a deferred running maximum
     auto softmax = [&](int i) {
         float s = 0.0f;
 #pragma unroll
-        for (int v = 0; v < 8; ++v) s += spart[v * kXabsSpStride + o_head * 17 + o_key];
+        for (int v = 0; v < NW; ++v) s += spart[v * kXabsSpStride + o_head * 17 + o_key];
         const int t = (tile_lo + i) * 16 + o_key;
         const bool valid = t < kCtx;
         if (raw && valid) raw[t] = s;                 // alignment heads: DecodingCache.alignmentWeights row tokenIndex + 1 (raw scores)
@@ -590,7 +606,11 @@ __global__ __launch_bounds__(256, 1) void xabs_vup_kernel(const XabsArgs a, int 
 // ---------------------------------------------------------------------------------------------- launchers
 static int xabs_env(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 
-bool xabs_supported(int d, int n_head) { return d % 256 == 0 && d >= 512 && d <= 1280 && n_head <= 32; }
+// "can run": the five Whisper widths, heads of 64 channels.  "is picked automatically" is the narrower xabs_auto_width: at d = 384 the
+// absorbed form is opt-in (cross_attention_mode = 1) until a measurement decides otherwise, so the automatic choice and WH_XABS keep
+// giving tiny / tiny.en sessions the K / V rows.
+bool xabs_supported(int d, int n_head) { return (d == 384 || (d % 256 == 0 && d >= 512 && d <= 1280)) && n_head <= 32 && n_head * 64 == d; }
+bool xabs_auto_width(int d, int n_head) { return xabs_supported(d, n_head) && d >= 512; }
 
 // Automatic key splits per slot (a constant of the session): as many as keep slots x splits workgroups within ONE round of the chip's 256 CUs, at most kXabsSplits.
 // Up to round 6 the choice was 4 whatever the batch; one large-v3 session alone, ms per decoder step at 4 / 3 / 2 / 1 splits (profiles/r06ah_lone_session_key_splits.jsonl):
@@ -609,6 +629,7 @@ int xabs_splits(int max_batch) {
 
 void launch_xabs_qk(const XabsArgs& a, int n_bt, hipStream_t st) {
     ProfScope ps_(KK_DEC_XQK, st);
+    if (a.d == 384) { xabs_qk_kernel<1, 2><<<dim3(3, a.n_head, n_bt), 128, 0, st>>>(a); return; }       // 12 row tiles: 3 workgroups of 2 waves
     const dim3 grid(a.d / 256, a.n_head, n_bt);
     if (a.n_head > 16) xabs_qk_kernel<2><<<grid, 256, 0, st>>>(a);
     else xabs_qk_kernel<1><<<grid, 256, 0, st>>>(a);
@@ -623,19 +644,34 @@ static void launch_attn_k(const XabsArgs& a, hipStream_t st) {
     const int n_grp = (b1 + 3) / 4 * a.n_split;             // (split, 4 slots) groups, 8 of them (one per XCD) to every 32 workgroup ids
     xabs_attn_kernel<CW, NHT, DBG, NTL><<<dim3((unsigned)((n_grp + 7) / 8 * 32)), 512, lds, st>>>(a);
 }
+template <int KSW, bool DBG, bool NTL>
+static void launch_attn_w4_k(const XabsArgs& a, hipStream_t st) {
+    constexpr int lds = xabs_lds_bytes_w(4, KSW);
+    static PerDeviceOnce once;
+    once.run([] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&xabs_attn_kernel<KSW, 1, DBG, NTL, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, lds); });
+    const int spw = a.spw > 1 ? a.spw : 1, b1 = (a.batch + spw - 1) / spw;
+    const int n_grp = (b1 + 3) / 4 * a.n_split;
+    xabs_attn_kernel<KSW, 1, DBG, NTL, 4><<<dim3((unsigned)((n_grp + 7) / 8 * 32)), 256, lds, st>>>(a);
+}
+// CW = 0: the 4-wave form of d = 384
+template <int CW, int NHT, bool DBG, bool NTL>
+static void launch_attn_any(const XabsArgs& a, hipStream_t st) {
+    if constexpr (CW == 0) launch_attn_w4_k<3, DBG, NTL>(a, st); else launch_attn_k<CW, NHT, DBG, NTL>(a, st);
+}
 template <int CW, int NHT>
 static void launch_attn_t(const XabsArgs& a, hipStream_t st) {
     static const int nt = xabs_env("WH_XABS_NT", 1);          // non-temporal policy on the encoder-output stream (in flight: 19.2 k vs 18.1 k sequence-steps/s, profiles/r04l_*); 0 = A/B side
     static const int ablate = xabs_env("WH_XABS_ABLATE", 0);  // timing probe (garbage results): 1 no LDS-DMA in the loop, 2 no S / softmax / P V work, 3 both
-    if (a.dbg || ablate) { XabsArgs b = a; b.ablate = ablate; launch_attn_k<CW, NHT, true, false>(b, st); return; }      // the stamped instantiation (tools/xabs_timeline.py)
+    if (a.dbg || ablate) { XabsArgs b = a; b.ablate = ablate; launch_attn_any<CW, NHT, true, false>(b, st); return; }      // the stamped instantiation (tools/xabs_timeline.py)
     // beam search (cross_div > 1: the beams of an audio read ONE encoder output): cacheable loads - the workgroups of an audio's beams are
     // dispatched back to back onto one XCD (4 consecutive slots per group) and the later ones are meant to hit the first one's lines in its L2
-    if (nt && a.cross_div <= 1) launch_attn_k<CW, NHT, false, true>(a, st); else launch_attn_k<CW, NHT, false, false>(a, st);
+    if (nt && a.cross_div <= 1) launch_attn_any<CW, NHT, false, true>(a, st); else launch_attn_any<CW, NHT, false, false>(a, st);
 }
 void launch_xabs_attn(const XabsArgs& a, hipStream_t st) {
     ProfScope ps_(KK_DEC_CROSS_ATTN, st);
     const bool two = a.n_head > 16;
     switch (a.d / 256) {
+        case 1: launch_attn_t<0, 1>(a, st); break;          // d = 384 (xabs_supported: no other width below 512)
         case 2: two ? launch_attn_t<2, 2>(a, st) : launch_attn_t<2, 1>(a, st); break;
         case 3: two ? launch_attn_t<3, 2>(a, st) : launch_attn_t<3, 1>(a, st); break;
         case 4: two ? launch_attn_t<4, 2>(a, st) : launch_attn_t<4, 1>(a, st); break;
@@ -645,11 +681,13 @@ void launch_xabs_attn(const XabsArgs& a, hipStream_t st) {
 
 void launch_xabs_vup(const XabsArgs& a, int n_bt, hipStream_t st) {
     ProfScope ps_(KK_DEC_XVUP, st);
-    // K slices: d / 16 k tiles over 4 waves x ks workgroups, TW tiles per wave; ks = 4 at every supported width (TW = d / 256)
-    constexpr int ks = 4;
+    // K slices: d / 16 k tiles over 4 waves x ks workgroups, TW tiles per wave; ks = 4 at the widths that are multiples of 256 (TW = d / 256),
+    // d = 384: 24 k tiles = 3 slices x 4 waves x 2 tiles
+    const int ks = a.d == 384 ? 3 : 4;
     const int nx = a.n_head * ks;
     const unsigned grid = (unsigned)(((nx + 7) / 8) * 8 * n_bt);
 #define XVUP(S_) do { switch (a.d / 256) { \
+        case 1: xabs_vup_kernel<S_, 2><<<grid, 256, 0, st>>>(a, ks, n_bt); break; \
         case 2: xabs_vup_kernel<S_, 2><<<grid, 256, 0, st>>>(a, ks, n_bt); break; \
         case 3: xabs_vup_kernel<S_, 3><<<grid, 256, 0, st>>>(a, ks, n_bt); break; \
         case 4: xabs_vup_kernel<S_, 4><<<grid, 256, 0, st>>>(a, ks, n_bt); break; \
