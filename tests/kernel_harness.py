@@ -1,7 +1,8 @@
 """ctypes side of tests/native/kernel_harness.hip (one launcher of csrc/kernels.h per call, host buffers in and out, guard bands and
-poison) and a Python restatement of the launchers' kernel choice (csrc/gemm.hip launch_epi / launch_split, csrc/layernorm.hip
-launch_layernorm) that labels every case with the kernel it is meant to reach.  Used by tests/test_gpu_kernels.py (device) and
-tests/test_kernel_harness.py (CPU: build, exports, predicates)."""
+poison) and a Python restatement of the launchers' kernel choice (csrc/launch_plan.h gemm_plan / layernorm_plan, the functions
+csrc/gemm.hip launch_epi and csrc/layernorm.hip launch_layernorm switch on) that labels every case with the kernel it is meant to reach;
+plan_check_build / plan_check_run put the real planners behind it (tests/native/launch_plan_check.cpp, g++).  Used by
+tests/test_gpu_kernels.py (device) and tests/test_kernel_harness.py, tests/test_launch_plan.py (CPU: build, exports, predicates)."""
 import ctypes as C
 import os
 import subprocess
@@ -45,6 +46,32 @@ def build(outdir):
                     "-I", os.path.join(ROOT, "whisperkit_amd", "csrc"), "-I", os.path.join(ROOT, "include"), SRC,
                     "-L", LIBDIR, "-lwhisperhip", "-Wl,-rpath," + LIBDIR, "-o", lib], check=True)
     return lib
+
+
+def plan_check_build(outdir):
+    """g++ tests/native/launch_plan_check.cpp against csrc/launch_plan.h and csrc/knobs.h; returns the program's path"""
+    exe = os.path.join(str(outdir), "launch_plan_check")
+    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "whisperkit_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "native", "launch_plan_check.cpp"), "-o", exe], check=True)
+    return exe
+
+
+def plan_check_run(exe, lines):
+    """one request line in, one answer line out (the protocol: the head of launch_plan_check.cpp)"""
+    lines = list(lines)
+    out = subprocess.run([exe], input="".join(l + "\n" for l in lines), capture_output=True, text=True)
+    got = out.stdout.splitlines()
+    assert out.returncode == 0 and len(got) == len(lines) and not any(g.startswith("ERROR") for g in got), (out.stdout[-2000:], out.stderr[-2000:])
+    return got
+
+
+def gemm_request(M, N, K, lda=None, a_batch_stride=0, ldc=None, d_model=0, epi=EPI_F16, split=False, out_align=16, epi_mode=1):
+    """the launch_plan_check line of gemm_path's arguments: an output base that out_align divides and 2 out_align does not; no persistent loop"""
+    return f"gemm {M} {N} {K} {K if lda is None else lda} {a_batch_stride} {N if ldc is None else ldc} {d_model} {epi} {int(split)} {out_align} {epi_mode} 0 0 0 256"
+
+
+def layernorm_request(d, x_align=16, gb_align=16, y32_align=16, y16_align=8, lo_align=8, has_lo=False, v4=2):
+    return f"ln {d} {x_align | gb_align | y32_align} {y16_align} {lo_align if has_lo else 0} {int(has_lo)} {v4}"
 
 
 class Harness:
@@ -100,9 +127,9 @@ class Harness:
 
 
 # ---------------------------------------------------------------------------------------------- the launchers' kernel choice, restated
-def gemm_path(M, N, K, lda=None, a_batch_stride=0, ldc=None, d_model=0, epi=EPI_F16, split=False, out_align=16):
-    """The kernel launch_epi (split=False) / launch_split (split=True) picks with the default environment (WH_GEMM_EPI_MODE = 1,
-    no persistent loop).  out_align: the largest power of two (<= 16) that divides every output base address."""
+def gemm_path(M, N, K, lda=None, a_batch_stride=0, ldc=None, d_model=0, epi=EPI_F16, split=False, out_align=16, epi_mode=1):
+    """The kernel launch_epi picks for the Float16 (split=False) / split (split=True) A operand with the default environment
+    (epi_mode = WH_GEMM_EPI_MODE = 1, no persistent loop).  out_align: the largest power of two (<= 16) that divides every output base address."""
     lda = K if lda is None else lda
     ldc = N if ldc is None else ldc
     tiles256 = -(-M // 256) * -(-N // 256)
@@ -110,18 +137,21 @@ def gemm_path(M, N, K, lda=None, a_batch_stride=0, ldc=None, d_model=0, epi=EPI_
     if tiles256 >= 64 and K % kt == 0 and lda % 8 == 0 and a_batch_stride % 8 == 0 and N % 4 == 0:
         name = "gemm256_split_kernel" if split else "gemm256_kernel"
         staged = (epi in STAGED_EPIS and out_align % 16 == 0 and N % 64 == 0 and M % 4 == 0 and ldc % 8 == 0 and d_model % 64 == 0)
-        return f"{name}<mode {1 if staged else 0}>"
+        return f"{name}<mode {epi_mode if staged and epi_mode in (1, 2) else 0}>"
     tiles128 = -(-M // 128) * -(-N // 128)
     name = "gemm_split_kernel" if split else "gemm_kernel"
     return f"{name}<128,128>" if tiles128 >= 192 else f"{name}<64,64>"
 
 
-def layernorm_path(d, x_align=16, gb_align=16, y32_align=16, y16_align=8, lo_align=8, has_lo=False):
-    """The kernel launch_layernorm picks with the default environment (WH_LN_V4 = 2: the non-temporal vector form)"""
+def layernorm_path(d, x_align=16, gb_align=16, y32_align=16, y16_align=8, lo_align=8, has_lo=False, v4=2):
+    """The kernel launch_layernorm picks with the default environment (v4 = WH_LN_V4 = 2: the non-temporal vector form; 1: the plain
+    vector form; 0: the scalar kernel)"""
     aligned = d % 4 == 0 and min(x_align, gb_align, y32_align) % 16 == 0 and y16_align % 8 == 0
     if has_lo:
         aligned = aligned and lo_align % 8 == 0
-    return "layernorm_v4_kernel<NT>" if aligned else "layernorm_kernel"
+    if not aligned or v4 == 0:
+        return "layernorm_kernel"
+    return "layernorm_v4_kernel<NT>" if v4 == 2 else "layernorm_v4_kernel"
 
 
 def encoder_shapes(dims, batch):

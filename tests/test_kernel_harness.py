@@ -1,9 +1,9 @@
 """CPU checks of the kernel-level test harness (tests/native/kernel_harness.hip, tests/kernel_harness.py): it builds against the in-tree
 library, exports its entry points, fails with a HIP status instead of crashing where there is no GPU, and its restatement of the
-launchers' kernel choice agrees with csrc/gemm.hip / csrc/layernorm.hip on the production shapes of every preset.  The device side:
+launchers' kernel choice agrees with csrc/launch_plan.h (the planners csrc/gemm.hip / csrc/layernorm.hip switch on) on the production
+shapes of every preset and on every case of the device tests.  The device side:
 tests/test_gpu_kernels.py."""
 import os
-import re
 
 import numpy as np
 import pytest
@@ -39,17 +39,93 @@ def test_harness_returns_a_hip_status_instead_of_crashing(kh):
         assert status != 0
 
 
-def test_dispatch_restatement_matches_the_launcher_source():
-    """the predicates kernel_harness.gemm_path / layernorm_path restate, as they stand in the launchers"""
-    src = re.sub(r"\s+", " ", open(os.path.join(KH.ROOT, "whisperkit_amd", "csrc", "gemm.hip")).read())
-    assert "tiles256 >= 64 && a.K % 64 == 0 && a.lda % 8 == 0 && a.a_batch_stride % 8 == 0 && a.N % 4 == 0" in src
-    assert "tiles256 >= 64 && a.K % 32 == 0 && a.lda % 8 == 0 && a.a_batch_stride % 8 == 0 && a.N % 4 == 0" in src
-    assert src.count("shape_ok = aligned && a.N % 64 == 0 && a.M % 4 == 0 && a.ldc % 8 == 0 && a.d_model % 64 == 0") == 2
-    assert src.count("if (tiles128 >= 192)") == 2
-    assert "EPI == EPI_F16 || EPI == EPI_GELU_F16 || EPI == EPI_RESID_F32 || EPI == EPI_QKV_ENC" in src
-    ln = re.sub(r"\s+", " ", open(os.path.join(KH.ROOT, "whisperkit_amd", "csrc", "layernorm.hip")).read())
-    assert ("aligned = d % 4 == 0 && (((uintptr_t)x | (uintptr_t)g | (uintptr_t)b | (uintptr_t)y32) % 16) == 0 && "
-            "((uintptr_t)y16 % 8) == 0") in ln
+def _gpu_kernel_cases():
+    """(gemm_path keyword arguments, expected kernel or None) of every GEMM case tests/test_gpu_kernels.py constructs - read from its own
+    case lists and parametrize marks; the shapes are those its run_* helpers build - and the arguments of its LayerNorm cases"""
+    import test_gpu_kernels as G
+    CTX, FRAMES, FRAMES_PAD = KH.CTX, KH.FRAMES, KH.FRAMES_PAD
+
+    def params(fn):
+        return [m.args[1] for m in fn.pytestmark if m.name == "parametrize"]
+
+    def qkv(d, batch, off=0, split=False):
+        return dict(M=batch * CTX, N=3 * d, K=d, ldc=d, d_model=d, epi=EPI_QKV_ENC, split=split, out_align=16 if off % 16 == 0 else 8)
+
+    def conv1(n_mels, d, batch, split=False):
+        return dict(M=batch * FRAMES, N=d, K=3 * n_mels, lda=n_mels, a_batch_stride=FRAMES_PAD * n_mels, ldc=d, epi=EPI_CONV1, split=split)
+
+    def conv2(d, batch, split=False):
+        return dict(M=batch * CTX, N=d, K=3 * d, lda=2 * d, a_batch_stride=FRAMES_PAD * d, ldc=d, epi=EPI_CONV2, split=split)
+
+    def cross_kv(d, L, batch, split=False):
+        return dict(M=batch * CTX, N=L * 2 * d, K=d, ldc=L * 2 * d, d_model=d, epi=EPI_CROSS_KV, split=split)
+
+    gemms = []
+    for epi, M, N, K, ldc, off, split, expect in G.ROWMAJOR_CASES:      # thresholds one step either side, unaligned bases, ldc padding
+        gemms.append((dict(M=M, N=N, K=K, ldc=ldc, epi=epi, split=split, out_align=16 if off % 16 == 0 else 8), expect))
+    gemms += [(qkv(d, b, off), e) for d, b, off, e in params(G.test_gemm_qkv_enc_layout_vs_fp64)[0]]
+    gemms.append((qkv(768, 3, split=True), "gemm256_split_kernel<mode 1>"))
+    gemms += [(conv1(nm, d, b), e) for nm, d, b, e in params(G.test_gemm_conv1_view_vs_fp64)[0]]
+    gemms.append((conv1(128, 1280, 3, split=True), "gemm256_split_kernel<mode 0>"))
+    gemms += [(conv2(d, b), e) for d, b, e in params(G.test_gemm_conv2_view_vs_fp64)[0]]
+    gemms.append((conv2(1024, 3, split=True), "gemm256_split_kernel<mode 0>"))
+    gemms += [(cross_kv(d, 2, b), e) for d, b, e in params(G.test_gemm_cross_kv_vs_fp64)[0]]
+    gemms.append((cross_kv(768, 2, 3, split=True), "gemm256_split_kernel<mode 0>"))
+    gemms.append((cross_kv(384, 2, 1), "gemm_kernel<64,64>"))           # test_gemm_cross_kv_hr24_edges
+    for name, batch, which in G.PRODUCTION:
+        dims = weights.MODEL_DIMS[name]
+        _, epi, M, N, K, lda, stride = next(s for s in KH.encoder_shapes(dims, batch) if s[0] == which)
+        gemms.append((dict(M=M, N=N, K=K, lda=lda, a_batch_stride=stride, ldc=N, d_model=dims.n_audio_state if epi in (EPI_QKV_ENC, EPI_CROSS_KV) else 0, epi=epi), None))
+    for split in (False, True):                                          # test_gemm256_rows_equal_gemm64_rows_bit_for_bit
+        for epi in (EPI_F16, EPI_GELU_F16, KH.EPI_F32):
+            for M, align in ((4500, 16), (4500, 8), (1500, 16)):
+                gemms.append((dict(M=M, N=1536, K=1280, epi=epi, split=split, out_align=align), None))
+    lns = [dict(d=d, x_align=xa, has_lo=lo) for d in G.LN_WIDTHS for lo in (False, True) for xa in (16, 8)]
+    return gemms, lns
+
+
+def test_dispatch_restatement_matches_the_launch_planners(tmp_path):
+    """kernel_harness.gemm_path / layernorm_path against the functions the launchers switch on (csrc/launch_plan.h through
+    tests/native/launch_plan_check.cpp): every preset x batch x operand form, every case of tests/test_gpu_kernels.py, every epilogue mode
+    and every LayerNorm form"""
+    exe = KH.plan_check_build(tmp_path)
+    gemms, lns = _gpu_kernel_cases()
+    assert len(gemms) > 100 and len(lns) == 28
+    for name, dims in sorted(weights.MODEL_DIMS.items()):
+        for batch in (1, 3, 32):
+            for which, epi, M, N, K, lda, stride in KH.encoder_shapes(dims, batch):
+                for split in (False, True):
+                    gemms.append((dict(M=M, N=N, K=K, lda=lda, a_batch_stride=stride, ldc=N,
+                                       d_model=dims.n_audio_state if epi in (EPI_QKV_ENC, EPI_CROSS_KV) else 0, epi=epi, split=split), None))
+        d = dims.n_audio_state
+        lns += [dict(d=d), dict(d=d, has_lo=True), dict(d=d, x_align=8), dict(d=d, y16_align=4), dict(d=d, lo_align=4, has_lo=True), dict(d=d, gb_align=8),
+                dict(d=d, y32_align=4), dict(d=d, lo_align=4)]
+    lns += [dict(d=130), dict(d=66, has_lo=True)]                        # d % 4 != 0
+    asked, want = [], []
+    for kw, expect in gemms:
+        for epi_mode in (0, 1, 2):
+            asked.append(KH.gemm_request(epi_mode=epi_mode, **kw))
+            want.append(KH.gemm_path(epi_mode=epi_mode, **kw))
+            if expect is not None and epi_mode == 1:
+                assert want[-1].startswith(expect), (kw, want[-1], expect)
+    for kw in lns:
+        for v4 in (0, 1, 2):
+            asked.append(KH.layernorm_request(v4=v4, **kw))
+            want.append(KH.layernorm_path(v4=v4, **kw))
+    got = KH.plan_check_run(exe, asked)
+    for line, g, w in zip(asked, got, want):
+        assert (g.split(" grid ")[0] if line.startswith("gemm") else g) == w, (line, g, w)
+    assert {w for w in want if w.startswith("layernorm")} == {"layernorm_kernel", "layernorm_v4_kernel", "layernorm_v4_kernel<NT>"}
+    for fam in ("gemm256_kernel<mode 0>", "gemm256_kernel<mode 1>", "gemm256_kernel<mode 2>", "gemm256_split_kernel<mode 2>", "gemm_kernel<128,128>",
+                "gemm_split_kernel<64,64>"):
+        assert fam in want, fam
+    # the knobs the restatement leaves at their defaults: no 256 tile at all; the persistent loop for the Float16 operand form only, on
+    # min(WH_GEMM_PERSIST_WGS or the CUs, the tiles rounded up to 8) workgroups
+    big = "4500 1536 1280 1280 0 1536 0 0"
+    got = KH.plan_check_run(exe, [f"gemm {big} 0 16 1 1 0 0 256", f"gemm {big} 0 16 1 0 1 0 256", f"gemm {big} 1 16 1 0 1 0 256",
+                                  f"gemm {big} 0 16 1 0 1 64 256", f"gemm {big} 0 16 1 0 0 0 256", f"gemm {big} 0 8 2 0 1 0 256"])
+    assert got == ["gemm_kernel<128,128> grid 12 36", "gemm256p_kernel<mode 1> grid 112 1", "gemm256_split_kernel<mode 1> grid 108 1",
+                   "gemm256p_kernel<mode 1> grid 64 1", "gemm256_kernel<mode 1> grid 108 1", "gemm256p_kernel<mode 0> grid 112 1"]
 
 
 # hand-derived kernel choices (tiles256 = ceil(M / 256) ceil(N / 256), tiles128 likewise)

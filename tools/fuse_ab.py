@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """A/B of decoder launch variants (the WH_* knobs are read once per process, so each variant is its own process): prints an MD5 of the
-greedy tokens + log-probs of every slot and the single-stream decode time.   WH_XATT_PERSIST=2 python tools/fuse_ab.py large-v3 64"""
+greedy tokens + log-probs of every slot and the single-stream decode time.   WH_XATT_PASSES=6 python tools/fuse_ab.py large-v3 64
+(the knobs: whisperkit_amd/csrc/knobs.h)"""
 import hashlib, json, os, sys, time
 import numpy as np
 import torch  # noqa: F401  (bench.py's process set-up, see tools/time_decode.py)

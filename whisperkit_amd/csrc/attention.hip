@@ -14,6 +14,7 @@
 #include <cstdlib>
 
 #include "kernels.h"
+#include "knobs.h"
 
 namespace wh {
 
@@ -307,7 +308,7 @@ __global__ __launch_bounds__(256, 2) void encoder_attention_v2_kernel(const f16*
 
 void launch_encoder_attention(const f16* q16, const f16* k16, const f16* vt16, f16* out16, int batch, int n_head, int d, hipStream_t st, f16* out_lo) {
     ProfScope ps_(KK_ENC_ATTN, st);
-    static const bool v1 = [] { const char* e = getenv("WH_ENC_ATTN_V1"); return e && e[0] == '1'; }();     // A/B knob: the round-2 kernel
+    const bool v1 = knob::once<knob::WH_ENC_ATTN_V1>();     // A/B knob: the round-2 kernel
     if (v1) {
         dim3 g((kCtx + 127) / 128, n_head, batch);
         if (out_lo) encoder_attention_kernel<true><<<g, 256, 0, st>>>(q16, k16, vt16, out16, n_head, d, out_lo);

@@ -10,6 +10,7 @@
 #include <cstdlib>
 
 #include "internal.h"
+#include "knobs.h"
 
 using namespace wh;
 
@@ -456,11 +457,10 @@ extern "C" int wh_session_create_with_mode(wh_model* m, int max_batch, int cross
 // sessions in flight never wait for each other's workgroups (hipExtStreamCreateWithCUMask: "the first 32 bits represent the first 32 CUs").
 static hipError_t create_session_stream(hipStream_t* st) {
     static std::atomic<int> counter{0};
-    const char* e = getenv("WH_CU_PARTS");
-    const int parts = e ? atoi(e) : 0;
+    const int parts = knob::now<knob::WH_CU_PARTS>();
     // WH_STREAM_PRIORITIES = "p0,p1,..." (experiment, round 6): session k's stream gets hardware-queue priority p[k % n] (-1 high, 0 normal, 1 low) - a strict order
     // between the sessions in flight instead of the queues' round robin when their workgroups compete for the same CUs.
-    if (const char* pr = getenv("WH_STREAM_PRIORITIES")) {
+    if (const char* pr = knob::text<knob::WH_STREAM_PRIORITIES>()) {
         int p[8], n = 0;
         for (const char* c = pr; *c && n < 8;) { p[n++] = atoi(c); while (*c && *c != ',') ++c; if (*c == ',') ++c; }
         if (n > 0) return hipStreamCreateWithPriority(st, hipStreamNonBlocking, p[counter.fetch_add(1) % n]);
@@ -469,8 +469,7 @@ static hipError_t create_session_stream(hipStream_t* st) {
     int dev = 0, n_cu = 256;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
-    const char* x = getenv("WH_CU_PART_EXTRA");
-    const int extra = x ? atoi(x) : 0, k = counter.fetch_add(1) % parts, w = n_cu / parts;
+    const int extra = knob::now<knob::WH_CU_PART_EXTRA>(), k = counter.fetch_add(1) % parts, w = n_cu / parts;
     uint32_t mask[16] = {};
     for (int i = k * w; i < k * w + w + extra; ++i) { const int c = ((i % n_cu) + n_cu) % n_cu; mask[c >> 5] |= 1u << (c & 31); }
     return hipExtStreamCreateWithCUMask(st, (uint32_t)((n_cu + 31) / 32), mask);
@@ -506,10 +505,9 @@ static int session_create_impl(wh_model* m, int max_batch, int cross_attention_m
     // choice and WH_XABS may pick it.  They differ at d = 384 (tiny / tiny.en), where the absorbed form is opt-in: without an explicit
     // mode such a session keeps the K / V rows at every max_batch.
     {
-        const char* e_ = getenv("WH_XABS");       // read per session: a process can hold sessions of both modes (tests, A/B)
+        const int xabs_mode = knob::now<knob::WH_XABS>();       // read per session: a process can hold sessions of both modes (tests, A/B)
         if (cross_attention_mode >= 0) s->use_xabs = cross_attention_mode != 0 && xabs_supported((int)d, (int)H);
         else {
-            const int xabs_mode = e_ ? atoi(e_) : -1;
             s->use_xabs = xabs_auto_width((int)d, (int)H) && (xabs_mode < 0 ? max_batch >= wh_xabs_auto_min_slots() : xabs_mode != 0);
         }
         if (s->use_xabs) { const int r_ = build_xabs(m); if (r_) { wh_session_destroy(s); return r_; } }
@@ -525,7 +523,7 @@ static int session_create_impl(wh_model* m, int max_batch, int cross_attention_m
         s->xabs.layers_host = m->xabs.data();
         s->xabs.n_split = cross_attention_splits > 0 ? cross_attention_splits : xabs_splits(max_batch);
         s->xabs.spw = slots_per_workgroup > 0 ? slots_per_workgroup : 1;
-        { const char* e = getenv("WH_XABS_SPW"); const int v = e ? atoi(e) : 0; if (v >= 1 && v <= kXabsMaxSlotsPerWorkgroup) s->xabs.spw = v; }      // A/B override
+        if (const int v = knob::now<knob::WH_XABS_SPW>()) s->xabs.spw = v;      // A/B override (1 .. kXabsMaxSlotsPerWorkgroup)
         s->xabs.qf_hi = c.take<f16>(B * nht * (d / 32) * 512); s->xabs.qf_lo = c.take<f16>(B * nht * (d / 32) * 512);
         s->xabs.part = c.take<float>(S * H * (d / 8) * B * 8);
         s->xabs.ml = c.take<float2>(S * H * B);
@@ -595,11 +593,9 @@ extern "C" int wh_xabs_auto_splits(int max_batch) { return wh::xabs_auto_splits(
 // 1 when a model of this decoder width and head count can run the absorbed cross-attention (cross_attention_mode = 1)
 extern "C" int wh_xabs_supports(int n_state, int n_head) { return wh::xabs_supported(n_state, n_head) ? 1 : 0; }
 // slots from which wh_session_create picks the absorbed cross-attention on its own (models whose width supports it)
-extern "C" int wh_xabs_auto_min_slots(void) {
-    const char* e = getenv("WH_XABS_MIN_SLOTS");
-    const int v = e ? atoi(e) : 0;
-    return v > 0 ? v : wh::kXabsAutoMinSlots;
-}
+extern "C" int wh_xabs_auto_min_slots(void) { return knob::now<knob::WH_XABS_MIN_SLOTS>(); }      // (default kXabsAutoMinSlots)
+static_assert(knob::kTable[knob::WH_XABS_MIN_SLOTS].dflt == wh::kXabsAutoMinSlots && knob::kTable[knob::WH_XABS_SPW].hi == wh::kXabsMaxSlotsPerWorkgroup &&
+              knob::kTable[knob::WH_XABS_SPLITS].hi == wh::kXabsSplits, "knobs.h: the ranges of the absorbed cross-attention knobs");
 // Development aid: copy the first `nbytes` of a named decode-step buffer to the host (after the session's stream has drained).
 extern "C" int wh_debug_peek(wh_session* s, const char* name, void* out, size_t nbytes) {
     CHECK_SESSION(s);
@@ -806,7 +802,7 @@ DecodeBuffers decode_buffers(wh_session* s, int batch, int max_position) {
     db.d32 = &s->d32; db.x = s->d32.x; db.q = s->d32.q;
     if (s->use_xabs) { s->xabs.enc = s->enc16; db.xabs = &s->xabs; }
     // cross-attention gate: WH_XATT_GATE=0 never, 1 always, unset: while the model carries more than one session (dec_shared.h)
-    static const int gate_mode = [] { const char* e = getenv("WH_XATT_GATE"); return e ? atoi(e) : -1; }();
+    const int gate_mode = knob::once<knob::WH_XATT_GATE>();
     const bool gate_on = gate_mode < 0 ? kXattnGateDefault && m->n_sessions.load() > 1 : gate_mode != 0;
     db.xattn_gate = gate_on ? m->xattn_gate : nullptr;
     return db;

@@ -43,6 +43,7 @@
 #include <hip/hip_runtime.h>
 
 #include "internal.h"
+#include "knobs.h"
 
 using whi::set_error;
 
@@ -91,10 +92,7 @@ const RcclApi* rccl_api(std::string* why) {
 }
 
 // ---- TCP helpers (whole buffers; every socket carries SO_RCVTIMEO / SO_SNDTIMEO, so a dead peer is an error after the deadline)
-int comm_timeout_s() {
-    static const int t = [] { const char* e = getenv("WH_COMM_TIMEOUT_S"); const int v = e ? atoi(e) : 120; return v > 0 ? v : 120; }();
-    return t;
-}
+int comm_timeout_s() { return wh::knob::once<wh::knob::WH_COMM_TIMEOUT_S>(); }
 void set_deadlines(int fd, int seconds = 0) {
     timeval tv{};
     tv.tv_sec = seconds > 0 ? seconds : comm_timeout_s();
@@ -152,7 +150,7 @@ extern "C" int wh_comm_unique_id(int transport, const char* address, uint8_t* id
         return set_error(WH_ERR_INVALID_ARGUMENT, "wh_comm_unique_id: the TCP transport needs \"host:port\" of rank 0");
     std::string a(address);
     if (a.find('#') == std::string::npos) {          // the job's token: "host:port#token" from the caller, or WH_COMM_TOKEN from the launcher's environment
-        const char* t = getenv("WH_COMM_TOKEN");
+        const char* t = wh::knob::text<wh::knob::WH_COMM_TOKEN>();
         if (t && *t) { a += '#'; a.append(t, strnlen(t, 2 * kTokenBytes)); }
     }
     if (a.size() >= WH_COMM_ID_BYTES) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_comm_unique_id: address + token exceed %d bytes", WH_COMM_ID_BYTES - 1);

@@ -31,6 +31,7 @@
 #include <cstdlib>
 
 #include "dec_shared.h"
+#include "knobs.h"
 
 namespace wh {
 
@@ -775,13 +776,11 @@ __global__ void rules_init_kernel(const SamplerCfg* __restrict__ cfgp, SeqState*
 void launch_rules_init(const SamplerCfg* cfg_dev, SeqState* seq, int batch, hipStream_t st) { rules_init_kernel<<<batch, 64, 0, st>>>(cfg_dev, seq); }
 
 // ---------------------------------------------------------------------------------------------- launchers
-static int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 // WH_DBG=1 timeline probe buffer [KK_COUNT][4096][8], allocated once per process (thread-safe function-local static)
 unsigned long long* debug_buffer() {
     static unsigned long long* const buf = [] {
         unsigned long long* p = nullptr;
-        const char* e = getenv("WH_DBG");
-        if (e && e[0] == '1') {
+        if (knob::once<knob::WH_DBG>()) {
             const size_t bytes = (size_t)KK_COUNT * 4096 * 8 * 8;
             if (hipMalloc((void**)&p, bytes) != hipSuccess) p = nullptr;
             else (void)hipMemset(p, 0, bytes);
@@ -791,62 +790,32 @@ unsigned long long* debug_buffer() {
     return buf;
 }
 
-int cross_attn_splits(int batch, int n_head) {
-    // Keys per workgroup 256 / 128 / 64, chosen from the head count ONLY: the number of splits fixes the order in which the
-    // partial softmax sums are combined, so it must not depend on the batch - a slot decodes to the same bits alone or in a
-    // batch of 32 (tests/test_gpu_dims.py).  With >= 12 heads even a batch of 8 gives >= 576 workgroups at 6 splits
-    // (measured large-v3: 8 passes 53.0 us at 32 slots / 20.4 at 8; 12 passes 53.8 / 20.8; 16 passes 58.5 / 20.7).
-    (void)batch;
-    static const int forced = env_int("WH_XATT_PASSES", 0);     // tuning knob: 8 / 6 / 4 / 2
-    // measured large-v3, 64 slots (profiles/r03a_*): 6 passes (8 splits, 70 registers, 7 waves per SIMD) 5.20 ms per decoder step against
-    // 5.38 with 8 passes (6 splits, 87 registers); 1754 vs 1715 audio-s/s with three sessions in flight
-    // round 5: the rows are 24-bit (24 bytes per lane and key: a pass carries 1.5 x the bytes of a Float16 pass): 4 passes at >= 12 heads
-    // (48 KB in flight per workgroup; the round-3 choice of 6 Float16 passes held the same), 2 passes below
-    int passes = forced ? forced : (n_head >= 12 ? 4 : 2);
-    passes = passes > 6 ? 8 : passes > 4 ? 6 : passes > 2 ? 4 : 2;            // instantiated: 2 / 4 / 6 / 8 passes = 24 / 12 / 8 / 6 splits
-    return (kCtx + passes * 32 - 1) / (passes * 32);
-}
-
 static void launch_self_attn(const AttnArgs& at, int H, int B, hipStream_t st) {
     ProfScope ps_(KK_DEC_SELF_ATTN, st);
     const dim3 grid(H, B);
-    const int passes = at.self_rows > 0 ? (at.self_rows + 31) / 32 : 7;
-    if (at.self_owner) {
-        switch (passes) {
-            case 1: dec_self_attn_owner_kernel<1><<<grid, 256, 0, st>>>(at); break;
-            case 2: dec_self_attn_owner_kernel<2><<<grid, 256, 0, st>>>(at); break;
-            case 3: dec_self_attn_owner_kernel<3><<<grid, 256, 0, st>>>(at); break;
-            case 4: dec_self_attn_owner_kernel<4><<<grid, 256, 0, st>>>(at); break;
-            case 5: dec_self_attn_owner_kernel<5><<<grid, 256, 0, st>>>(at); break;
-            case 6: dec_self_attn_owner_kernel<6><<<grid, 256, 0, st>>>(at); break;
-            default: dec_self_attn_owner_kernel<7><<<grid, 256, 0, st>>>(at);
-        }
-        return;
-    }
-    switch (passes) {
-        case 1: dec_self_attn_kernel<1><<<grid, 256, 0, st>>>(at); break;
-        case 2: dec_self_attn_kernel<2><<<grid, 256, 0, st>>>(at); break;
-        case 3: dec_self_attn_kernel<3><<<grid, 256, 0, st>>>(at); break;
-        case 4: dec_self_attn_kernel<4><<<grid, 256, 0, st>>>(at); break;
-        case 5: dec_self_attn_kernel<5><<<grid, 256, 0, st>>>(at); break;
-        case 6: dec_self_attn_kernel<6><<<grid, 256, 0, st>>>(at); break;
-        default: dec_self_attn_kernel<7><<<grid, 256, 0, st>>>(at);
-    }
+    const int passes = plan::self_attn_passes(at.self_rows);
+#define SELF_ATTN(KERNEL_) do { switch (passes) { \
+        case 1: KERNEL_<1><<<grid, 256, 0, st>>>(at); break; case 2: KERNEL_<2><<<grid, 256, 0, st>>>(at); break; \
+        case 3: KERNEL_<3><<<grid, 256, 0, st>>>(at); break; case 4: KERNEL_<4><<<grid, 256, 0, st>>>(at); break; \
+        case 5: KERNEL_<5><<<grid, 256, 0, st>>>(at); break; case 6: KERNEL_<6><<<grid, 256, 0, st>>>(at); break; \
+        default: KERNEL_<7><<<grid, 256, 0, st>>>(at); } } while (0)
+    if (at.self_owner) SELF_ATTN(dec_self_attn_owner_kernel); else SELF_ATTN(dec_self_attn_kernel);
+#undef SELF_ATTN
 }
 
 static void launch_cross_attn(const AttnArgs& at_in, int S, int H, int B, hipStream_t st) {
-    static const int nofence = env_int("WH_XATT_NOFENCE", 1);   // sc1 stores + sc1 loads need no acquire (MI355X_MICROARCH.md R1); 0 restores it (A/B)
+    const int nofence = knob::once<knob::WH_XATT_NOFENCE>();   // sc1 stores + sc1 loads need no acquire (MI355X_MICROARCH.md R1); 0 restores it (A/B)
     AttnArgs at = at_in;
     at.no_fence = nofence;
     ProfScope ps_(KK_DEC_CROSS_ATTN, st);
     const dim3 grid(S, H, B);
     // the gate goes back when workgroup (last - lead) is dispatched; WH_XATT_GATE_LEAD = workgroups before the end (tuning knob)
-    static const int gate_lead = env_int("WH_XATT_GATE_LEAD", 0);
+    const int gate_lead = knob::once<knob::WH_XATT_GATE_LEAD>();
     at.gate_wg = std::max(0, S * H * B - 1 - gate_lead);
-    static const int xlds = env_int("WH_XATT_LDS", 0);   // tuning knob: extra LDS per workgroup caps the residency
+    const int xlds = knob::once<knob::WH_XATT_LDS>();   // tuning knob: extra LDS per workgroup caps the residency
     // non-temporal K / V loads (each row is read once per step; measured large-v3, 32 slots: 51.9 -> 49.7 us per launch, 3 sessions in
     // flight 13.4 k -> 14.2 k sequence-steps/s, profiles/r02i_*); WH_XATT_NT=0 is the A/B side
-    static const int nt = env_int("WH_XATT_NT", 1);
+    const int nt = knob::once<knob::WH_XATT_NT>();
     const bool ntl = nt && at.cross_div <= 1;      // (cross_div > 1, beam search: cacheable loads - the L2 of the XCD serves the other beams of the audio)
 #define XATT(P_) do { if (ntl) dec_cross_attn_kernel<P_, true><<<grid, 256, xlds, st>>>(at); else dec_cross_attn_kernel<P_, false><<<grid, 256, xlds, st>>>(at); } while (0)
     if (S == 6) XATT(8);
@@ -865,7 +834,7 @@ void launch_decoder_step(const DecodeBuffers& db, const SamplerCfg* cfg_dev, con
     const int n_bt = (B + 31) / 32;
     const size_t self_stride = (size_t)db.max_batch * H * kMaxTok * kHeadDim;
     const size_t cross_stride = (size_t)db.max_batch * H * kCtx * kHeadDim;
-    const int S = cross_attn_splits(B, H);
+    const int S = plan::cross_attn_plan(H, knob::once<knob::WH_XATT_PASSES>(), kCtx).splits;      // (never a function of the batch: launch_plan.h)
     launch_dec32_embed(db.emb, db.pos, db.seq, B, d, V, n_bt, D.x, db.layers_host[0].ln1_g, D.za_hi, D.za_lo, D.stat, st);
     P32Args base{};
     base.batch = B; base.d = d; base.n_head = H; base.n_vocab = V; base.seq = db.seq; base.part = D.part; base.ticket = D.ticket;

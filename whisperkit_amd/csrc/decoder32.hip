@@ -25,6 +25,7 @@
 // takes a ticket, and the last arriver sums the slices in index order (MI355X_MICROARCH.md "splitk-seam": cheaper here than a
 // kernel boundary because the combine is 4-32 KB and the finisher also owns the epilogue).
 #include "dec_shared.h"
+#include "knobs.h"
 
 namespace wh {
 
@@ -492,93 +493,51 @@ void launch_dec32_embed(const f16* emb, const float* pos, const SeqState* seq, i
 }
 
 // ---------------------------------------------------------------------------------------------- launcher
-static int env_int32(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-
-// K splits across workgroups: only the N = d projections need them (40 row tiles at d = 1280 would leave 5/6 of the chip idle);
-// the split must divide the K / 64 tile groups.  WH_D32_KS_* override (tuning).
-int dec32_ksplit(int mode, int N, int K, bool f16_input) {
-    static const int ks_resid = env_int32("WH_D32_KS_RESID", 0), ks_fc2 = env_int32("WH_D32_KS_FC2", 0), ks_q = env_int32("WH_D32_KS_Q", 0),
-                     ks_wide = env_int32("WH_D32_KS_WIDE", 1), tile_kb = env_int32("WH_D32_TILE_KB", 96);
-    int want = (mode == P32_RESID) ? (f16_input ? ks_fc2 : ks_resid) : (mode == P32_Q ? ks_q : ks_wide);
-    // default for the N = d projections: as many K slices as keep a workgroup's weight slab at <= tile_kb KB (a 32-row tile of K
-    // columns is K / 16 KB): d = 384 -> 1 (no ticket at all), d = 1280 -> 1 for K = d, 4 for fc2's K = 4d
-    if (want <= 0) want = (K / 16 + tile_kb - 1) / tile_kb;
-    const int groups = K / 64;
-    want = max(1, min(want, 8));
-    while (want > 1 && groups % want) --want;
-    if ((long long)((N + 31) / 32) * want * 1024 > kD32PartFloats) want = 1;
-    return want;
-}
-
-template <int MODE, bool HILO, bool NTW>
-static void launch_tc_w(const P32Args& a, dim3 grid, hipStream_t st) {
-    const int tw = a.tw;
-    // chunk size of the weight stream: 5 k-tiles (196 - 204 registers: two workgroups per CU) up to four batch tiles; beyond (160- to 256-slot device batches: 200 - 1280 workgroups
-    // per launch, which must find room while two cross-attention streams hold most CUs) chunks of 2 (114 - 132 registers: three to four workgroups per CU): on the driver's line
-    // 2661 -> 2681 (from 8 tiles) -> 2689 - 2701 audio-s/s (from 6 / 5 tiles; profiles/r06r_projection_chunk_threshold.jsonl, r06q_*; no difference at 128 slots, r05n).  The
-    // chunking does not touch the order of the matrix instructions: same bits.  WH_D32_TC (chunk cap) and WH_D32_TC_BT (first batch-tile count with small chunks) override.
-    static const int tc_env = env_int32("WH_D32_TC", 0);
-    static const int tc_bt = env_int32("WH_D32_TC_BT", 5);
-    const int tc_cap = tc_env > 0 ? tc_env : (a.n_bt >= tc_bt ? 2 : 5);
-    if constexpr (MODE != P32_LOGITS && MODE != P32_Q) {
-        if (a.rt == 4) {    // four row tiles per workgroup: chunks of 1 k-tile (230 - 244 registers: two workgroups per CU)
-            dec32_proj_kernel<MODE, HILO, 1, NTW, 4><<<grid, 256, 0, st>>>(a);
-            return;
-        }
-    }
-    if (a.rt >= 2) {        // two row tiles per workgroup (launch_dec32_proj decides): chunks of 4 k-tiles (236 - 256 registers, two workgroups per CU like chunks of 2: 2823 -> 2834 audio-s/s), else 2 or 1; WH_D32_RT2_TC: A/B
-        static const int tc2 = env_int32("WH_D32_RT2_TC", 4);
-        if (tw % 4 == 0 && tc2 >= 4) dec32_proj_kernel<MODE, HILO, 4, NTW, 2><<<grid, 256, 0, st>>>(a);
-        else if (tw % 2 == 0 && tc2 >= 2) dec32_proj_kernel<MODE, HILO, 2, NTW, 2><<<grid, 256, 0, st>>>(a);
-        else dec32_proj_kernel<MODE, HILO, 1, NTW, 2><<<grid, 256, 0, st>>>(a);
-        return;
-    }
-    // chunks of <= 5 k-tiles: 6 would put the LOGITS instantiation at 226 VGPRs + accumulators = one wave per SIMD (tiny.en: 22 -> 47 us)
-    if (tw % 5 == 0 && tc_cap >= 5) dec32_proj_kernel<MODE, HILO, 5, NTW, 1><<<grid, 256, 0, st>>>(a);
-    else if (tw % 4 == 0 && tc_cap >= 4) dec32_proj_kernel<MODE, HILO, 4, NTW, 1><<<grid, 256, 0, st>>>(a);
-    else if (tw % 3 == 0 && tc_cap >= 3) dec32_proj_kernel<MODE, HILO, 3, NTW, 1><<<grid, 256, 0, st>>>(a);
-    else if (tw % 2 == 0) dec32_proj_kernel<MODE, HILO, 2, NTW, 1><<<grid, 256, 0, st>>>(a);
-    else dec32_proj_kernel<MODE, HILO, 1, NTW, 1><<<grid, 256, 0, st>>>(a);
-}
+// The decisions (K slices, row tiles per workgroup, chunk size, non-temporal weights, grid): launch_plan.h dec32_plan.  Here: the plan's
+// (MODE, HILO, TC, NTW, RT) -> the instantiation.  Four row tiles exist for qkv, fc1 and the RESID forms only.
 template <int MODE, bool HILO>
-static void launch_tc(const P32Args& a, dim3 grid, hipStream_t st) {
-    static const int ntw = env_int32("WH_D32_NTW", -1);      // -1: nt for a single batch tile only; 0 never; 1 always (the behaviour before round 4's last change)
-    const bool nt = ntw < 0 ? a.n_bt == 1 : ntw != 0;
-    if (nt) launch_tc_w<MODE, HILO, true>(a, grid, st); else launch_tc_w<MODE, HILO, false>(a, grid, st);
+static void launch_planned(const P32Args& a, const plan::Dec32Plan& p, hipStream_t st) {
+    const dim3 grid(p.grid);
+#define D32_GO(TC_, RT_) do { \
+        if (p.ntw) dec32_proj_kernel<MODE, HILO, TC_, true, RT_><<<grid, 256, 0, st>>>(a); \
+        else dec32_proj_kernel<MODE, HILO, TC_, false, RT_><<<grid, 256, 0, st>>>(a); \
+        return; } while (0)
+    if constexpr (MODE != P32_LOGITS && MODE != P32_Q) {
+        if (p.rt == 4) D32_GO(1, 4);
+    }
+    if (p.rt >= 2) {
+        if (p.tc == 4) D32_GO(4, 2);
+        if (p.tc == 2) D32_GO(2, 2);
+        D32_GO(1, 2);
+    }
+    switch (p.tc) {
+        case 5: D32_GO(5, 1);
+        case 4: D32_GO(4, 1);
+        case 3: D32_GO(3, 1);
+        case 2: D32_GO(2, 1);
+        default: D32_GO(1, 1);
+    }
+#undef D32_GO
 }
 
 unsigned long long* debug_buffer();
 void launch_dec32_proj(int mode, const P32Args& a_in, int n_bt, hipStream_t st) {
+    using namespace knob;
     P32Args a = a_in;
     a.dbg = (debug_buffer() && a.prof_kind >= 0) ? debug_buffer() + (size_t)a.prof_kind * 4096 * 8 : nullptr;   // WH_DBG=1 timeline probe
-    const bool hilo = a.zlo != nullptr;
-    a.ks = dec32_ksplit(mode, a.N, a.K, a.K > a.N);      // K > N: the fc2 shape (its own split knob)
-    a.tw = a.K / (64 * a.ks);
-    a.n_bt = n_bt;
-    // Row tiles per workgroup (round 6).  From four to five batch tiles on (128- to 256-slot device batches) a launch is 320 - 1280 workgroups and its time follows the CUs it gets
-    // (alone at 256 slots, whole chip / 128 / 64 CUs: qkv 21 / 33 / 56 us, fc1 23 / 36 / 64, fc2 28 / 44 / 80, profiles/r06t_chain_on_cus_ab.jsonl): the wide projections are bound by
-    // the bytes their workgroups pull through the CUs' L1s - 3 KB per pair of matrix instructions (1 KB weight tile + 2 KB hi | lo planes) - and beside two cross-attention
-    // streams they have half of the chip or less.  Two row tiles per workgroup share the planes (2 KB per pair), four (qkv, fc1, fc2) 1.5 KB: headline 2738 -> 2825 (two) -> 2837
-    // audio-s/s (four), profiles/r06u .. r06w_*.  Same bits (a row tile's k-tiles meet the same wave in the same order).  WH_D32_RT_BT / WH_D32_RT4_BT (first batch-tile count
-    // with 2 / 4 row tiles; 99 = never) and WH_D32_RT4_MODES (bit 0 qkv, 1 fc1, 2 fc2) are the A/B knobs.  Thresholds (profiles/r06ad_*): 128-slot batches x 3 in flight 2666 -> 2744
-    // with two row tiles (four: 2737), 64-slot batches 2350 -> 2345 with two, 2229 with four: two from four batch tiles on, four from five.
-    static const int rt_bt = env_int32("WH_D32_RT_BT", 4), rt4_bt = env_int32("WH_D32_RT4_BT", 5), rt4_modes = env_int32("WH_D32_RT4_MODES", 7);
-    a.rt = n_bt >= rt_bt ? 2 : 1;
-    {
-        const int bit = mode == P32_QKV ? 1 : mode == P32_FC1 ? 2 : (mode == P32_RESID && a.K > a.N) ? 4 : 0;
-        if (n_bt >= rt4_bt && (rt4_modes & bit) && ((a.N + 31) / 32) % 4 == 0) a.rt = 4;
-    }
-    const int nx = (((a.N + 31) / 32 + a.rt - 1) / a.rt) * a.ks;
-    const dim3 grid((unsigned)(((nx + 7) / 8) * 8 * n_bt));
+    const plan::Dec32Knobs k{once<WH_D32_KS_RESID>(), once<WH_D32_KS_FC2>(), once<WH_D32_KS_Q>(), once<WH_D32_KS_WIDE>(), once<WH_D32_TILE_KB>(), once<WH_D32_TC>(),
+                             once<WH_D32_TC_BT>(), once<WH_D32_RT2_TC>(), once<WH_D32_NTW>(), once<WH_D32_RT_BT>(), once<WH_D32_RT4_BT>(), once<WH_D32_RT4_MODES>()};
+    const plan::Dec32Plan p = plan::dec32_plan(mode, a.N, a.K, n_bt, k);
+    a.ks = p.ks; a.tw = p.tw; a.rt = p.rt; a.n_bt = n_bt;
     ProfScope ps_(a.prof_kind, st);
     switch (mode) {
-        case P32_QKV: launch_tc<P32_QKV, true>(a, grid, st); break;
-        case P32_Q: launch_tc<P32_Q, true>(a, grid, st); break;
-        case P32_FC1: launch_tc<P32_FC1, true>(a, grid, st); break;
-        case P32_LOGITS: launch_tc<P32_LOGITS, true>(a, grid, st); break;
+        case P32_QKV: launch_planned<P32_QKV, true>(a, p, st); break;
+        case P32_Q: launch_planned<P32_Q, true>(a, p, st); break;
+        case P32_FC1: launch_planned<P32_FC1, true>(a, p, st); break;
+        case P32_LOGITS: launch_planned<P32_LOGITS, true>(a, p, st); break;
         default:
-            if (hilo) launch_tc<P32_RESID, true>(a, grid, st);
-            else launch_tc<P32_RESID, false>(a, grid, st);
+            if (a.zlo != nullptr) launch_planned<P32_RESID, true>(a, p, st);
+            else launch_planned<P32_RESID, false>(a, p, st);
     }
 }
 

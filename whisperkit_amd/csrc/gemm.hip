@@ -18,6 +18,7 @@
 
 #include "epi_stage.h"
 #include "kernels.h"
+#include "knobs.h"
 
 namespace wh {
 
@@ -471,7 +472,7 @@ __device__ __forceinline__ void epi_staged_vt(const GemmArgs& a, f32x16 (&acc)[4
 }
 
 template <int EPI>
-constexpr bool kHasStagedEpilogue = EPI == EPI_F16 || EPI == EPI_GELU_F16 || EPI == EPI_RESID_F32 || EPI == EPI_QKV_ENC;
+constexpr bool kHasStagedEpilogue = plan::has_staged_epilogue(EPI);
 
 // ---------------------------------------------------------------------------------------------- 256 x 256 x 64 tile, ping-pong
 // Large-problem path (encoder GEMMs at batch >= 2, cross-K/V projection): 8 waves (2 along M x 4 along N, wave tile 128 x 64 =
@@ -890,105 +891,66 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(const GemmArgs a, int n_t
     }
 }
 
-// Split A operand (a.A_lo set, encoder_precision 1): the same kernel choice with gemm_split_kernel / gemm256_split_kernel (BK = 32 there: whole
-// 32-wide K tiles); never the persistent loop (an opt-in experiment of the Float16 form).
-template <int EPI>
-static void launch_split(const GemmArgs& a, hipStream_t st) {
-    const long long tiles256 = (long long)((a.M + 255) / 256) * ((a.N + 255) / 256);
-    static const bool no256 = [] { const char* e = getenv("WH_NO_GEMM256"); return e && e[0] == '1'; }();
-    if (!no256 && tiles256 >= 64 && a.K % 32 == 0 && a.lda % 8 == 0 && a.a_batch_stride % 8 == 0 && a.N % 4 == 0) {
-        static const int epi_mode = [] { const char* e = getenv("WH_GEMM_EPI_MODE"); return e && e[0] >= '0' && e[0] <= '2' ? e[0] - '0' : 1; }();
-        auto go = [&](auto mode_tag) {
-            constexpr int MODE = decltype(mode_tag)::value;
-            static PerDeviceOnce raised;
-            raised.run([] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_split_kernel<EPI, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, 131072); });
-            gemm256_split_kernel<EPI, MODE><<<(unsigned)tiles256, 512, 131072, st>>>(a);
-        };
-        if constexpr (kHasStagedEpilogue<EPI>) {
-            const bool aligned = (((uintptr_t)a.out16 | (uintptr_t)a.out32 | (uintptr_t)a.k16 | (uintptr_t)a.vt16 | (uintptr_t)a.out16_lo) & 15) == 0;
-            const bool shape_ok = aligned && a.N % 64 == 0 && a.M % 4 == 0 && a.ldc % 8 == 0 && a.d_model % 64 == 0;
-            if (shape_ok && epi_mode == 1) { go(std::integral_constant<int, 1>{}); return; }
-            if (shape_ok && epi_mode == 2) { go(std::integral_constant<int, 2>{}); return; }
-        }
-        go(std::integral_constant<int, 0>{});
-        return;
-    }
-    long long tiles128 = (long long)((a.M + 127) / 128) * ((a.N + 127) / 128);
-    if (tiles128 >= 192) {
-        dim3 g((a.N + 127) / 128, (a.M + 127) / 128);
-        gemm_split_kernel<128, 128, EPI><<<g, 256, 0, st>>>(a);
-    } else {
-        dim3 g((a.N + 63) / 64, (a.M + 63) / 64);
-        gemm_split_kernel<64, 64, EPI><<<g, 256, 0, st>>>(a);
-    }
+// CUs of the device rounded down to a multiple of 8 (the persistent grid)
+static int persist_cus() {
+    static PerDeviceOnce asked;
+    static int cus = 256;
+    asked.run([] { int dev = 0, n = 0; if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n >= 8) cus = n / 8 * 8; });
+    return cus;
 }
 
-template <int EPI>
+// The kernel choice: launch_plan.h gemm_plan (one tree for the Float16 and the split A operand).  Here: the plan -> the instantiation.
+template <int EPI, bool SPLIT>
 static void launch_epi(const GemmArgs& a, hipStream_t st) {
-    if (a.A_lo) { launch_split<EPI>(a, st); return; }
-    // large problems: 256 x 256 x 64 LDS-DMA kernel (needs whole 64-wide K tiles and 16-byte aligned rows)
-    const long long tiles256 = (long long)((a.M + 255) / 256) * ((a.N + 255) / 256);
-    static const bool no256 = [] { const char* e = getenv("WH_NO_GEMM256"); return e && e[0] == '1'; }();
-    if (!no256 && tiles256 >= 64 && a.K % 64 == 0 && a.lda % 8 == 0 && a.a_batch_stride % 8 == 0 && a.N % 4 == 0) {
-        // measured and rejected (profiles/r02s_*): staggering the first-round workgroups by up to a tile time to spread the store
-        // epilogues of the 256 CUs over each other's K loops - no change (1476 vs 1475 us, large-v3 fc1 at 64 chunks)
-        static const int epi_mode = [] { const char* e = getenv("WH_GEMM_EPI_MODE"); return e && e[0] >= '0' && e[0] <= '2' ? e[0] - '0' : 1; }();
-        // WH_GEMM_PERSIST=1: the persistent tile loop (gemm256p_kernel: one workgroup per CU, the next tile's first K-tile requested under the epilogue;
-        // bit-identical, measured no faster: the comment above the kernel); default 0 = one workgroup per tile (rounds 2 - 5).
-        // WH_GEMM_PERSIST_WGS: workgroups of the persistent grid (default = the CUs, a multiple of 8: a smaller grid confines the encoder to that many CUs)
-        static const int persist = [] { const char* e = getenv("WH_GEMM_PERSIST"); return e ? atoi(e) : 0; }();
-        static const int persist_wgs = [] { const char* e = getenv("WH_GEMM_PERSIST_WGS"); int v = e ? atoi(e) : 0; return v > 0 ? (v + 7) / 8 * 8 : 0; }();
-        auto go = [&](auto mode_tag) {
-            constexpr int MODE = decltype(mode_tag)::value;
-            if (persist) {
-                static PerDeviceOnce raised_p;
-                static int cus = 256;
-                raised_p.run([] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256p_kernel<EPI, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, 163840);
-                                  int dev = 0, n = 0; if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n >= 8) cus = n / 8 * 8; });
-                const int grid = (int)std::min<long long>(persist_wgs ? persist_wgs : cus, (tiles256 + 7) / 8 * 8);
-                static const int stagger = [] { const char* e = getenv("WH_GEMM_STAGGER"); return e ? atoi(e) : 0; }();
-                static const int gm_env = [] { const char* e = getenv("WH_GEMM_GM"); int v = e ? atoi(e) : 8; return v >= 1 && v <= 64 ? v : 8; }();
-                gemm256p_kernel<EPI, MODE><<<(unsigned)grid, 512, 163840, st>>>(a, (int)tiles256, stagger, gm_env);
-                return;
-            }
+    using namespace knob;
+    uintptr_t bases = (uintptr_t)a.out16 | (uintptr_t)a.out32 | (uintptr_t)a.k16 | (uintptr_t)a.vt16;
+    if constexpr (SPLIT) bases |= (uintptr_t)a.out16_lo;        // the split form writes a lo plane beside out16
+    const int persist = SPLIT ? 0 : once<WH_GEMM_PERSIST>();
+    const plan::GemmKnobs k{once<WH_NO_GEMM256>(), once<WH_GEMM_EPI_MODE>(), persist, persist ? once<WH_GEMM_PERSIST_WGS>() : 0, persist ? persist_cus() : 0};
+    const plan::GemmPlan p = plan::gemm_plan(a.M, a.N, a.K, a.lda, a.a_batch_stride, a.ldc, a.d_model, EPI, SPLIT, bases, k);
+    auto go256 = [&](auto mode_tag) {
+        constexpr int MODE = decltype(mode_tag)::value;
+        if constexpr (SPLIT) {
+            static PerDeviceOnce raised;
+            raised.run([] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_split_kernel<EPI, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, 131072); });
+            gemm256_split_kernel<EPI, MODE><<<p.grid_x, 512, 131072, st>>>(a);
+        } else if (p.family == plan::GEMM_256P) {
+            static PerDeviceOnce raised_p;
+            raised_p.run([] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256p_kernel<EPI, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, 163840); });
+            gemm256p_kernel<EPI, MODE><<<p.grid_x, 512, 163840, st>>>(a, (int)p.tiles256, once<WH_GEMM_STAGGER>(), once<WH_GEMM_GM>());
+        } else {
             static PerDeviceOnce raised;
             raised.run([] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_kernel<EPI, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, 131072); });
-            gemm256_kernel<EPI, MODE><<<(unsigned)tiles256, 512, 131072, st>>>(a);
-        };
-        if constexpr (kHasStagedEpilogue<EPI>) {
-            // the staged epilogues store uint4 / float4 vectors: every output base must be 16-byte aligned (hipMalloc bases + multiples of 8
-            // elements today; an offset view handed in by a future caller falls back to the direct epilogue instead of faulting - ADVICE r05)
-            const bool aligned = (((uintptr_t)a.out16 | (uintptr_t)a.out32 | (uintptr_t)a.k16 | (uintptr_t)a.vt16) & 15) == 0;
-            const bool shape_ok = aligned && a.N % 64 == 0 && a.M % 4 == 0 && a.ldc % 8 == 0 && a.d_model % 64 == 0;
-            if (shape_ok && epi_mode == 1) { go(std::integral_constant<int, 1>{}); return; }
-            if (shape_ok && epi_mode == 2) { go(std::integral_constant<int, 2>{}); return; }
+            gemm256_kernel<EPI, MODE><<<p.grid_x, 512, 131072, st>>>(a);
         }
-        go(std::integral_constant<int, 0>{});
-        return;
-    }
-    // small problems get 64x64 tiles so that more than a handful of CUs are busy
-    long long tiles128 = (long long)((a.M + 127) / 128) * ((a.N + 127) / 128);
-    if (tiles128 >= 192) {
-        dim3 g((a.N + 127) / 128, (a.M + 127) / 128);
-        gemm_kernel<128, 128, EPI><<<g, 256, 0, st>>>(a);
-    } else {
-        dim3 g((a.N + 63) / 64, (a.M + 63) / 64);
-        gemm_kernel<64, 64, EPI><<<g, 256, 0, st>>>(a);
+    };
+    const dim3 g(p.grid_x, p.grid_y);
+    switch (p.family) {
+        case plan::GEMM_256:
+        case plan::GEMM_256P:
+            if constexpr (kHasStagedEpilogue<EPI>) {
+                if (p.mode == 1) { go256(std::integral_constant<int, 1>{}); return; }
+                if (p.mode == 2) { go256(std::integral_constant<int, 2>{}); return; }
+            }
+            go256(std::integral_constant<int, 0>{});
+            return;
+        case plan::GEMM_128:
+            if constexpr (SPLIT) gemm_split_kernel<128, 128, EPI><<<g, 256, 0, st>>>(a); else gemm_kernel<128, 128, EPI><<<g, 256, 0, st>>>(a);
+            return;
+        case plan::GEMM_64:
+            if constexpr (SPLIT) gemm_split_kernel<64, 64, EPI><<<g, 256, 0, st>>>(a); else gemm_kernel<64, 64, EPI><<<g, 256, 0, st>>>(a);
+            return;
     }
 }
 
 void launch_gemm(GemmEpi epi, const GemmArgs& a, hipStream_t st) {
     ProfScope ps_(a.prof_kind, st);
+#define GEMM_EPI_CASE(E_) case E_: if (a.A_lo) launch_epi<E_, true>(a, st); else launch_epi<E_, false>(a, st); break
     switch (epi) {
-        case EPI_F16: launch_epi<EPI_F16>(a, st); break;
-        case EPI_GELU_F16: launch_epi<EPI_GELU_F16>(a, st); break;
-        case EPI_RESID_F32: launch_epi<EPI_RESID_F32>(a, st); break;
-        case EPI_QKV_ENC: launch_epi<EPI_QKV_ENC>(a, st); break;
-        case EPI_CONV1: launch_epi<EPI_CONV1>(a, st); break;
-        case EPI_CONV2: launch_epi<EPI_CONV2>(a, st); break;
-        case EPI_F32: launch_epi<EPI_F32>(a, st); break;
-        case EPI_CROSS_KV: launch_epi<EPI_CROSS_KV>(a, st); break;
+        GEMM_EPI_CASE(EPI_F16); GEMM_EPI_CASE(EPI_GELU_F16); GEMM_EPI_CASE(EPI_RESID_F32); GEMM_EPI_CASE(EPI_QKV_ENC);
+        GEMM_EPI_CASE(EPI_CONV1); GEMM_EPI_CASE(EPI_CONV2); GEMM_EPI_CASE(EPI_F32); GEMM_EPI_CASE(EPI_CROSS_KV);
     }
+#undef GEMM_EPI_CASE
 }
 
 }  // namespace wh

@@ -18,6 +18,7 @@
 #include <tuple>
 
 #include "internal.h"
+#include "knobs.h"
 
 using namespace wh;
 using whi::set_error;
@@ -255,10 +256,7 @@ void finalize_decoding_result(const SeqState& sq, const wh_decoding_options* opt
 
 constexpr int kStepsPerGraph = 8;
 
-static bool use_graphs() {
-    static const bool v = [] { const char* e = getenv("WH_NO_GRAPH"); return !(e && e[0] == '1'); }();
-    return v;
-}
+static bool use_graphs() { return !knob::once<knob::WH_NO_GRAPH>(); }
 
 // Step graphs live in the session (a session is driven by one host thread at a time): no process-wide cache, no lock.
 // `first_step`: token_index of the live slots at the graph's first step (decodeText starts every slot at 0 and advances them in
@@ -272,7 +270,7 @@ static int get_step_graph(wh_session* s, int batch, int first_step, hipGraphExec
     // The cache is capped (a large-v3 step graph holds ~2.5 k kernel nodes; a configuration = everything of the key but the row bound has up
     // to 28 graphs): when it is full, the configuration that was used longest ago goes - never the one being extended.  The stream is
     // drained first: no executable graph is destroyed while a launch of it may still be running.
-    static const size_t cap = [] { const char* e = getenv("WH_GRAPH_CAP"); const int v = e ? atoi(e) : 0; return (size_t)(v > 0 ? v : 4 * 28); }();
+    const size_t cap = (size_t)knob::once<knob::WH_GRAPH_CAP>();
     while (s->graphs.size() >= cap) {
         auto same_cfg = [](const WhGraphKey& a, const WhGraphKey& b) {
             return a.batch == b.batch && a.align == b.align && a.fused == b.fused && a.n_align == b.n_align && a.gate == b.gate;
@@ -373,7 +371,7 @@ static int run_token_loop(wh_session* s, int batch, int loop_count) {
     if (use_graphs()) {
         const int n_graphs = (loop_count + kStepsPerGraph - 1) / kStepsPerGraph;
         // WH_DBG_HOST=1: host-side cost of the replay loop (time inside hipGraphLaunch vs waiting for the device), one line per decode
-        static const bool dbg_host = [] { const char* e = getenv("WH_DBG_HOST"); return e && e[0] == '1'; }();
+        const bool dbg_host = knob::once<knob::WH_DBG_HOST>();
         double t_launch = 0.0, t_wait = 0.0;
         auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
         const double t_begin = dbg_host ? now() : 0.0;
@@ -457,7 +455,7 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
     // fused greedy path: every active slot samples at T = 0 (filters + softmax statistics in the logits epilogue)
     s->fused_greedy = true;
     for (int b = 0; b < batch; ++b) if (s->seq_host[b].active && s->seq_host[b].temperature != 0.0f) s->fused_greedy = false;
-    if (const char* e = getenv("WH_NO_FUSED_SAMPLER")) if (e[0] == '1') s->fused_greedy = false;
+    if (knob::now<knob::WH_NO_FUSED_SAMPLER>()) s->fused_greedy = false;
     WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * batch, hipMemcpyHostToDevice, s->st));
     launch_rules_init(s->cfg_dev, s->seq, batch, s->st);
     const int loop_count = std::min(opt->sample_length, kMaxTok - 1);

@@ -1,6 +1,7 @@
 // Launcher declarations shared between the .hip kernel files and the C-ABI implementation.
 #pragma once
 #include "common.h"
+#include "launch_plan.h"
 
 #include <atomic>
 #include <mutex>
@@ -99,19 +100,7 @@ __device__ __forceinline__ void split_f16(float x, f16& hi, f16& lo) {
 }
 
 // ---------------------------------------------------------------------------------------------- GEMM
-// C[M][N] = A[M][K] * W[N][K]^T (+ bias[N]) with fused epilogues.  A rows may be an overlapping-row view:
-// address(m, k) = A + (m / a_rows_per_batch) * a_batch_stride + (m % a_rows_per_batch) * lda + k.
-enum GemmEpi {
-    EPI_F16 = 0,        // out16[m*ldc + n] = v
-    EPI_GELU_F16 = 1,   // out16 = gelu(v)
-    EPI_RESID_F32 = 2,  // x32[m*ldc + n] += v                        (fp32 residual stream)
-    EPI_QKV_ENC = 3,    // n<d: q16[m*d+n]; n<2d: k16[m*d+n-d]; else V^T[(b*H+h)*64+c][t]   (encoder attention operands)
-    EPI_CONV1 = 4,      // out16[(b*3002 + t + 1)*ldc + n] = gelu(v)  (padded time-major input of conv2)
-    EPI_CONV2 = 5,      // x32[m*ldc + n] = gelu(v) + pos[t*ldc + n]
-    EPI_F32 = 6,        // out32[m*ldc + n] = v
-    EPI_CROSS_KV = 7,   // n = l*2d + kv*d + h*64 + c, m = b*1500 + t -> (kv ? V : K) hi / lo [(((l*Bmax + b)*H + h)*1500 + t)*64 + c]  (24-bit rows, hr24)
-};
-
+// (enum GemmEpi and the kernel choice: launch_plan.h)
 struct GemmArgs {
     const f16* A;
     const f16* W;
@@ -238,7 +227,6 @@ constexpr int kMaxVocab = 52224;
 static_assert(kMaxVocab <= kStatBlocks * 32, "fused greedy sampler: one statistics record per 32-row logits tile");
 constexpr int kMaxSplit = 24;   // cross-attention key splits (64 keys per workgroup at the finest)
 constexpr int kPartStride = 96; // floats per split partial (m, l, o[64]) padded to 3 x 128 bytes: no cache line is shared between splits
-int cross_attn_splits(int batch, int n_head);
 
 // ---------------------------------------------------------------------------------------------- MFMA decode path (decoder32.hip)
 // Batch tiles of 32 slots are the N side of v_mfma_f32_32x32x16_f16; weights are re-tiled at model load so that one
@@ -262,8 +250,7 @@ struct Dec32 {
     float* part; int* ticket; // split-K partial tiles + arrival counters
     size_t part_floats;
 };
-constexpr int kD32PartFloats = 2 * 1024 * 1024;   // per batch tile: row tiles x K splits x 1024 <= 2 M floats
-enum { P32_QKV = 0, P32_Q = 1, P32_RESID = 2, P32_FC1 = 3, P32_LOGITS = 4 };
+// (kD32PartFloats, the P32_* modes and the launch decisions: launch_plan.h dec32_plan)
 struct P32Args {
     int batch, N, K, d, n_head, n_vocab;
     int ks, tw;              // K splits across workgroups; 16-wide k tiles per wave = K / (64 ks)
@@ -288,7 +275,6 @@ void launch_dec32_embed(const f16* emb, const float* pos, const SeqState* seq, i
 // model-load helpers: re-tile W[N][K] -> out[ceil(N/32)][K/16][64][8]; g[n] = sum_k W[n][k] gamma[k], c[n] = sum_k W[n][k] beta[k] + bias[n] (f64 sums)
 void dec32_tile_weights(const f16* W, int N, int K, f16* out, hipStream_t st);
 void dec32_fold_vectors(const f16* W, int N, int K, const float* gamma, const float* beta, const float* bias, float* g, float* c, hipStream_t st);
-int dec32_ksplit(int mode, int N, int K, bool f16_input);
 
 // ---------------------------------------------------------------------------------------------- absorbed cross-attention (xabs.hip)
 constexpr int kXabsMaxSlotsPerWorkgroup = 16;   // slots one xabs_attn workgroup streams one after the other (wh_session_options)
@@ -296,11 +282,10 @@ constexpr int kMaxSessionSlots = 256;    // windows one session decodes in lock-
 constexpr int kXabsAutoMinSlots = 28;   // wh_session_create picks the absorbed path from this many slots (WH_XABS_MIN_SLOTS overrides): measured large-v3,
                                         // one stream, ms per decoder step with 24-bit K / V rows vs absorbed (4 splits): 16 slots 3.27 / 3.91, 24 slots 3.88 / 4.00, 28 slots
                                         // 4.17 / 4.05, 32 slots 4.40 / 4.09 (profiles/r05h_*, r05a_*)
-constexpr int kXabsSplits = 4;      // most key splits per slot (buffer sizes); a session uses Xabs::n_split of them, fixed at creation
 // key splits of a session: one workgroup per (slot, split) owns a whole CU (LDS, registers), so slots x splits is the number of CUs the
 // kernel takes.  WH_XABS_SPLITS overrides (A/B).
 int xabs_splits(int max_batch);
-int xabs_auto_splits(int max_batch);     // the automatic choice without the WH_XABS_SPLITS override (wh_xabs_auto_splits)
+using plan::xabs_auto_splits;            // the automatic choice without the WH_XABS_SPLITS override (wh_xabs_auto_splits)
 struct XabsLayerW {
     const f16* wkT;      // W_k^T tiles [H][d / 32][4][64][8] (A fragments of the Q' projection)
     const f16* wv_t;     // W_v in the decoder projection tiling [d / 32][d / 16][64][8]
@@ -329,8 +314,8 @@ struct XabsArgs {
     int* gate;                       // cross-attention gate (dec_shared.h, WH_XATT_GATE=1): xabs_qk takes it, xabs_attn's last workgroup returns it
     int spw;                         // xabs_attn: slots per workgroup (round 6): the launch has ceil(batch / spw) x n_split workgroups, each streams its slots one after the other
 };
-bool xabs_supported(int d, int n_head);     // the path can run: d = 384 / 512 / 768 / 1024 / 1280 with heads of 64 channels
-bool xabs_auto_width(int d, int n_head);    // ... and the automatic choice / WH_XABS may pick it: not at d = 384, where it is opt-in
+using plan::xabs_supported;                 // the path can run: d = 384 / 512 / 768 / 1024 / 1280 with heads of 64 channels
+using plan::xabs_auto_width;                // ... and the automatic choice / WH_XABS may pick it: not at d = 384, where it is opt-in
 void xabs_tile_wk(const f16* Wk, int d, int H, f16* out, hipStream_t st);
 void launch_xabs_qk(const XabsArgs& a, int n_bt, hipStream_t st);
 void launch_xabs_attn(const XabsArgs& a, hipStream_t st);

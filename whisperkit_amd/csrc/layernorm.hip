@@ -2,6 +2,7 @@
 // plus small conversion kernels.  One wave per row, row cached in registers, two-pass variance
 // (matches torch.nn.functional.layer_norm numerics).  HBM-bound: 4 B read + 2 B written per element.
 #include "kernels.h"
+#include "knobs.h"
 
 namespace wh {
 
@@ -103,17 +104,18 @@ __global__ __launch_bounds__(256) void layernorm_v4_kernel(const float* __restri
 
 void launch_layernorm(const float* x, const float* g, const float* b, int rows, int d, f16* y16, float* y32, hipStream_t st, f16* y16_lo) {
     ProfScope ps_(KK_LAYERNORM, st);
-    static const int v4 = [] { const char* e = getenv("WH_LN_V4"); return e ? atoi(e) : 2; }();      // 2 (default): non-temporal row loads and Float16 stores (514 -> 488 us per 384 000 rows: each is touched once before 3 GB of other traffic), 1: plain, 0: the scalar form; 1 and 2 give the same bits
-    const bool aligned = d % 4 == 0 && (((uintptr_t)x | (uintptr_t)g | (uintptr_t)b | (uintptr_t)y32) % 16) == 0 && ((uintptr_t)y16 % 8) == 0;
+    const plan::LnKernel which = plan::layernorm_plan(d, (uintptr_t)x | (uintptr_t)g | (uintptr_t)b | (uintptr_t)y32, (uintptr_t)y16, (uintptr_t)y16_lo, y16_lo != nullptr,
+                                                      knob::once<knob::WH_LN_V4>());
+    const unsigned grid = (rows + 3) / 4;
     if (y16_lo) {       // split encoder: y16 must be set
-        if (v4 == 2 && aligned && (uintptr_t)y16_lo % 8 == 0) layernorm_v4_kernel<true, true><<<(rows + 3) / 4, 256, 0, st>>>(x, g, b, rows, d, y16, y32, y16_lo);
-        else if (v4 && aligned && (uintptr_t)y16_lo % 8 == 0) layernorm_v4_kernel<false, true><<<(rows + 3) / 4, 256, 0, st>>>(x, g, b, rows, d, y16, y32, y16_lo);
-        else layernorm_kernel<<<(rows + 3) / 4, 256, 0, st>>>(x, g, b, rows, d, y16, y32, y16_lo);
+        if (which == plan::LN_V4_NT) layernorm_v4_kernel<true, true><<<grid, 256, 0, st>>>(x, g, b, rows, d, y16, y32, y16_lo);
+        else if (which == plan::LN_V4) layernorm_v4_kernel<false, true><<<grid, 256, 0, st>>>(x, g, b, rows, d, y16, y32, y16_lo);
+        else layernorm_kernel<<<grid, 256, 0, st>>>(x, g, b, rows, d, y16, y32, y16_lo);
         return;
     }
-    if (v4 == 2 && aligned) layernorm_v4_kernel<true><<<(rows + 3) / 4, 256, 0, st>>>(x, g, b, rows, d, y16, y32);
-    else if (v4 && aligned) layernorm_v4_kernel<false><<<(rows + 3) / 4, 256, 0, st>>>(x, g, b, rows, d, y16, y32);
-    else layernorm_kernel<<<(rows + 3) / 4, 256, 0, st>>>(x, g, b, rows, d, y16, y32, nullptr);
+    if (which == plan::LN_V4_NT) layernorm_v4_kernel<true><<<grid, 256, 0, st>>>(x, g, b, rows, d, y16, y32);
+    else if (which == plan::LN_V4) layernorm_v4_kernel<false><<<grid, 256, 0, st>>>(x, g, b, rows, d, y16, y32);
+    else layernorm_kernel<<<grid, 256, 0, st>>>(x, g, b, rows, d, y16, y32, nullptr);
 }
 
 __global__ void f32_to_f16_kernel(const float* __restrict__ in, f16* __restrict__ out, size_t n) {

@@ -23,6 +23,7 @@
 // Everything is bit-deterministic and batch-invariant: a (slot, split) workgroup never looks at another slot, the split count depends
 // on nothing but the build, partial sums are combined in index order.
 #include "dec_shared.h"
+#include "knobs.h"
 
 namespace wh {
 
@@ -604,27 +605,10 @@ __global__ __launch_bounds__(256, 1) void xabs_vup_kernel(const XabsArgs a, int 
 }
 
 // ---------------------------------------------------------------------------------------------- launchers
-static int xabs_env(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-
-// "can run": the five Whisper widths, heads of 64 channels.  "is picked automatically" is the narrower xabs_auto_width: at d = 384 the
-// absorbed form is opt-in (cross_attention_mode = 1) until a measurement decides otherwise, so the automatic choice and WH_XABS keep
-// giving tiny / tiny.en sessions the K / V rows.
-bool xabs_supported(int d, int n_head) { return (d == 384 || (d % 256 == 0 && d >= 512 && d <= 1280)) && n_head <= 32 && n_head * 64 == d; }
-bool xabs_auto_width(int d, int n_head) { return xabs_supported(d, n_head) && d >= 512; }
-
-// Automatic key splits per slot (a constant of the session): as many as keep slots x splits workgroups within ONE round of the chip's 256 CUs, at most kXabsSplits.
-// Up to round 6 the choice was 4 whatever the batch; one large-v3 session alone, ms per decoder step at 4 / 3 / 2 / 1 splits (profiles/r06ah_lone_session_key_splits.jsonl):
-// 32 slots 4.21 / 4.52 / 5.16 / 7.28; 96 slots 6.45 / 7.08 / 5.95 / 7.93; 128 slots 7.64 / 7.97 / 6.86 / 8.72; 192 slots 9.84 / 10.52 / 10.04 / 9.55; 256 slots 12.82 / 12.09 / 11.45 / 10.92 -
-// a second round of workgroups pays the kernel's exposed prologue and epilogue again.  (Slots that share an encoder output - beam search - are the exception: their streams
-// are L2 hits and more workgroups win, 240 audio-s/s with 4 splits against 228 with 2 on configs[4]; such a caller asks for 4: wh_session_create_tuned.)
-int xabs_auto_splits(int max_batch) {
-    const int s = 256 / (max_batch > 0 ? max_batch : 1);
-    return s < 1 ? 1 : (s > kXabsSplits ? kXabsSplits : s);
-}
+// (xabs_supported / xabs_auto_width / xabs_auto_splits and the grids below: launch_plan.h)
 int xabs_splits(int max_batch) {
-    const int e = xabs_env("WH_XABS_SPLITS", 0);
-    if (e >= 1 && e <= kXabsSplits) return e;
-    return xabs_auto_splits(max_batch);
+    const int e = knob::now<knob::WH_XABS_SPLITS>();       // 1 .. kXabsSplits, else 0
+    return e ? e : xabs_auto_splits(max_batch);
 }
 
 void launch_xabs_qk(const XabsArgs& a, int n_bt, hipStream_t st) {
@@ -640,18 +624,14 @@ static void launch_attn_k(const XabsArgs& a, hipStream_t st) {
     constexpr int lds = xabs_lds_bytes(CW);
     static PerDeviceOnce once;
     once.run([] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&xabs_attn_kernel<CW, NHT, DBG, NTL>), hipFuncAttributeMaxDynamicSharedMemorySize, lds); });
-    const int spw = a.spw > 1 ? a.spw : 1, b1 = (a.batch + spw - 1) / spw;
-    const int n_grp = (b1 + 3) / 4 * a.n_split;             // (split, 4 slots) groups, 8 of them (one per XCD) to every 32 workgroup ids
-    xabs_attn_kernel<CW, NHT, DBG, NTL><<<dim3((unsigned)((n_grp + 7) / 8 * 32)), 512, lds, st>>>(a);
+    xabs_attn_kernel<CW, NHT, DBG, NTL><<<dim3(plan::xabs_attn_grid(a.batch, a.spw, a.n_split)), 512, lds, st>>>(a);
 }
 template <int KSW, bool DBG, bool NTL>
 static void launch_attn_w4_k(const XabsArgs& a, hipStream_t st) {
     constexpr int lds = xabs_lds_bytes_w(4, KSW);
     static PerDeviceOnce once;
     once.run([] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&xabs_attn_kernel<KSW, 1, DBG, NTL, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, lds); });
-    const int spw = a.spw > 1 ? a.spw : 1, b1 = (a.batch + spw - 1) / spw;
-    const int n_grp = (b1 + 3) / 4 * a.n_split;
-    xabs_attn_kernel<KSW, 1, DBG, NTL, 4><<<dim3((unsigned)((n_grp + 7) / 8 * 32)), 256, lds, st>>>(a);
+    xabs_attn_kernel<KSW, 1, DBG, NTL, 4><<<dim3(plan::xabs_attn_grid(a.batch, a.spw, a.n_split)), 256, lds, st>>>(a);
 }
 // CW = 0: the 4-wave form of d = 384
 template <int CW, int NHT, bool DBG, bool NTL>
@@ -660,8 +640,8 @@ static void launch_attn_any(const XabsArgs& a, hipStream_t st) {
 }
 template <int CW, int NHT>
 static void launch_attn_t(const XabsArgs& a, hipStream_t st) {
-    static const int nt = xabs_env("WH_XABS_NT", 1);          // non-temporal policy on the encoder-output stream (in flight: 19.2 k vs 18.1 k sequence-steps/s, profiles/r04l_*); 0 = A/B side
-    static const int ablate = xabs_env("WH_XABS_ABLATE", 0);  // timing probe (garbage results): 1 no LDS-DMA in the loop, 2 no S / softmax / P V work, 3 both
+    const int nt = knob::once<knob::WH_XABS_NT>();          // non-temporal policy on the encoder-output stream (in flight: 19.2 k vs 18.1 k sequence-steps/s, profiles/r04l_*); 0 = A/B side
+    const int ablate = knob::once<knob::WH_XABS_ABLATE>();  // timing probe (garbage results): 1 no LDS-DMA in the loop, 2 no S / softmax / P V work, 3 both
     if (a.dbg || ablate) { XabsArgs b = a; b.ablate = ablate; launch_attn_any<CW, NHT, true, false>(b, st); return; }      // the stamped instantiation (tools/xabs_timeline.py)
     // beam search (cross_div > 1: the beams of an audio read ONE encoder output): cacheable loads - the workgroups of an audio's beams are
     // dispatched back to back onto one XCD (4 consecutive slots per group) and the later ones are meant to hit the first one's lines in its L2
@@ -681,11 +661,9 @@ void launch_xabs_attn(const XabsArgs& a, hipStream_t st) {
 
 void launch_xabs_vup(const XabsArgs& a, int n_bt, hipStream_t st) {
     ProfScope ps_(KK_DEC_XVUP, st);
-    // K slices: d / 16 k tiles over 4 waves x ks workgroups, TW tiles per wave; ks = 4 at the widths that are multiples of 256 (TW = d / 256),
-    // d = 384: 24 k tiles = 3 slices x 4 waves x 2 tiles
-    const int ks = a.d == 384 ? 3 : 4;
-    const int nx = a.n_head * ks;
-    const unsigned grid = (unsigned)(((nx + 7) / 8) * 8 * n_bt);
+    const plan::XabsVupPlan p = plan::xabs_vup_plan(a.d, a.n_head, n_bt);
+    const int ks = p.ks;
+    const unsigned grid = p.grid;
 #define XVUP(S_) do { switch (a.d / 256) { \
         case 1: xabs_vup_kernel<S_, 2><<<grid, 256, 0, st>>>(a, ks, n_bt); break; \
         case 2: xabs_vup_kernel<S_, 2><<<grid, 256, 0, st>>>(a, ks, n_bt); break; \
