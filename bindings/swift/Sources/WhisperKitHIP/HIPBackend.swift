@@ -54,8 +54,13 @@ public final class HIPSession {
     /// fp32 accumulator: end-to-end logits within 1e-3 sigma of fp32 openai/whisper, for about twice the encoder's matrix work and the 24-bit K / V rows
     /// (369 MB per slot at large-v3; `.automatic` cross-attention resolves to `.keyValueRows`, `.absorbed` throws).
     public enum EncoderPrecision: Int32 { case float16 = 0, split = 1 }
+    /// Where the word timestamps of the transcribe calls align a window (wh_session_set_word_alignment): `.host` (default) = per slot the [224][1500]
+    /// matrix to the host and dynamicTimeWarping on the calling thread; `.device` = per device batch one head-mean launch, one batched DTW launch
+    /// (csrc/align.hip) and one copy of the paths.  The paths, and so every word timing, are the same in both, index for index.
+    public enum WordAlignment: Int32 { case host = 0, device = 1 }
+    public var wordAlignment: WordAlignment = .host { didSet { _ = wh_session_set_word_alignment(handle, wordAlignment.rawValue) } }
     public init(model: HIPModel, maxBatch: Int = 1, crossAttention: CrossAttentionMode = .automatic, keySplits: Int = 0, slotsPerWorkgroup: Int = 0,
-                encoderPrecision: EncoderPrecision = .float16) throws {
+                encoderPrecision: EncoderPrecision = .float16, wordAlignment: WordAlignment = .host) throws {
         var h: OpaquePointer?
         if slotsPerWorkgroup > 0 || encoderPrecision != .float16 {
             var o = wh_session_options()
@@ -69,6 +74,8 @@ public final class HIPSession {
             try check(wh_session_create_tuned(model.handle, Int32(maxBatch), crossAttention.rawValue, Int32(keySplits), &h))
         }
         handle = h!; self.model = model
+        self.wordAlignment = wordAlignment
+        try check(wh_session_set_word_alignment(handle, wordAlignment.rawValue))        // (didSet does not run inside init)
     }
     deinit { wh_session_set_window_hooks(handle, nil); hookBox?.release(); wh_session_destroy(handle) }
 

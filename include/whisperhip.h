@@ -313,6 +313,22 @@ int wh_get_alignment_weights(wh_session* s, int b, float* out_host /* [224][1500
  * CoreML bundles bake it in is not published: default off (z_normalize 0, median_filter_width 0). */
 int wh_session_set_alignment_postprocess(wh_session* s, int z_normalize, int median_filter_width);
 
+/* Where the word-timestamp alignment of wh_transcribe* runs.  0 = host (default): per slot the head mean, the [224][1500] matrix to the
+ * host, a stream synchronise and wh_dynamic_time_warping on the calling thread.  1 = device: per device batch ONE head-mean launch, one
+ * batched DTW launch (csrc/align.hip) and one copy of the paths (at most rows + 1500 index pairs per slot).  The paths, and with them every
+ * word timing, are identical in both modes, index for index.  wh_session_word_alignment returns the mode, -1 for NULL. */
+int wh_session_set_word_alignment(wh_session* s, int mode);
+int wh_session_word_alignment(const wh_session* s);
+/* The alignment paths of slots [0, batch) after a decode, whatever the mode: head mean of all slots in one launch (with
+ * wh_session_set_alignment_postprocess on: the per-slot post-processing launches back to back), one DTW launch over rows[b] token rows of
+ * slot b (0 <= rows[b] <= 256; 0 = no path, rows beyond the 224 recorded ones read as zero), one device -> host copy, one synchronise.
+ * Slot b's path lands at b * capacity_per_slot, lengths[b] is its length (-length when it exceeds capacity_per_slot: nothing written). */
+int wh_alignment_paths(wh_session* s, int batch, const int32_t* rows, int32_t* text_idx, int32_t* time_idx, int32_t* lengths,
+                       int capacity_per_slot);
+/* Counters of the session since its creation: launches of the batched DTW kernel, bytes copied device -> host for the alignment
+ * (wh_get_alignment_weights, wh_alignment_paths and the word timestamps of wh_transcribe*).  Either pointer may be NULL. */
+int wh_session_word_alignment_stats(const wh_session* s, int64_t* dtw_launches, int64_t* alignment_d2h_bytes);
+
 /* A device-resident stage output as a plain tensor descriptor (what the MLMultiArray results of the CoreML stages,
  * Core/Models.swift:848-1107, become behind a C ABI): row-major, `device` = HIP device ordinal (the session's model device). The
  * memory stays owned by the session and is valid until the stage runs again on that session. */
@@ -574,6 +590,17 @@ int wh_transcription_create(const wh_tokenizer* tok, const wh_special_tokens* st
 int wh_transcription_add_window(wh_transcription* t, const wh_tokenizer* tok, const wh_decoding_options* opt,
                                 const wh_special_tokens* st, const wh_decoding_result* res, const float* alignment,
                                 int default_language_token, int segment_size, int32_t* seek_inout);
+/* wh_transcription_add_window with the window's alignment path (wh_dynamic_time_warping / wh_alignment_paths over the first
+ * wh_word_alignment_rows rows of the alignment weights) in place of the matrix: the same function body, minus its DTW call.
+ * text_idx == NULL or time_idx == NULL = no word timestamps. */
+int wh_transcription_add_window_path(wh_transcription* t, const wh_tokenizer* tok, const wh_decoding_options* opt,
+                                     const wh_special_tokens* st, const wh_decoding_result* res, const int32_t* text_idx,
+                                     const int32_t* time_idx, int path_len, int default_language_token, int segment_size,
+                                     int32_t* seek_inout);
+/* Rows of the alignment matrix that the word timestamps of one decoded window run the DTW over: the token count of the window's
+ * segments with a tokenizer (0 when the window has none), res->n_tokens without one.  It depends on the result's tokens and the
+ * options only, not on the window's seek.  -1 on an invalid argument. */
+int wh_word_alignment_rows(const wh_decoding_result* res, const wh_decoding_options* opt, const wh_special_tokens* st, int has_tokenizer);
 /* finalizeTranscriptionResult (Core/TranscribeTask.swift:297-312): result text and language code (needs a tokenizer) */
 int wh_transcription_finalize(wh_transcription* t, const wh_tokenizer* tok, const wh_decoding_options* opt,
                               const wh_special_tokens* st);
@@ -617,6 +644,12 @@ float wh_compression_ratio_text(const char* utf8, int nbytes);      /* TextUtili
 int wh_trimming_special_token_characters(const char* text, char* out, int capacity);
 /* SegmentSeeker.dynamicTimeWarping (Core/Text/SegmentSeeker.swift:195-278); returns path length */
 int wh_dynamic_time_warping(const float* matrix, int rows, int cols, int32_t* text_indices, int32_t* time_indices, int capacity);
+/* The same on HIP device `device` for n matrices in one launch (csrc/align.hip; needs no session and no model): matrices_host
+ * [n][rows_stride][cols], 1 <= rows[k] <= 256 (rows at or beyond rows_stride read as zero), 1 <= cols <= 1500, anything else is
+ * WH_ERR_INVALID_ARGUMENT.  Path k lands at k * capacity_per_matrix, lengths[k] is its length (-length when it exceeds the capacity:
+ * nothing written for that matrix).  Paths are identical to wh_dynamic_time_warping's, index for index. */
+int wh_dynamic_time_warping_device(int device, const float* matrices_host, int n, const int32_t* rows, int rows_stride, int cols,
+                                   int32_t* text_idx, int32_t* time_idx, int32_t* lengths, int capacity_per_matrix);
 /* DecodingFallback.init? (Core/Models.swift:357-381) -> WH_FALLBACK_*; *needs_fallback set */
 int wh_decoding_fallback(const wh_decoding_options* opt, int is_first_token_logprob_too_low, float no_speech_prob,
                          float compression_ratio, float avg_logprob, int32_t* needs_fallback);

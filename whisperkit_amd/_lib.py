@@ -186,6 +186,10 @@ SYMBOLS = {
     "wh_get_logits_device": (I, [VP, PVP]),
     "wh_session_set_cancel_flag": (I, [VP, VP]),
     "wh_session_set_alignment_postprocess": (I, [VP, I, I]),
+    "wh_session_set_word_alignment": (I, [VP, I]),
+    "wh_session_word_alignment": (I, [VP]),
+    "wh_alignment_paths": (I, [VP, I, PI32, PI32, PI32, PI32, I]),
+    "wh_session_word_alignment_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "wh_prefill_prompt": (I, [VP, POPT, PST, C.c_int32, PI32, I]),
     "wh_transcribe": (I, [VP, VP, I, POPT, PST, PVP]),
     "wh_transcribe_batch": (I, [VP, PVP, PI32, I, POPT, PST, PVP]),
@@ -225,6 +229,8 @@ SYMBOLS = {
                                                  PF, PF, PVP]),
     "wh_transcription_create": (I, [VP, PST, C.POINTER(WhSegment), I, PI32, PF, I, I, I, F, C.POINTER(WhTimings), PVP]),
     "wh_transcription_add_window": (I, [VP, VP, POPT, PST, C.POINTER(WhDecodingResult), PF, I, I, PI32]),
+    "wh_transcription_add_window_path": (I, [VP, VP, POPT, PST, C.POINTER(WhDecodingResult), PI32, PI32, I, I, I, PI32]),
+    "wh_word_alignment_rows": (I, [C.POINTER(WhDecodingResult), POPT, PST, I]),
     "wh_transcription_finalize": (I, [VP, VP, POPT, PST]),
     "wh_transcription_apply_seek_offset": (I, [VP, I]),
     "wh_transcription_to_json": (I, [VP, C.c_char_p, I]),
@@ -242,6 +248,7 @@ SYMBOLS = {
     "wh_compression_ratio_text": (F, [C.c_char_p, I]),
     "wh_trimming_special_token_characters": (I, [C.c_char_p, C.c_char_p, I]),
     "wh_dynamic_time_warping": (I, [PF, I, I, PI32, PI32, I]),
+    "wh_dynamic_time_warping_device": (I, [I, PF, I, PI32, I, I, PI32, PI32, PI32, I]),
     "wh_decoding_fallback": (I, [POPT, I, F, F, F, PI32]),
     "wh_find_seek_point_and_segments": (I, [C.POINTER(WhDecodingResult), POPT, PST, I, I, I, PI32, C.POINTER(WhSegment), I]),
     "wh_prepare_seek_clips": (I, [POPT, I, PI32, PI32, I]),

@@ -823,6 +823,39 @@ class Session:
         applied by getAlignmentWeights and the word timestamps; default off like the reference's host code."""
         _check(self.lib.wh_session_set_alignment_postprocess(self.handle, int(zNormalize), int(medianFilterWidth)))
 
+    WORD_ALIGNMENTS = {"host": 0, "device": 1}
+
+    def setWordAlignment(self, mode: str):
+        """Where the word timestamps of transcribe* align a window: "host" (default) - per slot the [224][1500] matrix to the host and
+        dynamicTimeWarping on the calling thread; "device" - per device batch one head-mean launch, one batched DTW launch (csrc/align.hip)
+        and one copy of the paths.  The paths, and so every word timing, are the same in both modes, index for index."""
+        if mode not in self.WORD_ALIGNMENTS:
+            raise ValueError(f"wordAlignment {mode!r}: expected 'host' or 'device'")
+        _check(self.lib.wh_session_set_word_alignment(self.handle, self.WORD_ALIGNMENTS[mode]))
+
+    @property
+    def wordAlignment(self) -> str:
+        return {0: "host", 1: "device"}[int(self.lib.wh_session_word_alignment(self.handle))]
+
+    def alignmentPaths(self, batch: int, rows: Sequence[int]) -> List[Tuple[List[int], List[int]]]:
+        """The DTW paths (textIndices, timeIndices) of slots [0, batch) over the first rows[b] alignment rows of slot b, after a decode:
+        one head-mean launch, one batched DTW launch, one copy (wh_alignment_paths; works in either wordAlignment mode)."""
+        r = np.ascontiguousarray(list(rows), dtype=np.int32)
+        if len(r) != batch:
+            raise ValueError("alignmentPaths: one row count per slot")
+        cap = int(r.max(initial=0)) + L.AUDIO_CTX
+        ti, tj = np.zeros((batch, cap), np.int32), np.zeros((batch, cap), np.int32)
+        n = np.zeros(batch, np.int32)
+        _check(self.lib.wh_alignment_paths(self.handle, batch, r.ctypes.data_as(L.PI32), ti.ctypes.data_as(L.PI32), tj.ctypes.data_as(L.PI32),
+                                           n.ctypes.data_as(L.PI32), cap))
+        return [(ti[b, :n[b]].tolist(), tj[b, :n[b]].tolist()) for b in range(batch)]
+
+    def wordAlignmentStats(self) -> Tuple[int, int]:
+        """(launches of the batched DTW kernel, bytes copied device -> host for the alignment) since the session was created"""
+        a, b = C.c_int64(), C.c_int64()
+        _check(self.lib.wh_session_word_alignment_stats(self.handle, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
     def setCancelFlag(self, flag: Optional["C.c_int32"]):
         """Task.checkCancellation: a ctypes.c_int32 polled by the running call (non-zero -> WhisperError code 102); None removes it.
         The object is kept alive by the session."""
@@ -950,6 +983,25 @@ def dynamicTimeWarping(matrix: np.ndarray):
     if n < 0:
         raise WhisperError(6, "dynamicTimeWarping failed")
     return list(ti[:n]), list(tj[:n])
+
+
+def dynamicTimeWarpingBatch(matrices, rows: Optional[Sequence[int]] = None, device: int = 0):
+    """dynamicTimeWarping of n matrices [n][rowsStored][cols] in one launch on HIP device `device` (wh_dynamic_time_warping_device):
+    [(textIndices, timeIndices)] per matrix, identical to dynamicTimeWarping(matrices[k][:rows[k]]).  rows[k] (default: rowsStored) may
+    exceed rowsStored: the missing rows are zero.  1 <= rows[k] <= 256, 1 <= cols <= 1500."""
+    m = np.ascontiguousarray(matrices, dtype=np.float32)
+    if m.ndim != 3:
+        raise ValueError("dynamicTimeWarpingBatch: matrices must be [n][rows][cols]")
+    n, stored, cols = m.shape
+    r = np.ascontiguousarray([stored] * n if rows is None else list(rows), dtype=np.int32)
+    if len(r) != n:
+        raise ValueError("dynamicTimeWarpingBatch: one row count per matrix")
+    cap = int(r.max(initial=1)) + cols
+    ti, tj = np.zeros((n, cap), np.int32), np.zeros((n, cap), np.int32)
+    ln = np.zeros(n, np.int32)
+    _check(L.load().wh_dynamic_time_warping_device(int(device), m.ctypes.data_as(L.PF), n, r.ctypes.data_as(L.PI32), stored, cols,
+                                                   ti.ctypes.data_as(L.PI32), tj.ctypes.data_as(L.PI32), ln.ctypes.data_as(L.PI32), cap))
+    return [(ti[k, :ln[k]].tolist(), tj[k, :ln[k]].tolist()) for k in range(n)]
 
 
 def decodingFallback(options: DecodingOptions, isFirstTokenLogProbTooLow: bool, noSpeechProb: float, compressionRatio_: float, avgLogProb: float):
@@ -1116,7 +1168,9 @@ class WindowAssembler:
         _check(self.lib.wh_transcription_create(None, C.byref(self.st), None, 0, None, None, 0, -1, 0, float("nan"), None, C.byref(self.handle)))
 
     def addWindow(self, result: DecodingResult, seek: int, segmentSize: int, alignmentWeights: Optional[np.ndarray] = None,
-                  defaultLanguageToken: int = -1) -> int:
+                  defaultLanguageToken: int = -1, alignmentPath: Optional[Tuple[Sequence[int], Sequence[int]]] = None) -> int:
+        """alignmentPath = (textIndices, timeIndices) of the window's DTW path (Session.alignmentPaths, dynamicTimeWarpingBatch) in place of
+        alignmentWeights: wh_transcription_add_window_path."""
         r = L.WhDecodingResult()
         r.n_tokens = len(result.tokens)
         for i, (t, l) in enumerate(zip(result.tokens, result.tokenLogProbs)):
@@ -1129,6 +1183,13 @@ class WindowAssembler:
             a = np.zeros((L.MAX_TOKEN_CONTEXT, L.AUDIO_CTX), np.float32)
             a[:len(alignmentWeights)] = alignmentWeights[:L.MAX_TOKEN_CONTEXT]
         sk = C.c_int32(seek)
+        if alignmentPath is not None:
+            ti = np.ascontiguousarray(list(alignmentPath[0]) or [0], dtype=np.int32)
+            tj = np.ascontiguousarray(list(alignmentPath[1]) or [0], dtype=np.int32)
+            _check(self.lib.wh_transcription_add_window_path(self.handle, self.tokenizer.handle if self.tokenizer else None, C.byref(o), C.byref(self.st),
+                                                             C.byref(r), ti.ctypes.data_as(L.PI32), tj.ctypes.data_as(L.PI32), len(alignmentPath[0]),
+                                                             defaultLanguageToken, segmentSize, C.byref(sk)))
+            return sk.value
         _check(self.lib.wh_transcription_add_window(self.handle, self.tokenizer.handle if self.tokenizer else None, C.byref(o), C.byref(self.st),
                                                     C.byref(r), None if a is None else a.ctypes.data_as(L.PF), defaultLanguageToken, segmentSize,
                                                     C.byref(sk)))

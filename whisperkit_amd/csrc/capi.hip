@@ -572,6 +572,8 @@ extern "C" void wh_session_destroy(wh_session* s) {
     if (s->d32_blob) hipFree(s->d32_blob);
     if (s->xabs_blob) hipFree(s->xabs_blob);
     if (s->align_tmp) hipFree(s->align_tmp);
+    if (s->dtw_dev) hipFree(s->dtw_dev);
+    if (s->dtw_host) hipHostFree(s->dtw_host);
     void* ptrs[] = {s->pcm, s->n_valid, s->logspec, s->maxkey, s->mel_t, s->mel_f32, s->h1, s->x, s->xn, s->q16, s->k16, s->vt16, s->att16,
                     s->hmlp, s->enc16, s->enc32, s->cross_k_hi, s->cross_v_hi, s->cross_k_lo, s->cross_v_lo, s->self_k, s->self_v, s->part, s->ticket, s->logits,
                     s->align, s->align_mean, s->seq, s->cfg_dev, s->suppress_dev, s->sup_mask_dev, s->stats, s->tok_out_dev, s->lp_out_dev, s->scratch_logits,
@@ -886,27 +888,117 @@ extern "C" int wh_predict_logits(wh_session* s, int batch, const int32_t* tokens
     return WH_OK;
 }
 
+// scratch of the optional alignment post-processing (one slot at a time), sized for the session's current alignment-head count
+static int ensure_align_tmp(wh_session* s) {
+    const size_t H = (size_t)s->n_align_alloc;
+    if (s->align_tmp && s->align_tmp_heads != s->n_align_alloc) { WH_HIP(hipStreamSynchronize(s->st)); hipFree(s->align_tmp); s->align_tmp = nullptr; }
+    if (!s->align_tmp) {
+        WH_HIP(hipMalloc((void**)&s->align_tmp, ((size_t)kMaxTok * H * kCtx + 2 * H * kCtx + 256) * sizeof(float)));
+        s->align_tmp_heads = s->n_align_alloc;
+    }
+    return WH_OK;
+}
+// slot b's [224][1500] alignment weights into align_mean: the optional post-processing, else the plain head mean
+static void launch_alignment_slot(wh_session* s, int b, bool postprocess) {
+    const size_t n = (size_t)kMaxTok * kCtx, H = (size_t)s->n_align_alloc;
+    if (postprocess) {
+        float* stat = s->align_tmp + (size_t)kMaxTok * H * kCtx;
+        launch_alignment_postprocess(s->align + (size_t)b * n * H, s->n_align_alloc, s->align_tmp, stat, reinterpret_cast<int*>(stat + 2 * H * kCtx),
+                                     s->align_znorm, s->align_median, s->align_mean + b * n, s->st);
+    } else {
+        launch_alignment_mean(s->align + (size_t)b * n * H, 1, s->n_align_alloc, s->align_mean + b * n, s->st);   // this slot only
+    }
+}
+
 extern "C" int wh_get_alignment_weights(wh_session* s, int b, float* out) {
     CHECK_SESSION(s); CHECK_SLOT(s, b);
     if (!out) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_get_alignment_weights: null output");
     if (!s->align) return set_error(WH_ERR_SEGMENTING_FAILED, "no alignment weights recorded (run a decode with word timestamps / the step API first)");
     size_t n = (size_t)kMaxTok * kCtx;
-    if (s->align_znorm || s->align_median > 1) {
-        const size_t H = (size_t)s->n_align_alloc;
-        if (s->align_tmp && s->align_tmp_heads != s->n_align_alloc) { WH_HIP(hipStreamSynchronize(s->st)); hipFree(s->align_tmp); s->align_tmp = nullptr; }
-        if (!s->align_tmp) {
-            WH_HIP(hipMalloc((void**)&s->align_tmp, ((size_t)kMaxTok * H * kCtx + 2 * H * kCtx + 256) * sizeof(float)));
-            s->align_tmp_heads = s->n_align_alloc;
-        }
-        float* stat = s->align_tmp + (size_t)kMaxTok * H * kCtx;
-        launch_alignment_postprocess(s->align + (size_t)b * n * H, s->n_align_alloc, s->align_tmp, stat, reinterpret_cast<int*>(stat + 2 * H * kCtx),
-                                     s->align_znorm, s->align_median, s->align_mean + b * n, s->st);
-    } else {
-        launch_alignment_mean(s->align + (size_t)b * n * s->n_align_alloc, 1, s->n_align_alloc, s->align_mean + b * n, s->st);   // this slot only
-    }
+    const bool postprocess = s->align_znorm || s->align_median > 1;
+    if (postprocess) { int r = ensure_align_tmp(s); if (r) return r; }
+    launch_alignment_slot(s, b, postprocess);
     WH_CHECK_LAUNCH();
     WH_HIP(hipMemcpyAsync(out, s->align_mean + b * n, n * 4, hipMemcpyDeviceToHost, s->st));
     WH_HIP(hipStreamSynchronize(s->st));
+    s->align_d2h_bytes += (long long)(n * 4);
+    return WH_OK;
+}
+
+// ---- word-timestamp alignment on the device (align.hip) -------------------------------------------
+namespace whi {
+int alignment_paths(wh_session* s, int batch, const int32_t* rows, const int32_t** len, const int32_t** ti, const int32_t** tj) {
+    if (!s->align) return set_error(WH_ERR_SEGMENTING_FAILED, "no alignment weights recorded (run a decode with word timestamps / the step API first)");
+    const size_t B = (size_t)s->B, cap = (size_t)kDtwPathCap;
+    int max_rows = 0;
+    for (int b = 0; b < batch; ++b) {
+        if (rows[b] < 0 || rows[b] > kDtwMaxRows) return set_error(WH_ERR_INVALID_ARGUMENT, "alignment paths: rows[%d] = %d outside [0, %d]", b, rows[b], kDtwMaxRows);
+        max_rows = std::max(max_rows, (int)rows[b]);
+    }
+    if (!s->dtw_dev) {
+        WH_HIP(hipMalloc((void**)&s->dtw_dev, (2 * B + 2 * B * cap) * sizeof(int)));
+        if (hipHostMalloc((void**)&s->dtw_host, (B + 2 * B * cap) * sizeof(int32_t)) != hipSuccess) {
+            hipFree(s->dtw_dev); s->dtw_dev = nullptr;
+            return set_error(WH_ERR_HIP, "hipHostMalloc of the alignment path buffer failed");
+        }
+    }
+    int* rows_dev = s->dtw_dev;
+    int* len_dev = rows_dev + B;                      // lengths | text_idx | time_idx are contiguous: one copy brings them back
+    int *ti_dev = len_dev + B, *tj_dev = ti_dev + B * cap;
+    *len = s->dtw_host; *ti = s->dtw_host + B; *tj = s->dtw_host + B + B * cap;
+    if (max_rows == 0) {                              // no slot has a token row: nothing to launch
+        memset(s->dtw_host, 0, B * sizeof(int32_t));
+        return WH_OK;
+    }
+    const bool postprocess = s->align_znorm || s->align_median > 1;
+    if (postprocess) {
+        int r = ensure_align_tmp(s); if (r) return r;
+        for (int b = 0; b < batch; ++b) launch_alignment_slot(s, b, true);       // back to back: the scratch is reused in stream order
+    } else {
+        launch_alignment_mean(s->align, batch, s->n_align_alloc, s->align_mean, s->st);
+    }
+    WH_CHECK_LAUNCH();
+    WH_HIP(hipMemcpyAsync(rows_dev, rows, sizeof(int) * (size_t)batch, hipMemcpyHostToDevice, s->st));
+    int r = launch_dtw_batch(s->align_mean, rows_dev, batch, max_rows, kMaxTok, kCtx, ti_dev, tj_dev, len_dev, kDtwPathCap, s->st);
+    if (r) return r;
+    s->dtw_launches += 1;
+    // slots [0, batch) of the three arrays: lengths, then the two index arrays up to the last slot in use
+    const size_t nbytes = (B + B * cap + (size_t)batch * cap) * sizeof(int32_t);
+    WH_HIP(hipMemcpyAsync(s->dtw_host, len_dev, nbytes, hipMemcpyDeviceToHost, s->st));
+    WH_HIP(hipStreamSynchronize(s->st));
+    s->align_d2h_bytes += (long long)nbytes;
+    return WH_OK;
+}
+}  // namespace whi
+
+extern "C" int wh_alignment_paths(wh_session* s, int batch, const int32_t* rows, int32_t* text_idx, int32_t* time_idx, int32_t* lengths,
+                                  int capacity_per_slot) {
+    CHECK_SESSION(s); CHECK_BATCH(s, batch);
+    if (!rows || !text_idx || !time_idx || !lengths || capacity_per_slot < 1) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_alignment_paths: null or empty argument");
+    const int32_t *len = nullptr, *ti = nullptr, *tj = nullptr;
+    int r = whi::alignment_paths(s, batch, rows, &len, &ti, &tj);
+    if (r) return r;
+    for (int b = 0; b < batch; ++b) {
+        const int n = len[b];
+        if (n > capacity_per_slot) { lengths[b] = -n; continue; }
+        lengths[b] = n;
+        memcpy(text_idx + (size_t)b * capacity_per_slot, ti + (size_t)b * kDtwPathCap, sizeof(int32_t) * (size_t)std::max(n, 0));
+        memcpy(time_idx + (size_t)b * capacity_per_slot, tj + (size_t)b * kDtwPathCap, sizeof(int32_t) * (size_t)std::max(n, 0));
+    }
+    return WH_OK;
+}
+
+extern "C" int wh_session_set_word_alignment(wh_session* s, int mode) {
+    if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_word_alignment: null session");
+    if (mode != 0 && mode != 1) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_word_alignment: mode %d (0 = host, 1 = device)", mode);
+    s->word_alignment = mode;
+    return WH_OK;
+}
+extern "C" int wh_session_word_alignment(const wh_session* s) { return s ? s->word_alignment : -1; }
+extern "C" int wh_session_word_alignment_stats(const wh_session* s, int64_t* dtw_launches, int64_t* alignment_d2h_bytes) {
+    if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_word_alignment_stats: null session");
+    if (dtw_launches) *dtw_launches = s->dtw_launches;
+    if (alignment_d2h_bytes) *alignment_d2h_bytes = s->align_d2h_bytes;
     return WH_OK;
 }
 

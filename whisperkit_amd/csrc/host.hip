@@ -771,6 +771,17 @@ static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_
             if (!any) break;
         }
         double t4 = now_s();
+        // ---- word alignment on the device (wh_session_set_word_alignment 1): every slot's DTW row count is known from its result alone
+        // (wh_word_alignment_rows), so the whole batch is aligned by one head-mean launch, one DTW launch and one copy of the paths
+        const bool device_paths = s->word_alignment == 1 && opt->word_timestamps && s->align;
+        const int32_t *path_len = nullptr, *path_ti = nullptr, *path_tj = nullptr;
+        double device_align_s = 0;
+        if (device_paths) {
+            std::vector<int32_t> rows(nb);
+            for (int b = 0; b < nb; ++b) { rows[b] = wh_word_alignment_rows(&res[b], opt, st, s->tok != nullptr); if (rows[b] < 0) return WH_ERR_SEGMENTING_FAILED; }
+            r = whi::alignment_paths(s, nb, rows.data(), &path_len, &path_ti, &path_tj); if (r) return r;
+            device_align_s = now_s() - t4;
+        }
         // ---- windowing (TranscribeTask.swift:175-278)
         for (int b = 0; b < nb; ++b) {
             AudioJob& j = jobs[slot_job[b]];
@@ -778,7 +789,7 @@ static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_
             // "Windowing" (TranscribeTask.swift:175-265) is host-only code shared with the CPU tests: wh_transcription_add_window
             std::vector<float> full;
             const float* alignment = nullptr;
-            if (opt->word_timestamps && s->align) {
+            if (opt->word_timestamps && s->align && !device_paths) {
                 full.resize((size_t)kMaxTok * kCtx);
                 r = wh_get_alignment_weights(s, b, full.data()); if (r) return r;
                 alignment = full.data();
@@ -786,7 +797,14 @@ static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_
             const double windows_before = tr->timings.total_decoding_windows;
             int32_t seek = j.seek;
             const int seg_before = (int)tr->segments.size();
-            r = wh_transcription_add_window(tr, s->tok, opt, st, &res[b], alignment, lang_slot[b], j.cur_size, &seek); if (r) return r;
+            if (device_paths) {
+                r = wh_transcription_add_window_path(tr, s->tok, opt, st, &res[b], path_ti + (size_t)b * kDtwPathCap, path_tj + (size_t)b * kDtwPathCap,
+                                                     path_len[b], lang_slot[b], j.cur_size, &seek);
+                tr->timings.decoding_word_timestamps += device_align_s / nb;      // the batch's device stage, shared out like the other stages
+            } else {
+                r = wh_transcription_add_window(tr, s->tok, opt, st, &res[b], alignment, lang_slot[b], j.cur_size, &seek);
+            }
+            if (r) return r;
             j.seek = seek;
             if (tr->timings.total_decoding_windows > windows_before) {      // the window had segments (`guard let currentSegments`, :239-242)
                 int n_new = (int)tr->segments.size() - seg_before;

@@ -84,6 +84,11 @@ struct wh_session {
     int n_align_alloc = 0;                // alignment heads the `align` allocation was sized for
     int align_znorm = 0, align_median = 0;   // optional openai/whisper-style post-processing (wh_session_set_alignment_postprocess)
     float* align_tmp = nullptr; int align_tmp_heads = 0;   // [224][n_align][1500] softmax rows + [2][n_align][1500] statistics + 224 flags
+    // word-timestamp alignment (wh_session_set_word_alignment): 0 = per slot on the host, 1 = one batched DTW launch per device batch (align.hip)
+    int word_alignment = 0;
+    int* dtw_dev = nullptr;                // rows [B] | lengths [B] | text_idx [B][kDtwPathCap] | time_idx [B][kDtwPathCap], allocated on first use
+    int32_t* dtw_host = nullptr;           // pinned mirror of lengths | text_idx | time_idx
+    long long dtw_launches = 0, align_d2h_bytes = 0;   // wh_session_word_alignment_stats
     std::map<WhGraphKey, hipGraphExec_t> graphs;   // captured 8-step decode graphs of THIS session (no process-wide state)
     std::map<WhGraphKey, unsigned long long> graph_use;   // last use (a counter) per graph: the cache is capped, least recently used configuration first
     unsigned long long graph_tick = 0;
@@ -140,6 +145,8 @@ wh::DecodeBuffers decode_buffers(wh_session* s, int batch, int max_position = wh
 void drop_session_graphs(wh_session* s);
 int ensure_align(wh_session* s);          // (re)allocate the raw alignment-head score buffer for the model's current head set
 int reset_decoder_inputs_masked(wh_session* s, int batch, const int32_t* active);
+// wh_alignment_paths with the paths left in the session's pinned buffer: slot b's path at ti / tj + b * kDtwPathCap, its length at len[b]
+int alignment_paths(wh_session* s, int batch, const int32_t* rows, const int32_t** len, const int32_t** ti, const int32_t** tj);
 // host logic shared by wh_decode_text / wh_transcribe (host.hip)
 void transcription_truncate_segments(wh_transcription* t, int n_keep);     // results.cpp: drop segments [n_keep, end) with their tokens / words
 void finalize_decoding_result(const wh::SeqState& sq, const wh_decoding_options* opt, const wh_special_tokens* st,

@@ -339,6 +339,13 @@ void launch_alignment_mean(const float* align, int batch, int n_align, float* ou
 // openai/whisper-style alignment post-processing of one slot (z-normalise over the token rows, median filter, head mean)
 void launch_alignment_postprocess(const float* align, int n_align, float* prob_tmp, float* stat_tmp, int* row_written, int znorm, int median_width,
                                   float* out, hipStream_t st);
+// batched dynamic time warping (align.hip): one workgroup per matrix m[k] = [rows_stride][cols] (rows at or beyond rows_stride read as 0), rows_dev[k]
+// in [0, max_rows] (0: length 0), paths to text_idx / time_idx [n][capacity], lengths [n] (-length when a path exceeds capacity).  Returns WH_OK,
+// WH_ERR_INVALID_ARGUMENT (max_rows outside [1, kDtwMaxRows], cols outside [1, kDtwMaxCols]: nothing is launched) or WH_ERR_HIP.
+constexpr int kDtwThreads = 256, kDtwMaxRows = 256, kDtwMaxCols = 1500;
+constexpr int kDtwPathCap = kDtwMaxRows + kDtwMaxCols;      // no path is longer: every step moves up, left or both
+int launch_dtw_batch(const float* m, const int* rows_dev, int n, int max_rows, int rows_stride, int cols, int* text_idx, int* time_idx, int* lengths,
+                     int capacity, hipStream_t st);
 void launch_f32_to_f16(const float* in, f16* out, size_t n, hipStream_t st);
 void launch_f32_to_f16_split(const float* in, f16* hi, f16* lo, size_t n, hipStream_t st);     // split_f16 of every element
 void launch_f16_to_f32(const f16* in, float* out, size_t n, hipStream_t st);

@@ -97,11 +97,6 @@ extern "C" int wh_transcription_create(const wh_tokenizer* tok, const wh_special
 }
 
 // ---- TranscribeTask.run windowing ------------------------------------------------------------------------------------------
-namespace whi {
-int add_word_timestamps(const wh_tokenizer* tok, const char* language, int special_begin, wh_segment* segments, int n_segments,
-                        const int32_t* tokens, const float* logprobs, const float* alignment, int alignment_rows, int seek,
-                        float last_speech_timestamp, wh_transcription* tr);   // words.cpp
-}
 
 static std::string language_code_of(const wh_tokenizer* tok, int language_token) {
     // decodeText: language = tokenizer.decode([languageToken]).trimmingSpecialTokenCharacters() (TextDecoder.swift:814), default "en"
@@ -112,12 +107,10 @@ static std::string language_code_of(const wh_tokenizer* tok, int language_token)
 
 // Without a tokenizer the words cannot be grouped by text: every text token becomes one word timed by DTW over its alignment row
 // (findAlignment, SegmentSeeker.swift:340-408, with one token per word; no punctuation merge, no duration constraints).
-static void add_token_timestamps(const float* full, const wh_decoding_result& res, const wh_special_tokens* st, wh_segment* segs, int ns,
-                                 int seek, wh_transcription* win) {
-    const int n = res.n_tokens, cols = WH_AUDIO_CTX;
-    int cap = n + cols + 8;
-    std::vector<int32_t> ti(cap), tj(cap);
-    int len = wh_dynamic_time_warping(full, n, cols, ti.data(), tj.data(), cap);
+// (ti, tj)[0, len) is the DTW path over the alignment rows of all res.n_tokens tokens.
+static void add_token_timestamps(const int32_t* ti, const int32_t* tj, int len, const wh_decoding_result& res, const wh_special_tokens* st,
+                                 wh_segment* segs, int ns, int seek, wh_transcription* win) {
+    const int n = res.n_tokens;
     if (len <= 0) return;
     std::vector<float> startT{0.0f}, endT;
     int cur = ti[0];
@@ -145,16 +138,38 @@ static void add_token_timestamps(const float* full, const wh_decoding_result& re
     }
 }
 
+// Rows of the alignment matrix the word timestamps of a window run the DTW over, given the window's segments (ns < 0: none): the segments'
+// tokens with a tokenizer (addWordTimestamps aligns those), every result token without one.
+static int alignment_rows_of(const wh_decoding_result* res, const wh_segment* segs, int ns, bool has_tokenizer) {
+    if (!has_tokenizer) return res->n_tokens;
+    int rows = 0;
+    for (int i = 0; i < ns; ++i) rows += segs[i].n_tokens;
+    return rows;
+}
+
+// The segments of findSeekPointAndSegments - their count and token ranges, and whether the window is skipped - follow from the result's
+// tokens, its no-speech / log-prob figures and the options alone: the seek only shifts the segment times.  So the row count is known
+// before the windowing runs, which lets wh_transcribe* align a whole device batch in one launch.
+extern "C" int wh_word_alignment_rows(const wh_decoding_result* res, const wh_decoding_options* opt, const wh_special_tokens* st, int has_tokenizer) {
+    if (!res || !opt || !st || res->n_tokens < 0 || res->n_tokens > WH_MAX_RESULT_TOKENS) { set_error(WH_ERR_INVALID_ARGUMENT, "wh_word_alignment_rows: invalid argument"); return -1; }
+    wh_segment segs[WH_MAX_RESULT_TOKENS];
+    int32_t new_seek = 0;
+    const int ns = wh_find_seek_point_and_segments(res, opt, st, 0, 0, WH_WINDOW_SAMPLES, &new_seek, segs, WH_MAX_RESULT_TOKENS);
+    if (ns < -1) { set_error(WH_ERR_SEGMENTING_FAILED, "findSeekPointAndSegments failed"); return -1; }
+    return alignment_rows_of(res, segs, ns, has_tokenizer != 0);
+}
+
 // The "Windowing" block of TranscribeTask.run (Core/TranscribeTask.swift:175-265) for one decoded window: findSeekPointAndSegments,
 // seek never moves backward, optional addWordTimestamps (zero-length segments dropped, seek refined with the last word's end),
-// maxWindowSeek clamp, segments / tokens appended to the transcription.  `alignment` = [224][1500] alignment weights of the window
-// or NULL (no word timestamps).  *seek_inout: window seek in, next seek out.
-extern "C" int wh_transcription_add_window(wh_transcription* tr, const wh_tokenizer* tok, const wh_decoding_options* opt,
-                                           const wh_special_tokens* st, const wh_decoding_result* res, const float* alignment,
-                                           int default_language_token, int segment_size, int32_t* seek_inout) {
-    if (!tr || !opt || !st || !res || !seek_inout) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_transcription_add_window: null argument");
+// maxWindowSeek clamp, segments / tokens appended to the transcription.  Word timestamps come from `alignment` ([224][1500] alignment
+// weights of the window: the DTW runs here, on the host) or from a path computed elsewhere (path_ti / path_tj / path_len); neither = no
+// word timestamps.  *seek_inout: window seek in, next seek out.
+static int add_window(const char* name, wh_transcription* tr, const wh_tokenizer* tok, const wh_decoding_options* opt, const wh_special_tokens* st,
+                      const wh_decoding_result* res, const float* alignment, const int32_t* path_ti, const int32_t* path_tj, int path_len,
+                      int default_language_token, int segment_size, int32_t* seek_inout) {
+    if (!tr || !opt || !st || !res || !seek_inout) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: null argument", name);
     if (res->n_tokens < 0 || res->n_tokens > WH_MAX_RESULT_TOKENS)
-        return set_error(WH_ERR_INVALID_ARGUMENT, "wh_transcription_add_window: n_tokens %d outside [0, %d]", res->n_tokens, WH_MAX_RESULT_TOKENS);
+        return set_error(WH_ERR_INVALID_ARGUMENT, "%s: n_tokens %d outside [0, %d]", name, res->n_tokens, WH_MAX_RESULT_TOKENS);
     if (!tr->language_set) { tr->language_token = res->language_token; tr->language_set = true; }   // "Use the predicted language if it was not detected ahead of time"
     const int prev_seek = *seek_inout;
     wh_segment segs[WH_MAX_RESULT_TOKENS];
@@ -163,18 +178,24 @@ extern "C" int wh_transcription_add_window(wh_transcription* tr, const wh_tokeni
     if (ns < -1) return set_error(WH_ERR_SEGMENTING_FAILED, "findSeekPointAndSegments failed");
     int seek = std::max(prev_seek, (int)new_seek);
     wh_transcription win;   // window-local words
-    const bool words = opt->word_timestamps && alignment;
+    const bool words = opt->word_timestamps && (alignment || (path_ti && path_tj));
     const auto tw0 = std::chrono::steady_clock::now();
     if (words) {
         if (ns < 0) ns = 0;   // `currentSegments ?? []` (:202)
+        std::vector<int32_t> host_ti, host_tj;
+        if (alignment) {      // the DTW call: the one thing the two entry points do differently
+            const int rows = alignment_rows_of(res, segs, ns, tok != nullptr);
+            path_len = rows > 0 ? whi::host_alignment_path(alignment, WH_MAX_TOKEN_CONTEXT, rows, host_ti, host_tj) : 0;
+            path_ti = host_ti.data(); path_tj = host_tj.data();
+        }
         const int window_language = res->language_token >= 0 ? res->language_token : default_language_token;
         if (tok) {
             const std::string code = language_code_of(tok, window_language);
-            int r = whi::add_word_timestamps(tok, code.c_str(), st->special_token_begin, segs, ns, res->tokens, res->token_logprobs, alignment,
-                                             WH_MAX_TOKEN_CONTEXT, prev_seek, (float)((double)prev_seek / (double)WH_SAMPLE_RATE), &win);
+            int r = whi::add_word_timestamps(tok, code.c_str(), st->special_token_begin, segs, ns, res->tokens, res->token_logprobs, path_ti, path_tj,
+                                             path_len, prev_seek, (float)((double)prev_seek / (double)WH_SAMPLE_RATE), &win);
             if (r) return r;
         } else {
-            add_token_timestamps(alignment, *res, st, segs, ns, prev_seek, &win);
+            add_token_timestamps(path_ti, path_tj, path_len, *res, st, segs, ns, prev_seek, &win);
         }
         tr->timings.total_timestamp_alignment_runs += 1;
         tr->words_enabled = true;
@@ -214,6 +235,22 @@ extern "C" int wh_transcription_add_window(wh_transcription* tr, const wh_tokeni
     }
     tr->timings.total_decoding_windows += 1;
     return WH_OK;
+}
+
+extern "C" int wh_transcription_add_window(wh_transcription* tr, const wh_tokenizer* tok, const wh_decoding_options* opt,
+                                           const wh_special_tokens* st, const wh_decoding_result* res, const float* alignment,
+                                           int default_language_token, int segment_size, int32_t* seek_inout) {
+    return add_window("wh_transcription_add_window", tr, tok, opt, st, res, alignment, nullptr, nullptr, 0, default_language_token, segment_size, seek_inout);
+}
+
+extern "C" int wh_transcription_add_window_path(wh_transcription* tr, const wh_tokenizer* tok, const wh_decoding_options* opt,
+                                                const wh_special_tokens* st, const wh_decoding_result* res, const int32_t* text_idx,
+                                                const int32_t* time_idx, int path_len, int default_language_token, int segment_size,
+                                                int32_t* seek_inout) {
+    if (path_len < 0 || path_len > WH_MAX_RESULT_TOKENS + WH_AUDIO_CTX + 8)
+        return set_error(WH_ERR_INVALID_ARGUMENT, "wh_transcription_add_window_path: path length %d out of range", path_len);
+    return add_window("wh_transcription_add_window_path", tr, tok, opt, st, res, nullptr, text_idx, time_idx, path_len, default_language_token, segment_size,
+                      seek_inout);
 }
 
 // Drop segments [n_keep, end) of a transcription together with their tokens, log-probs, words and texts (segments are appended in

@@ -48,6 +48,11 @@ float rounded2(float x);                                               // Float.
 
 // SegmentSeeker post-processing (Core/Text/SegmentSeeker.swift:280-338, 498-659)
 std::vector<Word> merge_punctuations(const std::vector<Word>& alignment, const std::string& prepended, const std::string& appended);
+// word timestamps of one window from its DTW path (words.cpp); host_alignment_path is the host's way to that path
+int host_alignment_path(const float* alignment, int alignment_rows, int rows, std::vector<int32_t>& ti, std::vector<int32_t>& tj);
+int add_word_timestamps(const wh_tokenizer* tok, const char* language, int special_begin, wh_segment* segments, int n_segments,
+                        const int32_t* tokens, const float* logprobs, const int32_t* ti, const int32_t* tj, int path_len, int seek,
+                        float last_speech_timestamp, wh_transcription* tr);
 extern const char* const kDefaultPrependPunctuations;
 extern const char* const kDefaultAppendPunctuations;
 

@@ -52,14 +52,25 @@ std::vector<Word> merge_punctuations(const std::vector<Word>& alignment, const s
     return out;
 }
 
-// findAlignment, SegmentSeeker.swift:340-408
-static int find_alignment(const wh_tokenizer* tok, const char* language, const std::vector<int>& word_token_ids, const float* matrix, int rows,
-                          const std::vector<float>& logprobs, std::vector<Word>& out) {
+// The DTW call of findAlignment on the host: the path over the first `rows` rows of `alignment` ([alignment_rows][1500]).  A result may carry
+// more tokens than the 224 alignment rows (the appended EOT): the missing rows are zero.  Returns the path length (< 0: the DTW failed).
+int host_alignment_path(const float* alignment, int alignment_rows, int rows, std::vector<int32_t>& ti, std::vector<int32_t>& tj) {
     const int cols = WH_AUDIO_CTX;
+    std::vector<float> padded;
+    if (rows > alignment_rows) {
+        padded.assign((size_t)rows * cols, 0.0f);
+        memcpy(padded.data(), alignment, sizeof(float) * (size_t)alignment_rows * cols);
+        alignment = padded.data();
+    }
     const int cap = rows + cols + 8;
-    std::vector<int32_t> ti(cap), tj(cap);
-    int len = wh_dynamic_time_warping(matrix, rows, cols, ti.data(), tj.data(), cap);
-    if (len < 0) return set_error(WH_ERR_SEGMENTING_FAILED, "dynamicTimeWarping failed on a %d x %d matrix", rows, cols);
+    ti.resize((size_t)cap); tj.resize((size_t)cap);
+    return wh_dynamic_time_warping(alignment, rows, cols, ti.data(), tj.data(), cap);
+}
+
+// findAlignment, SegmentSeeker.swift:340-408, after its dynamicTimeWarping call: (ti, tj)[0, len) is the path over the tokens' alignment rows
+static int find_alignment(const wh_tokenizer* tok, const char* language, const std::vector<int>& word_token_ids, const int32_t* ti, const int32_t* tj,
+                          int len, const std::vector<float>& logprobs, std::vector<Word>& out) {
+    if (len < 0) return set_error(WH_ERR_SEGMENTING_FAILED, "dynamicTimeWarping failed on a %d x %d matrix", (int)word_token_ids.size(), WH_AUDIO_CTX);
     std::vector<std::string> words;
     std::vector<std::vector<int>> word_tokens;
     tok->split_to_word_tokens(word_token_ids, language, words, word_tokens);
@@ -175,24 +186,19 @@ static void update_segments_with_word_timings(const wh_tokenizer* tok, int speci
     }
 }
 
-// addWordTimestamps, SegmentSeeker.swift:410-496, for one window.  `segments` index `tokens` / `logprobs`; row r of `alignment`
-// belongs to the r-th token of the segments in order.  Appends words (+ texts) to `tr` and rewrites segment start / end.
+// addWordTimestamps, SegmentSeeker.swift:410-496, for one window.  `segments` index `tokens` / `logprobs`; (ti, tj)[0, path_len) is the DTW
+// path over the alignment rows of the segments' tokens in order (row r = the r-th token; host_alignment_path or the device kernel of
+// align.hip - unused when the segments hold no token).  Appends words (+ texts) to `tr` and rewrites segment start / end.
 int add_word_timestamps(const wh_tokenizer* tok, const char* language, int special_begin, wh_segment* segments, int n_segments,
-                        const int32_t* tokens, const float* logprobs, const float* alignment, int alignment_rows, int seek,
+                        const int32_t* tokens, const float* logprobs, const int32_t* ti, const int32_t* tj, int path_len, int seek,
                         float last_speech_timestamp, wh_transcription* tr) {
     std::vector<int> ids;
     std::vector<float> lps;
     for (int s = 0; s < n_segments; ++s)
         for (int k = 0; k < segments[s].n_tokens; ++k) { ids.push_back(tokens[segments[s].token_offset + k]); lps.push_back(logprobs[segments[s].token_offset + k]); }
-    std::vector<float> padded;          // a result may carry one token more than the 224 alignment rows (the appended EOT): zero rows
-    if ((int)ids.size() > alignment_rows) {
-        padded.assign(ids.size() * (size_t)WH_AUDIO_CTX, 0.0f);
-        memcpy(padded.data(), alignment, sizeof(float) * (size_t)alignment_rows * WH_AUDIO_CTX);
-        alignment = padded.data();
-    }
     std::vector<Word> alignment_words;
     if (!ids.empty()) {
-        int r = find_alignment(tok, language, ids, alignment, (int)ids.size(), lps, alignment_words);
+        int r = find_alignment(tok, language, ids, ti, tj, path_len, lps, alignment_words);
         if (r) return r;
     }
     float median = 0, max_duration = 0;
@@ -235,8 +241,12 @@ extern "C" int wh_add_word_timestamps(const wh_tokenizer* tok, const char* langu
     tr->tokens.assign(tokens, tokens + n_tokens);
     tr->logprobs.assign(logprobs, logprobs + n_tokens);
     tr->segments.assign(segments, segments + n_segments);
+    int rows = 0, len = 0;
+    for (int s = 0; s < n_segments; ++s) rows += segments[s].n_tokens;
+    std::vector<int32_t> ti, tj;
+    if (rows > 0) len = whi::host_alignment_path(alignment, alignment_rows, rows, ti, tj);
     int r = whi::add_word_timestamps(tok, language_code, st->special_token_begin, tr->segments.data(), n_segments, tr->tokens.data(),
-                                     tr->logprobs.data(), alignment, alignment_rows, seek, last_speech_timestamp, tr);
+                                     tr->logprobs.data(), ti.data(), tj.data(), len, seek, last_speech_timestamp, tr);
     if (r) { delete tr; return r; }
     tr->has_text = true;
     tr->words_enabled = true;
