@@ -59,6 +59,11 @@ public final class HIPSession {
     /// (csrc/align.hip) and one copy of the paths.  The paths, and so every word timing, are the same in both, index for index.
     public enum WordAlignment: Int32 { case host = 0, device = 1 }
     public var wordAlignment: WordAlignment = .host { didSet { _ = wh_session_set_word_alignment(handle, wordAlignment.rawValue) } }
+    /// Where beam search (beam_size > 1) ranks its candidates (wh_session_set_beam_ranking): `.host` (default) = one copy of the top-k tables, one
+    /// synchronise and one upload of the next decode state per position; `.device` = beam_rank_kernel (csrc/beamrank.hip) per position, the host
+    /// looks at the device every 8 positions.  Results are the same in both, bit for bit.
+    public enum BeamRanking: Int32 { case host = 0, device = 1 }
+    public var beamRanking: BeamRanking = .host { didSet { _ = wh_session_set_beam_ranking(handle, beamRanking.rawValue) } }
     public init(model: HIPModel, maxBatch: Int = 1, crossAttention: CrossAttentionMode = .automatic, keySplits: Int = 0, slotsPerWorkgroup: Int = 0,
                 encoderPrecision: EncoderPrecision = .float16, wordAlignment: WordAlignment = .host) throws {
         var h: OpaquePointer?

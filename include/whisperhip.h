@@ -117,7 +117,8 @@ typedef struct wh_decoding_options {
     int32_t beam_size;            /* <= 1: greedy (the reference).  > 1: the temperature-0 pass of the fallback ladder is a beam search
                                      (wh_decode_text_beam: openai/whisper semantics, NO REFERENCE BEHAVIOUR - the reference's
                                      BeamSearchTokenSampler is fatalError); fallback temperatures > 0 sample as usual.  A transcribe call
-                                     then batches max_batch / beam_size windows per round; not combinable with word_timestamps */
+                                     then batches max_batch / beam_size windows per round; not combinable with word_timestamps.  Where
+                                     the candidates are ranked (host, the default, or device) is the session's beam-ranking mode */
     float beam_patience;          /* maxCandidates = Int(Float(beamSize) * patience), TokenSampler.swift:269; default 1 */
     int32_t reserved_;
 } wh_decoding_options;
@@ -459,12 +460,47 @@ int wh_beam_sampler_finalize(wh_beam_sampler* h, int n_beams, int len, const int
  * a * beam_size ... (n_audio * beam_size <= max_batch; nothing is copied: its beams read the audio's one cross K/V and each
  * other's self-attention rows in place, but the slots' self-attention caches are overwritten - prepare the decoder inputs again
  * before another decode), and every position expands the beams: decoder step, the LogitsFilters of opt per beam + log-softmax +
- * top (beam_size + 1) on the device, candidate ranking on the host (the cache "rearrangement" is a row -> owner table).
+ * top (beam_size + 1) on the device, then the candidate ranking (the cache "rearrangement" is a row -> owner table).  The ranking
+ * runs on the host by default - one copy of the top-k tables and one stream synchronise per position - or, in the session's
+ * beam-ranking mode 1, on the device, where the loop looks at the device every 8 positions only (see below).
  * language_tokens: per audio or NULL, as in wh_decode_text_languages.  Results follow the
  * DecodingResult conventions of wh_decode_text (temperature 0); word timestamps are not recorded along beams. */
 int wh_decode_text_beam(wh_session* s, int n_audio, int beam_size, float patience, const wh_decoding_options* opt,
                         const wh_special_tokens* st, const int32_t* prompt, int n_prompt, const int32_t* language_tokens,
                         wh_decoding_result* out /* [n_audio] */);
+
+/* Where wh_decode_text_beam (and with it the beam_size > 1 pass of wh_transcribe*) ranks the candidates.  0 = host (default): every
+ * position copies the top-k tables down, synchronises, ranks with the host sampler and uploads the next decode state and owner table.
+ * 1 = device: every position enqueues the decoder step, filter + top-k and beam_rank_kernel (csrc/beamrank.hip: the sampler's update,
+ * the first-token threshold, the length stop, the next decode state, the re-parented owner rows, the finished lists - all in device
+ * memory that ping-pongs between positions); every 8 positions the per-audio live flags come down, the stream is synchronised and the
+ * cancel flag is polled; after the loop the beams and finished lists are copied once and finalize / rank run on the host as before.
+ * Results are identical in both modes, bit for bit.  The device keeps at most WH_BEAM_RANK_MAX_CANDIDATES finished sequences per
+ * audio: a call whose max_candidates = Int(Float(beam_size) * patience) is larger is ranked on the host whatever the mode.
+ * Returns WH_ERR_INVALID_ARGUMENT for a NULL session or a mode other than 0 / 1; the getter returns the mode, -1 for NULL. */
+#define WH_BEAM_RANK_MAX_CANDIDATES 32
+int wh_session_set_beam_ranking(wh_session* s, int mode);
+int wh_session_beam_ranking(const wh_session* s);
+/* Counters of the session since its creation: launches of beam_rank_kernel, and stream synchronisations made inside the beam loop
+ * (host mode: one per position; device mode: one per 8 positions; the pre-fill's and the one that brings the results down after the
+ * loop are not counted).  Either pointer may be NULL. */
+int wh_session_beam_stats(const wh_session* s, int64_t* rank_launches, int64_t* loop_synchronisations);
+/* One ranking step for n_audio independent audios in ONE launch on HIP device `device`: wh_beam_sampler_update for each of them,
+ * without a session or a model (one upload, one launch, one download).  All audios share beam_size, max_candidates, eot_token and
+ * len; audio a has n_beams[a] (1 .. beam_size) live beams and a sampler that already holds finished_before[a] (0 .. max_candidates)
+ * sequences.  Inputs are padded to beam_size rows per audio: tokens / token_logprobs (or NULL: zeros) [n_audio][beam_size][len],
+ * sums [n_audio][beam_size], topk_* [n_audio][beam_size][topk_stride].  Outputs per audio: the first n_new[a] rows of new_tokens /
+ * new_token_logprobs (or NULL) [n_audio][beam_size][len + 1], new_sums and sources [n_audio][beam_size]; completed[a]; and the
+ * n_finished_new[a] sequences this step appends to the audio's finished list, in list order: finished_tokens /
+ * finished_token_logprobs (or NULL) [n_audio][max_candidates][len + 1], finished_sums [n_audio][max_candidates].  Rows beyond the
+ * counts are not written.  WH_ERR_INVALID_ARGUMENT without a launch, outputs untouched: beam_size outside 1..15, max_candidates
+ * outside 1..WH_BEAM_RANK_MAX_CANDIDATES, topk_stride < beam_size + 1, len outside 1..223, a count out of its range, a NULL array. */
+int wh_beam_rank_device(int device, int n_audio, int beam_size, int max_candidates, int32_t eot_token, int len,
+                        const int32_t* n_beams, const int32_t* finished_before, const int32_t* tokens, const float* token_logprobs,
+                        const float* sums, const float* topk_logprobs, const int32_t* topk_tokens, int topk_stride,
+                        int32_t* new_tokens, float* new_token_logprobs, float* new_sums, int32_t* sources, int32_t* n_new,
+                        int32_t* completed, int32_t* finished_tokens, float* finished_token_logprobs, float* finished_sums,
+                        int32_t* n_finished_new);
 
 /* TextDecoding.detectLanguage (Core/TextDecoder.swift:420-539) */
 int wh_detect_language(wh_session* s, int batch, const wh_special_tokens* st, int32_t* language_tokens_out,

@@ -186,6 +186,10 @@ SYMBOLS = {
     "wh_get_logits_device": (I, [VP, PVP]),
     "wh_session_set_cancel_flag": (I, [VP, VP]),
     "wh_session_set_alignment_postprocess": (I, [VP, I, I]),
+    "wh_session_set_beam_ranking": (I, [VP, I]),
+    "wh_session_beam_ranking": (I, [VP]),
+    "wh_session_beam_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "wh_beam_rank_device": (I, [I, I, I, I, C.c_int32, I, PI32, PI32, PI32, PF, PF, PF, PI32, I, PI32, PF, PF, PI32, PI32, PI32, PI32, PF, PF, PI32]),
     "wh_session_set_word_alignment": (I, [VP, I]),
     "wh_session_word_alignment": (I, [VP]),
     "wh_alignment_paths": (I, [VP, I, PI32, PI32, PI32, PI32, I]),

@@ -818,6 +818,26 @@ class Session:
                       None if lt is None else lt.ctypes.data_as(L.PI32), res)
         return [DecodingResult.from_c(r) for r in res]
 
+    BEAM_RANKINGS = {"host": 0, "device": 1}
+
+    def setBeamRanking(self, mode: str):
+        """Where decodeTextBeam (and transcribe* with beamSize > 1) ranks the beam candidates: "host" (default) - one copy of the top-k
+        tables, one synchronise and one upload of the next state per position; "device" - beam_rank_kernel (csrc/beamrank.hip) per
+        position, the host looks at the device every 8 positions.  Results are the same in both modes, bit for bit."""
+        if mode not in self.BEAM_RANKINGS:
+            raise ValueError(f"beamRanking {mode!r}: expected 'host' or 'device'")
+        _check(self.lib.wh_session_set_beam_ranking(self.handle, self.BEAM_RANKINGS[mode]))
+
+    @property
+    def beamRanking(self) -> str:
+        return {0: "host", 1: "device"}[int(self.lib.wh_session_beam_ranking(self.handle))]
+
+    def beamStats(self) -> Tuple[int, int]:
+        """(launches of beam_rank_kernel, stream synchronisations inside the beam loop) since the session was created"""
+        a, b = C.c_int64(), C.c_int64()
+        _check(self.lib.wh_session_beam_stats(self.handle, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
     def setAlignmentPostprocess(self, zNormalize: bool = False, medianFilterWidth: int = 0):
         """openai/whisper-style normalisation of the alignment heads (z-norm over the token rows, median filter over the frames)
         applied by getAlignmentWeights and the word timestamps; default off like the reference's host code."""
@@ -1002,6 +1022,40 @@ def dynamicTimeWarpingBatch(matrices, rows: Optional[Sequence[int]] = None, devi
     _check(L.load().wh_dynamic_time_warping_device(int(device), m.ctypes.data_as(L.PF), n, r.ctypes.data_as(L.PI32), stored, cols,
                                                    ti.ctypes.data_as(L.PI32), tj.ctypes.data_as(L.PI32), ln.ctypes.data_as(L.PI32), cap))
     return [(ti[k, :ln[k]].tolist(), tj[k, :ln[k]].tolist()) for k in range(n)]
+
+
+BEAM_RANK_MAX_CANDIDATES = 32      # WH_BEAM_RANK_MAX_CANDIDATES: finished sequences per audio the device ranking keeps
+
+
+def beamRankDevice(tokens, tokenLogProbs, sums, topkLogProbs, topkTokens, nBeams: Sequence[int], finishedBefore: Sequence[int],
+                   maxCandidates: int, eotToken: int, device: int = 0) -> List[dict]:
+    """One BeamSearchTokenSampler.update step for n independent audios in ONE launch on HIP device `device` (wh_beam_rank_device).
+    tokens / tokenLogProbs [n][beamSize][len] (rows beyond nBeams[a] are padding), sums [n][beamSize], topk* [n][beamSize][stride] with
+    stride >= beamSize + 1; finishedBefore[a]: sequences audio a's sampler already holds.  Per audio a dict: tokens [nNew][len + 1],
+    tokenLogProbs, sums, sources, completed, and the sequences this step appends to the finished list, in list order: finishedTokens
+    [k][len + 1], finishedTokenLogProbs, finishedSums."""
+    t = np.ascontiguousarray(tokens, dtype=np.int32)
+    if t.ndim != 3:
+        raise ValueError("beamRankDevice: tokens must be [n][beamSize][len]")
+    n, beam, ln = t.shape
+    lp = np.ascontiguousarray(tokenLogProbs, dtype=np.float32)
+    sm = np.ascontiguousarray(sums, dtype=np.float32)
+    kl = np.ascontiguousarray(topkLogProbs, dtype=np.float32)
+    kt = np.ascontiguousarray(topkTokens, dtype=np.int32)
+    nb = np.ascontiguousarray(list(nBeams), dtype=np.int32)
+    fb = np.ascontiguousarray(list(finishedBefore), dtype=np.int32)
+    if lp.shape != t.shape or sm.shape != (n, beam) or kl.shape != kt.shape or kl.shape[:2] != (n, beam) or len(nb) != n or len(fb) != n:
+        raise ValueError("beamRankDevice: inconsistent shapes")
+    stride, mc = int(kl.shape[2]), max(int(maxCandidates), 1)
+    nt, nl = np.zeros((n, beam, ln + 1), np.int32), np.zeros((n, beam, ln + 1), np.float32)
+    ns, src = np.zeros((n, beam), np.float32), np.zeros((n, beam), np.int32)
+    nn, done, nf = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+    ft, fl, fs = np.zeros((n, mc, ln + 1), np.int32), np.zeros((n, mc, ln + 1), np.float32), np.zeros((n, mc), np.float32)
+    p32, pf = (lambda a: a.ctypes.data_as(L.PI32)), (lambda a: a.ctypes.data_as(L.PF))
+    _check(L.load().wh_beam_rank_device(int(device), n, beam, int(maxCandidates), int(eotToken), ln, p32(nb), p32(fb), p32(t), pf(lp), pf(sm), pf(kl),
+                                        p32(kt), stride, p32(nt), pf(nl), pf(ns), p32(src), p32(nn), p32(done), p32(ft), pf(fl), pf(fs), p32(nf)))
+    return [dict(tokens=nt[a, :nn[a]], tokenLogProbs=nl[a, :nn[a]], sums=ns[a, :nn[a]], sources=src[a, :nn[a]], completed=bool(done[a]),
+                 finishedTokens=ft[a, :nf[a]], finishedTokenLogProbs=fl[a, :nf[a]], finishedSums=fs[a, :nf[a]]) for a in range(n)]
 
 
 def decodingFallback(options: DecodingOptions, isFirstTokenLogProbTooLow: bool, noSpeechProb: float, compressionRatio_: float, avgLogProb: float):

@@ -9,8 +9,9 @@
 // The CPU oracle of the same name (oracle/decode.py) is the checker; parity with openai/whisper itself is unpinned (not in the image).
 //
 // Device side: the ordinary decoder step over n_audio x beam_size slots, the batched LogitsFilter kernel, beam_topk_kernel
-// (log-softmax + the beam_size + 1 best entries per slot) and slot copies for the cache rearrangement.  The candidate ranking is host
-// code: 30 candidates per audio and step.
+// (log-softmax + the beam_size + 1 best entries per slot) and a row -> owner table for the cache rearrangement.  The candidate ranking is host
+// code by default: 30 candidates per audio and step, one host round trip per position.  wh_session_set_beam_ranking(s, 1) ranks on the device
+// (beam_rank_kernel, beamrank.hip): the loop then only looks at the device every 8 positions, like the greedy loop (beam_loop_device below).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -197,10 +198,131 @@ struct AudioBeams {
     int first_token_too_low = 0;
 };
 
-int ensure_beam_buffers(wh_session* s) {
-    if (!s->beam_owner) WH_HIP(hipMalloc((void**)&s->beam_owner, sizeof(int) * kMaxTok * (size_t)s->B));
-    if (!s->beam_lp) WH_HIP(hipMalloc((void**)&s->beam_lp, sizeof(float) * kBeamTopK * (size_t)s->B));
-    if (!s->beam_tok) WH_HIP(hipMalloc((void**)&s->beam_tok, sizeof(int) * kBeamTopK * (size_t)s->B));
+int ensure_beam_buffers(wh_session* s, bool device_ranking) {
+    const size_t B = (size_t)s->B;
+    if (!s->beam_owner) WH_HIP(hipMalloc((void**)&s->beam_owner, sizeof(int) * kMaxTok * B));
+    if (!s->beam_lp) WH_HIP(hipMalloc((void**)&s->beam_lp, sizeof(float) * kBeamTopK * B));
+    if (!s->beam_tok) WH_HIP(hipMalloc((void**)&s->beam_tok, sizeof(int) * kBeamTopK * B));
+    if (!device_ranking) return WH_OK;
+    // the second half of the ping-pong, the per-audio state and the finished lists (an audio per slot at beam size 1: sized by max_batch)
+    if (!s->beam_seq_alt) WH_HIP(hipMalloc((void**)&s->beam_seq_alt, sizeof(SeqState) * B));
+    if (!s->beam_owner_alt) WH_HIP(hipMalloc((void**)&s->beam_owner_alt, sizeof(int) * kMaxTok * B));
+    if (!s->beam_sum) WH_HIP(hipMalloc((void**)&s->beam_sum, sizeof(float) * 2 * B));
+    if (!s->beam_audio) WH_HIP(hipMalloc((void**)&s->beam_audio, sizeof(BeamAudioState) * B));
+    if (!s->beam_audio_host) WH_HIP(hipHostMalloc((void**)&s->beam_audio_host, sizeof(BeamAudioState) * B));
+    if (!s->beam_fin_tok) WH_HIP(hipMalloc((void**)&s->beam_fin_tok, sizeof(int) * kBeamSeqStride * kBeamFinishedCap * B));
+    if (!s->beam_fin_lp) WH_HIP(hipMalloc((void**)&s->beam_fin_lp, sizeof(float) * kBeamSeqStride * kBeamFinishedCap * B));
+    if (!s->beam_fin_sum) WH_HIP(hipMalloc((void**)&s->beam_fin_sum, sizeof(float) * kBeamFinishedCap * B));
+    if (!s->beam_fin_len) WH_HIP(hipMalloc((void**)&s->beam_fin_len, sizeof(int) * kBeamFinishedCap * B));
+    return WH_OK;
+}
+
+// The beam loop with the ranking on the device (wh_session_set_beam_ranking 1).  Per position: decoder step, filter + top-k, beam_rank_kernel,
+// nothing else - the kernel writes the next position's decode state, owner table and sums into the other half of a ping-pong (position
+// n_prompt - 1 reads buffer 0).  Every 8 positions the per-audio states come down and the loop ends when no audio is live; positions enqueued
+// after an audio stopped find its slots inactive.  Afterwards the beams (from the buffer each audio's state names) and the finished lists
+// are copied once into the host structures that BeamSampler::finalize / rank expect.
+int beam_loop_device(wh_session* s, int n_audio, int beam_size, int max_candidates, const wh_decoding_options* opt, const wh_special_tokens* st,
+                     int n_prompt, int prefilled_index, int loop_count, const std::vector<int>& owner, std::vector<AudioBeams>& A,
+                     std::vector<SeqState>& greedy) {
+    const int n_slots = n_audio * beam_size, B = s->B, first = n_prompt - 1;
+    constexpr int kPoll = 8;
+    BeamAudioState* ah = s->beam_audio_host;
+    for (int a = 0; a < n_audio; ++a) {
+        ah[a] = BeamAudioState{};
+        ah[a].live = A[a].live ? 1 : 0; ah[a].n_beams = A[a].live ? beam_size : 0;
+        ah[a].steps = A[a].steps; ah[a].first_token_too_low = A[a].first_token_too_low;
+        for (int j = 0; j < beam_size; ++j) {
+            SeqState& q = s->seq_host[a * beam_size + j];
+            memset(&q, 0, sizeof(q));
+            if (!A[a].live) continue;
+            const whi::BeamSeq& bq = A[a].beams[j];
+            std::copy(bq.tok.begin(), bq.tok.end(), q.tokens);
+            q.n_tokens = (int)bq.tok.size(); q.token_index = first; q.next_token = bq.tok.back(); q.prompt_len = n_prompt; q.active = 1;
+        }
+    }
+    WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * n_slots, hipMemcpyHostToDevice, s->st));
+    WH_HIP(hipMemsetAsync(s->beam_seq_alt, 0, sizeof(SeqState) * n_slots, s->st));
+    WH_HIP(hipMemcpyAsync(s->beam_owner, owner.data(), sizeof(int) * owner.size(), hipMemcpyHostToDevice, s->st));
+    WH_HIP(hipMemsetAsync(s->beam_sum, 0, sizeof(float) * 2 * (size_t)B, s->st));
+    WH_HIP(hipMemcpyAsync(s->beam_audio, ah, sizeof(BeamAudioState) * n_audio, hipMemcpyHostToDevice, s->st));
+    SeqState* seqs[2] = {s->seq, s->beam_seq_alt};
+    int* owners[2] = {s->beam_owner, s->beam_owner_alt};
+    float* sums[2] = {s->beam_sum, s->beam_sum + B};
+    bool any_live = true;       // (the caller checked)
+    for (int token_index = first; any_live && token_index < loop_count; ++token_index) {
+        const int in = (token_index - first) & 1, out = in ^ 1;
+        DecodeBuffers db = whi::decode_buffers(s, n_slots, token_index);
+        db.seq = seqs[in];
+        db.cross_div = beam_size;
+        db.self_owner = owners[in];
+        launch_decoder_step(db, nullptr, nullptr, false, s->st);
+        launch_beam_filter_topk(s->cfg_dev, s->suppress_dev, seqs[in], s->logits, n_slots, beam_size + 1, s->beam_lp, s->beam_tok, s->st);
+        WH_CHECK_LAUNCH();
+        BeamRankArgs k{};
+        k.n_audio = n_audio; k.beam_size = beam_size; k.max_candidates = max_candidates; k.eot = st->end_token; k.len = token_index + 1;
+        k.topk_stride = kBeamTopK; k.topk_lp = s->beam_lp; k.topk_tok = s->beam_tok;
+        k.tok_in = seqs[in]->tokens; k.lp_in = seqs[in]->logprobs; k.sum_in = sums[in];
+        k.tok_out = seqs[out]->tokens; k.lp_out = seqs[out]->logprobs; k.sum_out = sums[out];
+        k.in_stride = k.out_stride = (long long)(sizeof(SeqState) / sizeof(int));
+        k.audio = s->beam_audio;
+        k.fin_tok = s->beam_fin_tok; k.fin_lp = s->beam_fin_lp; k.fin_sum = s->beam_fin_sum; k.fin_len = s->beam_fin_len;
+        k.fin_cap = kBeamFinishedCap; k.fin_stride = kBeamSeqStride; k.fin_append = 1;
+        k.seq_in = seqs[in]; k.seq_out = seqs[out]; k.owner_in = owners[in]; k.owner_out = owners[out];
+        k.token_index = token_index; k.prompt_len = n_prompt; k.parity_out = out;
+        k.has_first_token_threshold = std::isnan(opt->first_token_log_prob_threshold) ? 0 : 1;
+        k.threshold_position = prefilled_index; k.first_token_log_prob_threshold = opt->first_token_log_prob_threshold;
+        int r = launch_beam_rank(k, s->st);
+        if (r) return r;
+        s->beam_rank_launches += 1;
+        if ((token_index - first + 1) % kPoll == 0 && token_index + 1 < loop_count) {
+            WH_HIP(hipMemcpyAsync(ah, s->beam_audio, sizeof(BeamAudioState) * n_audio, hipMemcpyDeviceToHost, s->st));
+            WH_HIP(hipStreamSynchronize(s->st));
+            s->beam_loop_syncs += 1;
+            if (s->cancel_flag && *s->cancel_flag) return set_error(WH_ERR_CANCELLED, "wh_decode_text_beam: cancelled through the session's cancel flag");
+            any_live = false;
+            for (int a = 0; a < n_audio; ++a) any_live |= ah[a].live != 0;
+        }
+    }
+    // ---- the results: per-audio state, both halves of the ping-pong, the finished lists
+    std::vector<SeqState> hseq((size_t)2 * n_slots);
+    std::vector<float> hsum((size_t)2 * n_slots), fsum((size_t)n_audio * kBeamFinishedCap), flp(fsum.size() * kBeamSeqStride);
+    std::vector<int> ftok(flp.size()), flen(fsum.size());
+    WH_HIP(hipMemcpyAsync(ah, s->beam_audio, sizeof(BeamAudioState) * n_audio, hipMemcpyDeviceToHost, s->st));
+    for (int h = 0; h < 2; ++h) {
+        WH_HIP(hipMemcpyAsync(hseq.data() + (size_t)h * n_slots, seqs[h], sizeof(SeqState) * n_slots, hipMemcpyDeviceToHost, s->st));
+        WH_HIP(hipMemcpyAsync(hsum.data() + (size_t)h * n_slots, sums[h], sizeof(float) * n_slots, hipMemcpyDeviceToHost, s->st));
+    }
+    WH_HIP(hipMemcpyAsync(ftok.data(), s->beam_fin_tok, sizeof(int) * ftok.size(), hipMemcpyDeviceToHost, s->st));
+    WH_HIP(hipMemcpyAsync(flp.data(), s->beam_fin_lp, sizeof(float) * flp.size(), hipMemcpyDeviceToHost, s->st));
+    WH_HIP(hipMemcpyAsync(flen.data(), s->beam_fin_len, sizeof(int) * flen.size(), hipMemcpyDeviceToHost, s->st));
+    WH_HIP(hipMemcpyAsync(fsum.data(), s->beam_fin_sum, sizeof(float) * fsum.size(), hipMemcpyDeviceToHost, s->st));
+    WH_HIP(hipStreamSynchronize(s->st));
+    for (int a = 0; a < n_audio; ++a) {
+        AudioBeams& ab = A[a];
+        if (ab.early) continue;                    // the pre-fill ended the window: nothing ran for this audio
+        const BeamAudioState& d = ah[a];
+        ab.live = d.live != 0;
+        ab.steps = d.steps;
+        if (d.first_token_too_low) { ab.first_token_too_low = 1; ab.early = true; greedy[a].first_token_too_low = 1; continue; }
+        ab.beams.resize(d.n_beams);
+        for (int j = 0; j < d.n_beams; ++j) {
+            const size_t at = (size_t)d.parity * n_slots + (size_t)a * beam_size + j;
+            const SeqState& q = hseq[at];
+            ab.beams[j].tok.assign(q.tokens, q.tokens + q.n_tokens);
+            ab.beams[j].lp.assign(q.logprobs, q.logprobs + q.n_tokens);
+            ab.beams[j].sum = hsum[at];
+        }
+        ab.sampler.finished.resize(d.finished);
+        for (int i = 0; i < d.finished; ++i) {
+            const size_t at = (size_t)a * kBeamFinishedCap + i;
+            const int* t = ftok.data() + at * kBeamSeqStride;
+            const int n = std::min(std::max(flen[at], 0), kBeamSeqStride);
+            ab.sampler.finished[i].tok.assign(t, t + n);
+            ab.sampler.finished[i].lp.assign(flp.data() + at * kBeamSeqStride, flp.data() + at * kBeamSeqStride + n);
+            ab.sampler.finished[i].sum = fsum[at];
+        }
+    }
     return WH_OK;
 }
 }  // namespace
@@ -222,7 +344,9 @@ static int wh_decode_text_beam_impl(wh_session* s, int n_audio, int beam_size, f
     (void)H;
     for (int i = 0; i < n_prompt; ++i)
         if (prompt[i] < 0 || prompt[i] >= V) return set_error(WH_ERR_PREFILL_FAILED, "wh_decode_text_beam: prompt token %d out of vocabulary", prompt[i]);
-    int r = ensure_beam_buffers(s);
+    // a finished list longer than the device list's capacity is ranked on the host (kernels.h kBeamFinishedCap; same results by definition)
+    const bool device_ranking = s->beam_ranking == 1 && max_candidates <= kBeamFinishedCap;
+    int r = ensure_beam_buffers(s, device_ranking);
     if (r) return r;
     const int prefilled_index = 0;
     r = whi::upload_sampler_cfg(s, opt, st, prefilled_index, n_prompt, 0, 0);
@@ -284,6 +408,12 @@ static int wh_decode_text_beam_impl(wh_session* s, int n_audio, int beam_size, f
     // ---- 3. the beam loop (decoding.py _main_loop with the reference's loop bounds)
     std::vector<float> h_lp((size_t)n_slots * kBeamTopK);
     std::vector<int> h_tok((size_t)n_slots * kBeamTopK);
+    if (device_ranking && any_live) {
+        if (s->cancel_flag && *s->cancel_flag) { hipStreamSynchronize(s->st); return set_error(WH_ERR_CANCELLED, "wh_decode_text_beam: cancelled through the session's cancel flag"); }
+        r = beam_loop_device(s, n_audio, beam_size, max_candidates, opt, st, n_prompt, prefilled_index, loop_count, owner, A, greedy);
+        if (r) { hipStreamSynchronize(s->st); return r; }
+        any_live = false;
+    }
     for (int token_index = n_prompt - 1; any_live && token_index < loop_count; ++token_index) {
         if (s->cancel_flag && *s->cancel_flag) { hipStreamSynchronize(s->st); return set_error(WH_ERR_CANCELLED, "wh_decode_text_beam: cancelled through the session's cancel flag"); }
         for (int a = 0; a < n_audio; ++a)
@@ -307,6 +437,7 @@ static int wh_decode_text_beam_impl(wh_session* s, int n_audio, int beam_size, f
         WH_HIP(hipMemcpyAsync(h_lp.data(), s->beam_lp, sizeof(float) * h_lp.size(), hipMemcpyDeviceToHost, s->st));
         WH_HIP(hipMemcpyAsync(h_tok.data(), s->beam_tok, sizeof(int) * h_tok.size(), hipMemcpyDeviceToHost, s->st));
         WH_HIP(hipStreamSynchronize(s->st));      // (also: `owner` / seq_host may be rewritten now)
+        s->beam_loop_syncs += 1;
         std::vector<int> pairs;
         any_live = false;
         for (int a = 0; a < n_audio; ++a) {

@@ -577,9 +577,11 @@ extern "C" void wh_session_destroy(wh_session* s) {
     void* ptrs[] = {s->pcm, s->n_valid, s->logspec, s->maxkey, s->mel_t, s->mel_f32, s->h1, s->x, s->xn, s->q16, s->k16, s->vt16, s->att16,
                     s->hmlp, s->enc16, s->enc32, s->cross_k_hi, s->cross_v_hi, s->cross_k_lo, s->cross_v_lo, s->self_k, s->self_v, s->part, s->ticket, s->logits,
                     s->align, s->align_mean, s->seq, s->cfg_dev, s->suppress_dev, s->sup_mask_dev, s->stats, s->tok_out_dev, s->lp_out_dev, s->scratch_logits,
-                    s->beam_owner, s->beam_tok, s->beam_lp, s->mel_t_lo, s->h1_lo, s->xn_lo, s->att_lo, s->hmlp_lo, s->enc_lo};
+                    s->beam_owner, s->beam_tok, s->beam_lp, s->beam_seq_alt, s->beam_owner_alt, s->beam_sum, s->beam_audio, s->beam_fin_tok, s->beam_fin_lp,
+                    s->beam_fin_sum, s->beam_fin_len, s->mel_t_lo, s->h1_lo, s->xn_lo, s->att_lo, s->hmlp_lo, s->enc_lo};
     for (void* p : ptrs) if (p) hipFree(p);
     if (s->seq_host) hipHostFree(s->seq_host);
+    if (s->beam_audio_host) hipHostFree(s->beam_audio_host);
     for (auto& e : s->ev) if (e) hipEventDestroy(e);
     if (s->st) hipStreamDestroy(s->st);
     delete s;
@@ -999,6 +1001,20 @@ extern "C" int wh_session_word_alignment_stats(const wh_session* s, int64_t* dtw
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_word_alignment_stats: null session");
     if (dtw_launches) *dtw_launches = s->dtw_launches;
     if (alignment_d2h_bytes) *alignment_d2h_bytes = s->align_d2h_bytes;
+    return WH_OK;
+}
+
+extern "C" int wh_session_set_beam_ranking(wh_session* s, int mode) {
+    if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_beam_ranking: null session");
+    if (mode != 0 && mode != 1) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_beam_ranking: mode %d (0 = host, 1 = device)", mode);
+    s->beam_ranking = mode;
+    return WH_OK;
+}
+extern "C" int wh_session_beam_ranking(const wh_session* s) { return s ? s->beam_ranking : -1; }
+extern "C" int wh_session_beam_stats(const wh_session* s, int64_t* rank_launches, int64_t* loop_synchronisations) {
+    if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_beam_stats: null session");
+    if (rank_launches) *rank_launches = s->beam_rank_launches;
+    if (loop_synchronisations) *loop_synchronisations = s->beam_loop_syncs;
     return WH_OK;
 }
 

@@ -109,6 +109,16 @@ struct wh_session {
     float* scratch_logits = nullptr;       // [V] for the filter / sample KAT entry points
     // beam search (wh_decode_text_beam, allocated on first use): row -> owning slot table of the self-attention cache, top-k outputs
     int *beam_owner = nullptr, *beam_tok = nullptr; float* beam_lp = nullptr;
+    // candidate ranking of the beam loop (wh_session_set_beam_ranking): 0 = on the host, one round trip per position; 1 = beam_rank_kernel
+    // (beamrank.hip).  Device mode ping-pongs the decode state, the owner table and the sums between positions: buffer 0 is seq / beam_owner /
+    // beam_sum, buffer 1 is beam_seq_alt / beam_owner_alt / beam_sum + B.  All of it is allocated on first use.
+    int beam_ranking = 0;
+    wh::SeqState* beam_seq_alt = nullptr; int* beam_owner_alt = nullptr; float* beam_sum = nullptr;
+    wh::BeamAudioState* beam_audio = nullptr;      // [B]
+    wh::BeamAudioState* beam_audio_host = nullptr; // pinned mirror (the live flags every 8 positions, the whole state after the loop)
+    int* beam_fin_tok = nullptr; float *beam_fin_lp = nullptr, *beam_fin_sum = nullptr;   // [B][kBeamFinishedCap][kBeamSeqStride] / [B][kBeamFinishedCap]
+    int* beam_fin_len = nullptr;           // [B][kBeamFinishedCap] tokens per finished sequence
+    long long beam_rank_launches = 0, beam_loop_syncs = 0;   // wh_session_beam_stats
     hipEvent_t ev[8]{};
     bool align_enabled = false;
     wh_timings last_timings{};

@@ -334,6 +334,39 @@ constexpr int kBeamTopK = 16;   // row stride of the top-k outputs: beam sizes u
 // beam search: the LogitsFiltering rules, log-softmax and the K best entries of every live slot's row in one pass (row in registers)
 void launch_beam_filter_topk(const SamplerCfg* cfg_dev, const int* suppress_dev, SeqState* seq, float* logits, int batch, int K, float* lp_out,
                              int* tok_out, hipStream_t st);
+// beam search candidate ranking on the device (beamrank.hip): BeamSampler::update for every audio of a launch, one workgroup per audio.
+constexpr int kBeamRankThreads = 256;     // >= 15 beams x 16 candidates: one candidate per thread
+constexpr int kBeamFinishedCap = 32;      // finished sequences per audio the device list holds (max_candidates = int(beam_size * patience);
+                                          // 30 = 15 beams at patience 2.0 fits, anything larger is ranked on the host)
+constexpr int kBeamSeqStride = kMaxTok + 8;   // ints / floats per finished sequence (the SeqState token capacity)
+struct BeamAudioState {                   // per audio, device memory
+    int live;                             // still expanding
+    int n_beams;                          // live beams (in: before the step, out: after it)
+    int finished;                         // sequences in the finished list
+    int steps, first_token_too_low;       // decode-loop bookkeeping (loop form)
+    int parity;                           // loop form: the state buffer (0 / 1) that holds the audio's current beams
+    int n_added, completed;               // outputs of the last step: sequences appended to the finished list, list full
+};
+// Element k of beam j of audio a lives at base[(a * beam_size + j) * slot_stride + k] for tokens and log-probabilities, sums at [a * beam_size + j];
+// the top-k tables at [(a * beam_size + j) * topk_stride + c].  Finished sequence i of audio a: fin_*[(a * fin_cap + i) * fin_stride + k].
+struct BeamRankArgs {
+    int n_audio, beam_size, max_candidates, eot, len, topk_stride;
+    const float* topk_lp; const int* topk_tok;
+    const int* tok_in; const float* lp_in; const float* sum_in;      // lp_in may be null (zeros)
+    int* tok_out; float* lp_out; float* sum_out;                     // lp_out may be null
+    long long in_stride, out_stride;
+    BeamAudioState* audio;
+    int* sources;                         // null, or [n_audio][beam_size]
+    int* fin_tok; float* fin_lp; float* fin_sum; int* fin_len;      // fin_lp / fin_len (tokens per sequence: len + 1) may be null
+    int fin_cap, fin_stride, fin_append;  // fin_append 1: new sequences go behind the `finished` the list already holds, 0: to the front
+    // loop form (seq_out != null): tok_* / lp_* point into seq_in / seq_out; the kernel also writes the next step's SeqState fields of every
+    // slot, the re-parented owner rows and the loop's stop rules (first-token threshold, length), and leaves audios that are not live alone
+    const SeqState* seq_in; SeqState* seq_out;
+    const int* owner_in; int* owner_out;  // [slots][kMaxTok]
+    int token_index, prompt_len, parity_out;
+    int has_first_token_threshold, threshold_position; float first_token_log_prob_threshold;
+};
+int launch_beam_rank(const BeamRankArgs& a, hipStream_t st);
 // mean over alignment heads -> [B][224][1500]
 void launch_alignment_mean(const float* align, int batch, int n_align, float* out, hipStream_t st);
 // openai/whisper-style alignment post-processing of one slot (z-normalise over the token rows, median filter, head mean)
