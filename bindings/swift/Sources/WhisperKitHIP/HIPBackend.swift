@@ -62,6 +62,11 @@ public final class HIPSession {
     /// Where beam search (beam_size > 1) ranks its candidates (wh_session_set_beam_ranking): `.host` (default) = one copy of the top-k tables, one
     /// synchronise and one upload of the next decode state per position; `.device` = beam_rank_kernel (csrc/beamrank.hip) per position, the host
     /// looks at the device every 8 positions.  Results are the same in both, bit for bit.
+    /// Compacted fallback passes (wh_session_set_fallback_compaction): `.off` (default) = every decode pass runs at the full batch width; `.on` = a pass
+    /// whose active mask is sparse (the temperature-fallback passes of transcribeWithOptions) decodes only the windows that failed, at a width from a fixed
+    /// ladder.  Same results, bit for bit.
+    public enum FallbackCompaction: Int32 { case off = 0, on = 1 }
+    public var fallbackCompaction: FallbackCompaction = .off { didSet { _ = wh_session_set_fallback_compaction(handle, fallbackCompaction.rawValue) } }
     public enum BeamRanking: Int32 { case host = 0, device = 1 }
     public var beamRanking: BeamRanking = .host { didSet { _ = wh_session_set_beam_ranking(handle, beamRanking.rawValue) } }
     public init(model: HIPModel, maxBatch: Int = 1, crossAttention: CrossAttentionMode = .automatic, keySplits: Int = 0, slotsPerWorkgroup: Int = 0,

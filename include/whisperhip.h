@@ -260,13 +260,16 @@ int wh_session_create_tuned(wh_model* m, int max_batch, int cross_attention_mode
                                           -1 resolves to 0, and an explicit 1 is WH_ERR_INVALID_ARGUMENT (the absorbed kernel streams the
                                           Float16 encoder output; a hi | lo stream would double the bytes of the decoder's dominant kernel).
                                           The rows cost L x 1500 x d x 2 x 3 bytes per slot: 369 MB at large-v3 (32 layers, d = 1280).
-                                          Results stay bit-identical across batch sizes within the mode. */
+                                          Results stay bit-identical across batch sizes within the mode.
+     fallback_compaction                  0 (default) off, 1 on: wh_session_set_fallback_compaction below.  (The field sits behind reserved_: the
+                                          struct keeps its size and every earlier offset.) */
 typedef struct wh_session_options {
     int32_t cross_attention_mode;
     int32_t cross_attention_splits;
     int32_t cross_attention_slots_per_workgroup;
     int32_t encoder_precision;           /* 0 Float16 operands (default), 1 split hi | lo (above) */
-    int32_t reserved_[4];
+    int32_t reserved_[3];
+    int32_t fallback_compaction;         /* 0 off (default), 1 decode passes with a sparse active mask run at a compacted batch width */
 } wh_session_options;
 void wh_session_options_default(wh_session_options* out);
 int wh_session_create_with_options(wh_model* m, int max_batch, const wh_session_options* opt, wh_session** out);
@@ -412,6 +415,21 @@ int wh_decode_text(wh_session* s, int batch, const wh_decoding_options* opt, con
 int wh_decode_text_languages(wh_session* s, int batch, const wh_decoding_options* opt, const wh_special_tokens* st,
                              const int32_t* prompt, int n_prompt, const int32_t* language_tokens, const float* temperatures,
                              const int32_t* active, uint64_t seed, wh_decoding_result* out /* [batch] */);
+/* Compacted decode passes.  0 = off (default): a pass of wh_decode_text / wh_decode_text_languages / the temperature ladder of wh_transcribe*
+ * runs at the full batch width whatever its `active` mask - the mask only suppresses stores, so ONE window of a 256-slot device batch that
+ * needs a fallback costs a second pass of up to 223 steps at 256-slot width.  1 = on: a pass whose mask leaves enough slots out to save at
+ * least one 32-slot batch tile runs at a compacted width from a fixed ladder (32 / 64 / 128 slots).  Compact slot i decodes live slot
+ * home[i] (ascending): it attends over that slot's encoder output / cross K / V rows, writes that slot's alignment rows and draws from that
+ * slot's random stream; its self-attention cache, activations and decode state are the compact slot's own (a pass starts them afresh).
+ * Results, progress callbacks (wh_progress.slot), early stops and alignment rows are in home-slot terms and equal the uncompacted pass bit
+ * for bit: a slot decodes to the same bits at any batch width, and the key splits stay the session's.  Slots outside the mask keep their
+ * alignment rows.  The beam-search pass, wh_decode_text_custom, wh_detect_language and the step API never compact.
+ * Returns WH_ERR_INVALID_ARGUMENT for a NULL session or a mode other than 0 / 1; the getter returns the mode, -1 for NULL. */
+int wh_session_set_fallback_compaction(wh_session* s, int mode);
+int wh_session_fallback_compaction(const wh_session* s);
+/* Counters of the session since its creation: decode passes (one per wh_decode_text / wh_decode_text_languages call or ladder rung), how many
+ * of them ran compacted, and the sum of the batch width over the decoder steps launched by them.  Any pointer may be NULL. */
+int wh_session_decode_pass_stats(const wh_session* s, int64_t* passes, int64_t* compacted_passes, int64_t* slot_steps);
 /* ---- user-pluggable LogitsFiltering / TokenSampling (Core/Text/LogitsFilter.swift:8-10, Core/Text/TokenSampler.swift:8-11) ----
  * The reference runs `logitsFilters` (custom filters first, Core/TextDecoder.swift:857-899) and the `TokenSampling` object on the
  * host once per token (:641-652).  The fused device loop of wh_decode_text knows the four built-in filters and the greedy /

@@ -55,7 +55,7 @@ class WhDecodingResult(C.Structure):
 
 class WhSessionOptions(C.Structure):
     _fields_ = [("cross_attention_mode", C.c_int32), ("cross_attention_splits", C.c_int32), ("cross_attention_slots_per_workgroup", C.c_int32),
-                ("encoder_precision", C.c_int32), ("reserved_", C.c_int32 * 4)]
+                ("encoder_precision", C.c_int32), ("reserved_", C.c_int32 * 3), ("fallback_compaction", C.c_int32)]
 
 
 class WhTensor(C.Structure):
@@ -186,6 +186,9 @@ SYMBOLS = {
     "wh_get_logits_device": (I, [VP, PVP]),
     "wh_session_set_cancel_flag": (I, [VP, VP]),
     "wh_session_set_alignment_postprocess": (I, [VP, I, I]),
+    "wh_session_set_fallback_compaction": (I, [VP, I]),
+    "wh_session_fallback_compaction": (I, [VP]),
+    "wh_session_decode_pass_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "wh_session_set_beam_ranking": (I, [VP, I]),
     "wh_session_beam_ranking": (I, [VP]),
     "wh_session_beam_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

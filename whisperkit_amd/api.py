@@ -818,6 +818,27 @@ class Session:
                       None if lt is None else lt.ctypes.data_as(L.PI32), res)
         return [DecodingResult.from_c(r) for r in res]
 
+    FALLBACK_COMPACTIONS = {"off": 0, "on": 1}
+
+    def setFallbackCompaction(self, mode: str):
+        """Whether a decode pass with a sparse `active` mask - decodeText(active=...), the temperature-fallback passes of transcribe* - runs
+        at a compacted batch width: "off" (default) - every pass at the full width; "on" - only the live slots are decoded, at a width from
+        a fixed ladder (32 / 64 / 128), each reading its home slot's encoder data and writing its home slot's alignment rows.  Results,
+        progress callbacks and alignment rows are the same in both modes, bit for bit."""
+        if mode not in self.FALLBACK_COMPACTIONS:
+            raise ValueError(f"fallbackCompaction {mode!r}: expected 'on' or 'off'")
+        _check(self.lib.wh_session_set_fallback_compaction(self.handle, self.FALLBACK_COMPACTIONS[mode]))
+
+    @property
+    def fallbackCompaction(self) -> str:
+        return {0: "off", 1: "on"}[int(self.lib.wh_session_fallback_compaction(self.handle))]
+
+    def decodePassStats(self) -> Tuple[int, int, int]:
+        """(decode passes, compacted passes, sum of the batch width over the decoder steps launched) since the session was created"""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        _check(self.lib.wh_session_decode_pass_stats(self.handle, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
+
     BEAM_RANKINGS = {"host": 0, "device": 1}
 
     def setBeamRanking(self, mode: str):

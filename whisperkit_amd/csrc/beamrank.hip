@@ -181,7 +181,7 @@ __global__ __launch_bounds__(kBeamRankThreads) void beam_rank_kernel(const BeamR
             q->temperature = 0.0f;
             q->prompt_len = has ? p.prompt_len : 0;
             for (int i = 0; i < 6; ++i) q->f_rules[i] = 0;
-            q->pad = 0;
+            q->rng_lane = 0;          // (beams are expanded at T = 0: no random draw)
         }
         // rearrange_kv_cache without moving a byte: rows 0 .. token_index follow the parent, later rows are the slot's own
         for (int idx = tid; idx < B * kMaxTok; idx += kBeamRankThreads) {

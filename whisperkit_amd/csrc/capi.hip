@@ -442,11 +442,15 @@ extern "C" int wh_session_create_with_options(wh_model* m, int max_batch, const 
     if (opt->encoder_precision == 1 && cross_attention_mode == 1)
         return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_create: encoder_precision 1 (split) needs the K / V-row cross-attention (cross_attention_mode -1 or 0): "
                          "the absorbed kernel streams the Float16 encoder output, and a hi | lo stream would double its bytes");
+    if (opt->fallback_compaction < 0 || opt->fallback_compaction > 1)
+        return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_create: fallback_compaction %d (expected 0 off, 1 on)", opt->fallback_compaction);
     if (cross_attention_mode == 1 && m && !xabs_supported(m->dims.n_text_state, m->dims.n_text_head))
         return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_create: the absorbed cross-attention needs a model width of 384 / 512 / 768 / 1024 / 1280 (this model: %d)", m->dims.n_text_state);
     // a split session resolves the automatic cross-attention choice to the K / V rows (their projection reads the split encoder output)
-    return session_create_impl(m, max_batch, opt->encoder_precision == 1 ? 0 : cross_attention_mode, cross_attention_splits,
-                               opt->cross_attention_slots_per_workgroup, out, opt->encoder_precision);
+    const int r = session_create_impl(m, max_batch, opt->encoder_precision == 1 ? 0 : cross_attention_mode, cross_attention_splits,
+                                      opt->cross_attention_slots_per_workgroup, out, opt->encoder_precision);
+    if (r == WH_OK) (*out)->fallback_compaction = opt->fallback_compaction;
+    return r;
 }
 extern "C" int wh_session_create_with_mode(wh_model* m, int max_batch, int cross_attention_mode, wh_session** out) {
     return wh_session_create_tuned(m, max_batch, cross_attention_mode, 0, out);
@@ -574,6 +578,8 @@ extern "C" void wh_session_destroy(wh_session* s) {
     if (s->align_tmp) hipFree(s->align_tmp);
     if (s->dtw_dev) hipFree(s->dtw_dev);
     if (s->dtw_host) hipHostFree(s->dtw_host);
+    if (s->slot_home_dev) hipFree(s->slot_home_dev);
+    if (s->slot_home_host) hipHostFree(s->slot_home_host);
     void* ptrs[] = {s->pcm, s->n_valid, s->logspec, s->maxkey, s->mel_t, s->mel_f32, s->h1, s->x, s->xn, s->q16, s->k16, s->vt16, s->att16,
                     s->hmlp, s->enc16, s->enc32, s->cross_k_hi, s->cross_v_hi, s->cross_k_lo, s->cross_v_lo, s->self_k, s->self_v, s->part, s->ticket, s->logits,
                     s->align, s->align_mean, s->seq, s->cfg_dev, s->suppress_dev, s->sup_mask_dev, s->stats, s->tok_out_dev, s->lp_out_dev, s->scratch_logits,
@@ -805,6 +811,10 @@ DecodeBuffers decode_buffers(wh_session* s, int batch, int max_position) {
     db.align = s->align_enabled ? s->align : nullptr; db.align_slot = m->align_slot_dev; db.n_align = s->n_align_alloc;
     db.d32 = &s->d32; db.x = s->d32.x; db.q = s->d32.q;
     if (s->use_xabs) { s->xabs.enc = s->enc16; db.xabs = &s->xabs; }
+    if (s->pass_mapped) {       // compacted pass (host.hip decode_text_impl)
+        db.slot_home = s->slot_home_dev;
+        if (s->use_xabs) { s->xabs_pass = s->xabs; s->xabs_pass.spw = s->pass_spw; db.xabs = &s->xabs_pass; }
+    }
     // cross-attention gate: WH_XATT_GATE=0 never, 1 always, unset: while the model carries more than one session (dec_shared.h)
     const int gate_mode = knob::once<knob::WH_XATT_GATE>();
     const bool gate_on = gate_mode < 0 ? kXattnGateDefault && m->n_sessions.load() > 1 : gate_mode != 0;
@@ -878,7 +888,7 @@ extern "C" int wh_predict_logits(wh_session* s, int batch, const int32_t* tokens
             return set_error(WH_ERR_DECODING_LOGITS_FAILED, "wh_predict_logits: token %d / position %d out of range", tokens[b], positions[b]);
         SeqState& q = s->seq_host[b];
         memset(&q, 0, sizeof(q));
-        q.next_token = tokens[b]; q.token_index = positions[b]; q.active = 1; q.done = 0;
+        q.next_token = tokens[b]; q.token_index = positions[b]; q.active = 1; q.done = 0; q.rng_lane = b;
     }
     // only the control fields are refreshed; token history on the device is not used by the bare step
     WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * batch, hipMemcpyHostToDevice, s->st));
@@ -1001,6 +1011,21 @@ extern "C" int wh_session_word_alignment_stats(const wh_session* s, int64_t* dtw
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_word_alignment_stats: null session");
     if (dtw_launches) *dtw_launches = s->dtw_launches;
     if (alignment_d2h_bytes) *alignment_d2h_bytes = s->align_d2h_bytes;
+    return WH_OK;
+}
+
+extern "C" int wh_session_set_fallback_compaction(wh_session* s, int mode) {
+    if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_fallback_compaction: null session");
+    if (mode != 0 && mode != 1) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_fallback_compaction: mode %d (0 = off, 1 = on)", mode);
+    s->fallback_compaction = mode;
+    return WH_OK;
+}
+extern "C" int wh_session_fallback_compaction(const wh_session* s) { return s ? s->fallback_compaction : -1; }
+extern "C" int wh_session_decode_pass_stats(const wh_session* s, int64_t* passes, int64_t* compacted_passes, int64_t* slot_steps) {
+    if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_decode_pass_stats: null session");
+    if (passes) *passes = s->decode_passes;
+    if (compacted_passes) *compacted_passes = s->compacted_passes;
+    if (slot_steps) *slot_steps = s->slot_steps;
     return WH_OK;
 }
 

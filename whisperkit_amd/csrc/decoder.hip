@@ -82,6 +82,7 @@ __device__ __forceinline__ void compute_filter_rules(const SamplerCfg& cfg, cons
 struct AttnArgs {
     int batch, d, n_head, layer, n_layer, n_split;
     int cross_div;           // > 1: slot b attends over the cross K / V of slot b / cross_div (beams of one audio share one copy)
+    int mapped;              // 1: a compacted pass - the cross-attention runs its mapped instantiation and reads slot_home (below); fills what was padding
     const float* q;          // [B][d]
     const f16* self_k; const f16* self_v;     // layer base [Bmax][H][224][64]
     const f16 *cross_k_hi, *cross_v_hi;       // layer base [Bmax][H][1500][64]: 24-bit rows (round 5: Float16 rows cost 7e-3 sigma under a sharp softmax) =
@@ -93,7 +94,10 @@ struct AttnArgs {
     SeqState* seq;
     int no_fence;
     int self_rows;             // self-attention: cache rows fetched (DecodeBuffers.self_rows)
-    const int* self_owner;     // self-attention: row -> owning slot table of beam search, or null
+    // One pointer, two readers that exclude each other (the args keep the size and the offsets they had before compacted passes existed, so the
+    // instantiations a session without the option launches are the same device code): the self-attention kernels read self_owner, the row ->
+    // owning slot table of beam search, or null; the cross-attention kernel reads slot_home [batch] (DecodeBuffers.slot_home) when mapped = 1
+    union { const int* self_owner; const int* slot_home; };
     int* gate; int gate_wg;    // cross-attention gate (dec_shared.h): the workgroup with linear id gate_wg gives it back at entry
     unsigned long long* dbg;   // optional timeline probe (WH_DBG=1)
 };
@@ -348,7 +352,9 @@ __device__ __forceinline__ void combine_splits(const AttnArgs& a, int b, int h, 
 // K / V rows are in flight, so that dec32_proj<P32_Q>'s launch disappears.  Parity-green (the whole GPU suite), and slower: the query phase is twelve
 // dependent L2 round trips that the row stream does not hide, and it is redundant across key splits and slots - tiny.en at 1 slot 10.8 -> 17.7 us
 // per launch (0.2266 -> 0.2365 ms per decoder step with the cross-query launch gone), at 8 slots 18.3 -> 42.4 us.  Code in git history.)
-template <int PASSES, bool NT>
+// MAP (compacted passes, DecodeBuffers.slot_home): the K / V rows read and the alignment rows written are those of slot a.slot_home[b]; the query,
+// the partials, the ticket and the slot state stay those of slot b.  Instantiations of their own: MAP = false is the code as it was.
+template <int PASSES, bool NT, bool MAP = false>
 __global__ __launch_bounds__(256) void dec_cross_attn_kernel(const AttnArgs a) {
     constexpr int KPB = PASSES * 32;
     __shared__ float red[16], osum[256], o_l[64];
@@ -359,7 +365,9 @@ __global__ __launch_bounds__(256) void dec_cross_attn_kernel(const AttnArgs a) {
     const int s_act = sq->active, s_done = sq->done, s_ti = sq->token_index;     // looked at after the K/V loads are issued
     const int d = a.d, S = a.n_split;
     const int t0 = sp * KPB, n = min(KPB, kCtx - t0);
-    const int bc = a.cross_div > 1 ? b / a.cross_div : b;       // the slot whose cross K / V this slot reads
+    int bc, bh = b;                                             // the slot whose cross K / V this slot reads / whose alignment rows it writes
+    if constexpr (MAP) { bh = a.slot_home[b]; bc = bh; }
+    else bc = a.cross_div > 1 ? b / a.cross_div : b;
     const size_t base = (((size_t)bc * a.n_head + h) * kCtx + t0) * kHeadDim;
     int slot = -1;
     if (a.align) slot = a.align_slot[a.layer * a.n_head + h];
@@ -372,7 +380,7 @@ __global__ __launch_bounds__(256) void dec_cross_attn_kernel(const AttnArgs a) {
     auto get_n = [&]() {
         if (!(s_act && !s_done)) return -1;
         const int pos = min(max(s_ti, 0), kMaxTok - 1);
-        if (slot >= 0 && pos + 1 < kMaxTok) raw = a.align + (((size_t)b * kMaxTok + pos + 1) * a.n_align + slot) * kCtx + t0;
+        if (slot >= 0 && pos + 1 < kMaxTok) raw = a.align + (((size_t)bh * kMaxTok + pos + 1) * a.n_align + slot) * kCtx + t0;
         return n;
     };
     auto qfix = [](float (&)[8], int) {};
@@ -679,7 +687,7 @@ __global__ __launch_bounds__(SAMP_T) void sampler_kernel(const SamplerCfg* __res
         float pr[8], total = 0.0f;
         for (int j = 0; j < k; ++j) { pr[j] = expf(tv[j] - lse); total += pr[j]; }
         const int counter = DO_ADVANCE ? sq->token_index : counter_override;
-        const float rnd = uniform01(cfg.seed + (unsigned long long)b * 0x632BE59BD9B4E019ull, counter) * total;
+        const float rnd = uniform01(cfg.seed + (unsigned long long)sq->rng_lane * 0x632BE59BD9B4E019ull, counter) * total;
         float accp = 0.0f;
         int chosen = 0;
         for (int j = 0; j < k; ++j) {
@@ -817,7 +825,9 @@ static void launch_cross_attn(const AttnArgs& at_in, int S, int H, int B, hipStr
     // flight 13.4 k -> 14.2 k sequence-steps/s, profiles/r02i_*); WH_XATT_NT=0 is the A/B side
     const int nt = knob::once<knob::WH_XATT_NT>();
     const bool ntl = nt && at.cross_div <= 1;      // (cross_div > 1, beam search: cacheable loads - the L2 of the XCD serves the other beams of the audio)
-#define XATT(P_) do { if (ntl) dec_cross_attn_kernel<P_, true><<<grid, 256, xlds, st>>>(at); else dec_cross_attn_kernel<P_, false><<<grid, 256, xlds, st>>>(at); } while (0)
+    // compacted pass (at.mapped): the mapped instantiations; its slots share no K / V rows, so the loads keep the non-temporal policy
+#define XATT(P_) do { if (at.mapped) { if (nt) dec_cross_attn_kernel<P_, true, true><<<grid, 256, xlds, st>>>(at); else dec_cross_attn_kernel<P_, false, true><<<grid, 256, xlds, st>>>(at); } \
+                      else if (ntl) dec_cross_attn_kernel<P_, true><<<grid, 256, xlds, st>>>(at); else dec_cross_attn_kernel<P_, false><<<grid, 256, xlds, st>>>(at); } while (0)
     if (S == 6) XATT(8);
     else if (S == 8) XATT(6);
     else if (S == 12) XATT(4);
@@ -873,6 +883,7 @@ void launch_decoder_step(const DecodeBuffers& db, const SamplerCfg* cfg_dev, con
             xa.gate = db.xattn_gate;
             xa.spw = X.spw;
             xa.dbg = debug_buffer() ? debug_buffer() + (size_t)KK_DEC_CROSS_ATTN * 4096 * 8 : nullptr;
+            if (db.slot_home) { xa.mapped = 1; xa.slot_home = db.slot_home; }       // compacted pass: no stamped form
             launch_xabs_qk(xa, n_bt, st);
             // (Round 6, measured and rejected, profiles/r06x_*, r06y_*: xabs_attn on a CU-masked HIP stream of its own - the stream kernels of all sessions confined to the first
             // n CUs, the launch chain on the rest or everywhere - joined to the session stream by an event pair per layer, eager launches: 2796 -> 2314 - 2387 audio-s/s for
@@ -881,6 +892,7 @@ void launch_decoder_step(const DecodeBuffers& db, const SamplerCfg* cfg_dev, con
             launch_xabs_vup(xa, n_bt, st);
         } else {
             at.dbg = debug_buffer() ? debug_buffer() + (size_t)KK_DEC_CROSS_ATTN * 4096 * 8 : nullptr;
+            if (db.slot_home) { at.mapped = 1; at.slot_home = db.slot_home; }       // (the self-attention launch above has read self_owner)
             launch_cross_attn(at, S, H, B, st);
         }
         a = base;               // x += W_co att + b_co; planes gamma_3 x, statistics for LN3

@@ -264,7 +264,9 @@ static bool use_graphs() { return !knob::once<knob::WH_NO_GRAPH>(); }
 // 8 positions (28 per key at most).
 static int get_step_graph(wh_session* s, int batch, int first_step, hipGraphExec_t* out) {
     DecodeBuffers db = whi::decode_buffers(s, batch, first_step + kStepsPerGraph - 1);
-    const WhGraphKey key{batch, s->align_enabled ? 1 : 0, s->fused_greedy ? 1 : 0, s->align_enabled ? s->n_align_alloc : 0, db.self_rows, db.xattn_gate ? 1 : 0};
+    // (a compacted pass bakes the slot table's address, the mapped kernel instantiations and its own slots per workgroup into its launches)
+    const WhGraphKey key{batch, s->align_enabled ? 1 : 0, s->fused_greedy ? 1 : 0, s->align_enabled ? s->n_align_alloc : 0, db.self_rows, db.xattn_gate ? 1 : 0,
+                         db.slot_home ? 1 : 0, db.slot_home ? s->pass_spw : 0};
     auto it = s->graphs.find(key);
     if (it != s->graphs.end()) { s->graph_use[key] = ++s->graph_tick; *out = it->second; return WH_OK; }
     // The cache is capped (a large-v3 step graph holds ~2.5 k kernel nodes; a configuration = everything of the key but the row bound has up
@@ -273,7 +275,7 @@ static int get_step_graph(wh_session* s, int batch, int first_step, hipGraphExec
     const size_t cap = (size_t)knob::once<knob::WH_GRAPH_CAP>();
     while (s->graphs.size() >= cap) {
         auto same_cfg = [](const WhGraphKey& a, const WhGraphKey& b) {
-            return a.batch == b.batch && a.align == b.align && a.fused == b.fused && a.n_align == b.n_align && a.gate == b.gate;
+            return a.batch == b.batch && a.align == b.align && a.fused == b.fused && a.n_align == b.n_align && a.gate == b.gate && a.mapped == b.mapped && a.spw == b.spw;
         };
         const WhGraphKey* victim = nullptr;
         unsigned long long victim_last = ~0ull;
@@ -322,7 +324,8 @@ static int report_progress(wh_session* s, int batch) {
         SeqState& q = s->seq_host[b];
         if (!q.active || q.done || q.n_tokens <= 0) continue;
         wh_progress p{};
-        p.slot = b; p.n_tokens = q.n_tokens; p.tokens = q.tokens;
+        p.slot = s->pass_mapped ? s->slot_home_host[b] : b;      // a compacted pass reports the window's home slot
+        p.n_tokens = q.n_tokens; p.tokens = q.tokens;
         float sum = 0;
         for (int i = 0; i < q.n_tokens; ++i) sum += q.logprobs[i];
         p.avg_logprob = sum / (float)q.n_tokens;
@@ -352,10 +355,11 @@ static int run_token_loop(wh_session* s, int batch, int loop_count) {
             CHECK_CANCEL(s);
             hipGraphExec_t exec = nullptr;
             if (use_graphs()) { int r = get_step_graph(s, batch, step, &exec); if (r) return r; }
-            if (exec) WH_HIP(hipGraphLaunch(exec, s->st));
+            if (exec) { WH_HIP(hipGraphLaunch(exec, s->st)); s->slot_steps += (long long)batch * kStepsPerGraph; }
             else for (int i = 0; i < kStepsPerGraph && step + i < loop_count; ++i) {
                 DecodeBuffers db = whi::decode_buffers(s, batch, step + i);
                 launch_decoder_step(db, s->cfg_dev, s->suppress_dev, true, s->st); WH_CHECK_LAUNCH();
+                s->slot_steps += batch;
             }
             WH_HIP(hipMemcpyAsync(s->seq_host, s->seq, bytes, hipMemcpyDeviceToHost, s->st));
             WH_HIP(hipStreamSynchronize(s->st));
@@ -383,6 +387,7 @@ static int run_token_loop(wh_session* s, int batch, int loop_count) {
             if (r) return r;
             const double ta = dbg_host ? now() : 0.0;
             WH_HIP(hipGraphLaunch(exec, s->st));
+            s->slot_steps += (long long)batch * kStepsPerGraph;
             if (dbg_host) t_launch += now() - ta;
             // snapshot the slot states behind graph g; while it runs, look at the snapshot behind graph g-1
             // (at most one graph of run-ahead; `done` is monotonic, so a torn snapshot is harmless)
@@ -400,6 +405,7 @@ static int run_token_loop(wh_session* s, int batch, int loop_count) {
             DecodeBuffers db = whi::decode_buffers(s, batch, step);
             launch_decoder_step(db, s->cfg_dev, s->suppress_dev, true, s->st);
             WH_CHECK_LAUNCH();
+            s->slot_steps += batch;
             if ((step & 7) == 7 && step + 1 < loop_count) {
                 WH_HIP(hipMemcpyAsync(s->seq_host, s->seq, bytes, hipMemcpyDeviceToHost, s->st));
                 WH_HIP(hipStreamSynchronize(s->st));
@@ -443,26 +449,62 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
     int lang_pos = -1;
     if (language_tokens && wh_is_model_multilingual(s->m))
         for (int i = 0; i + 1 < n_prompt; ++i) if (prompt[i] == st->start_of_transcript_token) { lang_pos = i + 1; break; }
-    for (int b = 0; b < batch; ++b) {
-        SeqState& q = s->seq_host[b];
+    // the decode state of home slot hb as the pass starts it
+    auto init_slot = [&](SeqState& q, int hb, bool act) {
         memset(&q, 0, sizeof(q));
         for (int i = 0; i < n_prompt; ++i) q.tokens[i] = prompt[i];
-        if (lang_pos >= 0 && language_tokens[b] >= 0 && language_tokens[b] < V) q.tokens[lang_pos] = language_tokens[b];
+        if (lang_pos >= 0 && language_tokens[hb] >= 0 && language_tokens[hb] < V) q.tokens[lang_pos] = language_tokens[hb];
         q.n_tokens = n_prompt; q.token_index = prefilled_index; q.next_token = q.tokens[0]; q.prompt_len = n_prompt;
-        q.active = active ? (active[b] != 0) : 1;
-        q.temperature = f16_round(temperatures ? temperatures[b] : opt->temperature);
+        q.active = act ? 1 : 0;
+        q.temperature = f16_round(temperatures ? temperatures[hb] : opt->temperature);
+        q.rng_lane = hb;          // the slot's random stream (T > 0) does not depend on where the slot is decoded
+    };
+    // ---- compacted pass (wh_session_set_fallback_compaction 1): a sparse `active` mask decodes at the width compact_pass_plan gives; compact
+    // slot i stands for home slot slot_home_host[i] - its encoder output / cross K / V rows, its alignment rows, its language token,
+    // temperature and random stream.  Everything below this block is in home-slot terms again.
+    int n_live = 0;
+    for (int b = 0; b < batch; ++b) n_live += (active ? active[b] != 0 : 1);
+    plan::CompactPassPlan cp{false, batch, s->use_xabs ? s->xabs.spw : 1};
+    if (s->fallback_compaction == 1 && active) cp = plan::compact_pass_plan(n_live, batch, s->B, s->use_xabs ? s->xabs.spw : 1);
+    struct PassScope { wh_session* s; ~PassScope() { s->pass_mapped = false; } } pass_scope{s};      // (every exit: the next caller of decode_buffers sees a plain pass)
+    const int width = cp.compact ? cp.width : batch;
+    if (cp.compact) {
+        if (!s->slot_home_dev) {
+            WH_HIP(hipMalloc((void**)&s->slot_home_dev, sizeof(int32_t) * s->B));
+            WH_HIP(hipHostMalloc((void**)&s->slot_home_host, sizeof(int32_t) * 2 * s->B));
+        }
+        int32_t* home = s->slot_home_host, *live = s->slot_home_host + s->B;
+        if (plan::compact_slot_map(active, batch, width, home, live) != n_live) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text: the compacted pass does not hold its live slots");
+        for (int i = 0; i < width; ++i) init_slot(s->seq_host[i], home[i], live[i] != 0);
+        WH_HIP(hipMemcpyAsync(s->slot_home_dev, home, sizeof(int32_t) * width, hipMemcpyHostToDevice, s->st));
+        s->pass_mapped = true; s->pass_spw = cp.spw;
+        s->compacted_passes += 1;
+    } else {
+        for (int b = 0; b < batch; ++b) init_slot(s->seq_host[b], b, active ? active[b] != 0 : true);
     }
+    s->decode_passes += 1;
     // fused greedy path: every active slot samples at T = 0 (filters + softmax statistics in the logits epilogue)
     s->fused_greedy = true;
-    for (int b = 0; b < batch; ++b) if (s->seq_host[b].active && s->seq_host[b].temperature != 0.0f) s->fused_greedy = false;
+    for (int b = 0; b < width; ++b) if (s->seq_host[b].active && s->seq_host[b].temperature != 0.0f) s->fused_greedy = false;
     if (knob::now<knob::WH_NO_FUSED_SAMPLER>()) s->fused_greedy = false;
-    WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * batch, hipMemcpyHostToDevice, s->st));
-    launch_rules_init(s->cfg_dev, s->seq, batch, s->st);
+    WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * width, hipMemcpyHostToDevice, s->st));
+    launch_rules_init(s->cfg_dev, s->seq, width, s->st);
     const int loop_count = std::min(opt->sample_length, kMaxTok - 1);
     s->skip_special_in_progress = opt->skip_special_tokens != 0;
     s->special_begin_in_progress = st->special_token_begin;
-    r = run_token_loop(s, batch, std::max(loop_count, 0));
+    r = run_token_loop(s, width, std::max(loop_count, 0));
     if (r) return r;
+    if (cp.compact) {
+        // back to home-slot terms, on the host and on the device: the live slots' final states at their home slots, every other slot as
+        // an uncompacted pass leaves it (initialised, inactive)
+        const int32_t* home = s->slot_home_host;
+        std::vector<SeqState> fin(s->seq_host, s->seq_host + n_live);
+        for (int b = 0; b < batch; ++b) init_slot(s->seq_host[b], b, false);
+        for (int i = 0; i < n_live; ++i) s->seq_host[home[i]] = fin[i];
+        s->pass_mapped = false;
+        WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * batch, hipMemcpyHostToDevice, s->st));
+        WH_HIP(hipStreamSynchronize(s->st));
+    }
     for (int b = 0; b < batch; ++b) {
         if (!s->seq_host[b].active) { memset(&out[b], 0, sizeof(out[b])); continue; }
         whi::finalize_decoding_result(s->seq_host[b], opt, st, s->seq_host[b].temperature, &out[b]);
@@ -556,7 +598,7 @@ extern "C" int wh_detect_language(wh_session* s, int batch, const wh_special_tok
     for (int b = 0; b < batch; ++b) {
         SeqState& q = s->seq_host[b];
         memset(&q, 0, sizeof(q));
-        q.tokens[0] = st->start_of_transcript_token; q.n_tokens = 1; q.next_token = st->start_of_transcript_token; q.active = 1;
+        q.tokens[0] = st->start_of_transcript_token; q.n_tokens = 1; q.next_token = st->start_of_transcript_token; q.active = 1; q.rng_lane = b;
     }
     WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * batch, hipMemcpyHostToDevice, s->st));
     bool keep = s->align_enabled;

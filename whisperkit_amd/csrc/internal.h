@@ -57,8 +57,9 @@ struct wh_model {
 // step graphs are keyed by everything their captured launches bake in
 struct WhGraphKey {
     int batch, align, fused, n_align, self_rows, gate;
+    int mapped, spw;      // compacted pass (slot table + mapped cross-attention instantiations) and its slots per absorbed-attention workgroup; 0, 0 otherwise
     bool operator<(const WhGraphKey& o) const {
-        return std::tie(batch, align, fused, n_align, self_rows, gate) < std::tie(o.batch, o.align, o.fused, o.n_align, o.self_rows, o.gate);
+        return std::tie(batch, align, fused, n_align, self_rows, gate, mapped, spw) < std::tie(o.batch, o.align, o.fused, o.n_align, o.self_rows, o.gate, o.mapped, o.spw);
     }
 };
 
@@ -119,6 +120,14 @@ struct wh_session {
     int* beam_fin_tok = nullptr; float *beam_fin_lp = nullptr, *beam_fin_sum = nullptr;   // [B][kBeamFinishedCap][kBeamSeqStride] / [B][kBeamFinishedCap]
     int* beam_fin_len = nullptr;           // [B][kBeamFinishedCap] tokens per finished sequence
     long long beam_rank_launches = 0, beam_loop_syncs = 0;   // wh_session_beam_stats
+    // compacted fallback passes (wh_session_set_fallback_compaction): 0 = off, 1 = a decode pass with a sparse `active` mask runs at the
+    // width launch_plan.h compact_pass_plan gives.  The table is allocated by the first compacted pass: slot_home_dev [B] on the device,
+    // slot_home_host [2][B] pinned (home slots | live flags).  pass_mapped / pass_spw hold only while decode_text_impl runs such a pass.
+    int fallback_compaction = 0;
+    int32_t *slot_home_dev = nullptr, *slot_home_host = nullptr;
+    bool pass_mapped = false; int pass_spw = 1;
+    wh::Xabs xabs_pass{};                 // the session's xabs with the pass's slots per workgroup
+    long long decode_passes = 0, compacted_passes = 0, slot_steps = 0;   // wh_session_decode_pass_stats
     hipEvent_t ev[8]{};
     bool align_enabled = false;
     wh_timings last_timings{};

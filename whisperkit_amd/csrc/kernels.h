@@ -185,7 +185,7 @@ struct SeqState {
     float temperature;
     int prompt_len;               // initialPromptIndex
     int f_rules[6];               // filter rules of the NEXT sampling step: blank, ts_active, r1_lo, r1_hi, r2_lo, r2_hi
-    int pad;
+    int rng_lane;                 // lane of the T > 0 sampler's random stream: the slot index, or the HOME slot in a compacted pass (slot_home below)
 };
 
 struct DecodeBuffers {
@@ -218,6 +218,8 @@ struct DecodeBuffers {
                              // continues another beam's sequence reads that beam's rows in place - no cache rearrangement copies)
     const struct Dec32* d32; // activation planes / split-K scratch / tiled weights of the projection kernels (decoder32.hip)
     const struct Xabs* xabs; // non-null: weight-absorbed cross-attention over the encoder output (xabs.hip) instead of the cross K / V stream
+    const int* slot_home;    // null, or [batch] (device): a compacted pass (launch_plan.h compact_pass_plan) - slot b attends over the encoder output / cross
+                             // K / V rows of slot slot_home[b] and writes that slot's alignment rows; everything else is indexed by b
 };
 constexpr int kStatBlocks = 1792; // >= workgroups of the logits kernel (V / 64 rows: GEMV path, V / 32 rows: MFMA path), multiple of 256
 // Largest vocabulary the sampling kernels cover: sampler_kernel holds SAMP_T x SAMP_E = 1024 x 51 ids in registers, the fused greedy
@@ -302,6 +304,7 @@ struct Xabs {
 };
 struct XabsArgs {
     int batch, max_batch, d, n_head, layer, n_split, cross_div;
+    int mapped;                      // 1: a compacted pass - xabs_attn runs its mapped instantiation and reads slot_home (below); fills what was padding
     const f16* enc; const float* q;
     const f16 *wkT, *wv_t; const float* bv;
     f16 *qf_hi, *qf_lo; float* part; float2* ml;
@@ -309,7 +312,11 @@ struct XabsArgs {
     float* align; const int* align_slot; int n_align;
     const SeqState* seq;
     float* kpart; int* ticket;       // K-slice scratch of xabs_vup (the projection kernels' part / ticket buffers)
-    unsigned long long* dbg;         // WH_DBG=1 timeline stamps of xabs_attn
+    // One pointer, two readers that exclude each other (the args keep the size and the offsets they had before compacted passes existed, so the
+    // instantiations a session without the option launches are the same device code): mapped = 0: dbg, the WH_DBG=1 timeline stamps of xabs_attn
+    // (stamped instantiation only); mapped = 1: slot_home [batch] (DecodeBuffers.slot_home) - whose encoder output slot b streams, whose
+    // alignment rows it writes (mapped instantiations only; they have no stamped form)
+    union { unsigned long long* dbg; const int* slot_home; };
     int ablate;                      // WH_XABS_ABLATE (timing probe, results are garbage): bit 0 no LDS-DMA, bit 1 no S / softmax / P V work
     int* gate;                       // cross-attention gate (dec_shared.h, WH_XATT_GATE=1): xabs_qk takes it, xabs_attn's last workgroup returns it
     int spw;                         // xabs_attn: slots per workgroup (round 6): the launch has ceil(batch / spw) x n_split workgroups, each streams its slots one after the other

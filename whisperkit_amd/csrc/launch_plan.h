@@ -206,5 +206,48 @@ inline XabsVupPlan xabs_vup_plan(int d, int n_head, int n_bt) {
     return {ks, (unsigned)(((nx + 7) / 8) * 8 * n_bt)};
 }
 
+// ============================================================================================== compacted decode passes
+// A decode pass whose `active` mask is sparse (a temperature-fallback pass: only the windows that failed decode again) can run at a compacted
+// batch width: compact slot i decodes home slot home[i] (DecodeBuffers.slot_home).  A slot decodes to the same bits at any batch width, so
+// the width is a pure cost decision:
+//   * compact only when at least one 32-slot batch tile is saved - every projection, the self-attention and the logits GEMM are sized by the
+//     tiles; inside a tile a dead slot costs the absorbed cross-attention a prologue and nothing else;
+//   * the width comes from a short fixed ladder (kCompactLadder): the step graphs are keyed by the width, and a session that produced a width
+//     per live count would thrash the capped graph cache.  For max_batch <= 256 a session sees at most 3 compacted widths;
+//   * key splits are not part of the plan: they fix the combine order and with it the bits (they stay the session's constant);
+//   * slots per absorbed-attention workgroup: the smallest value that keeps the launch within the workgroups (= CUs) the session's full-width
+//     launch takes, ceil(max_batch / slots_per_workgroup) per split - a compacted pass of few slots streams them side by side instead of one
+//     after the other.  Results do not depend on it.
+constexpr int kCompactLadder[] = {32, 64, 128};
+constexpr int kCompactRungs = (int)(sizeof(kCompactLadder) / sizeof(kCompactLadder[0]));
+struct CompactPassPlan { bool compact; int width, spw; };
+inline CompactPassPlan compact_pass_plan(int n_live, int batch, int max_batch, int slots_per_workgroup) {
+    const int spw0 = slots_per_workgroup > 1 ? slots_per_workgroup : 1;
+    CompactPassPlan p{false, batch, spw0};
+    if (n_live < 1 || n_live >= batch) return p;
+    for (int r = 0; r < kCompactRungs; ++r) {
+        const int w = kCompactLadder[r];
+        if (w < n_live) continue;
+        if ((w + 31) / 32 >= (batch + 31) / 32) break;      // no batch tile saved: the pass runs as it is
+        const int wgs = ((max_batch > batch ? max_batch : batch) + spw0 - 1) / spw0;       // workgroups per split of the session's full-width launch
+        p.compact = true; p.width = w; p.spw = (w + wgs - 1) / wgs;
+        break;
+    }
+    return p;
+}
+// The slot table of a compacted pass: home[0 .. n_live) = the live slots of active[0 .. batch) (null: all) in ascending order, live[i] = 1; the
+// padding entries i >= n_live are inactive (live[i] = 0) and point at a slot of their own inside the batch (the kernels form addresses from
+// them before they look at the slot state), home[i] = i.  Returns n_live, or -1 when the live slots do not fit into `width`.
+inline int compact_slot_map(const int32_t* active, int batch, int width, int32_t* home, int32_t* live) {
+    int n = 0;
+    for (int b = 0; b < batch; ++b) {
+        if (active && !active[b]) continue;
+        if (n >= width) return -1;
+        home[n] = b; live[n] = 1; ++n;
+    }
+    for (int i = n; i < width; ++i) { home[i] = i < batch ? i : 0; live[i] = 0; }
+    return n;
+}
+
 }  // namespace plan
 }  // namespace wh

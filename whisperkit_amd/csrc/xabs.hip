@@ -201,7 +201,9 @@ __host__ __device__ constexpr int xabs_lds_bytes(int cw) { return xabs_lds_bytes
 // all come out even, and the 4 waves own the softmax of 16 heads (one head tile).  The row size stays a multiple of 256 bytes (768), so
 // every tile row starts at LDS bank 0 and the xswz chunk swizzle decides the banks exactly as at the other widths.  At KSW = 3, NW = 4:
 // 52 864 bytes of LDS (ring 7 x 6 KB), no scratch (registers: DESIGN 3.4).
-template <int KSW, int NHT, bool DBG, bool NTL, int NW = 8>
+// MAP (compacted passes, DecodeBuffers.slot_home): the encoder output streamed and the alignment rows written are those of slot a.slot_home[b];
+// the Q' fragments, the partials and the slot state stay those of slot b.  Instantiations of their own: MAP = false is the code as it was.
+template <int KSW, int NHT, bool DBG, bool NTL, int NW = 8, bool MAP = false>
 __global__ __launch_bounds__(NW * 64, 2) void xabs_attn_kernel(const XabsArgs a) {
     static_assert(NW == 8 || NW == 4, "the waves split the channels: 8, or 4 at d = 384");
     static_assert(4 * NW >= 16 * NHT, "4 softmax-owner heads per wave");
@@ -235,7 +237,9 @@ __global__ __launch_bounds__(NW * 64, 2) void xabs_attn_kernel(const XabsArgs a)
   for (int b = b_first; b < a.batch; b += b1) {            // (workgroup-uniform)
     if (b != b_first) __syncthreads();                    // every wave is done with the previous slot's ring, partial tiles and P^T before they are written again
     XPHASE(9);
-    const int bc = a.cross_div > 1 ? b / a.cross_div : b;
+    int bc, bh = b;                                       // the slot whose encoder output is streamed / whose alignment rows are written
+    if constexpr (MAP) { bh = a.slot_home[b]; bc = bh; }
+    else bc = a.cross_div > 1 ? b / a.cross_div : b;
     const unsigned char* enc = reinterpret_cast<const unsigned char*>(a.enc + (size_t)bc * kCtx * D);
 
     // ---- LDS-DMA: a 16-key tile is two half tiles of 8 keys; half k (= 2 tile + {0, 1}) lives in ring slot k % 7.  Waves 0-3 fetch the
@@ -300,7 +304,7 @@ __global__ __launch_bounds__(NW * 64, 2) void xabs_attn_kernel(const XabsArgs a)
     }
     const int pos = min(max(s_ti, 0), kMaxTok - 1);
     float* raw = nullptr;
-    if (al_slot >= 0 && pos + 1 < kMaxTok) raw = a.align + (((size_t)b * kMaxTok + pos + 1) * a.n_align + al_slot) * kCtx;
+    if (al_slot >= 0 && pos + 1 < kMaxTok) raw = a.align + (((size_t)bh * kMaxTok + pos + 1) * a.n_align + al_slot) * kCtx;
     XPHASE(10);
 
     f32x16 acc[CW];
@@ -619,29 +623,31 @@ void launch_xabs_qk(const XabsArgs& a, int n_bt, hipStream_t st) {
     else xabs_qk_kernel<1><<<grid, 256, 0, st>>>(a);
 }
 
-template <int CW, int NHT, bool DBG, bool NTL>
+template <int CW, int NHT, bool DBG, bool NTL, bool MAP = false>
 static void launch_attn_k(const XabsArgs& a, hipStream_t st) {
     constexpr int lds = xabs_lds_bytes(CW);
     static PerDeviceOnce once;
-    once.run([] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&xabs_attn_kernel<CW, NHT, DBG, NTL>), hipFuncAttributeMaxDynamicSharedMemorySize, lds); });
-    xabs_attn_kernel<CW, NHT, DBG, NTL><<<dim3(plan::xabs_attn_grid(a.batch, a.spw, a.n_split)), 512, lds, st>>>(a);
+    once.run([] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&xabs_attn_kernel<CW, NHT, DBG, NTL, 8, MAP>), hipFuncAttributeMaxDynamicSharedMemorySize, lds); });
+    xabs_attn_kernel<CW, NHT, DBG, NTL, 8, MAP><<<dim3(plan::xabs_attn_grid(a.batch, a.spw, a.n_split)), 512, lds, st>>>(a);
 }
-template <int KSW, bool DBG, bool NTL>
+template <int KSW, bool DBG, bool NTL, bool MAP = false>
 static void launch_attn_w4_k(const XabsArgs& a, hipStream_t st) {
     constexpr int lds = xabs_lds_bytes_w(4, KSW);
     static PerDeviceOnce once;
-    once.run([] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&xabs_attn_kernel<KSW, 1, DBG, NTL, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, lds); });
-    xabs_attn_kernel<KSW, 1, DBG, NTL, 4><<<dim3(plan::xabs_attn_grid(a.batch, a.spw, a.n_split)), 256, lds, st>>>(a);
+    once.run([] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&xabs_attn_kernel<KSW, 1, DBG, NTL, 4, MAP>), hipFuncAttributeMaxDynamicSharedMemorySize, lds); });
+    xabs_attn_kernel<KSW, 1, DBG, NTL, 4, MAP><<<dim3(plan::xabs_attn_grid(a.batch, a.spw, a.n_split)), 256, lds, st>>>(a);
 }
 // CW = 0: the 4-wave form of d = 384
-template <int CW, int NHT, bool DBG, bool NTL>
+template <int CW, int NHT, bool DBG, bool NTL, bool MAP = false>
 static void launch_attn_any(const XabsArgs& a, hipStream_t st) {
-    if constexpr (CW == 0) launch_attn_w4_k<3, DBG, NTL>(a, st); else launch_attn_k<CW, NHT, DBG, NTL>(a, st);
+    if constexpr (CW == 0) launch_attn_w4_k<3, DBG, NTL, MAP>(a, st); else launch_attn_k<CW, NHT, DBG, NTL, MAP>(a, st);
 }
 template <int CW, int NHT>
 static void launch_attn_t(const XabsArgs& a, hipStream_t st) {
     const int nt = knob::once<knob::WH_XABS_NT>();          // non-temporal policy on the encoder-output stream (in flight: 19.2 k vs 18.1 k sequence-steps/s, profiles/r04l_*); 0 = A/B side
     const int ablate = knob::once<knob::WH_XABS_ABLATE>();  // timing probe (garbage results): 1 no LDS-DMA in the loop, 2 no S / softmax / P V work, 3 both
+    // compacted pass: the mapped instantiations (no stamped form).  Its slots share no encoder output, so the stream keeps the non-temporal policy.
+    if (a.mapped) { if (nt) launch_attn_any<CW, NHT, false, true, true>(a, st); else launch_attn_any<CW, NHT, false, false, true>(a, st); return; }
     if (a.dbg || ablate) { XabsArgs b = a; b.ablate = ablate; launch_attn_any<CW, NHT, true, false>(b, st); return; }      // the stamped instantiation (tools/xabs_timeline.py)
     // beam search (cross_div > 1: the beams of an audio read ONE encoder output): cacheable loads - the workgroups of an audio's beams are
     // dispatched back to back onto one XCD (4 consecutive slots per group) and the later ones are meant to hit the first one's lines in its L2
