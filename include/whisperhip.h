@@ -278,6 +278,8 @@ int wh_session_encoder_precision(const wh_session* s);                        /*
 /* development aid (kernel bring-up, tools/xabs_check.py): the first nbytes of a named decode-step device buffer ("q", "zb_hi", ...);
    nbytes beyond the buffer's size is WH_ERR_INVALID_ARGUMENT */
 int wh_debug_peek(wh_session* s, const char* name, void* out_host, size_t nbytes);
+/* development aid (leak tests): device + pinned allocations the models, sessions and stand-alone entry points of this process hold now */
+long long wh_debug_live_allocations(void);
 /* captured step graphs the session holds (one per configuration = (batch, alignment, sampler fusion) and 8 decoder positions; the cache is
    capped at WH_GRAPH_CAP, default 112, graphs: the configuration used longest ago is dropped first) */
 int wh_session_step_graph_count(const wh_session* s);

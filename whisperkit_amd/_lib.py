@@ -149,6 +149,7 @@ SYMBOLS = {
     "wh_session_cross_attention_slots_per_workgroup": (I, [VP]),
     "wh_session_encoder_precision": (I, [VP]),
     "wh_debug_peek": (I, [VP, C.c_char_p, VP, C.c_size_t]),
+    "wh_debug_live_allocations": (C.c_longlong, []),
     "wh_session_synchronize": (I, [VP]),
     "wh_session_stream": (VP, [VP]),
     "wh_set_audio": (I, [VP, I, VP, I]),

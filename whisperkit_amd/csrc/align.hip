@@ -143,12 +143,11 @@ extern "C" int wh_dynamic_time_warping_device(int device, const float* matrices_
     }
     WH_HIP(hipSetDevice(device));
     const size_t nm = (size_t)n * rows_stride * cols, np = (size_t)n * capacity_per_matrix;
+    DevMem tmp;                         // the two temporaries, freed on every way out
     float* m_dev = nullptr;
     int* i_dev = nullptr;               // rows [n] | lengths [n] | text_idx [n][capacity] | time_idx [n][capacity]
-    if (hipMalloc((void**)&m_dev, nm * sizeof(float)) != hipSuccess || hipMalloc((void**)&i_dev, (2 * (size_t)n + 2 * np) * sizeof(int)) != hipSuccess) {
-        if (m_dev) hipFree(m_dev);
+    if (tmp.alloc(&m_dev, nm, false) != hipSuccess || tmp.alloc(&i_dev, 2 * (size_t)n + 2 * np, false) != hipSuccess)
         return whi::set_error(WH_ERR_HIP, "wh_dynamic_time_warping_device: hipMalloc failed");
-    }
     int* len_dev = i_dev + n;
     int *ti_dev = len_dev + n, *tj_dev = ti_dev + np;
     int r = WH_OK;
@@ -170,8 +169,6 @@ extern "C" int wh_dynamic_time_warping_device(int device, const float* matrices_
             }
         }
     }
-    hipFree(m_dev);
-    hipFree(i_dev);
     return r;
     WH_CATCH("wh_dynamic_time_warping_device")
 }

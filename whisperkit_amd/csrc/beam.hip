@@ -200,20 +200,21 @@ struct AudioBeams {
 
 int ensure_beam_buffers(wh_session* s, bool device_ranking) {
     const size_t B = (size_t)s->B;
-    if (!s->beam_owner) WH_HIP(hipMalloc((void**)&s->beam_owner, sizeof(int) * kMaxTok * B));
-    if (!s->beam_lp) WH_HIP(hipMalloc((void**)&s->beam_lp, sizeof(float) * kBeamTopK * B));
-    if (!s->beam_tok) WH_HIP(hipMalloc((void**)&s->beam_tok, sizeof(int) * kBeamTopK * B));
+    // (not zero-filled; a call that fails part way keeps what it got and asks for the rest next time)
+    if (!s->beam_owner) WH_HIP(s->mem.alloc(&s->beam_owner, kMaxTok * B, false));
+    if (!s->beam_lp) WH_HIP(s->mem.alloc(&s->beam_lp, kBeamTopK * B, false));
+    if (!s->beam_tok) WH_HIP(s->mem.alloc(&s->beam_tok, kBeamTopK * B, false));
     if (!device_ranking) return WH_OK;
     // the second half of the ping-pong, the per-audio state and the finished lists (an audio per slot at beam size 1: sized by max_batch)
-    if (!s->beam_seq_alt) WH_HIP(hipMalloc((void**)&s->beam_seq_alt, sizeof(SeqState) * B));
-    if (!s->beam_owner_alt) WH_HIP(hipMalloc((void**)&s->beam_owner_alt, sizeof(int) * kMaxTok * B));
-    if (!s->beam_sum) WH_HIP(hipMalloc((void**)&s->beam_sum, sizeof(float) * 2 * B));
-    if (!s->beam_audio) WH_HIP(hipMalloc((void**)&s->beam_audio, sizeof(BeamAudioState) * B));
-    if (!s->beam_audio_host) WH_HIP(hipHostMalloc((void**)&s->beam_audio_host, sizeof(BeamAudioState) * B));
-    if (!s->beam_fin_tok) WH_HIP(hipMalloc((void**)&s->beam_fin_tok, sizeof(int) * kBeamSeqStride * kBeamFinishedCap * B));
-    if (!s->beam_fin_lp) WH_HIP(hipMalloc((void**)&s->beam_fin_lp, sizeof(float) * kBeamSeqStride * kBeamFinishedCap * B));
-    if (!s->beam_fin_sum) WH_HIP(hipMalloc((void**)&s->beam_fin_sum, sizeof(float) * kBeamFinishedCap * B));
-    if (!s->beam_fin_len) WH_HIP(hipMalloc((void**)&s->beam_fin_len, sizeof(int) * kBeamFinishedCap * B));
+    if (!s->beam_seq_alt) WH_HIP(s->mem.alloc(&s->beam_seq_alt, B, false));
+    if (!s->beam_owner_alt) WH_HIP(s->mem.alloc(&s->beam_owner_alt, kMaxTok * B, false));
+    if (!s->beam_sum) WH_HIP(s->mem.alloc(&s->beam_sum, 2 * B, false));
+    if (!s->beam_audio) WH_HIP(s->mem.alloc(&s->beam_audio, B, false));
+    if (!s->beam_audio_host) WH_HIP(s->mem.alloc_pinned(&s->beam_audio_host, B));
+    if (!s->beam_fin_tok) WH_HIP(s->mem.alloc(&s->beam_fin_tok, (size_t)kBeamSeqStride * kBeamFinishedCap * B, false));
+    if (!s->beam_fin_lp) WH_HIP(s->mem.alloc(&s->beam_fin_lp, (size_t)kBeamSeqStride * kBeamFinishedCap * B, false));
+    if (!s->beam_fin_sum) WH_HIP(s->mem.alloc(&s->beam_fin_sum, kBeamFinishedCap * B, false));
+    if (!s->beam_fin_len) WH_HIP(s->mem.alloc(&s->beam_fin_len, kBeamFinishedCap * B, false));
     return WH_OK;
 }
 

@@ -256,8 +256,9 @@ extern "C" int wh_beam_rank_device(int device, int n_audio, int beam_size, int m
     memcpy(&h[o_tk_tok], topk_tokens, ns * topk_stride * 4);
     BeamAudioState* ha = reinterpret_cast<BeamAudioState*>(&h[o_audio]);
     for (int a = 0; a < n_audio; ++a) { ha[a].live = 1; ha[a].n_beams = n_beams[a]; ha[a].finished = finished_before[a]; }
+    DevMem tmp;                         // the temporary, freed on every way out
     int32_t* d = nullptr;
-    if (hipMalloc((void**)&d, n_words * 4) != hipSuccess) return whi::set_error(WH_ERR_HIP, "wh_beam_rank_device: hipMalloc failed");
+    if (tmp.alloc(&d, n_words, false) != hipSuccess) return whi::set_error(WH_ERR_HIP, "wh_beam_rank_device: hipMalloc failed");
     int r = WH_OK;
     auto step = [&](hipError_t e, const char* what) {
         if (r == WH_OK && e != hipSuccess) r = whi::set_error(WH_ERR_HIP, "wh_beam_rank_device: %s failed: %s", what, hipGetErrorString(e));
@@ -277,7 +278,6 @@ extern "C" int wh_beam_rank_device(int device, int n_audio, int beam_size, int m
         r = launch_beam_rank(k, nullptr);
     }
     if (r == WH_OK) step(hipMemcpy(&h[o_out], d + o_out, (n_words - o_out) * 4, hipMemcpyDeviceToHost), "download");     // (synchronises)
-    hipFree(d);
     if (r != WH_OK) return r;
     for (int a = 0; a < n_audio; ++a) {
         const size_t s0 = (size_t)a * beam_size, f0 = (size_t)a * max_candidates;

@@ -84,8 +84,7 @@ static int build_mel_tables(wh_model* m) {
     const size_t o_filt = 2 * nb * 4, o_rng = o_filt + nf * 4, o_fc = o_rng + n_mels * sizeof(int2), o_foff = o_fc + fc.size() * 4;
     size_t bytes = o_foff + n_mels * sizeof(int);
     char* dev = nullptr;
-    WH_HIP(hipMalloc((void**)&dev, bytes));
-    m->mel_tables_dev = dev;
+    WH_HIP(m->mem.alloc(&dev, bytes, false));
     WH_HIP(hipMemcpy(dev, bc.data(), nb * 4, hipMemcpyHostToDevice));
     WH_HIP(hipMemcpy(dev + nb * 4, bs.data(), nb * 4, hipMemcpyHostToDevice));
     WH_HIP(hipMemcpy(dev + o_filt, filt.data(), nf * 4, hipMemcpyHostToDevice));
@@ -158,41 +157,36 @@ static int bind_weights(wh_model* m) {
     return WH_OK;
 }
 
-// Carve 256-byte aligned sub-buffers out of one allocation.
-struct Carver {
-    char* base = nullptr; size_t off = 0;
-    template <typename T> T* take(size_t n) { T* p = reinterpret_cast<T*>(base + off); off = (off + n * sizeof(T) + 255) / 256 * 256; return p; }
-};
+// the carved allocations (devmem.h) hand out read-only pointers for the kernels; the one-time builders below write through them
+template <typename T> static T* writable(const T* p) { return const_cast<T*>(p); }
 
 static int build_dec32(wh_model* m) {
     const wh_dims& D = m->dims;
-    const size_t d = D.n_text_state, L = D.n_text_layer, V = D.n_vocab, Vp = (V + 31) / 32 * 32;
-    size_t bytes = L * (14 * d * d * 2 + 16 * d * 4 + 12 * 256) + Vp * d * 2 + 2 * Vp * 4 + 3 * 256;
-    hipError_t e = hipMalloc(&m->dec32_blob, bytes);
-    if (e != hipSuccess) return set_error(WH_ERR_HIP, "hipMalloc(%zu) for the tiled decoder weights failed: %s", bytes, hipGetErrorString(e));
-    WH_HIP(hipMemset(m->dec32_blob, 0, bytes));
-    Carver c; c.base = (char*)m->dec32_blob;
+    const size_t d = D.n_text_state, L = D.n_text_layer, V = D.n_vocab;
     m->dec32.resize(L);
+    std::vector<Dec32LayerW> probe(L);          // the measuring pass stores bare offsets: into scratch, never into the model
+    Dec32 probe_top{};
+    const size_t bytes = mem::carve_model_dec32(nullptr, d, L, V, probe.data(), probe_top);
+    char* blob = nullptr;
+    hipError_t e = m->mem.alloc(&blob, bytes, true);
+    if (e != hipSuccess) return set_error(WH_ERR_HIP, "hipMalloc(%zu) for the tiled decoder weights failed: %s", bytes, hipGetErrorString(e));
+    mem::carve_model_dec32(blob, d, L, V, m->dec32.data(), *m);
     hipStream_t st = nullptr;
     for (size_t l = 0; l < L; ++l) {
         const DecLayerW& w = m->dec[l];
-        Dec32LayerW& t = m->dec32[l];
-        f16* p;
-        p = c.take<f16>(3 * d * d); dec32_tile_weights(w.qkv_w, 3 * d, d, p, st); t.qkv_t = p;
-        p = c.take<f16>(d * d); dec32_tile_weights(w.o_w, d, d, p, st); t.o_t = p;
-        p = c.take<f16>(d * d); dec32_tile_weights(w.cq_w, d, d, p, st); t.cq_t = p;
-        p = c.take<f16>(d * d); dec32_tile_weights(w.co_w, d, d, p, st); t.co_t = p;
-        p = c.take<f16>(4 * d * d); dec32_tile_weights(w.fc1_w, 4 * d, d, p, st); t.fc1_t = p;
-        p = c.take<f16>(4 * d * d); dec32_tile_weights(w.fc2_w, d, 4 * d, p, st); t.fc2_t = p;
-        float *g, *cc;
-        g = c.take<float>(3 * d); cc = c.take<float>(3 * d); dec32_fold_vectors(w.qkv_w, 3 * d, d, w.ln1_g, w.ln1_b, w.qkv_b, g, cc, st); t.qkv_g = g; t.qkv_c = cc;
-        g = c.take<float>(d); cc = c.take<float>(d); dec32_fold_vectors(w.cq_w, d, d, w.ln2_g, w.ln2_b, w.cq_b, g, cc, st); t.cq_g = g; t.cq_c = cc;
-        g = c.take<float>(4 * d); cc = c.take<float>(4 * d); dec32_fold_vectors(w.fc1_w, 4 * d, d, w.ln3_g, w.ln3_b, w.fc1_b, g, cc, st); t.fc1_g = g; t.fc1_c = cc;
+        const Dec32LayerW& t = m->dec32[l];
+        dec32_tile_weights(w.qkv_w, 3 * d, d, writable(t.qkv_t), st);
+        dec32_tile_weights(w.o_w, d, d, writable(t.o_t), st);
+        dec32_tile_weights(w.cq_w, d, d, writable(t.cq_t), st);
+        dec32_tile_weights(w.co_w, d, d, writable(t.co_t), st);
+        dec32_tile_weights(w.fc1_w, 4 * d, d, writable(t.fc1_t), st);
+        dec32_tile_weights(w.fc2_w, d, 4 * d, writable(t.fc2_t), st);
+        dec32_fold_vectors(w.qkv_w, 3 * d, d, w.ln1_g, w.ln1_b, w.qkv_b, writable(t.qkv_g), writable(t.qkv_c), st);
+        dec32_fold_vectors(w.cq_w, d, d, w.ln2_g, w.ln2_b, w.cq_b, writable(t.cq_g), writable(t.cq_c), st);
+        dec32_fold_vectors(w.fc1_w, 4 * d, d, w.ln3_g, w.ln3_b, w.fc1_b, writable(t.fc1_g), writable(t.fc1_c), st);
     }
-    f16* et = c.take<f16>(Vp * d); dec32_tile_weights(m->emb, V, d, et, st); m->emb_t = et;
-    float* g = c.take<float>(Vp); float* cc = c.take<float>(Vp);
-    dec32_fold_vectors(m->emb, V, d, m->lnf_g, m->lnf_b, nullptr, g, cc, st); m->lg_g = g; m->lg_c = cc;
-    if (c.off > bytes) return set_error(WH_ERR_HIP, "internal: tiled decoder weights overflow (%zu > %zu)", c.off, bytes);
+    dec32_tile_weights(m->emb, V, d, writable(m->emb_t), st);
+    dec32_fold_vectors(m->emb, V, d, m->lnf_g, m->lnf_b, nullptr, writable(m->lg_g), writable(m->lg_c), st);
     WH_CHECK_LAUNCH();
     WH_HIP(hipDeviceSynchronize());
     return WH_OK;
@@ -209,28 +203,28 @@ static int build_xabs(wh_model* m) {
     std::lock_guard<std::mutex> lk(m->xabs_mu);
     if (!m->xabs.empty()) return WH_OK;
     WH_HIP(hipSetDevice(m->device));
-    const size_t bytes = L * (2 * d * d * 2 + 2 * 256);
-    hipError_t e = hipMalloc(&m->xabs_blob, bytes);
-    if (e != hipSuccess) return set_error(WH_ERR_HIP, "hipMalloc(%zu) for the absorbed cross-attention weights failed: %s", bytes, hipGetErrorString(e));
-    Carver c; c.base = (char*)m->xabs_blob;
     std::vector<wh::XabsLayerW> tiles(L);
+    const size_t bytes = mem::carve_model_xabs(nullptr, d, L, tiles.data());
+    char* blob = nullptr;
+    hipError_t e = m->mem.alloc(&blob, bytes, false);
+    if (e != hipSuccess) return set_error(WH_ERR_HIP, "hipMalloc(%zu) for the absorbed cross-attention weights failed: %s", bytes, hipGetErrorString(e));
+    mem::carve_model_xabs(blob, d, L, tiles.data());
     // a private non-blocking stream: the build may run while other sessions of this model are decoding, and a device-wide synchronisation
     // on the null stream would wait for all of their work with the model's lock held
     hipStream_t st = nullptr;
-    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) { hipFree(m->xabs_blob); m->xabs_blob = nullptr; return set_error(WH_ERR_HIP, "stream for the absorbed cross-attention weights"); }
+    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) { m->mem.release(blob); return set_error(WH_ERR_HIP, "stream for the absorbed cross-attention weights"); }
     for (size_t l = 0; l < L; ++l) {
         const f16* wk = m->ckv_w + (l * 2 * d) * d;
         const f16* wv = m->ckv_w + (l * 2 * d + d) * d;
-        f16* p = c.take<f16>(d * d); xabs_tile_wk(wk, (int)d, (int)H, p, st); tiles[l].wkT = p;
-        p = c.take<f16>(d * d); dec32_tile_weights(wv, (int)d, (int)d, p, st); tiles[l].wv_t = p;
+        xabs_tile_wk(wk, (int)d, (int)H, writable(tiles[l].wkT), st);
+        dec32_tile_weights(wv, (int)d, (int)d, writable(tiles[l].wv_t), st);
         tiles[l].bv = m->ckv_b + l * 2 * d + d;
     }
     hipError_t le = hipGetLastError();
     if (le == hipSuccess) le = hipStreamSynchronize(st);
     hipStreamDestroy(st);
     if (le != hipSuccess) {         // nothing half-built stays behind: the next absorbed session tries again
-        hipFree(m->xabs_blob);
-        m->xabs_blob = nullptr;
+        m->mem.release(blob);
         return set_error(WH_ERR_HIP, "building the absorbed cross-attention weights failed: %s", hipGetErrorString(le));
     }
     m->xabs.swap(tiles);          // published complete: sessions only read it after their own build_xabs call returned
@@ -248,28 +242,14 @@ static int set_alignment_heads(wh_model* m, const int32_t* pairs, int n) {
     }
     m->align_slot = slot;
     m->n_align = cnt;
-    if (!m->align_slot_dev) WH_HIP(hipMalloc((void**)&m->align_slot_dev, sizeof(int) * L * H));
+    if (!m->align_slot_dev) WH_HIP(m->mem.alloc(&m->align_slot_dev, (size_t)L * H, false));
     WH_HIP(hipMemcpy(m->align_slot_dev, slot.data(), sizeof(int) * L * H, hipMemcpyHostToDevice));
     return WH_OK;
 }
 
-static int model_create_impl(const void* blob, size_t nbytes, int device, wh_model** out);
-// C entry points never let a C++ exception (bad_alloc from a hostile header, ...) cross the ABI
-extern "C" int wh_model_create(const void* blob, size_t nbytes, int device, wh_model** out) {
-    try { return model_create_impl(blob, nbytes, device, out); }
-    catch (const std::exception& e) { return set_error(WH_ERR_MODELS_UNAVAILABLE, "wh_model_create: %s", e.what()); }
-    catch (...) { return set_error(WH_ERR_MODELS_UNAVAILABLE, "wh_model_create: unknown exception"); }
-}
-static int model_create_impl(const void* blob, size_t nbytes, int device, wh_model** out) {
-    if (!blob || !out || nbytes < 56) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_model_create: null or truncated blob");
+// everything wh_model_create puts into a fresh model; on an error the caller destroys it with what it holds so far
+static int model_build(wh_model* m, const void* blob, size_t nbytes, int device) {
     const unsigned char* p = (const unsigned char*)blob;
-    if (memcmp(p, "WHIPW001", 8) != 0) return set_error(WH_ERR_MODELS_UNAVAILABLE, "wh_model_create: bad magic (expected WHIPW001)");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return set_error(WH_ERR_HIP, "no HIP device visible: the whisperhip product path has no CPU fallback");
-    if (device < 0 || device >= ndev) return set_error(WH_ERR_INVALID_ARGUMENT, "device %d out of range (%d visible)", device, ndev);
-    WH_HIP(hipSetDevice(device));
-    wh_model* m = new wh_model();
     m->device = device;
     memcpy(&m->dims, p + 8, sizeof(wh_dims));
     int32_t n_tensors;
@@ -280,24 +260,20 @@ static int model_create_impl(const void* blob, size_t nbytes, int device, wh_mod
         D.n_audio_state != D.n_text_state || D.n_audio_state > 1280 || (D.n_mels != 80 && D.n_mels != 128) ||
         D.n_audio_layer < 1 || D.n_audio_layer > 64 || D.n_text_layer < 1 || D.n_text_layer > 64 || D.n_vocab < 51864 || D.n_vocab > kMaxVocab ||
         D.n_text_ctx < kMaxTok || D.n_text_ctx > 4096 || n_tensors <= 0 || n_tensors > 65536 ||
-        56 + (size_t)n_tensors * sizeof(BlobEntry) > nbytes) {
-        delete m;
+        56 + (size_t)n_tensors * sizeof(BlobEntry) > nbytes)
         return set_error(WH_ERR_MODELS_UNAVAILABLE, "unsupported model dimensions in blob header");
-    }
-    hipError_t e = hipMalloc(&m->blob_dev, nbytes);
-    if (e != hipSuccess) { delete m; return set_error(WH_ERR_HIP, "hipMalloc(%zu) for weights failed: %s", nbytes, hipGetErrorString(e)); }
+    hipError_t e = m->mem.alloc(&m->blob_dev, nbytes, false);
+    if (e != hipSuccess) return set_error(WH_ERR_HIP, "hipMalloc(%zu) for weights failed: %s", nbytes, hipGetErrorString(e));
     m->blob_bytes = nbytes;
     e = hipMemcpy(m->blob_dev, blob, nbytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { wh_model_destroy(m); return set_error(WH_ERR_HIP, "weight upload failed: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) return set_error(WH_ERR_HIP, "weight upload failed: %s", hipGetErrorString(e));
     for (int i = 0; i < n_tensors; ++i) {
         BlobEntry en;
         memcpy(&en, p + 56 + (size_t)i * sizeof(BlobEntry), sizeof(BlobEntry));
-        if (en.offset < 0 || en.nbytes < 0 || (size_t)en.offset > nbytes || (size_t)en.nbytes > nbytes - (size_t)en.offset) {
-            wh_model_destroy(m);
+        if (en.offset < 0 || en.nbytes < 0 || (size_t)en.offset > nbytes || (size_t)en.nbytes > nbytes - (size_t)en.offset)
             return set_error(WH_ERR_MODELS_UNAVAILABLE, "tensor %d out of blob bounds", i);
-        }
         WhTensor t;
-        t.dev = (char*)m->blob_dev + en.offset;
+        t.dev = m->blob_dev + en.offset;
         t.dtype = en.dtype; t.ndim = en.ndim; t.nbytes = (size_t)en.nbytes;
         for (int k = 0; k < 4; ++k) t.shape[k] = en.shape[k];
         char nm[65]; memcpy(nm, en.name, 64); nm[64] = 0;
@@ -306,23 +282,38 @@ static int model_create_impl(const void* blob, size_t nbytes, int device, wh_mod
     int r = bind_weights(m);
     if (!r) r = build_mel_tables(m);
     if (!r) r = build_dec32(m);
-    if (!r) {
-        std::vector<int32_t> pairs;
-        auto ah = m->t.find("dec.alignment_heads");      // optional int32 [n][2] written by checkpoint conversion (generation_config.alignment_heads)
-        if (ah != m->t.end() && ah->second.dtype == 2 && ah->second.nbytes % 8 == 0 && ah->second.nbytes > 0) {
-            pairs.resize(ah->second.nbytes / 4);
-            if (hipMemcpy(pairs.data(), ah->second.dev, ah->second.nbytes, hipMemcpyDeviceToHost) != hipSuccess) pairs.clear();
-        }
-        if (pairs.empty())            // default: every head of the upper half of the decoder (openai/whisper model.py)
-            for (int l = D.n_text_layer / 2; l < D.n_text_layer; ++l)
-                for (int h = 0; h < D.n_text_head; ++h) { pairs.push_back(l); pairs.push_back(h); }
-        r = set_alignment_heads(m, pairs.data(), (int)pairs.size() / 2);
+    if (r) return r;
+    std::vector<int32_t> pairs;
+    auto ah = m->t.find("dec.alignment_heads");      // optional int32 [n][2] written by checkpoint conversion (generation_config.alignment_heads)
+    if (ah != m->t.end() && ah->second.dtype == 2 && ah->second.nbytes % 8 == 0 && ah->second.nbytes > 0) {
+        pairs.resize(ah->second.nbytes / 4);
+        if (hipMemcpy(pairs.data(), ah->second.dev, ah->second.nbytes, hipMemcpyDeviceToHost) != hipSuccess) pairs.clear();
     }
-    if (r) { wh_model_destroy(m); return r; }
-    if (hipMalloc((void**)&m->xattn_gate, 256) != hipSuccess || hipMemset(m->xattn_gate, 0, 256) != hipSuccess) {      // its own cache lines
-        wh_model_destroy(m);
+    if (pairs.empty())            // default: every head of the upper half of the decoder (openai/whisper model.py)
+        for (int l = D.n_text_layer / 2; l < D.n_text_layer; ++l)
+            for (int h = 0; h < D.n_text_head; ++h) { pairs.push_back(l); pairs.push_back(h); }
+    r = set_alignment_heads(m, pairs.data(), (int)pairs.size() / 2);
+    if (r) return r;
+    if (m->mem.alloc(&m->xattn_gate, 64, true) != hipSuccess)       // 256 bytes: its own cache lines
         return set_error(WH_ERR_HIP, "hipMalloc of the cross-attention gate word failed");
-    }
+    return WH_OK;
+}
+
+extern "C" int wh_model_create(const void* blob, size_t nbytes, int device, wh_model** out) {
+    if (!blob || !out || nbytes < 56) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_model_create: null or truncated blob");
+    if (memcmp(blob, "WHIPW001", 8) != 0) return set_error(WH_ERR_MODELS_UNAVAILABLE, "wh_model_create: bad magic (expected WHIPW001)");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return set_error(WH_ERR_HIP, "no HIP device visible: the whisperhip product path has no CPU fallback");
+    if (device < 0 || device >= ndev) return set_error(WH_ERR_INVALID_ARGUMENT, "device %d out of range (%d visible)", device, ndev);
+    WH_HIP(hipSetDevice(device));
+    // C entry points never let a C++ exception (bad_alloc from a hostile header, ...) cross the ABI; every failure ends in wh_model_destroy
+    wh_model* m = nullptr;
+    int r;
+    try { m = new wh_model(); r = model_build(m, blob, nbytes, device); }
+    catch (const std::exception& e) { r = set_error(WH_ERR_MODELS_UNAVAILABLE, "wh_model_create: %s", e.what()); }
+    catch (...) { r = set_error(WH_ERR_MODELS_UNAVAILABLE, "wh_model_create: unknown exception"); }
+    if (r) { wh_model_destroy(m); return r; }
     *out = m;
     return WH_OK;
 }
@@ -346,16 +337,7 @@ extern "C" int wh_model_load(const char* path, int device, wh_model** out) {
     }
 }
 
-extern "C" void wh_model_destroy(wh_model* m) {
-    if (!m) return;
-    if (m->blob_dev) hipFree(m->blob_dev);
-    if (m->dec32_blob) hipFree(m->dec32_blob);
-    if (m->xabs_blob) hipFree(m->xabs_blob);
-    if (m->mel_tables_dev) hipFree(m->mel_tables_dev);
-    if (m->align_slot_dev) hipFree(m->align_slot_dev);
-    if (m->xattn_gate) hipFree(m->xattn_gate);
-    delete m;
-}
+extern "C" void wh_model_destroy(wh_model* m) { delete m; }      // (the model's owner frees its device memory)
 
 extern "C" int wh_model_dims(const wh_model* m, wh_dims* out) {
     if (!m || !out) return set_error(WH_ERR_MODELS_UNAVAILABLE, "model is null");
@@ -405,13 +387,8 @@ extern "C" void wh_decoding_options_default(wh_decoding_options* o) {
 }
 
 // ------------------------------------------------------------------------------------------------ session
-template <typename T>
-static int dalloc(T** p, size_t n, bool zero = true) {
-    WH_HIP(hipMalloc((void**)p, n * sizeof(T)));
-    if (zero) WH_HIP(hipMemset(*p, 0, n * sizeof(T)));
-    return WH_OK;
-}
-#define DALLOC(ptr, n) do { int _r = dalloc(&(ptr), (size_t)(n)); if (_r) { wh_session_destroy(s); return _r; } } while (0)
+// zero-filled, on the NULL stream (session_build ends with the device-wide synchronisation that orders the fills before the session's stream)
+#define DALLOC(ptr, n) WH_HIP(s->mem.alloc(&(ptr), (size_t)(n), true))
 
 static int session_create_impl(wh_model* m, int max_batch, int cross_attention_mode, int cross_attention_splits, int slots_per_workgroup, wh_session** out,
                                int encoder_precision = 0);
@@ -478,16 +455,12 @@ static hipError_t create_session_stream(hipStream_t* st) {
     for (int i = k * w; i < k * w + w + extra; ++i) { const int c = ((i % n_cu) + n_cu) % n_cu; mask[c >> 5] |= 1u << (c & 31); }
     return hipExtStreamCreateWithCUMask(st, (uint32_t)((n_cu + 31) / 32), mask);
 }
-static int session_create_impl(wh_model* m, int max_batch, int cross_attention_mode, int cross_attention_splits, int slots_per_workgroup, wh_session** out,
-                               int encoder_precision) {
-    if (!m || !out) return set_error(WH_ERR_MODELS_UNAVAILABLE, "wh_session_create: model is null");
-    if (max_batch < 1 || max_batch > kMaxSessionSlots) return set_error(WH_ERR_INVALID_ARGUMENT, "max_batch %d out of range [1, %d]", max_batch, kMaxSessionSlots);
-    WH_HIP(hipSetDevice(m->device));
-    wh_session* s = new wh_session();
+// everything session_create_impl puts into a fresh session; on an error the caller destroys it with what it holds so far
+static int session_build(wh_session* s, wh_model* m, int max_batch, int cross_attention_mode, int cross_attention_splits, int slots_per_workgroup, int encoder_precision) {
     s->B = max_batch;
     const wh_dims& D = m->dims;
     const size_t B = max_batch, d = D.n_audio_state, L = D.n_text_layer, V = D.n_vocab, H = D.n_text_head;
-    if (create_session_stream(&s->st) != hipSuccess) { delete s; return set_error(WH_ERR_HIP, "hipStreamCreate failed"); }
+    if (create_session_stream(&s->st) != hipSuccess) return set_error(WH_ERR_HIP, "hipStreamCreate failed");
     s->m = m;                       // from here on wh_session_destroy undoes the count
     m->n_sessions.fetch_add(1);
     DALLOC(s->pcm, B * kWindowSamples); DALLOC(s->n_valid, B);
@@ -514,23 +487,18 @@ static int session_create_impl(wh_model* m, int max_batch, int cross_attention_m
         else {
             s->use_xabs = xabs_auto_width((int)d, (int)H) && (xabs_mode < 0 ? max_batch >= wh_xabs_auto_min_slots() : xabs_mode != 0);
         }
-        if (s->use_xabs) { const int r_ = build_xabs(m); if (r_) { wh_session_destroy(s); return r_; } }
+        if (s->use_xabs) { const int r_ = build_xabs(m); if (r_) return r_; }
     }
     if (s->use_xabs) {
-        const size_t nht = H > 16 ? 2 : 1, S = kXabsSplits;
-        const size_t bytes = 2 * (B * nht * (d / 32) * 1024) + S * H * (d / 8) * B * 32 + S * H * B * 8 + 4 * 256;
-        if (hipMalloc(&s->xabs_blob, bytes) != hipSuccess || hipMemset(s->xabs_blob, 0, bytes) != hipSuccess) {
-            wh_session_destroy(s);
-            return set_error(WH_ERR_HIP, "hipMalloc(%zu) for the absorbed cross-attention buffers failed", bytes);
-        }
-        Carver c; c.base = (char*)s->xabs_blob;
+        Xabs probe{};                 // (measured into scratch: the session never holds the bare offsets)
+        const size_t bytes = mem::carve_session_xabs(nullptr, d, H, B, probe);
+        char* blob = nullptr;
+        if (s->mem.alloc(&blob, bytes, true) != hipSuccess) return set_error(WH_ERR_HIP, "hipMalloc(%zu) for the absorbed cross-attention buffers failed", bytes);
+        mem::carve_session_xabs(blob, d, H, B, s->xabs);
         s->xabs.layers_host = m->xabs.data();
         s->xabs.n_split = cross_attention_splits > 0 ? cross_attention_splits : xabs_splits(max_batch);
         s->xabs.spw = slots_per_workgroup > 0 ? slots_per_workgroup : 1;
         if (const int v = knob::now<knob::WH_XABS_SPW>()) s->xabs.spw = v;      // A/B override (1 .. kXabsMaxSlotsPerWorkgroup)
-        s->xabs.qf_hi = c.take<f16>(B * nht * (d / 32) * 512); s->xabs.qf_lo = c.take<f16>(B * nht * (d / 32) * 512);
-        s->xabs.part = c.take<float>(S * H * (d / 8) * B * 8);
-        s->xabs.ml = c.take<float2>(S * H * B);
     } else {
         DALLOC(s->cross_k_hi, L * B * kCtx * d); DALLOC(s->cross_v_hi, L * B * kCtx * d);
         DALLOC(s->cross_k_lo, L * B * kCtx * d); DALLOC(s->cross_v_lo, L * B * kCtx * d);
@@ -542,28 +510,31 @@ static int session_create_impl(wh_model* m, int max_batch, int cross_attention_m
     DALLOC(s->seq, B); DALLOC(s->cfg_dev, 1); DALLOC(s->suppress_dev, kMaxSuppress); DALLOC(s->sup_mask_dev, V); DALLOC(s->stats, B * kStatBlocks * 8);
     DALLOC(s->tok_out_dev, B); DALLOC(s->lp_out_dev, B); DALLOC(s->scratch_logits, V);
     {
-        const size_t n_bt = (B + 31) / 32, R = n_bt * 32;
-        const size_t bytes = 2 * R * d * 4 + 4 * R * d * 2 + 2 * R * 4 * d * 2 + n_bt * (d / 32) * 32 * 8 + n_bt * (size_t)kD32PartFloats * 4 + n_bt * 4096 * 4 + 16 * 256;
-        if (hipMalloc(&s->d32_blob, bytes) != hipSuccess || hipMemset(s->d32_blob, 0, bytes) != hipSuccess) {
-            wh_session_destroy(s);
-            return set_error(WH_ERR_HIP, "hipMalloc(%zu) for the decode-step buffers failed", bytes);
-        }
-        Carver c; c.base = (char*)s->d32_blob;
         Dec32& q = s->d32;
-        q.layers_host = m->dec32.data(); q.emb_t = m->emb_t; q.lg_g = m->lg_g; q.lg_c = m->lg_c; q.n_bt = (int)n_bt;
-        q.x = c.take<float>(R * d); q.q = c.take<float>(R * d);
-        q.za_hi = c.take<f16>(R * d); q.za_lo = c.take<f16>(R * d); q.zb_hi = c.take<f16>(R * d); q.zb_lo = c.take<f16>(R * d);
-        q.h = c.take<f16>(R * 4 * d); q.h_lo = c.take<f16>(R * 4 * d);
-        q.stat = c.take<float2>(n_bt * (d / 32) * 32);
-        q.part = c.take<float>(n_bt * (size_t)kD32PartFloats); q.part_floats = kD32PartFloats;
-        q.ticket = c.take<int>(n_bt * 4096);
+        Dec32 probe{};
+        const size_t bytes = mem::carve_session_d32(nullptr, d, B, probe);
+        char* blob = nullptr;
+        if (s->mem.alloc(&blob, bytes, true) != hipSuccess) return set_error(WH_ERR_HIP, "hipMalloc(%zu) for the decode-step buffers failed", bytes);
+        mem::carve_session_d32(blob, d, B, q);
+        q.layers_host = m->dec32.data(); q.emb_t = m->emb_t; q.lg_g = m->lg_g; q.lg_c = m->lg_c; q.n_bt = (int)((B + 31) / 32);
+        q.part_floats = kD32PartFloats;
     }
-    if (hipHostMalloc((void**)&s->seq_host, sizeof(SeqState) * B) != hipSuccess) { wh_session_destroy(s); return set_error(WH_ERR_HIP, "hipHostMalloc failed"); }
+    if (s->mem.alloc_pinned(&s->seq_host, B) != hipSuccess) return set_error(WH_ERR_HIP, "hipHostMalloc failed");
     for (auto& e : s->ev) hipEventCreate(&e);
     (void)wh::debug_buffer();   // WH_DBG=1 probe buffer must exist before any stream capture
     // the zero-fills above ran on the NULL stream, which does not order against the session's non-blocking stream: make sure
     // they are done before the first kernel (a late memset of e.g. the arrival counters would corrupt a running decode)
-    if (hipDeviceSynchronize() != hipSuccess) { wh_session_destroy(s); return set_error(WH_ERR_HIP, "hipDeviceSynchronize failed after session allocation"); }
+    if (hipDeviceSynchronize() != hipSuccess) return set_error(WH_ERR_HIP, "hipDeviceSynchronize failed after session allocation");
+    return WH_OK;
+}
+static int session_create_impl(wh_model* m, int max_batch, int cross_attention_mode, int cross_attention_splits, int slots_per_workgroup, wh_session** out,
+                               int encoder_precision) {
+    if (!m || !out) return set_error(WH_ERR_MODELS_UNAVAILABLE, "wh_session_create: model is null");
+    if (max_batch < 1 || max_batch > kMaxSessionSlots) return set_error(WH_ERR_INVALID_ARGUMENT, "max_batch %d out of range [1, %d]", max_batch, kMaxSessionSlots);
+    WH_HIP(hipSetDevice(m->device));
+    wh_session* s = new wh_session();
+    const int r = session_build(s, m, max_batch, cross_attention_mode, cross_attention_splits, slots_per_workgroup, encoder_precision);
+    if (r) { wh_session_destroy(s); return r; }      // the one way out of a failed creation
     *out = s;
     return WH_OK;
 }
@@ -573,24 +544,9 @@ extern "C" void wh_session_destroy(wh_session* s) {
     if (s->m) s->m->n_sessions.fetch_sub(1);
     if (s->st) hipStreamSynchronize(s->st);
     whi::drop_session_graphs(s);
-    if (s->d32_blob) hipFree(s->d32_blob);
-    if (s->xabs_blob) hipFree(s->xabs_blob);
-    if (s->align_tmp) hipFree(s->align_tmp);
-    if (s->dtw_dev) hipFree(s->dtw_dev);
-    if (s->dtw_host) hipHostFree(s->dtw_host);
-    if (s->slot_home_dev) hipFree(s->slot_home_dev);
-    if (s->slot_home_host) hipHostFree(s->slot_home_host);
-    void* ptrs[] = {s->pcm, s->n_valid, s->logspec, s->maxkey, s->mel_t, s->mel_f32, s->h1, s->x, s->xn, s->q16, s->k16, s->vt16, s->att16,
-                    s->hmlp, s->enc16, s->enc32, s->cross_k_hi, s->cross_v_hi, s->cross_k_lo, s->cross_v_lo, s->self_k, s->self_v, s->part, s->ticket, s->logits,
-                    s->align, s->align_mean, s->seq, s->cfg_dev, s->suppress_dev, s->sup_mask_dev, s->stats, s->tok_out_dev, s->lp_out_dev, s->scratch_logits,
-                    s->beam_owner, s->beam_tok, s->beam_lp, s->beam_seq_alt, s->beam_owner_alt, s->beam_sum, s->beam_audio, s->beam_fin_tok, s->beam_fin_lp,
-                    s->beam_fin_sum, s->beam_fin_len, s->mel_t_lo, s->h1_lo, s->xn_lo, s->att_lo, s->hmlp_lo, s->enc_lo};
-    for (void* p : ptrs) if (p) hipFree(p);
-    if (s->seq_host) hipHostFree(s->seq_host);
-    if (s->beam_audio_host) hipHostFree(s->beam_audio_host);
     for (auto& e : s->ev) if (e) hipEventDestroy(e);
     if (s->st) hipStreamDestroy(s->st);
-    delete s;
+    delete s;                       // (the session's owner frees its device and pinned memory)
 }
 extern "C" int wh_session_max_batch(const wh_session* s) { return s ? s->B : -1; }
 extern "C" int wh_session_cross_attention_mode(const wh_session* s) { return s ? (s->use_xabs ? 1 : 0) : -1; }
@@ -630,6 +586,9 @@ extern "C" int wh_debug_peek(wh_session* s, const char* name, void* out, size_t 
     WH_HIP(hipMemcpy(out, src, nbytes, hipMemcpyDeviceToHost));
     return WH_OK;
 }
+// Development aid: device + pinned allocations the models, sessions and stand-alone entry points of this process hold right now (a leak
+// shows here without reading the card's free memory, which other processes move)
+extern "C" long long wh_debug_live_allocations(void) { return wh::mem::g_live.load(std::memory_order_relaxed); }
 extern "C" int wh_session_synchronize(wh_session* s) {
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "session is null");
     WH_HIP(hipStreamSynchronize(s->st));
@@ -830,13 +789,13 @@ int ensure_align(wh_session* s) {
     if (s->align && s->n_align_alloc != s->m->n_align) {
         WH_HIP(hipStreamSynchronize(s->st));
         drop_session_graphs(s);
-        hipFree(s->align);
+        s->mem.release(s->align);
         s->align = nullptr;
         s->n_align_alloc = 0;      // nothing is allocated: sizes derived from it (graph keys, align_tmp) must not see the old head count
     }
     if (!s->align && s->m->n_align > 0) {
         size_t n = (size_t)s->B * kMaxTok * s->m->n_align * kCtx;
-        WH_HIP(hipMalloc((void**)&s->align, n * sizeof(float)));
+        WH_HIP(s->mem.alloc(&s->align, n, false));
         WH_HIP(hipMemsetAsync(s->align, 0, n * sizeof(float), s->st));
         s->n_align_alloc = s->m->n_align;
     }
@@ -903,9 +862,9 @@ extern "C" int wh_predict_logits(wh_session* s, int batch, const int32_t* tokens
 // scratch of the optional alignment post-processing (one slot at a time), sized for the session's current alignment-head count
 static int ensure_align_tmp(wh_session* s) {
     const size_t H = (size_t)s->n_align_alloc;
-    if (s->align_tmp && s->align_tmp_heads != s->n_align_alloc) { WH_HIP(hipStreamSynchronize(s->st)); hipFree(s->align_tmp); s->align_tmp = nullptr; }
+    if (s->align_tmp && s->align_tmp_heads != s->n_align_alloc) { WH_HIP(hipStreamSynchronize(s->st)); s->mem.release(s->align_tmp); s->align_tmp = nullptr; }
     if (!s->align_tmp) {
-        WH_HIP(hipMalloc((void**)&s->align_tmp, ((size_t)kMaxTok * H * kCtx + 2 * H * kCtx + 256) * sizeof(float)));
+        WH_HIP(s->mem.alloc(&s->align_tmp, (size_t)kMaxTok * H * kCtx + 2 * H * kCtx + 256, false));
         s->align_tmp_heads = s->n_align_alloc;
     }
     return WH_OK;
@@ -947,13 +906,9 @@ int alignment_paths(wh_session* s, int batch, const int32_t* rows, const int32_t
         if (rows[b] < 0 || rows[b] > kDtwMaxRows) return set_error(WH_ERR_INVALID_ARGUMENT, "alignment paths: rows[%d] = %d outside [0, %d]", b, rows[b], kDtwMaxRows);
         max_rows = std::max(max_rows, (int)rows[b]);
     }
-    if (!s->dtw_dev) {
-        WH_HIP(hipMalloc((void**)&s->dtw_dev, (2 * B + 2 * B * cap) * sizeof(int)));
-        if (hipHostMalloc((void**)&s->dtw_host, (B + 2 * B * cap) * sizeof(int32_t)) != hipSuccess) {
-            hipFree(s->dtw_dev); s->dtw_dev = nullptr;
-            return set_error(WH_ERR_HIP, "hipHostMalloc of the alignment path buffer failed");
-        }
-    }
+    if (!s->dtw_dev) WH_HIP(s->mem.alloc(&s->dtw_dev, 2 * B + 2 * B * cap, false));
+    if (!s->dtw_host && s->mem.alloc_pinned(&s->dtw_host, B + 2 * B * cap) != hipSuccess)
+        return set_error(WH_ERR_HIP, "hipHostMalloc of the alignment path buffer failed");
     int* rows_dev = s->dtw_dev;
     int* len_dev = rows_dev + B;                      // lengths | text_idx | time_idx are contiguous: one copy brings them back
     int *ti_dev = len_dev + B, *tj_dev = ti_dev + B * cap;

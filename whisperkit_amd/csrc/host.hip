@@ -469,10 +469,8 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
     struct PassScope { wh_session* s; ~PassScope() { s->pass_mapped = false; } } pass_scope{s};      // (every exit: the next caller of decode_buffers sees a plain pass)
     const int width = cp.compact ? cp.width : batch;
     if (cp.compact) {
-        if (!s->slot_home_dev) {
-            WH_HIP(hipMalloc((void**)&s->slot_home_dev, sizeof(int32_t) * s->B));
-            WH_HIP(hipHostMalloc((void**)&s->slot_home_host, sizeof(int32_t) * 2 * s->B));
-        }
+        if (!s->slot_home_dev) WH_HIP(s->mem.alloc(&s->slot_home_dev, (size_t)s->B, false));
+        if (!s->slot_home_host) WH_HIP(s->mem.alloc_pinned(&s->slot_home_host, 2 * (size_t)s->B));
         int32_t* home = s->slot_home_host, *live = s->slot_home_host + s->B;
         if (plan::compact_slot_map(active, batch, width, home, live) != n_live) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text: the compacted pass does not hold its live slots");
         for (int i = 0; i < width; ++i) init_slot(s->seq_host[i], home[i], live[i] != 0);

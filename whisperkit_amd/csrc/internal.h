@@ -8,9 +8,34 @@
 #include <unordered_map>
 #include <vector>
 
+#include "devmem.h"
 #include "kernels.h"
 #include "text.h"
 #include "whisperhip.h"
+
+// every device and pinned allocation of a model or a session goes through one of these (devmem.h)
+struct HipMem {
+    using Err = hipError_t;
+    static constexpr Err ok = hipSuccess, out_of_memory = hipErrorOutOfMemory;
+    static Err dev_malloc(void** p, size_t n) { return hipMalloc(p, n); }
+    static Err dev_free(void* p) { return hipFree(p); }
+    static Err host_malloc(void** p, size_t n) { return hipHostMalloc(p, n); }
+    static Err host_free(void* p) { return hipHostFree(p); }
+    static Err dev_memset(void* p, int v, size_t n) { return hipMemset(p, v, n); }
+};
+using DevMem = wh::mem::Owned<HipMem>;
+
+// devmem.h sizes every carved region by the element type of its destination field, and tests/native/devmem_check.cpp checks the offsets
+// against mirror structs of these widths: a field that changes its type in kernels.h stops here, not in a silently moved offset
+#define W_(S, f) sizeof(*static_cast<wh::S*>(nullptr)->f)
+static_assert(W_(Dec32LayerW, qkv_t) == 2 && W_(Dec32LayerW, o_t) == 2 && W_(Dec32LayerW, cq_t) == 2 && W_(Dec32LayerW, co_t) == 2 && W_(Dec32LayerW, fc1_t) == 2 && W_(Dec32LayerW, fc2_t) == 2 &&
+              W_(Dec32LayerW, qkv_g) == 4 && W_(Dec32LayerW, qkv_c) == 4 && W_(Dec32LayerW, cq_g) == 4 && W_(Dec32LayerW, cq_c) == 4 && W_(Dec32LayerW, fc1_g) == 4 && W_(Dec32LayerW, fc1_c) == 4, "Dec32LayerW: carved element widths");
+static_assert(W_(Dec32, emb_t) == 2 && W_(Dec32, za_hi) == 2 && W_(Dec32, za_lo) == 2 && W_(Dec32, zb_hi) == 2 && W_(Dec32, zb_lo) == 2 && W_(Dec32, h) == 2 && W_(Dec32, h_lo) == 2 &&
+              W_(Dec32, lg_g) == 4 && W_(Dec32, lg_c) == 4 && W_(Dec32, x) == 4 && W_(Dec32, q) == 4 && W_(Dec32, part) == 4 && W_(Dec32, ticket) == 4 &&
+              W_(Dec32, stat) == 8, "Dec32: carved element widths");
+static_assert(W_(XabsLayerW, wkT) == 2 && W_(XabsLayerW, wv_t) == 2 && W_(Xabs, qf_hi) == 2 && W_(Xabs, qf_lo) == 2 && W_(Xabs, part) == 4 && W_(Xabs, ml) == 8,
+              "XabsLayerW / Xabs: carved element widths");
+#undef W_
 
 struct WhTensor {
     void* dev = nullptr;
@@ -26,24 +51,22 @@ struct EncLayerW {
 };
 
 struct wh_model {
+    DevMem mem;                       // owns every device allocation below
     wh_dims dims{};
     int device = 0;
-    void* blob_dev = nullptr;
+    char* blob_dev = nullptr;
     size_t blob_bytes = 0;
     std::unordered_map<std::string, WhTensor> t;
     wh::MelTables mel{};
-    void* mel_tables_dev = nullptr;
     std::vector<EncLayerW> enc;
     std::vector<wh::DecLayerW> dec;
     const f16 *conv1_w, *conv2_w, *emb, *ckv_w;
     const float *conv1_b, *conv2_b, *enc_pos, *lnp_g, *lnp_b, *dec_pos, *ckv_b, *lnf_g, *lnf_b;
     // MFMA decode path (decoder32.hip): decoder weights re-tiled into MFMA A-fragment order + LayerNorm fold vectors, built at load
     std::vector<wh::Dec32LayerW> dec32;
-    void* dec32_blob = nullptr;
     const f16* emb_t = nullptr; const float *lg_g = nullptr, *lg_c = nullptr;
     // weight-absorbed cross-attention (xabs.hip): W_k^T tiles + W_v tiles per layer, built by the first session that uses the path
     std::vector<wh::XabsLayerW> xabs;
-    void* xabs_blob = nullptr;
     std::mutex xabs_mu;
     std::vector<int> align_slot;   // [L*H] -> slot or -1
     int n_align = 0;
@@ -64,6 +87,7 @@ struct WhGraphKey {
 };
 
 struct wh_session {
+    DevMem mem;                       // owns every device and pinned allocation below, the lazily allocated ones included
     wh_model* m = nullptr;
     int B = 0;
     hipStream_t st = nullptr;
@@ -95,10 +119,8 @@ struct wh_session {
     unsigned long long graph_tick = 0;
     const volatile int32_t* cancel_flag = nullptr; // polled between step graphs and pipeline stages (Task.checkCancellation)
     bool use_xabs = false;                // cross-attention path of this session (fixed at creation: never a function of the live batch)
-    wh::Xabs xabs{};                      // absorbed queries + split partials (one allocation: xabs_blob)
-    void* xabs_blob = nullptr;
-    wh::Dec32 d32{};                      // decode-step activations: residual, planes, split-K scratch (one allocation: d32_blob)
-    void* d32_blob = nullptr;
+    wh::Xabs xabs{};                      // absorbed queries + split partials (one allocation: devmem.h carve_session_xabs)
+    wh::Dec32 d32{};                      // decode-step activations: residual, planes, split-K scratch (one allocation: devmem.h carve_session_d32)
     wh::SeqState* seq = nullptr;
     wh::SeqState* seq_host = nullptr;     // pinned
     wh::SamplerCfg* cfg_dev = nullptr;
