@@ -67,6 +67,10 @@ public final class HIPSession {
     /// ladder.  Same results, bit for bit.
     public enum FallbackCompaction: Int32 { case off = 0, on = 1 }
     public var fallbackCompaction: FallbackCompaction = .off { didSet { _ = wh_session_set_fallback_compaction(handle, fallbackCompaction.rawValue) } }
+    /// In-pass compaction (wh_session_set_inpass_compaction): `.off` (default) = a decode pass keeps the width it began with until every window is done;
+    /// `.on` = it narrows between step graphs (to 32 / 64 / 128 slots, when a 32-slot batch tile is saved) as its windows reach EOT.  Same results, bit for bit.
+    public enum InPassCompaction: Int32 { case off = 0, on = 1 }
+    public var inPassCompaction: InPassCompaction = .off { didSet { _ = wh_session_set_inpass_compaction(handle, inPassCompaction.rawValue) } }
     public enum BeamRanking: Int32 { case host = 0, device = 1 }
     public var beamRanking: BeamRanking = .host { didSet { _ = wh_session_set_beam_ranking(handle, beamRanking.rawValue) } }
     public init(model: HIPModel, maxBatch: Int = 1, crossAttention: CrossAttentionMode = .automatic, keySplits: Int = 0, slotsPerWorkgroup: Int = 0,

@@ -432,6 +432,22 @@ int wh_session_fallback_compaction(const wh_session* s);
 /* Counters of the session since its creation: decode passes (one per wh_decode_text / wh_decode_text_languages call or ladder rung), how many
  * of them ran compacted, and the sum of the batch width over the decoder steps launched by them.  Any pointer may be NULL. */
 int wh_session_decode_pass_stats(const wh_session* s, int64_t* passes, int64_t* compacted_passes, int64_t* slot_steps);
+/* In-pass compaction.  0 = off (default): a decode pass replays its step graphs at the width it began with until EVERY slot is done - a slot that
+ * reached EOT returns early from its kernels, but the grids stay sized by the 32-slot batch tiles, so one long window holds a 256-slot batch at eight
+ * tiles per step.  1 = on: a pass of wh_decode_text / wh_decode_text_languages / wh_transcribe* narrows BETWEEN step graphs when the slots still
+ * decoding fit a lower rung of the ladder above (32 / 64 / 128) and that saves at least one batch tile, and at least 16 steps are left.  The live
+ * slots move to compact slots 0 .. n - 1 in ascending home order (their decode state on the device, no host round trip); each keeps reading its
+ * earlier self-attention rows where they were written (a row -> owner table, no cache row is copied) and writes the later ones into its new
+ * slot's cache.  Results are identical to the off mode, bit for bit: tokens, log-probabilities, steps, fallback fields, alignment rows, word
+ * timings and progress callbacks (wh_progress.slot stays the home slot; a callback that returns 0 retires its slot like an EOT).  The option
+ * composes with wh_session_set_fallback_compaction: a pass that begins compacted may narrow further.  NOT narrowed: the beam-search pass
+ * (wh_decode_text_beam, the T = 0 pass of wh_transcribe* with beam_size > 1), wh_decode_text_custom, wh_detect_language and the step API.
+ * Returns WH_ERR_INVALID_ARGUMENT for a NULL session or a mode other than 0 / 1; the getter returns the mode, -1 for NULL. */
+int wh_session_set_inpass_compaction(wh_session* s, int mode);
+int wh_session_inpass_compaction(const wh_session* s);
+/* Counters of the session since its creation: narrowings, and the slot-steps they saved (width the pass began with minus the width launched, summed
+ * over the decoder steps launched).  wh_session_decode_pass_stats keeps its meaning: slot_steps sums the width actually launched.  Any pointer may be NULL. */
+int wh_session_inpass_compaction_stats(const wh_session* s, int64_t* switches, int64_t* slot_steps_saved);
 /* ---- user-pluggable LogitsFiltering / TokenSampling (Core/Text/LogitsFilter.swift:8-10, Core/Text/TokenSampler.swift:8-11) ----
  * The reference runs `logitsFilters` (custom filters first, Core/TextDecoder.swift:857-899) and the `TokenSampling` object on the
  * host once per token (:641-652).  The fused device loop of wh_decode_text knows the four built-in filters and the greedy /

@@ -190,6 +190,9 @@ SYMBOLS = {
     "wh_session_set_fallback_compaction": (I, [VP, I]),
     "wh_session_fallback_compaction": (I, [VP]),
     "wh_session_decode_pass_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "wh_session_set_inpass_compaction": (I, [VP, I]),
+    "wh_session_inpass_compaction": (I, [VP]),
+    "wh_session_inpass_compaction_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "wh_session_set_beam_ranking": (I, [VP, I]),
     "wh_session_beam_ranking": (I, [VP]),
     "wh_session_beam_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -839,6 +839,28 @@ class Session:
         _check(self.lib.wh_session_decode_pass_stats(self.handle, C.byref(a), C.byref(b), C.byref(c)))
         return int(a.value), int(b.value), int(c.value)
 
+    INPASS_COMPACTIONS = {"off": 0, "on": 1}
+
+    def setInPassCompaction(self, mode: str):
+        """Whether a decode pass of decodeText / transcribe* narrows between step graphs as its windows reach EOT: "off" (default) - the pass keeps the
+        width it began with until every slot is done; "on" - when the slots still decoding fit a lower rung of the ladder (32 / 64 / 128) and that
+        saves a 32-slot batch tile, they move to the front and the following steps launch at that rung.  Results, progress callbacks, alignment
+        rows and word timings are the same in both modes, bit for bit.  Composes with setFallbackCompaction; the beam-search pass,
+        decodeTextCustom and detectLanguage never narrow."""
+        if mode not in self.INPASS_COMPACTIONS:
+            raise ValueError(f"inPassCompaction {mode!r}: expected 'on' or 'off'")
+        _check(self.lib.wh_session_set_inpass_compaction(self.handle, self.INPASS_COMPACTIONS[mode]))
+
+    @property
+    def inPassCompaction(self) -> str:
+        return {0: "off", 1: "on"}[int(self.lib.wh_session_inpass_compaction(self.handle))]
+
+    def inPassCompactionStats(self) -> Tuple[int, int]:
+        """(narrowings, slot-steps saved by them) since the session was created"""
+        a, b = C.c_int64(), C.c_int64()
+        _check(self.lib.wh_session_inpass_compaction_stats(self.handle, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
     BEAM_RANKINGS = {"host": 0, "device": 1}
 
     def setBeamRanking(self, mode: str):

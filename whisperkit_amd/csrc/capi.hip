@@ -774,6 +774,7 @@ DecodeBuffers decode_buffers(wh_session* s, int batch, int max_position) {
         db.slot_home = s->slot_home_dev;
         if (s->use_xabs) { s->xabs_pass = s->xabs; s->xabs_pass.spw = s->pass_spw; db.xabs = &s->xabs_pass; }
     }
+    if (s->pass_owner) { db.self_owner = s->inpass_dev + s->B; db.owner_slots = s->B; }       // a pass that narrowed (host.hip inpass_narrow)
     // cross-attention gate: WH_XATT_GATE=0 never, 1 always, unset: while the model carries more than one session (dec_shared.h)
     const int gate_mode = knob::once<knob::WH_XATT_GATE>();
     const bool gate_on = gate_mode < 0 ? kXattnGateDefault && m->n_sessions.load() > 1 : gate_mode != 0;
@@ -976,6 +977,19 @@ extern "C" int wh_session_set_fallback_compaction(wh_session* s, int mode) {
     return WH_OK;
 }
 extern "C" int wh_session_fallback_compaction(const wh_session* s) { return s ? s->fallback_compaction : -1; }
+extern "C" int wh_session_set_inpass_compaction(wh_session* s, int mode) {
+    if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_inpass_compaction: null session");
+    if (mode != 0 && mode != 1) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_inpass_compaction: mode %d (0 = off, 1 = on)", mode);
+    s->inpass_compaction = mode;
+    return WH_OK;
+}
+extern "C" int wh_session_inpass_compaction(const wh_session* s) { return s ? s->inpass_compaction : -1; }
+extern "C" int wh_session_inpass_compaction_stats(const wh_session* s, int64_t* switches, int64_t* slot_steps_saved) {
+    if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_inpass_compaction_stats: null session");
+    if (switches) *switches = s->inpass_switches;
+    if (slot_steps_saved) *slot_steps_saved = s->inpass_slot_steps_saved;
+    return WH_OK;
+}
 extern "C" int wh_session_decode_pass_stats(const wh_session* s, int64_t* passes, int64_t* compacted_passes, int64_t* slot_steps) {
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_decode_pass_stats: null session");
     if (passes) *passes = s->decode_passes;

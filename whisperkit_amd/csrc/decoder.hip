@@ -298,6 +298,8 @@ __global__ __launch_bounds__(256) void dec_self_attn_owner_kernel(const AttnArgs
 #pragma unroll
     for (int i = 0; i < PASSES; ++i) {
         const int key = min(kg + 32 * i, n_load - 1);
+        // (a.batch bounds the OWNERS, not the grid: a pass that narrowed in flight is launched with the session's slot count here while blockIdx.y
+        // stays below the pass's width - launch_decoder_step.  Nothing else in this kernel, store_att included, may read a.batch.)
         const int own = min(max(a.self_owner[(size_t)b * kMaxTok + key], 0), a.batch - 1);
         off[i] = (((size_t)own * H + h) * kMaxTok + key) * kHeadDim + part * 8;
     }
@@ -864,7 +866,11 @@ void launch_decoder_step(const DecodeBuffers& db, const SamplerCfg* cfg_dev, con
         at.att_hi = D.zb_hi; at.att_lo = D.zb_lo; at.part = db.part; at.ticket = db.ticket; at.seq = db.seq;
         at.align = db.align; at.align_slot = db.align_slot; at.n_align = db.n_align; at.gate = db.xattn_gate;
         at.self_rows = db.self_rows; at.self_owner = db.self_owner;
-        launch_self_attn(at, H, B, st);
+        if (db.self_owner && db.owner_slots > B) {      // a narrowed pass: owners name any slot of the session (the owner kernel clamps to its `batch`, which it reads for nothing else)
+            AttnArgs sa = at;
+            sa.batch = db.owner_slots;
+            launch_self_attn(sa, H, B, st);
+        } else launch_self_attn(at, H, B, st);
         a = base;               // x += W_o att + b_o; planes gamma_2 x, statistics for LN2
         a.N = d; a.K = d; a.Wt = t.o_t; a.zhi = D.zb_hi; a.zlo = D.zb_lo; a.bias = w.o_b; a.gamma_next = w.ln2_g;
         a.zhi_out = D.za_hi; a.zlo_out = D.za_lo; a.stat_out = D.stat; a.prof_kind = KK_DEC_OPROJ;

@@ -266,7 +266,7 @@ static int get_step_graph(wh_session* s, int batch, int first_step, hipGraphExec
     DecodeBuffers db = whi::decode_buffers(s, batch, first_step + kStepsPerGraph - 1);
     // (a compacted pass bakes the slot table's address, the mapped kernel instantiations and its own slots per workgroup into its launches)
     const WhGraphKey key{batch, s->align_enabled ? 1 : 0, s->fused_greedy ? 1 : 0, s->align_enabled ? s->n_align_alloc : 0, db.self_rows, db.xattn_gate ? 1 : 0,
-                         db.slot_home ? 1 : 0, db.slot_home ? s->pass_spw : 0};
+                         db.slot_home ? 1 : 0, db.slot_home ? s->pass_spw : 0, db.self_owner ? 1 : 0};
     auto it = s->graphs.find(key);
     if (it != s->graphs.end()) { s->graph_use[key] = ++s->graph_tick; *out = it->second; return WH_OK; }
     // The cache is capped (a large-v3 step graph holds ~2.5 k kernel nodes; a configuration = everything of the key but the row bound has up
@@ -275,7 +275,7 @@ static int get_step_graph(wh_session* s, int batch, int first_step, hipGraphExec
     const size_t cap = (size_t)knob::once<knob::WH_GRAPH_CAP>();
     while (s->graphs.size() >= cap) {
         auto same_cfg = [](const WhGraphKey& a, const WhGraphKey& b) {
-            return a.batch == b.batch && a.align == b.align && a.fused == b.fused && a.n_align == b.n_align && a.gate == b.gate && a.mapped == b.mapped && a.spw == b.spw;
+            return a.batch == b.batch && a.align == b.align && a.fused == b.fused && a.n_align == b.n_align && a.gate == b.gate && a.mapped == b.mapped && a.spw == b.spw && a.owner == b.owner;
         };
         const WhGraphKey* victim = nullptr;
         unsigned long long victim_last = ~0ull;
@@ -345,32 +345,91 @@ static int report_progress(wh_session* s, int batch) {
     return WH_OK;
 }
 
-static int run_token_loop(wh_session* s, int batch, int loop_count) {
+// ---- in-pass compaction (wh_session_set_inpass_compaction): the layout of the pass run_token_loop drives, in the session's home-slot terms
+struct PassLayout {
+    int width = 0, width0 = 0;               // compact slots now / when the pass began
+    int n_home = 0;                          // home slots of the call (its `batch`): what is read back by home slot after a narrowing
+    int switches = 0;                        // narrowings of this pass so far
+    std::vector<int32_t> home, live, owner;  // [width] home slot and live flag of every compact slot; [width][kMaxTok] row owners once switches > 0
+};
+
+// The shared narrowing step of the three loops.  `snap` is a snapshot of the slot states taken in the layout (snap_home, snap_width) - the present
+// one or an earlier, wider one of this pass; a slot that finished after the snapshot is simply carried along as done.  steps_done: steps launched so far
+// (= the token_index every live slot has when the next launch begins).  Enqueued on the session stream behind the launches so far: park (old table),
+// the new tables (from this switch's own staging region), gather; the launches that follow use the new width.  Nothing waits.
+static int inpass_narrow(wh_session* s, PassLayout& L, const SeqState* snap, const std::vector<int32_t>& snap_home, int snap_width, int steps_done, int loop_count) {
+    const int B = s->B;
+    std::vector<char> alive((size_t)B, 0);
+    for (int i = 0; i < snap_width; ++i) if (snap[i].active && !snap[i].done) alive[snap_home[i]] = 1;
+    std::vector<int32_t> keep((size_t)L.width, 0);
+    int n_live = 0;
+    for (int i = 0; i < L.width; ++i) if (L.live[i] && alive[L.home[i]]) { keep[i] = 1; ++n_live; }
+    const plan::CompactPassPlan p = plan::inpass_compact_plan(n_live, L.width, B, s->use_xabs ? s->xabs.spw : 1, loop_count - steps_done);
+    if (!p.compact || L.switches >= plan::kInpassMaxSwitches) return WH_OK;
+    const size_t region = 2 * (size_t)B + (size_t)B * kMaxTok;
+    if (!s->slot_home_dev) WH_HIP(s->mem.alloc(&s->slot_home_dev, (size_t)B, false));
+    if (!s->slot_home_host) WH_HIP(s->mem.alloc_pinned(&s->slot_home_host, 2 * (size_t)B));
+    if (!s->seq_home) WH_HIP(s->mem.alloc(&s->seq_home, (size_t)B, true));
+    if (!s->inpass_dev) WH_HIP(s->mem.alloc(&s->inpass_dev, (size_t)B + (size_t)B * kMaxTok, false));
+    if (!s->inpass_stage) WH_HIP(s->mem.alloc_pinned(&s->inpass_stage, (size_t)plan::kInpassMaxSwitches * region));
+    int32_t* home = s->inpass_stage + (size_t)L.switches * region, *live = home + B, *owner = live + B;
+    const int n = plan::inpass_compose(L.home.data(), L.live.data(), L.switches ? L.owner.data() : nullptr, L.width, keep.data(), p.width, steps_done, kMaxTok, B,
+                                       home, live, owner);
+    if (n != n_live) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text: the narrowed pass does not hold its live slots");
+    launch_seq_park(s->seq, s->seq_home, s->pass_mapped ? s->slot_home_dev : nullptr, L.width, B, s->st);
+    WH_HIP(hipMemcpyAsync(s->slot_home_dev, home, sizeof(int32_t) * p.width, hipMemcpyHostToDevice, s->st));
+    WH_HIP(hipMemcpyAsync(s->inpass_dev, live, sizeof(int32_t) * p.width, hipMemcpyHostToDevice, s->st));
+    WH_HIP(hipMemcpyAsync(s->inpass_dev + B, owner, sizeof(int32_t) * (size_t)p.width * kMaxTok, hipMemcpyHostToDevice, s->st));
+    launch_seq_gather(s->seq_home, s->seq, s->slot_home_dev, s->inpass_dev, p.width, B, s->st);
+    WH_CHECK_LAUNCH();
+    L.width = p.width; L.switches += 1;
+    L.home.assign(home, home + p.width); L.live.assign(live, live + p.width); L.owner.assign(owner, owner + (size_t)p.width * kMaxTok);
+    memcpy(s->slot_home_host, home, sizeof(int32_t) * p.width);      // report_progress: compact slot -> home slot
+    s->pass_mapped = true; s->pass_spw = p.spw; s->pass_owner = true;
+    s->inpass_switches += 1;
+    return WH_OK;
+}
+
+// L: the pass may narrow (decode_text_impl with the option on), or null.  A pass that narrowed ends with seq_host in HOME-slot terms (entry b = the final
+// state of home slot b, for the home slots the pass decoded; the caller fills in the others); otherwise seq_host holds the `batch` compact slots as ever.
+static int run_token_loop(wh_session* s, int batch, int loop_count, PassLayout* L = nullptr) {
     // every slot's state lives on the device; the host only replays step graphs and polls the done flags
-    const size_t bytes = sizeof(SeqState) * batch;
-    auto all_done = [&]() { for (int b = 0; b < batch; ++b) if (s->seq_host[b].active && !s->seq_host[b].done) return false; return true; };
+    int width = batch;                                   // (changes only through inpass_narrow)
+    auto all_done_in = [](const SeqState* q, int n) { for (int b = 0; b < n; ++b) if (q[b].active && !q[b].done) return false; return true; };
+    auto all_done = [&]() { return all_done_in(s->seq_host, width); };
+    auto count_steps = [&](int steps) { s->slot_steps += (long long)width * steps; if (L) s->inpass_slot_steps_saved += (long long)(L->width0 - width) * steps; };
+    // the last read of the pass: the compact slots, or - after a narrowing - every state by home slot (parked once more)
+    auto final_read = [&]() -> int {
+        if (L && L->switches > 0) {
+            launch_seq_park(s->seq, s->seq_home, s->slot_home_dev, width, s->B, s->st);
+            WH_CHECK_LAUNCH();
+            WH_HIP(hipMemcpyAsync(s->seq_host, s->seq_home, sizeof(SeqState) * L->n_home, hipMemcpyDeviceToHost, s->st));
+        } else WH_HIP(hipMemcpyAsync(s->seq_host, s->seq, sizeof(SeqState) * width, hipMemcpyDeviceToHost, s->st));
+        WH_HIP(hipStreamSynchronize(s->st));
+        return WH_OK;
+    };
     if (s->progress_cb) {
         // with a callback installed the host needs whole snapshots: no run-ahead, one synchronisation per 8 steps
         for (int step = 0; step < loop_count; step += kStepsPerGraph) {
             CHECK_CANCEL(s);
             hipGraphExec_t exec = nullptr;
-            if (use_graphs()) { int r = get_step_graph(s, batch, step, &exec); if (r) return r; }
-            if (exec) { WH_HIP(hipGraphLaunch(exec, s->st)); s->slot_steps += (long long)batch * kStepsPerGraph; }
+            if (use_graphs()) { int r = get_step_graph(s, width, step, &exec); if (r) return r; }
+            if (exec) { WH_HIP(hipGraphLaunch(exec, s->st)); count_steps(kStepsPerGraph); }
             else for (int i = 0; i < kStepsPerGraph && step + i < loop_count; ++i) {
-                DecodeBuffers db = whi::decode_buffers(s, batch, step + i);
+                DecodeBuffers db = whi::decode_buffers(s, width, step + i);
                 launch_decoder_step(db, s->cfg_dev, s->suppress_dev, true, s->st); WH_CHECK_LAUNCH();
-                s->slot_steps += batch;
+                count_steps(1);
             }
-            WH_HIP(hipMemcpyAsync(s->seq_host, s->seq, bytes, hipMemcpyDeviceToHost, s->st));
+            WH_HIP(hipMemcpyAsync(s->seq_host, s->seq, sizeof(SeqState) * width, hipMemcpyDeviceToHost, s->st));
             WH_HIP(hipStreamSynchronize(s->st));
             if (all_done()) break;
-            int r = report_progress(s, batch);
+            int r = report_progress(s, width);
             if (r) return r;
             if (all_done()) break;
+            // (an exact snapshot in the present layout; a slot its callback has just stopped counts as finished)
+            if (L) { r = inpass_narrow(s, *L, s->seq_host, L->home, L->width, step + kStepsPerGraph, loop_count); if (r) return r; width = L->width; }
         }
-        WH_HIP(hipMemcpyAsync(s->seq_host, s->seq, bytes, hipMemcpyDeviceToHost, s->st));
-        WH_HIP(hipStreamSynchronize(s->st));
-        return WH_OK;
+        return final_read();
     }
     if (use_graphs()) {
         const int n_graphs = (loop_count + kStepsPerGraph - 1) / kStepsPerGraph;
@@ -380,42 +439,54 @@ static int run_token_loop(wh_session* s, int batch, int loop_count) {
         auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
         const double t_begin = dbg_host ? now() : 0.0;
         struct Report { bool on; double *l, *w, t0; int n; decltype(now)* clk; ~Report() { if (on) fprintf(stderr, "[wh host] decode loop: %d graph launches, %.2f ms inside hipGraphLaunch, %.2f ms waiting for the device, %.2f ms total\n", n, *l * 1e3, *w * 1e3, ((*clk)() - t0) * 1e3); } } report{dbg_host, &t_launch, &t_wait, t_begin, n_graphs, &now};
+        // A pass that may narrow alternates between two snapshot buffers and remembers the layout each snapshot was taken in: the copy behind graph g
+        // can be of another layout than the one behind graph g - 1 that the host is looking at.  Otherwise one buffer, as ever.
+        SeqState* const snap[2] = {s->seq_host, L ? s->seq_snap : s->seq_host};
+        std::vector<int32_t> snap_home[2];
+        int snap_width[2] = {width, width};
         for (int g = 0; g < n_graphs; ++g) {
             if (cancelled(s)) { hipStreamSynchronize(s->st); return set_error(WH_ERR_CANCELLED, "decodeText: cancelled through the session's cancel flag"); }
             hipGraphExec_t exec;
-            int r = get_step_graph(s, batch, g * kStepsPerGraph, &exec);
+            int r = get_step_graph(s, width, g * kStepsPerGraph, &exec);
             if (r) return r;
             const double ta = dbg_host ? now() : 0.0;
             WH_HIP(hipGraphLaunch(exec, s->st));
-            s->slot_steps += (long long)batch * kStepsPerGraph;
+            count_steps(kStepsPerGraph);
             if (dbg_host) t_launch += now() - ta;
             // snapshot the slot states behind graph g; while it runs, look at the snapshot behind graph g-1
             // (at most one graph of run-ahead; `done` is monotonic, so a torn snapshot is harmless)
-            WH_HIP(hipMemcpyAsync(s->seq_host, s->seq, bytes, hipMemcpyDeviceToHost, s->st));
+            WH_HIP(hipMemcpyAsync(snap[g & 1], s->seq, sizeof(SeqState) * width, hipMemcpyDeviceToHost, s->st));
             WH_HIP(hipEventRecord(s->ev[g & 1], s->st));
+            snap_width[g & 1] = width;
+            if (L) snap_home[g & 1] = L->home;
             if (g >= 1) {
                 const double tb = dbg_host ? now() : 0.0;
                 WH_HIP(hipEventSynchronize(s->ev[(g - 1) & 1]));
                 if (dbg_host) t_wait += now() - tb;
-                if (all_done()) break;
+                if (all_done_in(snap[(g - 1) & 1], snap_width[(g - 1) & 1])) break;
+                // graph g + 1 launches at the width the live slots behind graph g - 1 allow
+                if (L && g + 1 < n_graphs) {
+                    r = inpass_narrow(s, *L, snap[(g - 1) & 1], snap_home[(g - 1) & 1], snap_width[(g - 1) & 1], (g + 1) * kStepsPerGraph, loop_count);
+                    if (r) return r;
+                    width = L->width;
+                }
             }
         }
     } else {
         for (int step = 0; step < loop_count; ++step) {
-            DecodeBuffers db = whi::decode_buffers(s, batch, step);
+            DecodeBuffers db = whi::decode_buffers(s, width, step);
             launch_decoder_step(db, s->cfg_dev, s->suppress_dev, true, s->st);
             WH_CHECK_LAUNCH();
-            s->slot_steps += batch;
+            count_steps(1);
             if ((step & 7) == 7 && step + 1 < loop_count) {
-                WH_HIP(hipMemcpyAsync(s->seq_host, s->seq, bytes, hipMemcpyDeviceToHost, s->st));
+                WH_HIP(hipMemcpyAsync(s->seq_host, s->seq, sizeof(SeqState) * width, hipMemcpyDeviceToHost, s->st));
                 WH_HIP(hipStreamSynchronize(s->st));
                 if (all_done()) break;
+                if (L) { int r = inpass_narrow(s, *L, s->seq_host, L->home, L->width, step + 1, loop_count); if (r) return r; width = L->width; }
             }
         }
     }
-    WH_HIP(hipMemcpyAsync(s->seq_host, s->seq, bytes, hipMemcpyDeviceToHost, s->st));
-    WH_HIP(hipStreamSynchronize(s->st));
-    return WH_OK;
+    return final_read();
 }
 
 static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options* opt, const wh_special_tokens* st, const int32_t* prompt,
@@ -466,7 +537,7 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
     for (int b = 0; b < batch; ++b) n_live += (active ? active[b] != 0 : 1);
     plan::CompactPassPlan cp{false, batch, s->use_xabs ? s->xabs.spw : 1};
     if (s->fallback_compaction == 1 && active) cp = plan::compact_pass_plan(n_live, batch, s->B, s->use_xabs ? s->xabs.spw : 1);
-    struct PassScope { wh_session* s; ~PassScope() { s->pass_mapped = false; } } pass_scope{s};      // (every exit: the next caller of decode_buffers sees a plain pass)
+    struct PassScope { wh_session* s; ~PassScope() { s->pass_mapped = false; s->pass_owner = false; } } pass_scope{s};      // (every exit: the next caller of decode_buffers sees a plain pass)
     const int width = cp.compact ? cp.width : batch;
     if (cp.compact) {
         if (!s->slot_home_dev) WH_HIP(s->mem.alloc(&s->slot_home_dev, (size_t)s->B, false));
@@ -490,9 +561,44 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
     const int loop_count = std::min(opt->sample_length, kMaxTok - 1);
     s->skip_special_in_progress = opt->skip_special_tokens != 0;
     s->special_begin_in_progress = st->special_token_begin;
-    r = run_token_loop(s, width, std::max(loop_count, 0));
-    if (r) return r;
-    if (cp.compact) {
+    // ---- in-pass compaction (wh_session_set_inpass_compaction 1): the pass may narrow between step graphs as its slots finish (run_token_loop)
+    PassLayout lay;
+    if (s->inpass_compaction == 1) {
+        if (!s->seq_snap) WH_HIP(s->mem.alloc_pinned(&s->seq_snap, (size_t)s->B));
+        lay.width = lay.width0 = width; lay.n_home = batch;
+        lay.home.resize((size_t)width); lay.live.resize((size_t)width);
+        for (int i = 0; i < width; ++i) {
+            lay.home[i] = cp.compact ? s->slot_home_host[i] : i;
+            lay.live[i] = s->seq_host[i].active;
+        }
+    }
+    // a pass that narrowed, back to home-slot terms on the device: seq_host holds the decoded windows' states by home slot; every other slot as a
+    // plain pass leaves it (initialised, inactive)
+    auto upload_home_layout = [&]() -> int {
+        for (int b = 0; b < batch; ++b) if (!(active ? active[b] != 0 : true)) init_slot(s->seq_host[b], b, false);
+        s->pass_mapped = false; s->pass_owner = false;
+        WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * batch, hipMemcpyHostToDevice, s->st));
+        WH_HIP(hipStreamSynchronize(s->st));
+        return WH_OK;
+    };
+    r = run_token_loop(s, width, std::max(loop_count, 0), s->inpass_compaction == 1 ? &lay : nullptr);
+    if (r) {
+        // an error (a cancel, a failed capture) behind a switch: the device states lie in the compact layout with the finished windows parked.  Put
+        // them back by home slot as far as the device still answers, so that a step-API or wh_measure_kernels call that follows sees every slot in
+        // its place; the error of the loop is the one reported.
+        if (lay.switches > 0) {
+            const std::string msg = wh_last_error();
+            launch_seq_park(s->seq, s->seq_home, s->slot_home_dev, lay.width, s->B, s->st);
+            if (hipMemcpyAsync(s->seq_host, s->seq_home, sizeof(SeqState) * batch, hipMemcpyDeviceToHost, s->st) == hipSuccess &&
+                hipStreamSynchronize(s->st) == hipSuccess) (void)upload_home_layout();
+            set_error(r, "%s", msg.c_str());
+        }
+        return r;
+    }
+    if (lay.switches > 0) {
+        int r2 = upload_home_layout();
+        if (r2) return r2;
+    } else if (cp.compact) {
         // back to home-slot terms, on the host and on the device: the live slots' final states at their home slots, every other slot as
         // an uncompacted pass leaves it (initialised, inactive)
         const int32_t* home = s->slot_home_host;

@@ -81,8 +81,9 @@ struct wh_model {
 struct WhGraphKey {
     int batch, align, fused, n_align, self_rows, gate;
     int mapped, spw;      // compacted pass (slot table + mapped cross-attention instantiations) and its slots per absorbed-attention workgroup; 0, 0 otherwise
+    int owner;            // 1: a pass that narrowed in flight - the self-attention reads the session's row -> owner table (dec_self_attn_owner_kernel); 0 otherwise
     bool operator<(const WhGraphKey& o) const {
-        return std::tie(batch, align, fused, n_align, self_rows, gate, mapped, spw) < std::tie(o.batch, o.align, o.fused, o.n_align, o.self_rows, o.gate, o.mapped, o.spw);
+        return std::tie(batch, align, fused, n_align, self_rows, gate, mapped, spw, owner) < std::tie(o.batch, o.align, o.fused, o.n_align, o.self_rows, o.gate, o.mapped, o.spw, o.owner);
     }
 };
 
@@ -150,6 +151,17 @@ struct wh_session {
     bool pass_mapped = false; int pass_spw = 1;
     wh::Xabs xabs_pass{};                 // the session's xabs with the pass's slots per workgroup
     long long decode_passes = 0, compacted_passes = 0, slot_steps = 0;   // wh_session_decode_pass_stats
+    // in-pass compaction (wh_session_set_inpass_compaction): 0 = off, 1 = a wh_decode_text* pass narrows between step graphs as its slots finish
+    // (host.hip inpass_narrow, launch_plan.h inpass_compact_plan / inpass_compose, compact.hip).  Everything is allocated by the first pass that runs
+    // with the option on: seq_home [B] (device, the decode states by home slot), seq_snap [B] (pinned, the second snapshot buffer of the run-ahead
+    // loop), inpass_dev = live flags [B] | owner rows [B][kMaxTok] (device), inpass_stage = kInpassMaxSwitches regions of home [B] | live [B] |
+    // owner rows [B][kMaxTok] (pinned: one region per switch of a pass, so the host never writes a region the stream has not consumed).
+    // pass_owner holds only while decode_text_impl runs a pass that has narrowed.
+    int inpass_compaction = 0;
+    wh::SeqState *seq_home = nullptr, *seq_snap = nullptr;
+    int32_t *inpass_dev = nullptr, *inpass_stage = nullptr;
+    bool pass_owner = false;
+    long long inpass_switches = 0, inpass_slot_steps_saved = 0;          // wh_session_inpass_compaction_stats
     hipEvent_t ev[8]{};
     bool align_enabled = false;
     wh_timings last_timings{};

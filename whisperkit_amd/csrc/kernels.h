@@ -220,6 +220,8 @@ struct DecodeBuffers {
     const struct Xabs* xabs; // non-null: weight-absorbed cross-attention over the encoder output (xabs.hip) instead of the cross K / V stream
     const int* slot_home;    // null, or [batch] (device): a compacted pass (launch_plan.h compact_pass_plan) - slot b attends over the encoder output / cross
                              // K / V rows of slot slot_home[b] and writes that slot's alignment rows; everything else is indexed by b
+    int owner_slots;         // 0, or the slot count self_owner's entries are clamped to instead of `batch`: a pass that narrowed (compact.hip) reads history
+                             // rows from the caches of slots beyond its present width.  Host-side only: the kernels' arguments keep their layout
 };
 constexpr int kStatBlocks = 1792; // >= workgroups of the logits kernel (V / 64 rows: GEMV path, V / 32 rows: MFMA path), multiple of 256
 // Largest vocabulary the sampling kernels cover: sampler_kernel holds SAMP_T x SAMP_E = 1024 x 51 ids in registers, the fused greedy
@@ -332,6 +334,10 @@ void launch_xabs_vup(const XabsArgs& a, int n_bt, hipStream_t st);
 void launch_decoder_step(const DecodeBuffers& db, const SamplerCfg* cfg_dev, const int* suppress_dev, bool sample, hipStream_t st);
 // filter rules of the first sampling step of a decodeText call (later steps: computed by the sampler itself)
 void launch_rules_init(const SamplerCfg* cfg_dev, SeqState* seq, int batch, hipStream_t st);
+// in-pass compaction (compact.hip): the decode state of a narrowing pass moves through a home-indexed array [n_slots].  park: seq_home[home[i]] = seq[i]
+// for the active slots i < width (home null: i); gather: seq[i] = seq_home[home[i]] where live[i], an inactive zero state elsewhere.
+void launch_seq_park(const SeqState* seq, SeqState* seq_home, const int* home, int width, int n_slots, hipStream_t st);
+void launch_seq_gather(const SeqState* seq_home, SeqState* seq, const int* home, const int* live, int width, int n_slots, hipStream_t st);
 // standalone filter / sampler entry points (KAT surface of the C ABI)
 void launch_filter_only(const SamplerCfg* cfg_dev, const int* suppress_dev, SeqState* seq, float* logits, int n_vocab, hipStream_t st);
 void launch_sample_only(const SamplerCfg* cfg_dev, SeqState* seq, float* logits, int n_vocab, int counter, int* token_out, float* logprob_out, hipStream_t st);

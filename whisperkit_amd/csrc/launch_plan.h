@@ -249,5 +249,55 @@ inline int compact_slot_map(const int32_t* active, int batch, int width, int32_t
     return n;
 }
 
+// ============================================================================================== in-pass compaction
+// A pass narrows BETWEEN step graphs as its slots reach EOT (wh_session_set_inpass_compaction): when the slots still decoding fit a lower rung of the
+// ladder above and that saves a batch tile, the live slots move to compact slots 0 .. n - 1 (ascending home slot) and the following graphs launch at the
+// rung.  The rule is compact_pass_plan's, with two additions: the width never grows, and a pass with fewer than kInpassMinStepsLeft steps to go is left
+// alone (a switch costs a table upload, two small launches and - the first time a session meets the width at these positions - graph captures).
+// kInpassMinStepsLeft: two step graphs.  Kept, unconfirmed: the measurement (profiles/inpass_compaction_time.jsonl) found no cell slower with the
+// option on, but the large-v3 fixture did not spread its lengths, so no narrowing pass was timed at that size; the next measurement with spread lengths decides.
+constexpr int kInpassMinStepsLeft = 16;
+constexpr int kInpassMaxSwitches = kCompactRungs;      // every switch drops at least one rung
+inline CompactPassPlan inpass_compact_plan(int n_live, int width_now, int max_batch, int slots_per_workgroup, int steps_left) {
+    const int spw0 = slots_per_workgroup > 1 ? slots_per_workgroup : 1;
+    const CompactPassPlan none{false, width_now, spw0};
+    if (steps_left < kInpassMinStepsLeft) return none;
+    const CompactPassPlan p = compact_pass_plan(n_live, width_now, max_batch, spw0);
+    return (p.compact && p.width < width_now) ? p : none;
+}
+// The tables of a switch before step t.  The pass so far: width_old compact slots, slot i decoding home slot home_old[i] (null: i itself, a pass that
+// was never compacted) while live_old[i] != 0, and row r of its self-attention history held by the cache of slot owner_old[i * rows + r] (null: i itself,
+// no switch so far - a slot writes its K / V rows into the cache of the compact slot it occupies, whatever its home).  keep[i] != 0: slot i goes on.
+// All slots of a pass share token_index, so no cache holds a row >= t yet: the kept slots move to 0 .. n - 1 in ascending order (i_new <= i_old), read
+// the rows below t where they were written and write the rows from t on into the cache of their NEW slot:
+//   owner_new[i][r] = owner_old[old index of i][r]  (r < t),   i  (r >= t).
+// No cache row is copied, and a later switch composes the same way.  Padding entries i >= n: live_new[i] = 0, home_new[i] = i, owner_new[i][*] = i
+// (in range: the kernels form addresses from them before they look at the slot state).  The old and the new tables must not overlap.
+// Returns n, or -1 when the kept slots do not fit into width_new or an old entry is out of [0, n_slots).
+inline int inpass_compose(const int32_t* home_old, const int32_t* live_old, const int32_t* owner_old, int width_old, const int32_t* keep, int width_new,
+                          int t, int rows, int n_slots, int32_t* home_new, int32_t* live_new, int32_t* owner_new) {
+    if (width_new < 1 || width_new > n_slots || width_old > n_slots || rows < 1) return -1;
+    const int tt = t < 0 ? 0 : (t > rows ? rows : t);
+    int n = 0;
+    for (int i = 0; i < width_old; ++i) {
+        if (!keep[i] || (live_old && !live_old[i])) continue;
+        if (n >= width_new) return -1;
+        const int h = home_old ? home_old[i] : i;
+        if (h < 0 || h >= n_slots) return -1;
+        home_new[n] = h; live_new[n] = 1;
+        for (int r = 0; r < rows; ++r) {
+            const int own = r >= tt ? n : (owner_old ? owner_old[(long long)i * rows + r] : i);
+            if (own < 0 || own >= n_slots) return -1;
+            owner_new[(long long)n * rows + r] = own;
+        }
+        ++n;
+    }
+    for (int i = n; i < width_new; ++i) {
+        home_new[i] = i; live_new[i] = 0;
+        for (int r = 0; r < rows; ++r) owner_new[(long long)i * rows + r] = i;
+    }
+    return n;
+}
+
 }  // namespace plan
 }  // namespace wh
