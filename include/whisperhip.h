@@ -709,6 +709,38 @@ int wh_load_audio(const char* path, int channel_mode, const int32_t* channel_ind
                   double end_time, int max_read_frame_size, float** pcm_out, int* n_out);
 void wh_audio_free(float* pcm);
 
+/* ---- audio ingest on the device (opt-in; csrc/audio.hip) ----------------------------------------------
+ * A loader does the work of the three functions above on HIP device `device`: the host still reads the file and parses its header, the
+ * raw sample bytes go up, 16 kHz mono float comes down.  Every result equals the host function's bit for bit.  A loader owns two streams
+ * (never the default stream: it can work beside sessions), its device buffers, pinned staging and a cache of filter tables; device memory
+ * is bounded by a fixed staging budget (32 MB per buffer, eight buffers) unless one read-chunk alone is larger.  Every entry waits for its
+ * own work before it returns.  One loader serves one host thread at a time.  The free functions above stay the default. */
+typedef struct wh_audio_loader wh_audio_loader;
+/* WH_ERR_HIP with a message when no device is visible */
+int wh_audio_loader_create(int device, wh_audio_loader** out);
+void wh_audio_loader_destroy(wh_audio_loader* l);
+/* resampleAudio (:458-519): the contract of wh_resample (length query with out == NULL, the same errors), executed on the device */
+int wh_audio_loader_resample(wh_audio_loader* l, const float* in, int n_in, double in_rate, double out_rate, float* out, int capacity);
+/* AudioProcessor.convertToMono (:525-625): the contract of wh_convert_to_mono */
+int wh_audio_loader_convert_to_mono(wh_audio_loader* l, const float* const* channels, int n_channels, int n_frames, int mode,
+                                    const int32_t* indices, int n_indices, float* out);
+/* AudioProcessor.loadAudio(fromPath:channelMode:startTime:endTime:maxReadFrameSize:) (:229-300): the contract of wh_load_audio - the same
+ * arguments, the same errors, the result freed with wh_audio_free.  A 16 kHz mono file needs no launch. */
+int wh_audio_loader_load(wh_audio_loader* l, const char* path, int channel_mode, const int32_t* channel_indices, int n_channel_indices,
+                         double start_time, double end_time, int max_read_frame_size, float** pcm_out, int* n_out);
+/* AudioProcessor.loadAudio(at:channelMode:) (:352-379): one result and one status per path, order kept.  A path that cannot be loaded
+ * fails alone: statuses[i] is the wh_status wh_load_audio gives it, wh_audio_loader_item_error(l, i) its message, pcm_out[i] NULL.  The
+ * return value is WH_OK unless the call itself failed (then nothing is returned).  Each pcm_out[i] is freed with wh_audio_free.  The
+ * next file is read and staged while the previous one's kernels run. */
+int wh_audio_loader_load_batch(wh_audio_loader* l, const char* const* paths, int n_paths, int channel_mode, const int32_t* channel_indices,
+                               int n_channel_indices, float** pcm_out, int32_t* n_out, int32_t* statuses);
+const char* wh_audio_loader_item_error(const wh_audio_loader* l, int i);     /* of the last wh_audio_loader_load_batch; "" when path i loaded */
+/* since creation: kernel launches, bytes uploaded, bytes downloaded (any pointer may be NULL) */
+int wh_audio_loader_stats(const wh_audio_loader* l, int64_t* kernel_launches, int64_t* h2d_bytes, int64_t* d2h_bytes);
+/* since creation, in seconds: [0] file read + header parse, [1] copy into pinned staging, [2] upload, [3] kernels, [4] download (2 - 4 by
+ * HIP events), [5] copy from pinned memory into the result (tools/audio_ingest_time.py) */
+int wh_audio_loader_stage_seconds(const wh_audio_loader* l, double* seconds6);
+
 /* ---- host utilities restated from the reference -------------------------------------------------- */
 float wh_compression_ratio(const int32_t* tokens, int n);          /* TextUtilities.compressionRatio, Utilities/TextUtilities.swift:14-30 */
 float wh_compression_ratio_text(const char* utf8, int nbytes);      /* TextUtilities.compressionRatio(of: String), :33-52 */

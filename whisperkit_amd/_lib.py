@@ -255,6 +255,16 @@ SYMBOLS = {
     "wh_resample": (I, [PF, I, C.c_double, C.c_double, PF, I]),
     "wh_load_audio": (I, [C.c_char_p, I, PI32, I, C.c_double, C.c_double, I, C.POINTER(PF), C.POINTER(I)]),
     "wh_audio_free": (None, [PF]),
+    # audio ingest on the device (csrc/audio.hip)
+    "wh_audio_loader_create": (I, [I, PVP]),
+    "wh_audio_loader_destroy": (None, [VP]),
+    "wh_audio_loader_resample": (I, [VP, PF, I, C.c_double, C.c_double, PF, I]),
+    "wh_audio_loader_convert_to_mono": (I, [VP, PVP, I, I, I, PI32, I, PF]),
+    "wh_audio_loader_load": (I, [VP, C.c_char_p, I, PI32, I, C.c_double, C.c_double, I, C.POINTER(PF), C.POINTER(I)]),
+    "wh_audio_loader_load_batch": (I, [VP, C.POINTER(C.c_char_p), I, I, PI32, I, C.POINTER(PF), PI32, PI32]),
+    "wh_audio_loader_item_error": (C.c_char_p, [VP, I]),
+    "wh_audio_loader_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "wh_audio_loader_stage_seconds": (I, [VP, C.POINTER(C.c_double)]),
     "wh_compression_ratio": (F, [PI32, I]),
     "wh_compression_ratio_text": (F, [C.c_char_p, I]),
     "wh_trimming_special_token_characters": (I, [C.c_char_p, C.c_char_p, I]),

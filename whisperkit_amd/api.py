@@ -1252,6 +1252,88 @@ def loadAudio(fromPath: str, channelMode: str = "sumChannels", channels: Optiona
     return out
 
 
+class AudioLoader:
+    """Audio ingest on the device (opt-in; include/whisperhip.h wh_audio_loader_*, csrc/audio.hip): sample decode, mono mix and resampling of
+    WAV input run as HIP kernels, the host only reads the file and parses its header.  Every method returns what the free function of the
+    same name returns, bit for bit; the free functions stay the default.  A loader owns its streams, device buffers and pinned staging, and
+    can work beside sessions.  Use it from one thread at a time; `close()` (or the context manager) gives the memory back."""
+
+    def __init__(self, device: int = 0):
+        self.lib = L.load()
+        h = C.c_void_p()
+        _check(self.lib.wh_audio_loader_create(device, C.byref(h)))
+        self.h = h
+        self._finalizer = weakref.finalize(self, self.lib.wh_audio_loader_destroy, h)
+
+    def close(self):
+        self._finalizer()
+        self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def loadAudio(self, fromPath: str, channelMode: str = "sumChannels", channels: Optional[Sequence[int]] = None, startTime: float = 0.0,
+                  endTime: Optional[float] = None, maxReadFrameSize: int = 0) -> np.ndarray:
+        """AudioProcessor.loadAudio(fromPath:channelMode:startTime:endTime:maxReadFrameSize:) (Core/Audio/AudioProcessor.swift:229-300)."""
+        idx = None if channels is None else np.ascontiguousarray(list(channels), dtype=np.int32)
+        p, n = L.PF(), C.c_int()
+        _check(self.lib.wh_audio_loader_load(self.h, fromPath.encode(), 0 if channelMode == "specificChannel" else 1,
+                                             None if idx is None else idx.ctypes.data_as(L.PI32), 0 if idx is None else len(idx), startTime,
+                                             float("nan") if endTime is None else endTime, maxReadFrameSize, C.byref(p), C.byref(n)))
+        out = np.ctypeslib.as_array(p, shape=(max(n.value, 1),))[:n.value].copy()
+        self.lib.wh_audio_free(p)
+        return out
+
+    def loadAudios(self, paths: Sequence[str], channelMode: str = "sumChannels", channels: Optional[Sequence[int]] = None) -> list:
+        """AudioProcessor.loadAudio(at:channelMode:) (Core/Audio/AudioProcessor.swift:352-379): one entry per path, in order - the 16 kHz mono
+        float32 array, or the WhisperError loadAudio would have raised for that path."""
+        n = len(paths)
+        idx = None if channels is None else np.ascontiguousarray(list(channels), dtype=np.int32)
+        cpaths = (C.c_char_p * max(n, 1))(*[p.encode() for p in paths])
+        pcm, counts, statuses = (L.PF * max(n, 1))(), (C.c_int32 * max(n, 1))(), (C.c_int32 * max(n, 1))()
+        _check(self.lib.wh_audio_loader_load_batch(self.h, cpaths, n, 0 if channelMode == "specificChannel" else 1,
+                                                   None if idx is None else idx.ctypes.data_as(L.PI32), 0 if idx is None else len(idx), pcm, counts, statuses))
+        out = []
+        for i in range(n):
+            if statuses[i] != 0:
+                out.append(WhisperError(statuses[i], self.lib.wh_audio_loader_item_error(self.h, i).decode()))
+                continue
+            out.append(np.ctypeslib.as_array(pcm[i], shape=(max(counts[i], 1),))[:counts[i]].copy())
+            self.lib.wh_audio_free(pcm[i])
+        return out
+
+    def resampleAudio(self, audio: np.ndarray, fromSampleRate: float, toSampleRate: float = 16000.0) -> np.ndarray:
+        a = np.ascontiguousarray(audio, dtype=np.float32)
+        n = self.lib.wh_audio_loader_resample(self.h, a.ctypes.data_as(L.PF), len(a), fromSampleRate, toSampleRate, None, 0)
+        out = np.empty(max(n, 0), np.float32)
+        if n < 0 or (n > 0 and self.lib.wh_audio_loader_resample(self.h, a.ctypes.data_as(L.PF), len(a), fromSampleRate, toSampleRate, out.ctypes.data_as(L.PF), n) < 0):
+            raise WhisperError(4, self.lib.wh_last_error().decode())
+        return out
+
+    def convertToMono(self, channels: np.ndarray, mode: str = "sumChannels", indices: Optional[Sequence[int]] = None) -> np.ndarray:
+        """AudioProcessor.convertToMono (Core/Audio/AudioProcessor.swift:525-625); channels [n_channels][n_frames] float32."""
+        x = np.ascontiguousarray(channels, dtype=np.float32)
+        ptrs = (C.c_void_p * x.shape[0])(*[x[c].ctypes.data for c in range(x.shape[0])])
+        idx = None if indices is None else np.ascontiguousarray(list(indices), dtype=np.int32)
+        out = np.empty(x.shape[1], np.float32)
+        _check(self.lib.wh_audio_loader_convert_to_mono(self.h, ptrs, x.shape[0], x.shape[1], 0 if mode == "specificChannel" else 1,
+                                                        None if idx is None else idx.ctypes.data_as(L.PI32), 0 if idx is None else len(idx), out.ctypes.data_as(L.PF)))
+        return out
+
+    def stats(self) -> dict:
+        """since creation: kernel launches, bytes uploaded and downloaded, and the seconds spent per stage (upload, kernels and download by
+        HIP events)"""
+        k, up, down = C.c_int64(), C.c_int64(), C.c_int64()
+        _check(self.lib.wh_audio_loader_stats(self.h, C.byref(k), C.byref(up), C.byref(down)))
+        sec = (C.c_double * 6)()
+        _check(self.lib.wh_audio_loader_stage_seconds(self.h, sec))
+        names = ("readParse", "stagingCopy", "upload", "kernels", "download", "finalCopy")
+        return {"kernelLaunches": k.value, "h2dBytes": up.value, "d2hBytes": down.value, "stageSeconds": dict(zip(names, list(sec)))}
+
+
 class WindowAssembler:
     """The windowing half of TranscribeTask.run (Core/TranscribeTask.swift:175-312) on already decoded windows: feeds
     DecodingResults (+ alignment weights) to wh_transcription_add_window and finalises the TranscriptionResult.  Host only."""

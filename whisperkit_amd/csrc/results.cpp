@@ -11,6 +11,7 @@
 
 #include <zlib.h>
 
+#include "audio_plan.h"
 #include "json.h"
 #include "text.h"
 
@@ -655,20 +656,12 @@ extern "C" int wh_resample(const float* in, int n_in, double in_rate, double out
     if (!out) return (int)n_out;
     if (n_out > capacity) { set_error(WH_ERR_AUDIO_PROCESSING_FAILED, "wh_resample: %lld frames do not fit", n_out); return -1; }
     if (in_rate == out_rate) { memcpy(out, in, sizeof(float) * (size_t)n_out); return (int)n_out; }
-    const double ratio = out_rate / in_rate, fc = std::min(1.0, ratio) * 0.97;   // cutoff relative to the input Nyquist
-    const int zeros = 32, phases = 256;
-    const double half = zeros / fc, beta = 9.0;
-    auto bessel0 = [](double x) { double s = 1, t = 1; for (int k = 1; k < 60; ++k) { t *= (x / (2 * k)) * (x / (2 * k)); s += t; if (t < 1e-14 * s) break; } return s; };
-    const double ib = 1.0 / bessel0(beta);
-    // h(x) = fc sinc(fc x) kaiser(x / half), tabulated at 1/phases of an input sample and interpolated linearly
-    const int tn = (int)ceil(half * phases) + 2;
-    std::vector<double> h((size_t)tn + 1, 0.0);
-    for (int k = 0; k < tn; ++k) {
-        const double x = (double)k / phases, u = x / half;
-        if (u >= 1.0) break;
-        const double a = M_PI * fc * x;
-        h[k] = (fabs(a) < 1e-9 ? 1.0 : sin(a) / a) * fc * bessel0(beta * sqrt(1 - u * u)) * ib;
-    }
+    const wh::audio::ResampleGeometry g = wh::audio::resample_geometry(n_in, in_rate, out_rate);
+    const double ratio = g.ratio, half = g.half;
+    const int phases = wh::audio::kPhases;
+    // h(x) = fc sinc(fc x) kaiser(x / half), tabulated at 1/phases of an input sample and interpolated linearly (audio_plan.h: the
+    // device loader uploads the same table)
+    const std::vector<double> h = wh::audio::filter_table(g.fc, g.half, g.tn);
     for (long long o = 0; o < n_out; ++o) {
         const double center = (double)o / ratio;
         const long long lo = std::max(0LL, (long long)ceil(center - half)), hi = std::min((long long)n_in - 1, (long long)floor(center + half));
@@ -721,26 +714,13 @@ bool parse_wav(const std::string& f, Wav& w, std::string& err) {
     return true;
 }
 
-float sample_at(const Wav& w, const unsigned char* p) {   // AVAudioFile .pcmFormatFloat32 conversion: integers scaled by 2^-(bits-1)
-    if (w.format == 3) { if (w.bits == 32) { float v; memcpy(&v, p, 4); return v; } double d; memcpy(&d, p, 8); return (float)d; }
-    switch (w.bits) {
-        case 8: return ((int)p[0] - 128) / 128.0f;
-        case 16: return (float)(int16_t)rd16(p) / 32768.0f;
-        case 24: { int32_t v = (int32_t)((uint32_t)p[0] << 8 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 24) >> 8; return (float)v / 8388608.0f; }
-        default: return (float)((double)(int32_t)rd32(p) / 2147483648.0);
-    }
-}
+float sample_at(const Wav& w, const unsigned char* p) { return wh::audio::sample_at(w.format, w.bits, p); }   // AVAudioFile .pcmFormatFloat32 conversion (audio_plan.h)
 }  // namespace
 
-// AudioProcessor.loadAudio(fromPath:channelMode:startTime:endTime:maxReadFrameSize:) (AudioProcessor.swift:229-300) for RIFF/WAVE
-// input: 16 kHz mono is returned as read; anything else is read in chunks of max_read_frame_size frames (0 = 1 323 000,
-// Constants.defaultAudioReadFrameSize), each chunk mixed to mono (convertToMono - the peak renormalisation is per chunk, as in the
-// reference) and resampled to 16 kHz.  end_time = NAN means nil.  The caller frees *pcm_out with wh_audio_free.
-extern "C" int wh_load_audio(const char* path, int channel_mode, const int32_t* channel_indices, int n_channel_indices, double start_time,
-                             double end_time, int max_read_frame_size, float** pcm_out, int* n_out) {
-    if (!path || !pcm_out || !n_out) return set_error(WH_ERR_LOAD_AUDIO_FAILED, "wh_load_audio: null argument");
-    *pcm_out = nullptr; *n_out = 0;
-    std::string file, err;
+// The part of wh_load_audio before the first sample is read, with its errors: the file's bytes, the parsed header and the frames
+// start_time .. end_time select.  The host loader below and the device loader (audio.hip) both start here.
+int whi::open_wav(const char* path, double start_time, double end_time, std::string& file, wh::audio::WavSpan& span) {
+    std::string err;
     if (!wh::read_file(path, file)) return set_error(WH_ERR_LOAD_AUDIO_FAILED, "Resource path does not exist %s", path);
     Wav w;
     if (!parse_wav(file, w, err)) return set_error(WH_ERR_LOAD_AUDIO_FAILED, "%s: %s", path, err.c_str());
@@ -750,7 +730,26 @@ extern "C" int wh_load_audio(const char* path, int channel_mode, const int32_t* 
     const long long end = std::isnan(end_time) ? length : std::min((long long)(end_time * w.rate), length);
     if (start > end) return set_error(WH_ERR_LOAD_AUDIO_FAILED, "start time %.3f s is outside the file", start_time);
     if (end - start > 0x7fffffffLL) return set_error(WH_ERR_LOAD_AUDIO_FAILED, "audio too long for one buffer");
-    const long long frames = end - start;
+    span.format = w.format; span.channels = w.channels; span.bits = w.bits; span.block = w.block; span.rate = w.rate;
+    span.data = w.data + (size_t)start * w.block;
+    span.frames = end - start;
+    return WH_OK;
+}
+
+// AudioProcessor.loadAudio(fromPath:channelMode:startTime:endTime:maxReadFrameSize:) (AudioProcessor.swift:229-300) for RIFF/WAVE
+// input: 16 kHz mono is returned as read; anything else is read in chunks of max_read_frame_size frames (0 = 1 323 000,
+// Constants.defaultAudioReadFrameSize), each chunk mixed to mono (convertToMono - the peak renormalisation is per chunk, as in the
+// reference) and resampled to 16 kHz.  end_time = NAN means nil.  The caller frees *pcm_out with wh_audio_free.
+extern "C" int wh_load_audio(const char* path, int channel_mode, const int32_t* channel_indices, int n_channel_indices, double start_time,
+                             double end_time, int max_read_frame_size, float** pcm_out, int* n_out) {
+    if (!path || !pcm_out || !n_out) return set_error(WH_ERR_LOAD_AUDIO_FAILED, "wh_load_audio: null argument");
+    *pcm_out = nullptr; *n_out = 0;
+    std::string file;
+    wh::audio::WavSpan span;
+    if (int r = whi::open_wav(path, start_time, end_time, file, span)) return r;
+    Wav w;
+    w.format = span.format; w.channels = span.channels; w.bits = span.bits; w.block = span.block; w.rate = span.rate; w.data = span.data;
+    const long long start = 0, frames = span.frames;
     const int bps = w.bits / 8;
     std::vector<float> mono;
     if (w.rate == 16000.0 && w.channels == 1) {
