@@ -71,6 +71,10 @@ public final class HIPSession {
     /// `.on` = it narrows between step graphs (to 32 / 64 / 128 slots, when a 32-slot batch tile is saved) as its windows reach EOT.  Same results, bit for bit.
     public enum InPassCompaction: Int32 { case off = 0, on = 1 }
     public var inPassCompaction: InPassCompaction = .off { didSet { _ = wh_session_set_inpass_compaction(handle, inPassCompaction.rawValue) } }
+    /// Option mixing (wh_session_set_option_mixing): `.off` (default) = transcribeWithOptions runs audios whose options differ in separate groups; `.on` = audios
+    /// that agree in the pass-level fields share a device batch and each slot decodes under the options of its class (up to 16 classes per batch).
+    public enum OptionMixing: Int32 { case off = 0, on = 1 }
+    public var optionMixing: OptionMixing = .off { didSet { _ = wh_session_set_option_mixing(handle, optionMixing.rawValue) } }
     public enum BeamRanking: Int32 { case host = 0, device = 1 }
     public var beamRanking: BeamRanking = .host { didSet { _ = wh_session_set_beam_ranking(handle, beamRanking.rawValue) } }
     public init(model: HIPModel, maxBatch: Int = 1, crossAttention: CrossAttentionMode = .automatic, keySplits: Int = 0, slotsPerWorkgroup: Int = 0,

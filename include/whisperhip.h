@@ -448,6 +448,34 @@ int wh_session_inpass_compaction(const wh_session* s);
 /* Counters of the session since its creation: narrowings, and the slot-steps they saved (width the pass began with minus the width launched, summed
  * over the decoder steps launched).  wh_session_decode_pass_stats keeps its meaning: slot_steps sums the width actually launched.  Any pointer may be NULL. */
 int wh_session_inpass_compaction_stats(const wh_session* s, int64_t* switches, int64_t* slot_steps_saved);
+/* Option mixing.  0 = off (default): wh_transcribe_batch_with_options runs audios whose options differ in any field but the clip timestamps in
+ * separate groups, one after the other.  1 = on: audios share a device batch when the fields that belong to the PASS are equal - temperature,
+ * temperature_increment_on_fallback, temperature_fallback_count, seed, use_prefill_prompt, detect_language, word_timestamps, float16_logits,
+ * beam_size, beam_patience (audios with beam_size > 1 are never mixed and group as with 0).  The fields the device reads per slot - task,
+ * language_token, prompt_tokens, prefix_tokens, without_timestamps, suppress_blank, suppress_tokens, first_token_log_prob_threshold, sample_length,
+ * top_k - form a CLASS; a batch holds up to WH_MAX_OPTION_CLASSES classes (the next distinct class opens another group) and every slot decodes
+ * under the sampler configuration, suppress list, suppress mask and prompt of its class.  Everything else - skip_special_tokens, the fallback
+ * thresholds, max_window_seek, window_clip_time, max_initial_timestamp, clip_timestamps - is read on the host per audio and differs freely.
+ * A slot decodes to the bits it has in a pass of its own class alone (same slot, same seed); at T > 0 a mixed wh_transcribe* call places windows
+ * in other slots than a grouped one, and the random stream follows the slot.  Composes with both compaction options and device word alignment.
+ * The beam-search pass, wh_decode_text_custom and wh_detect_language are untouched.
+ * Returns WH_ERR_INVALID_ARGUMENT for a NULL session or a mode other than 0 / 1; the getter returns the mode, -1 for NULL. */
+#define WH_MAX_OPTION_CLASSES 16
+int wh_session_set_option_mixing(wh_session* s, int mode);
+int wh_session_option_mixing(const wh_session* s);
+/* Counters of the session since its creation: groups wh_transcribe_batch* ran MIXED (mode on; a beam-search group runs as with the mode off and is
+ * not counted), decode passes that ran with per-slot classes (the ladder rungs of those groups and wh_decode_text_mixed calls), and the largest class
+ * count of such a pass.  Any pointer may be NULL. */
+int wh_session_option_mixing_stats(const wh_session* s, int64_t* groups_run, int64_t* mixed_passes, int64_t* max_classes_in_a_pass);
+/* wh_decode_text with an option class per slot, whatever the session's mixing mode: slot b decodes under opts[class_of_slot[b]] with the prompt
+ * prompts[class_of_slot[b]] (n_prompts[c] tokens); language_tokens (per slot, or NULL) as in wh_decode_text_languages.  The pass-level fields
+ * (above) are read from opts[0]; the host loop runs to the largest sample_length and every slot stops at its own.  Arguments are validated as
+ * in wh_decode_text; n_classes outside [1, WH_MAX_OPTION_CLASSES], a class index outside [0, n_classes) or classes whose pass-level fields
+ * differ return WH_ERR_INVALID_ARGUMENT (checked before the session is looked at). */
+int wh_decode_text_mixed(wh_session* s, int batch, const wh_decoding_options* opts /* [n_classes] */, int n_classes,
+                         const int32_t* class_of_slot /* [batch] */, const wh_special_tokens* st, const int32_t* const* prompts /* [n_classes] */,
+                         const int32_t* n_prompts /* [n_classes] */, const int32_t* language_tokens /* [batch] or NULL */, const float* temperatures,
+                         const int32_t* active, uint64_t seed, wh_decoding_result* out /* [batch] */);
 /* ---- user-pluggable LogitsFiltering / TokenSampling (Core/Text/LogitsFilter.swift:8-10, Core/Text/TokenSampler.swift:8-11) ----
  * The reference runs `logitsFilters` (custom filters first, Core/TextDecoder.swift:857-899) and the `TokenSampling` object on the
  * host once per token (:641-652).  The fused device loop of wh_decode_text knows the four built-in filters and the greedy /
@@ -586,7 +614,9 @@ int wh_transcribe_batch(wh_session* s, const float* const* pcm_host, const int32
  * opts[i] are the options of audio i (a NULL entry, or opts == NULL, = DecodingOptions()); statuses[i] (may be NULL) receives audio i's
  * wh_status, out[i] its transcription or NULL.  Audios whose options differ only in their clip timestamps share lock-stepped device
  * batches; audios with different decoding options run in groups, one group after the other (the reference runs one TranscribeTask per
- * audio: grouping changes the batching, never a result).  Returns WH_OK whenever the per-audio results are valid - also when every audio
+ * audio: grouping changes the batching, never a result).  With wh_session_set_option_mixing 1 a group is everything that agrees in the
+ * pass-level fields: audios that differ in language, task, prompt / prefix / suppress lists, timestamps mode, sample length, top-k or any
+ * host-side threshold share the batch, up to WH_MAX_OPTION_CLASSES distinct device-visible combinations per group.  Returns WH_OK whenever the per-audio results are valid - also when every audio
  * failed - and non-zero for a null argument, a device error or cancellation. */
 int wh_transcribe_batch_with_options(wh_session* s, const float* const* pcm_host, const int32_t* n_samples, int n_audio,
                                      const wh_decoding_options* const* opts /* [n_audio] or NULL */, const wh_special_tokens* st,

@@ -193,6 +193,10 @@ SYMBOLS = {
     "wh_session_set_inpass_compaction": (I, [VP, I]),
     "wh_session_inpass_compaction": (I, [VP]),
     "wh_session_inpass_compaction_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "wh_session_set_option_mixing": (I, [VP, I]),
+    "wh_session_option_mixing": (I, [VP]),
+    "wh_session_option_mixing_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "wh_decode_text_mixed": (I, [VP, I, VP, I, VP, VP, VP, VP, VP, VP, VP, C.c_uint64, VP]),
     "wh_session_set_beam_ranking": (I, [VP, I]),
     "wh_session_beam_ranking": (I, [VP]),
     "wh_session_beam_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -861,6 +861,51 @@ class Session:
         _check(self.lib.wh_session_inpass_compaction_stats(self.handle, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
 
+    OPTION_MIXINGS = {"off": 0, "on": 1}
+    MAX_OPTION_CLASSES = 16
+
+    def setOptionMixing(self, mode: str):
+        """Whether transcribeWithOptions lets audios with different options share a device batch: "off" (default) - audios whose options differ in
+        anything but the clip timestamps run in separate groups; "on" - a group is everything that agrees in the pass-level fields (temperature
+        ladder, seed, usePrefillPrompt, detectLanguage, wordTimestamps, float16Logits, beam search) and each distinct combination of task, language,
+        prompt / prefix / suppress lists, withoutTimestamps, suppressBlank, firstTokenLogProbThreshold, sampleLength and topK is one of up to 16
+        classes the device reads per slot; everything else is read per audio on the host.  Composes with both compaction options."""
+        if mode not in self.OPTION_MIXINGS:
+            raise ValueError(f"optionMixing {mode!r}: expected 'on' or 'off'")
+        _check(self.lib.wh_session_set_option_mixing(self.handle, self.OPTION_MIXINGS[mode]))
+
+    def optionMixing(self) -> str:
+        return {0: "off", 1: "on"}[int(self.lib.wh_session_option_mixing(self.handle))]
+
+    def optionMixingStats(self) -> Tuple[int, int, int]:
+        """(groups transcribe* ran mixed, decode passes with per-slot classes, largest class count of such a pass) since the session was created"""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        _check(self.lib.wh_session_option_mixing_stats(self.handle, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
+
+    def decodeTextMixed(self, prompts: Sequence[Sequence[int]], optionsList: Sequence[DecodingOptions], classOfSlot: Sequence[int],
+                        temperatures: Optional[Sequence[float]] = None, active: Optional[Sequence[int]] = None, seed: int = 0, specialTokens=None,
+                        languageTokens: Optional[Sequence[int]] = None) -> List[DecodingResult]:
+        """decodeText with an option class per slot (wh_decode_text_mixed): slot b decodes under optionsList[classOfSlot[b]] with the prompt
+        prompts[classOfSlot[b]].  Works whatever setOptionMixing says; the pass-level fields must agree over the classes."""
+        st = specialTokens if specialTokens is not None else self.model.specialTokens
+        n, batch = len(optionsList), len(classOfSlot)
+        if len(prompts) != n:
+            raise ValueError("decodeTextMixed: one prompt per class")
+        cos = [o.to_c() for o in optionsList]
+        opts = (L.WhDecodingOptions * max(n, 1))(*cos)
+        ps = [np.ascontiguousarray(list(p), dtype=np.int32) for p in prompts]
+        pp = (C.c_void_p * max(n, 1))(*[p.ctypes.data for p in ps])
+        npr = np.ascontiguousarray([len(p) for p in ps], dtype=np.int32)
+        cls = np.ascontiguousarray(classOfSlot, dtype=np.int32)
+        temps = np.ascontiguousarray(temperatures if temperatures is not None else [optionsList[0].temperature] * batch, dtype=np.float32)
+        act = None if active is None else np.ascontiguousarray(active, dtype=np.int32)
+        lt = None if languageTokens is None else np.ascontiguousarray(languageTokens, dtype=np.int32)
+        res = (L.WhDecodingResult * max(batch, 1))()
+        self._guarded(self.lib.wh_decode_text_mixed, self.handle, batch, opts, n, cls.ctypes.data, C.byref(st), pp, npr.ctypes.data,
+                      None if lt is None else lt.ctypes.data, temps.ctypes.data, None if act is None else act.ctypes.data, seed, res)
+        return [DecodingResult.from_c(r) for r in res[:batch]]
+
     BEAM_RANKINGS = {"host": 0, "device": 1}
 
     def setBeamRanking(self, mode: str):

@@ -507,7 +507,7 @@ static int session_build(wh_session* s, wh_model* m, int max_batch, int cross_at
     DALLOC(s->part, B * H * kMaxSplit * kPartStride); DALLOC(s->ticket, B * H);
     DALLOC(s->logits, B * V);
     DALLOC(s->align_mean, B * kMaxTok * kCtx);
-    DALLOC(s->seq, B); DALLOC(s->cfg_dev, 1); DALLOC(s->suppress_dev, kMaxSuppress); DALLOC(s->sup_mask_dev, V); DALLOC(s->stats, B * kStatBlocks * 8);
+    DALLOC(s->seq, B); DALLOC(s->cfg_dev, kMaxOptionClasses); DALLOC(s->suppress_dev, kMaxOptionClasses * kMaxSuppress); DALLOC(s->sup_mask_dev, kMaxOptionClasses * (size_t)plan::option_mask_stride((int)V)); DALLOC(s->stats, B * kStatBlocks * 8);
     DALLOC(s->tok_out_dev, B); DALLOC(s->lp_out_dev, B); DALLOC(s->scratch_logits, V);
     {
         Dec32& q = s->d32;
@@ -766,7 +766,7 @@ DecodeBuffers decode_buffers(wh_session* s, int batch, int max_position) {
     db.emb = m->emb; db.pos = m->dec_pos; db.layers_host = m->dec.data(); db.lnf_g = m->lnf_g; db.lnf_b = m->lnf_b;
     db.self_k = s->self_k; db.self_v = s->self_v; db.cross_k_hi = s->cross_k_hi; db.cross_v_hi = s->cross_v_hi; db.cross_k_lo = s->cross_k_lo; db.cross_v_lo = s->cross_v_lo;
     db.part = s->part; db.ticket = s->ticket; db.logits = s->logits; db.seq = s->seq;
-    db.stats = s->stats; db.sup_mask = s->sup_mask_dev; db.fused_greedy = s->fused_greedy ? 1 : 0;
+    db.mixed = s->pass_mixed ? 1 : 0; db.stats = s->stats; db.sup_mask = s->sup_mask_dev; db.fused_greedy = s->fused_greedy ? 1 : 0;
     db.align = s->align_enabled ? s->align : nullptr; db.align_slot = m->align_slot_dev; db.n_align = s->n_align_alloc;
     db.d32 = &s->d32; db.x = s->d32.x; db.q = s->d32.q;
     if (s->use_xabs) { s->xabs.enc = s->enc16; db.xabs = &s->xabs; }
@@ -984,6 +984,20 @@ extern "C" int wh_session_set_inpass_compaction(wh_session* s, int mode) {
     return WH_OK;
 }
 extern "C" int wh_session_inpass_compaction(const wh_session* s) { return s ? s->inpass_compaction : -1; }
+extern "C" int wh_session_set_option_mixing(wh_session* s, int mode) {
+    if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_option_mixing: null session");
+    if (mode != 0 && mode != 1) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_option_mixing: mode %d (0 = off, 1 = on)", mode);
+    s->option_mixing = mode;
+    return WH_OK;
+}
+extern "C" int wh_session_option_mixing(const wh_session* s) { return s ? s->option_mixing : -1; }
+extern "C" int wh_session_option_mixing_stats(const wh_session* s, int64_t* groups_run, int64_t* mixed_passes, int64_t* max_classes_in_a_pass) {
+    if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_option_mixing_stats: null session");
+    if (groups_run) *groups_run = s->mix_groups_run;
+    if (mixed_passes) *mixed_passes = s->mix_mixed_passes;
+    if (max_classes_in_a_pass) *max_classes_in_a_pass = s->mix_max_classes;
+    return WH_OK;
+}
 extern "C" int wh_session_inpass_compaction_stats(const wh_session* s, int64_t* switches, int64_t* slot_steps_saved) {
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_inpass_compaction_stats: null session");
     if (switches) *switches = s->inpass_switches;
@@ -1076,9 +1090,10 @@ extern "C" int wh_session_set_cancel_flag(wh_session* s, const volatile int32_t*
 }
 
 // ---- filter / sampler KAT entry points ----------------------------------------------------------
-static int upload_cfg(wh_session* s, const wh_decoding_options* opt, const wh_special_tokens* st, int prefilled_index,
-                      int initial_prompt_index, int language_filter, int n_vocab, uint64_t seed) {
-    SamplerCfg c{};
+// the SamplerCfg and the filtered suppress list of one option set, on the host
+static int build_cfg(const wh_session* s, const wh_decoding_options* opt, const wh_special_tokens* st, int prefilled_index, int initial_prompt_index,
+                     int language_filter, int n_vocab, uint64_t seed, SamplerCfg& c, std::vector<int>& sup) {
+    c = SamplerCfg{};
     c.n_vocab = n_vocab;
     c.end_token = st->end_token; c.no_timestamps_token = st->no_timestamps_token; c.time_token_begin = st->time_token_begin;
     c.transcribe_token = st->transcribe_token; c.translate_token = st->translate_token; c.whitespace_token = st->whitespace_token;
@@ -1094,12 +1109,22 @@ static int upload_cfg(wh_session* s, const wh_decoding_options* opt, const wh_sp
     c.seed = seed;
     c.f16_logits = opt ? (opt->float16_logits != 0) : 0;
     // createLogitsFilters: suppressTokens filtered to ids < specialTokenBegin (TextDecoder.swift:876-879)
-    std::vector<int> sup;
+    sup.clear();
     if (opt && opt->suppress_tokens)
         for (int i = 0; i < opt->n_suppress_tokens; ++i)
             if (opt->suppress_tokens[i] < st->special_token_begin && opt->suppress_tokens[i] >= 0) sup.push_back(opt->suppress_tokens[i]);
     if ((int)sup.size() > kMaxSuppress) return set_error(WH_ERR_INVALID_ARGUMENT, "more than %d suppress tokens", kMaxSuppress);
     c.n_suppress = (int)sup.size();
+    return WH_OK;
+}
+
+// entry 0 of the session's tables: every pass but a mixed one
+static int upload_cfg(wh_session* s, const wh_decoding_options* opt, const wh_special_tokens* st, int prefilled_index,
+                      int initial_prompt_index, int language_filter, int n_vocab, uint64_t seed) {
+    SamplerCfg c;
+    std::vector<int> sup;
+    int r = build_cfg(s, opt, st, prefilled_index, initial_prompt_index, language_filter, n_vocab, seed, c, sup);
+    if (r) return r;
     {
         std::vector<unsigned char> mask((size_t)s->m->dims.n_vocab, 0);
         for (int t : sup) if (t < (int)mask.size()) mask[t] = 1;
@@ -1115,6 +1140,28 @@ static int upload_cfg(wh_session* s, const wh_decoding_options* opt, const wh_sp
 namespace whi { int upload_sampler_cfg(wh_session* s, const wh_decoding_options* opt, const wh_special_tokens* st, int prefilled_index,
                                        int initial_prompt_index, int language_filter, uint64_t seed) {
     return upload_cfg(s, opt, st, prefilled_index, initial_prompt_index, language_filter, s->m->dims.n_vocab, seed);
+}
+// The table entries 0 .. n - 1 of a mixed pass (option_mix.h): class c decodes under opts[c] with a prompt of n_prompts[c] tokens.  The three tables are
+// built on the host and go up in three copies behind one synchronisation, whatever the class count.
+int upload_sampler_cfg_classes(wh_session* s, const wh_decoding_options* const* opts, const int32_t* n_prompts, int n, const wh_special_tokens* st,
+                               int prefilled_index, uint64_t seed) {
+    if (n < 1 || n > kMaxOptionClasses) return set_error(WH_ERR_INVALID_ARGUMENT, "%d option classes (1 .. %d)", n, kMaxOptionClasses);
+    const int V = s->m->dims.n_vocab;
+    const size_t stride = (size_t)plan::option_mask_stride(V);
+    std::vector<SamplerCfg> cfg((size_t)n);
+    std::vector<int> lists((size_t)n * kMaxSuppress, 0), sup;
+    std::vector<unsigned char> masks((size_t)n * stride, 0);
+    for (int c = 0; c < n; ++c) {
+        int r = build_cfg(s, opts[c], st, prefilled_index, n_prompts[c], 0, V, seed, cfg[(size_t)c], sup);
+        if (r) return r;
+        for (size_t i = 0; i < sup.size(); ++i) lists[(size_t)c * kMaxSuppress + i] = sup[i];
+        for (int t : sup) if (t < V) masks[(size_t)c * stride + (size_t)t] = 1;
+    }
+    WH_HIP(hipMemcpyAsync(s->sup_mask_dev, masks.data(), masks.size(), hipMemcpyHostToDevice, s->st));
+    WH_HIP(hipMemcpyAsync(s->suppress_dev, lists.data(), sizeof(int) * lists.size(), hipMemcpyHostToDevice, s->st));
+    WH_HIP(hipMemcpyAsync(s->cfg_dev, cfg.data(), sizeof(SamplerCfg) * cfg.size(), hipMemcpyHostToDevice, s->st));
+    WH_HIP(hipStreamSynchronize(s->st));   // the tables are stack temporaries
+    return WH_OK;
 } }
 
 extern "C" int wh_filter_logits(wh_session* s, const wh_decoding_options* opt, const wh_special_tokens* st, const int32_t* tokens,

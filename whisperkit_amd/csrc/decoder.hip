@@ -524,6 +524,9 @@ __device__ __forceinline__ void advance_decode_state(const SamplerCfg& cfg, SeqS
 // TOPK > 0 (beam search, BeamSearchTokenSampler.update's device part, no reference behaviour): after the filters, the log-softmax of the
 // row and its TOPK best entries, descending, ties to the lower id (openai/whisper decoding.py:361 logprobs[idx].topk(beam_size + 1)) go to
 // logprob_out / token_out[b * kBeamTopK + k]; the row stays in registers (the two-kernel form re-read it K + 3 times through L2).
+// DO_ADVANCE == 2 (a mixed pass, option_mix.h): advance, with cfgp and suppress the session's per-class tables - the slot reads the entries of its class
+// (seq_class of SeqState.rng_lane) and draws from the lane in the word's low bits.  A value of an existing parameter, so that every other instantiation
+// keeps its name and its instructions (tools/device_code_hash.py): only mixed passes launch <1, 1, 2, 0>.
 template <int DO_FILTER, int DO_SAMPLE, int DO_ADVANCE, int WRITE_BACK, int TOPK = 0>
 __global__ __launch_bounds__(SAMP_T) void sampler_kernel(const SamplerCfg* __restrict__ cfgp, const int* __restrict__ suppress,
                                                         SeqState* __restrict__ seqs, float* __restrict__ logits_all,
@@ -533,6 +536,8 @@ __global__ __launch_bounds__(SAMP_T) void sampler_kernel(const SamplerCfg* __res
     const int b = blockIdx.x, tid = threadIdx.x;
     SeqState* sq = seqs + b;
     if ((DO_ADVANCE || TOPK) && !slot_live(sq)) return;
+    constexpr bool kMix = DO_ADVANCE == 2;
+    if constexpr (kMix) { const int cls = seq_class(sq->rng_lane); cfgp += cls; suppress += cls * kMaxSuppress; }
     const SamplerCfg cfg = *cfgp;
     const int V = cfg.n_vocab;
     float* logits = logits_all + (size_t)b * V;
@@ -689,7 +694,7 @@ __global__ __launch_bounds__(SAMP_T) void sampler_kernel(const SamplerCfg* __res
         float pr[8], total = 0.0f;
         for (int j = 0; j < k; ++j) { pr[j] = expf(tv[j] - lse); total += pr[j]; }
         const int counter = DO_ADVANCE ? sq->token_index : counter_override;
-        const float rnd = uniform01(cfg.seed + (unsigned long long)sq->rng_lane * 0x632BE59BD9B4E019ull, counter) * total;
+        const float rnd = uniform01(cfg.seed + (unsigned long long)(kMix ? seq_lane(sq->rng_lane) : sq->rng_lane) * 0x632BE59BD9B4E019ull, counter) * total;
         float accp = 0.0f;
         int chosen = 0;
         for (int j = 0; j < k; ++j) {
@@ -718,64 +723,16 @@ __device__ __forceinline__ void stat_wave_reduce(SoftStat& a) {
 // One workgroup per slot: merge the per-workgroup (text, timestamp) statistics of the logits kernel, apply the
 // "timestamp mass beats every text token" rule (LogitsFilter.swift:144-242), take the greedy token and its log-prob
 // (TokenSampler.swift:29-252, T = 0) and advance the decodeText state.
-__global__ __launch_bounds__(256) void sampler_final_kernel(const SamplerCfg* __restrict__ cfgp, SeqState* __restrict__ seqs,
-                                                            const float* __restrict__ stats, int nblk) {
-    __shared__ float sm[4][4];
-    __shared__ int si[4][3];
-    __shared__ SeqState sq_l;     // the slot's whole decode state: thread 0's bookkeeping (token history scans, appends) runs on
-                                  // this LDS copy instead of a chain of dependent global round trips
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    SeqState* sq = seqs + b;
-    if (!slot_live(sq)) return;
-    constexpr int kWords = sizeof(SeqState) / 4;
-    static_assert(kMaxTok <= 256, "one history token per thread");
-    for (int i = tid; i < kWords; i += 256) reinterpret_cast<int*>(&sq_l)[i] = reinterpret_cast<const int*>(sq)[i];
-    // index of the last timestamp token of the history, found by all threads (the rules of the NEXT step need it: compute_filter_rules)
-    const int n_hist = sq->n_tokens;
-    const int tbeg = cfgp->time_token_begin;
-    int last_ts = (tid < n_hist && tid < kMaxTok && sq->tokens[tid] >= tbeg) ? tid : -1;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) last_ts = max(last_ts, __shfl_xor(last_ts, o, 64));
-    SoftStat t{-INFINITY, 0.0f, 0x7fffffff}, u{-INFINITY, 0.0f, 0x7fffffff};
-    constexpr int NR = kStatBlocks / 256;      // records per thread: all loads are issued before the first merge (one L2 round
-    float4 lo[NR];                             // trip instead of NR dependent ones)
-    float2 hi[NR];
-#pragma unroll
-    for (int k = 0; k < NR; ++k) {
-        const int i = tid + 256 * k;
-        const float* e = stats + ((size_t)b * kStatBlocks + min(i, nblk - 1)) * 8;
-        lo[k] = *reinterpret_cast<const float4*>(e);
-        hi[k] = *reinterpret_cast<const float2*>(e + 4);
-    }
-#pragma unroll
-    for (int k = 0; k < NR; ++k) {
-        if (tid + 256 * k < nblk) {
-            stat_merge(t, lo[k].x, lo[k].y, __float_as_int(lo[k].z));
-            stat_merge(u, lo[k].w, hi[k].x, __float_as_int(hi[k].y));
-        }
-    }
-    stat_wave_reduce(t);
-    stat_wave_reduce(u);
-    if (lane == 0) { sm[wave][0] = t.m; sm[wave][1] = t.s; si[wave][0] = t.i; sm[wave][2] = u.m; sm[wave][3] = u.s; si[wave][1] = u.i; si[wave][2] = last_ts; }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < 4; ++w) { stat_merge(t, sm[w][0], sm[w][1], si[w][0]); stat_merge(u, sm[w][2], sm[w][3], si[w][1]); last_ts = max(last_ts, si[w][2]); }
-        const SamplerCfg cfg = *cfgp;
-        const bool ts_active = sq_l.f_rules[1] != 0;
-        int tok; float lp;
-        const bool cond = ts_active && timestamp_mass_wins(t, u, cfg.f16_logits != 0);
-        if (cond || t.m == -INFINITY) {          // text ids masked: the candidates are the timestamp ids
-            tok = u.i; lp = -logf(u.s);
-        } else {
-            SoftStat g = t;
-            stat_merge(g, u.m, u.s, u.i);        // equal maxima: the text id (smaller index) wins, like a first-maximum argmax
-            tok = g.i; lp = -logf(g.s);
-        }
-        advance_decode_state(cfg, &sq_l, tok, lp, sq_l.n_tokens, last_ts);
-    }
-    __syncthreads();
-    for (int i = tid; i < kWords; i += 256) reinterpret_cast<int*>(sq)[i] = reinterpret_cast<const int*>(&sq_l)[i];
-}
+#define SAMPLER_FINAL_NAME sampler_final_kernel
+#define SAMPLER_FINAL_MIXED 0
+#include "sampler_final.inc"
+#undef SAMPLER_FINAL_NAME
+#undef SAMPLER_FINAL_MIXED
+#define SAMPLER_FINAL_NAME sampler_final_mixed_kernel
+#define SAMPLER_FINAL_MIXED 1
+#include "sampler_final.inc"
+#undef SAMPLER_FINAL_NAME
+#undef SAMPLER_FINAL_MIXED
 
 __global__ void rules_init_kernel(const SamplerCfg* __restrict__ cfgp, SeqState* __restrict__ seqs) {
     if (threadIdx.x != 0) return;
@@ -783,7 +740,16 @@ __global__ void rules_init_kernel(const SamplerCfg* __restrict__ cfgp, SeqState*
     const SamplerCfg cfg = *cfgp;
     compute_filter_rules(cfg, sq, sq->n_tokens, cfg.n_vocab, sq->f_rules);
 }
-void launch_rules_init(const SamplerCfg* cfg_dev, SeqState* seq, int batch, hipStream_t st) { rules_init_kernel<<<batch, 64, 0, st>>>(cfg_dev, seq); }
+__global__ void rules_init_mixed_kernel(const SamplerCfg* __restrict__ cfgp, SeqState* __restrict__ seqs) {      // cfgp: the per-class table (option_mix.h)
+    if (threadIdx.x != 0) return;
+    SeqState* sq = seqs + blockIdx.x;
+    const SamplerCfg cfg = cfgp[seq_class(sq->rng_lane)];
+    compute_filter_rules(cfg, sq, sq->n_tokens, cfg.n_vocab, sq->f_rules);
+}
+void launch_rules_init(const SamplerCfg* cfg_dev, SeqState* seq, int batch, hipStream_t st, bool mixed) {
+    if (mixed) rules_init_mixed_kernel<<<batch, 64, 0, st>>>(cfg_dev, seq);
+    else rules_init_kernel<<<batch, 64, 0, st>>>(cfg_dev, seq);
+}
 
 // ---------------------------------------------------------------------------------------------- launchers
 // WH_DBG=1 timeline probe buffer [KK_COUNT][4096][8], allocated once per process (thread-safe function-local static)
@@ -920,13 +886,16 @@ void launch_decoder_step(const DecodeBuffers& db, const SamplerCfg* cfg_dev, con
     a.logits = fused ? nullptr : db.logits; a.prof_kind = KK_DEC_LOGITS;
     if (sample) a.cfg = cfg_dev;                 // Float16-logits switch
     if (fused) { a.stats = db.stats; a.sup_mask = db.sup_mask; }
-    launch_dec32_proj(P32_LOGITS, a, n_bt, st);
+    const bool mixed = sample && db.mixed;       // a mixed pass (option_mix.h): the per-class tables, the mixed instantiations
+    launch_dec32_proj(P32_LOGITS, a, n_bt, st, mixed && fused);
     if (fused) {
         ProfScope ps_(KK_SAMPLER, st);
-        sampler_final_kernel<<<B, 256, 0, st>>>(cfg_dev, db.seq, db.stats, (V + 31) / 32);
+        if (mixed) sampler_final_mixed_kernel<<<B, 256, 0, st>>>(cfg_dev, db.seq, db.stats, (V + 31) / 32);
+        else sampler_final_kernel<<<B, 256, 0, st>>>(cfg_dev, db.seq, db.stats, (V + 31) / 32);
     } else if (sample) {
         ProfScope ps_(KK_SAMPLER, st);
-        sampler_kernel<1, 1, 1, 0><<<B, SAMP_T, 0, st>>>(cfg_dev, suppress_dev, db.seq, db.logits, 0, nullptr, nullptr);
+        if (mixed) sampler_kernel<1, 1, 2, 0><<<B, SAMP_T, 0, st>>>(cfg_dev, suppress_dev, db.seq, db.logits, 0, nullptr, nullptr);
+        else sampler_kernel<1, 1, 1, 0><<<B, SAMP_T, 0, st>>>(cfg_dev, suppress_dev, db.seq, db.logits, 0, nullptr, nullptr);
     }
 }
 

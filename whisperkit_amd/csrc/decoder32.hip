@@ -140,10 +140,14 @@ __device__ __forceinline__ void chan_merge(float& cn, float& cm, float& cM2, flo
 // the CUs that the cross-attention streams of the other sessions leave can hold at once; on half of the CUs the projection chain takes twice as long
 // (profiles/r06s_cu_partition_sweep.jsonl), i.e. its cost in flight is workgroup ROUNDS, and two row tiles per workgroup halve them.  The k-tiles of a row tile
 // are multiplied by the same wave in the same order as with RT = 1 and meet in LDS in the same order: the same bits (tests/test_gpu_round6.py).
+// MODE P32_LOGITS_MIXED (a mixed pass, option_mix.h) is P32_LOGITS with one suppress mask per option class in a.sup_mask, option_mask_stride(N) bytes
+// apart: a slot reads the mask of its class (seq_class of SeqState.rng_lane).  A mode of its own, so that the instantiations of every other mode keep
+// their names and their instructions (tools/device_code_hash.py): only mixed passes launch it.
 template <int MODE, bool HILO, int TC, bool NTW, int RT>
 __global__ __launch_bounds__(256, 2) void dec32_proj_kernel(const P32Args a) {
-    constexpr bool kLN = MODE == P32_QKV || MODE == P32_Q || MODE == P32_FC1 || MODE == P32_LOGITS;
-    constexpr int kXs = MODE == P32_LOGITS ? 256 * 6 : 32 * 33;
+    constexpr bool kMix = MODE == P32_LOGITS_MIXED, kLogits = MODE == P32_LOGITS || kMix;
+    constexpr bool kLN = MODE == P32_QKV || MODE == P32_Q || MODE == P32_FC1 || kLogits;
+    constexpr int kXs = kLogits ? 256 * 6 : 32 * 33;
     __shared__ float red[RT][4][16][64];             // the four waves' partial tiles
     __shared__ float st_l[8][32][3];                 // LayerNorm statistics: 8 partial (n, mean, M2) per slot
     __shared__ float xs_raw[kXs];                    // RESID: the tile's new residual values; LOGITS: sampler records (one buffer: the row tiles of a workgroup use it in turn)
@@ -209,21 +213,23 @@ __global__ __launch_bounds__(256, 2) void dec32_proj_kernel(const P32Args a) {
     int tb = 0, ws_tok = 0, eot_tok = 0, nots_tok = 0, r16 = 0;
 #pragma unroll
     for (int t = 0; t < RT; ++t) masked4[t] = 0xffffffffu;
-    if constexpr (MODE == P32_LOGITS) {
+    if constexpr (kLogits) {
         if (a.cfg) r16 = a.cfg->f16_logits;
         if (a.stats) {
             if (valid) {
 #pragma unroll
                 for (int i = 0; i < 6; ++i) rules[i] = a.seq[gb].f_rules[i];
             }
+            const unsigned char* sup_mask = a.sup_mask;
+            if constexpr (kMix) { if (valid) sup_mask += (size_t)seq_class(a.seq[gb].rng_lane) * plan::option_mask_stride(a.N); }
 #pragma unroll
             for (int t = 0; t < RT; ++t) {
                 const int n = min(rt0 + t, n_rt - 1) * 32 + 4 * sub;
-                if (n + 3 < a.N) masked4[t] = *reinterpret_cast<const unsigned*>(a.sup_mask + n);
+                if (n + 3 < a.N) masked4[t] = *reinterpret_cast<const unsigned*>(sup_mask + n);
                 else {
                     masked4[t] = 0;
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) masked4[t] |= (unsigned)(n + i < a.N ? a.sup_mask[n + i] : 1) << (8 * i);
+                    for (int i = 0; i < 4; ++i) masked4[t] |= (unsigned)(n + i < a.N ? sup_mask[n + i] : 1) << (8 * i);
                 }
             }
             tb = a.cfg->time_token_begin; ws_tok = a.cfg->whitespace_token; eot_tok = a.cfg->end_token; nots_tok = a.cfg->no_timestamps_token;
@@ -367,7 +373,7 @@ __global__ __launch_bounds__(256, 2) void dec32_proj_kernel(const P32Args a) {
 #pragma unroll
   for (int t = 0; t < RT; ++t) {
     if (t >= n_mine) break;
-    if constexpr (MODE == P32_RESID || MODE == P32_LOGITS) { if (t > 0) __syncthreads(); }      // the previous tile's readers are done with xs_raw
+    if constexpr (MODE == P32_RESID || kLogits) { if (t > 0) __syncthreads(); }      // the previous tile's readers are done with xs_raw
     const int rt = rt0 + t, n = rt * 32 + 4 * sub;
     float y[4];
     if constexpr (kLN) {
@@ -502,7 +508,7 @@ static void launch_planned(const P32Args& a, const plan::Dec32Plan& p, hipStream
         if (p.ntw) dec32_proj_kernel<MODE, HILO, TC_, true, RT_><<<grid, 256, 0, st>>>(a); \
         else dec32_proj_kernel<MODE, HILO, TC_, false, RT_><<<grid, 256, 0, st>>>(a); \
         return; } while (0)
-    if constexpr (MODE != P32_LOGITS && MODE != P32_Q) {
+    if constexpr (MODE != P32_LOGITS && MODE != P32_LOGITS_MIXED && MODE != P32_Q) {
         if (p.rt == 4) D32_GO(1, 4);
     }
     if (p.rt >= 2) {
@@ -521,7 +527,7 @@ static void launch_planned(const P32Args& a, const plan::Dec32Plan& p, hipStream
 }
 
 unsigned long long* debug_buffer();
-void launch_dec32_proj(int mode, const P32Args& a_in, int n_bt, hipStream_t st) {
+void launch_dec32_proj(int mode, const P32Args& a_in, int n_bt, hipStream_t st, bool mixed) {
     using namespace knob;
     P32Args a = a_in;
     a.dbg = (debug_buffer() && a.prof_kind >= 0) ? debug_buffer() + (size_t)a.prof_kind * 4096 * 8 : nullptr;   // WH_DBG=1 timeline probe
@@ -534,7 +540,10 @@ void launch_dec32_proj(int mode, const P32Args& a_in, int n_bt, hipStream_t st) 
         case P32_QKV: launch_planned<P32_QKV, true>(a, p, st); break;
         case P32_Q: launch_planned<P32_Q, true>(a, p, st); break;
         case P32_FC1: launch_planned<P32_FC1, true>(a, p, st); break;
-        case P32_LOGITS: launch_planned<P32_LOGITS, true>(a, p, st); break;
+        case P32_LOGITS:
+            if (mixed && a.stats && a.sup_mask) launch_planned<P32_LOGITS_MIXED, true>(a, p, st);      // (the plan is the one of P32_LOGITS)
+            else launch_planned<P32_LOGITS, true>(a, p, st);
+            break;
         default:
             if (a.zlo != nullptr) launch_planned<P32_RESID, true>(a, p, st);
             else launch_planned<P32_RESID, false>(a, p, st);

@@ -26,6 +26,8 @@ using whi::set_error;
 namespace whi {
 int upload_sampler_cfg(wh_session* s, const wh_decoding_options* opt, const wh_special_tokens* st, int prefilled_index,
                        int initial_prompt_index, int language_filter, uint64_t seed);
+int upload_sampler_cfg_classes(wh_session* s, const wh_decoding_options* const* opts, const int32_t* n_prompts, int n, const wh_special_tokens* st,
+                               int prefilled_index, uint64_t seed);
 }
 
 
@@ -266,7 +268,7 @@ static int get_step_graph(wh_session* s, int batch, int first_step, hipGraphExec
     DecodeBuffers db = whi::decode_buffers(s, batch, first_step + kStepsPerGraph - 1);
     // (a compacted pass bakes the slot table's address, the mapped kernel instantiations and its own slots per workgroup into its launches)
     const WhGraphKey key{batch, s->align_enabled ? 1 : 0, s->fused_greedy ? 1 : 0, s->align_enabled ? s->n_align_alloc : 0, db.self_rows, db.xattn_gate ? 1 : 0,
-                         db.slot_home ? 1 : 0, db.slot_home ? s->pass_spw : 0, db.self_owner ? 1 : 0};
+                         db.slot_home ? 1 : 0, db.slot_home ? s->pass_spw : 0, db.self_owner ? 1 : 0, db.mixed};
     auto it = s->graphs.find(key);
     if (it != s->graphs.end()) { s->graph_use[key] = ++s->graph_tick; *out = it->second; return WH_OK; }
     // The cache is capped (a large-v3 step graph holds ~2.5 k kernel nodes; a configuration = everything of the key but the row bound has up
@@ -275,7 +277,7 @@ static int get_step_graph(wh_session* s, int batch, int first_step, hipGraphExec
     const size_t cap = (size_t)knob::once<knob::WH_GRAPH_CAP>();
     while (s->graphs.size() >= cap) {
         auto same_cfg = [](const WhGraphKey& a, const WhGraphKey& b) {
-            return a.batch == b.batch && a.align == b.align && a.fused == b.fused && a.n_align == b.n_align && a.gate == b.gate && a.mapped == b.mapped && a.spw == b.spw && a.owner == b.owner;
+            return a.batch == b.batch && a.align == b.align && a.fused == b.fused && a.n_align == b.n_align && a.gate == b.gate && a.mapped == b.mapped && a.spw == b.spw && a.owner == b.owner && a.mixed == b.mixed;
         };
         const WhGraphKey* victim = nullptr;
         unsigned long long victim_last = ~0ull;
@@ -333,7 +335,9 @@ static int report_progress(wh_session* s, int batch) {
         std::string text;
         if (s->tok) {
             std::vector<int> ids;
-            for (int i = 0; i < q.n_tokens; ++i) if (!s->skip_special_in_progress || q.tokens[i] < s->special_begin_in_progress) ids.push_back(q.tokens[i]);
+            // (a pass over slots with options of their own: each slot's text under its own skip_special_tokens, by home slot)
+            const bool skip = s->skip_special_by_slot ? s->skip_special_by_slot[p.slot] != 0 : s->skip_special_in_progress;
+            for (int i = 0; i < q.n_tokens; ++i) if (!skip || q.tokens[i] < s->special_begin_in_progress) ids.push_back(q.tokens[i]);
             text = s->tok->decode(ids);
             p.text = text.c_str();
         }
@@ -489,9 +493,20 @@ static int run_token_loop(wh_session* s, int batch, int loop_count, PassLayout* 
     return final_read();
 }
 
+// A mixed pass (option_mix.h): slot b decodes under class_of_slot[b]'s options and prompt.  The batch-key fields are equal over the classes (the caller has
+// checked); everything per pass is read from class 0.
+struct MixClasses {
+    int n;
+    const wh_decoding_options* const* opts;      // [n]
+    const int32_t* class_of_slot;                // [batch], home-slot terms
+    const int32_t* const* prompts; const int32_t* n_prompts;      // [n]
+    // null, or [batch] by home slot: the options each slot's RESULT is finalised under (wh_decoding_fallback reads the compression-ratio, log-prob and
+    // no-speech thresholds, which belong to the audio, not to its class: two audios of one class may fall back differently).  Null: the class's options
+    const wh_decoding_options* const* slot_opts;
+};
 static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options* opt, const wh_special_tokens* st, const int32_t* prompt,
                             int n_prompt, const int32_t* language_tokens, const float* temperatures, const int32_t* active, uint64_t seed,
-                            wh_decoding_result* out);
+                            wh_decoding_result* out, const MixClasses* mix = nullptr);
 extern "C" int wh_decode_text(wh_session* s, int batch, const wh_decoding_options* opt, const wh_special_tokens* st, const int32_t* prompt,
                               int n_prompt, const float* temperatures, const int32_t* active, uint64_t seed, wh_decoding_result* out) {
     return decode_text_impl(s, batch, opt, st, prompt, n_prompt, nullptr, temperatures, active, seed, out);
@@ -503,32 +518,51 @@ extern "C" int wh_decode_text_languages(wh_session* s, int batch, const wh_decod
 }
 static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options* opt, const wh_special_tokens* st, const int32_t* prompt,
                             int n_prompt, const int32_t* language_tokens, const float* temperatures, const int32_t* active, uint64_t seed,
-                            wh_decoding_result* out) {
+                            wh_decoding_result* out, const MixClasses* mix) {
     CHECK_SESSION(s); CHECK_BATCH(s, batch);
+    if (mix) { opt = mix->opts[0]; prompt = mix->prompts[0]; n_prompt = mix->n_prompts[0]; }
     if (!opt || !st || !prompt || !out) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text: null argument");
-    if (n_prompt < 1 || n_prompt >= kMaxTok) return set_error(WH_ERR_PREFILL_FAILED, "wh_decode_text: prompt length %d out of range [1,%d)", n_prompt, kMaxTok);
     const int V = s->m->dims.n_vocab;
-    for (int i = 0; i < n_prompt; ++i)
-        if (prompt[i] < 0 || prompt[i] >= V) return set_error(WH_ERR_PREFILL_FAILED, "wh_decode_text: prompt token %d out of vocabulary", prompt[i]);
     const int prefilled_index = 0;   // decoderInputs.cacheLength after reset (Core/Models.swift:313)
-    int r = whi::upload_sampler_cfg(s, opt, st, prefilled_index, n_prompt, 0, seed);
+    const int n_cls = mix ? mix->n : 1;
+    auto cls_prompt = [&](int c) { return mix ? mix->prompts[c] : prompt; };
+    auto cls_n_prompt = [&](int c) { return mix ? mix->n_prompts[c] : n_prompt; };
+    auto cls_opt = [&](int c) { return mix ? mix->opts[c] : opt; };
+    auto cls_of = [&](int hb) { return mix ? mix->class_of_slot[hb] : 0; };
+    int r = WH_OK;
+    for (int c = 0; c < n_cls; ++c) {
+        const int32_t* pr = cls_prompt(c);
+        const int np = cls_n_prompt(c);
+        if (!pr || !cls_opt(c)) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text: null argument");
+        if (np < 1 || np >= kMaxTok) return set_error(WH_ERR_PREFILL_FAILED, "wh_decode_text: prompt length %d out of range [1,%d)", np, kMaxTok);
+        for (int i = 0; i < np; ++i)
+            if (pr[i] < 0 || pr[i] >= V) return set_error(WH_ERR_PREFILL_FAILED, "wh_decode_text: prompt token %d out of vocabulary", pr[i]);
+    }
+    // (an unmixed pass: entry 0 of the tables, as ever; a mixed one: every class's entries behind one synchronisation)
+    r = mix ? whi::upload_sampler_cfg_classes(s, mix->opts, mix->n_prompts, n_cls, st, prefilled_index, seed)
+            : whi::upload_sampler_cfg(s, opt, st, prefilled_index, n_prompt, 0, seed);
     if (r) return r;
     if (opt->word_timestamps && s->m->n_align > 0) { r = whi::ensure_align(s); if (r) return r; }
     s->align_enabled = opt->word_timestamps && s->align;
     // per-slot language token (batched windows of different audios, each with its own detected language): it replaces the
     // token that follows <|startoftranscript|> in the shared prompt (prefillDecoderInputs, TextDecoder.swift:183-188)
-    int lang_pos = -1;
-    if (language_tokens && wh_is_model_multilingual(s->m))
-        for (int i = 0; i + 1 < n_prompt; ++i) if (prompt[i] == st->start_of_transcript_token) { lang_pos = i + 1; break; }
+    int lang_pos_of[kMaxOptionClasses];
+    for (int c = 0; c < n_cls; ++c) {
+        lang_pos_of[c] = -1;
+        if (language_tokens && wh_is_model_multilingual(s->m))
+            for (int i = 0; i + 1 < cls_n_prompt(c); ++i) if (cls_prompt(c)[i] == st->start_of_transcript_token) { lang_pos_of[c] = i + 1; break; }
+    }
     // the decode state of home slot hb as the pass starts it
     auto init_slot = [&](SeqState& q, int hb, bool act) {
+        const int c = cls_of(hb), np = cls_n_prompt(c), lang_pos = lang_pos_of[c];
+        const int32_t* pr = cls_prompt(c);
         memset(&q, 0, sizeof(q));
-        for (int i = 0; i < n_prompt; ++i) q.tokens[i] = prompt[i];
+        for (int i = 0; i < np; ++i) q.tokens[i] = pr[i];
         if (lang_pos >= 0 && language_tokens[hb] >= 0 && language_tokens[hb] < V) q.tokens[lang_pos] = language_tokens[hb];
-        q.n_tokens = n_prompt; q.token_index = prefilled_index; q.next_token = q.tokens[0]; q.prompt_len = n_prompt;
+        q.n_tokens = np; q.token_index = prefilled_index; q.next_token = q.tokens[0]; q.prompt_len = np;
         q.active = act ? 1 : 0;
         q.temperature = f16_round(temperatures ? temperatures[hb] : opt->temperature);
-        q.rng_lane = hb;          // the slot's random stream (T > 0) does not depend on where the slot is decoded
+        q.rng_lane = seq_pack_lane(hb, c);      // the slot's random stream (T > 0) does not depend on where the slot is decoded; its option class (0 unless mixed)
     };
     // ---- compacted pass (wh_session_set_fallback_compaction 1): a sparse `active` mask decodes at the width compact_pass_plan gives; compact
     // slot i stands for home slot slot_home_host[i] - its encoder output / cross K / V rows, its alignment rows, its language token,
@@ -537,7 +571,7 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
     for (int b = 0; b < batch; ++b) n_live += (active ? active[b] != 0 : 1);
     plan::CompactPassPlan cp{false, batch, s->use_xabs ? s->xabs.spw : 1};
     if (s->fallback_compaction == 1 && active) cp = plan::compact_pass_plan(n_live, batch, s->B, s->use_xabs ? s->xabs.spw : 1);
-    struct PassScope { wh_session* s; ~PassScope() { s->pass_mapped = false; s->pass_owner = false; } } pass_scope{s};      // (every exit: the next caller of decode_buffers sees a plain pass)
+    struct PassScope { wh_session* s; ~PassScope() { s->pass_mapped = false; s->pass_owner = false; s->pass_mixed = false; } } pass_scope{s};      // (every exit: the next caller of decode_buffers sees a plain pass)
     const int width = cp.compact ? cp.width : batch;
     if (cp.compact) {
         if (!s->slot_home_dev) WH_HIP(s->mem.alloc(&s->slot_home_dev, (size_t)s->B, false));
@@ -552,13 +586,15 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
         for (int b = 0; b < batch; ++b) init_slot(s->seq_host[b], b, active ? active[b] != 0 : true);
     }
     s->decode_passes += 1;
+    if (mix) { s->pass_mixed = true; s->mix_mixed_passes += 1; s->mix_max_classes = std::max<long long>(s->mix_max_classes, n_cls); }
     // fused greedy path: every active slot samples at T = 0 (filters + softmax statistics in the logits epilogue)
     s->fused_greedy = true;
     for (int b = 0; b < width; ++b) if (s->seq_host[b].active && s->seq_host[b].temperature != 0.0f) s->fused_greedy = false;
     if (knob::now<knob::WH_NO_FUSED_SAMPLER>()) s->fused_greedy = false;
     WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * width, hipMemcpyHostToDevice, s->st));
-    launch_rules_init(s->cfg_dev, s->seq, width, s->st);
-    const int loop_count = std::min(opt->sample_length, kMaxTok - 1);
+    launch_rules_init(s->cfg_dev, s->seq, width, s->st, mix != nullptr);
+    int loop_count = 0;       // a slot finishes at its class's count (SamplerCfg.loop_count); the host loop runs to the largest
+    for (int c = 0; c < n_cls; ++c) loop_count = std::max(loop_count, std::min(cls_opt(c)->sample_length, kMaxTok - 1));
     s->skip_special_in_progress = opt->skip_special_tokens != 0;
     s->special_begin_in_progress = st->special_token_begin;
     // ---- in-pass compaction (wh_session_set_inpass_compaction 1): the pass may narrow between step graphs as its slots finish (run_token_loop)
@@ -611,9 +647,37 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
     }
     for (int b = 0; b < batch; ++b) {
         if (!s->seq_host[b].active) { memset(&out[b], 0, sizeof(out[b])); continue; }
-        whi::finalize_decoding_result(s->seq_host[b], opt, st, s->seq_host[b].temperature, &out[b]);
+        const wh_decoding_options* fo = (mix && mix->slot_opts && mix->slot_opts[b]) ? mix->slot_opts[b] : cls_opt(cls_of(b));      // the audio's own thresholds
+        whi::finalize_decoding_result(s->seq_host[b], fo, st, s->seq_host[b].temperature, &out[b]);
     }
     return WH_OK;
+}
+
+// wh_decode_text with an option class per slot.  What needs no session is checked first: a caller learns about a bad class table without a device.
+extern "C" int wh_decode_text_mixed(wh_session* s, int batch, const wh_decoding_options* opts, int n_classes, const int32_t* class_of_slot,
+                                    const wh_special_tokens* st, const int32_t* const* prompts, const int32_t* n_prompts, const int32_t* language_tokens,
+                                    const float* temperatures, const int32_t* active, uint64_t seed, wh_decoding_result* out) {
+    if (n_classes < 1 || n_classes > kMaxOptionClasses)
+        return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text_mixed: %d option classes (1 .. %d)", n_classes, kMaxOptionClasses);
+    if (!opts || !class_of_slot) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text_mixed: null class table");
+    for (int c = 1; c < n_classes; ++c)
+        if (!plan::option_batch_key_equal(opts[0], opts[c]))
+            return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text_mixed: class %d differs from class 0 in a field that belongs to the pass (temperature ladder, seed, "
+                             "use_prefill_prompt, detect_language, word_timestamps, float16_logits, beam search)", c);
+    if (batch >= 1 && batch <= kMaxSessionSlots)
+        for (int b = 0; b < batch; ++b)
+            if (class_of_slot[b] < 0 || class_of_slot[b] >= n_classes)
+                return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text_mixed: slot %d names class %d of %d", b, class_of_slot[b], n_classes);
+    CHECK_SESSION(s); CHECK_BATCH(s, batch);
+    if (!st || !prompts || !n_prompts || !out) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text_mixed: null argument");
+    const wh_decoding_options* po[kMaxOptionClasses];
+    int32_t skip[kMaxSessionSlots];
+    for (int c = 0; c < n_classes; ++c) po[c] = &opts[c];
+    for (int b = 0; b < batch; ++b) skip[b] = opts[class_of_slot[b]].skip_special_tokens != 0;
+    const MixClasses mix{n_classes, po, class_of_slot, prompts, n_prompts, nullptr};
+    struct SkipScope { wh_session* s; const int32_t* keep; ~SkipScope() { s->skip_special_by_slot = keep; } } skip_scope{s, s->skip_special_by_slot};
+    s->skip_special_by_slot = skip;
+    return decode_text_impl(s, batch, nullptr, st, nullptr, 0, language_tokens, temperatures, active, seed, out, &mix);
 }
 
 // decodeText with caller-supplied LogitsFiltering / TokenSampling objects: the reference's host loop (Core/TextDecoder.swift:573-757)
@@ -789,6 +853,7 @@ struct AudioJob {
     std::vector<std::pair<int, int>> clips;
     size_t clip = 0; int seek = 0; bool started = false; bool finished = false;
     int windows = 0;
+    int cls = 0;                                    // option class inside its group (option mixing; 0 otherwise)
     wh_transcription* tr;
     int cur_seek = 0, cur_size = 0;   // window in flight
 };
@@ -809,8 +874,15 @@ static bool job_next_window(AudioJob& j, const wh_decoding_options* opt) {
     return false;
 }
 
-static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_decoding_options* opt, const wh_special_tokens* st) {
+// classes: null, or (option mixing) the options that stand for the option classes of this group - job j decodes under class j.cls and everything the
+// host reads per audio (windowing, thresholds, text) comes from the job's own options; `opt` is then class 0 and serves the batch-key fields, which are
+// equal over the group (option_mix.h).  Null: every job runs under `opt`, as ever.
+static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_decoding_options* opt, const wh_special_tokens* st,
+                           const std::vector<const wh_decoding_options*>* classes = nullptr) {
     const wh_model* m = s->m;
+    const bool mixed = classes != nullptr;
+    auto jopt = [&](const AudioJob& j) { return mixed ? j.opt : opt; };
+    struct SkipScope { wh_session* s; ~SkipScope() { s->skip_special_by_slot = nullptr; } } skip_scope{s};
     const bool multilingual = wh_is_model_multilingual(m) != 0;
     const int detect = opt->detect_language < 0 ? !opt->use_prefill_prompt : opt->detect_language;
     const double t_start = now_s();
@@ -838,7 +910,7 @@ static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_
         double t0 = now_s();
         for (size_t ji = 0; ji < jobs.size() && (int)slot_job.size() < round_cap; ++ji) {
             AudioJob& j = jobs[ji];
-            if (j.finished || j.status != WH_OK || !job_next_window(j, opt)) continue;
+            if (j.finished || j.status != WH_OK || !job_next_window(j, jopt(j))) continue;
             const int b = (int)slot_job.size();
             // a window without samples: the reference slices audioArray[seek ..< seek + segmentSize], AudioProcessor.padOrTrimAudio returns nil for
             // the empty slice ("startIndex is outside the buffer size", Core/Audio/AudioProcessor.swift:151-155) and the task throws
@@ -871,24 +943,55 @@ static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_
         // language token per slot: every audio of the batch detects (and is prompted with) its own language, like the reference's
         // one TranscribeTask per audio (WhisperKit.swift:735-792); -1 = the options' language / English default of prefillDecoderInputs
         std::vector<int32_t> lang_slot(nb, opt->language_token);
+        // (option mixing) the class of every slot, the prompt of every class, each slot's skip_special_tokens for the progress callback
+        std::vector<int32_t> cls_slot, skip_slot, mix_np;
+        std::vector<const wh_decoding_options*> opt_slot;      // each slot's own options: its result's fallback decision (finalize_decoding_result)
+        std::vector<std::vector<int32_t>> mix_prompt;
+        std::vector<const int32_t*> mix_pp;
+        bool any_detects = opt->language_token < 0;
+        if (mixed) {
+            cls_slot.resize(nb); skip_slot.resize(nb); opt_slot.resize(nb);
+            any_detects = false;
+            for (int b = 0; b < nb; ++b) {
+                const AudioJob& j = jobs[slot_job[b]];
+                cls_slot[b] = j.cls; opt_slot[b] = j.opt; skip_slot[b] = j.opt->skip_special_tokens != 0; lang_slot[b] = j.opt->language_token;
+                any_detects |= j.opt->language_token < 0;
+            }
+            s->skip_special_by_slot = skip_slot.data();
+        }
         for (size_t ti = 0; ti < temps.size(); ++ti) {
             CHECK_CANCEL(s);
             std::vector<float> tv(nb, temps[ti]);
             bool per_slot_lang = false;
-            if (multilingual && opt->language_token < 0 && detect) {
+            if (multilingual && any_detects && detect) {
                 std::vector<int32_t> lt(nb); std::vector<float> ll(nb);
                 r = wh_detect_language(s, nb, st, lt.data(), ll.data()); if (r) return r;
                 for (int b = 0; b < nb; ++b) {
                     if (!active[b]) continue;
+                    if (mixed && jobs[slot_job[b]].opt->language_token >= 0) continue;      // this audio states its language
                     lang_slot[b] = lt[b];
                     wh_transcription* t = jobs[slot_job[b]].tr;
                     if (!t->language_set) { t->language_token = lt[b]; t->language_set = true; }
                 }
                 per_slot_lang = true;
             }
-            if (opt->use_prefill_prompt) {
+            if (opt->use_prefill_prompt && !mixed) {
                 n_prompt = wh_prefill_prompt(m, opt, st, opt->language_token, prompt.data(), (int)prompt.size());
                 if (n_prompt <= 0) return set_error(WH_ERR_PREFILL_FAILED, "prefill prompt does not fit");
+            }
+            if (mixed && mix_prompt.empty()) {
+                for (const wh_decoding_options* co : *classes) {
+                    std::vector<int32_t> pr(kMaxPrompt);
+                    int np = 1;
+                    pr[0] = st->start_of_transcript_token;
+                    if (co->use_prefill_prompt) {
+                        np = wh_prefill_prompt(m, co, st, co->language_token, pr.data(), (int)pr.size());
+                        if (np <= 0) return set_error(WH_ERR_PREFILL_FAILED, "prefill prompt does not fit");
+                    }
+                    pr.resize((size_t)np);
+                    mix_prompt.push_back(std::move(pr)); mix_np.push_back(np);
+                }
+                for (const auto& pr : mix_prompt) mix_pp.push_back(pr.data());
             }
             r = whi::reset_decoder_inputs_masked(s, nb, active.data()); if (r) return r;     // accepted slots keep their alignment rows
             uint64_t seed = opt->seed + 1000003ull * (uint64_t)jobs[slot_job[0]].windows + ti;
@@ -901,6 +1004,13 @@ static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_
                 bool again = false;
                 for (int b = 0; b < nb; ++b) again |= tmp[b].needs_fallback != 0;
                 if (again && ti + 1 < temps.size()) { r = wh_prepare_decoder_inputs(s, nb); if (r) return r; }   // the beam slots overwrote the windows' cross K/V
+            } else if (mixed) {
+                // a slot whose audio states its language keeps its class's prompt (-1: no replacement), a detected one gets its own token
+                std::vector<int32_t> ml(lang_slot);
+                for (int b = 0; b < nb; ++b) if (jobs[slot_job[b]].opt->language_token >= 0) ml[b] = -1;
+                const MixClasses mix{(int)classes->size(), classes->data(), cls_slot.data(), mix_pp.data(), mix_np.data(), opt_slot.data()};
+                r = decode_text_impl(s, nb, nullptr, st, nullptr, 0, langs ? ml.data() : nullptr, tv.data(), active.data(), seed, tmp.data(), &mix);
+                if (r) return r;
             } else {
                 r = decode_text_impl(s, nb, opt, st, prompt.data(), n_prompt, langs, tv.data(), active.data(), seed, tmp.data());
                 if (r) return r;
@@ -924,7 +1034,7 @@ static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_
         double device_align_s = 0;
         if (device_paths) {
             std::vector<int32_t> rows(nb);
-            for (int b = 0; b < nb; ++b) { rows[b] = wh_word_alignment_rows(&res[b], opt, st, s->tok != nullptr); if (rows[b] < 0) return WH_ERR_SEGMENTING_FAILED; }
+            for (int b = 0; b < nb; ++b) { rows[b] = wh_word_alignment_rows(&res[b], jopt(jobs[slot_job[b]]), st, s->tok != nullptr); if (rows[b] < 0) return WH_ERR_SEGMENTING_FAILED; }
             r = whi::alignment_paths(s, nb, rows.data(), &path_len, &path_ti, &path_tj); if (r) return r;
             device_align_s = now_s() - t4;
         }
@@ -932,6 +1042,7 @@ static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_
         for (int b = 0; b < nb; ++b) {
             AudioJob& j = jobs[slot_job[b]];
             wh_transcription* tr = j.tr;
+            const wh_decoding_options* const jo = jopt(j);
             // "Windowing" (TranscribeTask.swift:175-265) is host-only code shared with the CPU tests: wh_transcription_add_window
             std::vector<float> full;
             const float* alignment = nullptr;
@@ -944,11 +1055,11 @@ static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_
             int32_t seek = j.seek;
             const int seg_before = (int)tr->segments.size();
             if (device_paths) {
-                r = wh_transcription_add_window_path(tr, s->tok, opt, st, &res[b], path_ti + (size_t)b * kDtwPathCap, path_tj + (size_t)b * kDtwPathCap,
+                r = wh_transcription_add_window_path(tr, s->tok, jo, st, &res[b], path_ti + (size_t)b * kDtwPathCap, path_tj + (size_t)b * kDtwPathCap,
                                                      path_len[b], lang_slot[b], j.cur_size, &seek);
                 tr->timings.decoding_word_timestamps += device_align_s / nb;      // the batch's device stage, shared out like the other stages
             } else {
-                r = wh_transcription_add_window(tr, s->tok, opt, st, &res[b], alignment, lang_slot[b], j.cur_size, &seek);
+                r = wh_transcription_add_window(tr, s->tok, jo, st, &res[b], alignment, lang_slot[b], j.cur_size, &seek);
             }
             if (r) return r;
             j.seek = seek;
@@ -972,7 +1083,7 @@ static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_
         if (j.status != WH_OK) continue;
         wh_transcription* tr = j.tr;
         tr->timings.full_pipeline = now_s() - t_start;
-        int fr = wh_transcription_finalize(tr, s->tok, opt, st);
+        int fr = wh_transcription_finalize(tr, s->tok, jopt(j), st);
         if (fr) { j.status = fr; j.error = wh_last_error(); }
     }
     return WH_OK;
@@ -1026,11 +1137,25 @@ static int transcribe_items(wh_session* s, const float* const* pcm, const int32_
         if (g < 0) { g = (int)group_opt.size(); group_opt.push_back(j.opt); }
         group_of[(size_t)i] = g;
     }
+    // option mixing (wh_session_set_option_mixing 1): the groups are the batch keys (option_mix.h option_mix_plan); a group's audios carry their class
+    plan::OptionMixPlan mixp;
+    const bool mixing = s->option_mixing == 1;
+    if (mixing) {
+        std::vector<const wh_decoding_options*> po((size_t)n_audio, nullptr);
+        for (int i = 0; i < n_audio; ++i) if (group_of[(size_t)i] >= 0) po[(size_t)i] = all[(size_t)i].opt;
+        mixp = plan::option_mix_plan(po.data(), n_audio);
+        group_of = mixp.group;
+        group_opt.clear();
+        for (const auto& cl : mixp.classes) group_opt.push_back(cl[0]);
+        for (int i = 0; i < n_audio; ++i) if (mixp.cls[(size_t)i] >= 0) all[(size_t)i].cls = mixp.cls[(size_t)i];
+    }
     int hard = WH_OK;
     for (size_t g = 0; g < group_opt.size(); ++g) {
         std::vector<AudioJob> jobs;
         for (int i = 0; i < n_audio; ++i) if (group_of[(size_t)i] == (int)g) { jobs.push_back(all[(size_t)i]); jobs.back().tr = new wh_transcription(); }
-        const int r = hard ? hard : transcribe_jobs(s, jobs, group_opt[g], st);       // after a device error nothing else can run
+        const bool mix_group = mixing && plan::option_mixable(*group_opt[g]);      // (beam search groups run as without the option)
+        if (mix_group && !hard) s->mix_groups_run += 1;
+        const int r = hard ? hard : transcribe_jobs(s, jobs, group_opt[g], st, mix_group ? &mixp.classes[g] : nullptr);       // after a device error nothing else can run
         const std::string why = r ? wh_last_error() : "";
         if (r == WH_ERR_HIP || r == WH_ERR_CANCELLED) hard = r;
         for (auto& j : jobs) {
@@ -1228,6 +1353,7 @@ extern "C" int wh_measure_kernels(wh_session* s, int batch, int n_steps, double*
         for (int b = 0; b < batch; ++b) {
             SeqState& q = s->seq_host[b];
             q = saved[b];
+            q.rng_lane = seq_lane(q.rng_lane);      // states a mixed pass left behind carry their class: the unmixed sampler launched below reads the whole word as the lane
             int pl = std::max(q.prompt_len, 1);
             q.n_tokens = pl; q.token_index = 0; q.next_token = q.tokens[0]; q.done = 0; q.active = 1; q.steps = 0; q.first_token_too_low = 0;
         }

@@ -82,8 +82,10 @@ struct WhGraphKey {
     int batch, align, fused, n_align, self_rows, gate;
     int mapped, spw;      // compacted pass (slot table + mapped cross-attention instantiations) and its slots per absorbed-attention workgroup; 0, 0 otherwise
     int owner;            // 1: a pass that narrowed in flight - the self-attention reads the session's row -> owner table (dec_self_attn_owner_kernel); 0 otherwise
+    int mixed;            // 1: a mixed pass (option_mix.h) - the logits epilogue and the samplers run their *_mixed instantiations; 0 otherwise
     bool operator<(const WhGraphKey& o) const {
-        return std::tie(batch, align, fused, n_align, self_rows, gate, mapped, spw, owner) < std::tie(o.batch, o.align, o.fused, o.n_align, o.self_rows, o.gate, o.mapped, o.spw, o.owner);
+        return std::tie(batch, align, fused, n_align, self_rows, gate, mapped, spw, owner, mixed) <
+               std::tie(o.batch, o.align, o.fused, o.n_align, o.self_rows, o.gate, o.mapped, o.spw, o.owner, o.mixed);
     }
 };
 
@@ -124,9 +126,16 @@ struct wh_session {
     wh::Dec32 d32{};                      // decode-step activations: residual, planes, split-K scratch (one allocation: devmem.h carve_session_d32)
     wh::SeqState* seq = nullptr;
     wh::SeqState* seq_host = nullptr;     // pinned
+    // per option class (option_mix.h), at fixed addresses so that captured step graphs stay valid: [kMaxOptionClasses] | [kMaxOptionClasses][kMaxSuppress] |
+    // [kMaxOptionClasses][option_mask_stride(V)].  Every pass but a mixed one reads and writes entry 0 only - the tables it has always had
     wh::SamplerCfg* cfg_dev = nullptr;
     int* suppress_dev = nullptr;
-    unsigned char* sup_mask_dev = nullptr;   // [V] SuppressTokensFilter byte mask (fused greedy sampler)
+    unsigned char* sup_mask_dev = nullptr;   // SuppressTokensFilter byte masks (fused greedy sampler)
+    // option mixing (wh_session_set_option_mixing): 0 = off, 1 = wh_transcribe_batch_with_options groups its audios by batch key (option_mix_plan) and
+    // decodes a group's classes in one pass.  pass_mixed holds only while decode_text_impl runs a pass with classes (host.hip MixClasses; wh_decode_text_mixed works whatever the mode).
+    int option_mixing = 0;
+    bool pass_mixed = false;
+    long long mix_groups_run = 0, mix_mixed_passes = 0, mix_max_classes = 0;   // wh_session_option_mixing_stats: groups that ran mixed, passes with classes, largest class count
     float* stats = nullptr;                  // [B][kStatBlocks][8]
     bool fused_greedy = false;
     int *tok_out_dev = nullptr; float* lp_out_dev = nullptr;
@@ -170,6 +179,7 @@ struct wh_session {
     void* progress_user = nullptr;
     wh_window_hooks hooks{};                 // TranscribeTask.windowPreprocess / windowPostProcess / segmentDiscoveryCallback
     bool skip_special_in_progress = false;
+    const int32_t* skip_special_by_slot = nullptr;   // non-null while a pass runs whose slots carry options of their own: [home slot] skip_special_tokens
     int special_begin_in_progress = 1 << 30;
     // per-audio Result of the last wh_transcribe_batch* call (WhisperKit.transcribeWithOptions returns one Result per audio, WhisperKit.swift:786-790)
     std::vector<int> item_status;

@@ -2,6 +2,7 @@
 #pragma once
 #include "common.h"
 #include "launch_plan.h"
+#include "option_mix.h"
 
 #include <atomic>
 #include <mutex>
@@ -186,7 +187,17 @@ struct SeqState {
     int prompt_len;               // initialPromptIndex
     int f_rules[6];               // filter rules of the NEXT sampling step: blank, ts_active, r1_lo, r1_hi, r2_lo, r2_hi
     int rng_lane;                 // lane of the T > 0 sampler's random stream: the slot index, or the HOME slot in a compacted pass (slot_home below)
+                                  // A mixed pass (option_mix.h) keeps the slot's option class in bits 16.. of this word (seq_lane / seq_class below): the
+                                  // struct keeps its size and offsets, so every kernel of an unmixed pass - class 0, the word IS the lane - is the device
+                                  // code it was, and the class travels with the state through compact.hip and the compacted-pass slot map.
+                                  // Invariant: only the mixed instantiations split the word; every other reader (sampler_kernel) takes it whole.  So whoever
+                                  // starts an unmixed launch writes the lane alone: decode_text_impl / wh_detect_language / the step API / the beam loop
+                                  // initialise it, and wh_measure_kernels, the one caller that re-arms states a pass left behind, strips the class
 };
+constexpr int kSeqClassShift = 16;
+constexpr int seq_lane(int rng_lane) { return rng_lane & ((1 << kSeqClassShift) - 1); }
+constexpr int seq_class(int rng_lane) { return (rng_lane >> kSeqClassShift) & (kMaxOptionClasses - 1); }
+constexpr int seq_pack_lane(int lane, int cls) { return lane | (cls << kSeqClassShift); }
 
 struct DecodeBuffers {
     int batch, max_batch, d, n_head, n_layer, n_vocab;
@@ -220,6 +231,7 @@ struct DecodeBuffers {
     const struct Xabs* xabs; // non-null: weight-absorbed cross-attention over the encoder output (xabs.hip) instead of the cross K / V stream
     const int* slot_home;    // null, or [batch] (device): a compacted pass (launch_plan.h compact_pass_plan) - slot b attends over the encoder output / cross
                              // K / V rows of slot slot_home[b] and writes that slot's alignment rows; everything else is indexed by b
+    int mixed;               // 1: a mixed pass (launch_decoder_step below).  Host-side only
     int owner_slots;         // 0, or the slot count self_owner's entries are clamped to instead of `batch`: a pass that narrowed (compact.hip) reads history
                              // rows from the caches of slots beyond its present width.  Host-side only: the kernels' arguments keep their layout
 };
@@ -273,7 +285,9 @@ struct P32Args {
     int prof_kind;
     unsigned long long* dbg;     // WH_DBG=1: 8 wall-clock stamps per workgroup (tools/probe_dec32.py)
 };
-void launch_dec32_proj(int mode, const P32Args& a, int n_bt, hipStream_t st);
+// mixed (P32_LOGITS with the fused statistics only): a.sup_mask holds one mask per option class, option_mask_stride(N) bytes apart, and every slot
+// reads the mask of its class - dec32_proj_kernel<P32_LOGITS_MIXED, ...>; false: the instantiations that have always run
+void launch_dec32_proj(int mode, const P32Args& a, int n_bt, hipStream_t st, bool mixed = false);
 void launch_dec32_embed(const f16* emb, const float* pos, const SeqState* seq, int batch, int d, int n_vocab, int n_bt, float* x,
                         const float* gamma_next, f16* zhi, f16* zlo, float2* stat, hipStream_t st);
 // model-load helpers: re-tile W[N][K] -> out[ceil(N/32)][K/16][64][8]; g[n] = sum_k W[n][k] gamma[k], c[n] = sum_k W[n][k] beta[k] + bias[n] (f64 sums)
@@ -283,6 +297,7 @@ void dec32_fold_vectors(const f16* W, int N, int K, const float* gamma, const fl
 // ---------------------------------------------------------------------------------------------- absorbed cross-attention (xabs.hip)
 constexpr int kXabsMaxSlotsPerWorkgroup = 16;   // slots one xabs_attn workgroup streams one after the other (wh_session_options)
 constexpr int kMaxSessionSlots = 256;    // windows one session decodes in lock-step (eight 32-slot batch tiles of the decoder projections)
+static_assert((kMaxOptionClasses & (kMaxOptionClasses - 1)) == 0 && kMaxSessionSlots <= (1 << kSeqClassShift), "SeqState.rng_lane: lane | class");
 constexpr int kXabsAutoMinSlots = 28;   // wh_session_create picks the absorbed path from this many slots (WH_XABS_MIN_SLOTS overrides): measured large-v3,
                                         // one stream, ms per decoder step with 24-bit K / V rows vs absorbed (4 splits): 16 slots 3.27 / 3.91, 24 slots 3.88 / 4.00, 28 slots
                                         // 4.17 / 4.05, 32 slots 4.40 / 4.09 (profiles/r05h_*, r05a_*)
@@ -331,9 +346,12 @@ void launch_xabs_attn(const XabsArgs& a, hipStream_t st);
 void launch_xabs_vup(const XabsArgs& a, int n_bt, hipStream_t st);
 
 // one decoder forward + (optionally) fused filter/sample/state-advance for all slots
+// db.mixed (a mixed pass, option_mix.h): cfg_dev / suppress_dev / db.sup_mask are the session's per-class tables [kMaxOptionClasses] /
+// [kMaxOptionClasses][kMaxSuppress] / [kMaxOptionClasses][option_mask_stride(V)] and every slot reads the entry of its class (seq_class) - the
+// *_mixed instantiations; otherwise entry 0 through the instantiations that have always run
 void launch_decoder_step(const DecodeBuffers& db, const SamplerCfg* cfg_dev, const int* suppress_dev, bool sample, hipStream_t st);
 // filter rules of the first sampling step of a decodeText call (later steps: computed by the sampler itself)
-void launch_rules_init(const SamplerCfg* cfg_dev, SeqState* seq, int batch, hipStream_t st);
+void launch_rules_init(const SamplerCfg* cfg_dev, SeqState* seq, int batch, hipStream_t st, bool mixed = false);
 // in-pass compaction (compact.hip): the decode state of a narrowing pass moves through a home-indexed array [n_slots].  park: seq_home[home[i]] = seq[i]
 // for the active slots i < width (home null: i); gather: seq[i] = seq_home[home[i]] where live[i], an inactive zero state elsewhere.
 void launch_seq_park(const SeqState* seq, SeqState* seq_home, const int* home, int width, int n_slots, hipStream_t st);

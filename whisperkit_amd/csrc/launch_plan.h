@@ -24,7 +24,8 @@ enum GemmEpi {
 
 // ---------------------------------------------------------------------------------------------- decoder projections (decoder32.hip)
 constexpr int kD32PartFloats = 2 * 1024 * 1024;   // per batch tile: row tiles x K splits x 1024 <= 2 M floats
-enum { P32_QKV = 0, P32_Q = 1, P32_RESID = 2, P32_FC1 = 3, P32_LOGITS = 4 };
+enum { P32_QKV = 0, P32_Q = 1, P32_RESID = 2, P32_FC1 = 3, P32_LOGITS = 4,
+       P32_LOGITS_MIXED = 5 };      // kernel instantiation only (decoder32.hip): P32_LOGITS with a suppress mask per option class; planned and launched as P32_LOGITS
 
 // ---------------------------------------------------------------------------------------------- absorbed cross-attention (xabs.hip)
 constexpr int kXabsSplits = 4;      // most key splits per slot (buffer sizes); a session uses Xabs::n_split of them, fixed at creation
