@@ -129,6 +129,20 @@ public final class HIPSession {
         }
     }
 
+    /// WhisperKit.transcribe(audioArray:) with chunkingStrategy .vad (Core/WhisperKit.swift:867-931) over audio that already lives on the
+    /// device (a `wh_device_audio` from wh_audio_loader_load_device or wh_device_audio_upload; opt-in): the VAD reads the samples there and
+    /// every window is copied device to device.  The results equal the array call's.  Returns (seek offset in samples, transcription) per
+    /// chunk that succeeded; the handles are owned by the caller (wh_transcription_free), the audio stays the caller's (wh_device_audio_free).
+    public func transcribeChunked(deviceAudio: OpaquePointer, options: wh_decoding_options, specialTokens: wh_special_tokens) throws -> [(Int, OpaquePointer)] {
+        var o = options, st = specialTokens
+        let cap = max(4, Int(wh_device_audio_samples(deviceAudio)) / 16000 + 4)
+        var outs = [OpaquePointer?](repeating: nil, count: cap)
+        var seeks = [Int32](repeating: 0, count: cap)
+        var n: Int32 = 0
+        try check(wh_transcribe_chunked_device(handle, deviceAudio, &o, &st, &outs, Int32(cap), &seeks, &n))
+        return (0..<Int(n)).map { (Int(seeks[$0]), outs[$0]!) }
+    }
+
     final class HookBox {
         var pre: ((Int, UnsafeBufferPointer<Float>, Int, Int) -> Void)?
         var post: ((Int, Int, Int, OpaquePointer, Int, Int) -> Int?)?      // returns how many of the window's segments to keep (nil = all)

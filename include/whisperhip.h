@@ -634,6 +634,18 @@ const char* wh_session_item_error(const wh_session* s, int audio_index);
  * skipped as in updateSeekOffsetsForResults (`case .failure`: logged, not returned): *n_out counts the chunks that succeeded. */
 int wh_transcribe_chunked(wh_session* s, const float* pcm_host, int n_samples, const wh_decoding_options* opt,
                           const wh_special_tokens* st, wh_transcription** out, int capacity, int32_t* seek_offsets_out, int* n_out);
+/* WhisperKit.transcribeWithOptions(audioArrays:decodeOptionsArray:) (Core/WhisperKit.swift:716-812) over device audios: the contract and
+ * the results of wh_transcribe_batch_with_options (option mixing, compacted passes, device word alignment and beam search included - all
+ * of them sit below the source of a window); every window is copied device to device.  A window_preprocess hook receives a host copy of
+ * its window (counted in the audio's d2h_bytes).  An audio on another device than the session's: WH_ERR_INVALID_ARGUMENT. */
+struct wh_device_audio;
+int wh_transcribe_device_batch_with_options(wh_session* s, const struct wh_device_audio* const* audios, int n_audio,
+                                            const wh_decoding_options* const* opts /* [n_audio] or NULL */, const wh_special_tokens* st,
+                                            wh_transcription** out /* [n_audio] */, int32_t* statuses /* [n_audio] or NULL */);
+/* WhisperKit.transcribe(audioArray:) with chunkingStrategy .vad (Core/WhisperKit.swift:867-931) over a device audio: the contract and the
+ * results of wh_transcribe_chunked, with wh_vad_chunk_all_device in place of the host chunker. */
+int wh_transcribe_chunked_device(wh_session* s, struct wh_device_audio* a, const wh_decoding_options* opt, const wh_special_tokens* st,
+                                 wh_transcription** out, int capacity, int32_t* seek_offsets_out, int* n_out);
 void wh_transcription_free(wh_transcription* t);
 int wh_transcription_n_segments(const wh_transcription* t);
 int wh_transcription_segment(const wh_transcription* t, int i, wh_segment* out);
@@ -771,6 +783,36 @@ int wh_audio_loader_stats(const wh_audio_loader* l, int64_t* kernel_launches, in
  * HIP events), [5] copy from pinned memory into the result (tools/audio_ingest_time.py) */
 int wh_audio_loader_stage_seconds(const wh_audio_loader* l, double* seconds6);
 
+/* ---- device-resident audio (opt-in; csrc/vad.hip, csrc/audio.hip) -------------------------------------
+ * 16 kHz mono float32 that lives on HIP device `device`: the audioArray of WhisperKit.transcribe(audioArray:) (Core/WhisperKit.swift:867-931)
+ * kept where the session reads it.  A loader writes its result into a handle instead of downloading it, the energy VAD reads the samples
+ * there (wh_vad_*_device below), and wh_transcribe_device_batch_with_options / wh_transcribe_chunked_device take their windows from it
+ * device to device: from a file to a TranscriptionResult only the file's bytes and the result touch host memory.  Every result equals the
+ * host path's bit for bit.  A handle owns its samples and one stream (never the default stream); a returned handle is complete - no caller
+ * needs an event.  One handle serves one host thread at a time.  The host entry points stay the default. */
+typedef struct wh_device_audio wh_device_audio;
+/* AudioProcessor.loadAudio(fromPath:channelMode:startTime:endTime:maxReadFrameSize:) (:229-300): the arguments, the errors and the messages
+ * of wh_audio_loader_load; the samples equal wh_load_audio's bit for bit and are written by the loader's kernels into the handle's buffer -
+ * nothing is downloaded (the loader's d2h_bytes does not move).  A 16 kHz mono file is converted on the host and uploaded once. */
+int wh_audio_loader_load_device(wh_audio_loader* l, const char* path, int channel_mode, const int32_t* channel_indices, int n_channel_indices,
+                                double start_time, double end_time, int max_read_frame_size, wh_device_audio** out);
+/* AudioProcessor.loadAudio(at:channelMode:) (:352-379): the contract of wh_audio_loader_load_batch with out[i] a handle or NULL - order
+ * kept, a path fails alone with its status and its wh_audio_loader_item_error message, the next file is read while the previous one's
+ * kernels run. */
+int wh_audio_loader_load_batch_device(wh_audio_loader* l, const char* const* paths, int n_paths, int channel_mode, const int32_t* channel_indices,
+                                      int n_channel_indices, wh_device_audio** out /* [n_paths] */, int32_t* statuses /* [n_paths] */);
+/* n samples of host memory as a device audio (the audioArray a caller already holds); n == 0 gives an empty audio */
+int wh_device_audio_upload(int device, const float* pcm_host, int n, wh_device_audio** out);
+/* samples [offset, offset + n) back to the host; WH_ERR_INVALID_ARGUMENT for a range outside the audio */
+int wh_device_audio_download(const wh_device_audio* a, int offset, int n, float* out_host);
+int wh_device_audio_samples(const wh_device_audio* a);          /* audioArray.count; -1 for NULL */
+int wh_device_audio_device(const wh_device_audio* a);           /* the HIP device the samples live on; -1 for NULL */
+const float* wh_device_audio_data(const wh_device_audio* a);    /* the device pointer wh_set_audio_device takes (NULL for an empty audio) */
+/* since creation: launches of the frame-energy kernel, bytes copied device -> host on behalf of this audio (frame sums, downloads, windows
+ * fetched for a window_preprocess hook); any pointer may be NULL */
+int wh_device_audio_counters(const wh_device_audio* a, int64_t* vad_launches, int64_t* d2h_bytes);
+void wh_device_audio_free(wh_device_audio* a);
+
 /* ---- host utilities restated from the reference -------------------------------------------------- */
 float wh_compression_ratio(const int32_t* tokens, int n);          /* TextUtilities.compressionRatio, Utilities/TextUtilities.swift:14-30 */
 float wh_compression_ratio_text(const char* utf8, int nbytes);      /* TextUtilities.compressionRatio(of: String), :33-52 */
@@ -800,6 +842,24 @@ int wh_vad_voice_activity(const float* pcm, int n, int frame_length_samples, int
 /* VADAudioChunker.chunkAll (Core/Audio/AudioChunker.swift:66-107); returns number of chunks */
 int wh_vad_chunk_all(const float* pcm, int n, int max_chunk_length, const wh_decoding_options* opt,
                      int32_t* chunk_start, int32_t* chunk_end, int capacity);
+/* The per-frame sums of squares EnergyVAD.voiceActivity (Core/Audio/EnergyVAD.swift:41-57) thresholds: out[i] = sum of pcm[k]^2 over frame
+ * i, accumulated in double in index order - the loop of wh_vad_voice_activity, which compares (float)sqrt(out[i] / count) with the threshold.
+ * The frame count / capacity convention of wh_vad_voice_activity (out == NULL returns the count, -count when it exceeds the capacity, -1 for
+ * an invalid argument). */
+int wh_vad_frame_energy(const float* pcm, int n, int frame_length_samples, int frame_overlap_samples, double* out, int capacity);
+/* The same over samples [offset, offset + n) of a device audio, one lane per frame (csrc/vad.hip): the sums equal wh_vad_frame_energy's bit
+ * for bit.  -1 also for a range outside the audio.  n == 0 launches nothing. */
+int wh_vad_frame_energy_device(wh_device_audio* a, int offset, int n, int frame_length_samples, int frame_overlap_samples,
+                               double* out_host, int capacity);
+/* EnergyVAD.voiceActivity (Core/Audio/EnergyVAD.swift:41-57) over samples [offset, offset + n) of a device audio: the device returns the
+ * frame sums, the host takes wh_vad_voice_activity's square root, division and comparison - the same decision for every frame. */
+int wh_vad_voice_activity_device(wh_device_audio* a, int offset, int n, int frame_length_samples, int frame_overlap_samples,
+                                 float energy_threshold, uint8_t* out_host, int capacity);
+/* VADAudioChunker.chunkAll (Core/Audio/AudioChunker.swift:66-107) over a device audio: the chunks of wh_vad_chunk_all on the same samples,
+ * index for index, and its -1 for a range that starts outside the samples.  At most one launch per clip (when every range lies on the
+ * clip's frame grid) or per chunk. */
+int wh_vad_chunk_all_device(wh_device_audio* a, int max_chunk_length, const wh_decoding_options* opt,
+                            int32_t* chunk_start, int32_t* chunk_end, int capacity);
 
 /* ---- multi-GPU: chunk partition + result gather across one-process-per-GPU ranks ------------------------------------
  * The reference fans independent audio arrays out over a TaskGroup sharing the model objects (Core/WhisperKit.swift:735-812)

@@ -211,6 +211,8 @@ SYMBOLS = {
     "wh_transcribe_batch_with_options": (I, [VP, PVP, PI32, I, C.POINTER(POPT), PST, PVP, PI32]),
     "wh_session_item_status": (I, [VP, I]), "wh_session_item_error": (C.c_char_p, [VP, I]),
     "wh_transcribe_chunked": (I, [VP, VP, I, POPT, PST, PVP, I, PI32, C.POINTER(I)]),
+    "wh_transcribe_device_batch_with_options": (I, [VP, PVP, I, C.POINTER(POPT), PST, PVP, PI32]),
+    "wh_transcribe_chunked_device": (I, [VP, VP, POPT, PST, PVP, I, PI32, C.POINTER(I)]),
     "wh_transcription_free": (None, [VP]),
     "wh_transcription_n_segments": (I, [VP]),
     "wh_transcription_segment": (I, [VP, I, C.POINTER(WhSegment)]),
@@ -269,6 +271,16 @@ SYMBOLS = {
     "wh_audio_loader_item_error": (C.c_char_p, [VP, I]),
     "wh_audio_loader_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "wh_audio_loader_stage_seconds": (I, [VP, C.POINTER(C.c_double)]),
+    # device-resident audio (csrc/vad.hip, csrc/audio.hip)
+    "wh_audio_loader_load_device": (I, [VP, C.c_char_p, I, PI32, I, C.c_double, C.c_double, I, PVP]),
+    "wh_audio_loader_load_batch_device": (I, [VP, C.POINTER(C.c_char_p), I, I, PI32, I, PVP, PI32]),
+    "wh_device_audio_upload": (I, [I, PF, I, PVP]),
+    "wh_device_audio_download": (I, [VP, I, I, PF]),
+    "wh_device_audio_samples": (I, [VP]),
+    "wh_device_audio_device": (I, [VP]),
+    "wh_device_audio_data": (VP, [VP]),
+    "wh_device_audio_counters": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "wh_device_audio_free": (None, [VP]),
     "wh_compression_ratio": (F, [PI32, I]),
     "wh_compression_ratio_text": (F, [C.c_char_p, I]),
     "wh_trimming_special_token_characters": (I, [C.c_char_p, C.c_char_p, I]),
@@ -279,6 +291,10 @@ SYMBOLS = {
     "wh_prepare_seek_clips": (I, [POPT, I, PI32, PI32, I]),
     "wh_vad_voice_activity": (I, [PF, I, I, I, F, PU8, I]),
     "wh_vad_chunk_all": (I, [PF, I, I, POPT, PI32, PI32, I]),
+    "wh_vad_frame_energy": (I, [PF, I, I, I, C.POINTER(C.c_double), I]),
+    "wh_vad_frame_energy_device": (I, [VP, I, I, I, I, C.POINTER(C.c_double), I]),
+    "wh_vad_voice_activity_device": (I, [VP, I, I, I, I, F, PU8, I]),
+    "wh_vad_chunk_all_device": (I, [VP, I, POPT, PI32, PI32, I]),
     "wh_comm_unique_id": (I, [I, C.c_char_p, PU8]),
     "wh_comm_create": (I, [I, PU8, I, I, I, PVP]),
     "wh_comm_destroy": (None, [VP]),

@@ -1026,9 +1026,15 @@ class Session:
         if len(decodeOptionsArray) != n:
             raise WhisperError(9, "The number of audio arrays and decoding options must be balanced.")
         st = specialTokens if specialTokens is not None else self.model.specialTokens
-        arrs = [np.ascontiguousarray(a, dtype=np.float32) for a in audioArrays]
         keep = [(o or DecodingOptions()).to_c() for o in decodeOptionsArray]        # keeps the option structs and their arrays alive
         optp = (L.POPT * n)(*[C.pointer(o) for o in keep])
+        if _device_items(audioArrays, "transcribeWithOptions"):                     # DeviceAudio items: windows go device to device
+            hs = (C.c_void_p * n)(*[a._h for a in audioArrays])
+            outs = (C.c_void_p * n)()
+            stat = (C.c_int32 * n)()
+            self._guarded(self.lib.wh_transcribe_device_batch_with_options, self.handle, hs, n, optp, C.byref(st), outs, stat)
+            return [_collect(outs[i]) if stat[i] == 0 else WhisperError(int(stat[i]), self.lib.wh_session_item_error(self.handle, i).decode()) for i in range(n)]
+        arrs = [np.ascontiguousarray(a, dtype=np.float32) for a in audioArrays]
         ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in arrs])
         lens = (C.c_int32 * n)(*[len(a) for a in arrs])
         outs = (C.c_void_p * n)()
@@ -1058,6 +1064,13 @@ class Session:
         [(seekOffsetSamples, TranscriptionResult)] per VAD chunk, segment / word times already shifted to the full audio."""
         st = specialTokens if specialTokens is not None else self.model.specialTokens
         o = (options or DecodingOptions()).to_c()
+        if isinstance(audioArray, DeviceAudio):                                     # the VAD and the windows read the samples on the device
+            cap = max(4, audioArray.numSamples // 16000 + 4)
+            outs = (C.c_void_p * cap)()
+            seeks = (C.c_int32 * cap)()
+            n = C.c_int()
+            self._guarded(self.lib.wh_transcribe_chunked_device, self.handle, audioArray._h, C.byref(o), C.byref(st), outs, cap, seeks, C.byref(n))
+            return [(int(seeks[i]), _collect(outs[i])) for i in range(n.value)]
         a = np.ascontiguousarray(audioArray, dtype=np.float32)
         cap = max(4, len(a) // 16000 + 4)
         outs = (C.c_void_p * cap)()
@@ -1162,7 +1175,37 @@ def prepareSeekClips(options: DecodingOptions, contentFrames: int) -> List[Tuple
     return [(cs[i], ce[i]) for i in range(n)]
 
 
+def frameEnergy(audio, frameLengthSamples: int = 1600, frameOverlapSamples: int = 0) -> np.ndarray:
+    """The per-frame sums of squares (float64) that voiceActivity thresholds (wh_vad_frame_energy): one double accumulator per frame, samples
+    in index order.  `audio`: an array, or a DeviceAudio - then the sums come from the device (wh_vad_frame_energy_device), bit for bit."""
+    lib = L.load()
+    if isinstance(audio, DeviceAudio):
+        n = lib.wh_vad_frame_energy_device(audio._h, 0, audio.numSamples, frameLengthSamples, frameOverlapSamples, None, 0)
+    else:
+        a = np.ascontiguousarray(audio, dtype=np.float32)
+        n = lib.wh_vad_frame_energy(a.ctypes.data_as(L.PF), len(a), frameLengthSamples, frameOverlapSamples, None, 0)
+    if n < 0:
+        raise WhisperError(4, "frameEnergy failed")
+    out = np.zeros(n, np.float64)
+    if n > 0:
+        p = out.ctypes.data_as(C.POINTER(C.c_double))
+        got = (lib.wh_vad_frame_energy_device(audio._h, 0, audio.numSamples, frameLengthSamples, frameOverlapSamples, p, n) if isinstance(audio, DeviceAudio)
+               else lib.wh_vad_frame_energy(a.ctypes.data_as(L.PF), len(a), frameLengthSamples, frameOverlapSamples, p, n))
+        if got != n:
+            raise WhisperError(4, "frameEnergy failed")
+    return out
+
+
 def voiceActivity(audio, frameLengthSamples: int = 1600, frameOverlapSamples: int = 0, energyThreshold: float = 0.02) -> List[bool]:
+    if isinstance(audio, DeviceAudio):
+        lib = L.load()
+        n = lib.wh_vad_voice_activity_device(audio._h, 0, audio.numSamples, frameLengthSamples, frameOverlapSamples, energyThreshold, None, 0)
+        if n <= 0:
+            return []
+        out = (C.c_uint8 * n)()
+        if lib.wh_vad_voice_activity_device(audio._h, 0, audio.numSamples, frameLengthSamples, frameOverlapSamples, energyThreshold, out, n) != n:
+            raise WhisperError(4, "voiceActivity failed")
+        return [bool(v) for v in out]
     a = np.ascontiguousarray(audio, dtype=np.float32)
     lib = L.load()
     n = lib.wh_vad_voice_activity(a.ctypes.data_as(L.PF), len(a), frameLengthSamples, frameOverlapSamples, energyThreshold, None, 0)
@@ -1174,6 +1217,14 @@ def voiceActivity(audio, frameLengthSamples: int = 1600, frameOverlapSamples: in
 
 
 def vadChunkAll(audio, maxChunkLength: int = L.WINDOW_SAMPLES, options: Optional[DecodingOptions] = None):
+    if isinstance(audio, DeviceAudio):
+        o = (options or DecodingOptions()).to_c()
+        cap = max(4, audio.numSamples // 16000 + 4)
+        cs, ce = (C.c_int32 * cap)(), (C.c_int32 * cap)()
+        n = L.load().wh_vad_chunk_all_device(audio._h, maxChunkLength, C.byref(o), cs, ce, cap)
+        if n < 0:
+            raise WhisperError(4, "vadChunkAll failed")
+        return [(cs[i], ce[i]) for i in range(n)]
     a = np.ascontiguousarray(audio, dtype=np.float32)
     o = (options or DecodingOptions()).to_c()
     cap = max(4, len(a) // 16000 + 4)
@@ -1297,6 +1348,71 @@ def loadAudio(fromPath: str, channelMode: str = "sumChannels", channels: Optiona
     return out
 
 
+class DeviceAudio:
+    """16 kHz mono float32 that lives on the device (opt-in; include/whisperhip.h wh_device_audio_*, csrc/vad.hip): what
+    AudioLoader.loadAudioDevice returns and frameEnergy / voiceActivity / vadChunkAll / Session.transcribeWithOptions / Session.transcribeChunked
+    accept in place of an array - with the array's results, bit for bit.  Owns its device memory; `close()` (or the context manager) gives it
+    back.  Use it from one thread at a time."""
+
+    def __init__(self, handle):
+        self.lib = L.load()
+        self._h = handle if isinstance(handle, C.c_void_p) else C.c_void_p(handle)
+        self._finalizer = weakref.finalize(self, self.lib.wh_device_audio_free, self._h)
+
+    @classmethod
+    def fromArray(cls, array, device: int = 0) -> "DeviceAudio":
+        a = np.ascontiguousarray(array, dtype=np.float32)
+        h = C.c_void_p()
+        _check(L.load().wh_device_audio_upload(int(device), a.ctypes.data_as(L.PF), len(a), C.byref(h)))
+        return cls(h)
+
+    def close(self):
+        self._finalizer()
+        self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __len__(self):
+        return self.numSamples
+
+    @property
+    def numSamples(self) -> int:
+        return int(self.lib.wh_device_audio_samples(self._h))
+
+    @property
+    def device(self) -> int:
+        return int(self.lib.wh_device_audio_device(self._h))
+
+    @property
+    def devicePointer(self) -> Optional[int]:
+        """the pointer Session.padOrTrimDevice / wh_set_audio_device take (None for an empty audio)"""
+        return self.lib.wh_device_audio_data(self._h)
+
+    def download(self, offset: int = 0, count: Optional[int] = None) -> np.ndarray:
+        n = self.numSamples - offset if count is None else count
+        out = np.empty(max(n, 0), np.float32)
+        _check(self.lib.wh_device_audio_download(self._h, offset, n, out.ctypes.data_as(L.PF)))
+        return out
+
+    def counters(self) -> dict:
+        """since creation: launches of the frame-energy kernel, bytes copied device -> host on behalf of this audio"""
+        k, d = C.c_int64(), C.c_int64()
+        _check(self.lib.wh_device_audio_counters(self._h, C.byref(k), C.byref(d)))
+        return {"vadLaunches": int(k.value), "d2hBytes": int(d.value)}
+
+
+def _device_items(items, who: str) -> bool:
+    """True when every item is a DeviceAudio, False when none is; a mixture is a TypeError"""
+    n_dev = sum(isinstance(a, DeviceAudio) for a in items)
+    if n_dev not in (0, len(items)):
+        raise TypeError(f"{who}: arrays and DeviceAudio items cannot be mixed in one call")
+    return n_dev > 0
+
+
 class AudioLoader:
     """Audio ingest on the device (opt-in; include/whisperhip.h wh_audio_loader_*, csrc/audio.hip): sample decode, mono mix and resampling of
     WAV input run as HIP kernels, the host only reads the file and parses its header.  Every method returns what the free function of the
@@ -1349,6 +1465,27 @@ class AudioLoader:
             out.append(np.ctypeslib.as_array(pcm[i], shape=(max(counts[i], 1),))[:counts[i]].copy())
             self.lib.wh_audio_free(pcm[i])
         return out
+
+    def loadAudioDevice(self, fromPath: str, channelMode: str = "sumChannels", channels: Optional[Sequence[int]] = None, startTime: float = 0.0,
+                        endTime: Optional[float] = None, maxReadFrameSize: int = 0) -> DeviceAudio:
+        """loadAudio with the result left on the device: the samples of loadAudio, bit for bit, and nothing is downloaded."""
+        idx = None if channels is None else np.ascontiguousarray(list(channels), dtype=np.int32)
+        h = C.c_void_p()
+        _check(self.lib.wh_audio_loader_load_device(self.h, fromPath.encode(), 0 if channelMode == "specificChannel" else 1,
+                                                    None if idx is None else idx.ctypes.data_as(L.PI32), 0 if idx is None else len(idx), startTime,
+                                                    float("nan") if endTime is None else endTime, maxReadFrameSize, C.byref(h)))
+        return DeviceAudio(h)
+
+    def loadAudiosDevice(self, paths: Sequence[str], channelMode: str = "sumChannels", channels: Optional[Sequence[int]] = None) -> list:
+        """loadAudios with the results left on the device: one entry per path, in order - a DeviceAudio, or the WhisperError of that path."""
+        n = len(paths)
+        idx = None if channels is None else np.ascontiguousarray(list(channels), dtype=np.int32)
+        cpaths = (C.c_char_p * max(n, 1))(*[p.encode() for p in paths])
+        hs, statuses = (C.c_void_p * max(n, 1))(), (C.c_int32 * max(n, 1))()
+        _check(self.lib.wh_audio_loader_load_batch_device(self.h, cpaths, n, 0 if channelMode == "specificChannel" else 1,
+                                                          None if idx is None else idx.ctypes.data_as(L.PI32), 0 if idx is None else len(idx), hs, statuses))
+        return [DeviceAudio(hs[i]) if statuses[i] == 0 else WhisperError(statuses[i], self.lib.wh_audio_loader_item_error(self.h, i).decode())
+                for i in range(n)]
 
     def resampleAudio(self, audio: np.ndarray, fromSampleRate: float, toSampleRate: float = 16000.0) -> np.ndarray:
         a = np.ascontiguousarray(audio, dtype=np.float32)

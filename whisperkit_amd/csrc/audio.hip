@@ -180,6 +180,7 @@ struct Group {
     const double* table = nullptr;
     size_t n_out = 0;
     float* dst = nullptr;
+    float* dev_dst = nullptr;                     // set: the resample launch writes its n_out samples here on the device and nothing comes down
 };
 
 }  // namespace
@@ -277,7 +278,7 @@ int issue(wh_audio_loader* l, const Group& g) {
     const size_t n_frames = (size_t)g.mix.n_frames;
     if (int r = grow(l, s.raw_dev, s.raw_cap, g.raw_bytes, false, &s.raw_pin)) return r;
     if (int r = grow(l, s.mixed, s.mixed_cap, n_frames, false)) return r;
-    if (int r = grow(l, s.out_dev, s.out_cap, g.n_out, false, &s.out_pin)) return r;
+    if (!g.dev_dst) if (int r = grow(l, s.out_dev, s.out_cap, g.n_out, false, &s.out_pin)) return r;
     const size_t n_chunks = g.sum ? (size_t)((g.mix.n_frames + g.mix.chunk_frames - 1) / g.mix.chunk_frames) : 0;
     if (int r = grow(l, s.peaks, s.peaks_cap, 2 * n_chunks, false)) return r;
 
@@ -309,19 +310,19 @@ int issue(wh_audio_loader* l, const Group& g) {
     if (g.resample) {
         const unsigned bx = (unsigned)((g.rs.n_out_full + kAudioThreads - 1) / kAudioThreads);
         if (bx && g.n_out) {
-            audio_resample_kernel<<<dim3(bx, (unsigned)g.rs.n_chunks), kAudioThreads, 0, l->run>>>(s.mixed, g.table, s.out_dev, g.rs);
+            audio_resample_kernel<<<dim3(bx, (unsigned)g.rs.n_chunks), kAudioThreads, 0, l->run>>>(s.mixed, g.table, g.dev_dst ? g.dev_dst : s.out_dev, g.rs);
             AL_HIP(hipGetLastError());
             ++l->launches;
         }
         result = s.out_dev;
     }
     AL_HIP(hipEventRecord(s.k1, l->run));
-    if (g.n_out) {
+    if (g.n_out && !g.dev_dst) {
         AL_HIP(hipMemcpyAsync(s.out_pin, result, g.n_out * sizeof(float), hipMemcpyDeviceToHost, l->run));
         l->d2h += (long long)(g.n_out * sizeof(float));
     }
     AL_HIP(hipEventRecord(s.done, l->run));
-    s.busy = true; s.dst = g.dst; s.n_out = g.n_out;
+    s.busy = true; s.dst = g.dst; s.n_out = g.dev_dst ? 0 : g.n_out;
     return WH_OK;
 }
 
@@ -341,13 +342,26 @@ void abandon(wh_audio_loader* l) {
 
 // One opened file -> its malloc'ed 16 kHz mono result.  Groups are ISSUED here; the last ones may still be in flight when this returns
 // (the caller finishes them: wh_audio_loader_load at once, the batch after it has issued the next file's first group).
-int load_span(wh_audio_loader* l, const wa::WavSpan& w, const MixPlan& plan, int max_read_frame_size, float** pcm_out, int* n_out) {
+// dev_out set (wh_audio_loader_load_device): the result is a device audio instead - the resample launches write into its buffer, nothing comes down.
+int load_span(wh_audio_loader* l, const wa::WavSpan& w, const MixPlan& plan, int max_read_frame_size, float** pcm_out, int* n_out,
+              wh_device_audio** dev_out = nullptr) {
     const long long frames = w.frames;
     const int bps = w.bits / 8;
     if (w.rate == 16000.0 && w.channels == 1) {                 // returned as read: no launch
         float* buf = (float*)malloc(sizeof(float) * (size_t)std::max<long long>(frames, 1));
         if (!buf) return set_error(WH_ERR_LOAD_AUDIO_FAILED, "Unable to create audio buffer");
         for (long long i = 0; i < frames; ++i) buf[i] = wa::sample_at(w.format, w.bits, w.data + (size_t)i * w.block);
+        if (dev_out) {                                          // converted on the host as ever, uploaded once
+            int r = whi::device_audio_new(l->device, (int)frames, dev_out);
+            if (!r && frames > 0) {
+                hipError_t e = hipMemcpyAsync((*dev_out)->data, buf, (size_t)frames * sizeof(float), hipMemcpyHostToDevice, l->up);
+                if (e == hipSuccess) e = hipStreamSynchronize(l->up);
+                if (e != hipSuccess) { wh_device_audio_free(*dev_out); *dev_out = nullptr; r = set_error(WH_ERR_HIP, "audio loader: uploading %lld samples failed: %s", frames, hipGetErrorString(e)); }
+                else l->h2d += (long long)frames * (long long)sizeof(float);
+            }
+            free(buf);
+            return r;
+        }
         *pcm_out = buf; *n_out = (int)frames;
         return WH_OK;
     }
@@ -359,8 +373,9 @@ int load_span(wh_audio_loader* l, const wa::WavSpan& w, const MixPlan& plan, int
     const long long full_out = chunks.empty() ? 0 : chunks.front().frames == chunk ? chunks.front().n_out : 0;
     const double* table = nullptr;
     if (w.rate != 16000.0 && total > 0) { if (int r = table_for(l, w.rate, 16000.0, geo, &table)) return r; }
-    float* buf = (float*)malloc(sizeof(float) * (size_t)std::max<long long>(total, 1));
-    if (!buf) return set_error(WH_ERR_LOAD_AUDIO_FAILED, "Unable to create audio buffer");
+    float* buf = nullptr;
+    if (dev_out) { if (int r = whi::device_audio_new(l->device, (int)total, dev_out)) return r; }
+    else if (!(buf = (float*)malloc(sizeof(float) * (size_t)std::max<long long>(total, 1)))) return set_error(WH_ERR_LOAD_AUDIO_FAILED, "Unable to create audio buffer");
     // whole chunks per group under the staging budget (raw bytes, mono floats and output floats alike); at least one
     const size_t per_chunk = std::max<size_t>({(size_t)chunk * (size_t)w.block, (size_t)chunk * 4, (size_t)std::max<long long>(full_out, 0) * 4, (size_t)1});
     const size_t cpg = std::min<size_t>(std::max<size_t>(kAudioStageBytes / per_chunk, 1), (size_t)kAudioMaxGroupChunks);
@@ -379,9 +394,10 @@ int load_span(wh_audio_loader* l, const wa::WavSpan& w, const MixPlan& plan, int
         g.rs = ResampleArgs{chunk, n, c1 - c0 > 1 ? chunks[c0].n_out : chunks[c1 - 1].n_out, chunks[c1 - 1].n_out, (int)(c1 - c0), w.rate == 16000.0, geo.ratio, geo.half};
         g.table = table;
         g.n_out = (size_t)(chunks[c1 - 1].out_off + chunks[c1 - 1].n_out - chunks[c0].out_off);
-        g.dst = buf + chunks[c0].out_off;
-        if (int r = issue(l, g)) { abandon(l); free(buf); return r; }
+        if (dev_out) g.dev_dst = (*dev_out)->data + chunks[c0].out_off; else g.dst = buf + chunks[c0].out_off;
+        if (int r = issue(l, g)) { abandon(l); free(buf); if (dev_out) { wh_device_audio_free(*dev_out); *dev_out = nullptr; } return r; }
     }
+    if (dev_out) return WH_OK;
     *pcm_out = buf; *n_out = (int)total;
     return WH_OK;
 }
@@ -546,6 +562,66 @@ extern "C" int wh_audio_loader_load_batch(wh_audio_loader* l, const char* const*
     }
     return WH_OK;
     WH_CATCH("wh_audio_loader_load_batch")
+}
+
+extern "C" int wh_audio_loader_load_device(wh_audio_loader* l, const char* path, int channel_mode, const int32_t* channel_indices, int n_channel_indices,
+                                           double start_time, double end_time, int max_read_frame_size, wh_device_audio** out) {
+    if (!l) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_audio_loader_load_device: null loader");
+    if (!path || !out) return set_error(WH_ERR_LOAD_AUDIO_FAILED, "wh_load_audio: null argument");
+    *out = nullptr;
+    WH_TRY
+    const double t0 = now_s();
+    std::string file;
+    wa::WavSpan span;
+    if (int r = whi::open_wav(path, start_time, end_time, file, span)) return r;
+    l->stage_s[0] += now_s() - t0;
+    CHECK_LOADER(l);
+    const MixPlan plan = mix_plan(span.channels, channel_mode, channel_indices, n_channel_indices);
+    if (int r = upload_selection(l, plan.sel)) return r;
+    wh_device_audio* a = nullptr;
+    if (int r = load_span(l, span, plan, max_read_frame_size, nullptr, nullptr, &a)) return r;
+    if (int r = finish_all(l)) { abandon(l); wh_device_audio_free(a); return r; }
+    *out = a;
+    return WH_OK;
+    WH_CATCH("wh_audio_loader_load_device")
+}
+
+extern "C" int wh_audio_loader_load_batch_device(wh_audio_loader* l, const char* const* paths, int n_paths, int channel_mode, const int32_t* channel_indices,
+                                                 int n_channel_indices, wh_device_audio** out, int32_t* statuses) {
+    if (!l) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_audio_loader_load_batch_device: null loader");
+    if (n_paths < 0 || (n_paths && (!paths || !out || !statuses))) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_audio_loader_load_batch_device: null argument");
+    WH_TRY
+    CHECK_LOADER(l);
+    l->item_error.assign((size_t)n_paths, std::string());
+    for (int i = 0; i < n_paths; ++i) { out[i] = nullptr; statuses[i] = WH_OK; }
+    int fatal = WH_OK;
+    int last_channels = -1;
+    for (int i = 0; i < n_paths && !fatal; ++i) {
+        if (!paths[i]) { statuses[i] = set_error(WH_ERR_LOAD_AUDIO_FAILED, "wh_load_audio: null argument"); l->item_error[i] = wh_last_error(); continue; }
+        const double t0 = now_s();
+        std::string file;
+        wa::WavSpan span;
+        const int r = whi::open_wav(paths[i], 0.0, NAN, file, span);
+        l->stage_s[0] += now_s() - t0;
+        if (r) { statuses[i] = r; l->item_error[i] = wh_last_error(); continue; }      // this path fails alone
+        const MixPlan plan = mix_plan(span.channels, channel_mode, channel_indices, n_channel_indices);
+        if (span.channels != last_channels) {            // (as in wh_audio_loader_load_batch)
+            if (int e = finish_all(l)) { fatal = e; break; }
+            if (int e = upload_selection(l, plan.sel)) { fatal = e; break; }
+            last_channels = span.channels;
+        }
+        // the groups staged from `file` are in pinned memory when load_span returns; the last two may still run while the next file is read
+        if (int e = load_span(l, span, plan, 0, nullptr, nullptr, &out[i])) { fatal = e; break; }
+    }
+    if (!fatal) fatal = finish_all(l);
+    if (fatal) {
+        const std::string msg = wh_last_error();
+        abandon(l);
+        for (int i = 0; i < n_paths; ++i) { wh_device_audio_free(out[i]); out[i] = nullptr; }
+        return set_error(fatal, "%s", msg.c_str());
+    }
+    return WH_OK;
+    WH_CATCH("wh_audio_loader_load_batch_device")
 }
 
 extern "C" const char* wh_audio_loader_item_error(const wh_audio_loader* l, int i) {

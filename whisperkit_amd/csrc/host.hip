@@ -847,6 +847,7 @@ extern "C" int wh_find_seek_point_and_segments(const wh_decoding_result* res, co
 
 struct AudioJob {
     const float* pcm; int n;
+    const wh_device_audio* dev = nullptr;           // set: pcm points into this device audio (wh_transcribe_*device*): windows go device to device
     int index = 0;                                  // position of the audio in the caller's batch (hook argument, item status)
     const wh_decoding_options* opt = nullptr;       // this audio's options (clip timestamps are per audio; everything else is shared by its group)
     int status = WH_OK; std::string error;          // Result<[TranscriptionResult], Error> of this audio (WhisperKit.swift:786-790)
@@ -915,13 +916,23 @@ static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_
             // a window without samples: the reference slices audioArray[seek ..< seek + segmentSize], AudioProcessor.padOrTrimAudio returns nil for
             // the empty slice ("startIndex is outside the buffer size", Core/Audio/AudioProcessor.swift:151-155) and the task throws
             // transcriptionFailed("Audio samples are nil") (Core/TranscribeTask.swift:126-129) - a clip that ends beyond the samples gets here
-            int r = j.cur_size > 0 ? wh_set_audio(s, b, j.pcm + j.cur_seek, j.cur_size)
+            int r = j.cur_size > 0 ? (j.dev ? wh_set_audio_device(s, b, j.pcm + j.cur_seek, j.cur_size) : wh_set_audio(s, b, j.pcm + j.cur_seek, j.cur_size))
                                    : set_error(WH_ERR_TRANSCRIPTION_FAILED, "audio %d: Audio samples are nil (window start %d is outside the buffer size %d)", j.index, j.cur_seek, j.n);
             if (r == WH_ERR_HIP) return r;                                 // the device is gone: every audio of the group fails
             if (r) { j.status = r; j.error = wh_last_error(); j.finished = true; continue; }
             slot_job.push_back((int)ji);
-            if (s->hooks.window_preprocess)                                // TranscribeTask.windowPreprocess (:130)
-                s->hooks.window_preprocess(s->hooks.user, j.index, j.pcm + j.cur_seek, j.cur_seek, j.cur_size);
+            if (s->hooks.window_preprocess) {                              // TranscribeTask.windowPreprocess (:130)
+                const float* win = j.pcm + j.cur_seek;
+                std::vector<float> copy;
+                if (j.dev) {                                               // the hook expects host samples: it gets a copy of its window
+                    copy.resize((size_t)j.cur_size);
+                    WH_HIP(hipMemcpyAsync(copy.data(), win, sizeof(float) * (size_t)j.cur_size, hipMemcpyDeviceToHost, s->st));
+                    WH_HIP(hipStreamSynchronize(s->st));
+                    j.dev->d2h_bytes += (long long)sizeof(float) * j.cur_size;
+                    win = copy.data();
+                }
+                s->hooks.window_preprocess(s->hooks.user, j.index, win, j.cur_seek, j.cur_size);
+            }
             j.tr->seeks.push_back(j.cur_seek);
         }
         if (slot_job.empty()) break;
@@ -1114,8 +1125,10 @@ static bool same_group_options(const wh_decoding_options& a, const wh_decoding_o
 // a group; groups run one after the other (the reference runs one TranscribeTask per audio: grouping changes the batching, not a result).
 // A failure that belongs to one audio (bad buffer, a window outside the samples) fails that audio; a failure of a group's shared state
 // (invalid option combination, a device error) fails the group's audios; the other groups still run.
+// devs: null, or (wh_transcribe_*device*) the device audio pcm[i] points into, per audio
 static int transcribe_items(wh_session* s, const float* const* pcm, const int32_t* n_samples, int n_audio, const wh_decoding_options* const* opts,
-                            const wh_decoding_options* shared, const wh_special_tokens* st, wh_transcription** out, int32_t* statuses) {
+                            const wh_decoding_options* shared, const wh_special_tokens* st, wh_transcription** out, int32_t* statuses,
+                            const wh_device_audio* const* devs = nullptr) {
     wh_decoding_options dflt;
     wh_decoding_options_default(&dflt);
     s->item_status.assign((size_t)n_audio, WH_OK);
@@ -1126,6 +1139,7 @@ static int transcribe_items(wh_session* s, const float* const* pcm, const int32_
     for (int i = 0; i < n_audio; ++i) {
         AudioJob& j = all[(size_t)i];
         j.index = i; j.pcm = pcm[i]; j.n = n_samples[i]; j.tr = nullptr;
+        j.dev = devs ? devs[i] : nullptr;
         j.opt = (opts && opts[i]) ? opts[i] : (shared ? shared : &dflt);
         out[i] = nullptr;
         if (j.n < 0 || (j.n > 0 && !j.pcm)) {
@@ -1254,6 +1268,71 @@ extern "C" int wh_transcribe_chunked(wh_session* s, const float* pcm, int n, con
     }
     *n_out = kept;
     return WH_OK;
+}
+
+// ---- the same over device audios (opt-in; vad.hip): the source of a window changes, nothing else
+static int check_device_audios(const wh_session* s, const wh_device_audio* const* audios, int n_audio, const char* who) {
+    for (int i = 0; i < n_audio; ++i)
+        if (audios[i] && audios[i]->device != s->m->device)
+            return set_error(WH_ERR_INVALID_ARGUMENT, "%s: audio %d lives on device %d, the session on device %d", who, i, audios[i]->device, s->m->device);
+    return WH_OK;
+}
+
+extern "C" int wh_transcribe_device_batch_with_options(wh_session* s, const wh_device_audio* const* audios, int n_audio, const wh_decoding_options* const* opts,
+                                                       const wh_special_tokens* st, wh_transcription** out, int32_t* statuses) {
+    CHECK_SESSION(s);
+    if (!audios || n_audio < 1 || !st || !out) return set_error(WH_ERR_TRANSCRIPTION_FAILED, "wh_transcribe_device_batch_with_options: null argument");
+    WH_TRY
+    if (int r = check_device_audios(s, audios, n_audio, "wh_transcribe_device_batch_with_options")) return r;
+    std::vector<const float*> ptrs((size_t)n_audio);
+    std::vector<int32_t> lens((size_t)n_audio);
+    for (int i = 0; i < n_audio; ++i) { ptrs[(size_t)i] = audios[i] ? audios[i]->data : nullptr; lens[(size_t)i] = audios[i] ? audios[i]->n : -1; }    // a null audio: "invalid buffer", alone
+    return transcribe_items(s, ptrs.data(), lens.data(), n_audio, opts, nullptr, st, out, statuses, audios);
+    WH_CATCH("wh_transcribe_device_batch_with_options")
+}
+
+extern "C" int wh_transcribe_chunked_device(wh_session* s, wh_device_audio* a, const wh_decoding_options* opt, const wh_special_tokens* st,
+                                            wh_transcription** out, int capacity, int32_t* seek_offsets_out, int* n_out) {
+    CHECK_SESSION(s);
+    if (!opt || !st || !out || !n_out || capacity < 1 || !a || (a->n > 0 && !a->data))
+        return set_error(WH_ERR_TRANSCRIPTION_FAILED, "wh_transcribe_chunked_device: invalid argument");
+    *n_out = 0;
+    WH_TRY
+    if (int r = check_device_audios(s, &a, 1, "wh_transcribe_chunked_device")) return r;
+    if (a->n <= kWindowSamples) {      // not chunkable (as in wh_transcribe_chunked)
+        const float* p[1] = {a->data};
+        int32_t nn[1] = {a->n};
+        int r = transcribe_items(s, p, nn, 1, nullptr, opt, st, &out[0], nullptr, &a);
+        if (r) return r;
+        if (seek_offsets_out) seek_offsets_out[0] = 0;
+        *n_out = 1;
+        return WH_OK;
+    }
+    std::vector<std::pair<int, int>> chunks;
+    const int nc = whi::vad_chunks_device(a, kWindowSamples, opt, chunks);
+    if (nc < 0) return set_error(WH_ERR_AUDIO_PROCESSING_FAILED, "wh_transcribe_chunked: startIndex is outside the buffer size");
+    if (nc > capacity) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_transcribe_chunked: %d chunks exceed the capacity %d", nc, capacity);
+    wh_decoding_options chunked = *opt;
+    chunked.clip_timestamps = nullptr;
+    chunked.n_clip_timestamps = 0;
+    std::vector<const float*> ptrs((size_t)nc);
+    std::vector<int32_t> lens((size_t)nc);
+    std::vector<const wh_device_audio*> devs((size_t)nc, a);
+    for (int i = 0; i < nc; ++i) { ptrs[(size_t)i] = a->data + chunks[(size_t)i].first; lens[(size_t)i] = chunks[(size_t)i].second - chunks[(size_t)i].first; }
+    int r = transcribe_items(s, ptrs.data(), lens.data(), nc, nullptr, &chunked, st, out, nullptr, devs.data());
+    if (r) return r;
+    int kept = 0;
+    for (int i = 0; i < nc; ++i) {
+        if (!out[i]) continue;
+        wh_transcription_apply_seek_offset(out[i], chunks[(size_t)i].first);
+        wh_transcription* t = out[i];
+        out[i] = nullptr; out[kept] = t;
+        if (seek_offsets_out) seek_offsets_out[kept] = chunks[(size_t)i].first;
+        ++kept;
+    }
+    *n_out = kept;
+    return WH_OK;
+    WH_CATCH("wh_transcribe_chunked_device")
 }
 
 extern "C" int wh_session_set_progress_callback(wh_session* s, wh_progress_fn fn, void* user) {

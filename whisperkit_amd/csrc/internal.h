@@ -186,8 +186,25 @@ struct wh_session {
     std::vector<std::string> item_error;
 };
 
+// 16 kHz mono float32 that lives on the device (opt-in; vad.hip): what wh_audio_loader_load_device / wh_device_audio_upload hand out and
+// wh_vad_*_device / wh_transcribe_*device* read.  `data` is complete when the handle is returned (the producer waited for its own work).
+struct wh_device_audio {
+    DevMem mem;                       // owns the samples and the frame-sum buffers below
+    int device = 0;
+    int n = 0;
+    float* data = nullptr;            // [n]
+    hipStream_t st = nullptr;         // the VAD launches and their copies (never the default stream)
+    double *sums_dev = nullptr, *sums_pin = nullptr; size_t sums_cap = 0;     // frame sums of one launch, grown on demand
+    long long vad_launches = 0;
+    mutable long long d2h_bytes = 0;  // frame sums, downloads, windows fetched for a window_preprocess hook
+};
+
 namespace whi {
 int set_error(int code, const char* fmt, ...);
+// a handle for n samples on `device` with its stream and an uninitialised sample buffer (vad.hip); the caller fills data[0 .. n)
+int device_audio_new(int device, int n, wh_device_audio** out);
+// the chunks of wh_vad_chunk_all_device in one pass over the audio (vad.hip); the chunk count, or -1.  May throw std::bad_alloc
+int vad_chunks_device(wh_device_audio* a, int max_chunk, const wh_decoding_options* opt, std::vector<std::pair<int, int>>& out);
 #define WH_HIP(expr)                                                                               \
     do {                                                                                           \
         hipError_t _e = (expr);                                                                    \
