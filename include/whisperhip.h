@@ -566,6 +566,52 @@ int wh_beam_rank_device(int device, int n_audio, int beam_size, int max_candidat
                         int32_t* completed, int32_t* finished_tokens, float* finished_token_logprobs, float* finished_sums,
                         int32_t* n_finished_new);
 
+/* ---- forced-transcript pass: NO REFERENCE BEHAVIOUR: openai/whisper `timing.find_alignment` semantics -------------------------
+ * The reference can only decode.  These entry points run the decoder over tokens the caller ALREADY has - scoring, and word timings for
+ * a given transcript - in one decoder launch per up to max_batch positions instead of one launch chain per position: position p of audio
+ * a is a virtual slot that embeds tokens[a][p] at position p, reads the self-attention rows of a's earlier positions from the slots that
+ * hold them and attends over a's encoder data (csrc/forced_plan.h, forced.hip).  The step kernels are the ones
+ * wh_predict_logits launches, and the logits of every position are the bits that stepping the same tokens through wh_predict_logits one
+ * position per call gives.
+ *
+ * wh_score_tokens: slots 0 .. n_audio - 1 hold the windows' encoder outputs (the caller has run the encoder and
+ * wh_prepare_decoder_inputs, as for wh_decode_text); tokens[a] is audio a's full sequence including the forced prompt.
+ * token_logprobs_out[a][i] = log p(tokens[a][i] | tokens[a][0 .. i)) for i >= 1, entry 0 is 0; best_tokens_out[a][i] /
+ * best_logprobs_out[a][i] (either may be NULL) are the argmax of the same distribution (the lowest id on ties) and its log-probability,
+ * entries 0 are -1 / 0.  All arrays hold n_tokens[a] entries.  The scores are the plain log-softmax over the whole vocabulary in fp32: NO
+ * logits filter, NO temperature - openai/whisper's convention for scoring a given text, not the decode loop's filtered `token_logprobs`.
+ * The last token of a sequence is only scored, never fed.  record_alignment != 0: the alignment rows of slots 0 .. n_audio - 1 are zeroed
+ * and rewritten by the pass (wh_get_alignment_weights / wh_alignment_paths read them as after a decode with word timestamps).  The
+ * slots' self-attention caches and decode states are overwritten.  The session's cancel flag is polled between launches.
+ * WH_ERR_INVALID_ARGUMENT, checked before the session is looked at: n_audio < 1 or beyond any session's slots, n_tokens[a] outside
+ * [0, 224], a token outside the vocabulary, a NULL pointer where one is needed; n_audio beyond THIS session's slots once it is known. */
+int wh_score_tokens(wh_session* s, int n_audio, const int32_t* const* tokens, const int32_t* n_tokens, int record_alignment,
+                    float* const* token_logprobs_out, int32_t* const* best_tokens_out, float* const* best_logprobs_out);
+/* Forced alignment of n_audio audios of at most ONE window each (an audio longer than 30 s: WH_ERR_INVALID_ARGUMENT for that audio alone;
+ * long-form alignment is out of scope).  Per audio: log-mel, encoder, the forced pass over wh_prefill_prompt(opts[a]) (the options'
+ * language token; nothing is detected) + text_tokens[a] + the end token - more than 224 tokens is that audio's error - and then the
+ * window code of wh_transcribe: a wh_decoding_result with the given tokens and the forced scores, findSeekPointAndSegments, word timings
+ * from the alignment rows the pass recorded (word_timestamps is taken as set).  wh_session_set_word_alignment (host / device DTW) and
+ * wh_session_set_alignment_postprocess apply.  opts: one per audio.  out[a]: the transcription, or NULL with status[a] (may be NULL) and
+ * wh_session_item_status / wh_session_item_error telling why.  Needs a tokenizer on the session (else WH_ERR_TOKENIZER_UNAVAILABLE) and
+ * a model with alignment heads (wh_supports_word_timestamps, else WH_ERR_INVALID_ARGUMENT) - wh_transcribe leaves the words out in both
+ * cases; here they are what was asked for. */
+int wh_align_tokens_batch(wh_session* s, const float* const* pcm_host, const int32_t* n_samples, int n_audio,
+                          const wh_decoding_options* opts /* one per audio */, const wh_special_tokens* st,
+                          const int32_t* const* text_tokens, const int32_t* n_text, wh_transcription** out, int32_t* status);
+/* Counters of the session since its creation: forced passes (wh_score_tokens calls + rounds of wh_align_tokens_batch: passes STARTED - one
+ * that is cancelled at once or has no position to run counts, with 0 launches), their decoder launches and the positions (virtual slots)
+ * those launches ran.  Any pointer may be NULL. */
+int wh_session_forced_pass_stats(const wh_session* s, int64_t* passes, int64_t* launches, int64_t* positions);
+/* Development aid: while logits_out is installed every forced pass copies each launch's logits rows to it before the next launch rewrites
+ * them - row k ([n_vocab] floats) is the k-th virtual slot of the call in plan order (launch by launch, slot by slot; forced_plan.h).
+ * A call whose rows exceed capacity_floats copies the launches that fit.  NULL removes it; the buffer must outlive the installation. */
+int wh_debug_forced_capture(wh_session* s, float* logits_out, size_t capacity_floats);
+/* Development aid: the score kernel of the forced pass alone, over n_rows (<= max_batch) caller-supplied logits rows of the model's vocabulary,
+ * row i placed where a launch leaves slot i's row: log p(targets[i]) (0 for a target outside the vocabulary), the argmax and its log-probability. */
+int wh_debug_forced_score(wh_session* s, const float* logits_rows, int n_rows, const int32_t* targets, float* logprobs_out,
+                          int32_t* best_tokens_out, float* best_logprobs_out);
+
 /* TextDecoding.detectLanguage (Core/TextDecoder.swift:420-539) */
 int wh_detect_language(wh_session* s, int batch, const wh_special_tokens* st, int32_t* language_tokens_out,
                        float* logprobs_out);

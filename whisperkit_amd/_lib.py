@@ -205,6 +205,12 @@ SYMBOLS = {
     "wh_session_word_alignment": (I, [VP]),
     "wh_alignment_paths": (I, [VP, I, PI32, PI32, PI32, PI32, I]),
     "wh_session_word_alignment_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    # forced-transcript pass (csrc/forced.hip, forced_plan.h)
+    "wh_score_tokens": (I, [VP, I, PVP, PI32, I, PVP, PVP, PVP]),
+    "wh_align_tokens_batch": (I, [VP, PVP, PI32, I, POPT, PST, PVP, PI32, PVP, PI32]),
+    "wh_session_forced_pass_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "wh_debug_forced_capture": (I, [VP, VP, C.c_size_t]),
+    "wh_debug_forced_score": (I, [VP, VP, I, PI32, PF, PI32, PF]),
     "wh_prefill_prompt": (I, [VP, POPT, PST, C.c_int32, PI32, I]),
     "wh_transcribe": (I, [VP, VP, I, POPT, PST, PVP]),
     "wh_transcribe_batch": (I, [VP, PVP, PI32, I, POPT, PST, PVP]),

@@ -141,6 +141,17 @@ class DecodingResult:
 
 
 @dataclasses.dataclass
+class TokenScores:
+    """Session.scoreTokens of one audio: tokenLogProbs[i] = log p(tokens[i] | tokens[:i]) (entry 0 is 0.0), bestTokens[i] / bestLogProbs[i] the argmax of
+    the same distribution and its log-probability (entry 0: -1 / 0.0).  Plain log-softmax of the raw logits: no logits filter, no temperature."""
+    tokenLogProbs: List[float]
+    bestTokens: List[int]
+    bestLogProbs: List[float]
+    sumLogProb: float
+    avgLogProb: float       # over the scored tokens (all but the first); 0.0 when there is none
+
+
+@dataclasses.dataclass
 class WordTiming:
     tokens: List[int]
     start: float
@@ -963,6 +974,64 @@ class Session:
         a, b = C.c_int64(), C.c_int64()
         _check(self.lib.wh_session_word_alignment_stats(self.handle, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
+
+    # ---- forced-transcript pass (no reference behaviour: openai/whisper timing.find_alignment semantics; csrc/forced_plan.h, forced.hip)
+    def scoreTokens(self, tokenLists: Sequence[Sequence[int]], recordAlignment: bool = False) -> List[TokenScores]:
+        """Per-token log-probabilities of given sequences, audio a in slot a (encoder run, prepareDecoderInputs called): every position of every
+        sequence is a virtual slot of one decoder launch per up to maxBatch positions (wh_score_tokens) instead of one launch chain per position.
+        tokenLists[a] is the full sequence including the forced prompt; its last token is scored, never fed.  recordAlignment=True rewrites the
+        alignment rows of the slots (getAlignmentWeights / alignmentPaths read them)."""
+        n = len(tokenLists)
+        toks = [np.ascontiguousarray(list(t), dtype=np.int32) for t in tokenLists]
+        lens = (C.c_int32 * n)(*[len(t) for t in toks])
+        lp = [np.zeros(max(len(t), 1), np.float32) for t in toks]
+        bt = [np.zeros(max(len(t), 1), np.int32) for t in toks]
+        bl = [np.zeros(max(len(t), 1), np.float32) for t in toks]
+        ptr = lambda arrs: (C.c_void_p * n)(*[a.ctypes.data for a in arrs])
+        self._guarded(self.lib.wh_score_tokens, self.handle, n, ptr(toks), lens, int(recordAlignment), ptr(lp), ptr(bt), ptr(bl))
+        out = []
+        for a in range(n):
+            k = len(toks[a])
+            s = float(np.sum(lp[a][1:k], dtype=np.float32)) if k > 1 else 0.0
+            out.append(TokenScores(lp[a][:k].tolist(), bt[a][:k].tolist(), bl[a][:k].tolist(), s, s / (k - 1) if k > 1 else 0.0))
+        return out
+
+    def alignTokens(self, audioArrays: Sequence[np.ndarray], tokenLists: Sequence[Sequence[int]],
+                    options: Union[None, DecodingOptions, Sequence[Optional[DecodingOptions]]] = None,
+                    specialTokens=None) -> List[Union[TranscriptionResult, WhisperError]]:
+        """Forced alignment (wh_align_tokens_batch): word timings for transcripts the caller already has.  audioArrays[a]: at most one 30 s window of
+        16 kHz samples; tokenLists[a]: the text tokens (timestamp tokens included where the text has them) WITHOUT the forced prompt and the end token -
+        the pass runs over prefillPrompt(options) + tokenLists[a] + EOT.  options: one for all, or one per audio.  Entry a of the result is audio a's
+        TranscriptionResult, built by the window code a decoded window goes through, or the WhisperError it failed with.  Needs a tokenizer on the
+        session and a model with alignment heads.  Host arrays only: api.DeviceAudio is not accepted."""
+        n = len(audioArrays)
+        if len(tokenLists) != n:
+            raise WhisperError(9, "The number of audio arrays and token lists must be balanced.")
+        if options is None or isinstance(options, DecodingOptions):
+            options = [options] * n
+        if len(options) != n:
+            raise WhisperError(9, "The number of audio arrays and decoding options must be balanced.")
+        if _device_items(audioArrays, "alignTokens"):
+            raise TypeError("alignTokens: host arrays only (DeviceAudio is not supported)")
+        st = specialTokens if specialTokens is not None else self.model.specialTokens
+        keep = [(o or DecodingOptions()).to_c() for o in options]                   # keeps the option structs and their arrays alive
+        optv = (L.WhDecodingOptions * n)(*keep)
+        arrs = [np.ascontiguousarray(a, dtype=np.float32) for a in audioArrays]
+        toks = [np.ascontiguousarray(list(t), dtype=np.int32) for t in tokenLists]
+        ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in arrs])
+        lens = (C.c_int32 * n)(*[len(a) for a in arrs])
+        tptr = (C.c_void_p * n)(*[t.ctypes.data for t in toks])
+        tlen = (C.c_int32 * n)(*[len(t) for t in toks])
+        outs = (C.c_void_p * n)()
+        stat = (C.c_int32 * n)()
+        self._guarded(self.lib.wh_align_tokens_batch, self.handle, ptrs, lens, n, optv, C.byref(st), tptr, tlen, outs, stat)
+        return [_collect(outs[i]) if stat[i] == 0 else WhisperError(int(stat[i]), self.lib.wh_session_item_error(self.handle, i).decode()) for i in range(n)]
+
+    def forcedPassStats(self) -> Tuple[int, int, int]:
+        """(forced passes, their decoder launches, the positions those launches ran) since the session was created"""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        _check(self.lib.wh_session_forced_pass_stats(self.handle, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
 
     def setCancelFlag(self, flag: Optional["C.c_int32"]):
         """Task.checkCancellation: a ctypes.c_int32 polled by the running call (non-zero -> WhisperError code 102); None removes it.

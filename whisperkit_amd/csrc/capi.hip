@@ -580,6 +580,7 @@ extern "C" int wh_debug_peek(wh_session* s, const char* name, void* out, size_t 
     else if (s->use_xabs && n == "ml") { src = s->xabs.ml; have = (size_t)kXabsSplits * H * B * 8; }
     else if (n == "enc16") { src = s->enc16; have = B * kCtx * d * 2; }
     else if (s->enc_lo && n == "enc_lo") { src = s->enc_lo; have = B * kCtx * (size_t)s->m->dims.n_audio_state * 2; }
+    else if (s->align && n == "align") { src = s->align; have = B * kMaxTok * (size_t)s->n_align_alloc * kCtx * 4; }      // raw score rows [B][224][n_align][1500]
     if (!src) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_peek: no buffer named '%s' in this session", name);
     if (nbytes > have) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_peek: '%s' holds %zu bytes, %zu requested", name, have, nbytes);
     WH_HIP(hipStreamSynchronize(s->st));

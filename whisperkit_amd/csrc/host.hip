@@ -17,6 +17,7 @@
 #include <mutex>
 #include <tuple>
 
+#include "forced_plan.h"
 #include "internal.h"
 #include "knobs.h"
 
@@ -1333,6 +1334,293 @@ extern "C" int wh_transcribe_chunked_device(wh_session* s, wh_device_audio* a, c
     *n_out = kept;
     return WH_OK;
     WH_CATCH("wh_transcribe_chunked_device")
+}
+
+// ------------------------------------------------------------------------------------------------ forced-transcript pass
+// NO REFERENCE BEHAVIOUR: openai/whisper timing.find_alignment semantics.  The tokens are given, so every position of every audio is a
+// virtual slot of a decoder launch (forced_plan.h): forced_arm_kernel writes the slots' positions, owner rows and home slots, the step kernels run as they
+// are at width = positions of the launch, forced_score_kernel reads the logits rows.  Eager launches, like the beam loop.
+static int forced_ensure(wh_session* s) {
+    const size_t cap = (size_t)s->B * (kMaxTok - 1);      // positions of one call at most: n_audio <= B sequences of <= kMaxTok tokens
+    if (!s->forced_owner) WH_HIP(s->mem.alloc(&s->forced_owner, (size_t)s->B * kMaxTok, false));
+    if (!s->slot_home_dev) WH_HIP(s->mem.alloc(&s->slot_home_dev, (size_t)s->B, false));
+    if (!s->forced_desc) WH_HIP(s->mem.alloc_pinned(&s->forced_desc, cap));
+    if (!s->forced_desc_dev) WH_HIP(s->mem.alloc(&s->forced_desc_dev, cap, false));
+    if (!s->forced_out) WH_HIP(s->mem.alloc(&s->forced_out, 3 * cap, false));
+    if (!s->forced_out_host) WH_HIP(s->mem.alloc_pinned(&s->forced_out_host, 3 * cap));
+    return WH_OK;
+}
+
+// tokens[a][0 .. n_tokens[a]) validated by the caller (vocabulary, lengths <= kMaxTok, n_audio <= B); slots 0 .. n_audio - 1 hold the windows' encoder
+// data.  lp_out[a][i] = log p(tokens[a][i] | tokens[a][0 .. i)) for i >= 1, entry 0 = 0; best_out / best_lp_out (each may be null): the unfiltered
+// argmax of the row that scored token i and its log-probability, entry 0 = -1 / 0.
+static int forced_pass_impl(wh_session* s, int n_audio, const int32_t* const* tokens, const int32_t* n_tokens, bool record_alignment,
+                            float* const* lp_out, int32_t* const* best_out, float* const* best_lp_out) {
+    const int B = s->B, V = s->m->dims.n_vocab;
+    int r = forced_ensure(s);
+    if (r) return r;
+    // every exit: the next caller of decode_buffers sees a plain session, with the sampler / alignment switches the last decode left
+    struct Scope { wh_session* s; bool fused, align; ~Scope() { s->pass_mapped = false; s->pass_owner = false; s->pass_mixed = false; s->fused_greedy = fused; s->align_enabled = align; } }
+        scope{s, s->fused_greedy, s->align_enabled};
+    if (record_alignment && s->m->n_align > 0) {
+        r = whi::ensure_align(s);
+        if (r) return r;
+        WH_HIP(hipMemsetAsync(s->align, 0, (size_t)n_audio * kMaxTok * s->n_align_alloc * kCtx * sizeof(float), s->st));      // home slots 0 .. n_audio - 1
+    }
+    s->align_enabled = record_alignment && s->align;
+    s->fused_greedy = false; s->pass_mixed = false; s->pass_owner = false;
+    const size_t cap = (size_t)B * (kMaxTok - 1);
+    float* const lp_dev = s->forced_out;
+    int* const best_dev = reinterpret_cast<int*>(s->forced_out + cap);
+    float* const best_lp_dev = s->forced_out + 2 * cap;
+    const std::vector<plan::ForcedLaunch> launches = plan::forced_pass_plan(n_tokens, n_audio, B);
+    const int spw0 = s->use_xabs ? s->xabs.spw : 1;
+    size_t base = 0;
+    s->forced_passes += 1;
+    for (const plan::ForcedLaunch& l : launches) {
+        if (cancelled(s)) { hipStreamSynchronize(s->st); return set_error(WH_ERR_CANCELLED, "forced pass: cancelled through the session's cancel flag"); }
+        const int n = (int)l.slots.size();
+        if (base + (size_t)n > cap) return set_error(WH_ERR_DECODING_FAILED, "forced pass: the plan holds more positions than the session's staging");
+        // this launch's own region of the pinned staging (uploaded stream-ordered below, like inpass_stage): the stream has consumed nothing the host writes here
+        ForcedDesc* d = s->forced_desc + base;
+        for (int i = 0; i < n; ++i) {
+            const plan::ForcedSlot& v = l.slots[(size_t)i];
+            d[i] = ForcedDesc{v.audio, v.position, tokens[v.audio][v.position], v.first, v.len, tokens[v.audio][v.position + 1], {0, 0}};
+        }
+        WH_HIP(hipMemcpyAsync(s->forced_desc_dev + base, d, sizeof(ForcedDesc) * (size_t)n, hipMemcpyHostToDevice, s->st));
+        launch_forced_arm(s->forced_desc_dev + base, s->seq, s->forced_owner, s->slot_home_dev, n, B, V, s->st);
+        const plan::CompactPassPlan cp = plan::compact_pass_plan(n, B, B, spw0);      // slots per absorbed-attention workgroup: the value of the ladder rung that holds n slots (results do not depend on it)
+        s->pass_mapped = true; s->pass_spw = cp.compact ? cp.spw : spw0;
+        DecodeBuffers db = whi::decode_buffers(s, n, l.self_rows - 1);
+        db.self_owner = s->forced_owner; db.owner_slots = B;
+        launch_decoder_step(db, nullptr, nullptr, false, s->st);
+        launch_forced_score(s->logits, s->forced_desc_dev + base, n, V, lp_dev + base, best_dev + base, best_lp_dev + base, s->st);
+        WH_CHECK_LAUNCH();
+        if (s->forced_capture && (base + (size_t)n) * V <= s->forced_capture_floats)       // wh_debug_forced_capture: the rows before the next launch rewrites them
+            WH_HIP(hipMemcpyAsync(s->forced_capture + base * V, s->logits, sizeof(float) * (size_t)n * V, hipMemcpyDeviceToHost, s->st));
+        s->forced_launches += 1; s->forced_positions += n;
+        base += (size_t)n;
+    }
+    if (base) {
+        WH_HIP(hipMemcpyAsync(s->forced_out_host, lp_dev, sizeof(float) * base, hipMemcpyDeviceToHost, s->st));
+        WH_HIP(hipMemcpyAsync(s->forced_out_host + cap, best_dev, sizeof(int) * base, hipMemcpyDeviceToHost, s->st));
+        WH_HIP(hipMemcpyAsync(s->forced_out_host + 2 * cap, best_lp_dev, sizeof(float) * base, hipMemcpyDeviceToHost, s->st));
+    }
+    WH_HIP(hipStreamSynchronize(s->st));
+    for (int a = 0; a < n_audio; ++a) {
+        if (n_tokens[a] < 1) continue;
+        if (lp_out && lp_out[a]) lp_out[a][0] = 0.0f;
+        if (best_out && best_out[a]) best_out[a][0] = -1;
+        if (best_lp_out && best_lp_out[a]) best_lp_out[a][0] = 0.0f;
+    }
+    size_t k = 0;
+    const int* const best_host = reinterpret_cast<const int*>(s->forced_out_host + cap);
+    for (const plan::ForcedLaunch& l : launches)
+        for (const plan::ForcedSlot& v : l.slots) {
+            if (lp_out && lp_out[v.audio]) lp_out[v.audio][v.position + 1] = s->forced_out_host[k];
+            if (best_out && best_out[v.audio]) best_out[v.audio][v.position + 1] = best_host[k];
+            if (best_lp_out && best_lp_out[v.audio]) best_lp_out[v.audio][v.position + 1] = s->forced_out_host[2 * cap + k];
+            ++k;
+        }
+    return WH_OK;
+}
+
+// what needs no session, for both entry points: a caller learns about a bad token list without a device
+static int forced_check_tokens(const char* who, int n_audio, const int32_t* const* tokens, const int32_t* n_tokens, int n_vocab) {
+    for (int a = 0; a < n_audio; ++a) {
+        if (n_tokens[a] < 0 || n_tokens[a] > kMaxTok) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: audio %d has %d tokens (0 .. %d)", who, a, n_tokens[a], kMaxTok);
+        if (n_tokens[a] > 0 && !tokens[a]) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: audio %d: null token list", who, a);
+        for (int i = 0; i < n_tokens[a]; ++i)
+            if (tokens[a][i] < 0 || tokens[a][i] >= n_vocab) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: audio %d: token %d out of vocabulary", who, a, tokens[a][i]);
+    }
+    return WH_OK;
+}
+
+extern "C" int wh_score_tokens(wh_session* s, int n_audio, const int32_t* const* tokens, const int32_t* n_tokens, int record_alignment,
+                               float* const* token_logprobs_out, int32_t* const* best_tokens_out, float* const* best_logprobs_out) {
+    if (n_audio < 1 || n_audio > kMaxSessionSlots) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_score_tokens: %d audios (1 .. the session's slots)", n_audio);
+    if (!tokens || !n_tokens || !token_logprobs_out) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_score_tokens: null argument");
+    for (int a = 0; a < n_audio; ++a)
+        if (n_tokens[a] > 0 && !token_logprobs_out[a]) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_score_tokens: audio %d: null output", a);
+    if (int r = forced_check_tokens("wh_score_tokens", n_audio, tokens, n_tokens, kMaxVocab)) return r;
+    CHECK_SESSION(s); CHECK_BATCH(s, n_audio);
+    if (int r = forced_check_tokens("wh_score_tokens", n_audio, tokens, n_tokens, s->m->dims.n_vocab)) return r;
+    WH_TRY
+    return forced_pass_impl(s, n_audio, tokens, n_tokens, record_alignment != 0, token_logprobs_out, best_tokens_out, best_logprobs_out);
+    WH_CATCH("wh_score_tokens")
+}
+
+extern "C" int wh_session_forced_pass_stats(const wh_session* s, int64_t* passes, int64_t* launches, int64_t* positions) {
+    if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_forced_pass_stats: null session");
+    if (passes) *passes = s->forced_passes;
+    if (launches) *launches = s->forced_launches;
+    if (positions) *positions = s->forced_positions;
+    return WH_OK;
+}
+
+// Development aid: the next forced passes copy every launch's logits rows to `logits_out` before the following launch rewrites them - row k is the k-th
+// virtual slot of the call in plan order (launch by launch, slot by slot), [n_vocab] floats each; a call whose rows do not fit copies the launches that do.
+// NULL switches it off.  The buffer must stay valid while it is installed.
+extern "C" int wh_debug_forced_capture(wh_session* s, float* logits_out, size_t capacity_floats) {
+    if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_forced_capture: null session");
+    s->forced_capture = logits_out;
+    s->forced_capture_floats = logits_out ? capacity_floats : 0;
+    return WH_OK;
+}
+
+// Development aid: forced_score_kernel alone over caller-supplied logits rows - n_rows (<= max_batch) rows of the model's vocabulary go into the session's
+// logits buffer (row i where a launch leaves slot i's row, so the rows start at every alignment the pass meets), one launch, three small copies back.
+extern "C" int wh_debug_forced_score(wh_session* s, const float* logits_rows, int n_rows, const int32_t* targets, float* logprobs_out,
+                                     int32_t* best_tokens_out, float* best_logprobs_out) {
+    CHECK_SESSION(s); CHECK_BATCH(s, n_rows);
+    if (!logits_rows || !targets || !logprobs_out || !best_tokens_out || !best_logprobs_out) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_forced_score: null argument");
+    const int V = s->m->dims.n_vocab;
+    int r = forced_ensure(s);
+    if (r) return r;
+    const size_t cap = (size_t)s->B * (kMaxTok - 1);
+    WH_HIP(hipStreamSynchronize(s->st));                  // nothing in flight reads the staging the host writes next
+    for (int i = 0; i < n_rows; ++i) s->forced_desc[i] = ForcedDesc{0, 0, 0, 0, 1, targets[i], {0, 0}};
+    WH_HIP(hipMemcpyAsync(s->forced_desc_dev, s->forced_desc, sizeof(ForcedDesc) * (size_t)n_rows, hipMemcpyHostToDevice, s->st));
+    WH_HIP(hipMemcpyAsync(s->logits, logits_rows, sizeof(float) * (size_t)n_rows * V, hipMemcpyHostToDevice, s->st));
+    launch_forced_score(s->logits, s->forced_desc_dev, n_rows, V, s->forced_out, reinterpret_cast<int*>(s->forced_out + cap), s->forced_out + 2 * cap, s->st);
+    WH_CHECK_LAUNCH();
+    WH_HIP(hipMemcpyAsync(logprobs_out, s->forced_out, sizeof(float) * n_rows, hipMemcpyDeviceToHost, s->st));
+    WH_HIP(hipMemcpyAsync(best_tokens_out, s->forced_out + cap, sizeof(int) * n_rows, hipMemcpyDeviceToHost, s->st));
+    WH_HIP(hipMemcpyAsync(best_logprobs_out, s->forced_out + 2 * cap, sizeof(float) * n_rows, hipMemcpyDeviceToHost, s->st));
+    WH_HIP(hipStreamSynchronize(s->st));
+    return WH_OK;
+}
+
+// Forced alignment: word timings for transcripts the caller already has.  Per audio: one window through mel and encoder, the forced pass over
+// wh_prefill_prompt(opts[a]) + text_tokens[a] + EOT with the alignment rows recorded, then the window code a decoded window goes through.
+extern "C" int wh_align_tokens_batch(wh_session* s, const float* const* pcm_host, const int32_t* n_samples, int n_audio, const wh_decoding_options* opts,
+                                     const wh_special_tokens* st, const int32_t* const* text_tokens, const int32_t* n_text, wh_transcription** out,
+                                     int32_t* status) {
+    if (n_audio < 1) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_align_tokens_batch: %d audios", n_audio);
+    if (!pcm_host || !n_samples || !opts || !st || !text_tokens || !n_text || !out) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_align_tokens_batch: null argument");
+    CHECK_SESSION(s);
+    if (!s->tok) return set_error(WH_ERR_TOKENIZER_UNAVAILABLE, "wh_align_tokens_batch: the session has no tokenizer (wh_session_set_tokenizer)");
+    if (!(s->m->n_align > 0)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_align_tokens_batch: the model has no alignment heads (wh_supports_word_timestamps)");
+    WH_TRY
+    const int V = s->m->dims.n_vocab;
+    s->item_status.assign((size_t)n_audio, WH_OK);
+    s->item_error.assign((size_t)n_audio, std::string());
+    auto fail = [&](int a, int code) { s->item_status[(size_t)a] = code; s->item_error[(size_t)a] = wh_last_error(); };
+    std::vector<std::vector<int32_t>> seq((size_t)n_audio);
+    std::vector<wh_decoding_options> wo(opts, opts + n_audio);      // the audio's options with word timestamps on: what the window code reads
+    for (int a = 0; a < n_audio; ++a) {
+        out[a] = nullptr;
+        wo[(size_t)a].word_timestamps = 1;
+        if (n_samples[a] < 1 || !pcm_host[a]) { fail(a, set_error(WH_ERR_AUDIO_PROCESSING_FAILED, "audio %d: invalid buffer", a)); continue; }
+        if (n_samples[a] > kWindowSamples) { fail(a, set_error(WH_ERR_INVALID_ARGUMENT, "audio %d: %d samples exceed one window of %d (long-form alignment is out of scope)", a, n_samples[a], kWindowSamples)); continue; }
+        if (n_text[a] < 0 || (n_text[a] > 0 && !text_tokens[a])) { fail(a, set_error(WH_ERR_INVALID_ARGUMENT, "audio %d: invalid token list", a)); continue; }
+        std::vector<int32_t> p(kMaxPrompt);
+        int np = 1;
+        p[0] = st->start_of_transcript_token;
+        if (opts[a].use_prefill_prompt) np = wh_prefill_prompt(s->m, &opts[a], st, opts[a].language_token, p.data(), (int)p.size());
+        if (np <= 0) { fail(a, set_error(WH_ERR_PREFILL_FAILED, "audio %d: prefill prompt does not fit", a)); continue; }
+        if (np + n_text[a] + 1 > kMaxTok) { fail(a, set_error(WH_ERR_INVALID_ARGUMENT, "audio %d: prompt (%d) + text (%d) + end token exceed %d tokens", a, np, n_text[a], kMaxTok)); continue; }
+        p.resize((size_t)np);
+        p.insert(p.end(), text_tokens[a], text_tokens[a] + n_text[a]);
+        p.push_back(st->end_token);
+        const int32_t* pp = p.data(); const int32_t pn = (int32_t)p.size();
+        if (int r = forced_check_tokens("wh_align_tokens_batch", 1, &pp, &pn, V)) { fail(a, r); continue; }
+        seq[(size_t)a] = std::move(p);
+    }
+    const double cf_start = cf_absolute_time();
+    std::vector<int> todo;
+    for (int a = 0; a < n_audio; ++a) if (s->item_status[(size_t)a] == WH_OK) todo.push_back(a);
+    // rounds of up to B windows; an error that is not one audio's (the device, a cancel) ends the call and frees what the earlier rounds returned
+    const int hard = [&]() -> int {
+    for (size_t r0 = 0; r0 < todo.size(); r0 += (size_t)s->B) {
+        const int nb = (int)std::min(todo.size() - r0, (size_t)s->B);
+        if (cancelled(s)) return set_error(WH_ERR_CANCELLED, "wh_align_tokens_batch: cancelled through the session's cancel flag");
+        const double t0 = now_s();
+        for (int b = 0; b < nb; ++b) { const int a = todo[r0 + b]; int r = wh_set_audio(s, b, pcm_host[a], n_samples[a]); if (r) return r; }
+        int r = wh_log_mel_spectrogram(s, nb); if (r) return r;
+        r = wh_encode_features(s, nb); if (r) return r;
+        r = wh_prepare_decoder_inputs(s, nb); if (r) return r;
+        WH_HIP(hipStreamSynchronize(s->st));
+        const double t1 = now_s();
+        std::vector<const int32_t*> tp((size_t)nb);
+        std::vector<int32_t> tn((size_t)nb);
+        std::vector<std::vector<float>> lp((size_t)nb);
+        std::vector<float*> lpp((size_t)nb);
+        for (int b = 0; b < nb; ++b) {
+            const std::vector<int32_t>& q = seq[(size_t)todo[r0 + b]];
+            tp[(size_t)b] = q.data(); tn[(size_t)b] = (int32_t)q.size(); lp[(size_t)b].assign(q.size(), 0.0f); lpp[(size_t)b] = lp[(size_t)b].data();
+        }
+        r = forced_pass_impl(s, nb, tp.data(), tn.data(), true, lpp.data(), nullptr, nullptr); if (r) return r;
+        const double t2 = now_s();
+        // a DecodingResult per window with the given tokens and the forced scores: SOT .. EOT as finalize_decoding_result slices a decoded sequence
+        std::vector<wh_decoding_result> res((size_t)nb);
+        for (int b = 0; b < nb; ++b) {
+            const std::vector<int32_t>& q = seq[(size_t)todo[r0 + b]];
+            wh_decoding_result& o = res[(size_t)b];
+            memset(&o, 0, sizeof(o));
+            int start = 0, end = (int)q.size() - 1;
+            for (int i = 0; i < (int)q.size(); ++i) if (q[(size_t)i] == st->start_of_transcript_token) { start = i; break; }
+            for (int i = 0; i < (int)q.size(); ++i) if (q[(size_t)i] == st->end_token) { end = i; break; }
+            if (end < start) end = (int)q.size() - 1;
+            const int n = std::min(end - start + 1, WH_MAX_RESULT_TOKENS);
+            float sum = 0.0f;
+            std::vector<int32_t> words;
+            o.language_token = -1;
+            for (int i = 0; i < n; ++i) {
+                const int t = q[(size_t)(start + i)];
+                o.tokens[i] = t; o.token_logprobs[i] = lp[(size_t)b][(size_t)(start + i)]; sum += o.token_logprobs[i];
+                if (t < st->special_token_begin) words.push_back(t);
+                if (o.language_token < 0 && t >= st->language_token_begin && t < st->language_token_begin + st->n_language_tokens) o.language_token = t;
+            }
+            o.n_tokens = n; o.avg_logprob = sum / (float)n; o.compression_ratio = wh_compression_ratio(words.data(), (int)words.size());
+            o.steps = (int)q.size() - 1;
+        }
+        const bool device_paths = s->word_alignment == 1;
+        const int32_t *path_len = nullptr, *path_ti = nullptr, *path_tj = nullptr;
+        if (device_paths) {
+            std::vector<int32_t> rows((size_t)nb);
+            for (int b = 0; b < nb; ++b) { rows[(size_t)b] = wh_word_alignment_rows(&res[(size_t)b], &wo[(size_t)todo[r0 + b]], st, 1); if (rows[(size_t)b] < 0) return WH_ERR_SEGMENTING_FAILED; }
+            r = whi::alignment_paths(s, nb, rows.data(), &path_len, &path_ti, &path_tj); if (r) return r;
+        }
+        for (int b = 0; b < nb; ++b) {
+            const int a = todo[r0 + b];
+            const wh_decoding_options* jo = &wo[(size_t)a];
+            wh_transcription* tr = new wh_transcription();
+            tr->timings.pipeline_start = cf_start; tr->timings.input_audio_seconds = (double)n_samples[a] / WH_SAMPLE_RATE;
+            tr->seeks.push_back(0);
+            int32_t seek = 0;
+            if (device_paths) {
+                r = wh_transcription_add_window_path(tr, s->tok, jo, st, &res[(size_t)b], path_ti + (size_t)b * kDtwPathCap, path_tj + (size_t)b * kDtwPathCap, path_len[b],
+                                                     jo->language_token, n_samples[a], &seek);
+            } else {
+                std::vector<float> full((size_t)kMaxTok * kCtx);
+                r = wh_get_alignment_weights(s, b, full.data());
+                if (r == WH_ERR_HIP) { delete tr; return r; }
+                if (!r) r = wh_transcription_add_window(tr, s->tok, jo, st, &res[(size_t)b], full.data(), jo->language_token, n_samples[a], &seek);
+            }
+            tr->timings.encoding += (t1 - t0) / nb; tr->timings.decoding_loop += (t2 - t1) / nb; tr->timings.total_decoding_loops += res[(size_t)b].steps;
+            tr->timings.total_logmel_runs += 1; tr->timings.total_encoding_runs += 1; tr->timings.total_audio_processing_runs += 1;
+            tr->timings.full_pipeline = now_s() - t0;
+            if (!r) r = wh_transcription_finalize(tr, s->tok, jo, st);
+            if (r) { fail(a, r); delete tr; continue; }
+            out[a] = tr;
+        }
+    }
+    return WH_OK;
+    }();
+    if (hard) {
+        for (int a = 0; a < n_audio; ++a) { delete out[a]; out[a] = nullptr; }
+        return hard;
+    }
+    int n_ok = 0, first_bad = WH_OK;
+    for (int a = 0; a < n_audio; ++a) {
+        if (status) status[a] = s->item_status[(size_t)a];
+        if (s->item_status[(size_t)a] == WH_OK) ++n_ok; else if (first_bad == WH_OK) first_bad = s->item_status[(size_t)a];
+    }
+    if (n_ok == 0 && !status)       // a caller that did not ask for per-audio statuses still learns why nothing came back
+        for (int a = 0; a < n_audio; ++a) if (s->item_status[(size_t)a] == first_bad) return set_error(first_bad, "%s", s->item_error[(size_t)a].c_str());
+    return WH_OK;
+    WH_CATCH("wh_align_tokens_batch")
 }
 
 extern "C" int wh_session_set_progress_callback(wh_session* s, wh_progress_fn fn, void* user) {

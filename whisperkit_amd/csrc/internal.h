@@ -171,6 +171,15 @@ struct wh_session {
     int32_t *inpass_dev = nullptr, *inpass_stage = nullptr;
     bool pass_owner = false;
     long long inpass_switches = 0, inpass_slot_steps_saved = 0;          // wh_session_inpass_compaction_stats
+    // forced-transcript pass (wh_score_tokens / wh_align_tokens_batch: host.hip forced_pass_impl, forced_plan.h, forced.hip).  Everything is allocated by
+    // the first pass: forced_owner [B][kMaxTok] (device, the row -> owner rows of the virtual slots), forced_desc [B * (kMaxTok - 1)] (pinned staging:
+    // a call's launches take consecutive regions of it, one descriptor per position, so the host never writes a region the stream has not consumed;
+    // each region is uploaded to the same offset of forced_desc_dev, which the kernels read), forced_out = log p(target) | argmax | log p(argmax), [B * (kMaxTok - 1)] each (device) and its pinned mirror.
+    int32_t* forced_owner = nullptr;
+    wh::ForcedDesc *forced_desc = nullptr, *forced_desc_dev = nullptr;
+    float *forced_out = nullptr, *forced_out_host = nullptr;
+    long long forced_passes = 0, forced_launches = 0, forced_positions = 0;      // wh_session_forced_pass_stats
+    float* forced_capture = nullptr; size_t forced_capture_floats = 0;            // wh_debug_forced_capture: host buffer the launches' logits rows are copied to, or null
     hipEvent_t ev[8]{};
     bool align_enabled = false;
     wh_timings last_timings{};

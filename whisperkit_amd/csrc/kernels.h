@@ -356,6 +356,19 @@ void launch_rules_init(const SamplerCfg* cfg_dev, SeqState* seq, int batch, hipS
 // for the active slots i < width (home null: i); gather: seq[i] = seq_home[home[i]] where live[i], an inactive zero state elsewhere.
 void launch_seq_park(const SeqState* seq, SeqState* seq_home, const int* home, int width, int n_slots, hipStream_t st);
 void launch_seq_gather(const SeqState* seq_home, SeqState* seq, const int* home, const int* live, int width, int n_slots, hipStream_t st);
+// forced-transcript pass (forced.hip, forced_plan.h): what one virtual slot of a launch is, 32 bytes, staged in pinned memory and uploaded per launch
+struct ForcedDesc {
+    int home;                // the audio's slot: whose encoder data the slot attends over, whose alignment rows it writes (DecodeBuffers.slot_home)
+    int position, token;     // SeqState.token_index / next_token of the step
+    int first, len;          // the audio's slot range: row r of the slot's history lives in the cache of slot first + r % len (DecodeBuffers.self_owner)
+    int target;              // the token to score against the step's logits row (the sequence's next token), or -1
+    int pad[2];
+};
+static_assert(sizeof(ForcedDesc) == 32, "ForcedDesc: one 32-byte sector per virtual slot");
+// arm: desc[0 .. n) -> seq[0 .. n) control fields (as wh_predict_logits writes them), owner [n][kMaxTok], slot_home [n]
+void launch_forced_arm(const ForcedDesc* desc, SeqState* seq, int* owner, int* slot_home, int n, int n_slots, int n_vocab, hipStream_t st);
+// score: the plain log-softmax of logits rows 0 .. n - 1 ([n][n_vocab] floats) -> log p(desc[i].target), the argmax (lowest id on ties) and its log p
+void launch_forced_score(const float* logits, const ForcedDesc* desc, int n, int n_vocab, float* lp_out, int* best_out, float* best_lp_out, hipStream_t st);
 // standalone filter / sampler entry points (KAT surface of the C ABI)
 void launch_filter_only(const SamplerCfg* cfg_dev, const int* suppress_dev, SeqState* seq, float* logits, int n_vocab, hipStream_t st);
 void launch_sample_only(const SamplerCfg* cfg_dev, SeqState* seq, float* logits, int n_vocab, int counter, int* token_out, float* logprob_out, hipStream_t st);
