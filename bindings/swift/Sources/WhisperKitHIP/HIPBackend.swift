@@ -75,6 +75,11 @@ public final class HIPSession {
     /// that agree in the pass-level fields share a device batch and each slot decodes under the options of its class (up to 16 classes per batch).
     public enum OptionMixing: Int32 { case off = 0, on = 1 }
     public var optionMixing: OptionMixing = .off { didSet { _ = wh_session_set_option_mixing(handle, optionMixing.rawValue) } }
+    /// Speculative greedy decode (wh_session_set_draft; no reference behaviour): with a draft session attached - any model with the same vocabulary, on
+    /// the same device - the first T = 0 greedy pass of the transcribe calls lets the draft propose `k` tokens per launch chain and this session check
+    /// them in one launch (csrc/spec.hip) when windows x (k + 1) fit its slots.  Same results, bit for bit; `nil` detaches.  The draft is not owned.
+    public func setDraft(_ draft: HIPSession?, k: Int = 4) throws { try check(wh_session_set_draft(handle, draft?.handle, Int32(k))); self.draft = draft }
+    private var draft: HIPSession?
     public enum BeamRanking: Int32 { case host = 0, device = 1 }
     public var beamRanking: BeamRanking = .host { didSet { _ = wh_session_set_beam_ranking(handle, beamRanking.rawValue) } }
     public init(model: HIPModel, maxBatch: Int = 1, crossAttention: CrossAttentionMode = .automatic, keySplits: Int = 0, slotsPerWorkgroup: Int = 0,

@@ -612,6 +612,43 @@ int wh_debug_forced_capture(wh_session* s, float* logits_out, size_t capacity_fl
 int wh_debug_forced_score(wh_session* s, const float* logits_rows, int n_rows, const int32_t* targets, float* logprobs_out,
                           int32_t* best_tokens_out, float* best_logprobs_out);
 
+/* ---- speculative greedy decode: NO REFERENCE BEHAVIOUR (draft-and-verify decoding, csrc/spec_plan.h, spec.hip) -----
+ * A decode pass is one dependent launch chain per token.  Here a proposer guesses the next K tokens of every audio and the session (the
+ * target) runs the known position and the K guessed ones as virtual slots of ONE launch chain, under its own logits filters and its own
+ * greedy sampler; it keeps the longest prefix it would have produced itself plus its own next token.  At T = 0 the tokens, the
+ * log-probabilities, the stop reason and the alignment rows are those of wh_decode_text, bit for bit; only the number of launch chains
+ * depends on the proposals.  Audio a (encoder data in slot a, as for wh_decode_text) uses the slots [a (K + 1), (a + 1)(K + 1)) for its
+ * positions, so n_audio (K + 1) <= max_batch and 1 <= K <= 15 (WH_ERR_INVALID_ARGUMENT otherwise).  Greedy at T = 0 only: an
+ * opt->temperature other than 0 or a beam_size > 1 is WH_ERR_INVALID_ARGUMENT.  The positions of the prompt are look-ahead inputs that
+ * are always kept: a long prompt_tokens prompt is fed K + 1 positions per launch chain.  The progress callback is not called.  Results
+ * follow the wh_decode_text conventions; language_tokens as in wh_decode_text_languages (or NULL).
+ *
+ * wh_decode_text_guided: the proposals are lists.  proposals[a][i] (n_proposals[a] of them, each inside the vocabulary) is the guess for
+ * sampled token i of audio a, counted from the end of the prompt, whatever was accepted before; past the list a round runs the known
+ * position only.  proposals == NULL: no proposals at all.  Use: re-decoding with the hypothesis of a cheaper system or an earlier pass.
+ *
+ * wh_decode_text_speculative: the proposals are the greedy samples of `draft`, a second session of ANY model with the same n_vocab
+ * (otherwise WH_ERR_INVALID_ARGUMENT) on the same device with max_batch >= n_audio, whose slots 0 .. n_audio - 1 hold the same windows
+ * (the caller has run its log-mel, encoder and wh_prepare_decoder_inputs).  Every round the draft's slots are re-armed with the history
+ * the target has accepted and run their ordinary greedy step up to K positions ahead.  Neither session may be used by another thread
+ * during the call. */
+int wh_decode_text_guided(wh_session* s, int n_audio, int K, const wh_decoding_options* opt, const wh_special_tokens* st,
+                          const int32_t* prompt, int n_prompt, const int32_t* language_tokens, const int32_t* const* proposals,
+                          const int32_t* n_proposals, wh_decoding_result* out /* [n_audio] */);
+int wh_decode_text_speculative(wh_session* s, wh_session* draft, int n_audio, int K, const wh_decoding_options* opt,
+                               const wh_special_tokens* st, const int32_t* prompt, int n_prompt, const int32_t* language_tokens,
+                               wh_decoding_result* out /* [n_audio] */);
+/* Attach a draft session (or NULL: detach; K is then ignored) for wh_transcribe*: the first rung of the temperature ladder (T = 0,
+ * greedy, no option mixing, no progress callback) of a device batch of w windows runs as wh_decode_text_speculative when
+ * w (K + 1) <= max_batch and the draft has w slots; the draft gets the same windows through its own log-mel and encoder (n_mels may
+ * differ).  Every other pass runs as it does without a draft, and the results are equal either way.  The draft is not owned: detach it
+ * before it is destroyed.  wh_session_draft_k: the attached K, 0 without a draft, -1 for NULL. */
+int wh_session_set_draft(wh_session* s, wh_session* draft_or_null, int K);
+int wh_session_draft_k(const wh_session* s);
+/* Counters of the session since its creation: speculative passes, their rounds (decoder launch chains of the target), the positions
+ * (virtual slots) those rounds ran and the look-ahead positions the target kept.  Any pointer may be NULL. */
+int wh_session_speculative_stats(const wh_session* s, int64_t* passes, int64_t* rounds, int64_t* positions_run, int64_t* tokens_accepted);
+
 /* TextDecoding.detectLanguage (Core/TextDecoder.swift:420-539) */
 int wh_detect_language(wh_session* s, int batch, const wh_special_tokens* st, int32_t* language_tokens_out,
                        float* logprobs_out);

@@ -211,6 +211,12 @@ SYMBOLS = {
     "wh_session_forced_pass_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "wh_debug_forced_capture": (I, [VP, VP, C.c_size_t]),
     "wh_debug_forced_score": (I, [VP, VP, I, PI32, PF, PI32, PF]),
+    # speculative greedy decode (csrc/spec.hip, spec_plan.h)
+    "wh_decode_text_guided": (I, [VP, I, I, POPT, PST, PI32, I, PI32, PVP, PI32, C.POINTER(WhDecodingResult)]),
+    "wh_decode_text_speculative": (I, [VP, VP, I, I, POPT, PST, PI32, I, PI32, C.POINTER(WhDecodingResult)]),
+    "wh_session_set_draft": (I, [VP, VP, I]),
+    "wh_session_draft_k": (I, [VP]),
+    "wh_session_speculative_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "wh_prefill_prompt": (I, [VP, POPT, PST, C.c_int32, PI32, I]),
     "wh_transcribe": (I, [VP, VP, I, POPT, PST, PVP]),
     "wh_transcribe_batch": (I, [VP, PVP, PI32, I, POPT, PST, PVP]),

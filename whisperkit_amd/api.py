@@ -766,6 +766,57 @@ class Session:
                           lt.ctypes.data_as(L.PI32), temps.ctypes.data_as(L.PF), None if act is None else act.ctypes.data_as(L.PI32), seed, res)
         return [DecodingResult.from_c(r) for r in res]
 
+    # ---- speculative greedy decode (no reference behaviour: draft-and-verify decoding; csrc/spec_plan.h, spec.hip)
+    def decodeTextGuided(self, prompt: Sequence[int], options: DecodingOptions, proposals: Sequence[Optional[Sequence[int]]], K: int,
+                         specialTokens=None, languageTokens: Optional[Sequence[int]] = None) -> List[DecodingResult]:
+        """decodeText at T = 0 for the audios in slots [0, len(proposals)), checking up to K proposed tokens per audio and launch chain
+        (wh_decode_text_guided): proposals[a][i] is the guess for sampled token i of audio a, counted from the end of the prompt (None or []: no
+        guesses).  Tokens, log-probabilities and stop reasons are decodeText's; len(proposals) * (K + 1) slots must fit the session."""
+        n = len(proposals)
+        st = specialTokens if specialTokens is not None else self.model.specialTokens
+        o = options.to_c()
+        p = np.ascontiguousarray(list(prompt), dtype=np.int32)
+        lists = [np.ascontiguousarray(list(q) if q is not None else [], dtype=np.int32) for q in proposals]
+        ptrs = (C.c_void_p * max(n, 1))(*[q.ctypes.data if len(q) else None for q in lists])
+        lens = (C.c_int32 * max(n, 1))(*[len(q) for q in lists])
+        lt = None if languageTokens is None else np.ascontiguousarray(languageTokens, dtype=np.int32)
+        assert lt is None or len(lt) == n
+        res = (L.WhDecodingResult * max(n, 1))()
+        self._guarded(self.lib.wh_decode_text_guided, self.handle, n, int(K), C.byref(o), C.byref(st), p.ctypes.data_as(L.PI32), len(p),
+                      None if lt is None else lt.ctypes.data_as(L.PI32), ptrs, lens, res)
+        return [DecodingResult.from_c(r) for r in res[:n]]
+
+    def decodeTextSpeculative(self, draft: "Session", prompt: Sequence[int], options: DecodingOptions, batch: int, K: int, specialTokens=None,
+                              languageTokens: Optional[Sequence[int]] = None) -> List[DecodingResult]:
+        """decodeText at T = 0 for slots [0, batch) with `draft` - a session of any model with the same vocabulary whose slots hold the same windows
+        (encoded, prepareDecoderInputs called) - proposing K tokens per launch chain (wh_decode_text_speculative).  Results are decodeText's."""
+        st = specialTokens if specialTokens is not None else self.model.specialTokens
+        o = options.to_c()
+        p = np.ascontiguousarray(list(prompt), dtype=np.int32)
+        lt = None if languageTokens is None else np.ascontiguousarray(languageTokens, dtype=np.int32)
+        assert lt is None or len(lt) == batch
+        res = (L.WhDecodingResult * max(batch, 1))()
+        self._guarded(self.lib.wh_decode_text_speculative, self.handle, draft.handle, batch, int(K), C.byref(o), C.byref(st), p.ctypes.data_as(L.PI32),
+                      len(p), None if lt is None else lt.ctypes.data_as(L.PI32), res)
+        return [DecodingResult.from_c(r) for r in res[:batch]]
+
+    def setDraft(self, draft: Optional["Session"], K: int = 4):
+        """Attach a draft session (None: detach): the first T = 0 greedy pass of transcribe runs speculatively, K proposals per launch chain, when its
+        windows x (K + 1) fit this session and the draft has the slots (wh_session_set_draft).  Results do not change; speculativeStats() shows it.
+        The draft is not owned: keep it alive, and detach it before closing it."""
+        _check(self.lib.wh_session_set_draft(self.handle, None if draft is None else draft.handle, int(K)))
+        self._draft = draft
+
+    @property
+    def draftK(self) -> int:
+        return int(self.lib.wh_session_draft_k(self.handle))
+
+    def speculativeStats(self) -> Tuple[int, int, int, int]:
+        """(speculative passes, their rounds = launch chains of this session, positions those rounds ran, look-ahead positions kept) since creation"""
+        a, b, c, d = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        _check(self.lib.wh_session_speculative_stats(self.handle, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return int(a.value), int(b.value), int(c.value), int(d.value)
+
     def decodeTextCustom(self, prompt: Sequence[int], options: DecodingOptions, logitsFilters: Sequence = (), sampler=None,
                          temperature: Optional[float] = None, seed: int = 0, specialTokens=None) -> DecodingResult:
         """TextDecoding.decodeText with the caller's own `LogitsFiltering` / `TokenSampling` objects (Core/Text/LogitsFilter.swift:8-10,

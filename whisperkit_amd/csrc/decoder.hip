@@ -35,48 +35,8 @@
 
 namespace wh {
 
-// ---------------------------------------------------------------------------------------------- fused greedy sampler, part 1
-// Filter rules of one sampling step as scalars (restating LogitsFilter.swift): r[0] SuppressBlank active,
-// r[1] TimestampRules active, [r2, r3) and [r4, r5) id ranges masked by the timestamp rules.
-// last_ts_hint: -2 = scan the history for the last timestamp token (TimestampRulesFilter walks it backwards); >= -1 = the caller already knows the
-// index of the last token >= time_token_begin in [0, n_tok) (-1: none) - sampler_final_kernel finds it with all of its threads, because with
-// text-only histories (random-init weights: the benchmark) the one-thread backward walk over <= 223 LDS words was 9 of the kernel's 12 us
-__device__ __forceinline__ void compute_filter_rules(const SamplerCfg& cfg, const SeqState* sq, int n_tok, int V, int* r, int last_ts_hint = -2) {
-    const int tb = cfg.time_token_begin;
-    int blank = 0, ts_active = 0, r1lo = 0, r1hi = 0, r2lo = 0, r2hi = 0;
-    blank = cfg.suppress_blank && (n_tok == cfg.prefilled_index);            // SuppressBlankFilter :44-50
-    if (cfg.timestamp_rules) {                                               // TimestampRulesFilter :72-129
-        int sb = -1;
-        if (cfg.is_multilingual) {                                           // :131-142
-            for (int i = 0; i < 3 && i < n_tok; ++i)
-                if (sq->tokens[i] == cfg.transcribe_token || sq->tokens[i] == cfg.translate_token) { sb = max(i + 1, cfg.initial_prompt_index); break; }
-        } else sb = cfg.initial_prompt_index;
-        if (sb >= 0 && sb <= n_tok) {
-            ts_active = 1;
-            if (n_tok > sb) {
-                int cnt = n_tok - sb;
-                bool lastTs = sq->tokens[n_tok - 1] >= tb;
-                bool penTs = cnt < 2 || sq->tokens[n_tok - 2] >= tb;
-                if (lastTs) {
-                    if (penTs) { r1lo = tb; r1hi = V; }          // has to be non-timestamp
-                    else { r1lo = 0; r1hi = cfg.end_token; }     // cannot be normal text
-                }
-                int lastTimestamp = -1;
-                if (last_ts_hint >= -1) {
-                    if (last_ts_hint >= sb) lastTimestamp = sq->tokens[last_ts_hint];
-                } else {
-                    for (int i = n_tok - 1; i >= sb; --i)
-                        if (sq->tokens[i] >= tb) { lastTimestamp = sq->tokens[i]; break; }
-                }
-                if (lastTimestamp >= 0) {
-                    int tl = (lastTs && !penTs) ? lastTimestamp : lastTimestamp + 1;
-                    r2lo = tb; r2hi = tl;
-                }
-            }
-        }
-    }
-    r[0] = blank; r[1] = ts_active; r[2] = r1lo; r[3] = r1hi; r[4] = r2lo; r[5] = r2hi;
-}
+// (the filter rules of a sampling step and the decodeText bookkeeping after it - compute_filter_rules, advance_decode_state - live in dec_shared.h:
+// the speculative pass's arming kernel, spec.hip, runs the same code)
 
 // ---------------------------------------------------------------------------------------------- attention
 struct AttnArgs {
@@ -479,45 +439,6 @@ __device__ __forceinline__ float uniform01(unsigned long long seed, int counter)
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     z = z ^ (z >> 31);
     return (float)(z >> 40) * (1.0f / 16777216.0f);
-}
-
-// decodeText bookkeeping after one sampled token (TextDecoder.swift:573-757), then the filter rules of the next step
-// last_ts_pre: index of the last timestamp token in [0, n_tok) BEFORE this step's token is appended (-1 none), or -2 = unknown (scan)
-__device__ __forceinline__ void advance_decode_state(const SamplerCfg& cfg, SeqState* sq, int tok, float lp, int n_tok, int last_ts_pre = -2) {
-    const int tb = cfg.time_token_begin;
-    const int ti_cur = sq->token_index;
-    const bool isFirstToken = ti_cur == cfg.prefilled_index;
-    const bool tooLow = isFirstToken && cfg.has_first_token_threshold && lp < cfg.first_token_log_prob_threshold;
-    const bool completed = tok == cfg.end_token;
-    const bool segDone = completed || n_tok >= kMaxTok - 1 || tooLow;
-    sq->steps += 1;
-    sq->first_token_too_low = tooLow ? 1 : 0;
-    if (segDone) {
-        sq->done = 1;
-        return;
-    }
-    const bool isPrefill = ti_cur < sq->prompt_len - 1;
-    int nt = n_tok;
-    if (!isPrefill) { sq->tokens[nt] = tok; sq->logprobs[nt] = lp; nt += 1; sq->n_tokens = nt; }
-    const int ti_next = ti_cur + 1;
-    if (ti_next >= cfg.loop_count) {
-        sq->done = 1;
-        return;
-    }
-    int next = tok;
-    if (ti_next < sq->prompt_len) {                                   // :581-594 (loop top of the next iteration)
-        const bool isLast = ti_next == sq->prompt_len - 1;
-        const bool isTs = sq->tokens[ti_next] >= tb;
-        const bool predTs = next >= tb;
-        if (!(isLast && isTs && predTs)) next = sq->tokens[ti_next];
-        else sq->tokens[ti_next] = next;
-    }
-    sq->token_index = ti_next;
-    sq->next_token = next;
-    // (the prompt-timestamp replacement above writes a timestamp over a timestamp: an index found before it still points at one)
-    int hint = last_ts_pre;
-    if (hint >= -1 && nt > n_tok && tok >= tb) hint = nt - 1;          // the token appended by this step is the newest timestamp
-    compute_filter_rules(cfg, sq, nt, cfg.n_vocab, sq->f_rules, hint);
 }
 
 // MODE bit 0: apply filters; bit 1: sample; bit 2: advance decodeText state; bit 3: write filtered logits back

@@ -785,6 +785,279 @@ extern "C" int wh_detect_language(wh_session* s, int batch, const wh_special_tok
     return WH_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ speculative greedy decode
+// NO REFERENCE BEHAVIOUR (spec_plan.h, spec.hip).  A proposer guesses the next K tokens of every audio; the target runs the known position
+// and the guessed ones as virtual slots of ONE decoder launch (owner-table self-attention, mapped cross-attention: the instantiations the forced pass
+// uses) under its own filters and its own fused greedy sampler, and spec_accept_kernel keeps the prefix the target would have produced itself plus
+// its own next token.  T = 0 only: tokens, log-probabilities and stop reasons are the ordinary loop's.  Eager launches, one synchronisation per round.
+constexpr int kSpecStageRegions = 2 * kMaxTok;      // a round confirms at least one position (<= 223 rounds) and stages at most two descriptor sets
+
+static int spec_ensure(wh_session* s) {
+    const size_t B = (size_t)s->B, half = std::max<size_t>(B / 2, 1);
+    if (!s->spec_master) WH_HIP(s->mem.alloc(&s->spec_master, B, true));
+    if (!s->spec_owner) WH_HIP(s->mem.alloc(&s->spec_owner, B * kMaxTok, false));
+    if (!s->slot_home_dev) WH_HIP(s->mem.alloc(&s->slot_home_dev, B, false));
+    if (!s->spec_desc) WH_HIP(s->mem.alloc_pinned(&s->spec_desc, (size_t)kSpecStageRegions * half));
+    if (!s->spec_desc_dev) WH_HIP(s->mem.alloc(&s->spec_desc_dev, (size_t)kSpecStageRegions * half, false));
+    if (!s->spec_io) WH_HIP(s->mem.alloc(&s->spec_io, half, true));
+    if (!s->spec_io_host) WH_HIP(s->mem.alloc_pinned(&s->spec_io_host, half));
+    return WH_OK;
+}
+
+// The one interface of the two public forms.  Before every round the pass tells the proposer where each audio stands (p0[a]: its first unconfirmed
+// position; live[a]) and gets the look-ahead inputs beyond the prompt either as host lists - desc[a].first / n / tok, proposals for the sampled tokens
+// first .. first + n - 1 counted from the end of the prompt - or as a device SeqState array whose histories hold them (the return value; null: the lists).
+struct SpecProposer {
+    virtual ~SpecProposer() {}
+    virtual int propose(wh_session* s, int n_audio, int K, int n_prompt, int limit, const int* p0, const char* live, SpecDesc* desc, SpecDesc* stage2,
+                        SpecDesc* stage2_dev, const SeqState** dev_src) = 0;
+    virtual void confirmed(int n_audio, const int* p0_next) {}
+    virtual int upper_k(int a, int p0, int K, int n_prompt, int limit, int end_token) const = 0;      // the look-ahead the round can arm at most
+};
+
+struct ScriptedProposer : SpecProposer {
+    const int32_t* const* lists; const int32_t* n_lists; int end_token;
+    int propose(wh_session*, int n_audio, int K, int n_prompt, int, const int* p0, const char* live, SpecDesc* desc, SpecDesc*, SpecDesc*, const SeqState** dev_src) override {
+        for (int a = 0; a < n_audio; ++a) {
+            SpecDesc& d = desc[a];
+            memset(&d, 0, sizeof(d));
+            if (!live[a]) continue;
+            d.first = std::max(p0[a] + 1 - n_prompt, 0);
+            const int have = lists && lists[a] ? n_lists[a] : 0;
+            d.n = std::max(0, std::min(K, have - d.first));
+            for (int i = 0; i < d.n; ++i) d.tok[i] = lists[a][d.first + i];
+        }
+        *dev_src = nullptr;
+        return WH_OK;
+    }
+    int upper_k(int a, int p0, int K, int n_prompt, int limit, int end) const override {
+        return plan::spec_lookahead(p0, K, n_prompt, limit, lists ? lists[a] : nullptr, lists && lists[a] ? n_lists[a] : 0, end);
+    }
+};
+
+// The draft session's slots 0 .. n_audio - 1 hold the same windows.  Per round: every draft slot is re-armed from the target's master state (the accepted
+// history as a forced prompt, resuming at resume[a], the first position the draft has not yet fed the accepted input) and steps through p0 + K with its
+// ordinary greedy step - the prompt-forcing path catches up, the samples beyond the history are the proposals, read in place by the target's arming kernel.
+// The draft's launches go to the TARGET's stream: one stream orders everything, the draft's own stream is idle (synchronised when the pass begins).
+struct DraftProposer : SpecProposer {
+    wh_session* draft;
+    std::vector<int> resume;
+    int steps_run = 0;
+    int propose(wh_session* s, int n_audio, int K, int n_prompt, int limit, const int* p0, const char* live, SpecDesc* desc, SpecDesc* stage2, SpecDesc* stage2_dev,
+                const SeqState** dev_src) override {
+        int steps = 0, first_pos = kMaxTok;
+        for (int a = 0; a < n_audio; ++a) {
+            memset(&desc[a], 0, sizeof(SpecDesc)); memset(&stage2[a], 0, sizeof(SpecDesc));
+            const bool want = live[a] && p0[a] + K >= n_prompt && p0[a] + 1 < limit;      // some look-ahead position lies beyond the prompt
+            if (!want) continue;
+            desc[a].n = K;                                                                // the target takes at most K of the draft's samples
+            stage2[a].first = resume[(size_t)a]; stage2[a].n = 1;
+            steps = std::max(steps, std::min(p0[a] + K, limit - 1) + 1 - resume[(size_t)a]);
+            first_pos = std::min(first_pos, resume[(size_t)a]);
+        }
+        steps_run = steps;
+        *dev_src = draft->seq;
+        if (steps <= 0) return WH_OK;
+        WH_HIP(hipMemcpyAsync(stage2_dev, stage2, sizeof(SpecDesc) * (size_t)n_audio, hipMemcpyHostToDevice, s->st));
+        launch_spec_arm_draft(draft->cfg_dev, s->spec_master, stage2_dev, draft->seq, n_audio, s->st);
+        for (int i = 0; i < steps; ++i) {
+            int top = 0;
+            for (int a = 0; a < n_audio; ++a) if (stage2[a].n) top = std::max(top, resume[(size_t)a] + i);
+            DecodeBuffers db = whi::decode_buffers(draft, n_audio, std::min(top, kMaxTok - 1));
+            launch_decoder_step(db, draft->cfg_dev, draft->suppress_dev, true, s->st);
+        }
+        WH_CHECK_LAUNCH();
+        draft->slot_steps += (long long)n_audio * steps;
+        for (int a = 0; a < n_audio; ++a) if (stage2[a].n) resume[(size_t)a] += steps;   // (an upper bound: confirmed() brings it down to what the target kept)
+        return WH_OK;
+    }
+    void confirmed(int n_audio, const int* p0_next) override {
+        for (int a = 0; a < n_audio; ++a) resume[(size_t)a] = std::min(resume[(size_t)a], p0_next[a]);
+    }
+    int upper_k(int, int p0, int K, int, int limit, int) const override { return std::max(0, std::min(K, limit - 1 - p0)); }
+};
+
+// Validated by the callers: n_audio K fits the session, T = 0, greedy, the prompt.  Slots 0 .. n_audio - 1 hold the windows' encoder data.
+static int spec_pass_impl(wh_session* s, int n_audio, int K, const wh_decoding_options* opt, const wh_special_tokens* st, const int32_t* prompt, int n_prompt,
+                          const int32_t* language_tokens, SpecProposer& pr, wh_decoding_result* out) {
+    const int B = s->B, V = s->m->dims.n_vocab, R = plan::spec_ring(K), width = n_audio * R;
+    int r = spec_ensure(s);
+    if (r) return r;
+    r = whi::upload_sampler_cfg(s, opt, st, 0, n_prompt, 0, opt->seed);
+    if (r) return r;
+    if (opt->word_timestamps && s->m->n_align > 0) { r = whi::ensure_align(s); if (r) return r; }
+    // every exit: the next caller of decode_buffers sees a plain session
+    struct Scope { wh_session* s; ~Scope() { s->pass_mapped = false; s->pass_owner = false; s->pass_mixed = false; s->pass_spw = 1; } } scope{s};
+    s->align_enabled = opt->word_timestamps && s->align;
+    s->fused_greedy = !knob::now<knob::WH_NO_FUSED_SAMPLER>();
+    s->pass_mixed = false; s->pass_owner = false;
+    const int limit = std::max(std::min(opt->sample_length, kMaxTok - 1), 0);      // SamplerCfg.loop_count: positions 0 .. limit - 1 exist
+    int lang_pos = -1;
+    if (language_tokens && wh_is_model_multilingual(s->m))
+        for (int i = 0; i + 1 < n_prompt; ++i) if (prompt[i] == st->start_of_transcript_token) { lang_pos = i + 1; break; }
+    for (int a = 0; a < n_audio; ++a) {                                            // the master states, as decode_text_impl starts a slot
+        SeqState& q = s->seq_host[a];
+        memset(&q, 0, sizeof(q));
+        for (int i = 0; i < n_prompt; ++i) q.tokens[i] = prompt[i];
+        if (lang_pos >= 0 && language_tokens[a] >= 0 && language_tokens[a] < V) q.tokens[lang_pos] = language_tokens[a];
+        q.n_tokens = n_prompt; q.token_index = 0; q.next_token = q.tokens[0]; q.prompt_len = n_prompt; q.active = 1; q.temperature = 0.0f; q.rng_lane = a;
+    }
+    WH_HIP(hipMemcpyAsync(s->spec_master, s->seq_host, sizeof(SeqState) * (size_t)n_audio, hipMemcpyHostToDevice, s->st));
+    launch_rules_init(s->cfg_dev, s->spec_master, n_audio, s->st);
+    WH_CHECK_LAUNCH();
+    s->decode_passes += 1; s->spec_passes += 1;
+    const size_t half = std::max<size_t>((size_t)B / 2, 1);
+    const plan::CompactPassPlan cp = plan::compact_pass_plan(width, B, B, s->use_xabs ? s->xabs.spw : 1);      // slots per absorbed-attention workgroup of the rung that holds `width` slots (results do not depend on it)
+    const int spw = cp.compact ? cp.spw : (s->use_xabs ? s->xabs.spw : 1);
+    std::vector<int> p0((size_t)n_audio, 0), p0_next((size_t)n_audio, 0);
+    std::vector<char> live((size_t)n_audio, limit > 0 ? 1 : 0);
+    int n_live = limit > 0 ? n_audio : 0;
+    size_t region = 0;
+    while (n_live > 0) {
+        if (cancelled(s)) { hipStreamSynchronize(s->st); return set_error(WH_ERR_CANCELLED, "speculative pass: cancelled through the session's cancel flag"); }
+        if (region + 2 > (size_t)kSpecStageRegions) return set_error(WH_ERR_DECODING_FAILED, "speculative pass: more rounds than positions");
+        // this round's own regions of the pinned staging (uploaded stream-ordered): the stream has consumed nothing the host writes here
+        SpecDesc* d = s->spec_desc + region * half;
+        SpecDesc* d_dev = s->spec_desc_dev + region * half;
+        const SeqState* dev_src = nullptr;
+        r = pr.propose(s, n_audio, K, n_prompt, limit, p0.data(), live.data(), d, d + half, d_dev + half, &dev_src);
+        if (r) return r;
+        region += 2;
+        int top = 0;                                          // the largest position the round can run
+        for (int a = 0; a < n_audio; ++a) if (live[a]) top = std::max(top, p0[a] + pr.upper_k(a, p0[a], K, n_prompt, limit, st->end_token));
+        WH_HIP(hipMemcpyAsync(d_dev, d, sizeof(SpecDesc) * (size_t)n_audio, hipMemcpyHostToDevice, s->st));
+        launch_spec_arm(s->cfg_dev, s->spec_master, d_dev, dev_src, s->seq, s->spec_owner, s->slot_home_dev, s->spec_io, n_audio, K, s->st);
+        s->pass_mapped = true; s->pass_spw = spw;
+        DecodeBuffers db = whi::decode_buffers(s, width, std::min(top, kMaxTok - 1));
+        db.self_owner = s->spec_owner; db.owner_slots = B;
+        launch_decoder_step(db, s->cfg_dev, s->suppress_dev, true, s->st);
+        launch_spec_accept(s->spec_master, s->seq, s->spec_io, n_audio, K, s->st);
+        WH_CHECK_LAUNCH();
+        WH_HIP(hipMemcpyAsync(s->spec_io_host, s->spec_io, sizeof(SpecRound) * (size_t)n_audio, hipMemcpyDeviceToHost, s->st));
+        WH_HIP(hipStreamSynchronize(s->st));
+        s->spec_rounds += 1; s->slot_steps += width;
+        for (int a = 0; a < n_audio; ++a) {
+            p0_next[(size_t)a] = p0[(size_t)a];
+            if (!live[a]) continue;
+            const SpecRound& o = s->spec_io_host[a];
+            if (o.k < 0 || o.k > K || o.accepted < 0 || o.accepted > o.k) return set_error(WH_ERR_DECODING_FAILED, "speculative pass: audio %d: the round reports %d of %d positions", a, o.accepted, o.k);
+            s->spec_positions += 1 + o.k; s->spec_accepted += o.accepted;
+            p0[(size_t)a] = p0_next[(size_t)a] = p0[(size_t)a] + o.accepted + (o.done ? 0 : 1);      // a finished audio stays at the last position it ran
+            if (o.done) { live[a] = 0; --n_live; }
+            else if (o.token_index != p0[(size_t)a]) return set_error(WH_ERR_DECODING_FAILED, "speculative pass: audio %d stands at position %d, the host at %d", a, o.token_index, p0[(size_t)a]);
+        }
+        pr.confirmed(n_audio, p0_next.data());
+    }
+    // The alignment rows past each audio's last position (position p writes row p + 1) are those of look-ahead positions the target did not keep: zeroed,
+    // so the rows equal an ordinary decode's.  Then the states in home-slot terms, on the device and on the host, as a plain pass leaves them.
+    if (s->align_enabled) {
+        const size_t row = (size_t)s->n_align_alloc * kCtx;
+        for (int a = 0; a < n_audio; ++a) {
+            const int from = std::min((limit > 0 ? p0[(size_t)a] : -1) + 2, kMaxTok);
+            if (from < kMaxTok) WH_HIP(hipMemsetAsync(s->align + ((size_t)a * kMaxTok + from) * row, 0, (size_t)(kMaxTok - from) * row * sizeof(float), s->st));
+        }
+    }
+    WH_HIP(hipMemsetAsync(s->seq, 0, sizeof(SeqState) * (size_t)width, s->st));
+    WH_HIP(hipMemcpyAsync(s->seq, s->spec_master, sizeof(SeqState) * (size_t)n_audio, hipMemcpyDeviceToDevice, s->st));
+    WH_HIP(hipMemcpyAsync(s->seq_host, s->spec_master, sizeof(SeqState) * (size_t)n_audio, hipMemcpyDeviceToHost, s->st));
+    WH_HIP(hipStreamSynchronize(s->st));
+    for (int a = 0; a < n_audio; ++a) whi::finalize_decoding_result(s->seq_host[a], opt, st, s->seq_host[a].temperature, &out[a]);
+    return WH_OK;
+}
+
+// what needs no session, for both entry points
+static int spec_check_args(const char* who, int n_audio, int K, const wh_decoding_options* opt, const wh_special_tokens* st, const int32_t* prompt, int n_prompt,
+                           const wh_decoding_result* out, int max_batch) {
+    if (!plan::spec_k_valid(K)) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: K = %d (1 .. %d)", who, K, plan::kSpecMaxK);
+    if (n_audio < 1) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: %d audios", who, n_audio);
+    if (!plan::spec_fits(n_audio, K, max_batch)) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: %d audios x (K + 1 = %d) slots exceed the session's %d", who, n_audio, K + 1, max_batch);
+    if (!opt || !st || !prompt || !out) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: null argument", who);
+    if (opt->temperature != 0.0f) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: temperature %g (a speculative pass is greedy at T = 0)", who, (double)opt->temperature);
+    if (opt->beam_size > 1) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: beam_size %d (a speculative pass is greedy)", who, opt->beam_size);
+    if (n_prompt < 1 || n_prompt >= kMaxTok) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: prompt length %d out of range [1,%d)", who, n_prompt, kMaxTok);
+    return WH_OK;
+}
+static int spec_check_tokens(const char* who, int n_audio, const int32_t* prompt, int n_prompt, const int32_t* const* proposals, const int32_t* n_proposals, int n_vocab) {
+    for (int i = 0; i < n_prompt; ++i)
+        if (prompt[i] < 0 || prompt[i] >= n_vocab) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: prompt token %d out of vocabulary", who, prompt[i]);
+    if (!proposals) return WH_OK;
+    if (!n_proposals) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: proposals without their counts", who);
+    for (int a = 0; a < n_audio; ++a) {
+        if (n_proposals[a] < 0 || n_proposals[a] > kMaxTok) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: audio %d has %d proposals (0 .. %d)", who, a, n_proposals[a], kMaxTok);
+        if (n_proposals[a] > 0 && !proposals[a]) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: audio %d: null proposal list", who, a);
+        for (int i = 0; i < n_proposals[a]; ++i)
+            if (proposals[a][i] < 0 || proposals[a][i] >= n_vocab) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: audio %d: proposal %d out of vocabulary", who, a, proposals[a][i]);
+    }
+    return WH_OK;
+}
+
+extern "C" int wh_decode_text_guided(wh_session* s, int n_audio, int K, const wh_decoding_options* opt, const wh_special_tokens* st, const int32_t* prompt,
+                                     int n_prompt, const int32_t* language_tokens, const int32_t* const* proposals, const int32_t* n_proposals,
+                                     wh_decoding_result* out) {
+    const char* who = "wh_decode_text_guided";
+    if (int r = spec_check_args(who, n_audio, K, opt, st, prompt, n_prompt, out, kMaxSessionSlots)) return r;
+    if (int r = spec_check_tokens(who, n_audio, prompt, n_prompt, proposals, n_proposals, kMaxVocab)) return r;
+    CHECK_SESSION(s);
+    if (int r = spec_check_args(who, n_audio, K, opt, st, prompt, n_prompt, out, s->B)) return r;
+    if (int r = spec_check_tokens(who, n_audio, prompt, n_prompt, proposals, n_proposals, s->m->dims.n_vocab)) return r;
+    WH_TRY
+    ScriptedProposer pr;
+    pr.lists = proposals; pr.n_lists = n_proposals; pr.end_token = st->end_token;
+    return spec_pass_impl(s, n_audio, K, opt, st, prompt, n_prompt, language_tokens, pr, out);
+    WH_CATCH("wh_decode_text_guided")
+}
+
+// the draft can serve `n_audio` windows of `s`: another session on the same device, the same vocabulary, the slots
+static int spec_check_draft(const char* who, const wh_session* s, const wh_session* draft, int n_audio) {
+    if (!draft || !draft->m) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: null draft session", who);
+    if (draft == s) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: the draft is the target session itself", who);
+    if (draft->m->dims.n_vocab != s->m->dims.n_vocab) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: the draft's vocabulary (%d) is not the target's (%d)", who, draft->m->dims.n_vocab, s->m->dims.n_vocab);
+    if (draft->m->device != s->m->device) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: the draft lives on device %d, the target on %d", who, draft->m->device, s->m->device);
+    if (n_audio > draft->B) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: %d audios exceed the draft session's %d slots", who, n_audio, draft->B);
+    return WH_OK;
+}
+
+extern "C" int wh_decode_text_speculative(wh_session* s, wh_session* draft, int n_audio, int K, const wh_decoding_options* opt, const wh_special_tokens* st,
+                                          const int32_t* prompt, int n_prompt, const int32_t* language_tokens, wh_decoding_result* out) {
+    const char* who = "wh_decode_text_speculative";
+    if (int r = spec_check_args(who, n_audio, K, opt, st, prompt, n_prompt, out, kMaxSessionSlots)) return r;
+    if (int r = spec_check_tokens(who, n_audio, prompt, n_prompt, nullptr, nullptr, kMaxVocab)) return r;
+    CHECK_SESSION(s);
+    if (int r = spec_check_args(who, n_audio, K, opt, st, prompt, n_prompt, out, s->B)) return r;
+    if (int r = spec_check_tokens(who, n_audio, prompt, n_prompt, nullptr, nullptr, s->m->dims.n_vocab)) return r;
+    if (int r = spec_check_draft(who, s, draft, n_audio)) return r;
+    WH_TRY
+    // the draft's sampler tables (the same options; its own vocabulary-sized masks) and switches, on its own stream, which is then idle for the pass
+    int r = whi::upload_sampler_cfg(draft, opt, st, 0, n_prompt, 0, opt->seed);
+    if (r) return r;
+    WH_HIP(hipStreamSynchronize(draft->st));
+    struct DraftScope { wh_session* d; bool fused, align; ~DraftScope() { d->fused_greedy = fused; d->align_enabled = align; } } draft_scope{draft, draft->fused_greedy, draft->align_enabled};
+    draft->fused_greedy = !knob::now<knob::WH_NO_FUSED_SAMPLER>(); draft->align_enabled = false;
+    DraftProposer pr;
+    pr.draft = draft; pr.resume.assign((size_t)n_audio, 0);
+    return spec_pass_impl(s, n_audio, K, opt, st, prompt, n_prompt, language_tokens, pr, out);
+    WH_CATCH("wh_decode_text_speculative")
+}
+
+extern "C" int wh_session_set_draft(wh_session* s, wh_session* draft, int K) {
+    if (!s || !s->m) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_draft: null session");
+    if (!draft) { s->draft = nullptr; s->draft_k = 0; return WH_OK; }
+    if (!plan::spec_k_valid(K)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_draft: K = %d (1 .. %d)", K, plan::kSpecMaxK);
+    if (int r = spec_check_draft("wh_session_set_draft", s, draft, 1)) return r;
+    s->draft = draft; s->draft_k = K;
+    return WH_OK;
+}
+extern "C" int wh_session_draft_k(const wh_session* s) { return s ? (s->draft ? s->draft_k : 0) : -1; }
+
+extern "C" int wh_session_speculative_stats(const wh_session* s, int64_t* passes, int64_t* rounds, int64_t* positions_run, int64_t* tokens_accepted) {
+    if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_speculative_stats: null session");
+    if (passes) *passes = s->spec_passes;
+    if (rounds) *rounds = s->spec_rounds;
+    if (positions_run) *positions_run = s->spec_positions;
+    if (tokens_accepted) *tokens_accepted = s->spec_accepted;
+    return WH_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ segments
 extern "C" int wh_find_seek_point_and_segments(const wh_decoding_result* res, const wh_decoding_options* opt, const wh_special_tokens* st,
                                                int all_segments_count, int current_seek, int segment_size, int32_t* new_seek,
@@ -1022,6 +1295,21 @@ static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_
                 for (int b = 0; b < nb; ++b) if (jobs[slot_job[b]].opt->language_token >= 0) ml[b] = -1;
                 const MixClasses mix{(int)classes->size(), classes->data(), cls_slot.data(), mix_pp.data(), mix_np.data(), opt_slot.data()};
                 r = decode_text_impl(s, nb, nullptr, st, nullptr, 0, langs ? ml.data() : nullptr, tv.data(), active.data(), seed, tmp.data(), &mix);
+                if (r) return r;
+            } else if (s->draft && ti == 0 && temps[ti] == 0.0f && all_active && beam == 1 && !s->progress_cb && plan::spec_fits(nb, s->draft_k, s->B) &&
+                       !spec_check_draft("wh_transcribe", s, s->draft, nb)) {
+                // first rung with a draft attached (wh_session_set_draft) and room for the rings: the speculative pass (results are the ordinary pass's).  The
+                // draft gets the same windows through its own log-mel and encoder
+                wh_session* const dr = s->draft;
+                for (int b = 0; b < nb; ++b) {
+                    const AudioJob& j = jobs[slot_job[b]];
+                    r = j.dev ? wh_set_audio_device(dr, b, j.pcm + j.cur_seek, j.cur_size) : wh_set_audio(dr, b, j.pcm + j.cur_seek, j.cur_size);
+                    if (r) return r;
+                }
+                r = wh_log_mel_spectrogram(dr, nb); if (r) return r;
+                r = wh_encode_features(dr, nb); if (r) return r;
+                r = wh_prepare_decoder_inputs(dr, nb); if (r) return r;
+                r = wh_decode_text_speculative(s, dr, nb, s->draft_k, opt, st, prompt.data(), n_prompt, langs, tmp.data());
                 if (r) return r;
             } else {
                 r = decode_text_impl(s, nb, opt, st, prompt.data(), n_prompt, langs, tv.data(), active.data(), seed, tmp.data());

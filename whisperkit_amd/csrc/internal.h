@@ -180,6 +180,16 @@ struct wh_session {
     float *forced_out = nullptr, *forced_out_host = nullptr;
     long long forced_passes = 0, forced_launches = 0, forced_positions = 0;      // wh_session_forced_pass_stats
     float* forced_capture = nullptr; size_t forced_capture_floats = 0;            // wh_debug_forced_capture: host buffer the launches' logits rows are copied to, or null
+    // speculative greedy decode (wh_decode_text_guided / wh_decode_text_speculative: host.hip spec_pass_impl, spec_plan.h, spec.hip).  Everything is allocated by
+    // the first pass: spec_master [B] (device, the audios' master states), spec_owner [B][kMaxTok] (device, the row -> owner rows of the virtual slots),
+    // spec_desc [kSpecStageRounds][B / 2] (pinned staging: a pass's rounds take consecutive regions of it, so the host never writes a region the stream has
+    // not consumed; each is uploaded to the same offset of spec_desc_dev), spec_io [B / 2] (device, what a round leaves per audio) and its pinned mirror.
+    wh::SeqState* spec_master = nullptr;
+    int32_t* spec_owner = nullptr;
+    wh::SpecDesc *spec_desc = nullptr, *spec_desc_dev = nullptr;
+    wh::SpecRound *spec_io = nullptr, *spec_io_host = nullptr;
+    wh_session* draft = nullptr; int draft_k = 0;      // wh_session_set_draft: not owned
+    long long spec_passes = 0, spec_rounds = 0, spec_positions = 0, spec_accepted = 0;      // wh_session_speculative_stats
     hipEvent_t ev[8]{};
     bool align_enabled = false;
     wh_timings last_timings{};

@@ -3,6 +3,7 @@
 #include "common.h"
 #include "launch_plan.h"
 #include "option_mix.h"
+#include "spec_plan.h"
 
 #include <atomic>
 #include <mutex>
@@ -369,6 +370,28 @@ static_assert(sizeof(ForcedDesc) == 32, "ForcedDesc: one 32-byte sector per virt
 void launch_forced_arm(const ForcedDesc* desc, SeqState* seq, int* owner, int* slot_home, int n, int n_slots, int n_vocab, hipStream_t st);
 // score: the plain log-softmax of logits rows 0 .. n - 1 ([n][n_vocab] floats) -> log p(desc[i].target), the argmax (lowest id on ties) and its log p
 void launch_forced_score(const float* logits, const ForcedDesc* desc, int n, int n_vocab, float* lp_out, int* best_out, float* best_lp_out, hipStream_t st);
+// speculative greedy decode (spec.hip, spec_plan.h): what a round knows about one audio, 128 bytes, staged in pinned memory and uploaded per round.
+//   target form: tok[i] is the proposal for the audio's sampled token first + i (counted from the end of the prompt), n of them (0 .. kSpecMaxK)
+//   draft form (the re-arming of a draft slot): first = the position the draft slot resumes at, n = 0: the slot sits the round out
+struct SpecDesc { int first, n; int tok[plan::kSpecMaxK]; int pad[15]; };
+static_assert(sizeof(SpecDesc) == 128, "SpecDesc: one 128-byte line per audio");
+// what a round leaves per audio for the next kernel and the host: the look-ahead it armed, the inputs it fed, and what the target kept
+struct SpecRound {
+    int k;                  // arm: positions p0 .. p0 + k were armed (-1: the audio was finished before the round)
+    int input[16];          // arm: the input token of position p0 + j
+    int accepted, done;     // accept: j* (look-ahead positions kept) and the audio's done flag after the round
+    int token_index;        // accept: the master state's token_index after the round
+    int pad[12];
+};
+static_assert(sizeof(SpecRound) == 128, "SpecRound: one 128-byte line per audio");
+// arm (target form): master[a] + the look-ahead inputs -> the whole SeqState of audio a's K + 1 virtual slots, their owner rows [slot][kMaxTok] and
+// home slots; draft_seq (or null): the look-ahead inputs beyond the prompt are draft_seq[a]'s own samples instead of the descriptor's list
+void launch_spec_arm(const SamplerCfg* cfg_dev, const SeqState* master, const SpecDesc* desc, const SeqState* draft_seq, SeqState* seq, int* owner,
+                     int* slot_home, SpecRound* io, int n_audio, int K, hipStream_t st);
+// arm (draft form): draft_seq[a] = master[a]'s accepted history as a forced prompt, resuming at position desc[a].first
+void launch_spec_arm_draft(const SamplerCfg* draft_cfg_dev, const SeqState* master, const SpecDesc* desc, SeqState* draft_seq, int n_audio, hipStream_t st);
+// accept: one wave per audio - the longest accepted prefix of the round, master[a] = the virtual slot's state after it
+void launch_spec_accept(SeqState* master, const SeqState* seq, SpecRound* io, int n_audio, int K, hipStream_t st);
 // standalone filter / sampler entry points (KAT surface of the C ABI)
 void launch_filter_only(const SamplerCfg* cfg_dev, const int* suppress_dev, SeqState* seq, float* logits, int n_vocab, hipStream_t st);
 void launch_sample_only(const SamplerCfg* cfg_dev, SeqState* seq, float* logits, int n_vocab, int counter, int* token_out, float* logprob_out, hipStream_t st);
