@@ -80,6 +80,27 @@ public final class HIPSession {
     /// them in one launch (csrc/spec.hip) when windows x (k + 1) fit its slots.  Same results, bit for bit; `nil` detaches.  The draft is not owned.
     public func setDraft(_ draft: HIPSession?, k: Int = 4) throws { try check(wh_session_set_draft(handle, draft?.handle, Int32(k))); self.draft = draft }
     private var draft: HIPSession?
+    /// No-speech detection (wh_session_set_no_speech_detection; NO REFERENCE BEHAVIOUR: openai/whisper `decoding.py` `no_speech_prob` semantics - WhisperKit leaves
+    /// noSpeechProb at 0): `.off` (default) = noSpeechProb is 0 and noSpeechThreshold does nothing; `.on` = noSpeechProb is p(<|nospeech|>) at the
+    /// <|startoftranscript|> step, computed on the device, so noSpeechThreshold starts to bite - turning it on changes results; `.stop` = as `.on`, and a window
+    /// with noSpeechThreshold set, logProbThreshold nil and noSpeechProb above the threshold stops decoding at that step (same TranscriptionResult).
+    public enum NoSpeechDetection: Int32 { case off = 0, on = 1, stop = 2 }
+    public var noSpeechDetection: NoSpeechDetection = .off { didSet { _ = wh_session_set_no_speech_detection(handle, noSpeechDetection.rawValue) } }
+    public var noSpeechDetectionMode: NoSpeechDetection { NoSpeechDetection(rawValue: wh_session_no_speech_detection(handle)) ?? .off }
+    /// (rows scored, scored rows above their audio's noSpeechThreshold, windows stopped by `.stop`) since the session was created
+    public func noSpeechDetectionStats() throws -> (rowsScored: Int, windowsOverThreshold: Int, windowsStopped: Int) {
+        var a: Int64 = 0, b: Int64 = 0, c: Int64 = 0
+        try check(wh_session_no_speech_stats(handle, &a, &b, &c))
+        return (Int(a), Int(b), Int(c))
+    }
+    /// The probe (wh_no_speech_probs): noSpeechProb of the encoded windows in slots 0 ..< batch from one step on <|startoftranscript|> at position 0; the decode
+    /// state is put back.  Not conditioned on promptTokens.
+    public func noSpeechProbs(batch: Int, specialTokens: wh_special_tokens) throws -> [Float] {
+        var st = specialTokens
+        var out = [Float](repeating: 0, count: batch)
+        try check(wh_no_speech_probs(handle, Int32(batch), &st, &out))
+        return out
+    }
     public enum BeamRanking: Int32 { case host = 0, device = 1 }
     public var beamRanking: BeamRanking = .host { didSet { _ = wh_session_set_beam_ranking(handle, beamRanking.rawValue) } }
     public init(model: HIPModel, maxBatch: Int = 1, crossAttention: CrossAttentionMode = .automatic, keySplits: Int = 0, slotsPerWorkgroup: Int = 0,

@@ -649,6 +649,44 @@ int wh_session_draft_k(const wh_session* s);
  * (virtual slots) those rounds ran and the look-ahead positions the target kept.  Any pointer may be NULL. */
 int wh_session_speculative_stats(const wh_session* s, int64_t* passes, int64_t* rounds, int64_t* positions_run, int64_t* tokens_accepted);
 
+/* ---- no-speech detection: NO REFERENCE BEHAVIOUR: openai/whisper `decoding.py` `no_speech_prob` semantics (csrc/nospeech_plan.h, nospeech.hip) ----
+ * The reference leaves DecodingResult.noSpeechProb at 0 (`// TODO: implement no speech prob`, TextDecoder.swift:802), so noSpeechThreshold, the
+ * "silence" answer of wh_decoding_fallback and the seeker's window skip can never fire.  With this option on, wh_decoding_result.no_speech_prob
+ * is openai/whisper's value: the probability of <|nospeech|> (st->no_speech_token) under the softmax of the RAW logits row - before any logits
+ * filter; rounded to Float16 first under float16_logits - of the step that feeds the first <|startoftranscript|> of the slot's prompt (position 0
+ * for the usual prompt, behind <|startofprev|> ... with prompt_tokens; a prompt without one, or a slot that finishes before that step, keeps 0).
+ * One small kernel between that step's logits launch and its sampler launch computes it on the device; the value depends on the window and
+ * the prompt only - every temperature rung, batch width, slot, compacted, narrowed or mixed pass reports the same bits.
+ *
+ * mode 0 (default): off.  no_speech_prob is exactly 0 and every pass launches what it has always launched.
+ * mode 1: on.  TURNING IT ON CHANGES RESULTS - that is its purpose: DecodingOptions' default noSpeechThreshold = 0.6 starts to bite.  A window whose
+ *   value exceeds its audio's no_speech_threshold reports WH_FALLBACK_SILENCE and is not decoded again at a higher temperature, and
+ *   wh_find_seek_point_and_segments skips it when log_prob_threshold is nil or the average log-probability is below it.  Segments, JSON
+ *   and wh_chunk_record carry the value.
+ * mode 2: on + stop.  As mode 1, and a window whose fate is sealed at the scoring step - no_speech_threshold set, log_prob_threshold nil
+ *   (NaN), value > no_speech_threshold - is marked done on the device there and then: its remaining steps are not decoded, in-pass compaction
+ *   can narrow the pass, no fallback rung follows.  The wh_transcription (segments, text, words, window seeks) is what mode 1 gives.  The
+ *   wh_decoding_result of a stopped window differs: its tokens are [<|startoftranscript|> ... the rest of the prompt, <|endoftext|>], it has
+ *   fewer steps and no progress reports; the timing counters (decoding loops, fallbacks) differ too.  The beam pass never stops a window.
+ *
+ * Supported: wh_decode_text, wh_decode_text_languages, wh_decode_text_mixed, every temperature rung of wh_transcribe* (greedy, sampled,
+ * compacted, narrowed, mixed, host and device audio) and wh_decode_text_beam (the value of the audio's first beam at the scoring step).
+ * NOT supported - the field stays 0: wh_decode_text_custom, wh_decode_text_guided, wh_decode_text_speculative, wh_align_tokens_batch.
+ * While the mode is not 0, wh_transcribe* ignores an attached draft (wh_session_set_draft): the first rung runs the ordinary pass and
+ * wh_session_speculative_stats shows it.  NULL session or a mode outside 0 .. 2: WH_ERR_INVALID_ARGUMENT; the getter returns -1 for NULL. */
+int wh_session_set_no_speech_detection(wh_session* s, int mode);
+int wh_session_no_speech_detection(const wh_session* s);
+/* Counters of the session since its creation: rows nospeech_kernel scored (one per decoded window and pass, the probe's rows included), scored
+ * rows whose value exceeded their audio's no_speech_threshold (per pass: a window that is decoded on two rungs counts twice), and windows
+ * mode 2 stopped.  Any pointer may be NULL. */
+int wh_session_no_speech_stats(const wh_session* s, int64_t* rows_scored, int64_t* windows_over_threshold, int64_t* windows_stopped);
+/* The probe, for callers that screen windows before they spend a decode on them: one step on <|startoftranscript|> at position 0 for the
+ * slots 0 .. batch - 1 (the shape of wh_detect_language; the windows are encoded and wh_prepare_decoder_inputs has run), the same kernel,
+ * whatever the session's mode.  The slots' decode states and the cache rows the step overwrites are put back.  For a prompt that begins
+ * with <|startoftranscript|> and Float32 logits these are the bits the decode pass reports; behind prompt_tokens the pass's value is
+ * conditioned on that prompt and the probe's is not, and under float16_logits the pass scores the rounded row and the probe the Float32 row. */
+int wh_no_speech_probs(wh_session* s, int batch, const wh_special_tokens* st, float* probs_out /* [batch] */);
+
 /* TextDecoding.detectLanguage (Core/TextDecoder.swift:420-539) */
 int wh_detect_language(wh_session* s, int batch, const wh_special_tokens* st, int32_t* language_tokens_out,
                        float* logprobs_out);

@@ -217,6 +217,11 @@ SYMBOLS = {
     "wh_session_set_draft": (I, [VP, VP, I]),
     "wh_session_draft_k": (I, [VP]),
     "wh_session_speculative_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    # no-speech detection (csrc/nospeech.hip, nospeech_plan.h)
+    "wh_session_set_no_speech_detection": (I, [VP, I]),
+    "wh_session_no_speech_detection": (I, [VP]),
+    "wh_session_no_speech_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "wh_no_speech_probs": (I, [VP, I, PST, PF]),
     "wh_prefill_prompt": (I, [VP, POPT, PST, C.c_int32, PI32, I]),
     "wh_transcribe": (I, [VP, VP, I, POPT, PST, PVP]),
     "wh_transcribe_batch": (I, [VP, PVP, PI32, I, POPT, PST, PVP]),

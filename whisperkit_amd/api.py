@@ -923,6 +923,40 @@ class Session:
         _check(self.lib.wh_session_inpass_compaction_stats(self.handle, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
 
+    NO_SPEECH_DETECTIONS = {"off": 0, "on": 1, "stop": 2}
+
+    def setNoSpeechDetection(self, mode: str):
+        """NO REFERENCE BEHAVIOUR (openai/whisper decoding.py no_speech_prob semantics; the reference leaves noSpeechProb at 0).  "off" (default) -
+        DecodingResult.noSpeechProb is exactly 0 and noSpeechThreshold does nothing; "on" - noSpeechProb is the probability of <|nospeech|> under
+        the softmax of the raw logits at the <|startoftranscript|> step, computed on the device, so the default noSpeechThreshold = 0.6 starts to
+        bite: TURNING IT ON CHANGES RESULTS (silent windows report fallback "silence", are not decoded again and are skipped by the seeker);
+        "stop" - as "on", and a window with noSpeechThreshold set, logProbThreshold None and noSpeechProb above the threshold stops decoding at
+        that step (same TranscriptionResult as "on"; the DecodingResult of a stopped window is [SOT ... EOT] with fewer steps).  Supported by
+        decodeText / decodeTextMixed / decodeTextBeam / transcribe*; decodeTextCustom, decodeTextGuided, decodeTextSpeculative and alignTokens report 0,
+        and transcribe* ignores an attached draft while the mode is not "off"."""
+        if mode not in self.NO_SPEECH_DETECTIONS:
+            raise ValueError(f"noSpeechDetection {mode!r}: expected 'off', 'on' or 'stop'")
+        _check(self.lib.wh_session_set_no_speech_detection(self.handle, self.NO_SPEECH_DETECTIONS[mode]))
+
+    @property
+    def noSpeechDetection(self) -> str:
+        return {0: "off", 1: "on", 2: "stop"}[int(self.lib.wh_session_no_speech_detection(self.handle))]
+
+    def noSpeechDetectionStats(self) -> Tuple[int, int, int]:
+        """(rows scored, scored rows above their audio's noSpeechThreshold, windows stopped by "stop") since the session was created"""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        _check(self.lib.wh_session_no_speech_stats(self.handle, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
+
+    def noSpeechProbs(self, batch: int = 1, specialTokens=None) -> List[float]:
+        """The probe: noSpeechProb of the encoded windows in slots 0 .. batch - 1 from one step on <|startoftranscript|> at position 0 (the shape of
+        detectLanguage), whatever the session's mode; the decode state is put back.  For a prompt that begins with <|startoftranscript|> these are
+        the bits a decode pass reports (Float32 logits); behind promptTokens the pass's value is conditioned on the prompt and the probe's is not."""
+        st = specialTokens if specialTokens is not None else self.model.specialTokens
+        out = (C.c_float * batch)()
+        self._guarded(self.lib.wh_no_speech_probs, self.handle, batch, C.byref(st), out)
+        return list(out)
+
     OPTION_MIXINGS = {"off": 0, "on": 1}
     MAX_OPTION_CLASSES = 16
 

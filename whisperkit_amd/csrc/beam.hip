@@ -240,6 +240,7 @@ int beam_loop_device(wh_session* s, int n_audio, int beam_size, int max_candidat
             const whi::BeamSeq& bq = A[a].beams[j];
             std::copy(bq.tok.begin(), bq.tok.end(), q.tokens);
             q.n_tokens = (int)bq.tok.size(); q.token_index = first; q.next_token = bq.tok.back(); q.prompt_len = n_prompt; q.active = 1;
+            if (s->pass_ns.lo == first) q.rng_lane = a * beam_size + j;      // no-speech detection, scoring step = the loop's first: the audio's first beam scores (lane / beam_size)
         }
     }
     WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * n_slots, hipMemcpyHostToDevice, s->st));
@@ -257,7 +258,7 @@ int beam_loop_device(wh_session* s, int n_audio, int beam_size, int max_candidat
         db.seq = seqs[in];
         db.cross_div = beam_size;
         db.self_owner = owners[in];
-        launch_decoder_step(db, nullptr, nullptr, false, s->st);
+        launch_decoder_step(db, nullptr, nullptr, false, s->st, whi::nospeech_step_args(s, token_index));
         launch_beam_filter_topk(s->cfg_dev, s->suppress_dev, seqs[in], s->logits, n_slots, beam_size + 1, s->beam_lp, s->beam_tok, s->st);
         WH_CHECK_LAUNCH();
         BeamRankArgs k{};
@@ -354,6 +355,16 @@ static int wh_decode_text_beam_impl(wh_session* s, int n_audio, int beam_size, f
     if (r) return r;
     s->align_enabled = false;
     const int loop_count = std::max(std::min(opt->sample_length, kMaxTok - 1), 0);
+    // ---- no-speech detection (NO REFERENCE BEHAVIOUR): the value comes from the audio's own slot at a scoring step inside the pre-fill, from its
+    // first beam (slot a * beam_size, lane_div = beam_size) when the scoring step is the beam loop's first.  The host loops do not read `done`: mode 2 never stops a beam pass
+    const bool ns_on = s->no_speech_detection != plan::kNoSpeechOff;
+    struct NsScope { wh_session* s; ~NsScope() { s->pass_ns = plan::NoSpeechRange{-1, -1}; } } ns_scope{s};
+    if (ns_on) {
+        const int p = plan::nospeech_position(prompt, n_prompt, st->start_of_transcript_token);
+        const std::vector<int> pos((size_t)n_audio, p);
+        r = whi::nospeech_arm(s, n_audio, pos.data(), nullptr, st->no_speech_token, p == n_prompt - 1 ? beam_size : 1);
+        if (r) return r;
+    }
     int lang_pos = -1;
     if (language_tokens && wh_is_model_multilingual(s->m))
         for (int i = 0; i + 1 < n_prompt; ++i) if (prompt[i] == st->start_of_transcript_token) { lang_pos = i + 1; break; }
@@ -366,6 +377,7 @@ static int wh_decode_text_beam_impl(wh_session* s, int n_audio, int beam_size, f
         for (int i = 0; i < n_prompt; ++i) q.tokens[i] = prompt[i];
         if (lang_pos >= 0 && language_tokens[b] >= 0 && language_tokens[b] < V) q.tokens[lang_pos] = language_tokens[b];
         q.n_tokens = n_prompt; q.token_index = prefilled_index; q.next_token = q.tokens[0]; q.prompt_len = n_prompt; q.active = 1; q.temperature = 0.0f;
+        if (ns_on) q.rng_lane = b;      // the home slot nospeech_kernel writes to (T = 0: no other reader)
     }
     s->fused_greedy = false;
     WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * n_audio, hipMemcpyHostToDevice, s->st));
@@ -373,7 +385,7 @@ static int wh_decode_text_beam_impl(wh_session* s, int n_audio, int beam_size, f
     const int n_prefill = std::min(n_prompt - 1, loop_count);
     for (int step = 0; step < n_prefill; ++step) {
         DecodeBuffers db = whi::decode_buffers(s, n_audio, step);
-        launch_decoder_step(db, s->cfg_dev, s->suppress_dev, true, s->st);
+        launch_decoder_step(db, s->cfg_dev, s->suppress_dev, true, s->st, whi::nospeech_step_args(s, step));
         WH_CHECK_LAUNCH();
     }
     WH_HIP(hipMemcpyAsync(s->seq_host, s->seq, sizeof(SeqState) * n_audio, hipMemcpyDeviceToHost, s->st));
@@ -425,6 +437,7 @@ static int wh_decode_text_beam_impl(wh_session* s, int n_audio, int beam_size, f
                 const whi::BeamSeq& bq = A[a].beams[j];
                 std::copy(bq.tok.begin(), bq.tok.end(), q.tokens);
                 q.n_tokens = (int)bq.tok.size(); q.token_index = token_index; q.next_token = bq.tok.back(); q.prompt_len = n_prompt; q.active = 1;
+                if (s->pass_ns.lo == token_index) q.rng_lane = a * beam_size + j;      // (no-speech detection: the scoring step, see above)
             }
         WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * n_slots, hipMemcpyHostToDevice, s->st));
         for (int j = 0; j < n_slots; ++j) owner[(size_t)j * kMaxTok + token_index] = j;      // the row this step writes is the slot's own
@@ -432,7 +445,7 @@ static int wh_decode_text_beam_impl(wh_session* s, int n_audio, int beam_size, f
         DecodeBuffers db = whi::decode_buffers(s, n_slots, token_index);
         db.cross_div = beam_size;
         db.self_owner = s->beam_owner;
-        launch_decoder_step(db, nullptr, nullptr, false, s->st);
+        launch_decoder_step(db, nullptr, nullptr, false, s->st, whi::nospeech_step_args(s, token_index));
         launch_beam_filter_topk(s->cfg_dev, s->suppress_dev, s->seq, s->logits, n_slots, beam_size + 1, s->beam_lp, s->beam_tok, s->st);
         WH_CHECK_LAUNCH();
         WH_HIP(hipMemcpyAsync(h_lp.data(), s->beam_lp, sizeof(float) * h_lp.size(), hipMemcpyDeviceToHost, s->st));
@@ -471,6 +484,11 @@ static int wh_decode_text_beam_impl(wh_session* s, int n_audio, int beam_size, f
         }
     }
     // ---- 4. finalize, rank, results in the reference's DecodingResult conventions (TextDecoder.swift:776-854)
+    if (ns_on) {
+        const std::vector<const wh_decoding_options*> no((size_t)n_audio, opt);
+        r = whi::nospeech_collect(s, n_audio, no.data());
+        if (r) return r;
+    }
     for (int a = 0; a < n_audio; ++a) {
         AudioBeams& ab = A[a];
         SeqState fin = greedy[a];
@@ -484,7 +502,7 @@ static int wh_decode_text_beam_impl(wh_session* s, int n_audio, int beam_size, f
         }
         fin.steps = ab.steps;
         fin.first_token_too_low = ab.first_token_too_low;
-        whi::finalize_decoding_result(fin, opt, st, 0.0f, &out[a]);
+        whi::finalize_decoding_result(fin, opt, st, 0.0f, &out[a], ns_on ? whi::nospeech_prob(s, a) : 0.0f);
     }
     return WH_OK;
 }

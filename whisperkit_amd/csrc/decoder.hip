@@ -727,7 +727,7 @@ static void launch_cross_attn(const AttnArgs& at_in, int S, int H, int B, hipStr
 // One decoder step for all slots: embed -> per layer [QKV, self-attention, out projection, cross query, cross-attention, cross out
 // projection, fc1, fc2] -> logits -> sampler.  Every activation hand-off is a plane pair in B-fragment order, every LayerNorm is
 // folded into the consumer's epilogue (see decoder32.hip).
-void launch_decoder_step(const DecodeBuffers& db, const SamplerCfg* cfg_dev, const int* suppress_dev, bool sample, hipStream_t st) {
+void launch_decoder_step(const DecodeBuffers& db, const SamplerCfg* cfg_dev, const int* suppress_dev, bool sample, hipStream_t st, const NoSpeechArgs* ns) {
     const Dec32& D = *db.d32;
     const int d = db.d, B = db.batch, H = db.n_head, L = db.n_layer, V = db.n_vocab;
     const int n_bt = (B + 31) / 32;
@@ -804,11 +804,12 @@ void launch_decoder_step(const DecodeBuffers& db, const SamplerCfg* cfg_dev, con
     const bool fused = sample && db.fused_greedy;
     P32Args a = base;           // final LayerNorm (folded) + tied-embedding logits (+ the fused greedy sampler statistics)
     a.N = V; a.K = d; a.Wt = D.emb_t; a.zhi = D.za_hi; a.zlo = D.za_lo; a.fold_g = D.lg_g; a.fold_c = D.lg_c;
-    a.logits = fused ? nullptr : db.logits; a.prof_kind = KK_DEC_LOGITS;
+    a.logits = (fused && !ns) ? nullptr : db.logits; a.prof_kind = KK_DEC_LOGITS;      // (a scoring step of the no-speech detection keeps the rows: a runtime argument, the same instantiation)
     if (sample) a.cfg = cfg_dev;                 // Float16-logits switch
     if (fused) { a.stats = db.stats; a.sup_mask = db.sup_mask; }
     const bool mixed = sample && db.mixed;       // a mixed pass (option_mix.h): the per-class tables, the mixed instantiations
     launch_dec32_proj(P32_LOGITS, a, n_bt, st, mixed && fused);
+    if (ns) launch_nospeech(*ns, db.seq, db.logits, B, V, st);      // before any sampler: the unfused one filters the rows in place, every one advances token_index
     if (fused) {
         ProfScope ps_(KK_SAMPLER, st);
         if (mixed) sampler_final_mixed_kernel<<<B, 256, 0, st>>>(cfg_dev, db.seq, db.stats, (V + 31) / 32);

@@ -223,7 +223,7 @@ extern "C" int wh_prefill_prompt(const wh_model* m, const wh_decoding_options* o
 // ------------------------------------------------------------------------------------------------ decodeText
 namespace whi {
 void finalize_decoding_result(const SeqState& sq, const wh_decoding_options* opt, const wh_special_tokens* st, float temperature,
-                              wh_decoding_result* out) {
+                              wh_decoding_result* out, float no_speech_prob) {
     // TextDecoder.swift:776-854: finalize (append EOT), slice SOT...EOT, avg log prob, compression ratio, fallback
     memset(out, 0, sizeof(*out));
     std::vector<int> tok(sq.tokens, sq.tokens + sq.n_tokens);
@@ -248,7 +248,7 @@ void finalize_decoding_result(const SeqState& sq, const wh_decoding_options* opt
     out->n_tokens = n;
     out->avg_logprob = sum / (float)n;
     out->compression_ratio = wh_compression_ratio(words.data(), (int)words.size());
-    out->no_speech_prob = 0.0f;   // TextDecoder.swift:802 (TODO in the reference)
+    out->no_speech_prob = no_speech_prob;   // 0 = TextDecoder.swift:802 (TODO in the reference); the window's value with no-speech detection on (nospeech.hip)
     out->temperature = roundf(f16_round(temperature) * 1000.0f) / 1000.0f;   // Float(sampler.temperature).rounded(3)
     out->is_first_token_logprob_too_low = sq.first_token_too_low;
     out->steps = sq.steps;
@@ -269,7 +269,8 @@ static int get_step_graph(wh_session* s, int batch, int first_step, hipGraphExec
     DecodeBuffers db = whi::decode_buffers(s, batch, first_step + kStepsPerGraph - 1);
     // (a compacted pass bakes the slot table's address, the mapped kernel instantiations and its own slots per workgroup into its launches)
     const WhGraphKey key{batch, s->align_enabled ? 1 : 0, s->fused_greedy ? 1 : 0, s->align_enabled ? s->n_align_alloc : 0, db.self_rows, db.xattn_gate ? 1 : 0,
-                         db.slot_home ? 1 : 0, db.slot_home ? s->pass_spw : 0, db.self_owner ? 1 : 0, db.mixed};
+                         db.slot_home ? 1 : 0, db.slot_home ? s->pass_spw : 0, db.self_owner ? 1 : 0, db.mixed,
+                         (int)plan::nospeech_step_mask(first_step, kStepsPerGraph, s->pass_ns)};
     auto it = s->graphs.find(key);
     if (it != s->graphs.end()) { s->graph_use[key] = ++s->graph_tick; *out = it->second; return WH_OK; }
     // The cache is capped (a large-v3 step graph holds ~2.5 k kernel nodes; a configuration = everything of the key but the row bound has up
@@ -278,7 +279,7 @@ static int get_step_graph(wh_session* s, int batch, int first_step, hipGraphExec
     const size_t cap = (size_t)knob::once<knob::WH_GRAPH_CAP>();
     while (s->graphs.size() >= cap) {
         auto same_cfg = [](const WhGraphKey& a, const WhGraphKey& b) {
-            return a.batch == b.batch && a.align == b.align && a.fused == b.fused && a.n_align == b.n_align && a.gate == b.gate && a.mapped == b.mapped && a.spw == b.spw && a.owner == b.owner && a.mixed == b.mixed;
+            return a.batch == b.batch && a.align == b.align && a.fused == b.fused && a.n_align == b.n_align && a.gate == b.gate && a.mapped == b.mapped && a.spw == b.spw && a.owner == b.owner && a.mixed == b.mixed && a.ns_mask == b.ns_mask;
         };
         const WhGraphKey* victim = nullptr;
         unsigned long long victim_last = ~0ull;
@@ -297,7 +298,7 @@ static int get_step_graph(wh_session* s, int batch, int first_step, hipGraphExec
     }
     hipGraph_t graph;
     WH_HIP(hipStreamBeginCapture(s->st, hipStreamCaptureModeThreadLocal));
-    for (int i = 0; i < kStepsPerGraph; ++i) launch_decoder_step(db, s->cfg_dev, s->suppress_dev, true, s->st);
+    for (int i = 0; i < kStepsPerGraph; ++i) launch_decoder_step(db, s->cfg_dev, s->suppress_dev, true, s->st, whi::nospeech_step_args(s, first_step + i));
     WH_HIP(hipStreamEndCapture(s->st, &graph));
     hipGraphExec_t exec;
     WH_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
@@ -349,6 +350,53 @@ static int report_progress(wh_session* s, int batch) {
     }
     return WH_OK;
 }
+
+// ---- no-speech detection (wh_session_set_no_speech_detection; NO REFERENCE BEHAVIOUR: openai/whisper decoding.py no_speech_prob semantics)
+namespace whi {
+static int nospeech_ensure(wh_session* s) {
+    const size_t n = 4 * (size_t)s->B + 2;
+    if (!s->ns_dev) WH_HIP(s->mem.alloc(&s->ns_dev, n, true));
+    if (!s->ns_host) WH_HIP(s->mem.alloc_pinned(&s->ns_host, n));
+    NoSpeechArgs& a = s->ns_args;
+    a.pos = s->ns_dev; a.stop = reinterpret_cast<const float*>(s->ns_dev + s->B); a.prob = reinterpret_cast<float*>(s->ns_dev + 2 * (size_t)s->B);
+    a.stopped = s->ns_dev + 3 * (size_t)s->B; a.cfg = s->ns_dev + 4 * (size_t)s->B; a.n_slots = s->B;
+    return WH_OK;
+}
+// The caller's stream holds no launch that reads the tables (every pass ends drained).  prob starts at -1, "not scored": a probability is never negative
+int nospeech_arm(wh_session* s, int n, const int* pos, const float* stop, int token, int lane_div) {
+    int r = nospeech_ensure(s);
+    if (r) return r;
+    const int B = s->B;
+    int32_t* h = s->ns_host;
+    const float never = INFINITY, unscored = -1.0f;
+    for (int b = 0; b < B; ++b) {
+        h[b] = b < n ? pos[b] : -1;
+        memcpy(h + B + b, (b < n && stop) ? &stop[b] : &never, sizeof(float));
+        memcpy(h + 2 * (size_t)B + b, &unscored, sizeof(float));
+        h[3 * (size_t)B + b] = 0;
+    }
+    h[4 * (size_t)B] = token; h[4 * (size_t)B + 1] = lane_div;
+    WH_HIP(hipMemcpyAsync(s->ns_dev, h, sizeof(int32_t) * (4 * (size_t)B + 2), hipMemcpyHostToDevice, s->st));
+    s->pass_ns = plan::nospeech_step_range(pos, n);
+    return WH_OK;
+}
+// behind the pass: prob | stopped by home slot into the pinned mirror (an unscored slot reads 0), the counters.  opts: null, or [n] the options whose
+// noSpeechThreshold a scored slot is counted against (null entries: not counted)
+int nospeech_collect(wh_session* s, int n, const wh_decoding_options* const* opts) {
+    const size_t B = (size_t)s->B;
+    WH_HIP(hipMemcpyAsync(s->ns_host + 2 * B, s->ns_dev + 2 * B, sizeof(int32_t) * 2 * B, hipMemcpyDeviceToHost, s->st));
+    WH_HIP(hipStreamSynchronize(s->st));
+    for (int b = 0; b < n; ++b) {
+        float p;
+        memcpy(&p, s->ns_host + 2 * B + b, sizeof(p));
+        if (p < 0.0f) { p = 0.0f; memcpy(s->ns_host + 2 * B + b, &p, sizeof(p)); continue; }
+        s->ns_rows_scored += 1;
+        if (opts && opts[b] && !isnan(opts[b]->no_speech_threshold) && p > opts[b]->no_speech_threshold) s->ns_windows_over += 1;
+        if (s->ns_host[3 * B + b]) s->ns_windows_stopped += 1;
+    }
+    return WH_OK;
+}
+}  // namespace whi
 
 // ---- in-pass compaction (wh_session_set_inpass_compaction): the layout of the pass run_token_loop drives, in the session's home-slot terms
 struct PassLayout {
@@ -422,7 +470,7 @@ static int run_token_loop(wh_session* s, int batch, int loop_count, PassLayout* 
             if (exec) { WH_HIP(hipGraphLaunch(exec, s->st)); count_steps(kStepsPerGraph); }
             else for (int i = 0; i < kStepsPerGraph && step + i < loop_count; ++i) {
                 DecodeBuffers db = whi::decode_buffers(s, width, step + i);
-                launch_decoder_step(db, s->cfg_dev, s->suppress_dev, true, s->st); WH_CHECK_LAUNCH();
+                launch_decoder_step(db, s->cfg_dev, s->suppress_dev, true, s->st, whi::nospeech_step_args(s, step + i)); WH_CHECK_LAUNCH();
                 count_steps(1);
             }
             WH_HIP(hipMemcpyAsync(s->seq_host, s->seq, sizeof(SeqState) * width, hipMemcpyDeviceToHost, s->st));
@@ -480,7 +528,7 @@ static int run_token_loop(wh_session* s, int batch, int loop_count, PassLayout* 
     } else {
         for (int step = 0; step < loop_count; ++step) {
             DecodeBuffers db = whi::decode_buffers(s, width, step);
-            launch_decoder_step(db, s->cfg_dev, s->suppress_dev, true, s->st);
+            launch_decoder_step(db, s->cfg_dev, s->suppress_dev, true, s->st, whi::nospeech_step_args(s, step));
             WH_CHECK_LAUNCH();
             count_steps(1);
             if ((step & 7) == 7 && step + 1 < loop_count) {
@@ -572,7 +620,7 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
     for (int b = 0; b < batch; ++b) n_live += (active ? active[b] != 0 : 1);
     plan::CompactPassPlan cp{false, batch, s->use_xabs ? s->xabs.spw : 1};
     if (s->fallback_compaction == 1 && active) cp = plan::compact_pass_plan(n_live, batch, s->B, s->use_xabs ? s->xabs.spw : 1);
-    struct PassScope { wh_session* s; ~PassScope() { s->pass_mapped = false; s->pass_owner = false; s->pass_mixed = false; } } pass_scope{s};      // (every exit: the next caller of decode_buffers sees a plain pass)
+    struct PassScope { wh_session* s; ~PassScope() { s->pass_mapped = false; s->pass_owner = false; s->pass_mixed = false; s->pass_ns = plan::NoSpeechRange{-1, -1}; } } pass_scope{s};      // (every exit: the next caller of decode_buffers sees a plain pass)
     const int width = cp.compact ? cp.width : batch;
     if (cp.compact) {
         if (!s->slot_home_dev) WH_HIP(s->mem.alloc(&s->slot_home_dev, (size_t)s->B, false));
@@ -585,6 +633,25 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
         s->compacted_passes += 1;
     } else {
         for (int b = 0; b < batch; ++b) init_slot(s->seq_host[b], b, active ? active[b] != 0 : true);
+    }
+    // ---- no-speech detection (wh_session_set_no_speech_detection; NO REFERENCE BEHAVIOUR): every decoded slot's scoring position - the first
+    // <|startoftranscript|> of its class's prompt - and, in mode 2, its stop threshold from the options its result is finalised under, by home slot
+    std::vector<const wh_decoding_options*> ns_opts;
+    if (s->no_speech_detection != plan::kNoSpeechOff) {
+        int cpos[kMaxOptionClasses];
+        for (int c = 0; c < n_cls; ++c) cpos[c] = plan::nospeech_position(cls_prompt(c), cls_n_prompt(c), st->start_of_transcript_token);
+        std::vector<int> pos((size_t)batch);
+        std::vector<float> stop((size_t)batch);
+        ns_opts.assign((size_t)batch, nullptr);
+        for (int b = 0; b < batch; ++b) {
+            const bool act = active ? active[b] != 0 : true;
+            const wh_decoding_options* fo = (mix && mix->slot_opts && mix->slot_opts[b]) ? mix->slot_opts[b] : cls_opt(cls_of(b));
+            pos[b] = act ? cpos[cls_of(b)] : -1;
+            stop[b] = plan::nospeech_stop_threshold(s->no_speech_detection, fo);
+            if (act) ns_opts[b] = fo;
+        }
+        r = whi::nospeech_arm(s, batch, pos.data(), stop.data(), st->no_speech_token, 1);
+        if (r) return r;
     }
     s->decode_passes += 1;
     if (mix) { s->pass_mixed = true; s->mix_mixed_passes += 1; s->mix_max_classes = std::max<long long>(s->mix_max_classes, n_cls); }
@@ -646,10 +713,12 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
         WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * batch, hipMemcpyHostToDevice, s->st));
         WH_HIP(hipStreamSynchronize(s->st));
     }
+    const bool ns_on = !ns_opts.empty();
+    if (ns_on) { r = whi::nospeech_collect(s, batch, ns_opts.data()); if (r) return r; }
     for (int b = 0; b < batch; ++b) {
         if (!s->seq_host[b].active) { memset(&out[b], 0, sizeof(out[b])); continue; }
         const wh_decoding_options* fo = (mix && mix->slot_opts && mix->slot_opts[b]) ? mix->slot_opts[b] : cls_opt(cls_of(b));      // the audio's own thresholds
-        whi::finalize_decoding_result(s->seq_host[b], fo, st, s->seq_host[b].temperature, &out[b]);
+        whi::finalize_decoding_result(s->seq_host[b], fo, st, s->seq_host[b].temperature, &out[b], ns_on ? whi::nospeech_prob(s, b) : 0.0f);
     }
     return WH_OK;
 }
@@ -782,6 +851,60 @@ extern "C" int wh_detect_language(wh_session* s, int batch, const wh_special_tok
     WH_HIP(hipMemcpyAsync(lp.data(), s->lp_out_dev, sizeof(float) * batch, hipMemcpyDeviceToHost, s->st));
     WH_HIP(hipStreamSynchronize(s->st));
     if (lp_out) for (int b = 0; b < batch; ++b) lp_out[b] = lp[b];
+    return WH_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ no-speech detection
+// NO REFERENCE BEHAVIOUR: openai/whisper `decoding.py` `no_speech_prob` semantics (nospeech_plan.h, nospeech.hip).
+extern "C" int wh_session_set_no_speech_detection(wh_session* s, int mode) {
+    if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_no_speech_detection: null session");
+    if (!plan::nospeech_mode_valid(mode)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_no_speech_detection: mode %d (0 = off, 1 = on, 2 = on + stop)", mode);
+    s->no_speech_detection = mode;
+    return WH_OK;
+}
+extern "C" int wh_session_no_speech_detection(const wh_session* s) { return s ? s->no_speech_detection : -1; }
+extern "C" int wh_session_no_speech_stats(const wh_session* s, int64_t* rows_scored, int64_t* windows_over_threshold, int64_t* windows_stopped) {
+    if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_no_speech_stats: null session");
+    if (rows_scored) *rows_scored = s->ns_rows_scored;
+    if (windows_over_threshold) *windows_over_threshold = s->ns_windows_over;
+    if (windows_stopped) *windows_stopped = s->ns_windows_stopped;
+    return WH_OK;
+}
+
+// The probe: one step on SOT at position 0 (the shape of wh_detect_language) with nospeech_kernel behind its logits launch, whatever the session's mode.
+// The slots' decode states and row 0 of their self-attention caches - what the step overwrites - are put back.
+extern "C" int wh_no_speech_probs(wh_session* s, int batch, const wh_special_tokens* st, float* probs_out) {
+    CHECK_SESSION(s); CHECK_BATCH(s, batch);
+    if (!st || !probs_out) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_no_speech_probs: null argument");
+    const wh_dims& dm = s->m->dims;
+    const size_t kv_rows = (size_t)dm.n_text_layer * s->B * dm.n_text_head, row_bytes = sizeof(f16) * kHeadDim, pitch = row_bytes * kMaxTok;
+    if (!s->ns_seq_keep) WH_HIP(s->mem.alloc(&s->ns_seq_keep, (size_t)s->B, false));
+    if (!s->ns_kv_keep) WH_HIP(s->mem.alloc(&s->ns_kv_keep, 2 * kv_rows * kHeadDim, false));
+    WH_HIP(hipMemcpyAsync(s->ns_seq_keep, s->seq, sizeof(SeqState) * batch, hipMemcpyDeviceToDevice, s->st));
+    WH_HIP(hipMemcpy2DAsync(s->ns_kv_keep, row_bytes, s->self_k, pitch, row_bytes, kv_rows, hipMemcpyDeviceToDevice, s->st));
+    WH_HIP(hipMemcpy2DAsync(s->ns_kv_keep + kv_rows * kHeadDim, row_bytes, s->self_v, pitch, row_bytes, kv_rows, hipMemcpyDeviceToDevice, s->st));
+    struct Scope { wh_session* s; ~Scope() { s->pass_ns = plan::NoSpeechRange{-1, -1}; } } scope{s};
+    const std::vector<int> pos((size_t)batch, 0);
+    int r = whi::nospeech_arm(s, batch, pos.data(), nullptr, st->no_speech_token, 1);
+    if (r) return r;
+    for (int b = 0; b < batch; ++b) {
+        SeqState& q = s->seq_host[b];
+        memset(&q, 0, sizeof(q));
+        q.tokens[0] = st->start_of_transcript_token; q.n_tokens = 1; q.next_token = st->start_of_transcript_token; q.active = 1; q.rng_lane = b;
+    }
+    WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * batch, hipMemcpyHostToDevice, s->st));
+    const bool keep = s->align_enabled;
+    s->align_enabled = false;
+    DecodeBuffers db = whi::decode_buffers(s, batch, 0);
+    s->align_enabled = keep;
+    launch_decoder_step(db, nullptr, nullptr, false, s->st, &s->ns_args);
+    WH_CHECK_LAUNCH();
+    WH_HIP(hipMemcpyAsync(s->seq, s->ns_seq_keep, sizeof(SeqState) * batch, hipMemcpyDeviceToDevice, s->st));
+    WH_HIP(hipMemcpy2DAsync(s->self_k, pitch, s->ns_kv_keep, row_bytes, row_bytes, kv_rows, hipMemcpyDeviceToDevice, s->st));
+    WH_HIP(hipMemcpy2DAsync(s->self_v, pitch, s->ns_kv_keep + kv_rows * kHeadDim, row_bytes, row_bytes, kv_rows, hipMemcpyDeviceToDevice, s->st));
+    r = whi::nospeech_collect(s, batch, nullptr);
+    if (r) return r;
+    for (int b = 0; b < batch; ++b) probs_out[b] = whi::nospeech_prob(s, b);
     return WH_OK;
 }
 
@@ -1296,9 +1419,10 @@ static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_
                 const MixClasses mix{(int)classes->size(), classes->data(), cls_slot.data(), mix_pp.data(), mix_np.data(), opt_slot.data()};
                 r = decode_text_impl(s, nb, nullptr, st, nullptr, 0, langs ? ml.data() : nullptr, tv.data(), active.data(), seed, tmp.data(), &mix);
                 if (r) return r;
-            } else if (s->draft && ti == 0 && temps[ti] == 0.0f && all_active && beam == 1 && !s->progress_cb && plan::spec_fits(nb, s->draft_k, s->B) &&
+            } else if (s->draft && s->no_speech_detection == plan::kNoSpeechOff && ti == 0 && temps[ti] == 0.0f && all_active && beam == 1 && !s->progress_cb && plan::spec_fits(nb, s->draft_k, s->B) &&
                        !spec_check_draft("wh_transcribe", s, s->draft, nb)) {
                 // first rung with a draft attached (wh_session_set_draft) and room for the rings: the speculative pass (results are the ordinary pass's).  The
+                // speculative pass reports no no-speech value, so a session with no-speech detection on runs the ordinary pass below instead.  The
                 // draft gets the same windows through its own log-mel and encoder
                 wh_session* const dr = s->draft;
                 for (int b = 0; b < nb; ++b) {

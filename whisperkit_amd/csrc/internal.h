@@ -1,5 +1,6 @@
 // Internal model / session structures behind the opaque C-ABI handles.
 #pragma once
+#include <cstring>
 #include <map>
 #include <new>
 #include <stdexcept>
@@ -10,6 +11,7 @@
 
 #include "devmem.h"
 #include "kernels.h"
+#include "nospeech_plan.h"
 #include "text.h"
 #include "whisperhip.h"
 
@@ -83,9 +85,10 @@ struct WhGraphKey {
     int mapped, spw;      // compacted pass (slot table + mapped cross-attention instantiations) and its slots per absorbed-attention workgroup; 0, 0 otherwise
     int owner;            // 1: a pass that narrowed in flight - the self-attention reads the session's row -> owner table (dec_self_attn_owner_kernel); 0 otherwise
     int mixed;            // 1: a mixed pass (option_mix.h) - the logits epilogue and the samplers run their *_mixed instantiations; 0 otherwise
+    int ns_mask;          // bit i: step i of the graph stores its logits rows and runs nospeech_kernel (nospeech_plan.h nospeech_step_mask); 0 with the mode off
     bool operator<(const WhGraphKey& o) const {
-        return std::tie(batch, align, fused, n_align, self_rows, gate, mapped, spw, owner, mixed) <
-               std::tie(o.batch, o.align, o.fused, o.n_align, o.self_rows, o.gate, o.mapped, o.spw, o.owner, o.mixed);
+        return std::tie(batch, align, fused, n_align, self_rows, gate, mapped, spw, owner, mixed, ns_mask) <
+               std::tie(o.batch, o.align, o.fused, o.n_align, o.self_rows, o.gate, o.mapped, o.spw, o.owner, o.mixed, o.ns_mask);
     }
 };
 
@@ -190,6 +193,16 @@ struct wh_session {
     wh::SpecRound *spec_io = nullptr, *spec_io_host = nullptr;
     wh_session* draft = nullptr; int draft_k = 0;      // wh_session_set_draft: not owned
     long long spec_passes = 0, spec_rounds = 0, spec_positions = 0, spec_accepted = 0;      // wh_session_speculative_stats
+    // no-speech detection (wh_session_set_no_speech_detection: host.hip nospeech_arm, nospeech_plan.h, nospeech.hip): 0 = off, 1 = on, 2 = on + stop.  Everything is
+    // allocated by the first pass that runs with the mode on: ns_dev = pos [B] | stop [B] (float) | prob [B] (float) | stopped [B] | cfg [2] (device, by home slot;
+    // what ns_args points into, at fixed addresses so that captured step graphs stay valid) and its pinned mirror ns_host.  pass_ns holds only while a pass
+    // runs whose steps lo .. hi carry the logits store and the kernel; (-1, -1) otherwise, and always with the mode off.
+    int no_speech_detection = 0;
+    int32_t *ns_dev = nullptr, *ns_host = nullptr;
+    wh::NoSpeechArgs ns_args{};
+    wh::plan::NoSpeechRange pass_ns{-1, -1};
+    wh::SeqState* ns_seq_keep = nullptr; f16* ns_kv_keep = nullptr;      // wh_no_speech_probs: the decode states and the cache rows 0 ([2][L][B][H][64]) the probe puts back
+    long long ns_rows_scored = 0, ns_windows_over = 0, ns_windows_stopped = 0;      // wh_session_no_speech_stats
     hipEvent_t ev[8]{};
     bool align_enabled = false;
     wh_timings last_timings{};
@@ -248,6 +261,13 @@ int reset_decoder_inputs_masked(wh_session* s, int batch, const int32_t* active)
 int alignment_paths(wh_session* s, int batch, const int32_t* rows, const int32_t** len, const int32_t** ti, const int32_t** tj);
 // host logic shared by wh_decode_text / wh_transcribe (host.hip)
 void transcription_truncate_segments(wh_transcription* t, int n_keep);     // results.cpp: drop segments [n_keep, end) with their tokens / words
+// no_speech_prob: the window's value (no-speech detection, nospeech.hip), or 0 - the reference's constant
 void finalize_decoding_result(const wh::SeqState& sq, const wh_decoding_options* opt, const wh_special_tokens* st,
-                              float temperature, wh_decoding_result* out);
+                              float temperature, wh_decoding_result* out, float no_speech_prob = 0.0f);
+// no-speech detection (host.hip): allocate the tables; arm them for a pass over the home slots 0 .. n - 1 (pos / stop by home slot, null stop: never) and set
+// pass_ns; read prob | stopped back behind the pass (the stream is drained) and count.  prob of home slot b: nospeech_prob(s, b)
+int nospeech_arm(wh_session* s, int n, const int* pos, const float* stop, int token, int lane_div);
+int nospeech_collect(wh_session* s, int n, const wh_decoding_options* const* opts);
+inline float nospeech_prob(const wh_session* s, int b) { float v; memcpy(&v, s->ns_host + 2 * (size_t)s->B + b, sizeof(v)); return v; }
+inline const wh::NoSpeechArgs* nospeech_step_args(const wh_session* s, int step) { return wh::plan::nospeech_step_in_range(step, s->pass_ns) ? &s->ns_args : nullptr; }
 }  // namespace whi

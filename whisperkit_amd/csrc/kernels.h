@@ -350,7 +350,22 @@ void launch_xabs_vup(const XabsArgs& a, int n_bt, hipStream_t st);
 // db.mixed (a mixed pass, option_mix.h): cfg_dev / suppress_dev / db.sup_mask are the session's per-class tables [kMaxOptionClasses] /
 // [kMaxOptionClasses][kMaxSuppress] / [kMaxOptionClasses][option_mask_stride(V)] and every slot reads the entry of its class (seq_class) - the
 // *_mixed instantiations; otherwise entry 0 through the instantiations that have always run
-void launch_decoder_step(const DecodeBuffers& db, const SamplerCfg* cfg_dev, const int* suppress_dev, bool sample, hipStream_t st);
+// no-speech detection (nospeech.hip, nospeech_plan.h; NO REFERENCE BEHAVIOUR: openai/whisper decoding.py no_speech_prob semantics): what nospeech_kernel reads and
+// writes, session memory at fixed addresses.  Every table is indexed by HOME slot (seq_lane(SeqState.rng_lane) / lane_div): a value survives fallback
+// compaction and in-pass narrowing.  lane_div > 1 (the beam loop, slot = audio x beam_size + beam): only the first beam of an audio scores, into entry audio.
+struct NoSpeechArgs {
+    const int* pos;          // [n_slots] scoring position (token_index of the step that feeds <|startoftranscript|>), -1: none
+    const float* stop;       // [n_slots] stop threshold (mode 2: p > stop marks the slot done), +inf: never
+    float* prob;             // [n_slots] out: p(<|nospeech|>)
+    int* stopped;            // [n_slots] out: 1 where the kernel stopped the slot
+    const int* cfg;          // [2] the <|nospeech|> id, lane_div - device memory, so that a captured step graph does not bake a call's values in
+    int n_slots;             // the session's slot count
+};
+// one workgroup per slot of `batch`: a live slot whose token_index equals its scoring position scores its row of logits ([batch][n_vocab], as the step's
+// logits launch wrote it) - between the logits launch and the sampler launch of a step
+void launch_nospeech(const NoSpeechArgs& a, SeqState* seq, const float* logits, int batch, int n_vocab, hipStream_t st);
+// ns (or null): the step stores its logits rows even on the fused-greedy path and runs nospeech_kernel between the logits launch and the sampler launch
+void launch_decoder_step(const DecodeBuffers& db, const SamplerCfg* cfg_dev, const int* suppress_dev, bool sample, hipStream_t st, const NoSpeechArgs* ns = nullptr);
 // filter rules of the first sampling step of a decodeText call (later steps: computed by the sampler itself)
 void launch_rules_init(const SamplerCfg* cfg_dev, SeqState* seq, int batch, hipStream_t st, bool mixed = false);
 // in-pass compaction (compact.hip): the decode state of a narrowing pass moves through a home-indexed array [n_slots].  park: seq_home[home[i]] = seq[i]
