@@ -101,6 +101,39 @@ public final class HIPSession {
         try check(wh_no_speech_probs(handle, Int32(batch), &st, &out))
         return out
     }
+    /// Device logit rules (wh_session_set_logit_rules; NO REFERENCE BEHAVIOUR: the semantics are transformers' `SequenceBiasLogitsProcessor` (single-token
+    /// sequences), `RepetitionPenaltyLogitsProcessor` and `NoRepeatNGramLogitsProcessor`, applied in the order `generate` applies them).  An opt-in rule set
+    /// of the session, applied on the device to the raw logits row of every live slot at every step, before the session's own filters - what a custom
+    /// `LogitsFiltering` object does on the host, at any batch width.  The history is the slot's sampled text tokens: the prompt, timestamps and special
+    /// tokens never count.  Setting rules changes results; the defaults (the neutral set) turn the mode off.
+    public func setLogitRules(repetitionPenalty: Float = 1.0, noRepeatNgramSize: Int = 0, tokenBias: [(token: Int32, bias: Float)] = []) throws {
+        let ids = tokenBias.map { $0.token }, vals = tokenBias.map { $0.bias }
+        try ids.withUnsafeBufferPointer { ip in
+            try vals.withUnsafeBufferPointer { vp in
+                var r: wh_logit_rules = .init()
+                wh_logit_rules_default(&r)
+                r.repetition_penalty = repetitionPenalty; r.no_repeat_ngram_size = Int32(noRepeatNgramSize); r.n_bias = Int32(ids.count)
+                r.bias_tokens = ids.isEmpty ? nil : ip.baseAddress; r.bias_values = vals.isEmpty ? nil : vp.baseAddress
+                try check(wh_session_set_logit_rules(handle, &r))
+            }
+        }
+    }
+    public func logitRules() throws -> (repetitionPenalty: Float, noRepeatNgramSize: Int, tokenBias: [(token: Int32, bias: Float)]) {
+        var r: wh_logit_rules = .init()
+        try check(wh_session_logit_rules(handle, &r))
+        let bias = (0 ..< Int(r.n_bias)).map { (token: r.bias_tokens![$0], bias: r.bias_values![$0]) }
+        return (r.repetition_penalty, Int(r.no_repeat_ngram_size), bias)
+    }
+    /// (decode passes that ran under rules, launches of logit_rules_kernel in them) since the session was created
+    public func logitRulesStats() throws -> (passes: Int, launches: Int) {
+        var a: Int64 = 0, b: Int64 = 0
+        try check(wh_session_logit_rules_stats(handle, &a, &b))
+        return (Int(a), Int(b))
+    }
+    /// Development aid (wh_debug_logit_rules_apply): the kernel alone over caller-supplied rows and token lists ([nRows][224]), in place
+    public func debugLogitRulesApply(rows: inout [Float], nRows: Int, tokens: [Int32], nTokens: [Int32], promptLens: [Int32]) throws {
+        try check(wh_debug_logit_rules_apply(handle, &rows, Int32(nRows), tokens, nTokens, promptLens))
+    }
     public enum BeamRanking: Int32 { case host = 0, device = 1 }
     public var beamRanking: BeamRanking = .host { didSet { _ = wh_session_set_beam_ranking(handle, beamRanking.rawValue) } }
     public init(model: HIPModel, maxBatch: Int = 1, crossAttention: CrossAttentionMode = .automatic, keySplits: Int = 0, slotsPerWorkgroup: Int = 0,

@@ -687,6 +687,54 @@ int wh_session_no_speech_stats(const wh_session* s, int64_t* rows_scored, int64_
  * conditioned on that prompt and the probe's is not, and under float16_logits the pass scores the rounded row and the probe the Float32 row. */
 int wh_no_speech_probs(wh_session* s, int batch, const wh_special_tokens* st, float* probs_out /* [batch] */);
 
+/* ---- device logit rules: NO REFERENCE BEHAVIOUR: the semantics are transformers' `SequenceBiasLogitsProcessor` (single-token sequences),
+ * `RepetitionPenaltyLogitsProcessor` and `NoRepeatNGramLogitsProcessor`, applied in the order `generate` applies them
+ * (csrc/logit_rules_plan.h, logit_rules.hip) ----
+ * The reference lets a caller install LogitsFiltering objects that run before the built-in chain (Core/Text/LogitsFilter.swift:8-10,
+ * TextDecoder.swift:860-862); here that hook is wh_decode_text_custom, a host loop over one window.  The three filters callers ask for in
+ * practice are declarative and run on the device inside the step graphs instead, at any batch width: an opt-in rule set of the session,
+ * applied to the raw logits row of every live slot at every step - after the no-speech kernel has read the row, before the session's own
+ * filters (under float16_logits: on the rounded row, in fp32; the sampler rounds again as it does for a custom filter).  Per slot and step:
+ *   1. history H = the slot's sampled text tokens: tokens[prompt_len .. n_tokens) with every id >= special_token_begin dropped.  The
+ *      prompt (prompt_tokens / prefix_tokens included) never counts; timestamps, <|endoftext|>, task and language tokens never count.
+ *   2. bias: for every entry i: row[bias_tokens[i]] += bias_values[i] (one fp32 add).  At most 256 entries, ids in [0, n_vocab), no id
+ *      twice, every value finite or -inf.
+ *   3. repetition_penalty p (finite, > 0; 1 = off): for every DISTINCT t in H: row[t] = row[t] < 0 ? row[t] * p : row[t] / p.
+ *   4. no_repeat_ngram_size n (0 = off, 1 .. 8): if |H| >= n - 1, for every i in [0, |H| - n] with H[i .. i+n-1) == H[|H|-n+1 .. |H|):
+ *      row[H[i+n-1]] = -inf.  n = 1 bans every token of H.
+ * A pass under rules runs the unfused sampler (as under WH_NO_FUSED_SAMPLER) with one more small kernel per step in front of it.
+ * SETTING RULES CHANGES RESULTS - that is their purpose.  With no rules set every pass launches exactly what it has always launched.
+ *
+ * Runs in: wh_decode_text, wh_decode_text_languages, wh_decode_text_mixed and every temperature rung of wh_transcribe* (greedy, sampled,
+ * compacted, narrowed, mixed, host and device audio).  Does NOT run in wh_detect_language, wh_no_speech_probs, wh_score_tokens /
+ * wh_align_tokens_batch and wh_decode_text_custom (its caller brings their own filters).  With rules set, wh_decode_text_beam,
+ * wh_decode_text_guided, wh_decode_text_speculative and a wh_transcribe* audio with beam_size > 1 return WH_ERR_INVALID_ARGUMENT (for
+ * wh_transcribe_batch* that is the audio's own status), and wh_transcribe* ignores an attached draft (wh_session_set_draft). */
+typedef struct wh_logit_rules {
+    float repetition_penalty;       /* 1 = off */
+    int32_t no_repeat_ngram_size;   /* 0 = off */
+    int32_t n_bias;
+    int32_t reserved_;
+    const int32_t* bias_tokens;     /* [n_bias] */
+    const float* bias_values;       /* [n_bias] */
+} wh_logit_rules;
+void wh_logit_rules_default(wh_logit_rules* r);   /* the neutral set: 1, 0, no bias */
+/* Copies the rules into the session (its device copy is rewritten in place: captured step graphs stay valid).  NULL or the neutral set
+ * (repetition_penalty == 1, no_repeat_ngram_size == 0, n_bias == 0) turns the mode off.  An invalid set returns WH_ERR_INVALID_ARGUMENT
+ * and leaves the session as it was. */
+int wh_session_set_logit_rules(wh_session* s, const wh_logit_rules* rules);
+/* The session's copy (the neutral set when the mode is off); the arrays belong to the session and hold until the next setter call. */
+int wh_session_logit_rules(const wh_session* s, wh_logit_rules* out);
+/* Counters since the session's creation: decode passes that ran under rules, and launches of logit_rules_kernel in them (one per step).
+ * Either pointer may be NULL. */
+int wh_session_logit_rules_stats(const wh_session* s, int64_t* passes, int64_t* launches);
+/* Development aid: logit_rules_kernel alone, under the session's rule set (which must be set), over caller-supplied rows and histories.
+ * rows_inout [n_rows][n_vocab] are filtered in place; row i's token list is tokens[i * WH_MAX_TOKEN_CONTEXT ...] with n_tokens[i] entries
+ * of which the first prompt_lens[i] are the prompt.  special_token_begin is that of wh_special_tokens_default.  n_rows <= max_batch;
+ * the decode states of slots 0 .. n_rows - 1 and the logits buffer are overwritten. */
+int wh_debug_logit_rules_apply(wh_session* s, float* rows_inout, int n_rows, const int32_t* tokens, const int32_t* n_tokens,
+                               const int32_t* prompt_lens);
+
 /* TextDecoding.detectLanguage (Core/TextDecoder.swift:420-539) */
 int wh_detect_language(wh_session* s, int batch, const wh_special_tokens* st, int32_t* language_tokens_out,
                        float* logprobs_out);

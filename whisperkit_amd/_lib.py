@@ -78,6 +78,12 @@ class WhProgress(C.Structure):
                 ("compression_ratio", C.c_float), ("text", C.c_char_p)]
 
 
+class WhLogitRules(C.Structure):
+    """wh_logit_rules (device logit rules, csrc/logit_rules_plan.h): 32 bytes"""
+    _fields_ = [("repetition_penalty", C.c_float), ("no_repeat_ngram_size", C.c_int32), ("n_bias", C.c_int32), ("reserved_", C.c_int32),
+                ("bias_tokens", C.POINTER(C.c_int32)), ("bias_values", C.POINTER(C.c_float))]
+
+
 PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(WhProgress))
 WINDOW_PRE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int)
 WINDOW_POST_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int)
@@ -222,6 +228,12 @@ SYMBOLS = {
     "wh_session_no_speech_detection": (I, [VP]),
     "wh_session_no_speech_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "wh_no_speech_probs": (I, [VP, I, PST, PF]),
+    # device logit rules (csrc/logit_rules.hip, logit_rules_plan.h)
+    "wh_logit_rules_default": (None, [C.POINTER(WhLogitRules)]),
+    "wh_session_set_logit_rules": (I, [VP, C.POINTER(WhLogitRules)]),
+    "wh_session_logit_rules": (I, [VP, C.POINTER(WhLogitRules)]),
+    "wh_session_logit_rules_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "wh_debug_logit_rules_apply": (I, [VP, PF, I, PI32, PI32, PI32]),
     "wh_prefill_prompt": (I, [VP, POPT, PST, C.c_int32, PI32, I]),
     "wh_transcribe": (I, [VP, VP, I, POPT, PST, PVP]),
     "wh_transcribe_batch": (I, [VP, PVP, PI32, I, POPT, PST, PVP]),

@@ -957,6 +957,38 @@ class Session:
         self._guarded(self.lib.wh_no_speech_probs, self.handle, batch, C.byref(st), out)
         return list(out)
 
+    def setLogitRules(self, repetitionPenalty: float = 1.0, noRepeatNgramSize: int = 0, tokenBias=None):
+        """NO REFERENCE BEHAVIOUR: the semantics are transformers' SequenceBiasLogitsProcessor (single-token sequences), RepetitionPenaltyLogitsProcessor and
+        NoRepeatNGramLogitsProcessor, applied in the order `generate` applies them.  An opt-in rule set of the session, applied on the device to the raw
+        logits row of every live slot at every step, before the session's own filters (csrc/logit_rules.hip):
+          tokenBias           {id: bias} or [(id, bias), ...]: row[id] += bias; at most 256 distinct ids of the vocabulary, every bias finite or -inf
+          repetitionPenalty   p (finite, > 0; 1 = off): every distinct text token the slot has sampled: row[t] = row[t] * p if row[t] < 0 else row[t] / p
+          noRepeatNgramSize   n (0 = off, 1 .. 8): a token that would complete an n-gram of text tokens the slot has already sampled gets -inf
+        The history is the slot's sampled text tokens only: the prompt (promptTokens / prefixTokens), timestamps and special tokens never count.
+        SETTING RULES CHANGES RESULTS.  No arguments (the neutral set) turns the mode off.  Runs in decodeText / decodeTextMixed / transcribe*
+        (every temperature rung, compacted, narrowed and mixed passes) under the unfused sampler; decodeTextCustom, detectLanguage, noSpeechProbs and
+        the forced pass do not run the rules; decodeTextBeam / decodeTextGuided / decodeTextSpeculative and beamSize > 1 in transcribe* are refused
+        while rules are set, and transcribe* ignores an attached draft."""
+        pairs = list(tokenBias.items()) if isinstance(tokenBias, dict) else list(tokenBias or [])
+        ids = np.ascontiguousarray([int(t) for t, _ in pairs], dtype=np.int32)
+        vals = np.ascontiguousarray([float(b) for _, b in pairs], dtype=np.float32)
+        r = L.WhLogitRules(float(repetitionPenalty), int(noRepeatNgramSize), len(pairs), 0,
+                           ids.ctypes.data_as(L.PI32) if len(pairs) else None, vals.ctypes.data_as(L.PF) if len(pairs) else None)
+        _check(self.lib.wh_session_set_logit_rules(self.handle, C.byref(r)))
+
+    def logitRules(self) -> dict:
+        """the session's rule set: {"repetitionPenalty", "noRepeatNgramSize", "tokenBias": [(id, bias), ...]} - the neutral set when the mode is off"""
+        r = L.WhLogitRules()
+        _check(self.lib.wh_session_logit_rules(self.handle, C.byref(r)))
+        return {"repetitionPenalty": float(r.repetition_penalty), "noRepeatNgramSize": int(r.no_repeat_ngram_size),
+                "tokenBias": [(int(r.bias_tokens[i]), float(r.bias_values[i])) for i in range(r.n_bias)]}
+
+    def logitRulesStats(self) -> Tuple[int, int]:
+        """(decode passes that ran under rules, launches of logit_rules_kernel in them) since the session was created"""
+        a, b = C.c_int64(), C.c_int64()
+        _check(self.lib.wh_session_logit_rules_stats(self.handle, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
     OPTION_MIXINGS = {"off": 0, "on": 1}
     MAX_OPTION_CLASSES = 16
 

@@ -270,7 +270,7 @@ static int get_step_graph(wh_session* s, int batch, int first_step, hipGraphExec
     // (a compacted pass bakes the slot table's address, the mapped kernel instantiations and its own slots per workgroup into its launches)
     const WhGraphKey key{batch, s->align_enabled ? 1 : 0, s->fused_greedy ? 1 : 0, s->align_enabled ? s->n_align_alloc : 0, db.self_rows, db.xattn_gate ? 1 : 0,
                          db.slot_home ? 1 : 0, db.slot_home ? s->pass_spw : 0, db.self_owner ? 1 : 0, db.mixed,
-                         (int)plan::nospeech_step_mask(first_step, kStepsPerGraph, s->pass_ns)};
+                         (int)plan::nospeech_step_mask(first_step, kStepsPerGraph, s->pass_ns), s->pass_lr ? 1 : 0};
     auto it = s->graphs.find(key);
     if (it != s->graphs.end()) { s->graph_use[key] = ++s->graph_tick; *out = it->second; return WH_OK; }
     // The cache is capped (a large-v3 step graph holds ~2.5 k kernel nodes; a configuration = everything of the key but the row bound has up
@@ -279,7 +279,7 @@ static int get_step_graph(wh_session* s, int batch, int first_step, hipGraphExec
     const size_t cap = (size_t)knob::once<knob::WH_GRAPH_CAP>();
     while (s->graphs.size() >= cap) {
         auto same_cfg = [](const WhGraphKey& a, const WhGraphKey& b) {
-            return a.batch == b.batch && a.align == b.align && a.fused == b.fused && a.n_align == b.n_align && a.gate == b.gate && a.mapped == b.mapped && a.spw == b.spw && a.owner == b.owner && a.mixed == b.mixed && a.ns_mask == b.ns_mask;
+            return a.batch == b.batch && a.align == b.align && a.fused == b.fused && a.n_align == b.n_align && a.gate == b.gate && a.mapped == b.mapped && a.spw == b.spw && a.owner == b.owner && a.mixed == b.mixed && a.ns_mask == b.ns_mask && a.logit_rules == b.logit_rules;
         };
         const WhGraphKey* victim = nullptr;
         unsigned long long victim_last = ~0ull;
@@ -298,7 +298,7 @@ static int get_step_graph(wh_session* s, int batch, int first_step, hipGraphExec
     }
     hipGraph_t graph;
     WH_HIP(hipStreamBeginCapture(s->st, hipStreamCaptureModeThreadLocal));
-    for (int i = 0; i < kStepsPerGraph; ++i) launch_decoder_step(db, s->cfg_dev, s->suppress_dev, true, s->st, whi::nospeech_step_args(s, first_step + i));
+    for (int i = 0; i < kStepsPerGraph; ++i) launch_decoder_step(db, s->cfg_dev, s->suppress_dev, true, s->st, whi::nospeech_step_args(s, first_step + i), whi::logit_rules_step_args(s));
     WH_HIP(hipStreamEndCapture(s->st, &graph));
     hipGraphExec_t exec;
     WH_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
@@ -450,7 +450,7 @@ static int run_token_loop(wh_session* s, int batch, int loop_count, PassLayout* 
     int width = batch;                                   // (changes only through inpass_narrow)
     auto all_done_in = [](const SeqState* q, int n) { for (int b = 0; b < n; ++b) if (q[b].active && !q[b].done) return false; return true; };
     auto all_done = [&]() { return all_done_in(s->seq_host, width); };
-    auto count_steps = [&](int steps) { s->slot_steps += (long long)width * steps; if (L) s->inpass_slot_steps_saved += (long long)(L->width0 - width) * steps; };
+    auto count_steps = [&](int steps) { s->slot_steps += (long long)width * steps; if (L) s->inpass_slot_steps_saved += (long long)(L->width0 - width) * steps; if (s->pass_lr) s->lr_launches += steps; };
     // the last read of the pass: the compact slots, or - after a narrowing - every state by home slot (parked once more)
     auto final_read = [&]() -> int {
         if (L && L->switches > 0) {
@@ -470,7 +470,7 @@ static int run_token_loop(wh_session* s, int batch, int loop_count, PassLayout* 
             if (exec) { WH_HIP(hipGraphLaunch(exec, s->st)); count_steps(kStepsPerGraph); }
             else for (int i = 0; i < kStepsPerGraph && step + i < loop_count; ++i) {
                 DecodeBuffers db = whi::decode_buffers(s, width, step + i);
-                launch_decoder_step(db, s->cfg_dev, s->suppress_dev, true, s->st, whi::nospeech_step_args(s, step + i)); WH_CHECK_LAUNCH();
+                launch_decoder_step(db, s->cfg_dev, s->suppress_dev, true, s->st, whi::nospeech_step_args(s, step + i), whi::logit_rules_step_args(s)); WH_CHECK_LAUNCH();
                 count_steps(1);
             }
             WH_HIP(hipMemcpyAsync(s->seq_host, s->seq, sizeof(SeqState) * width, hipMemcpyDeviceToHost, s->st));
@@ -528,7 +528,7 @@ static int run_token_loop(wh_session* s, int batch, int loop_count, PassLayout* 
     } else {
         for (int step = 0; step < loop_count; ++step) {
             DecodeBuffers db = whi::decode_buffers(s, width, step);
-            launch_decoder_step(db, s->cfg_dev, s->suppress_dev, true, s->st, whi::nospeech_step_args(s, step));
+            launch_decoder_step(db, s->cfg_dev, s->suppress_dev, true, s->st, whi::nospeech_step_args(s, step), whi::logit_rules_step_args(s));
             WH_CHECK_LAUNCH();
             count_steps(1);
             if ((step & 7) == 7 && step + 1 < loop_count) {
@@ -620,7 +620,7 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
     for (int b = 0; b < batch; ++b) n_live += (active ? active[b] != 0 : 1);
     plan::CompactPassPlan cp{false, batch, s->use_xabs ? s->xabs.spw : 1};
     if (s->fallback_compaction == 1 && active) cp = plan::compact_pass_plan(n_live, batch, s->B, s->use_xabs ? s->xabs.spw : 1);
-    struct PassScope { wh_session* s; ~PassScope() { s->pass_mapped = false; s->pass_owner = false; s->pass_mixed = false; s->pass_ns = plan::NoSpeechRange{-1, -1}; } } pass_scope{s};      // (every exit: the next caller of decode_buffers sees a plain pass)
+    struct PassScope { wh_session* s; ~PassScope() { s->pass_mapped = false; s->pass_owner = false; s->pass_mixed = false; s->pass_ns = plan::NoSpeechRange{-1, -1}; s->pass_lr = false; } } pass_scope{s};      // (every exit: the next caller of decode_buffers sees a plain pass)
     const int width = cp.compact ? cp.width : batch;
     if (cp.compact) {
         if (!s->slot_home_dev) WH_HIP(s->mem.alloc(&s->slot_home_dev, (size_t)s->B, false));
@@ -659,6 +659,14 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
     s->fused_greedy = true;
     for (int b = 0; b < width; ++b) if (s->seq_host[b].active && s->seq_host[b].temperature != 0.0f) s->fused_greedy = false;
     if (knob::now<knob::WH_NO_FUSED_SAMPLER>()) s->fused_greedy = false;
+    // ---- device logit rules (wh_session_set_logit_rules; NO REFERENCE BEHAVIOUR): the unfused sampler with logit_rules_kernel in front of it at every
+    // step.  The setter wrote the rule set; the history's cut-off is this call's special_token_begin
+    if (s->logit_rules_on) {
+        s->fused_greedy = false;
+        s->lr_host[2] = st->special_token_begin;
+        WH_HIP(hipMemcpyAsync(s->lr_dev + 2, s->lr_host + 2, sizeof(int32_t), hipMemcpyHostToDevice, s->st));
+        s->pass_lr = true; s->lr_passes += 1;
+    }
     WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * width, hipMemcpyHostToDevice, s->st));
     launch_rules_init(s->cfg_dev, s->seq, width, s->st, mix != nullptr);
     int loop_count = 0;       // a slot finishes at its class's count (SamplerCfg.loop_count); the host loop runs to the largest
@@ -908,6 +916,92 @@ extern "C" int wh_no_speech_probs(wh_session* s, int batch, const wh_special_tok
     return WH_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ device logit rules
+// NO REFERENCE BEHAVIOUR: the semantics are transformers' `SequenceBiasLogitsProcessor` (single-token sequences), `RepetitionPenaltyLogitsProcessor` and
+// `NoRepeatNGramLogitsProcessor`, applied in the order `generate` applies them (logit_rules_plan.h, logit_rules.hip).
+extern "C" void wh_logit_rules_default(wh_logit_rules* r) {
+    if (!r) return;
+    memset(r, 0, sizeof(*r));
+    r->repetition_penalty = 1.0f;
+}
+// The setter writes the device copy: the stream is drained on both sides, so no launch reads a half-written set and the next pass reads the new one
+// through the address its graphs captured.
+extern "C" int wh_session_set_logit_rules(wh_session* s, const wh_logit_rules* rules) {
+    if (!s || !s->m) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_logit_rules: null session");
+    if (const char* why = plan::logit_rules_invalid(rules, s->m->dims.n_vocab)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_logit_rules: %s", why);
+    if (plan::logit_rules_neutral(rules)) {
+        s->logit_rules_on = false;
+        s->lr_rules = wh_logit_rules{1.0f, 0, 0, 0, nullptr, nullptr};
+        return WH_OK;
+    }
+    if (hipSetDevice(s->m->device) != hipSuccess) return set_error(WH_ERR_HIP, "wh_session_set_logit_rules: hipSetDevice(%d) failed", s->m->device);
+    if (!s->lr_dev) WH_HIP(s->mem.alloc(&s->lr_dev, (size_t)plan::kLogitRulesWords, false));      // (not zeroed: a memset on the null stream could land behind the copy below, which writes every word)
+    if (!s->lr_host) WH_HIP(s->mem.alloc_pinned(&s->lr_host, (size_t)plan::kLogitRulesWords));
+    WH_HIP(hipStreamSynchronize(s->st));
+    int32_t* h = s->lr_host;
+    memset(h, 0, sizeof(int32_t) * plan::kLogitRulesWords);
+    memcpy(h, &rules->repetition_penalty, sizeof(float));
+    h[1] = rules->no_repeat_ngram_size; h[2] = s->m->dims.n_vocab; h[3] = rules->n_bias;      // (h[2], the history's cut-off: every pass writes its own special_token_begin)
+    for (int i = 0; i < rules->n_bias; ++i) {
+        s->lr_bias_tokens[i] = rules->bias_tokens[i]; s->lr_bias_values[i] = rules->bias_values[i];
+        h[plan::kLogitRulesHead + i] = rules->bias_tokens[i];
+        memcpy(h + plan::kLogitRulesHead + plan::kLogitRulesMaxBias + i, &rules->bias_values[i], sizeof(float));
+    }
+    WH_HIP(hipMemcpyAsync(s->lr_dev, h, sizeof(int32_t) * plan::kLogitRulesWords, hipMemcpyHostToDevice, s->st));
+    WH_HIP(hipStreamSynchronize(s->st));
+    s->lr_rules = wh_logit_rules{rules->repetition_penalty, rules->no_repeat_ngram_size, rules->n_bias, 0, s->lr_bias_tokens, s->lr_bias_values};
+    s->logit_rules_on = true;
+    return WH_OK;
+}
+// The session's copy; its arrays stay valid until the next setter call.  The neutral set when the mode is off
+extern "C" int wh_session_logit_rules(const wh_session* s, wh_logit_rules* out) {
+    if (!s || !out) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_logit_rules: null argument");
+    *out = s->lr_rules;
+    return WH_OK;
+}
+extern "C" int wh_session_logit_rules_stats(const wh_session* s, int64_t* passes, int64_t* launches) {
+    if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_logit_rules_stats: null session");
+    if (passes) *passes = s->lr_passes;
+    if (launches) *launches = s->lr_launches;
+    return WH_OK;
+}
+
+// Development aid: logit_rules_kernel alone over caller-supplied rows and histories - n_rows (<= max_batch) rows of the model's vocabulary go into the session's
+// logits buffer (row i where a launch leaves slot i's row), slot i's decode state gets tokens [i][WH_MAX_TOKEN_CONTEXT], n_tokens[i] and prompt_lens[i],
+// one launch under the session's rule set, the rows come back.  The history's cut-off is the special_token_begin of wh_special_tokens_default.
+extern "C" int wh_debug_logit_rules_apply(wh_session* s, float* rows_inout, int n_rows, const int32_t* tokens, const int32_t* n_tokens, const int32_t* prompt_lens) {
+    CHECK_SESSION(s); CHECK_BATCH(s, n_rows);
+    if (!rows_inout || !tokens || !n_tokens || !prompt_lens) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_logit_rules_apply: null argument");
+    if (!s->logit_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_logit_rules_apply: the session has no logit rules set (wh_session_set_logit_rules)");
+    const int V = s->m->dims.n_vocab;
+    for (int i = 0; i < n_rows; ++i) {
+        if (n_tokens[i] < 0 || n_tokens[i] > kMaxTok || prompt_lens[i] < 0 || prompt_lens[i] > n_tokens[i])
+            return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_logit_rules_apply: row %d has %d tokens, prompt length %d (0 <= prompt <= tokens <= %d)", i, n_tokens[i], prompt_lens[i], kMaxTok);
+        for (int k = 0; k < n_tokens[i]; ++k)
+            if (tokens[(size_t)i * kMaxTok + k] < 0 || tokens[(size_t)i * kMaxTok + k] >= V)
+                return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_logit_rules_apply: row %d token %d out of vocabulary", i, tokens[(size_t)i * kMaxTok + k]);
+    }
+    wh_special_tokens st;
+    memset(&st, 0, sizeof(st));
+    if (wh_special_tokens_default(s->m, &st) != WH_OK) st.special_token_begin = V;
+    WH_HIP(hipStreamSynchronize(s->st));                  // nothing in flight reads the staging the host writes next
+    for (int i = 0; i < n_rows; ++i) {
+        SeqState& q = s->seq_host[i];
+        memset(&q, 0, sizeof(q));
+        for (int k = 0; k < n_tokens[i]; ++k) q.tokens[k] = tokens[(size_t)i * kMaxTok + k];
+        q.n_tokens = n_tokens[i]; q.prompt_len = prompt_lens[i]; q.active = 1; q.rng_lane = i;
+    }
+    s->lr_host[2] = st.special_token_begin;
+    WH_HIP(hipMemcpyAsync(s->lr_dev + 2, s->lr_host + 2, sizeof(int32_t), hipMemcpyHostToDevice, s->st));
+    WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * n_rows, hipMemcpyHostToDevice, s->st));
+    WH_HIP(hipMemcpyAsync(s->logits, rows_inout, sizeof(float) * (size_t)n_rows * V, hipMemcpyHostToDevice, s->st));
+    launch_logit_rules(s->lr_dev, s->seq, s->logits, n_rows, V, s->st);
+    WH_CHECK_LAUNCH();
+    WH_HIP(hipMemcpyAsync(rows_inout, s->logits, sizeof(float) * (size_t)n_rows * V, hipMemcpyDeviceToHost, s->st));
+    WH_HIP(hipStreamSynchronize(s->st));
+    return WH_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ speculative greedy decode
 // NO REFERENCE BEHAVIOUR (spec_plan.h, spec.hip).  A proposer guesses the next K tokens of every audio; the target runs the known position
 // and the guessed ones as virtual slots of ONE decoder launch (owner-table self-attention, mapped cross-attention: the instantiations the forced pass
@@ -1123,6 +1217,7 @@ extern "C" int wh_decode_text_guided(wh_session* s, int n_audio, int K, const wh
     CHECK_SESSION(s);
     if (int r = spec_check_args(who, n_audio, K, opt, st, prompt, n_prompt, out, s->B)) return r;
     if (int r = spec_check_tokens(who, n_audio, prompt, n_prompt, proposals, n_proposals, s->m->dims.n_vocab)) return r;
+    if (s->logit_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: the session has logit rules set (wh_session_set_logit_rules), which the speculative pass does not run", who);
     WH_TRY
     ScriptedProposer pr;
     pr.lists = proposals; pr.n_lists = n_proposals; pr.end_token = st->end_token;
@@ -1149,6 +1244,7 @@ extern "C" int wh_decode_text_speculative(wh_session* s, wh_session* draft, int 
     if (int r = spec_check_args(who, n_audio, K, opt, st, prompt, n_prompt, out, s->B)) return r;
     if (int r = spec_check_tokens(who, n_audio, prompt, n_prompt, nullptr, nullptr, s->m->dims.n_vocab)) return r;
     if (int r = spec_check_draft(who, s, draft, n_audio)) return r;
+    if (s->logit_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: the session has logit rules set (wh_session_set_logit_rules), which the speculative pass does not run", who);
     WH_TRY
     // the draft's sampler tables (the same options; its own vocabulary-sized masks) and switches, on its own stream, which is then idle for the pass
     int r = whi::upload_sampler_cfg(draft, opt, st, 0, n_prompt, 0, opt->seed);
@@ -1296,6 +1392,7 @@ static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_
     // beam search (no reference behaviour, wh_decode_text_beam): the T = 0 pass expands every window into beam_size slots
     const int beam = opt->beam_size > 1 ? opt->beam_size : 1;
     if (beam > 1 && opt->word_timestamps) return set_error(WH_ERR_INVALID_ARGUMENT, "beam_size > 1 cannot be combined with word_timestamps");
+    if (beam > 1 && s->logit_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "beam_size > 1 cannot be combined with the session's logit rules (wh_session_set_logit_rules)");
     if (beam > s->B) return set_error(WH_ERR_INVALID_ARGUMENT, "beam_size %d exceeds the session's %d slots", beam, s->B);
     const int round_cap = s->B / beam;
     std::vector<int> slot_job;   // job index per slot for the current round
@@ -1419,10 +1516,10 @@ static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_
                 const MixClasses mix{(int)classes->size(), classes->data(), cls_slot.data(), mix_pp.data(), mix_np.data(), opt_slot.data()};
                 r = decode_text_impl(s, nb, nullptr, st, nullptr, 0, langs ? ml.data() : nullptr, tv.data(), active.data(), seed, tmp.data(), &mix);
                 if (r) return r;
-            } else if (s->draft && s->no_speech_detection == plan::kNoSpeechOff && ti == 0 && temps[ti] == 0.0f && all_active && beam == 1 && !s->progress_cb && plan::spec_fits(nb, s->draft_k, s->B) &&
+            } else if (s->draft && s->no_speech_detection == plan::kNoSpeechOff && !s->logit_rules_on && ti == 0 && temps[ti] == 0.0f && all_active && beam == 1 && !s->progress_cb && plan::spec_fits(nb, s->draft_k, s->B) &&
                        !spec_check_draft("wh_transcribe", s, s->draft, nb)) {
                 // first rung with a draft attached (wh_session_set_draft) and room for the rings: the speculative pass (results are the ordinary pass's).  The
-                // speculative pass reports no no-speech value, so a session with no-speech detection on runs the ordinary pass below instead.  The
+                // speculative pass reports no no-speech value and runs no logit rules, so a session with either on runs the ordinary pass below instead.  The
                 // draft gets the same windows through its own log-mel and encoder
                 wh_session* const dr = s->draft;
                 for (int b = 0; b < nb; ++b) {

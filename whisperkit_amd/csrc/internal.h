@@ -11,6 +11,7 @@
 
 #include "devmem.h"
 #include "kernels.h"
+#include "logit_rules_plan.h"
 #include "nospeech_plan.h"
 #include "text.h"
 #include "whisperhip.h"
@@ -86,9 +87,10 @@ struct WhGraphKey {
     int owner;            // 1: a pass that narrowed in flight - the self-attention reads the session's row -> owner table (dec_self_attn_owner_kernel); 0 otherwise
     int mixed;            // 1: a mixed pass (option_mix.h) - the logits epilogue and the samplers run their *_mixed instantiations; 0 otherwise
     int ns_mask;          // bit i: step i of the graph stores its logits rows and runs nospeech_kernel (nospeech_plan.h nospeech_step_mask); 0 with the mode off
+    int logit_rules;      // 1: every step runs logit_rules_kernel before the (unfused) sampler (wh_session_set_logit_rules); 0 with no rules set
     bool operator<(const WhGraphKey& o) const {
-        return std::tie(batch, align, fused, n_align, self_rows, gate, mapped, spw, owner, mixed, ns_mask) <
-               std::tie(o.batch, o.align, o.fused, o.n_align, o.self_rows, o.gate, o.mapped, o.spw, o.owner, o.mixed, o.ns_mask);
+        return std::tie(batch, align, fused, n_align, self_rows, gate, mapped, spw, owner, mixed, ns_mask, logit_rules) <
+               std::tie(o.batch, o.align, o.fused, o.n_align, o.self_rows, o.gate, o.mapped, o.spw, o.owner, o.mixed, o.ns_mask, o.logit_rules);
     }
 };
 
@@ -203,6 +205,17 @@ struct wh_session {
     wh::plan::NoSpeechRange pass_ns{-1, -1};
     wh::SeqState* ns_seq_keep = nullptr; f16* ns_kv_keep = nullptr;      // wh_no_speech_probs: the decode states and the cache rows 0 ([2][L][B][H][64]) the probe puts back
     long long ns_rows_scored = 0, ns_windows_over = 0, ns_windows_stopped = 0;      // wh_session_no_speech_stats
+    // device logit rules (wh_session_set_logit_rules: host.hip, logit_rules_plan.h, logit_rules.hip).  logit_rules_on: a set other than the neutral one is
+    // installed; lr_rules is the session's copy (its arrays are lr_bias_tokens / lr_bias_values).  lr_dev (device, kLogitRulesWords words at a fixed address,
+    // so that captured step graphs stay valid when values change) and its pinned mirror lr_host are allocated by the first setter that installs rules.
+    // pass_lr holds only while decode_text_impl runs a pass under the rules (the unfused sampler, the kernel in front of it).
+    bool logit_rules_on = false;
+    wh_logit_rules lr_rules{1.0f, 0, 0, 0, nullptr, nullptr};
+    int32_t lr_bias_tokens[wh::plan::kLogitRulesMaxBias] = {};
+    float lr_bias_values[wh::plan::kLogitRulesMaxBias] = {};
+    int32_t *lr_dev = nullptr, *lr_host = nullptr;
+    bool pass_lr = false;
+    long long lr_passes = 0, lr_launches = 0;      // wh_session_logit_rules_stats
     hipEvent_t ev[8]{};
     bool align_enabled = false;
     wh_timings last_timings{};
@@ -270,4 +283,6 @@ int nospeech_arm(wh_session* s, int n, const int* pos, const float* stop, int to
 int nospeech_collect(wh_session* s, int n, const wh_decoding_options* const* opts);
 inline float nospeech_prob(const wh_session* s, int b) { float v; memcpy(&v, s->ns_host + 2 * (size_t)s->B + b, sizeof(v)); return v; }
 inline const wh::NoSpeechArgs* nospeech_step_args(const wh_session* s, int step) { return wh::plan::nospeech_step_in_range(step, s->pass_ns) ? &s->ns_args : nullptr; }
+// device logit rules: the rule set a step of the running pass hands to launch_decoder_step, or null (no rules set, or a pass that does not run them)
+inline const int* logit_rules_step_args(const wh_session* s) { return s->pass_lr ? s->lr_dev : nullptr; }
 }  // namespace whi

@@ -364,8 +364,14 @@ struct NoSpeechArgs {
 // one workgroup per slot of `batch`: a live slot whose token_index equals its scoring position scores its row of logits ([batch][n_vocab], as the step's
 // logits launch wrote it) - between the logits launch and the sampler launch of a step
 void launch_nospeech(const NoSpeechArgs& a, SeqState* seq, const float* logits, int batch, int n_vocab, hipStream_t st);
+// device logit rules (logit_rules.hip, logit_rules_plan.h; NO REFERENCE BEHAVIOUR: transformers' SequenceBias / RepetitionPenalty / NoRepeatNGram processors):
+// one workgroup per slot of `batch`: a live slot applies the session's rule set (`rules`: logit_rules_plan.h kLogitRulesWords words of device memory) to its
+// row of logits ([batch][n_vocab], as the step's logits launch wrote it) from the history in its SeqState - between the logits launch and the sampler launch
+void launch_logit_rules(const int* rules, const SeqState* seq, float* logits, int batch, int n_vocab, hipStream_t st);
 // ns (or null): the step stores its logits rows even on the fused-greedy path and runs nospeech_kernel between the logits launch and the sampler launch
-void launch_decoder_step(const DecodeBuffers& db, const SamplerCfg* cfg_dev, const int* suppress_dev, bool sample, hipStream_t st, const NoSpeechArgs* ns = nullptr);
+// logit_rules (or null; only with the unfused sampler): logit_rules_kernel runs behind it, before the sampler
+void launch_decoder_step(const DecodeBuffers& db, const SamplerCfg* cfg_dev, const int* suppress_dev, bool sample, hipStream_t st, const NoSpeechArgs* ns = nullptr,
+                         const int* logit_rules = nullptr);
 // filter rules of the first sampling step of a decodeText call (later steps: computed by the sampler itself)
 void launch_rules_init(const SamplerCfg* cfg_dev, SeqState* seq, int batch, hipStream_t st, bool mixed = false);
 // in-pass compaction (compact.hip): the decode state of a narrowing pass moves through a home-indexed array [n_slots].  park: seq_home[home[i]] = seq[i]
