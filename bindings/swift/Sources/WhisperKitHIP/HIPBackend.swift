@@ -134,6 +134,46 @@ public final class HIPSession {
     public func debugLogitRulesApply(rows: inout [Float], nRows: Int, tokens: [Int32], nTokens: [Int32], promptLens: [Int32]) throws {
         try check(wh_debug_logit_rules_apply(handle, &rows, Int32(nRows), tokens, nTokens, promptLens))
     }
+    /// Device phrase rules (wh_session_set_phrase_rules; NO REFERENCE BEHAVIOUR: the semantics are transformers' `SequenceBiasLogitsProcessor` for sequences of
+    /// any length, of which `NoBadWordsLogitsProcessor` is the special case bias = -inf).  An opt-in rule set of the session that bans or boosts multi-token
+    /// sequences: when the slot's sampled text tokens end with all ids of a sequence but the last, the last id's logit gets the bias - on the device, at
+    /// every step of every live slot, before the logit rules and the session's own filters.  1 ... 16 ids per sequence, at most 4096 sequences, every bias
+    /// finite or -inf.  Setting rules changes results; an empty list turns the mode off.  Out of scope: text in place of ids, beam search under rules,
+    /// retraction of a bias when a partial match breaks, per-audio rule sets.
+    public func setPhraseRules(_ sequences: [(tokens: [Int32], bias: Float)] = []) throws {
+        let flat = sequences.flatMap { $0.tokens }, lens = sequences.map { Int32($0.tokens.count) }, vals = sequences.map { $0.bias }
+        try flat.withUnsafeBufferPointer { fp in
+            try lens.withUnsafeBufferPointer { lp in
+                try vals.withUnsafeBufferPointer { vp in
+                    var r: wh_phrase_rules = .init()
+                    r.n_sequences = Int32(sequences.count)
+                    r.tokens = flat.isEmpty ? nil : fp.baseAddress; r.lengths = lens.isEmpty ? nil : lp.baseAddress; r.biases = vals.isEmpty ? nil : vp.baseAddress
+                    try check(wh_session_set_phrase_rules(handle, &r))
+                }
+            }
+        }
+    }
+    public func phraseRules() throws -> [(tokens: [Int32], bias: Float)] {
+        var r: wh_phrase_rules = .init()
+        try check(wh_session_phrase_rules(handle, &r))
+        var out: [(tokens: [Int32], bias: Float)] = [], at = 0
+        for i in 0 ..< Int(r.n_sequences) {
+            let n = Int(r.lengths![i])
+            out.append((tokens: (0 ..< n).map { r.tokens![at + $0] }, bias: r.biases![i]))
+            at += n
+        }
+        return out
+    }
+    /// (decode passes that ran under phrase rules, launches of phrase_rules_kernel in them, matches of sequences of two or more ids counted on the device)
+    public func phraseRulesStats() throws -> (passes: Int, launches: Int, matches: Int) {
+        var a: Int64 = 0, b: Int64 = 0, c: Int64 = 0
+        try check(wh_session_phrase_rules_stats(handle, &a, &b, &c))
+        return (Int(a), Int(b), Int(c))
+    }
+    /// Development aid (wh_debug_phrase_rules_apply): the kernel alone over caller-supplied rows and token lists ([nRows][224]), in place
+    public func debugPhraseRulesApply(rows: inout [Float], nRows: Int, tokens: [Int32], nTokens: [Int32], promptLens: [Int32], live: [Int32]? = nil) throws {
+        try check(wh_debug_phrase_rules_apply(handle, &rows, Int32(nRows), tokens, nTokens, promptLens, live))
+    }
     public enum BeamRanking: Int32 { case host = 0, device = 1 }
     public var beamRanking: BeamRanking = .host { didSet { _ = wh_session_set_beam_ranking(handle, beamRanking.rawValue) } }
     public init(model: HIPModel, maxBatch: Int = 1, crossAttention: CrossAttentionMode = .automatic, keySplits: Int = 0, slotsPerWorkgroup: Int = 0,

@@ -735,6 +735,55 @@ int wh_session_logit_rules_stats(const wh_session* s, int64_t* passes, int64_t* 
 int wh_debug_logit_rules_apply(wh_session* s, float* rows_inout, int n_rows, const int32_t* tokens, const int32_t* n_tokens,
                                const int32_t* prompt_lens);
 
+/* ---- device phrase rules: NO REFERENCE BEHAVIOUR: the semantics are transformers' `SequenceBiasLogitsProcessor` for sequences of any length
+ * (of which `NoBadWordsLogitsProcessor` is the special case bias = -inf), applied to input_ids = [sentinel] + H, where the sentinel occurs in
+ * no sequence (csrc/phrase_rules_plan.h, phrase_rules.hip) ----
+ * Ban or boost MULTI-TOKEN sequences: stock hallucinations ("Thanks for watching!"), words that are several tokens long, custom
+ * vocabulary.  wh_logit_rules biases single tokens only; until now a phrase rule meant the one-window host loop of wh_decode_text_custom.
+ * An opt-in rule set of the session: an ordered list of (sequence, bias) - a sequence is 1 .. 16 ids in [0, n_vocab), a bias is finite or
+ * -inf, no sequence twice, at most 4096 sequences (both limits are design constants that size one fixed device table per session, not
+ * measured values).  Applied on the device to the raw Float32 logits row of every live slot at every step, before the logit rules and the
+ * session's own filters.  Per slot and step:
+ *   1. history H = the history of the logit rules, unchanged: tokens[prompt_len .. n_tokens) with every id >= special_token_begin dropped.
+ *      The prompt never counts; timestamps never count, so a phrase still matches across a segment boundary (intended).  A prefix id at
+ *      or above special_token_begin can never match; it is not refused, since the setter does not know a pass's special tokens.
+ *   2. match: a sequence of length L with prefix seq[0 .. L-1) and target t = seq[L-1] matches iff |H| >= L - 1 and the last L - 1
+ *      entries of H equal the prefix.  L = 1 always matches.
+ *   3. sum: for every distinct target t: sum_t in Float32 from +0.0f, first the length-1 entry for t if there is one, then the biases of
+ *      the matching longer sequences in caller order; row[t] = row[t] + sum_t.  Only targets of the table are written.
+ * With wh_session_set_logit_rules also set: phrase rules first, then the logit rules - a phrase rule and a token bias on one token give
+ * (row + sum_t) + b.  A pass under phrase rules runs the unfused sampler with one more small kernel per step in front of it.
+ * SETTING RULES CHANGES RESULTS - that is their purpose.  With no rules set every pass launches exactly what it has always launched.
+ *
+ * Runs in: wh_decode_text, wh_decode_text_languages, wh_decode_text_mixed and every temperature rung of wh_transcribe* (greedy, sampled,
+ * compacted, narrowed, mixed, host and device audio).  Does NOT run in wh_detect_language, wh_no_speech_probs, wh_score_tokens /
+ * wh_align_tokens_batch and wh_decode_text_custom (its caller brings their own filters).  With rules set, wh_decode_text_beam,
+ * wh_decode_text_guided, wh_decode_text_speculative and a wh_transcribe* audio with beam_size > 1 return WH_ERR_INVALID_ARGUMENT (for
+ * wh_transcribe_batch* that is the audio's own status), and wh_transcribe* ignores an attached draft (wh_session_set_draft).
+ * Out of scope: text-in APIs (the library has no tokenizer encode: ids in, as everywhere else), beam search under rules, retraction of
+ * a bias when a partial match breaks, per-audio rule sets (session-level, like the logit rules), more than 4096 sequences. */
+typedef struct wh_phrase_rules {
+    int32_t n_sequences;            /* 0 = off */
+    int32_t reserved_;
+    const int32_t* tokens;          /* the sequences one behind the other: lengths[0] ids, then lengths[1] ids, ... */
+    const int32_t* lengths;         /* [n_sequences], each 1 .. 16 */
+    const float* biases;            /* [n_sequences] */
+} wh_phrase_rules;
+/* Copies the rules into the session (its device table is rewritten in place, stream-ordered on the session's stream: captured step graphs
+ * stay valid).  NULL or an empty set turns the mode off.  An invalid set returns WH_ERR_INVALID_ARGUMENT and leaves the session as it was. */
+int wh_session_set_phrase_rules(wh_session* s, const wh_phrase_rules* rules);
+/* The session's copy (n_sequences == 0 when the mode is off); the arrays belong to the session and hold until the next setter call. */
+int wh_session_phrase_rules(const wh_session* s, wh_phrase_rules* out);
+/* Counters since the session's creation: decode passes that ran under phrase rules, launches of phrase_rules_kernel in them (one per
+ * step), and matches: (slot, step, sequence of length >= 2) triples whose prefix matched, counted on the device and read with one 8-byte
+ * copy after a stream synchronise.  Any pointer may be NULL.  The logit-rule counters never move because of phrase rules. */
+int wh_session_phrase_rules_stats(const wh_session* s, int64_t* passes, int64_t* launches, int64_t* matches);
+/* Development aid: phrase_rules_kernel alone, under the session's rule set (which must be set), over caller-supplied rows and histories,
+ * in the shape of wh_debug_logit_rules_apply.  live (or NULL: every row): row i is a live slot iff live[i] != 0; other rows come back
+ * untouched.  The launch's matches go into the session's counter. */
+int wh_debug_phrase_rules_apply(wh_session* s, float* rows_inout, int n_rows, const int32_t* tokens, const int32_t* n_tokens,
+                                const int32_t* prompt_lens, const int32_t* live);
+
 /* TextDecoding.detectLanguage (Core/TextDecoder.swift:420-539) */
 int wh_detect_language(wh_session* s, int batch, const wh_special_tokens* st, int32_t* language_tokens_out,
                        float* logprobs_out);

@@ -84,6 +84,12 @@ class WhLogitRules(C.Structure):
                 ("bias_tokens", C.POINTER(C.c_int32)), ("bias_values", C.POINTER(C.c_float))]
 
 
+class WhPhraseRules(C.Structure):
+    """wh_phrase_rules (device phrase rules, csrc/phrase_rules_plan.h): 32 bytes"""
+    _fields_ = [("n_sequences", C.c_int32), ("reserved_", C.c_int32), ("tokens", C.POINTER(C.c_int32)), ("lengths", C.POINTER(C.c_int32)),
+                ("biases", C.POINTER(C.c_float))]
+
+
 PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(WhProgress))
 WINDOW_PRE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int)
 WINDOW_POST_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int)
@@ -234,6 +240,11 @@ SYMBOLS = {
     "wh_session_logit_rules": (I, [VP, C.POINTER(WhLogitRules)]),
     "wh_session_logit_rules_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "wh_debug_logit_rules_apply": (I, [VP, PF, I, PI32, PI32, PI32]),
+    # device phrase rules (csrc/phrase_rules.hip, phrase_rules_plan.h)
+    "wh_session_set_phrase_rules": (I, [VP, C.POINTER(WhPhraseRules)]),
+    "wh_session_phrase_rules": (I, [VP, C.POINTER(WhPhraseRules)]),
+    "wh_session_phrase_rules_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "wh_debug_phrase_rules_apply": (I, [VP, PF, I, PI32, PI32, PI32, PI32]),
     "wh_prefill_prompt": (I, [VP, POPT, PST, C.c_int32, PI32, I]),
     "wh_transcribe": (I, [VP, VP, I, POPT, PST, PVP]),
     "wh_transcribe_batch": (I, [VP, PVP, PI32, I, POPT, PST, PVP]),

@@ -989,6 +989,49 @@ class Session:
         _check(self.lib.wh_session_logit_rules_stats(self.handle, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
 
+    def setPhraseRules(self, sequences=None):
+        """NO REFERENCE BEHAVIOUR: the semantics are transformers' SequenceBiasLogitsProcessor for sequences of any length (of which NoBadWordsLogitsProcessor is
+        the special case bias = -inf), applied to input_ids = [sentinel] + H.  An opt-in rule set of the session that bans or boosts MULTI-TOKEN sequences,
+        applied on the device to the raw logits row of every live slot at every step, before the logit rules and the session's own filters
+        (csrc/phrase_rules.hip):
+          sequences   {(id, ...): bias} or [((id, ...), bias), ...]: 1 .. 16 ids of the vocabulary each, every bias finite or -inf, no sequence twice, at
+                      most 4096 sequences.  When the slot's sampled text tokens end with ids[:-1], row[ids[-1]] gets the bias; a sequence of one id always
+                      applies.  Several sequences on one target are summed first (fp32 from +0.0: the one-id entry, then the matching longer ones in the
+                      caller's order) and added once.
+        The history is that of setLogitRules: the prompt (promptTokens / prefixTokens), timestamps and special tokens never count, so a phrase still matches
+        across a segment boundary, and a prefix id at or above specialTokenBegin never matches (it is not refused).  api.phraseBoost builds a boost list.
+        SETTING RULES CHANGES RESULTS.  No argument or an empty list turns the mode off.  Runs wherever the logit rules run (decodeText / decodeTextMixed /
+        transcribe*: every temperature rung, compacted, narrowed and mixed passes) under the unfused sampler; decodeTextCustom, detectLanguage, noSpeechProbs
+        and the forced pass do not run the rules; decodeTextBeam / decodeTextGuided / decodeTextSpeculative and beamSize > 1 in transcribe* are refused while
+        rules are set, and transcribe* ignores an attached draft.  Out of scope: text in place of ids, beam search under rules, retraction of a bias when
+        a partial match breaks, per-audio rule sets, more than 4096 sequences."""
+        pairs = list(sequences.items()) if isinstance(sequences, dict) else list(sequences or [])
+        seqs = [[int(t) for t in seq] for seq, _ in pairs]
+        flat = np.ascontiguousarray([t for seq in seqs for t in seq], dtype=np.int32)
+        lens = np.ascontiguousarray([len(seq) for seq in seqs], dtype=np.int32)
+        vals = np.ascontiguousarray([float(b) for _, b in pairs], dtype=np.float32)
+        r = L.WhPhraseRules(len(pairs), 0, flat.ctypes.data_as(L.PI32) if len(flat) else None, lens.ctypes.data_as(L.PI32) if len(pairs) else None,
+                            vals.ctypes.data_as(L.PF) if len(pairs) else None)
+        _check(self.lib.wh_session_set_phrase_rules(self.handle, C.byref(r)))
+
+    def phraseRules(self) -> list:
+        """the session's phrase rules, in the caller's order: [((id, ...), bias), ...] - empty when the mode is off"""
+        r = L.WhPhraseRules()
+        _check(self.lib.wh_session_phrase_rules(self.handle, C.byref(r)))
+        out, at = [], 0
+        for i in range(r.n_sequences):
+            n = int(r.lengths[i])
+            out.append((tuple(int(r.tokens[at + k]) for k in range(n)), float(r.biases[i])))
+            at += n
+        return out
+
+    def phraseRulesStats(self) -> Tuple[int, int, int]:
+        """(decode passes that ran under phrase rules, launches of phrase_rules_kernel in them, (slot, step, sequence of two or more ids) matches counted on
+        the device) since the session was created"""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        _check(self.lib.wh_session_phrase_rules_stats(self.handle, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
+
     OPTION_MIXINGS = {"off": 0, "on": 1}
     MAX_OPTION_CLASSES = 16
 
@@ -1267,6 +1310,26 @@ class Session:
 
 
 # ---- host utilities (no GPU needed) ---------------------------------------------------------------
+MAX_PHRASE_LENGTH, MAX_PHRASE_SEQUENCES = 16, 4096      # csrc/phrase_rules_plan.h kPhraseMaxLen, kPhraseMaxSeqs (design constants)
+
+
+def phraseBoost(phrases, bias: float) -> List[Tuple[Tuple[int, ...], float]]:
+    """Custom vocabulary for Session.setPhraseRules (NO REFERENCE BEHAVIOUR): every phrase (a sequence of token ids) expands into all of its prefixes of one
+    or more ids, each with `bias`, so that every token of the phrase is boosted while the decode is on the phrase's path - the first token always, the k-th
+    once the k - 1 before it have been sampled.  A prefix that several phrases share is kept once (the first).  Raises ValueError when a phrase is empty or
+    longer than 16 ids, or the list passes 4096 sequences."""
+    out = {}
+    for phrase in phrases:
+        ids = tuple(int(t) for t in phrase)
+        if not 1 <= len(ids) <= MAX_PHRASE_LENGTH:
+            raise ValueError(f"phraseBoost: a phrase of {len(ids)} ids (1 .. {MAX_PHRASE_LENGTH})")
+        for n in range(1, len(ids) + 1):
+            out.setdefault(ids[:n], float(bias))
+    if len(out) > MAX_PHRASE_SEQUENCES:
+        raise ValueError(f"phraseBoost: {len(out)} sequences, more than the {MAX_PHRASE_SEQUENCES} one rule set holds")
+    return list(out.items())
+
+
 def compressionRatio(tokens: Sequence[int]) -> float:
     a = np.ascontiguousarray(list(tokens), dtype=np.int32)
     return float(L.load().wh_compression_ratio(a.ctypes.data_as(L.PI32), len(a)))

@@ -728,7 +728,7 @@ static void launch_cross_attn(const AttnArgs& at_in, int S, int H, int B, hipStr
 // projection, fc1, fc2] -> logits -> sampler.  Every activation hand-off is a plane pair in B-fragment order, every LayerNorm is
 // folded into the consumer's epilogue (see decoder32.hip).
 void launch_decoder_step(const DecodeBuffers& db, const SamplerCfg* cfg_dev, const int* suppress_dev, bool sample, hipStream_t st, const NoSpeechArgs* ns,
-                         const int* logit_rules) {
+                         const int* logit_rules, const PhraseRulesArgs* phrase_rules) {
     const Dec32& D = *db.d32;
     const int d = db.d, B = db.batch, H = db.n_head, L = db.n_layer, V = db.n_vocab;
     const int n_bt = (B + 31) / 32;
@@ -811,6 +811,7 @@ void launch_decoder_step(const DecodeBuffers& db, const SamplerCfg* cfg_dev, con
     const bool mixed = sample && db.mixed;       // a mixed pass (option_mix.h): the per-class tables, the mixed instantiations
     launch_dec32_proj(P32_LOGITS, a, n_bt, st, mixed && fused);
     if (ns) launch_nospeech(*ns, db.seq, db.logits, B, V, st);      // before any sampler: the unfused one filters the rows in place, every one advances token_index
+    if (phrase_rules && sample && !fused) launch_phrase_rules(*phrase_rules, db.seq, db.logits, B, V, st);      // the raw rows too: phrase rules first, then the logit rules
     if (logit_rules && sample && !fused) launch_logit_rules(logit_rules, db.seq, db.logits, B, V, st);      // the raw rows, behind the no-speech kernel's read of them
     if (fused) {
         ProfScope ps_(KK_SAMPLER, st);

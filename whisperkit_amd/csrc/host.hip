@@ -270,7 +270,7 @@ static int get_step_graph(wh_session* s, int batch, int first_step, hipGraphExec
     // (a compacted pass bakes the slot table's address, the mapped kernel instantiations and its own slots per workgroup into its launches)
     const WhGraphKey key{batch, s->align_enabled ? 1 : 0, s->fused_greedy ? 1 : 0, s->align_enabled ? s->n_align_alloc : 0, db.self_rows, db.xattn_gate ? 1 : 0,
                          db.slot_home ? 1 : 0, db.slot_home ? s->pass_spw : 0, db.self_owner ? 1 : 0, db.mixed,
-                         (int)plan::nospeech_step_mask(first_step, kStepsPerGraph, s->pass_ns), s->pass_lr ? 1 : 0};
+                         (int)plan::nospeech_step_mask(first_step, kStepsPerGraph, s->pass_ns), s->pass_lr ? 1 : 0, s->pass_pr ? 1 : 0};
     auto it = s->graphs.find(key);
     if (it != s->graphs.end()) { s->graph_use[key] = ++s->graph_tick; *out = it->second; return WH_OK; }
     // The cache is capped (a large-v3 step graph holds ~2.5 k kernel nodes; a configuration = everything of the key but the row bound has up
@@ -279,7 +279,7 @@ static int get_step_graph(wh_session* s, int batch, int first_step, hipGraphExec
     const size_t cap = (size_t)knob::once<knob::WH_GRAPH_CAP>();
     while (s->graphs.size() >= cap) {
         auto same_cfg = [](const WhGraphKey& a, const WhGraphKey& b) {
-            return a.batch == b.batch && a.align == b.align && a.fused == b.fused && a.n_align == b.n_align && a.gate == b.gate && a.mapped == b.mapped && a.spw == b.spw && a.owner == b.owner && a.mixed == b.mixed && a.ns_mask == b.ns_mask && a.logit_rules == b.logit_rules;
+            return a.batch == b.batch && a.align == b.align && a.fused == b.fused && a.n_align == b.n_align && a.gate == b.gate && a.mapped == b.mapped && a.spw == b.spw && a.owner == b.owner && a.mixed == b.mixed && a.ns_mask == b.ns_mask && a.logit_rules == b.logit_rules && a.phrase_rules == b.phrase_rules;
         };
         const WhGraphKey* victim = nullptr;
         unsigned long long victim_last = ~0ull;
@@ -298,7 +298,7 @@ static int get_step_graph(wh_session* s, int batch, int first_step, hipGraphExec
     }
     hipGraph_t graph;
     WH_HIP(hipStreamBeginCapture(s->st, hipStreamCaptureModeThreadLocal));
-    for (int i = 0; i < kStepsPerGraph; ++i) launch_decoder_step(db, s->cfg_dev, s->suppress_dev, true, s->st, whi::nospeech_step_args(s, first_step + i), whi::logit_rules_step_args(s));
+    for (int i = 0; i < kStepsPerGraph; ++i) launch_decoder_step(db, s->cfg_dev, s->suppress_dev, true, s->st, whi::nospeech_step_args(s, first_step + i), whi::logit_rules_step_args(s), whi::phrase_rules_step_args(s));
     WH_HIP(hipStreamEndCapture(s->st, &graph));
     hipGraphExec_t exec;
     WH_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
@@ -450,7 +450,7 @@ static int run_token_loop(wh_session* s, int batch, int loop_count, PassLayout* 
     int width = batch;                                   // (changes only through inpass_narrow)
     auto all_done_in = [](const SeqState* q, int n) { for (int b = 0; b < n; ++b) if (q[b].active && !q[b].done) return false; return true; };
     auto all_done = [&]() { return all_done_in(s->seq_host, width); };
-    auto count_steps = [&](int steps) { s->slot_steps += (long long)width * steps; if (L) s->inpass_slot_steps_saved += (long long)(L->width0 - width) * steps; if (s->pass_lr) s->lr_launches += steps; };
+    auto count_steps = [&](int steps) { s->slot_steps += (long long)width * steps; if (L) s->inpass_slot_steps_saved += (long long)(L->width0 - width) * steps; if (s->pass_lr) s->lr_launches += steps; if (s->pass_pr) s->pr_launches += steps; };
     // the last read of the pass: the compact slots, or - after a narrowing - every state by home slot (parked once more)
     auto final_read = [&]() -> int {
         if (L && L->switches > 0) {
@@ -470,7 +470,7 @@ static int run_token_loop(wh_session* s, int batch, int loop_count, PassLayout* 
             if (exec) { WH_HIP(hipGraphLaunch(exec, s->st)); count_steps(kStepsPerGraph); }
             else for (int i = 0; i < kStepsPerGraph && step + i < loop_count; ++i) {
                 DecodeBuffers db = whi::decode_buffers(s, width, step + i);
-                launch_decoder_step(db, s->cfg_dev, s->suppress_dev, true, s->st, whi::nospeech_step_args(s, step + i), whi::logit_rules_step_args(s)); WH_CHECK_LAUNCH();
+                launch_decoder_step(db, s->cfg_dev, s->suppress_dev, true, s->st, whi::nospeech_step_args(s, step + i), whi::logit_rules_step_args(s), whi::phrase_rules_step_args(s)); WH_CHECK_LAUNCH();
                 count_steps(1);
             }
             WH_HIP(hipMemcpyAsync(s->seq_host, s->seq, sizeof(SeqState) * width, hipMemcpyDeviceToHost, s->st));
@@ -528,7 +528,7 @@ static int run_token_loop(wh_session* s, int batch, int loop_count, PassLayout* 
     } else {
         for (int step = 0; step < loop_count; ++step) {
             DecodeBuffers db = whi::decode_buffers(s, width, step);
-            launch_decoder_step(db, s->cfg_dev, s->suppress_dev, true, s->st, whi::nospeech_step_args(s, step), whi::logit_rules_step_args(s));
+            launch_decoder_step(db, s->cfg_dev, s->suppress_dev, true, s->st, whi::nospeech_step_args(s, step), whi::logit_rules_step_args(s), whi::phrase_rules_step_args(s));
             WH_CHECK_LAUNCH();
             count_steps(1);
             if ((step & 7) == 7 && step + 1 < loop_count) {
@@ -620,7 +620,7 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
     for (int b = 0; b < batch; ++b) n_live += (active ? active[b] != 0 : 1);
     plan::CompactPassPlan cp{false, batch, s->use_xabs ? s->xabs.spw : 1};
     if (s->fallback_compaction == 1 && active) cp = plan::compact_pass_plan(n_live, batch, s->B, s->use_xabs ? s->xabs.spw : 1);
-    struct PassScope { wh_session* s; ~PassScope() { s->pass_mapped = false; s->pass_owner = false; s->pass_mixed = false; s->pass_ns = plan::NoSpeechRange{-1, -1}; s->pass_lr = false; } } pass_scope{s};      // (every exit: the next caller of decode_buffers sees a plain pass)
+    struct PassScope { wh_session* s; ~PassScope() { s->pass_mapped = false; s->pass_owner = false; s->pass_mixed = false; s->pass_ns = plan::NoSpeechRange{-1, -1}; s->pass_lr = false; s->pass_pr = false; } } pass_scope{s};      // (every exit: the next caller of decode_buffers sees a plain pass)
     const int width = cp.compact ? cp.width : batch;
     if (cp.compact) {
         if (!s->slot_home_dev) WH_HIP(s->mem.alloc(&s->slot_home_dev, (size_t)s->B, false));
@@ -666,6 +666,13 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
         s->lr_host[2] = st->special_token_begin;
         WH_HIP(hipMemcpyAsync(s->lr_dev + 2, s->lr_host + 2, sizeof(int32_t), hipMemcpyHostToDevice, s->st));
         s->pass_lr = true; s->lr_passes += 1;
+    }
+    // ---- device phrase rules (wh_session_set_phrase_rules; NO REFERENCE BEHAVIOUR): likewise, phrase_rules_kernel directly in front of logit_rules_kernel
+    if (s->phrase_rules_on) {
+        s->fused_greedy = false;
+        s->pr_host[2] = st->special_token_begin;
+        WH_HIP(hipMemcpyAsync(s->pr_dev + 2, s->pr_host + 2, sizeof(int32_t), hipMemcpyHostToDevice, s->st));
+        s->pass_pr = true; s->pr_passes += 1;
     }
     WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * width, hipMemcpyHostToDevice, s->st));
     launch_rules_init(s->cfg_dev, s->seq, width, s->st, mix != nullptr);
@@ -1002,6 +1009,101 @@ extern "C" int wh_debug_logit_rules_apply(wh_session* s, float* rows_inout, int 
     return WH_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ device phrase rules
+// NO REFERENCE BEHAVIOUR: the semantics are transformers' `SequenceBiasLogitsProcessor` for sequences of any length (of which `NoBadWordsLogitsProcessor` is
+// the special case bias = -inf), on input_ids = [sentinel] + H (phrase_rules_plan.h, phrase_rules.hip).
+// The setter builds the table in the pinned staging and uploads it stream-ordered on the session's stream: the stream is drained first, so no copy in flight
+// reads a half-written staging; every later launch of the stream reads the new table through the address its graphs captured.
+extern "C" int wh_session_set_phrase_rules(wh_session* s, const wh_phrase_rules* rules) {
+    if (!s || !s->m) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_phrase_rules: null session");
+    WH_TRY
+    if (const char* why = plan::phrase_rules_invalid(rules, s->m->dims.n_vocab)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_phrase_rules: %s", why);
+    if (plan::phrase_rules_neutral(rules)) {
+        s->phrase_rules_on = false;
+        s->pr_rules = wh_phrase_rules{0, 0, nullptr, nullptr, nullptr};
+        return WH_OK;
+    }
+    if (hipSetDevice(s->m->device) != hipSuccess) return set_error(WH_ERR_HIP, "wh_session_set_phrase_rules: hipSetDevice(%d) failed", s->m->device);
+    if (!s->pr_dev) WH_HIP(s->mem.alloc(&s->pr_dev, (size_t)plan::kPhraseTableWords, false));      // (not zeroed: the copy below writes every word)
+    if (!s->pr_host) WH_HIP(s->mem.alloc_pinned(&s->pr_host, (size_t)plan::kPhraseTableWords));
+    if (!s->pr_args.matches) {
+        WH_HIP(s->mem.alloc(&s->pr_args.matches, (size_t)1, false));
+        WH_HIP(hipMemsetAsync(s->pr_args.matches, 0, sizeof(unsigned long long), s->st));
+    }
+    s->pr_args.table = s->pr_dev;
+    WH_HIP(hipStreamSynchronize(s->st));
+    plan::phrase_table_build(*rules, s->m->dims.n_vocab, s->pr_host);
+    WH_HIP(hipMemcpyAsync(s->pr_dev, s->pr_host, sizeof(int32_t) * plan::kPhraseTableWords, hipMemcpyHostToDevice, s->st));
+    size_t n_ids = 0;
+    for (int i = 0; i < rules->n_sequences; ++i) n_ids += (size_t)rules->lengths[i];
+    s->pr_tokens.assign(rules->tokens, rules->tokens + n_ids);
+    s->pr_lengths.assign(rules->lengths, rules->lengths + rules->n_sequences);
+    s->pr_biases.assign(rules->biases, rules->biases + rules->n_sequences);
+    s->pr_rules = wh_phrase_rules{rules->n_sequences, 0, s->pr_tokens.data(), s->pr_lengths.data(), s->pr_biases.data()};
+    s->phrase_rules_on = true;
+    return WH_OK;
+    WH_CATCH("wh_session_set_phrase_rules")
+}
+// The session's copy; its arrays stay valid until the next setter call.  The empty set when the mode is off
+extern "C" int wh_session_phrase_rules(const wh_session* s, wh_phrase_rules* out) {
+    if (!s || !out) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_phrase_rules: null argument");
+    *out = s->pr_rules;
+    return WH_OK;
+}
+// matches: the device counter, one 8-byte copy behind a drained stream
+extern "C" int wh_session_phrase_rules_stats(const wh_session* s, int64_t* passes, int64_t* launches, int64_t* matches) {
+    if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_phrase_rules_stats: null session");
+    if (passes) *passes = s->pr_passes;
+    if (launches) *launches = s->pr_launches;
+    if (matches) {
+        unsigned long long v = 0;
+        if (s->pr_args.matches) {
+            if (hipSetDevice(s->m->device) != hipSuccess) return set_error(WH_ERR_HIP, "wh_session_phrase_rules_stats: hipSetDevice(%d) failed", s->m->device);
+            WH_HIP(hipStreamSynchronize(s->st));
+            WH_HIP(hipMemcpy(&v, s->pr_args.matches, sizeof(v), hipMemcpyDeviceToHost));
+        }
+        *matches = (int64_t)v;
+    }
+    return WH_OK;
+}
+
+// Development aid: phrase_rules_kernel alone over caller-supplied rows and histories, in the shape of wh_debug_logit_rules_apply.  live (or null): row i is a
+// live slot iff live[i] != 0 - the others are inactive slots, whose rows the kernel must leave alone.
+extern "C" int wh_debug_phrase_rules_apply(wh_session* s, float* rows_inout, int n_rows, const int32_t* tokens, const int32_t* n_tokens, const int32_t* prompt_lens,
+                                           const int32_t* live) {
+    if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_phrase_rules_apply: null session");
+    CHECK_SESSION(s); CHECK_BATCH(s, n_rows);
+    if (!rows_inout || !tokens || !n_tokens || !prompt_lens) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_phrase_rules_apply: null argument");
+    if (!s->phrase_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_phrase_rules_apply: the session has no phrase rules set (wh_session_set_phrase_rules)");
+    const int V = s->m->dims.n_vocab;
+    for (int i = 0; i < n_rows; ++i) {
+        if (n_tokens[i] < 0 || n_tokens[i] > kMaxTok || prompt_lens[i] < 0 || prompt_lens[i] > n_tokens[i])
+            return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_phrase_rules_apply: row %d has %d tokens, prompt length %d (0 <= prompt <= tokens <= %d)", i, n_tokens[i], prompt_lens[i], kMaxTok);
+        for (int k = 0; k < n_tokens[i]; ++k)
+            if (tokens[(size_t)i * kMaxTok + k] < 0 || tokens[(size_t)i * kMaxTok + k] >= V)
+                return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_phrase_rules_apply: row %d token %d out of vocabulary", i, tokens[(size_t)i * kMaxTok + k]);
+    }
+    wh_special_tokens st;
+    memset(&st, 0, sizeof(st));
+    if (wh_special_tokens_default(s->m, &st) != WH_OK) st.special_token_begin = V;
+    WH_HIP(hipStreamSynchronize(s->st));                  // nothing in flight reads the staging the host writes next
+    for (int i = 0; i < n_rows; ++i) {
+        SeqState& q = s->seq_host[i];
+        memset(&q, 0, sizeof(q));
+        for (int k = 0; k < n_tokens[i]; ++k) q.tokens[k] = tokens[(size_t)i * kMaxTok + k];
+        q.n_tokens = n_tokens[i]; q.prompt_len = prompt_lens[i]; q.active = (!live || live[i]) ? 1 : 0; q.rng_lane = i;
+    }
+    s->pr_host[2] = st.special_token_begin;
+    WH_HIP(hipMemcpyAsync(s->pr_dev + 2, s->pr_host + 2, sizeof(int32_t), hipMemcpyHostToDevice, s->st));
+    WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * n_rows, hipMemcpyHostToDevice, s->st));
+    WH_HIP(hipMemcpyAsync(s->logits, rows_inout, sizeof(float) * (size_t)n_rows * V, hipMemcpyHostToDevice, s->st));
+    launch_phrase_rules(s->pr_args, s->seq, s->logits, n_rows, V, s->st);
+    WH_CHECK_LAUNCH();
+    WH_HIP(hipMemcpyAsync(rows_inout, s->logits, sizeof(float) * (size_t)n_rows * V, hipMemcpyDeviceToHost, s->st));
+    WH_HIP(hipStreamSynchronize(s->st));
+    return WH_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ speculative greedy decode
 // NO REFERENCE BEHAVIOUR (spec_plan.h, spec.hip).  A proposer guesses the next K tokens of every audio; the target runs the known position
 // and the guessed ones as virtual slots of ONE decoder launch (owner-table self-attention, mapped cross-attention: the instantiations the forced pass
@@ -1218,6 +1320,7 @@ extern "C" int wh_decode_text_guided(wh_session* s, int n_audio, int K, const wh
     if (int r = spec_check_args(who, n_audio, K, opt, st, prompt, n_prompt, out, s->B)) return r;
     if (int r = spec_check_tokens(who, n_audio, prompt, n_prompt, proposals, n_proposals, s->m->dims.n_vocab)) return r;
     if (s->logit_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: the session has logit rules set (wh_session_set_logit_rules), which the speculative pass does not run", who);
+    if (s->phrase_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: the session has phrase rules set (wh_session_set_phrase_rules), which the speculative pass does not run", who);
     WH_TRY
     ScriptedProposer pr;
     pr.lists = proposals; pr.n_lists = n_proposals; pr.end_token = st->end_token;
@@ -1245,6 +1348,7 @@ extern "C" int wh_decode_text_speculative(wh_session* s, wh_session* draft, int 
     if (int r = spec_check_tokens(who, n_audio, prompt, n_prompt, nullptr, nullptr, s->m->dims.n_vocab)) return r;
     if (int r = spec_check_draft(who, s, draft, n_audio)) return r;
     if (s->logit_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: the session has logit rules set (wh_session_set_logit_rules), which the speculative pass does not run", who);
+    if (s->phrase_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: the session has phrase rules set (wh_session_set_phrase_rules), which the speculative pass does not run", who);
     WH_TRY
     // the draft's sampler tables (the same options; its own vocabulary-sized masks) and switches, on its own stream, which is then idle for the pass
     int r = whi::upload_sampler_cfg(draft, opt, st, 0, n_prompt, 0, opt->seed);
@@ -1393,6 +1497,7 @@ static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_
     const int beam = opt->beam_size > 1 ? opt->beam_size : 1;
     if (beam > 1 && opt->word_timestamps) return set_error(WH_ERR_INVALID_ARGUMENT, "beam_size > 1 cannot be combined with word_timestamps");
     if (beam > 1 && s->logit_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "beam_size > 1 cannot be combined with the session's logit rules (wh_session_set_logit_rules)");
+    if (beam > 1 && s->phrase_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "beam_size > 1 cannot be combined with the session's phrase rules (wh_session_set_phrase_rules)");
     if (beam > s->B) return set_error(WH_ERR_INVALID_ARGUMENT, "beam_size %d exceeds the session's %d slots", beam, s->B);
     const int round_cap = s->B / beam;
     std::vector<int> slot_job;   // job index per slot for the current round
@@ -1516,10 +1621,10 @@ static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_
                 const MixClasses mix{(int)classes->size(), classes->data(), cls_slot.data(), mix_pp.data(), mix_np.data(), opt_slot.data()};
                 r = decode_text_impl(s, nb, nullptr, st, nullptr, 0, langs ? ml.data() : nullptr, tv.data(), active.data(), seed, tmp.data(), &mix);
                 if (r) return r;
-            } else if (s->draft && s->no_speech_detection == plan::kNoSpeechOff && !s->logit_rules_on && ti == 0 && temps[ti] == 0.0f && all_active && beam == 1 && !s->progress_cb && plan::spec_fits(nb, s->draft_k, s->B) &&
+            } else if (s->draft && s->no_speech_detection == plan::kNoSpeechOff && !s->logit_rules_on && !s->phrase_rules_on && ti == 0 && temps[ti] == 0.0f && all_active && beam == 1 && !s->progress_cb && plan::spec_fits(nb, s->draft_k, s->B) &&
                        !spec_check_draft("wh_transcribe", s, s->draft, nb)) {
                 // first rung with a draft attached (wh_session_set_draft) and room for the rings: the speculative pass (results are the ordinary pass's).  The
-                // speculative pass reports no no-speech value and runs no logit rules, so a session with either on runs the ordinary pass below instead.  The
+                // speculative pass reports no no-speech value and runs neither logit nor phrase rules, so a session with any of them on runs the ordinary pass below instead.  The
                 // draft gets the same windows through its own log-mel and encoder
                 wh_session* const dr = s->draft;
                 for (int b = 0; b < nb; ++b) {

@@ -13,6 +13,7 @@
 #include "kernels.h"
 #include "logit_rules_plan.h"
 #include "nospeech_plan.h"
+#include "phrase_rules_plan.h"
 #include "text.h"
 #include "whisperhip.h"
 
@@ -88,9 +89,10 @@ struct WhGraphKey {
     int mixed;            // 1: a mixed pass (option_mix.h) - the logits epilogue and the samplers run their *_mixed instantiations; 0 otherwise
     int ns_mask;          // bit i: step i of the graph stores its logits rows and runs nospeech_kernel (nospeech_plan.h nospeech_step_mask); 0 with the mode off
     int logit_rules;      // 1: every step runs logit_rules_kernel before the (unfused) sampler (wh_session_set_logit_rules); 0 with no rules set
+    int phrase_rules;     // 1: every step runs phrase_rules_kernel in front of that (wh_session_set_phrase_rules); 0 with no phrase rules set
     bool operator<(const WhGraphKey& o) const {
-        return std::tie(batch, align, fused, n_align, self_rows, gate, mapped, spw, owner, mixed, ns_mask, logit_rules) <
-               std::tie(o.batch, o.align, o.fused, o.n_align, o.self_rows, o.gate, o.mapped, o.spw, o.owner, o.mixed, o.ns_mask, o.logit_rules);
+        return std::tie(batch, align, fused, n_align, self_rows, gate, mapped, spw, owner, mixed, ns_mask, logit_rules, phrase_rules) <
+               std::tie(o.batch, o.align, o.fused, o.n_align, o.self_rows, o.gate, o.mapped, o.spw, o.owner, o.mixed, o.ns_mask, o.logit_rules, o.phrase_rules);
     }
 };
 
@@ -216,6 +218,18 @@ struct wh_session {
     int32_t *lr_dev = nullptr, *lr_host = nullptr;
     bool pass_lr = false;
     long long lr_passes = 0, lr_launches = 0;      // wh_session_logit_rules_stats
+    // device phrase rules (wh_session_set_phrase_rules: host.hip, phrase_rules_plan.h, phrase_rules.hip).  phrase_rules_on: a non-empty set is installed;
+    // pr_rules is the session's copy (its arrays are the three vectors).  pr_args.table (device, kPhraseTableWords words at a fixed address, so that captured
+    // step graphs stay valid when values change), its pinned mirror pr_host and the 64-bit match counter pr_args.matches are allocated by the first setter
+    // that installs rules.  pass_pr holds only while decode_text_impl runs a pass under the rules, as pass_lr does.
+    bool phrase_rules_on = false;
+    wh_phrase_rules pr_rules{0, 0, nullptr, nullptr, nullptr};
+    std::vector<int32_t> pr_tokens, pr_lengths;
+    std::vector<float> pr_biases;
+    int32_t *pr_dev = nullptr, *pr_host = nullptr;
+    wh::PhraseRulesArgs pr_args{nullptr, nullptr};
+    bool pass_pr = false;
+    long long pr_passes = 0, pr_launches = 0;      // wh_session_phrase_rules_stats (matches: the device counter)
     hipEvent_t ev[8]{};
     bool align_enabled = false;
     wh_timings last_timings{};
@@ -285,4 +299,6 @@ inline float nospeech_prob(const wh_session* s, int b) { float v; memcpy(&v, s->
 inline const wh::NoSpeechArgs* nospeech_step_args(const wh_session* s, int step) { return wh::plan::nospeech_step_in_range(step, s->pass_ns) ? &s->ns_args : nullptr; }
 // device logit rules: the rule set a step of the running pass hands to launch_decoder_step, or null (no rules set, or a pass that does not run them)
 inline const int* logit_rules_step_args(const wh_session* s) { return s->pass_lr ? s->lr_dev : nullptr; }
+// device phrase rules: likewise
+inline const wh::PhraseRulesArgs* phrase_rules_step_args(const wh_session* s) { return s->pass_pr ? &s->pr_args : nullptr; }
 }  // namespace whi

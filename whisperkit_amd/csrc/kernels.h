@@ -368,10 +368,20 @@ void launch_nospeech(const NoSpeechArgs& a, SeqState* seq, const float* logits, 
 // one workgroup per slot of `batch`: a live slot applies the session's rule set (`rules`: logit_rules_plan.h kLogitRulesWords words of device memory) to its
 // row of logits ([batch][n_vocab], as the step's logits launch wrote it) from the history in its SeqState - between the logits launch and the sampler launch
 void launch_logit_rules(const int* rules, const SeqState* seq, float* logits, int batch, int n_vocab, hipStream_t st);
+// device phrase rules (phrase_rules.hip, phrase_rules_plan.h; NO REFERENCE BEHAVIOUR: transformers' SequenceBiasLogitsProcessor for sequences of any length):
+// session memory at fixed addresses - the phrase table (kPhraseTableWords words) and the 64-bit counter of matching sequences of length >= 2 (or null)
+struct PhraseRulesArgs {
+    const int* table;
+    unsigned long long* matches;
+};
+// one workgroup per slot of `batch`: a live slot adds, for every target of the table, the summed biases of the sequences its history matches to its row of
+// logits ([batch][n_vocab], as the step's logits launch wrote it) - between the logits launch and logit_rules_kernel / the sampler launch
+void launch_phrase_rules(const PhraseRulesArgs& a, const SeqState* seq, float* logits, int batch, int n_vocab, hipStream_t st);
 // ns (or null): the step stores its logits rows even on the fused-greedy path and runs nospeech_kernel between the logits launch and the sampler launch
 // logit_rules (or null; only with the unfused sampler): logit_rules_kernel runs behind it, before the sampler
+// phrase_rules (or null; only with the unfused sampler): phrase_rules_kernel runs directly in front of logit_rules_kernel
 void launch_decoder_step(const DecodeBuffers& db, const SamplerCfg* cfg_dev, const int* suppress_dev, bool sample, hipStream_t st, const NoSpeechArgs* ns = nullptr,
-                         const int* logit_rules = nullptr);
+                         const int* logit_rules = nullptr, const PhraseRulesArgs* phrase_rules = nullptr);
 // filter rules of the first sampling step of a decodeText call (later steps: computed by the sampler itself)
 void launch_rules_init(const SamplerCfg* cfg_dev, SeqState* seq, int batch, hipStream_t st, bool mixed = false);
 // in-pass compaction (compact.hip): the decode state of a narrowing pass moves through a home-indexed array [n_slots].  park: seq_home[home[i]] = seq[i]
