@@ -761,7 +761,7 @@ int wh_debug_logit_rules_apply(wh_session* s, float* rows_inout, int n_rows, con
  * wh_decode_text_guided, wh_decode_text_speculative and a wh_transcribe* audio with beam_size > 1 return WH_ERR_INVALID_ARGUMENT (for
  * wh_transcribe_batch* that is the audio's own status), and wh_transcribe* ignores an attached draft (wh_session_set_draft).
  * Out of scope: text-in APIs (the library has no tokenizer encode: ids in, as everywhere else), beam search under rules, retraction of
- * a bias when a partial match breaks, per-audio rule sets (session-level, like the logit rules), more than 4096 sequences. */
+ * a bias when a partial match breaks, more than 4096 sequences.  (A rule set per audio: wh_session_define_rule_set below.) */
 typedef struct wh_phrase_rules {
     int32_t n_sequences;            /* 0 = off */
     int32_t reserved_;
@@ -864,6 +864,64 @@ int wh_transcribe_device_batch_with_options(wh_session* s, const struct wh_devic
  * results of wh_transcribe_chunked, with wh_vad_chunk_all_device in place of the host chunker. */
 int wh_transcribe_chunked_device(wh_session* s, struct wh_device_audio* a, const wh_decoding_options* opt, const wh_special_tokens* st,
                                  wh_transcription** out, int capacity, int32_t* seek_offsets_out, int* n_out);
+
+/* ---- per-audio rule sets: NO REFERENCE BEHAVIOUR (csrc/rule_sets_plan.h, rule_sets.hip) ----
+ * wh_session_set_logit_rules and wh_session_set_phrase_rules are session-level: one rule set governs every slot of every pass.  Custom
+ * vocabulary, banned phrases and word boost belong to the REQUEST, though: a caller that serves several tenants had to set the rules,
+ * transcribe tenant A's audios, set them again, transcribe tenant B's.  Opt-in: a session holds WH_MAX_RULE_SETS numbered rule sets, every
+ * audio (or home slot, at the step level) names the set it decodes under, and audios with different sets share a device batch.
+ *   index 0        the session's own rule set: whatever wh_session_set_logit_rules / wh_session_set_phrase_rules installed, possibly nothing
+ *   index 1 .. 15  a bank; each entry is one wh_logit_rules plus one wh_phrase_rules with the limits, validation and arithmetic of the two
+ *                  setters (256 biases, n <= 8, 4096 sequences of 1 .. 16 ids).  The whole bank (about 5 MB of device memory) is allocated
+ *                  by the first definition and rewritten in place, stream-ordered on the session's stream: captured step graphs stay valid.
+ * A slot assigned set k decodes under set k's phrase rules, then set k's logit rules: order and arithmetic are exactly those of a pass whose
+ * session-level rules are set k.  A slot assigned 0 decodes under the session's own rules, or under none when those are off.
+ * A pass in which every live slot is assigned 0 is the pass it has always been, bit for bit and launch for launch.  A pass with a live slot
+ * under another set is SET-AWARE: it runs the unfused sampler with ONE kernel per step in front of it, which looks the slot's set up by its
+ * home slot - so compacted, narrowed and mixed passes need nothing else.  The logit-rule and phrase-rule counters do not move in such a pass.
+ * Assigning an undefined index is WH_ERR_INVALID_ARGUMENT: the audio's own status in wh_transcribe_*_with_rule_sets, the call's status in
+ * wh_decode_text / wh_decode_text_languages / wh_decode_text_mixed, checked before anything is launched.
+ * Grouping (wh_transcribe_*_with_rule_sets): the set index never splits a group.  One bit does: whether an audio decodes under any rules
+ * at all (a set other than 0, or set 0 while the session's own rules are on) - un-ruled audios keep the fused sampler and with it their
+ * bits, so they form groups of their own.  Grouping changes the batching, never a result.
+ * wh_decode_text_beam, wh_decode_text_guided and wh_decode_text_speculative return WH_ERR_INVALID_ARGUMENT while a slot of the call is
+ * assigned a set other than 0, as does a wh_transcribe* audio with beam_size > 1 and such a set; wh_transcribe* ignores an attached draft for
+ * a group that carries sets.  wh_detect_language, wh_no_speech_probs, wh_score_tokens / wh_align_tokens_batch and wh_decode_text_custom do
+ * not run rule sets.  WH_MAX_RULE_SETS is a design constant (it sizes the bank), not a measured value.
+ * Out of scope: more than 15 banked sets; a "no rules at all" assignment while the session's own rules are on; rule sets in the beam,
+ * guided, speculative, forced and custom passes; text-in APIs; keeping the fused sampler in a set-aware pass. */
+#define WH_MAX_RULE_SETS 16
+/* Defines banked set `index` (1 .. 15) from the two halves (either may be NULL or neutral: that half is off); both NULL or neutral
+ * undefines the index.  An invalid set returns WH_ERR_INVALID_ARGUMENT and leaves the bank as it was. */
+int wh_session_define_rule_set(wh_session* s, int index, const wh_logit_rules* logit_rules, const wh_phrase_rules* phrase_rules);
+/* Reads set `index` (0 .. 15; 0 = the session's own rules) back; an undefined index gives the neutral halves.  Either pointer may be
+ * NULL.  The arrays belong to the session and hold until the next definition of that index (index 0: the next setter call). */
+int wh_session_rule_set(const wh_session* s, int index, wh_logit_rules* logit_rules_out, wh_phrase_rules* phrase_rules_out);
+/* Step-level assignment by home slot: slot b of wh_decode_text / wh_decode_text_languages / wh_decode_text_mixed decodes under set
+ * set_of_slot[b] (0 .. 15), slots n .. max_batch - 1 under 0.  NULL: every slot under 0.  It persists until changed; every
+ * wh_transcribe* call owns the assignment for its duration and leaves it all 0, so a step-level assignment never reaches a window. */
+int wh_session_set_slot_rule_sets(wh_session* s, const int32_t* set_of_slot, int n);
+int wh_session_slot_rule_sets(const wh_session* s, int32_t* set_of_slot_out /* [n] */, int n);
+/* wh_transcribe_batch_with_options / wh_transcribe_device_batch_with_options - their contract, option mixing included - with
+ * rule_set_of_audio[i] the rule set of audio i (NULL: every audio under set 0). */
+int wh_transcribe_batch_with_rule_sets(wh_session* s, const float* const* pcm_host, const int32_t* n_samples, int n_audio,
+                                       const wh_decoding_options* const* opts /* [n_audio] or NULL */,
+                                       const int32_t* rule_set_of_audio /* [n_audio] or NULL */, const wh_special_tokens* st,
+                                       wh_transcription** out /* [n_audio] */, int32_t* statuses /* [n_audio] or NULL */);
+int wh_transcribe_device_batch_with_rule_sets(wh_session* s, const struct wh_device_audio* const* audios, int n_audio,
+                                              const wh_decoding_options* const* opts /* [n_audio] or NULL */,
+                                              const int32_t* rule_set_of_audio /* [n_audio] or NULL */, const wh_special_tokens* st,
+                                              wh_transcription** out /* [n_audio] */, int32_t* statuses /* [n_audio] or NULL */);
+/* Counters since the session's creation: set-aware decode passes, launches of rule_sets_kernel in them (one per step), and per set the
+ * (slot, step, sequence of length >= 2) triples whose prefix matched under it, counted on the device and read with one copy after a stream
+ * synchronise (entry 0: slots under the session's own phrase rules inside set-aware passes).  Any pointer may be NULL. */
+int wh_session_rule_set_stats(const wh_session* s, int64_t* passes, int64_t* launches, int64_t* matches /* [WH_MAX_RULE_SETS] */);
+/* Development aid: rule_sets_kernel alone over caller-supplied rows and histories, in the shape of wh_debug_phrase_rules_apply, with
+ * set_of_row[i] the set of row i (any value: a row under an index that is out of range or undefined comes back untouched, like a row
+ * that is not live).  At least one banked set must have been defined.  The launch's matches go into the session's counters. */
+int wh_debug_rule_sets_apply(wh_session* s, float* rows_inout, int n_rows, const int32_t* tokens, const int32_t* n_tokens,
+                             const int32_t* prompt_lens, const int32_t* live, const int32_t* set_of_row);
+
 void wh_transcription_free(wh_transcription* t);
 int wh_transcription_n_segments(const wh_transcription* t);
 int wh_transcription_segment(const wh_transcription* t, int i, wh_segment* out);

@@ -245,6 +245,13 @@ SYMBOLS = {
     "wh_session_phrase_rules": (I, [VP, C.POINTER(WhPhraseRules)]),
     "wh_session_phrase_rules_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "wh_debug_phrase_rules_apply": (I, [VP, PF, I, PI32, PI32, PI32, PI32]),
+    # per-audio rule sets (csrc/rule_sets.hip, rule_sets_plan.h)
+    "wh_session_define_rule_set": (I, [VP, I, C.POINTER(WhLogitRules), C.POINTER(WhPhraseRules)]),
+    "wh_session_rule_set": (I, [VP, I, C.POINTER(WhLogitRules), C.POINTER(WhPhraseRules)]),
+    "wh_session_set_slot_rule_sets": (I, [VP, PI32, I]),
+    "wh_session_slot_rule_sets": (I, [VP, PI32, I]),
+    "wh_session_rule_set_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "wh_debug_rule_sets_apply": (I, [VP, PF, I, PI32, PI32, PI32, PI32, PI32]),
     "wh_prefill_prompt": (I, [VP, POPT, PST, C.c_int32, PI32, I]),
     "wh_transcribe": (I, [VP, VP, I, POPT, PST, PVP]),
     "wh_transcribe_batch": (I, [VP, PVP, PI32, I, POPT, PST, PVP]),
@@ -252,6 +259,8 @@ SYMBOLS = {
     "wh_session_item_status": (I, [VP, I]), "wh_session_item_error": (C.c_char_p, [VP, I]),
     "wh_transcribe_chunked": (I, [VP, VP, I, POPT, PST, PVP, I, PI32, C.POINTER(I)]),
     "wh_transcribe_device_batch_with_options": (I, [VP, PVP, I, C.POINTER(POPT), PST, PVP, PI32]),
+    "wh_transcribe_batch_with_rule_sets": (I, [VP, PVP, PI32, I, C.POINTER(POPT), PI32, PST, PVP, PI32]),
+    "wh_transcribe_device_batch_with_rule_sets": (I, [VP, PVP, I, C.POINTER(POPT), PI32, PST, PVP, PI32]),
     "wh_transcribe_chunked_device": (I, [VP, VP, POPT, PST, PVP, I, PI32, C.POINTER(I)]),
     "wh_transcription_free": (None, [VP]),
     "wh_transcription_n_segments": (I, [VP]),

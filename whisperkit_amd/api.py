@@ -1004,7 +1004,7 @@ class Session:
         transcribe*: every temperature rung, compacted, narrowed and mixed passes) under the unfused sampler; decodeTextCustom, detectLanguage, noSpeechProbs
         and the forced pass do not run the rules; decodeTextBeam / decodeTextGuided / decodeTextSpeculative and beamSize > 1 in transcribe* are refused while
         rules are set, and transcribe* ignores an attached draft.  Out of scope: text in place of ids, beam search under rules, retraction of a bias when
-        a partial match breaks, per-audio rule sets, more than 4096 sequences."""
+        a partial match breaks, more than 4096 sequences.  (A rule set per audio: defineRuleSet.)"""
         pairs = list(sequences.items()) if isinstance(sequences, dict) else list(sequences or [])
         seqs = [[int(t) for t in seq] for seq, _ in pairs]
         flat = np.ascontiguousarray([t for seq in seqs for t in seq], dtype=np.int32)
@@ -1031,6 +1031,66 @@ class Session:
         a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
         _check(self.lib.wh_session_phrase_rules_stats(self.handle, C.byref(a), C.byref(b), C.byref(c)))
         return int(a.value), int(b.value), int(c.value)
+
+    MAX_RULE_SETS = 16      # include/whisperhip.h WH_MAX_RULE_SETS (a design constant): index 0 is the session's own rules, 1 .. 15 the bank
+
+    def defineRuleSet(self, index: int, repetitionPenalty: float = 1.0, noRepeatNgramSize: int = 0, tokenBias=None, phrases=None):
+        """NO REFERENCE BEHAVIOUR.  Defines rule set `index` (1 .. 15) of the session's bank: one setLogitRules set (repetitionPenalty, noRepeatNgramSize,
+        tokenBias) plus one setPhraseRules list (phrases), with their limits, validation and arithmetic.  Every audio of transcribeWithOptions(..., ruleSets=...)
+        and every slot of decodeText / decodeTextMixed (setSlotRuleSets) names the set it decodes under, and audios with different sets share a device batch: a
+        slot under set k decodes to the bits of a pass whose session-level rules are set k.  Index 0 is the session's own rules (setLogitRules /
+        setPhraseRules), possibly none.  Only the index and nothing else undefines it.  A pass whose live slots all name 0 is unchanged; any other pass runs the
+        unfused sampler with one kernel per step in front of it (csrc/rule_sets.hip).  decodeTextBeam / decodeTextGuided /
+        decodeTextSpeculative and beamSize > 1 are refused for slots and audios under a set other than 0; an attached draft is ignored for a group that
+        carries sets.  The bank (about 5 MB) is allocated by the first definition."""
+        pairs = list(tokenBias.items()) if isinstance(tokenBias, dict) else list(tokenBias or [])
+        ids = np.ascontiguousarray([int(t) for t, _ in pairs], dtype=np.int32)
+        vals = np.ascontiguousarray([float(b) for _, b in pairs], dtype=np.float32)
+        lr = L.WhLogitRules(float(repetitionPenalty), int(noRepeatNgramSize), len(pairs), 0,
+                            ids.ctypes.data_as(L.PI32) if len(pairs) else None, vals.ctypes.data_as(L.PF) if len(pairs) else None)
+        seqp = list(phrases.items()) if isinstance(phrases, dict) else list(phrases or [])
+        seqs = [[int(t) for t in seq] for seq, _ in seqp]
+        flat = np.ascontiguousarray([t for seq in seqs for t in seq], dtype=np.int32)
+        lens = np.ascontiguousarray([len(seq) for seq in seqs], dtype=np.int32)
+        bias = np.ascontiguousarray([float(b) for _, b in seqp], dtype=np.float32)
+        pr = L.WhPhraseRules(len(seqp), 0, flat.ctypes.data_as(L.PI32) if len(flat) else None, lens.ctypes.data_as(L.PI32) if len(seqp) else None,
+                             bias.ctypes.data_as(L.PF) if len(seqp) else None)
+        _check(self.lib.wh_session_define_rule_set(self.handle, int(index), C.byref(lr), C.byref(pr)))
+
+    def ruleSet(self, index: int) -> dict:
+        """rule set `index` (0 = the session's own rules) as {"repetitionPenalty", "noRepeatNgramSize", "tokenBias": [(id, bias), ...], "phrases": [((id, ...),
+        bias), ...]} - the neutral values when the index is not defined"""
+        lr, pr = L.WhLogitRules(), L.WhPhraseRules()
+        _check(self.lib.wh_session_rule_set(self.handle, int(index), C.byref(lr), C.byref(pr)))
+        phrases, at = [], 0
+        for i in range(pr.n_sequences):
+            n = int(pr.lengths[i])
+            phrases.append((tuple(int(pr.tokens[at + k]) for k in range(n)), float(pr.biases[i])))
+            at += n
+        return {"repetitionPenalty": float(lr.repetition_penalty), "noRepeatNgramSize": int(lr.no_repeat_ngram_size),
+                "tokenBias": [(int(lr.bias_tokens[i]), float(lr.bias_values[i])) for i in range(lr.n_bias)], "phrases": phrases}
+
+    def setSlotRuleSets(self, setOfSlot=None):
+        """Step-level assignment by home slot: slot b of decodeText / decodeTextMixed decodes under rule set setOfSlot[b] (0 .. 15), every other slot and None
+        under 0.  It persists until changed; every transcribe* call takes the assignment over for its duration and leaves it all 0."""
+        if setOfSlot is None:
+            _check(self.lib.wh_session_set_slot_rule_sets(self.handle, None, 0))
+            return
+        a = np.ascontiguousarray([int(k) for k in setOfSlot], dtype=np.int32)
+        _check(self.lib.wh_session_set_slot_rule_sets(self.handle, a.ctypes.data_as(L.PI32), len(a)))
+
+    def slotRuleSets(self) -> List[int]:
+        """the rule set of every home slot of the session"""
+        out = (C.c_int32 * self.B)()
+        _check(self.lib.wh_session_slot_rule_sets(self.handle, out, self.B))
+        return [int(k) for k in out]
+
+    def ruleSetStats(self) -> Tuple[int, int, List[int]]:
+        """(set-aware decode passes, launches of rule_sets_kernel in them, per rule set the phrase matches counted on the device [16]) since the session was
+        created"""
+        a, b, m = C.c_int64(), C.c_int64(), (C.c_int64 * self.MAX_RULE_SETS)()
+        _check(self.lib.wh_session_rule_set_stats(self.handle, C.byref(a), C.byref(b), m))
+        return int(a.value), int(b.value), [int(v) for v in m]
 
     OPTION_MIXINGS = {"off": 0, "on": 1}
     MAX_OPTION_CLASSES = 16
@@ -1244,16 +1304,21 @@ class Session:
 
     # ---- TranscribeTask.run / WhisperKit.transcribe(audioArrays:)
     def transcribeWithOptions(self, audioArrays: Sequence[np.ndarray], decodeOptionsArray: Optional[Sequence[Optional[DecodingOptions]]] = None,
-                              specialTokens=None) -> List[Union[TranscriptionResult, WhisperError]]:
+                              specialTokens=None, *, ruleSets: Optional[Sequence[int]] = None) -> List[Union[TranscriptionResult, WhisperError]]:
         """WhisperKit.transcribeWithOptions(audioArrays:decodeOptionsArray:) (Core/WhisperKit.swift:716-812): one DecodingOptions per audio (None =
         DecodingOptions()) and one Result per audio - entry i is audio i's TranscriptionResult or the WhisperError it failed with; a failing
         audio does not fail its neighbours (`.failure(error)`, :786-790).  Raises only when the call itself could not run (mismatched
-        counts as in :724-726, device error, cancellation, an exception raised inside a callback)."""
+        counts as in :724-726, device error, cancellation, an exception raised inside a callback).
+        ruleSets (NO REFERENCE BEHAVIOUR; defineRuleSet): one rule set index per audio; audios with different sets share a device batch.  An index that is not
+        defined is that audio's WhisperError."""
         n = len(audioArrays)
         if decodeOptionsArray is None:
             decodeOptionsArray = [None] * n
         if len(decodeOptionsArray) != n:
             raise WhisperError(9, "The number of audio arrays and decoding options must be balanced.")
+        if ruleSets is not None and len(ruleSets) != n:
+            raise WhisperError(9, "The number of audio arrays and rule sets must be balanced.")
+        sets = None if ruleSets is None else (C.c_int32 * n)(*[int(k) for k in ruleSets])
         st = specialTokens if specialTokens is not None else self.model.specialTokens
         keep = [(o or DecodingOptions()).to_c() for o in decodeOptionsArray]        # keeps the option structs and their arrays alive
         optp = (L.POPT * n)(*[C.pointer(o) for o in keep])
@@ -1261,14 +1326,20 @@ class Session:
             hs = (C.c_void_p * n)(*[a._h for a in audioArrays])
             outs = (C.c_void_p * n)()
             stat = (C.c_int32 * n)()
-            self._guarded(self.lib.wh_transcribe_device_batch_with_options, self.handle, hs, n, optp, C.byref(st), outs, stat)
+            if sets is None:
+                self._guarded(self.lib.wh_transcribe_device_batch_with_options, self.handle, hs, n, optp, C.byref(st), outs, stat)
+            else:
+                self._guarded(self.lib.wh_transcribe_device_batch_with_rule_sets, self.handle, hs, n, optp, sets, C.byref(st), outs, stat)
             return [_collect(outs[i]) if stat[i] == 0 else WhisperError(int(stat[i]), self.lib.wh_session_item_error(self.handle, i).decode()) for i in range(n)]
         arrs = [np.ascontiguousarray(a, dtype=np.float32) for a in audioArrays]
         ptrs = (C.c_void_p * n)(*[a.ctypes.data for a in arrs])
         lens = (C.c_int32 * n)(*[len(a) for a in arrs])
         outs = (C.c_void_p * n)()
         stat = (C.c_int32 * n)()
-        self._guarded(self.lib.wh_transcribe_batch_with_options, self.handle, ptrs, lens, n, optp, C.byref(st), outs, stat)
+        if sets is None:
+            self._guarded(self.lib.wh_transcribe_batch_with_options, self.handle, ptrs, lens, n, optp, C.byref(st), outs, stat)
+        else:
+            self._guarded(self.lib.wh_transcribe_batch_with_rule_sets, self.handle, ptrs, lens, n, optp, sets, C.byref(st), outs, stat)
         return [_collect(outs[i]) if stat[i] == 0 else WhisperError(int(stat[i]), self.lib.wh_session_item_error(self.handle, i).decode()) for i in range(n)]
 
     def transcribeWithResults(self, audioArrays: Sequence[np.ndarray], options: Optional[DecodingOptions] = None, specialTokens=None):

@@ -811,6 +811,7 @@ void launch_decoder_step(const DecodeBuffers& db, const SamplerCfg* cfg_dev, con
     const bool mixed = sample && db.mixed;       // a mixed pass (option_mix.h): the per-class tables, the mixed instantiations
     launch_dec32_proj(P32_LOGITS, a, n_bt, st, mixed && fused);
     if (ns) launch_nospeech(*ns, db.seq, db.logits, B, V, st);      // before any sampler: the unfused one filters the rows in place, every one advances token_index
+    if (db.rule_sets && sample && !fused) launch_rule_sets(*db.rule_sets, db.seq, db.logits, B, V, st);      // a set-aware pass: every slot under the set its home slot names
     if (phrase_rules && sample && !fused) launch_phrase_rules(*phrase_rules, db.seq, db.logits, B, V, st);      // the raw rows too: phrase rules first, then the logit rules
     if (logit_rules && sample && !fused) launch_logit_rules(logit_rules, db.seq, db.logits, B, V, st);      // the raw rows, behind the no-speech kernel's read of them
     if (fused) {

@@ -270,7 +270,7 @@ static int get_step_graph(wh_session* s, int batch, int first_step, hipGraphExec
     // (a compacted pass bakes the slot table's address, the mapped kernel instantiations and its own slots per workgroup into its launches)
     const WhGraphKey key{batch, s->align_enabled ? 1 : 0, s->fused_greedy ? 1 : 0, s->align_enabled ? s->n_align_alloc : 0, db.self_rows, db.xattn_gate ? 1 : 0,
                          db.slot_home ? 1 : 0, db.slot_home ? s->pass_spw : 0, db.self_owner ? 1 : 0, db.mixed,
-                         (int)plan::nospeech_step_mask(first_step, kStepsPerGraph, s->pass_ns), s->pass_lr ? 1 : 0, s->pass_pr ? 1 : 0};
+                         (int)plan::nospeech_step_mask(first_step, kStepsPerGraph, s->pass_ns), s->pass_lr ? 1 : 0, s->pass_pr ? 1 : 0, s->pass_rs ? s->pass_rs_key : 0};
     auto it = s->graphs.find(key);
     if (it != s->graphs.end()) { s->graph_use[key] = ++s->graph_tick; *out = it->second; return WH_OK; }
     // The cache is capped (a large-v3 step graph holds ~2.5 k kernel nodes; a configuration = everything of the key but the row bound has up
@@ -279,7 +279,7 @@ static int get_step_graph(wh_session* s, int batch, int first_step, hipGraphExec
     const size_t cap = (size_t)knob::once<knob::WH_GRAPH_CAP>();
     while (s->graphs.size() >= cap) {
         auto same_cfg = [](const WhGraphKey& a, const WhGraphKey& b) {
-            return a.batch == b.batch && a.align == b.align && a.fused == b.fused && a.n_align == b.n_align && a.gate == b.gate && a.mapped == b.mapped && a.spw == b.spw && a.owner == b.owner && a.mixed == b.mixed && a.ns_mask == b.ns_mask && a.logit_rules == b.logit_rules && a.phrase_rules == b.phrase_rules;
+            return a.batch == b.batch && a.align == b.align && a.fused == b.fused && a.n_align == b.n_align && a.gate == b.gate && a.mapped == b.mapped && a.spw == b.spw && a.owner == b.owner && a.mixed == b.mixed && a.ns_mask == b.ns_mask && a.logit_rules == b.logit_rules && a.phrase_rules == b.phrase_rules && a.rule_sets == b.rule_sets;
         };
         const WhGraphKey* victim = nullptr;
         unsigned long long victim_last = ~0ull;
@@ -450,7 +450,7 @@ static int run_token_loop(wh_session* s, int batch, int loop_count, PassLayout* 
     int width = batch;                                   // (changes only through inpass_narrow)
     auto all_done_in = [](const SeqState* q, int n) { for (int b = 0; b < n; ++b) if (q[b].active && !q[b].done) return false; return true; };
     auto all_done = [&]() { return all_done_in(s->seq_host, width); };
-    auto count_steps = [&](int steps) { s->slot_steps += (long long)width * steps; if (L) s->inpass_slot_steps_saved += (long long)(L->width0 - width) * steps; if (s->pass_lr) s->lr_launches += steps; if (s->pass_pr) s->pr_launches += steps; };
+    auto count_steps = [&](int steps) { s->slot_steps += (long long)width * steps; if (L) s->inpass_slot_steps_saved += (long long)(L->width0 - width) * steps; if (s->pass_lr) s->lr_launches += steps; if (s->pass_pr) s->pr_launches += steps; if (s->pass_rs) s->rs_launches += steps; };
     // the last read of the pass: the compact slots, or - after a narrowing - every state by home slot (parked once more)
     auto final_read = [&]() -> int {
         if (L && L->switches > 0) {
@@ -572,6 +572,16 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
     if (mix) { opt = mix->opts[0]; prompt = mix->prompts[0]; n_prompt = mix->n_prompts[0]; }
     if (!opt || !st || !prompt || !out) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text: null argument");
     const int V = s->m->dims.n_vocab;
+    // ---- per-audio rule sets (wh_session_define_rule_set; NO REFERENCE BEHAVIOUR): a pass is set-aware iff a live slot names a set other than 0; a
+    // live slot that names an undefined set fails the call before anything is launched
+    const int32_t* const set_of_slot = s->rs_slot.empty() ? nullptr : s->rs_slot.data();
+    const bool set_aware = plan::rule_sets_pass_aware(set_of_slot, active, batch);
+    if (set_aware) {
+        unsigned defined = 0;
+        for (int k = 1; k < plan::kMaxRuleSets; ++k) if (s->rs_sets[k].defined) defined |= 1u << k;
+        const int bad = plan::rule_sets_first_undefined(set_of_slot, active, batch, defined);
+        if (bad >= 0) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text: slot %d is assigned rule set %d, which is not defined (wh_session_define_rule_set)", bad, set_of_slot[bad]);
+    }
     const int prefilled_index = 0;   // decoderInputs.cacheLength after reset (Core/Models.swift:313)
     const int n_cls = mix ? mix->n : 1;
     auto cls_prompt = [&](int c) { return mix ? mix->prompts[c] : prompt; };
@@ -620,7 +630,7 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
     for (int b = 0; b < batch; ++b) n_live += (active ? active[b] != 0 : 1);
     plan::CompactPassPlan cp{false, batch, s->use_xabs ? s->xabs.spw : 1};
     if (s->fallback_compaction == 1 && active) cp = plan::compact_pass_plan(n_live, batch, s->B, s->use_xabs ? s->xabs.spw : 1);
-    struct PassScope { wh_session* s; ~PassScope() { s->pass_mapped = false; s->pass_owner = false; s->pass_mixed = false; s->pass_ns = plan::NoSpeechRange{-1, -1}; s->pass_lr = false; s->pass_pr = false; } } pass_scope{s};      // (every exit: the next caller of decode_buffers sees a plain pass)
+    struct PassScope { wh_session* s; ~PassScope() { s->pass_mapped = false; s->pass_owner = false; s->pass_mixed = false; s->pass_ns = plan::NoSpeechRange{-1, -1}; s->pass_lr = false; s->pass_pr = false; s->pass_rs = false; } } pass_scope{s};      // (every exit: the next caller of decode_buffers sees a plain pass)
     const int width = cp.compact ? cp.width : batch;
     if (cp.compact) {
         if (!s->slot_home_dev) WH_HIP(s->mem.alloc(&s->slot_home_dev, (size_t)s->B, false));
@@ -665,14 +675,35 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
         s->fused_greedy = false;
         s->lr_host[2] = st->special_token_begin;
         WH_HIP(hipMemcpyAsync(s->lr_dev + 2, s->lr_host + 2, sizeof(int32_t), hipMemcpyHostToDevice, s->st));
-        s->pass_lr = true; s->lr_passes += 1;
+        if (!set_aware) { s->pass_lr = true; s->lr_passes += 1; }      // (a set-aware pass hands the table to rule_sets_kernel as set 0's)
     }
     // ---- device phrase rules (wh_session_set_phrase_rules; NO REFERENCE BEHAVIOUR): likewise, phrase_rules_kernel directly in front of logit_rules_kernel
     if (s->phrase_rules_on) {
         s->fused_greedy = false;
         s->pr_host[2] = st->special_token_begin;
         WH_HIP(hipMemcpyAsync(s->pr_dev + 2, s->pr_host + 2, sizeof(int32_t), hipMemcpyHostToDevice, s->st));
-        s->pass_pr = true; s->pr_passes += 1;
+        if (!set_aware) { s->pass_pr = true; s->pr_passes += 1; }
+    }
+    // ---- per-audio rule sets: a set-aware pass runs the unfused sampler with rule_sets_kernel alone in front of it - set 0 is the session's own two tables (as far
+    // as they are on), set k >= 1 lies in the bank.  Every defined set gets this call's special_token_begin (written when it differs from what the set holds);
+    // the slot table goes up by home slot, so compacted, narrowed and mixed passes need nothing else
+    if (set_aware) {
+        s->fused_greedy = false;
+        for (int k = 1; k < plan::kMaxRuleSets; ++k) {
+            wh_session::RuleSetCopy& c = s->rs_sets[k];
+            if (!c.defined || c.special_begin == st->special_token_begin) continue;
+            int32_t* base = s->rs_dev + whi::kRsOffBank + plan::rule_set_offset(k);
+            WH_HIP(hipMemsetD32Async(base + plan::kRuleSetOffPhrase + 2, st->special_token_begin, 1, s->st));
+            WH_HIP(hipMemsetD32Async(base + plan::kRuleSetOffLogit + 2, st->special_token_begin, 1, s->st));
+            c.special_begin = st->special_token_begin;
+        }
+        memset(s->rs_host, 0, sizeof(int32_t) * (size_t)s->B);
+        for (int b = 0; b < batch; ++b) if (plan::slot_is_live(active, b)) s->rs_host[b] = set_of_slot[b];
+        WH_HIP(hipMemcpyAsync(s->rs_dev + whi::kRsOffSlots, s->rs_host, sizeof(int32_t) * (size_t)s->B, hipMemcpyHostToDevice, s->st));
+        s->rs_args.own_logit = s->logit_rules_on ? s->lr_dev : nullptr;
+        s->rs_args.own_phrase = s->phrase_rules_on ? s->pr_dev : nullptr;
+        s->pass_rs_key = 1 | (s->logit_rules_on ? 2 : 0) | (s->phrase_rules_on ? 4 : 0);
+        s->pass_rs = true; s->rs_passes += 1;
     }
     WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * width, hipMemcpyHostToDevice, s->st));
     launch_rules_init(s->cfg_dev, s->seq, width, s->st, mix != nullptr);
@@ -946,14 +977,8 @@ extern "C" int wh_session_set_logit_rules(wh_session* s, const wh_logit_rules* r
     if (!s->lr_host) WH_HIP(s->mem.alloc_pinned(&s->lr_host, (size_t)plan::kLogitRulesWords));
     WH_HIP(hipStreamSynchronize(s->st));
     int32_t* h = s->lr_host;
-    memset(h, 0, sizeof(int32_t) * plan::kLogitRulesWords);
-    memcpy(h, &rules->repetition_penalty, sizeof(float));
-    h[1] = rules->no_repeat_ngram_size; h[2] = s->m->dims.n_vocab; h[3] = rules->n_bias;      // (h[2], the history's cut-off: every pass writes its own special_token_begin)
-    for (int i = 0; i < rules->n_bias; ++i) {
-        s->lr_bias_tokens[i] = rules->bias_tokens[i]; s->lr_bias_values[i] = rules->bias_values[i];
-        h[plan::kLogitRulesHead + i] = rules->bias_tokens[i];
-        memcpy(h + plan::kLogitRulesHead + plan::kLogitRulesMaxBias + i, &rules->bias_values[i], sizeof(float));
-    }
+    plan::logit_table_build(rules, s->m->dims.n_vocab, h);      // (h[2], the history's cut-off: every pass writes its own special_token_begin)
+    for (int i = 0; i < rules->n_bias; ++i) { s->lr_bias_tokens[i] = rules->bias_tokens[i]; s->lr_bias_values[i] = rules->bias_values[i]; }
     WH_HIP(hipMemcpyAsync(s->lr_dev, h, sizeof(int32_t) * plan::kLogitRulesWords, hipMemcpyHostToDevice, s->st));
     WH_HIP(hipStreamSynchronize(s->st));
     s->lr_rules = wh_logit_rules{rules->repetition_penalty, rules->no_repeat_ngram_size, rules->n_bias, 0, s->lr_bias_tokens, s->lr_bias_values};
@@ -1098,6 +1123,160 @@ extern "C" int wh_debug_phrase_rules_apply(wh_session* s, float* rows_inout, int
     WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * n_rows, hipMemcpyHostToDevice, s->st));
     WH_HIP(hipMemcpyAsync(s->logits, rows_inout, sizeof(float) * (size_t)n_rows * V, hipMemcpyHostToDevice, s->st));
     launch_phrase_rules(s->pr_args, s->seq, s->logits, n_rows, V, s->st);
+    WH_CHECK_LAUNCH();
+    WH_HIP(hipMemcpyAsync(rows_inout, s->logits, sizeof(float) * (size_t)n_rows * V, hipMemcpyDeviceToHost, s->st));
+    WH_HIP(hipStreamSynchronize(s->st));
+    return WH_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ per-audio rule sets
+// NO REFERENCE BEHAVIOUR (rule_sets_plan.h, rule_sets.hip): a bank of 15 numbered rule sets beside the session's own (index 0), each one
+// wh_logit_rules plus one wh_phrase_rules with the limits, validation and arithmetic of the two setters above; every home slot names the set it decodes under.
+// The first definition allocates everything in one piece and fills it with neutral sets; a definition rewrites its set in place, stream-ordered on the
+// session's stream behind a drained stream, so captured step graphs stay valid.
+static int rule_sets_ensure(wh_session* s) {
+    if (s->rs_dev) return WH_OK;
+    const size_t words = (size_t)whi::kRsOffBank + (size_t)plan::kRuleSetBankWords;
+    if (!s->rs_host) WH_HIP(s->mem.alloc_pinned(&s->rs_host, (size_t)kMaxSessionSlots + (size_t)plan::kRuleSetStride));
+    int32_t* dev = nullptr;
+    WH_HIP(s->mem.alloc(&dev, words, false));      // (filled on the session's stream: counters 0, every slot under set 0, every set neutral - p = 1.0f)
+    WH_HIP(hipMemsetAsync(dev, 0, sizeof(int32_t) * words, s->st));
+    for (int k = 1; k < plan::kMaxRuleSets; ++k)
+        WH_HIP(hipMemsetD32Async(dev + whi::kRsOffBank + plan::rule_set_offset(k) + plan::kRuleSetOffLogit, 0x3f800000, 1, s->st));
+    WH_HIP(hipStreamSynchronize(s->st));
+    s->rs_dev = dev;
+    s->rs_args = RuleSetsArgs{dev + whi::kRsOffBank, dev + whi::kRsOffSlots, nullptr, nullptr, reinterpret_cast<unsigned long long*>(dev), s->B};
+    return WH_OK;
+}
+extern "C" int wh_session_define_rule_set(wh_session* s, int index, const wh_logit_rules* logit_rules, const wh_phrase_rules* phrase_rules) {
+    if (!s || !s->m) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_define_rule_set: null session");
+    WH_TRY
+    if (!plan::rule_set_banked(index)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_define_rule_set: index %d (1 .. %d; 0 is the session's own set)", index, plan::kMaxRuleSets - 1);
+    if (const char* why = plan::logit_rules_invalid(logit_rules, s->m->dims.n_vocab)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_define_rule_set: %s", why);
+    if (const char* why = plan::phrase_rules_invalid(phrase_rules, s->m->dims.n_vocab)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_define_rule_set: %s", why);
+    const bool lr_off = plan::logit_rules_neutral(logit_rules), pr_off = plan::phrase_rules_neutral(phrase_rules);
+    wh_session::RuleSetCopy& c = s->rs_sets[index];
+    if (lr_off && pr_off && !c.defined) return WH_OK;      // (undefining what is not defined: nothing to write, nothing to allocate)
+    if (hipSetDevice(s->m->device) != hipSuccess) return set_error(WH_ERR_HIP, "wh_session_define_rule_set: hipSetDevice(%d) failed", s->m->device);
+    if (int r = rule_sets_ensure(s)) return r;
+    WH_HIP(hipStreamSynchronize(s->st));                    // nothing in flight reads the staging the host writes next
+    int32_t* stage = s->rs_host + kMaxSessionSlots;
+    plan::rule_set_build(logit_rules, phrase_rules, s->m->dims.n_vocab, stage);
+    WH_HIP(hipMemcpyAsync(s->rs_dev + whi::kRsOffBank + plan::rule_set_offset(index), stage, sizeof(int32_t) * (size_t)plan::kRuleSetStride, hipMemcpyHostToDevice, s->st));
+    WH_HIP(hipStreamSynchronize(s->st));
+    c.defined = !(lr_off && pr_off);
+    c.special_begin = s->m->dims.n_vocab;
+    c.bias_tokens.clear(); c.bias_values.clear(); c.tokens.clear(); c.lengths.clear(); c.biases.clear();
+    c.lr = wh_logit_rules{1.0f, 0, 0, 0, nullptr, nullptr};
+    c.pr = wh_phrase_rules{0, 0, nullptr, nullptr, nullptr};
+    if (!lr_off) {
+        c.bias_tokens.assign(logit_rules->bias_tokens, logit_rules->bias_tokens + logit_rules->n_bias);
+        c.bias_values.assign(logit_rules->bias_values, logit_rules->bias_values + logit_rules->n_bias);
+        c.lr = wh_logit_rules{logit_rules->repetition_penalty, logit_rules->no_repeat_ngram_size, logit_rules->n_bias, 0, c.bias_tokens.data(), c.bias_values.data()};
+    }
+    if (!pr_off) {
+        size_t n_ids = 0;
+        for (int i = 0; i < phrase_rules->n_sequences; ++i) n_ids += (size_t)phrase_rules->lengths[i];
+        c.tokens.assign(phrase_rules->tokens, phrase_rules->tokens + n_ids);
+        c.lengths.assign(phrase_rules->lengths, phrase_rules->lengths + phrase_rules->n_sequences);
+        c.biases.assign(phrase_rules->biases, phrase_rules->biases + phrase_rules->n_sequences);
+        c.pr = wh_phrase_rules{phrase_rules->n_sequences, 0, c.tokens.data(), c.lengths.data(), c.biases.data()};
+    }
+    return WH_OK;
+    WH_CATCH("wh_session_define_rule_set")
+}
+// The session's copy of set `index` (0: its own rules); the arrays stay valid until the next definition of that index.  Neutral halves when undefined
+extern "C" int wh_session_rule_set(const wh_session* s, int index, wh_logit_rules* logit_rules_out, wh_phrase_rules* phrase_rules_out) {
+    if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_rule_set: null session");
+    if (!plan::rule_set_index_valid(index)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_rule_set: index %d (0 .. %d)", index, plan::kMaxRuleSets - 1);
+    if (logit_rules_out) *logit_rules_out = index == 0 ? s->lr_rules : s->rs_sets[index].lr;
+    if (phrase_rules_out) *phrase_rules_out = index == 0 ? s->pr_rules : s->rs_sets[index].pr;
+    return WH_OK;
+}
+// Step-level assignment by home slot: slots n .. max_batch - 1 and a null table name set 0.  Any index of 0 .. 15 is accepted here; a decode call whose
+// live slots name an undefined set fails with WH_ERR_INVALID_ARGUMENT
+extern "C" int wh_session_set_slot_rule_sets(wh_session* s, const int32_t* set_of_slot, int n) {
+    if (!s || !s->m) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_slot_rule_sets: null session");
+    WH_TRY
+    if (!set_of_slot) { s->rs_slot.clear(); return WH_OK; }
+    if (n < 0 || n > s->B) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_slot_rule_sets: %d slots (0 .. %d)", n, s->B);
+    for (int b = 0; b < n; ++b)
+        if (!plan::rule_set_index_valid(set_of_slot[b])) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_slot_rule_sets: slot %d names rule set %d (0 .. %d)", b, set_of_slot[b], plan::kMaxRuleSets - 1);
+    std::vector<int32_t> next((size_t)s->B, 0);
+    for (int b = 0; b < n; ++b) next[(size_t)b] = set_of_slot[b];
+    s->rs_slot.swap(next);
+    return WH_OK;
+    WH_CATCH("wh_session_set_slot_rule_sets")
+}
+extern "C" int wh_session_slot_rule_sets(const wh_session* s, int32_t* set_of_slot_out, int n) {
+    if (!s || !set_of_slot_out) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_slot_rule_sets: null argument");
+    if (n < 0 || n > s->B) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_slot_rule_sets: %d slots (0 .. %d)", n, s->B);
+    for (int b = 0; b < n; ++b) set_of_slot_out[b] = b < (int)s->rs_slot.size() ? s->rs_slot[(size_t)b] : 0;
+    return WH_OK;
+}
+// matches [WH_MAX_RULE_SETS]: the device counters, one copy behind a drained stream
+extern "C" int wh_session_rule_set_stats(const wh_session* s, int64_t* passes, int64_t* launches, int64_t* matches) {
+    if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_rule_set_stats: null session");
+    if (passes) *passes = s->rs_passes;
+    if (launches) *launches = s->rs_launches;
+    if (matches) {
+        unsigned long long v[plan::kMaxRuleSets] = {};
+        if (s->rs_dev) {
+            if (hipSetDevice(s->m->device) != hipSuccess) return set_error(WH_ERR_HIP, "wh_session_rule_set_stats: hipSetDevice(%d) failed", s->m->device);
+            WH_HIP(hipStreamSynchronize(s->st));
+            WH_HIP(hipMemcpy(v, s->rs_dev, sizeof(v), hipMemcpyDeviceToHost));
+        }
+        for (int k = 0; k < plan::kMaxRuleSets; ++k) matches[k] = (int64_t)v[k];
+    }
+    return WH_OK;
+}
+
+// Development aid: rule_sets_kernel alone over caller-supplied rows and histories, in the shape of wh_debug_phrase_rules_apply.  set_of_row[i]: the set of row i
+// (row i is home slot i) - ANY value: the kernel must leave a row under an index that is out of range or undefined alone.  At least one banked set must have
+// been defined (the bank exists).  The launch's matches go into the session's counters.
+extern "C" int wh_debug_rule_sets_apply(wh_session* s, float* rows_inout, int n_rows, const int32_t* tokens, const int32_t* n_tokens, const int32_t* prompt_lens,
+                                        const int32_t* live, const int32_t* set_of_row) {
+    if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_rule_sets_apply: null session");
+    CHECK_SESSION(s); CHECK_BATCH(s, n_rows);
+    if (!rows_inout || !tokens || !n_tokens || !prompt_lens || !set_of_row) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_rule_sets_apply: null argument");
+    if (!s->rs_dev) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_rule_sets_apply: the session has no rule set defined (wh_session_define_rule_set)");
+    const int V = s->m->dims.n_vocab;
+    for (int i = 0; i < n_rows; ++i) {
+        if (n_tokens[i] < 0 || n_tokens[i] > kMaxTok || prompt_lens[i] < 0 || prompt_lens[i] > n_tokens[i])
+            return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_rule_sets_apply: row %d has %d tokens, prompt length %d (0 <= prompt <= tokens <= %d)", i, n_tokens[i], prompt_lens[i], kMaxTok);
+        for (int k = 0; k < n_tokens[i]; ++k)
+            if (tokens[(size_t)i * kMaxTok + k] < 0 || tokens[(size_t)i * kMaxTok + k] >= V)
+                return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_rule_sets_apply: row %d token %d out of vocabulary", i, tokens[(size_t)i * kMaxTok + k]);
+    }
+    wh_special_tokens st;
+    memset(&st, 0, sizeof(st));
+    if (wh_special_tokens_default(s->m, &st) != WH_OK) st.special_token_begin = V;
+    WH_HIP(hipStreamSynchronize(s->st));                  // nothing in flight reads the staging the host writes next
+    for (int i = 0; i < n_rows; ++i) {
+        SeqState& q = s->seq_host[i];
+        memset(&q, 0, sizeof(q));
+        for (int k = 0; k < n_tokens[i]; ++k) q.tokens[k] = tokens[(size_t)i * kMaxTok + k];
+        q.n_tokens = n_tokens[i]; q.prompt_len = prompt_lens[i]; q.active = (!live || live[i]) ? 1 : 0; q.rng_lane = i;
+    }
+    if (s->logit_rules_on) { s->lr_host[2] = st.special_token_begin; WH_HIP(hipMemcpyAsync(s->lr_dev + 2, s->lr_host + 2, sizeof(int32_t), hipMemcpyHostToDevice, s->st)); }
+    if (s->phrase_rules_on) { s->pr_host[2] = st.special_token_begin; WH_HIP(hipMemcpyAsync(s->pr_dev + 2, s->pr_host + 2, sizeof(int32_t), hipMemcpyHostToDevice, s->st)); }
+    for (int k = 1; k < plan::kMaxRuleSets; ++k) {
+        wh_session::RuleSetCopy& c = s->rs_sets[k];
+        if (!c.defined || c.special_begin == st.special_token_begin) continue;
+        int32_t* base = s->rs_dev + whi::kRsOffBank + plan::rule_set_offset(k);
+        WH_HIP(hipMemsetD32Async(base + plan::kRuleSetOffPhrase + 2, st.special_token_begin, 1, s->st));
+        WH_HIP(hipMemsetD32Async(base + plan::kRuleSetOffLogit + 2, st.special_token_begin, 1, s->st));
+        c.special_begin = st.special_token_begin;
+    }
+    memset(s->rs_host, 0, sizeof(int32_t) * (size_t)s->B);
+    for (int i = 0; i < n_rows; ++i) s->rs_host[i] = set_of_row[i];
+    WH_HIP(hipMemcpyAsync(s->rs_dev + whi::kRsOffSlots, s->rs_host, sizeof(int32_t) * (size_t)s->B, hipMemcpyHostToDevice, s->st));
+    RuleSetsArgs a = s->rs_args;
+    a.own_logit = s->logit_rules_on ? s->lr_dev : nullptr;
+    a.own_phrase = s->phrase_rules_on ? s->pr_dev : nullptr;
+    WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * n_rows, hipMemcpyHostToDevice, s->st));
+    WH_HIP(hipMemcpyAsync(s->logits, rows_inout, sizeof(float) * (size_t)n_rows * V, hipMemcpyHostToDevice, s->st));
+    launch_rule_sets(a, s->seq, s->logits, n_rows, V, s->st);
     WH_CHECK_LAUNCH();
     WH_HIP(hipMemcpyAsync(rows_inout, s->logits, sizeof(float) * (size_t)n_rows * V, hipMemcpyDeviceToHost, s->st));
     WH_HIP(hipStreamSynchronize(s->st));
@@ -1321,6 +1500,7 @@ extern "C" int wh_decode_text_guided(wh_session* s, int n_audio, int K, const wh
     if (int r = spec_check_tokens(who, n_audio, prompt, n_prompt, proposals, n_proposals, s->m->dims.n_vocab)) return r;
     if (s->logit_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: the session has logit rules set (wh_session_set_logit_rules), which the speculative pass does not run", who);
     if (s->phrase_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: the session has phrase rules set (wh_session_set_phrase_rules), which the speculative pass does not run", who);
+    if (whi::rule_sets_assigned(s, n_audio)) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: a slot of the call is assigned a rule set (wh_session_set_slot_rule_sets), which the speculative pass does not run", who);
     WH_TRY
     ScriptedProposer pr;
     pr.lists = proposals; pr.n_lists = n_proposals; pr.end_token = st->end_token;
@@ -1349,6 +1529,7 @@ extern "C" int wh_decode_text_speculative(wh_session* s, wh_session* draft, int 
     if (int r = spec_check_draft(who, s, draft, n_audio)) return r;
     if (s->logit_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: the session has logit rules set (wh_session_set_logit_rules), which the speculative pass does not run", who);
     if (s->phrase_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: the session has phrase rules set (wh_session_set_phrase_rules), which the speculative pass does not run", who);
+    if (whi::rule_sets_assigned(s, n_audio)) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: a slot of the call is assigned a rule set (wh_session_set_slot_rule_sets), which the speculative pass does not run", who);
     WH_TRY
     // the draft's sampler tables (the same options; its own vocabulary-sized masks) and switches, on its own stream, which is then idle for the pass
     int r = whi::upload_sampler_cfg(draft, opt, st, 0, n_prompt, 0, opt->seed);
@@ -1452,6 +1633,7 @@ struct AudioJob {
     size_t clip = 0; int seek = 0; bool started = false; bool finished = false;
     int windows = 0;
     int cls = 0;                                    // option class inside its group (option mixing; 0 otherwise)
+    int rule_set = 0;                               // the rule set this audio decodes under (wh_transcribe_batch_with_rule_sets; 0 = the session's own)
     wh_transcription* tr;
     int cur_seek = 0, cur_size = 0;   // window in flight
 };
@@ -1498,6 +1680,10 @@ static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_
     if (beam > 1 && opt->word_timestamps) return set_error(WH_ERR_INVALID_ARGUMENT, "beam_size > 1 cannot be combined with word_timestamps");
     if (beam > 1 && s->logit_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "beam_size > 1 cannot be combined with the session's logit rules (wh_session_set_logit_rules)");
     if (beam > 1 && s->phrase_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "beam_size > 1 cannot be combined with the session's phrase rules (wh_session_set_phrase_rules)");
+    bool job_sets = false;      // per-audio rule sets: does an audio of this group name a set other than 0?  (the set never splits a group: rule_sets_plan.h)
+    for (const auto& j : jobs) job_sets |= j.rule_set != 0;
+    s->rs_slot.clear();         // (a group before this one may have carried sets: this one starts with every slot under 0)
+    if (beam > 1 && job_sets) return set_error(WH_ERR_INVALID_ARGUMENT, "beam_size > 1 cannot be combined with a rule set (wh_transcribe_batch_with_rule_sets)");
     if (beam > s->B) return set_error(WH_ERR_INVALID_ARGUMENT, "beam_size %d exceeds the session's %d slots", beam, s->B);
     const int round_cap = s->B / beam;
     std::vector<int> slot_job;   // job index per slot for the current round
@@ -1536,6 +1722,11 @@ static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_
         }
         if (slot_job.empty()) break;
         const int nb = (int)slot_job.size();
+        // per-audio rule sets: the round's windows name their audios' sets by home slot (decode_text_impl uploads the table for every set-aware pass)
+        if (job_sets) {
+            s->rs_slot.assign((size_t)s->B, 0);
+            for (int b = 0; b < nb; ++b) s->rs_slot[(size_t)b] = jobs[slot_job[b]].rule_set;
+        }
         double t1 = now_s();
         int r = wh_log_mel_spectrogram(s, nb); if (r) return r;
         hipStreamSynchronize(s->st);
@@ -1621,10 +1812,10 @@ static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_
                 const MixClasses mix{(int)classes->size(), classes->data(), cls_slot.data(), mix_pp.data(), mix_np.data(), opt_slot.data()};
                 r = decode_text_impl(s, nb, nullptr, st, nullptr, 0, langs ? ml.data() : nullptr, tv.data(), active.data(), seed, tmp.data(), &mix);
                 if (r) return r;
-            } else if (s->draft && s->no_speech_detection == plan::kNoSpeechOff && !s->logit_rules_on && !s->phrase_rules_on && ti == 0 && temps[ti] == 0.0f && all_active && beam == 1 && !s->progress_cb && plan::spec_fits(nb, s->draft_k, s->B) &&
+            } else if (s->draft && s->no_speech_detection == plan::kNoSpeechOff && !s->logit_rules_on && !s->phrase_rules_on && !job_sets && ti == 0 && temps[ti] == 0.0f && all_active && beam == 1 && !s->progress_cb && plan::spec_fits(nb, s->draft_k, s->B) &&
                        !spec_check_draft("wh_transcribe", s, s->draft, nb)) {
                 // first rung with a draft attached (wh_session_set_draft) and room for the rings: the speculative pass (results are the ordinary pass's).  The
-                // speculative pass reports no no-speech value and runs neither logit nor phrase rules, so a session with any of them on runs the ordinary pass below instead.  The
+                // speculative pass reports no no-speech value and runs neither logit nor phrase rules nor rule sets, so a session with any of them on (or a group that carries sets) runs the ordinary pass below instead.  The
                 // draft gets the same windows through its own log-mel and encoder
                 wh_session* const dr = s->draft;
                 for (int b = 0; b < nb; ++b) {
@@ -1743,14 +1934,21 @@ static bool same_group_options(const wh_decoding_options& a, const wh_decoding_o
 // devs: null, or (wh_transcribe_*device*) the device audio pcm[i] points into, per audio
 static int transcribe_items(wh_session* s, const float* const* pcm, const int32_t* n_samples, int n_audio, const wh_decoding_options* const* opts,
                             const wh_decoding_options* shared, const wh_special_tokens* st, wh_transcription** out, int32_t* statuses,
-                            const wh_device_audio* const* devs = nullptr) {
+                            const wh_device_audio* const* devs = nullptr, const int32_t* rule_sets = nullptr) {
     wh_decoding_options dflt;
     wh_decoding_options_default(&dflt);
+    // per-audio rule sets (rule_sets: [n_audio] or null = all 0): the call owns the session's slot assignment for its duration and leaves it all 0, so a
+    // step-level assignment never reaches a window.  An audio is `ruled` iff it decodes under any rules at all: that bit splits groups, the set index does not
+    struct SlotSetScope { wh_session* s; ~SlotSetScope() { s->rs_slot.clear(); } } slot_set_scope{s};
+    s->rs_slot.clear();
+    const bool session_rules_on = s->logit_rules_on || s->phrase_rules_on;
+    std::vector<unsigned char> ruled((size_t)n_audio, session_rules_on ? 1 : 0);
     s->item_status.assign((size_t)n_audio, WH_OK);
     s->item_error.assign((size_t)n_audio, std::string());
     std::vector<AudioJob> all((size_t)n_audio);
     std::vector<int> group_of((size_t)n_audio, -1);
     std::vector<const wh_decoding_options*> group_opt;
+    std::vector<unsigned char> group_ruled;      // (the partition first, then the grouping inside each part)
     for (int i = 0; i < n_audio; ++i) {
         AudioJob& j = all[(size_t)i];
         j.index = i; j.pcm = pcm[i]; j.n = n_samples[i]; j.tr = nullptr;
@@ -1761,9 +1959,15 @@ static int transcribe_items(wh_session* s, const float* const* pcm, const int32_
             j.status = set_error(WH_ERR_AUDIO_PROCESSING_FAILED, "audio %d: invalid buffer", i); j.error = wh_last_error();
             continue;
         }
+        j.rule_set = rule_sets ? rule_sets[i] : 0;
+        if (j.rule_set != 0 && (!plan::rule_set_banked(j.rule_set) || !s->rs_sets[j.rule_set].defined)) {
+            j.status = set_error(WH_ERR_INVALID_ARGUMENT, "audio %d: rule set %d is not defined (wh_session_define_rule_set: 1 .. %d)", i, j.rule_set, plan::kMaxRuleSets - 1); j.error = wh_last_error();
+            continue;
+        }
+        ruled[(size_t)i] = plan::rule_set_ruled(j.rule_set, session_rules_on) ? 1 : 0;
         int g = -1;
-        for (size_t k = 0; k < group_opt.size() && g < 0; ++k) if (same_group_options(*group_opt[k], *j.opt)) g = (int)k;
-        if (g < 0) { g = (int)group_opt.size(); group_opt.push_back(j.opt); }
+        for (size_t k = 0; k < group_opt.size() && g < 0; ++k) if (group_ruled[k] == ruled[(size_t)i] && same_group_options(*group_opt[k], *j.opt)) g = (int)k;
+        if (g < 0) { g = (int)group_opt.size(); group_opt.push_back(j.opt); group_ruled.push_back(ruled[(size_t)i]); }
         group_of[(size_t)i] = g;
     }
     // option mixing (wh_session_set_option_mixing 1): the groups are the batch keys (option_mix.h option_mix_plan); a group's audios carry their class
@@ -1772,7 +1976,7 @@ static int transcribe_items(wh_session* s, const float* const* pcm, const int32_
     if (mixing) {
         std::vector<const wh_decoding_options*> po((size_t)n_audio, nullptr);
         for (int i = 0; i < n_audio; ++i) if (group_of[(size_t)i] >= 0) po[(size_t)i] = all[(size_t)i].opt;
-        mixp = plan::option_mix_plan(po.data(), n_audio);
+        mixp = plan::rule_sets_mix_plan(po.data(), rule_sets ? ruled.data() : nullptr, n_audio);
         group_of = mixp.group;
         group_opt.clear();
         for (const auto& cl : mixp.classes) group_opt.push_back(cl[0]);
@@ -1904,6 +2108,28 @@ extern "C" int wh_transcribe_device_batch_with_options(wh_session* s, const wh_d
     for (int i = 0; i < n_audio; ++i) { ptrs[(size_t)i] = audios[i] ? audios[i]->data : nullptr; lens[(size_t)i] = audios[i] ? audios[i]->n : -1; }    // a null audio: "invalid buffer", alone
     return transcribe_items(s, ptrs.data(), lens.data(), n_audio, opts, nullptr, st, out, statuses, audios);
     WH_CATCH("wh_transcribe_device_batch_with_options")
+}
+
+// ---- wh_transcribe_batch_with_options / wh_transcribe_device_batch_with_options with a rule set per audio (rule_sets_plan.h)
+extern "C" int wh_transcribe_batch_with_rule_sets(wh_session* s, const float* const* pcm, const int32_t* n_samples, int n_audio, const wh_decoding_options* const* opts,
+                                                  const int32_t* rule_set_of_audio, const wh_special_tokens* st, wh_transcription** out, int32_t* statuses) {
+    CHECK_SESSION(s);
+    if (!pcm || !n_samples || n_audio < 1 || !st || !out) return set_error(WH_ERR_TRANSCRIPTION_FAILED, "wh_transcribe_batch_with_rule_sets: null argument");
+    WH_TRY
+    return transcribe_items(s, pcm, n_samples, n_audio, opts, nullptr, st, out, statuses, nullptr, rule_set_of_audio);
+    WH_CATCH("wh_transcribe_batch_with_rule_sets")
+}
+extern "C" int wh_transcribe_device_batch_with_rule_sets(wh_session* s, const wh_device_audio* const* audios, int n_audio, const wh_decoding_options* const* opts,
+                                                         const int32_t* rule_set_of_audio, const wh_special_tokens* st, wh_transcription** out, int32_t* statuses) {
+    CHECK_SESSION(s);
+    if (!audios || n_audio < 1 || !st || !out) return set_error(WH_ERR_TRANSCRIPTION_FAILED, "wh_transcribe_device_batch_with_rule_sets: null argument");
+    WH_TRY
+    if (int r = check_device_audios(s, audios, n_audio, "wh_transcribe_device_batch_with_rule_sets")) return r;
+    std::vector<const float*> ptrs((size_t)n_audio);
+    std::vector<int32_t> lens((size_t)n_audio);
+    for (int i = 0; i < n_audio; ++i) { ptrs[(size_t)i] = audios[i] ? audios[i]->data : nullptr; lens[(size_t)i] = audios[i] ? audios[i]->n : -1; }    // a null audio: "invalid buffer", alone
+    return transcribe_items(s, ptrs.data(), lens.data(), n_audio, opts, nullptr, st, out, statuses, audios, rule_set_of_audio);
+    WH_CATCH("wh_transcribe_device_batch_with_rule_sets")
 }
 
 extern "C" int wh_transcribe_chunked_device(wh_session* s, wh_device_audio* a, const wh_decoding_options* opt, const wh_special_tokens* st,

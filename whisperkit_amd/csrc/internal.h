@@ -14,6 +14,7 @@
 #include "logit_rules_plan.h"
 #include "nospeech_plan.h"
 #include "phrase_rules_plan.h"
+#include "rule_sets_plan.h"
 #include "text.h"
 #include "whisperhip.h"
 
@@ -90,9 +91,11 @@ struct WhGraphKey {
     int ns_mask;          // bit i: step i of the graph stores its logits rows and runs nospeech_kernel (nospeech_plan.h nospeech_step_mask); 0 with the mode off
     int logit_rules;      // 1: every step runs logit_rules_kernel before the (unfused) sampler (wh_session_set_logit_rules); 0 with no rules set
     int phrase_rules;     // 1: every step runs phrase_rules_kernel in front of that (wh_session_set_phrase_rules); 0 with no phrase rules set
+    int rule_sets;        // 0, or a set-aware pass (rule_sets_plan.h): 1 | 2 (the session's own logit rules are handed to rule_sets_kernel) | 4 (its phrase rules are) -
+                          // the launch bakes those two pointers or null; logit_rules and phrase_rules are 0 then
     bool operator<(const WhGraphKey& o) const {
-        return std::tie(batch, align, fused, n_align, self_rows, gate, mapped, spw, owner, mixed, ns_mask, logit_rules, phrase_rules) <
-               std::tie(o.batch, o.align, o.fused, o.n_align, o.self_rows, o.gate, o.mapped, o.spw, o.owner, o.mixed, o.ns_mask, o.logit_rules, o.phrase_rules);
+        return std::tie(batch, align, fused, n_align, self_rows, gate, mapped, spw, owner, mixed, ns_mask, logit_rules, phrase_rules, rule_sets) <
+               std::tie(o.batch, o.align, o.fused, o.n_align, o.self_rows, o.gate, o.mapped, o.spw, o.owner, o.mixed, o.ns_mask, o.logit_rules, o.phrase_rules, o.rule_sets);
     }
 };
 
@@ -230,6 +233,26 @@ struct wh_session {
     wh::PhraseRulesArgs pr_args{nullptr, nullptr};
     bool pass_pr = false;
     long long pr_passes = 0, pr_launches = 0;      // wh_session_phrase_rules_stats (matches: the device counter)
+    // per-audio rule sets (wh_session_define_rule_set: host.hip, rule_sets_plan.h, rule_sets.hip).  rs_sets[k], k = 1 .. 15: the session's copy of banked set k
+    // (entry 0 is never used: set 0 is lr_rules / pr_rules above).  rs_slot: the set index of every home slot, empty = all 0; the step-level setter writes it,
+    // every wh_transcribe* call owns it for its duration and leaves it all 0.  Everything on the device is ONE allocation made by the first definition:
+    // rs_dev = match counters [kMaxRuleSets] (64-bit) | slot table [kMaxSessionSlots] | bank [15][kRuleSetStride], at fixed addresses so that captured step
+    // graphs stay valid; rs_host (pinned) = slot table mirror [kMaxSessionSlots] | the staging of one set [kRuleSetStride].  pass_rs holds only while
+    // decode_text_impl runs a set-aware pass; rs_args is what its launches bake, pass_rs_key the graph key's field.
+    struct RuleSetCopy {
+        bool defined = false;
+        int special_begin = -1;                    // the special_token_begin word the device copy holds (-1: not known)
+        wh_logit_rules lr{1.0f, 0, 0, 0, nullptr, nullptr};
+        wh_phrase_rules pr{0, 0, nullptr, nullptr, nullptr};
+        std::vector<int32_t> bias_tokens, tokens, lengths;
+        std::vector<float> bias_values, biases;
+    };
+    RuleSetCopy rs_sets[wh::plan::kMaxRuleSets];
+    std::vector<int32_t> rs_slot;
+    int32_t *rs_dev = nullptr, *rs_host = nullptr;
+    wh::RuleSetsArgs rs_args{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+    bool pass_rs = false; int pass_rs_key = 0;
+    long long rs_passes = 0, rs_launches = 0;      // wh_session_rule_set_stats (matches: the device counters)
     hipEvent_t ev[8]{};
     bool align_enabled = false;
     wh_timings last_timings{};
@@ -301,4 +324,11 @@ inline const wh::NoSpeechArgs* nospeech_step_args(const wh_session* s, int step)
 inline const int* logit_rules_step_args(const wh_session* s) { return s->pass_lr ? s->lr_dev : nullptr; }
 // device phrase rules: likewise
 inline const wh::PhraseRulesArgs* phrase_rules_step_args(const wh_session* s) { return s->pass_pr ? &s->pr_args : nullptr; }
+// per-audio rule sets: does any of the home slots 0 .. n - 1 name a set other than 0?  (the passes that do not run rule sets refuse such a call)
+inline bool rule_sets_assigned(const wh_session* s, int n) {
+    for (int b = 0; b < n && b < (int)s->rs_slot.size(); ++b) if (s->rs_slot[(size_t)b] != 0) return true;
+    return false;
+}
+// the device regions of rs_dev, in 32-bit words
+constexpr int kRsOffSlots = 2 * wh::plan::kMaxRuleSets, kRsOffBank = kRsOffSlots + wh::kMaxSessionSlots;
 }  // namespace whi

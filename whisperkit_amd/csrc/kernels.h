@@ -235,6 +235,8 @@ struct DecodeBuffers {
     int mixed;               // 1: a mixed pass (launch_decoder_step below).  Host-side only
     int owner_slots;         // 0, or the slot count self_owner's entries are clamped to instead of `batch`: a pass that narrowed (compact.hip) reads history
                              // rows from the caches of slots beyond its present width.  Host-side only: the kernels' arguments keep their layout
+    const struct RuleSetsArgs* rule_sets;   // null, or a set-aware pass (rule_sets.hip, launch_decoder_step below): rule_sets_kernel runs in front of the unfused
+                             // sampler in place of phrase_rules_kernel / logit_rules_kernel.  Host-side only
 };
 constexpr int kStatBlocks = 1792; // >= workgroups of the logits kernel (V / 64 rows: GEMV path, V / 32 rows: MFMA path), multiple of 256
 // Largest vocabulary the sampling kernels cover: sampler_kernel holds SAMP_T x SAMP_E = 1024 x 51 ids in registers, the fused greedy
@@ -377,9 +379,24 @@ struct PhraseRulesArgs {
 // one workgroup per slot of `batch`: a live slot adds, for every target of the table, the summed biases of the sequences its history matches to its row of
 // logits ([batch][n_vocab], as the step's logits launch wrote it) - between the logits launch and logit_rules_kernel / the sampler launch
 void launch_phrase_rules(const PhraseRulesArgs& a, const SeqState* seq, float* logits, int batch, int n_vocab, hipStream_t st);
+// per-audio rule sets (rule_sets.hip, rule_sets_plan.h; NO REFERENCE BEHAVIOUR): session memory at fixed addresses - the bank of sets 1 .. 15
+// (15 x kRuleSetStride words), the set index of every HOME slot [n_slots], the session's own two tables for set 0 (either may be null: that half is off)
+// and the per-set 64-bit counters of matching sequences of length >= 2 [kMaxRuleSets] (or null)
+struct RuleSetsArgs {
+    const int* bank;
+    const int* slot_set;
+    const int* own_phrase;
+    const int* own_logit;
+    unsigned long long* matches;
+    int n_slots;
+};
+// one workgroup per slot of `batch`: a live slot applies the phrase rules, then the logit rules, of the set its home slot names to its row of logits
+// ([batch][n_vocab], as the step's logits launch wrote it) - between the logits launch and the sampler launch, in ONE launch
+void launch_rule_sets(const RuleSetsArgs& a, const SeqState* seq, float* logits, int batch, int n_vocab, hipStream_t st);
 // ns (or null): the step stores its logits rows even on the fused-greedy path and runs nospeech_kernel between the logits launch and the sampler launch
 // logit_rules (or null; only with the unfused sampler): logit_rules_kernel runs behind it, before the sampler
 // phrase_rules (or null; only with the unfused sampler): phrase_rules_kernel runs directly in front of logit_rules_kernel
+// db.rule_sets (or null; only with the unfused sampler): a set-aware pass - rule_sets_kernel runs there instead, and both of the above are null
 void launch_decoder_step(const DecodeBuffers& db, const SamplerCfg* cfg_dev, const int* suppress_dev, bool sample, hipStream_t st, const NoSpeechArgs* ns = nullptr,
                          const int* logit_rules = nullptr, const PhraseRulesArgs* phrase_rules = nullptr);
 // filter rules of the first sampling step of a decodeText call (later steps: computed by the sampler itself)
