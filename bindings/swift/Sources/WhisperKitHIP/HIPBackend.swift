@@ -93,6 +93,32 @@ public final class HIPSession {
         try check(wh_session_no_speech_stats(handle, &a, &b, &c))
         return (Int(a), Int(b), Int(c))
     }
+    /// Token alternatives (wh_session_set_token_alternatives; NO REFERENCE BEHAVIOUR: torch.topk(log_softmax(row / T), n) and the entropy of that distribution):
+    /// 0 (default) = off; 1 ... 8 = every position a decode pass samples and appends records the n best (id, logProb) pairs of the distribution the token was
+    /// drawn from and its entropy in nats, inside the sampler's own launch.  Tokens and log-probabilities do not change; beam, guided and speculative passes are
+    /// refused while the mode is on.
+    public func setTokenAlternatives(_ n: Int) throws { try check(wh_session_set_token_alternatives(handle, Int32(n))) }
+    public var tokenAlternatives: Int { Int(wh_session_token_alternatives(handle)) }
+    /// After a decodeText call: the rows of home slot `slot`, aligned with that slot's result tokens - ids / logProbs [nTokens][n], entropies [nTokens];
+    /// (-1, -inf) / 0 where nothing was recorded.  n == 0: the slot has none.
+    public func decodeAlternatives(slot: Int) throws -> (ids: [Int32], logProbs: [Float], entropies: [Float], n: Int, nTokens: Int) {
+        var ids = [Int32](repeating: -1, count: Int(WH_MAX_RESULT_TOKENS) * Int(WH_MAX_ALTERNATIVES))
+        var lps = [Float](repeating: -.infinity, count: ids.count)
+        var ent = [Float](repeating: 0, count: Int(WH_MAX_RESULT_TOKENS))
+        var n: Int32 = 0, nt: Int32 = 0
+        try check(wh_decode_alternatives(handle, Int32(slot), &ids, &lps, &ent, &n, &nt))
+        return (Array(ids[0 ..< Int(n * nt)]), Array(lps[0 ..< Int(n * nt)]), Array(ent[0 ..< Int(nt)]), Int(n), Int(nt))
+    }
+    /// The flat rows of a transcription, aligned with wh_transcription_tokens (segment i owns [token_offset, token_offset + n_tokens) of them as well);
+    /// nil when the transcription carries none.
+    public static func transcriptionAlternatives(_ t: OpaquePointer) throws -> (ids: [Int32], logProbs: [Float], entropies: [Float], n: Int)? {
+        var ip: UnsafePointer<Int32>? = nil, lp: UnsafePointer<Float>? = nil, ep: UnsafePointer<Float>? = nil
+        var n: Int32 = 0, nt: Int32 = 0
+        try check(wh_transcription_alternatives(t, &ip, &lp, &ep, &n, &nt))
+        guard n > 0, let i = ip, let l = lp, let e = ep else { return nil }
+        return (Array(UnsafeBufferPointer(start: i, count: Int(n * nt))), Array(UnsafeBufferPointer(start: l, count: Int(n * nt))),
+                Array(UnsafeBufferPointer(start: e, count: Int(nt))), Int(n))
+    }
     /// The probe (wh_no_speech_probs): noSpeechProb of the encoded windows in slots 0 ..< batch from one step on <|startoftranscript|> at position 0; the decode
     /// state is put back.  Not conditioned on promptTokens.
     public func noSpeechProbs(batch: Int, specialTokens: wh_special_tokens) throws -> [Float] {

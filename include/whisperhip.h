@@ -922,6 +922,55 @@ int wh_session_rule_set_stats(const wh_session* s, int64_t* passes, int64_t* lau
 int wh_debug_rule_sets_apply(wh_session* s, float* rows_inout, int n_rows, const int32_t* tokens, const int32_t* n_tokens,
                              const int32_t* prompt_lens, const int32_t* live, const int32_t* set_of_row);
 
+/* ---- token alternatives (opt-in; NO REFERENCE BEHAVIOUR: torch.topk(log_softmax(row / T), n) and the entropy of that distribution) ----
+ * n = 0 (the default) is off, n = 1 .. WH_MAX_ALTERNATIVES is on; anything else is WH_ERR_INVALID_ARGUMENT.  While the mode is on, every
+ * position a decode pass samples AND appends (index >= the prompt length in the slot's token list; prompt, prefill and prefix positions
+ * and the end token record nothing) records
+ *   - the n best entries of the distribution the token was drawn from: the fp32 log-softmax of the row after the no-speech read, the rule
+ *     kernels and the session's own filters, rounded under float16_logits where the sampler rounds it, scaled by 1 / T at T != 0 exactly as
+ *     token_logprobs is; (id, logprob) pairs in descending order, ties to the lower id, (-1, -inf) beyond the finite entries;
+ *   - the entropy of that distribution in nats over its finite entries, H = lse - sum(e^(x - m) x) / sum(e^(x - m)), summed in an order
+ *     that depends on the element index only (a row gives the same bits in every slot).
+ * It is the sampler's own distribution and lse: at T = 0 pair 0 of a recorded position is the sampled token with token_logprobs' bytes; at
+ * T > 0 with top_k <= n the sampled token is among the pairs with its bytes.
+ * A pass under the mode runs the unfused sampler, which records inside its own launch from the registers that hold the row; the buffers are
+ * indexed by home slot, so compacted, narrowed and mixed passes need nothing else, and one copy per pass brings the decoded slots' rows down.
+ * It runs in wh_decode_text / wh_decode_text_languages / wh_decode_text_mixed and every temperature rung of wh_transcribe* (a window ends
+ * with the rows of the rung whose result is kept), under no-speech detection (a stopped window has no recorded position), logit rules,
+ * phrase rules and rule sets.  wh_detect_language, wh_no_speech_probs, wh_score_tokens / wh_align_tokens_batch and wh_decode_text_custom do
+ * not record.  wh_decode_text_beam, wh_decode_text_guided and wh_decode_text_speculative return WH_ERR_INVALID_ARGUMENT while the mode is
+ * on, as does a wh_transcribe* audio with beam_size > 1 (its own status); wh_transcribe* ignores an attached draft.
+ * With the mode off the library launches the kernels and graphs it launched before.
+ * Out of scope: word-level alternatives; alternatives in the beam, guided, speculative, forced and custom passes; keeping the fused sampler
+ * while recording; n > 8; alternatives in JSON. */
+#define WH_MAX_ALTERNATIVES 8
+int wh_session_set_token_alternatives(wh_session* s, int n);
+int wh_session_token_alternatives(const wh_session* s);   /* the value; -1 for a NULL session */
+/* After a wh_decode_text* call: the rows of home slot `slot` from the last pass that decoded it, aligned index for index with that
+ * slot's wh_decoding_result.tokens - ids_out / logprobs_out [*n_tokens][*n_alt] (capacity WH_MAX_RESULT_TOKENS * WH_MAX_ALTERNATIVES),
+ * entropy_out [*n_tokens].  Positions that recorded nothing are (-1, -inf) / 0.  *n_alt == 0: the slot has no rows.  Any pointer may be NULL. */
+int wh_decode_alternatives(const wh_session* s, int slot, int32_t* ids_out, float* logprobs_out, float* entropy_out, int* n_alt,
+                           int* n_tokens);
+/* Flat arrays aligned with wh_transcription_tokens - ids / logprobs [*n_tokens][*n_alt], entropy [*n_tokens] - so segment i owns
+ * [token_offset, token_offset + n_tokens) of them as well.  *n_alt == 0: the transcription carries none (wh_transcription_from_json and
+ * wh_transcription_create yield such; wh_merge_transcriptions carries them only if every input does with one n_alt).  The arrays belong
+ * to the transcription.  JSON, SRT and VTT output do not contain them. */
+int wh_transcription_alternatives(const wh_transcription* t, const int32_t** ids, const float** logprobs, const float** entropy,
+                                  int* n_alt, int* n_tokens);
+/* For callers of the piecewise builder: attaches the rows of the window added last (wh_transcription_add_window*), indexed like that
+ * window's result tokens (what wh_decode_alternatives returns); the library slices them by the segments it cut.  wh_transcribe* uses the
+ * same path.  The first call fixes the transcription's n_alt; tokens of windows without a call read (-1, -inf) / 0. */
+int wh_transcription_set_window_alternatives(wh_transcription* t, int n_alt, const int32_t* ids, const float* logprobs,
+                                             const float* entropy, int n_tokens);
+/* Counters since the session's creation: decode passes under the mode, positions recorded in the results they returned, bytes copied
+ * from the device for them.  Any pointer may be NULL. */
+int wh_session_token_alternatives_stats(const wh_session* s, int64_t* passes, int64_t* positions_recorded, int64_t* d2h_bytes);
+/* Development aid: the recording path alone over caller-supplied rows ([n_rows][n_vocab], n_rows <= max_batch) with the filters off; row
+ * i is scaled by 1 / temperatures[i] where that is not 0 (NULL: all 0; taken as given).  ids_out / logprobs_out [n_rows][n],
+ * entropy_out [n_rows].  It overwrites the rows of home slots 0 .. n_rows - 1. */
+int wh_debug_token_alternatives_apply(wh_session* s, const float* rows, int n_rows, const float* temperatures, int n, int32_t* ids_out,
+                                      float* logprobs_out, float* entropy_out);
+
 void wh_transcription_free(wh_transcription* t);
 int wh_transcription_n_segments(const wh_transcription* t);
 int wh_transcription_segment(const wh_transcription* t, int i, wh_segment* out);

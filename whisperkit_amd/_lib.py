@@ -252,6 +252,14 @@ SYMBOLS = {
     "wh_session_slot_rule_sets": (I, [VP, PI32, I]),
     "wh_session_rule_set_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "wh_debug_rule_sets_apply": (I, [VP, PF, I, PI32, PI32, PI32, PI32, PI32]),
+    # token alternatives (csrc/alternatives_plan.h, the recording instantiations of sampler_kernel)
+    "wh_session_set_token_alternatives": (I, [VP, I]),
+    "wh_session_token_alternatives": (I, [VP]),
+    "wh_session_token_alternatives_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "wh_decode_alternatives": (I, [VP, I, PI32, PF, PF, C.POINTER(I), C.POINTER(I)]),
+    "wh_transcription_alternatives": (I, [VP, C.POINTER(PI32), C.POINTER(PF), C.POINTER(PF), C.POINTER(I), C.POINTER(I)]),
+    "wh_transcription_set_window_alternatives": (I, [VP, I, PI32, PF, PF, I]),
+    "wh_debug_token_alternatives_apply": (I, [VP, PF, I, PF, I, PI32, PF, PF]),
     "wh_prefill_prompt": (I, [VP, POPT, PST, C.c_int32, PI32, I]),
     "wh_transcribe": (I, [VP, VP, I, POPT, PST, PVP]),
     "wh_transcribe_batch": (I, [VP, PVP, PI32, I, POPT, PST, PVP]),

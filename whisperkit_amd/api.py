@@ -131,6 +131,10 @@ class DecodingResult:
     needsFallback: bool
     isFirstTokenLogProbTooLow: bool
     steps: int
+    # token alternatives (Session.setTokenAlternatives; None with the mode off): alternatives[i] = the n (id, logProb) pairs recorded for tokens[i], descending,
+    # (-1, -inf) where nothing was recorded (prompt positions, the end token) or fewer than n entries were finite; entropies[i] = the entropy in nats (0 likewise)
+    alternatives: Optional[List[List[Tuple[int, float]]]] = None
+    entropies: Optional[List[float]] = None
 
     @classmethod
     def from_c(cls, r):
@@ -220,6 +224,27 @@ class TranscriptionResult:
         return [w for g in self.segments for w in g.words]
 
     allWordsFlat: List[WordTiming] = dataclasses.field(default_factory=list, repr=False, compare=False)   # every word of the C object
+
+    def tokenAlternatives(self):
+        """Token alternatives of the C object (Session.setTokenAlternatives), aligned with `tokens`: (ids int32 [nTokens][n], logProbs float32 [nTokens][n],
+        entropies float32 [nTokens]) as numpy arrays, or None when the transcription carries none (the mode was off; fromJSON / withSeekOffset copies)."""
+        ip, lp, ep, na, nt = L.PI32(), L.PF(), L.PF(), C.c_int(), C.c_int()
+        _check(L.load().wh_transcription_alternatives(self._handle, C.byref(ip), C.byref(lp), C.byref(ep), C.byref(na), C.byref(nt)))
+        if na.value == 0:
+            return None
+        n, t = na.value, nt.value
+        if t == 0:
+            return np.zeros((0, n), np.int32), np.zeros((0, n), np.float32), np.zeros((0,), np.float32)
+        return (np.ctypeslib.as_array(ip, (t, n)).copy(), np.ctypeslib.as_array(lp, (t, n)).copy(), np.ctypeslib.as_array(ep, (t,)).copy())
+
+    def segmentAlternatives(self, i: int):
+        """The slice of tokenAlternatives() that belongs to segments[i] (its tokens are a contiguous run of the flat token array), or None."""
+        alt = self.tokenAlternatives()
+        if alt is None:
+            return None
+        g = L.WhSegment()
+        _check(L.load().wh_transcription_segment(self._handle, i, C.byref(g)))
+        return tuple(a[g.token_offset:g.token_offset + g.n_tokens] for a in alt)
 
 
 def _string(fn, *args) -> str:
@@ -764,7 +789,7 @@ class Session:
             assert len(lt) == batch
             self._guarded(self.lib.wh_decode_text_languages, self.handle, batch, C.byref(o), C.byref(st), p.ctypes.data_as(L.PI32), len(p),
                           lt.ctypes.data_as(L.PI32), temps.ctypes.data_as(L.PF), None if act is None else act.ctypes.data_as(L.PI32), seed, res)
-        return [DecodingResult.from_c(r) for r in res]
+        return self._with_alternatives([DecodingResult.from_c(r) for r in res], act)
 
     # ---- speculative greedy decode (no reference behaviour: draft-and-verify decoding; csrc/spec_plan.h, spec.hip)
     def decodeTextGuided(self, prompt: Sequence[int], options: DecodingOptions, proposals: Sequence[Optional[Sequence[int]]], K: int,
@@ -957,6 +982,62 @@ class Session:
         self._guarded(self.lib.wh_no_speech_probs, self.handle, batch, C.byref(st), out)
         return list(out)
 
+    MAX_ALTERNATIVES = 8
+
+    def setTokenAlternatives(self, n: int):
+        """NO REFERENCE BEHAVIOUR: torch.topk(log_softmax(row / T), n) and the entropy of that distribution.  n = 0 (default) off; n = 1 .. 8: every position a
+        decode pass samples and appends records the n best (id, logProb) pairs of the distribution the token was drawn from - the fp32 log-softmax of the row
+        after the rule kernels and the session's filters, scaled by 1 / T at T != 0 - and its entropy in nats, inside the sampler's own launch
+        (csrc/alternatives_plan.h).  Tokens and log-probabilities do not change; the pass runs the unfused sampler.  decodeText / decodeTextMixed
+        fill DecodingResult.alternatives / .entropies, transcribe* results answer tokenAlternatives(); decodeTextBeam / decodeTextGuided /
+        decodeTextSpeculative and beamSize > 1 in transcribe* are refused while the mode is on, and transcribe* ignores an attached draft."""
+        _check(self.lib.wh_session_set_token_alternatives(self.handle, int(n)))
+
+    def tokenAlternatives(self) -> int:
+        return int(self.lib.wh_session_token_alternatives(self.handle))
+
+    def tokenAlternativesStats(self) -> Tuple[int, int, int]:
+        """(decode passes under the mode, positions recorded in the results they returned, bytes copied from the device for them) since the session was created"""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        _check(self.lib.wh_session_token_alternatives_stats(self.handle, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
+
+    def decodeAlternatives(self, slot: int = 0):
+        """The rows of home slot `slot` from the last decodeText* pass that decoded it, aligned with that result's tokens: (ids int32 [nTokens][n], logProbs
+        float32 [nTokens][n], entropies float32 [nTokens]), or None when the slot has none."""
+        cap = L.WH_MAX_RESULT_TOKENS
+        ids = np.empty((cap * self.MAX_ALTERNATIVES,), np.int32)
+        lps = np.empty((cap * self.MAX_ALTERNATIVES,), np.float32)
+        ent = np.empty((cap,), np.float32)
+        na, nt = C.c_int(), C.c_int()
+        _check(self.lib.wh_decode_alternatives(self.handle, slot, ids.ctypes.data_as(L.PI32), lps.ctypes.data_as(L.PF), ent.ctypes.data_as(L.PF), C.byref(na), C.byref(nt)))
+        if na.value == 0:
+            return None
+        n, t = na.value, nt.value
+        return ids[:t * n].reshape(t, n).copy(), lps[:t * n].reshape(t, n).copy(), ent[:t].copy()
+
+    def _with_alternatives(self, results, active=None):
+        if self.tokenAlternatives() > 0:
+            for b, r in enumerate(results):
+                if active is not None and not active[b]:
+                    continue
+                alt = self.decodeAlternatives(b)
+                if alt is not None and len(alt[2]) == len(r.tokens):
+                    r.alternatives = [[(int(i), float(l)) for i, l in zip(ri, rl)] for ri, rl in zip(alt[0], alt[1])]
+                    r.entropies = [float(e) for e in alt[2]]
+        return results
+
+    def debugTokenAlternativesApply(self, rows, n: int, temperatures=None):
+        """Development aid (wh_debug_token_alternatives_apply): the recording path alone over rows [nRows][nVocab] with the filters off -> (ids [nRows][n],
+        logProbs [nRows][n], entropies [nRows])."""
+        x = np.ascontiguousarray(rows, dtype=np.float32)
+        assert x.ndim == 2 and x.shape[1] == self.model.dims.n_vocab
+        t = None if temperatures is None else np.ascontiguousarray(temperatures, dtype=np.float32)
+        ids = np.empty((x.shape[0], n), np.int32); lps = np.empty((x.shape[0], n), np.float32); ent = np.empty((x.shape[0],), np.float32)
+        _check(self.lib.wh_debug_token_alternatives_apply(self.handle, x.ctypes.data_as(L.PF), x.shape[0], None if t is None else t.ctypes.data_as(L.PF), int(n),
+                                                          ids.ctypes.data_as(L.PI32), lps.ctypes.data_as(L.PF), ent.ctypes.data_as(L.PF)))
+        return ids, lps, ent
+
     def setLogitRules(self, repetitionPenalty: float = 1.0, noRepeatNgramSize: int = 0, tokenBias=None):
         """NO REFERENCE BEHAVIOUR: the semantics are transformers' SequenceBiasLogitsProcessor (single-token sequences), RepetitionPenaltyLogitsProcessor and
         NoRepeatNGramLogitsProcessor, applied in the order `generate` applies them.  An opt-in rule set of the session, applied on the device to the raw
@@ -1135,7 +1216,7 @@ class Session:
         res = (L.WhDecodingResult * max(batch, 1))()
         self._guarded(self.lib.wh_decode_text_mixed, self.handle, batch, opts, n, cls.ctypes.data, C.byref(st), pp, npr.ctypes.data,
                       None if lt is None else lt.ctypes.data, temps.ctypes.data, None if act is None else act.ctypes.data, seed, res)
-        return [DecodingResult.from_c(r) for r in res[:batch]]
+        return self._with_alternatives([DecodingResult.from_c(r) for r in res[:batch]], act)
 
     BEAM_RANKINGS = {"host": 0, "device": 1}
 
@@ -1870,11 +1951,26 @@ class WindowAssembler:
             _check(self.lib.wh_transcription_add_window_path(self.handle, self.tokenizer.handle if self.tokenizer else None, C.byref(o), C.byref(self.st),
                                                              C.byref(r), ti.ctypes.data_as(L.PI32), tj.ctypes.data_as(L.PI32), len(alignmentPath[0]),
                                                              defaultLanguageToken, segmentSize, C.byref(sk)))
+            self._attach_alternatives(result)
             return sk.value
         _check(self.lib.wh_transcription_add_window(self.handle, self.tokenizer.handle if self.tokenizer else None, C.byref(o), C.byref(self.st),
                                                     C.byref(r), None if a is None else a.ctypes.data_as(L.PF), defaultLanguageToken, segmentSize,
                                                     C.byref(sk)))
+        self._attach_alternatives(result)
         return sk.value
+
+    def _attach_alternatives(self, result: DecodingResult):
+        if result.alternatives is not None and result.entropies is not None:
+            self.setWindowAlternatives([[i for i, _ in row] for row in result.alternatives], [[l for _, l in row] for row in result.alternatives], result.entropies)
+
+    def setWindowAlternatives(self, ids, logProbs, entropies):
+        """wh_transcription_set_window_alternatives: the token alternatives of the window added last, indexed like that window's result tokens (ids / logProbs
+        [nTokens][n], entropies [nTokens]); the library slices them by the segments it cut.  addWindow does this for a DecodingResult that carries them."""
+        i = np.ascontiguousarray(ids, dtype=np.int32)
+        l = np.ascontiguousarray(logProbs, dtype=np.float32)
+        e = np.ascontiguousarray(entropies, dtype=np.float32)
+        assert i.ndim == 2 and i.shape == l.shape and e.shape == (i.shape[0],)
+        _check(self.lib.wh_transcription_set_window_alternatives(self.handle, i.shape[1], i.ctypes.data_as(L.PI32), l.ctypes.data_as(L.PF), e.ctypes.data_as(L.PF), i.shape[0]))
 
     def result(self) -> TranscriptionResult:
         o = self.options.to_c()

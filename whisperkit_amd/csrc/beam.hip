@@ -342,6 +342,7 @@ static int wh_decode_text_beam_impl(wh_session* s, int n_audio, int beam_size, f
                          n_audio * beam_size, s->B);
     if (n_prompt < 1 || n_prompt >= kMaxTok) return set_error(WH_ERR_PREFILL_FAILED, "wh_decode_text_beam: prompt length %d out of range [1,%d)", n_prompt, kMaxTok);
     if (opt->word_timestamps) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text_beam: word timestamps are not recorded along beams (decode the chosen tokens again with wh_decode_text and prefixTokens to align them)");
+    if (s->token_alternatives > 0) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text_beam: the session records token alternatives (wh_session_set_token_alternatives), which the beam pass does not do");
     if (s->logit_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text_beam: the session has logit rules set (wh_session_set_logit_rules), which the beam pass does not run");
     if (s->phrase_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text_beam: the session has phrase rules set (wh_session_set_phrase_rules), which the beam pass does not run");
     if (whi::rule_sets_assigned(s, n_audio * beam_size)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text_beam: a slot of the call is assigned a rule set (wh_session_set_slot_rule_sets), which the beam pass does not run");

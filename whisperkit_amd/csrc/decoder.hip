@@ -30,6 +30,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "alternatives_plan.h"
 #include "dec_shared.h"
 #include "knobs.h"
 
@@ -448,6 +449,10 @@ __device__ __forceinline__ float uniform01(unsigned long long seed, int counter)
 // DO_ADVANCE == 2 (a mixed pass, option_mix.h): advance, with cfgp and suppress the session's per-class tables - the slot reads the entries of its class
 // (seq_class of SeqState.rng_lane) and draws from the lane in the word's low bits.  A value of an existing parameter, so that every other instantiation
 // keeps its name and its instructions (tools/device_code_hash.py): only mixed passes launch <1, 1, 2, 0>.
+// DO_SAMPLE == 2 (token alternatives, alternatives_plan.h): sample, and - when the step appends its token - record the n best entries of the
+// log-softmax the token was drawn from and the entropy of that distribution, from the registers that hold the filtered, scaled row.  token_out / logprob_out are
+// the buffers by home slot (ids; log-probabilities with the entropies behind them), counter_override carries n and the buffers' slot count.  Again a value of an
+// existing parameter: <1, 2, 1, 0> (a plain pass), <1, 2, 2, 0> (a mixed pass) and <0, 2, 0, 0> (the kernel-alone entry point) are the only ones launched.
 template <int DO_FILTER, int DO_SAMPLE, int DO_ADVANCE, int WRITE_BACK, int TOPK = 0>
 __global__ __launch_bounds__(SAMP_T) void sampler_kernel(const SamplerCfg* __restrict__ cfgp, const int* __restrict__ suppress,
                                                         SeqState* __restrict__ seqs, float* __restrict__ logits_all,
@@ -625,8 +630,46 @@ __global__ __launch_bounds__(SAMP_T) void sampler_kernel(const SamplerCfg* __res
         tok = ti[chosen];
         lp = tv[chosen] - lse;
     }
+    if constexpr (DO_SAMPLE == 2) {
+        const int n_alt = min(plan::alternatives_arg_n(counter_override), plan::kMaxAlternatives), slots = plan::alternatives_arg_slots(counter_override);
+        const int home = kMix ? seq_lane(sq->rng_lane) : sq->rng_lane;
+        const int ti_cur = sq->token_index;
+        bool rec = gmax != -INFINITY;                        // (a row without a finite entry keeps what the host's reset wrote)
+        if (DO_ADVANCE) rec = rec && plan::alternatives_step_records(ti_cur, sq->prompt_len, n_tok, kMaxTok, tok, cfg.end_token, ti_cur == cfg.prefilled_index,
+                                                                    cfg.has_first_token_threshold != 0, cfg.first_token_log_prob_threshold, lp);
+        const long long po = plan::alternatives_pair_offset(home, n_tok, 0, slots), eo = plan::alternatives_entropy_offset(home, n_tok, slots);
+        rec = rec && po >= 0 && eo >= 0;
+        __syncthreads();                                     // every thread has read the state thread 0 advances below: `rec` is workgroup-uniform
+        if (rec) {
+            // entropy over the finite entries, H = lse - sum(e^(x - m) x) / sum(e^(x - m)): one more strided sum in element order, then the block sum
+            float sx = 0.0f;
+#pragma unroll
+            for (int e = 0; e < SAMP_E; ++e) {
+                const int n = tid + SAMP_T * e;
+                if (n < V && x[e] != -INFINITY) sx += expf(x[e] - gmax) * x[e];
+            }
+            sx = block_sum(sx, &br);
+            if (tid == 0) (logprob_out + plan::alternatives_lp_floats(slots))[eo] = lse - sx / se;
+            // the n best, descending, ties to the lower id: the TOPK branch's repeated argmax, on the scaled row and with the sampler's own lse
+            // (nothing reads the row after this: a reported entry is struck out in its register)
+            float bv = gmax; int bi = gidx;
+            for (int k = 0; k < n_alt; ++k) {
+                const bool fin = bv != -INFINITY;
+                if (tid == 0) { token_out[po + k] = fin ? bi : plan::kAltNoId; logprob_out[po + k] = fin ? bv - lse : -INFINITY; }
+                if (k + 1 == n_alt) break;
+                float m2 = -INFINITY; int i2 = 0x7fffffff;
+#pragma unroll
+                for (int e = 0; e < SAMP_E; ++e) {
+                    const int n = tid + SAMP_T * e;
+                    if (n == bi) x[e] = -INFINITY;
+                    if (n < V && (x[e] > m2 || (x[e] == m2 && n < i2))) { m2 = x[e]; i2 = n; }
+                }
+                block_argmax(m2, i2, &br, &bv, &bi);
+            }
+        }
+    }
     if (tid == 0) {
-        if (token_out) { token_out[b] = tok; logprob_out[b] = lp; }
+        if (DO_SAMPLE != 2 && token_out) { token_out[b] = tok; logprob_out[b] = lp; }
         if (DO_ADVANCE) advance_decode_state(cfg, sq, tok, lp, n_tok);
     }
 }
@@ -820,6 +863,11 @@ void launch_decoder_step(const DecodeBuffers& db, const SamplerCfg* cfg_dev, con
         else sampler_final_kernel<<<B, 256, 0, st>>>(cfg_dev, db.seq, db.stats, (V + 31) / 32);
     } else if (sample) {
         ProfScope ps_(KK_SAMPLER, st);
+        if (db.alt_n > 0) {      // token alternatives: the recording instantiations, the buffers by home slot
+            const int arg = plan::alternatives_pack_arg(db.alt_n, db.max_batch);
+            if (mixed) sampler_kernel<1, 2, 2, 0><<<B, SAMP_T, 0, st>>>(cfg_dev, suppress_dev, db.seq, db.logits, arg, db.alt_ids, db.alt_lp);
+            else sampler_kernel<1, 2, 1, 0><<<B, SAMP_T, 0, st>>>(cfg_dev, suppress_dev, db.seq, db.logits, arg, db.alt_ids, db.alt_lp);
+        } else
         if (mixed) sampler_kernel<1, 1, 2, 0><<<B, SAMP_T, 0, st>>>(cfg_dev, suppress_dev, db.seq, db.logits, 0, nullptr, nullptr);
         else sampler_kernel<1, 1, 1, 0><<<B, SAMP_T, 0, st>>>(cfg_dev, suppress_dev, db.seq, db.logits, 0, nullptr, nullptr);
     }
@@ -827,6 +875,10 @@ void launch_decoder_step(const DecodeBuffers& db, const SamplerCfg* cfg_dev, con
 
 void launch_filter_only(const SamplerCfg* cfg_dev, const int* suppress_dev, SeqState* seq, float* logits, int n_vocab, hipStream_t st) {
     sampler_kernel<1, 0, 0, 1><<<1, SAMP_T, 0, st>>>(cfg_dev, suppress_dev, seq, logits, 0, nullptr, nullptr);
+}
+// token alternatives, the kernel alone: the recording path over `batch` caller-given rows with the filters off (row b: temperature, list length and home slot from seq[b])
+void launch_alternatives_only(const SamplerCfg* cfg_dev, SeqState* seq, float* logits, int batch, int n, int max_batch, int* alt_ids, float* alt_lp, hipStream_t st) {
+    sampler_kernel<0, 2, 0, 0><<<batch, SAMP_T, 0, st>>>(cfg_dev, nullptr, seq, logits, plan::alternatives_pack_arg(n, max_batch), alt_ids, alt_lp);
 }
 void launch_sample_only(const SamplerCfg* cfg_dev, SeqState* seq, float* logits, int n_vocab, int counter, int* token_out, float* logprob_out, hipStream_t st) {
     sampler_kernel<0, 1, 0, 0><<<1, SAMP_T, 0, st>>>(cfg_dev, nullptr, seq, logits, counter, token_out, logprob_out);

@@ -270,7 +270,7 @@ static int get_step_graph(wh_session* s, int batch, int first_step, hipGraphExec
     // (a compacted pass bakes the slot table's address, the mapped kernel instantiations and its own slots per workgroup into its launches)
     const WhGraphKey key{batch, s->align_enabled ? 1 : 0, s->fused_greedy ? 1 : 0, s->align_enabled ? s->n_align_alloc : 0, db.self_rows, db.xattn_gate ? 1 : 0,
                          db.slot_home ? 1 : 0, db.slot_home ? s->pass_spw : 0, db.self_owner ? 1 : 0, db.mixed,
-                         (int)plan::nospeech_step_mask(first_step, kStepsPerGraph, s->pass_ns), s->pass_lr ? 1 : 0, s->pass_pr ? 1 : 0, s->pass_rs ? s->pass_rs_key : 0};
+                         (int)plan::nospeech_step_mask(first_step, kStepsPerGraph, s->pass_ns), s->pass_lr ? 1 : 0, s->pass_pr ? 1 : 0, s->pass_rs ? s->pass_rs_key : 0, s->pass_alt};
     auto it = s->graphs.find(key);
     if (it != s->graphs.end()) { s->graph_use[key] = ++s->graph_tick; *out = it->second; return WH_OK; }
     // The cache is capped (a large-v3 step graph holds ~2.5 k kernel nodes; a configuration = everything of the key but the row bound has up
@@ -279,7 +279,7 @@ static int get_step_graph(wh_session* s, int batch, int first_step, hipGraphExec
     const size_t cap = (size_t)knob::once<knob::WH_GRAPH_CAP>();
     while (s->graphs.size() >= cap) {
         auto same_cfg = [](const WhGraphKey& a, const WhGraphKey& b) {
-            return a.batch == b.batch && a.align == b.align && a.fused == b.fused && a.n_align == b.n_align && a.gate == b.gate && a.mapped == b.mapped && a.spw == b.spw && a.owner == b.owner && a.mixed == b.mixed && a.ns_mask == b.ns_mask && a.logit_rules == b.logit_rules && a.phrase_rules == b.phrase_rules && a.rule_sets == b.rule_sets;
+            return a.batch == b.batch && a.align == b.align && a.fused == b.fused && a.n_align == b.n_align && a.gate == b.gate && a.mapped == b.mapped && a.spw == b.spw && a.owner == b.owner && a.mixed == b.mixed && a.ns_mask == b.ns_mask && a.logit_rules == b.logit_rules && a.phrase_rules == b.phrase_rules && a.rule_sets == b.rule_sets && a.alternatives == b.alternatives;
         };
         const WhGraphKey* victim = nullptr;
         unsigned long long victim_last = ~0ull;
@@ -394,6 +394,45 @@ int nospeech_collect(wh_session* s, int n, const wh_decoding_options* const* opt
         if (opts && opts[b] && !isnan(opts[b]->no_speech_threshold) && p > opts[b]->no_speech_threshold) s->ns_windows_over += 1;
         if (s->ns_host[3 * B + b]) s->ns_windows_stopped += 1;
     }
+    return WH_OK;
+}
+}  // namespace whi
+
+// ---- token alternatives (wh_session_set_token_alternatives; NO REFERENCE BEHAVIOUR: torch.topk(log_softmax(row / T)) and the entropy of that distribution)
+namespace whi {
+// The caller's stream holds no launch that writes the buffers (every pass ends drained).  Runs of live home slots: one memset triple for a full pass
+int alternatives_arm(wh_session* s, int n, const int32_t* active) {
+    if (!s->alt_ids || !s->alt_f32) return set_error(WH_ERR_INVALID_ARGUMENT, "token alternatives: the buffers are not allocated (wh_session_set_token_alternatives)");
+    const size_t row = (size_t)plan::kAltPositions * plan::kMaxAlternatives;
+    const float ninf = -INFINITY;
+    int32_t ninf_bits;
+    memcpy(&ninf_bits, &ninf, sizeof(ninf_bits));
+    std::vector<int32_t> begin((size_t)n), count((size_t)n);
+    const int runs = plan::alternatives_live_runs(active, n, begin.data(), count.data());
+    float* const ent = s->alt_f32 + plan::alternatives_lp_floats(s->B);
+    for (int k = 0; k < runs; ++k) {
+        const size_t b0 = (size_t)begin[(size_t)k], nb = (size_t)count[(size_t)k];
+        WH_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s->alt_ids + b0 * row), plan::kAltNoId, nb * row, s->st));
+        WH_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s->alt_f32 + b0 * row), ninf_bits, nb * row, s->st));
+        WH_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ent + b0 * plan::kAltPositions), 0, nb * plan::kAltPositions, s->st));
+    }
+    s->pass_alt = s->token_alternatives;
+    s->alt_passes += 1;
+    return WH_OK;
+}
+int alternatives_collect(wh_session* s, int n, const int32_t* active) {
+    const size_t row = (size_t)plan::kAltPositions * plan::kMaxAlternatives;
+    std::vector<int32_t> begin((size_t)n), count((size_t)n);
+    const int runs = plan::alternatives_live_runs(active, n, begin.data(), count.data());
+    const size_t ent_off = plan::alternatives_lp_floats(s->B);
+    for (int k = 0; k < runs; ++k) {
+        const size_t b0 = (size_t)begin[(size_t)k], nb = (size_t)count[(size_t)k];
+        WH_HIP(hipMemcpyAsync(s->alt_ids_host + b0 * row, s->alt_ids + b0 * row, sizeof(int32_t) * nb * row, hipMemcpyDeviceToHost, s->st));
+        WH_HIP(hipMemcpyAsync(s->alt_f32_host + b0 * row, s->alt_f32 + b0 * row, sizeof(float) * nb * row, hipMemcpyDeviceToHost, s->st));
+        WH_HIP(hipMemcpyAsync(s->alt_f32_host + ent_off + b0 * plan::kAltPositions, s->alt_f32 + ent_off + b0 * plan::kAltPositions, sizeof(float) * nb * plan::kAltPositions, hipMemcpyDeviceToHost, s->st));
+        s->alt_d2h_bytes += (long long)(nb * (2 * row + plan::kAltPositions) * 4);
+    }
+    WH_HIP(hipStreamSynchronize(s->st));
     return WH_OK;
 }
 }  // namespace whi
@@ -630,7 +669,7 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
     for (int b = 0; b < batch; ++b) n_live += (active ? active[b] != 0 : 1);
     plan::CompactPassPlan cp{false, batch, s->use_xabs ? s->xabs.spw : 1};
     if (s->fallback_compaction == 1 && active) cp = plan::compact_pass_plan(n_live, batch, s->B, s->use_xabs ? s->xabs.spw : 1);
-    struct PassScope { wh_session* s; ~PassScope() { s->pass_mapped = false; s->pass_owner = false; s->pass_mixed = false; s->pass_ns = plan::NoSpeechRange{-1, -1}; s->pass_lr = false; s->pass_pr = false; s->pass_rs = false; } } pass_scope{s};      // (every exit: the next caller of decode_buffers sees a plain pass)
+    struct PassScope { wh_session* s; ~PassScope() { s->pass_mapped = false; s->pass_owner = false; s->pass_mixed = false; s->pass_ns = plan::NoSpeechRange{-1, -1}; s->pass_lr = false; s->pass_pr = false; s->pass_rs = false; s->pass_alt = 0; } } pass_scope{s};      // (every exit: the next caller of decode_buffers sees a plain pass)
     const int width = cp.compact ? cp.width : batch;
     if (cp.compact) {
         if (!s->slot_home_dev) WH_HIP(s->mem.alloc(&s->slot_home_dev, (size_t)s->B, false));
@@ -705,6 +744,13 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
         s->pass_rs_key = 1 | (s->logit_rules_on ? 2 : 0) | (s->phrase_rules_on ? 4 : 0);
         s->pass_rs = true; s->rs_passes += 1;
     }
+    // ---- token alternatives (wh_session_set_token_alternatives; NO REFERENCE BEHAVIOUR): the unfused sampler's recording instantiation.  The rows of
+    // the home slots this pass decodes start from "nothing recorded"; a fallback rung so overwrites only the windows it decodes again
+    if (s->token_alternatives > 0) {
+        s->fused_greedy = false;
+        r = whi::alternatives_arm(s, batch, active);
+        if (r) return r;
+    }
     WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * width, hipMemcpyHostToDevice, s->st));
     launch_rules_init(s->cfg_dev, s->seq, width, s->st, mix != nullptr);
     int loop_count = 0;       // a slot finishes at its class's count (SamplerCfg.loop_count); the host loop runs to the largest
@@ -761,10 +807,19 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
     }
     const bool ns_on = !ns_opts.empty();
     if (ns_on) { r = whi::nospeech_collect(s, batch, ns_opts.data()); if (r) return r; }
+    const bool alt_on = s->pass_alt > 0;
+    if (alt_on) { r = whi::alternatives_collect(s, batch, active); if (r) return r; }
     for (int b = 0; b < batch; ++b) {
         if (!s->seq_host[b].active) { memset(&out[b], 0, sizeof(out[b])); continue; }
         const wh_decoding_options* fo = (mix && mix->slot_opts && mix->slot_opts[b]) ? mix->slot_opts[b] : cls_opt(cls_of(b));      // the audio's own thresholds
         whi::finalize_decoding_result(s->seq_host[b], fo, st, s->seq_host[b].temperature, &out[b], ns_on ? whi::nospeech_prob(s, b) : 0.0f);
+        if (alt_on) {      // result token i is the list's token start + i (finalize_decoding_result's slice): where wh_decode_alternatives finds its row
+            const SeqState& q = s->seq_host[b];
+            int start = 0;
+            for (int i = 0; i < q.n_tokens; ++i) if (q.tokens[i] == st->start_of_transcript_token) { start = i; break; }
+            s->alt_start[(size_t)b] = start; s->alt_count[(size_t)b] = out[b].n_tokens; s->alt_nrec[(size_t)b] = s->pass_alt;
+            for (int i = q.prompt_len; i < q.n_tokens; ++i) s->alt_positions += s->alt_ids_host[((size_t)b * plan::kAltPositions + i) * plan::kMaxAlternatives] != plan::kAltNoId;
+        }
     }
     return WH_OK;
 }
@@ -951,6 +1006,101 @@ extern "C" int wh_no_speech_probs(wh_session* s, int batch, const wh_special_tok
     r = whi::nospeech_collect(s, batch, nullptr);
     if (r) return r;
     for (int b = 0; b < batch; ++b) probs_out[b] = whi::nospeech_prob(s, b);
+    return WH_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ token alternatives
+// NO REFERENCE BEHAVIOUR: torch.topk(log_softmax(row / T), n) and the entropy of that distribution, on the row the sampler draws from (DESIGN 3.5.15;
+// alternatives_plan.h, the DO_SAMPLE == 2 instantiations of sampler_kernel).
+// The first call that turns the mode on allocates the buffers; they keep their addresses for the session's life, so graphs captured under the mode stay valid
+extern "C" int wh_session_set_token_alternatives(wh_session* s, int n) {
+    if (!s || !s->m) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_token_alternatives: null session");
+    if (!plan::alternatives_n_valid(n)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_token_alternatives: n %d (0 = off, 1 .. %d)", n, plan::kMaxAlternatives);
+    if (n > 0 && !s->alt_ids) {
+        if (hipSetDevice(s->m->device) != hipSuccess) return set_error(WH_ERR_HIP, "wh_session_set_token_alternatives: hipSetDevice(%d) failed", s->m->device);
+        WH_TRY
+        s->alt_start.assign((size_t)s->B, 0); s->alt_count.assign((size_t)s->B, 0); s->alt_nrec.assign((size_t)s->B, 0);
+        WH_CATCH("wh_session_set_token_alternatives")
+        if (!s->alt_f32) WH_HIP(s->mem.alloc(&s->alt_f32, plan::alternatives_f32_floats(s->B), false));
+        if (!s->alt_ids_host) WH_HIP(s->mem.alloc_pinned(&s->alt_ids_host, plan::alternatives_id_words(s->B)));
+        if (!s->alt_f32_host) WH_HIP(s->mem.alloc_pinned(&s->alt_f32_host, plan::alternatives_f32_floats(s->B)));
+        WH_HIP(s->mem.alloc(&s->alt_ids, plan::alternatives_id_words(s->B), false));      // (last: alt_ids set = everything is there; every pass resets the rows it decodes)
+    }
+    s->token_alternatives = n;
+    return WH_OK;
+}
+extern "C" int wh_session_token_alternatives(const wh_session* s) { return s ? s->token_alternatives : -1; }
+extern "C" int wh_session_token_alternatives_stats(const wh_session* s, int64_t* passes, int64_t* positions_recorded, int64_t* d2h_bytes) {
+    if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_token_alternatives_stats: null session");
+    if (passes) *passes = s->alt_passes;
+    if (positions_recorded) *positions_recorded = s->alt_positions;
+    if (d2h_bytes) *d2h_bytes = s->alt_d2h_bytes;
+    return WH_OK;
+}
+// The rows of home slot `slot` as the last pass that decoded it left them, aligned with that pass's wh_decoding_result.tokens: n_tokens rows of n_alt pairs
+extern "C" int wh_decode_alternatives(const wh_session* s, int slot, int32_t* ids_out, float* logprobs_out, float* entropy_out, int* n_alt_out, int* n_tokens_out) {
+    if (!s || !s->m) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_alternatives: null session");
+    if (slot < 0 || slot >= s->B) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_alternatives: slot %d out of range [0,%d)", slot, s->B);
+    const int n = s->alt_ids ? s->alt_nrec[(size_t)slot] : 0, count = n > 0 ? s->alt_count[(size_t)slot] : 0;
+    if (n_alt_out) *n_alt_out = n;
+    if (n_tokens_out) *n_tokens_out = count;
+    const size_t ent_off = plan::alternatives_lp_floats(s->B);
+    for (int i = 0; i < count; ++i) {
+        const int row = plan::alternatives_result_row(s->alt_start[(size_t)slot], i);
+        for (int k = 0; k < n; ++k) {
+            const long long o = row >= 0 ? plan::alternatives_pair_offset(slot, row, k, s->B) : -1;
+            if (ids_out) ids_out[(size_t)i * n + k] = o >= 0 ? s->alt_ids_host[o] : plan::kAltNoId;
+            if (logprobs_out) logprobs_out[(size_t)i * n + k] = o >= 0 ? s->alt_f32_host[o] : -INFINITY;
+        }
+        if (entropy_out) entropy_out[i] = row >= 0 ? s->alt_f32_host[ent_off + (size_t)plan::alternatives_entropy_offset(slot, row, s->B)] : 0.0f;
+    }
+    return WH_OK;
+}
+// Development aid: the recording instantiation alone, filters off - n_rows (<= max_batch) rows of the model's vocabulary go into the session's logits buffer, row i
+// is sampled under temperatures[i] (null: 0; taken as given, not rounded to Float16) as home slot i with an empty token list, so it records at position 0; the
+// n pairs and the entropy of every row come back.  It overwrites the rows of home slots 0 .. n_rows - 1 of the session's buffers (allocating them if need be).
+extern "C" int wh_debug_token_alternatives_apply(wh_session* s, const float* rows, int n_rows, const float* temperatures, int n, int32_t* ids_out, float* logprobs_out,
+                                                 float* entropy_out) {
+    CHECK_SESSION(s); CHECK_BATCH(s, n_rows);
+    if (!rows || !ids_out || !logprobs_out || !entropy_out) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_token_alternatives_apply: null argument");
+    if (n < 1 || !plan::alternatives_n_valid(n)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_token_alternatives_apply: n %d (1 .. %d)", n, plan::kMaxAlternatives);
+    const int keep = s->token_alternatives;
+    int r = wh_session_set_token_alternatives(s, n);      // (allocates on first use)
+    s->token_alternatives = keep;
+    if (r) return r;
+    const int V = s->m->dims.n_vocab;
+    wh_decoding_options o;
+    wh_decoding_options_default(&o);
+    o.top_k = 1; o.without_timestamps = 1;
+    wh_special_tokens st{};
+    r = whi::upload_sampler_cfg(s, &o, &st, 0, 0, 0, 0);      // (drains the stream: nothing in flight reads the staging the host writes next)
+    if (r) return r;
+    for (int i = 0; i < n_rows; ++i) {
+        SeqState& q = s->seq_host[i];
+        memset(&q, 0, sizeof(q));
+        q.active = 1; q.rng_lane = i; q.temperature = temperatures ? temperatures[i] : 0.0f;
+    }
+    struct Scope { wh_session* s; ~Scope() { s->pass_alt = 0; } } scope{s};
+    r = whi::alternatives_arm(s, n_rows, nullptr);
+    if (r) return r;
+    s->alt_passes -= 1;                                   // (not a decode pass)
+    WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * n_rows, hipMemcpyHostToDevice, s->st));
+    WH_HIP(hipMemcpyAsync(s->logits, rows, sizeof(float) * (size_t)n_rows * V, hipMemcpyHostToDevice, s->st));
+    launch_alternatives_only(s->cfg_dev, s->seq, s->logits, n_rows, n, s->B, s->alt_ids, s->alt_f32, s->st);
+    WH_CHECK_LAUNCH();
+    const long long bytes_before = s->alt_d2h_bytes;
+    r = whi::alternatives_collect(s, n_rows, nullptr);
+    s->alt_d2h_bytes = bytes_before;
+    if (r) return r;
+    const size_t ent_off = plan::alternatives_lp_floats(s->B);
+    for (int i = 0; i < n_rows; ++i) {
+        for (int k = 0; k < n; ++k) {
+            const long long po = plan::alternatives_pair_offset(i, 0, k, s->B);
+            ids_out[(size_t)i * n + k] = s->alt_ids_host[po]; logprobs_out[(size_t)i * n + k] = s->alt_f32_host[po];
+        }
+        entropy_out[i] = s->alt_f32_host[ent_off + (size_t)plan::alternatives_entropy_offset(i, 0, s->B)];
+        s->alt_nrec[(size_t)i] = 0;                       // (what wh_decode_alternatives knew about these slots is gone)
+    }
     return WH_OK;
 }
 
@@ -1498,6 +1648,7 @@ extern "C" int wh_decode_text_guided(wh_session* s, int n_audio, int K, const wh
     CHECK_SESSION(s);
     if (int r = spec_check_args(who, n_audio, K, opt, st, prompt, n_prompt, out, s->B)) return r;
     if (int r = spec_check_tokens(who, n_audio, prompt, n_prompt, proposals, n_proposals, s->m->dims.n_vocab)) return r;
+    if (s->token_alternatives > 0) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: the session records token alternatives (wh_session_set_token_alternatives), which the speculative pass does not do", who);
     if (s->logit_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: the session has logit rules set (wh_session_set_logit_rules), which the speculative pass does not run", who);
     if (s->phrase_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: the session has phrase rules set (wh_session_set_phrase_rules), which the speculative pass does not run", who);
     if (whi::rule_sets_assigned(s, n_audio)) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: a slot of the call is assigned a rule set (wh_session_set_slot_rule_sets), which the speculative pass does not run", who);
@@ -1527,6 +1678,7 @@ extern "C" int wh_decode_text_speculative(wh_session* s, wh_session* draft, int 
     if (int r = spec_check_args(who, n_audio, K, opt, st, prompt, n_prompt, out, s->B)) return r;
     if (int r = spec_check_tokens(who, n_audio, prompt, n_prompt, nullptr, nullptr, s->m->dims.n_vocab)) return r;
     if (int r = spec_check_draft(who, s, draft, n_audio)) return r;
+    if (s->token_alternatives > 0) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: the session records token alternatives (wh_session_set_token_alternatives), which the speculative pass does not do", who);
     if (s->logit_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: the session has logit rules set (wh_session_set_logit_rules), which the speculative pass does not run", who);
     if (s->phrase_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: the session has phrase rules set (wh_session_set_phrase_rules), which the speculative pass does not run", who);
     if (whi::rule_sets_assigned(s, n_audio)) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: a slot of the call is assigned a rule set (wh_session_set_slot_rule_sets), which the speculative pass does not run", who);
@@ -1678,6 +1830,7 @@ static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_
     // beam search (no reference behaviour, wh_decode_text_beam): the T = 0 pass expands every window into beam_size slots
     const int beam = opt->beam_size > 1 ? opt->beam_size : 1;
     if (beam > 1 && opt->word_timestamps) return set_error(WH_ERR_INVALID_ARGUMENT, "beam_size > 1 cannot be combined with word_timestamps");
+    if (beam > 1 && s->token_alternatives > 0) return set_error(WH_ERR_INVALID_ARGUMENT, "beam_size > 1 cannot be combined with token alternatives (wh_session_set_token_alternatives)");
     if (beam > 1 && s->logit_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "beam_size > 1 cannot be combined with the session's logit rules (wh_session_set_logit_rules)");
     if (beam > 1 && s->phrase_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "beam_size > 1 cannot be combined with the session's phrase rules (wh_session_set_phrase_rules)");
     bool job_sets = false;      // per-audio rule sets: does an audio of this group name a set other than 0?  (the set never splits a group: rule_sets_plan.h)
@@ -1812,7 +1965,7 @@ static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_
                 const MixClasses mix{(int)classes->size(), classes->data(), cls_slot.data(), mix_pp.data(), mix_np.data(), opt_slot.data()};
                 r = decode_text_impl(s, nb, nullptr, st, nullptr, 0, langs ? ml.data() : nullptr, tv.data(), active.data(), seed, tmp.data(), &mix);
                 if (r) return r;
-            } else if (s->draft && s->no_speech_detection == plan::kNoSpeechOff && !s->logit_rules_on && !s->phrase_rules_on && !job_sets && ti == 0 && temps[ti] == 0.0f && all_active && beam == 1 && !s->progress_cb && plan::spec_fits(nb, s->draft_k, s->B) &&
+            } else if (s->draft && s->no_speech_detection == plan::kNoSpeechOff && s->token_alternatives == 0 && !s->logit_rules_on && !s->phrase_rules_on && !job_sets && ti == 0 && temps[ti] == 0.0f && all_active && beam == 1 && !s->progress_cb && plan::spec_fits(nb, s->draft_k, s->B) &&
                        !spec_check_draft("wh_transcribe", s, s->draft, nb)) {
                 // first rung with a draft attached (wh_session_set_draft) and room for the rings: the speculative pass (results are the ordinary pass's).  The
                 // speculative pass reports no no-speech value and runs neither logit nor phrase rules nor rule sets, so a session with any of them on (or a group that carries sets) runs the ordinary pass below instead.  The
@@ -1880,6 +2033,14 @@ static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_
             }
             if (r) return r;
             j.seek = seek;
+            // token alternatives: the rows of the rung whose result is kept (its pass was the last to decode home slot b), sliced by the segments just cut
+            if (s->token_alternatives > 0 && tr->timings.total_decoding_windows > windows_before) {
+                int n_alt = 0, n_rows = 0;
+                std::vector<int32_t> aid((size_t)WH_MAX_RESULT_TOKENS * plan::kMaxAlternatives);
+                std::vector<float> alp((size_t)WH_MAX_RESULT_TOKENS * plan::kMaxAlternatives), aen((size_t)WH_MAX_RESULT_TOKENS);
+                r = wh_decode_alternatives(s, b, aid.data(), alp.data(), aen.data(), &n_alt, &n_rows); if (r) return r;
+                if (n_alt > 0 && n_rows == res[b].n_tokens) { r = wh_transcription_set_window_alternatives(tr, n_alt, aid.data(), alp.data(), aen.data(), n_rows); if (r) return r; }
+            }
             if (tr->timings.total_decoding_windows > windows_before) {      // the window had segments (`guard let currentSegments`, :239-242)
                 int n_new = (int)tr->segments.size() - seg_before;
                 if (s->hooks.window_postprocess) {                         // TranscribeTask.windowPostProcess (:246-250)

@@ -9,6 +9,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "alternatives_plan.h"
 #include "devmem.h"
 #include "kernels.h"
 #include "logit_rules_plan.h"
@@ -93,9 +94,10 @@ struct WhGraphKey {
     int phrase_rules;     // 1: every step runs phrase_rules_kernel in front of that (wh_session_set_phrase_rules); 0 with no phrase rules set
     int rule_sets;        // 0, or a set-aware pass (rule_sets_plan.h): 1 | 2 (the session's own logit rules are handed to rule_sets_kernel) | 4 (its phrase rules are) -
                           // the launch bakes those two pointers or null; logit_rules and phrase_rules are 0 then
+    int alternatives;     // 0, or the n of a pass that records token alternatives (alternatives_plan.h): the unfused sampler's recording instantiation with n baked in
     bool operator<(const WhGraphKey& o) const {
-        return std::tie(batch, align, fused, n_align, self_rows, gate, mapped, spw, owner, mixed, ns_mask, logit_rules, phrase_rules, rule_sets) <
-               std::tie(o.batch, o.align, o.fused, o.n_align, o.self_rows, o.gate, o.mapped, o.spw, o.owner, o.mixed, o.ns_mask, o.logit_rules, o.phrase_rules, o.rule_sets);
+        return std::tie(batch, align, fused, n_align, self_rows, gate, mapped, spw, owner, mixed, ns_mask, logit_rules, phrase_rules, rule_sets, alternatives) <
+               std::tie(o.batch, o.align, o.fused, o.n_align, o.self_rows, o.gate, o.mapped, o.spw, o.owner, o.mixed, o.ns_mask, o.logit_rules, o.phrase_rules, o.rule_sets, o.alternatives);
     }
 };
 
@@ -253,6 +255,17 @@ struct wh_session {
     wh::RuleSetsArgs rs_args{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
     bool pass_rs = false; int pass_rs_key = 0;
     long long rs_passes = 0, rs_launches = 0;      // wh_session_rule_set_stats (matches: the device counters)
+    // token alternatives (wh_session_set_token_alternatives: host.hip alternatives_arm / alternatives_collect, alternatives_plan.h, the recording instantiations of
+    // sampler_kernel).  token_alternatives: 0 = off, n = 1 .. 8.  Everything is allocated by the first setter call that turns the mode on: alt_ids (device, int32
+    // [B][224][8]) and alt_f32 (device, float: log-probabilities [B][224][8] | entropies [B][224]), both by home slot at fixed addresses so that captured step
+    // graphs stay valid, and their pinned mirrors.  alt_start / alt_count / alt_nrec: per home slot, the list index of result token 0, the result's token count and the n of the
+    // last pass that decoded the slot (wh_decode_alternatives).  pass_alt holds only while decode_text_impl runs a pass under the mode.
+    int token_alternatives = 0;
+    int32_t *alt_ids = nullptr, *alt_ids_host = nullptr;
+    float *alt_f32 = nullptr, *alt_f32_host = nullptr;
+    std::vector<int32_t> alt_start, alt_count, alt_nrec;
+    int pass_alt = 0;
+    long long alt_passes = 0, alt_positions = 0, alt_d2h_bytes = 0;      // wh_session_token_alternatives_stats
     hipEvent_t ev[8]{};
     bool align_enabled = false;
     wh_timings last_timings{};
@@ -320,6 +333,10 @@ int nospeech_arm(wh_session* s, int n, const int* pos, const float* stop, int to
 int nospeech_collect(wh_session* s, int n, const wh_decoding_options* const* opts);
 inline float nospeech_prob(const wh_session* s, int b) { float v; memcpy(&v, s->ns_host + 2 * (size_t)s->B + b, sizeof(v)); return v; }
 inline const wh::NoSpeechArgs* nospeech_step_args(const wh_session* s, int step) { return wh::plan::nospeech_step_in_range(step, s->pass_ns) ? &s->ns_args : nullptr; }
+// token alternatives (host.hip): reset the rows of the live home slots among 0 .. n - 1 and set pass_alt; behind the pass (the stream is drained) bring those rows
+// down into the pinned mirrors and count.  The rows of home slot b: alternatives_rows
+int alternatives_arm(wh_session* s, int n, const int32_t* active);
+int alternatives_collect(wh_session* s, int n, const int32_t* active);
 // device logit rules: the rule set a step of the running pass hands to launch_decoder_step, or null (no rules set, or a pass that does not run them)
 inline const int* logit_rules_step_args(const wh_session* s) { return s->pass_lr ? s->lr_dev : nullptr; }
 // device phrase rules: likewise

@@ -237,6 +237,9 @@ struct DecodeBuffers {
                              // rows from the caches of slots beyond its present width.  Host-side only: the kernels' arguments keep their layout
     const struct RuleSetsArgs* rule_sets;   // null, or a set-aware pass (rule_sets.hip, launch_decoder_step below): rule_sets_kernel runs in front of the unfused
                              // sampler in place of phrase_rules_kernel / logit_rules_kernel.  Host-side only
+    int* alt_ids;            // token alternatives (alternatives_plan.h, launch_decoder_step below): alt_n > 0 - the unfused sampler runs its recording instantiation
+    float* alt_lp;           // and writes ids [max_batch][224][8] / log-probabilities [max_batch][224][8] | entropies [max_batch][224] by home slot.  Host-side only
+    int alt_n;
 };
 constexpr int kStatBlocks = 1792; // >= workgroups of the logits kernel (V / 64 rows: GEMV path, V / 32 rows: MFMA path), multiple of 256
 // Largest vocabulary the sampling kernels cover: sampler_kernel holds SAMP_T x SAMP_E = 1024 x 51 ids in registers, the fused greedy
@@ -444,6 +447,9 @@ void launch_spec_accept(SeqState* master, const SeqState* seq, SpecRound* io, in
 void launch_filter_only(const SamplerCfg* cfg_dev, const int* suppress_dev, SeqState* seq, float* logits, int n_vocab, hipStream_t st);
 void launch_sample_only(const SamplerCfg* cfg_dev, SeqState* seq, float* logits, int n_vocab, int counter, int* token_out, float* logprob_out, hipStream_t st);
 // filter + sample without advancing the decode state (detectLanguage)
+// token alternatives (alternatives_plan.h): the recording instantiation of sampler_kernel alone, filters off, over `batch` rows of `logits`; row b records at
+// (home slot seq[b].rng_lane, position seq[b].n_tokens) of alt_ids / alt_lp, which are laid out for max_batch home slots
+void launch_alternatives_only(const SamplerCfg* cfg_dev, SeqState* seq, float* logits, int batch, int n, int max_batch, int* alt_ids, float* alt_lp, hipStream_t st);
 void launch_filter_sample(const SamplerCfg* cfg_dev, const int* suppress_dev, SeqState* seq, float* logits, int batch, int* token_out, float* logprob_out, hipStream_t st);
 constexpr int kBeamTopK = 16;   // row stride of the top-k outputs: beam sizes up to 15 (topk(beam_size + 1))
 // beam search: the LogitsFiltering rules, log-softmax and the K best entries of every live slot's row in one pass (row in registers)

@@ -172,6 +172,7 @@ static int add_window(const char* name, wh_transcription* tr, const wh_tokenizer
     if (res->n_tokens < 0 || res->n_tokens > WH_MAX_RESULT_TOKENS)
         return set_error(WH_ERR_INVALID_ARGUMENT, "%s: n_tokens %d outside [0, %d]", name, res->n_tokens, WH_MAX_RESULT_TOKENS);
     if (!tr->language_set) { tr->language_token = res->language_token; tr->language_set = true; }   // "Use the predicted language if it was not detected ahead of time"
+    tr->last_window.clear();      // (wh_transcription_set_window_alternatives: the slices of THIS window, none if it adds no segment)
     const int prev_seek = *seek_inout;
     wh_segment segs[WH_MAX_RESULT_TOKENS];
     int32_t new_seek = prev_seek;
@@ -213,6 +214,7 @@ static int add_window(const char* name, wh_transcription* tr, const wh_tokenizer
         wh_segment g = segs[i];
         const int src = g.token_offset;
         g.token_offset = (int)tr->tokens.size();
+        tr->last_window.push_back(wh_transcription::WindowSlice{src, g.n_tokens, g.token_offset});
         std::vector<int> text_ids;
         for (int k = 0; k < g.n_tokens; ++k) {
             const int id = res->tokens[src + k];
@@ -235,6 +237,49 @@ static int add_window(const char* name, wh_transcription* tr, const wh_tokenizer
         if (tok) tr->segment_text.push_back(tok->decode(text_ids));   // SegmentSeeker.swift:118-121,162-165
     }
     tr->timings.total_decoding_windows += 1;
+    whi::transcription_sync_alternatives(tr);      // (the new tokens: "nothing recorded" until the window's rows are attached)
+    return WH_OK;
+}
+
+// ---- token alternatives (NO REFERENCE BEHAVIOUR): the rows ride the flat token array
+namespace whi {
+void transcription_sync_alternatives(wh_transcription* t) {
+    if (!t || t->n_alt <= 0) return;
+    const size_t n = t->tokens.size();
+    t->alt_ids.resize(n * (size_t)t->n_alt, -1);
+    t->alt_lp.resize(n * (size_t)t->n_alt, -INFINITY);
+    t->alt_entropy.resize(n, 0.0f);
+}
+}  // namespace whi
+// The rows of the window added last, indexed like that window's result tokens: ids / logprobs [n_tokens][n_alt], entropy [n_tokens].  The library slices them by
+// the segments it cut from the window.  The first call fixes the transcription's n_alt; a window added without a call keeps "nothing recorded"
+extern "C" int wh_transcription_set_window_alternatives(wh_transcription* t, int n_alt, const int32_t* ids, const float* logprobs, const float* entropy, int n_tokens) {
+    if (!t || !ids || !logprobs || !entropy) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_transcription_set_window_alternatives: null argument");
+    if (n_alt < 1 || n_alt > WH_MAX_ALTERNATIVES) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_transcription_set_window_alternatives: n_alt %d (1 .. %d)", n_alt, WH_MAX_ALTERNATIVES);
+    if (t->n_alt > 0 && t->n_alt != n_alt) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_transcription_set_window_alternatives: n_alt %d, the transcription carries %d", n_alt, t->n_alt);
+    if (n_tokens < 0 || n_tokens > WH_MAX_RESULT_TOKENS) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_transcription_set_window_alternatives: n_tokens %d outside [0, %d]", n_tokens, WH_MAX_RESULT_TOKENS);
+    for (const auto& w : t->last_window)
+        if (w.src < 0 || w.src + w.n > n_tokens || w.dst < 0 || (size_t)(w.dst + w.n) > t->tokens.size())
+            return set_error(WH_ERR_INVALID_ARGUMENT, "wh_transcription_set_window_alternatives: %d rows do not cover the window added last (a segment holds result tokens [%d, %d))", n_tokens, w.src, w.src + w.n);
+    t->n_alt = n_alt;
+    whi::transcription_sync_alternatives(t);
+    for (const auto& w : t->last_window) {
+        std::copy(ids + (size_t)w.src * n_alt, ids + (size_t)(w.src + w.n) * n_alt, t->alt_ids.begin() + (size_t)w.dst * n_alt);
+        std::copy(logprobs + (size_t)w.src * n_alt, logprobs + (size_t)(w.src + w.n) * n_alt, t->alt_lp.begin() + (size_t)w.dst * n_alt);
+        std::copy(entropy + w.src, entropy + w.src + w.n, t->alt_entropy.begin() + w.dst);
+    }
+    return WH_OK;
+}
+// Flat arrays aligned with wh_transcription_tokens: ids / logprobs [n_tokens][n_alt], entropy [n_tokens]; segment i owns [token_offset, token_offset + n_tokens)
+// of them as well.  *n_alt == 0: the transcription carries none (the pointers are then NULL)
+extern "C" int wh_transcription_alternatives(const wh_transcription* t, const int32_t** ids, const float** logprobs, const float** entropy, int* n_alt, int* n_tokens) {
+    if (!t || !n_alt) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_transcription_alternatives: null argument");
+    const bool on = t->n_alt > 0;
+    *n_alt = on ? t->n_alt : 0;
+    if (n_tokens) *n_tokens = on ? (int)t->alt_entropy.size() : 0;
+    if (ids) *ids = on ? t->alt_ids.data() : nullptr;
+    if (logprobs) *logprobs = on ? t->alt_lp.data() : nullptr;
+    if (entropy) *entropy = on ? t->alt_entropy.data() : nullptr;
     return WH_OK;
 }
 
@@ -271,6 +316,8 @@ void transcription_truncate_segments(wh_transcription* t, int n_keep) {
     }
     if (t->segment_text.size() > (size_t)n_keep) t->segment_text.resize((size_t)n_keep);
     t->segments.resize((size_t)n_keep);
+    while (!t->last_window.empty() && (size_t)(t->last_window.back().dst + t->last_window.back().n) > t->tokens.size()) t->last_window.pop_back();
+    transcription_sync_alternatives(t);
 }
 }  // namespace whi
 
@@ -306,6 +353,10 @@ extern "C" int wh_merge_transcriptions(const wh_transcription* const* results, i
     }
     std::vector<const wh_transcription*> valid;
     for (int i = 0; i < n; ++i) if (results[i]) valid.push_back(results[i]);
+    // token alternatives: carried iff every input carries them with one n_alt
+    int merged_alt = valid.empty() ? 0 : valid[0]->n_alt;
+    for (const wh_transcription* r : valid) if (r->n_alt != merged_alt || r->alt_entropy.size() != r->tokens.size()) merged_alt = 0;
+    m->n_alt = merged_alt > 0 ? merged_alt : 0;
     for (size_t ri = 0; ri < valid.size(); ++ri) {
         const wh_transcription* r = valid[ri];
         if (!r->has_text) m->has_text = false;
@@ -317,6 +368,12 @@ extern "C" int wh_merge_transcriptions(const wh_transcription* const* results, i
             g.token_offset = (int)m->tokens.size();
             m->tokens.insert(m->tokens.end(), r->tokens.begin() + tsrc, r->tokens.begin() + tsrc + g.n_tokens);
             m->logprobs.insert(m->logprobs.end(), r->logprobs.begin() + tsrc, r->logprobs.begin() + tsrc + g.n_tokens);
+            if (m->n_alt > 0) {
+                const size_t na = (size_t)m->n_alt;
+                m->alt_ids.insert(m->alt_ids.end(), r->alt_ids.begin() + (size_t)tsrc * na, r->alt_ids.begin() + (size_t)(tsrc + g.n_tokens) * na);
+                m->alt_lp.insert(m->alt_lp.end(), r->alt_lp.begin() + (size_t)tsrc * na, r->alt_lp.begin() + (size_t)(tsrc + g.n_tokens) * na);
+                m->alt_entropy.insert(m->alt_entropy.end(), r->alt_entropy.begin() + tsrc, r->alt_entropy.begin() + tsrc + g.n_tokens);
+            }
             g.word_offset = (int)m->words.size();
             for (int k = 0; k < g.n_words; ++k) {
                 wh_word_timing w = r->words[wsrc + k];

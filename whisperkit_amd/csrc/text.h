@@ -76,4 +76,17 @@ struct wh_transcription {
     int language_token = -1;
     bool language_set = false;       // detectedLanguage is fixed by the first detection / first decoded window (TranscribeTask.swift:352,375-377)
     wh_timings timings{};
+    // token alternatives (wh_transcription_set_window_alternatives; results.cpp): n_alt == 0 - the transcription carries none.  Otherwise alt_ids / alt_lp hold
+    // n_alt (id, log-probability) pairs and alt_entropy one value per entry of `tokens`, index for index; a token of a window that got no rows holds
+    // (-1, -inf) / 0.  last_window: the segments of the window added last - result tokens [src, src + n) became flat tokens [dst, dst + n)
+    int n_alt = 0;
+    std::vector<int32_t> alt_ids;
+    std::vector<float> alt_lp, alt_entropy;
+    struct WindowSlice { int src, n, dst; };
+    std::vector<WindowSlice> last_window;
 };
+
+namespace whi {
+// the alternative arrays follow `tokens` (padding behind a growth, a cut behind a truncation); nothing with n_alt == 0
+void transcription_sync_alternatives(wh_transcription* t);
+}
