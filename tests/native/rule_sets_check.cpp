@@ -230,10 +230,61 @@ static void check_arithmetic(std::mt19937& rng) {
     CHECK(m > 0 && row[0] != 1.0f, "%lld", m);
 }
 
+// the row check of the wh_debug_*_apply entries against a literal restatement, on the cases the device tests send
+static void check_debug_rows() {
+    const int V = 51864, T = 224;
+    std::vector<int32_t> tok((size_t)2 * T, 7);
+    const int pairs[][2] = {{225, 0}, {3, 4}, {-1, 0}, {0, 0}, {224, 224}};
+    for (const auto& c : pairs) {
+        for (int at = 0; at < 2; ++at) {      // the case as row `at`, beside a valid row
+            int32_t nt[2] = {5, 5}, pl[2] = {2, 2};
+            nt[at] = c[0]; pl[at] = c[1];
+            const bool bad = c[0] < 0 || c[0] > T || c[1] < 0 || c[1] > c[0];
+            const RuleRowsFault f = rule_rows_invalid(tok.data(), nt, pl, 2, V, T);
+            CHECK(f.row == (bad ? at : -1) && (f.why != nullptr) == bad, "(%d, %d) as row %d: row %d", c[0], c[1], at, f.row);
+        }
+    }
+    // an id equal to n_vocab, at the last position the row counts; one position further it is not looked at
+    int32_t nt[2] = {224, 10}, pl[2] = {0, 10};
+    tok[(size_t)T + 9] = V;
+    RuleRowsFault f = rule_rows_invalid(tok.data(), nt, pl, 2, V, T);
+    CHECK(f.row == 1 && f.why && strstr(f.why, "vocabulary"), "row %d", f.row);
+    nt[1] = 9; pl[1] = 9;
+    CHECK(rule_rows_invalid(tok.data(), nt, pl, 2, V, T).row == -1, "an id behind the row's tokens");
+    tok[(size_t)T + 9] = V - 1; nt[1] = 10;
+    CHECK(rule_rows_invalid(tok.data(), nt, pl, 2, V, T).row == -1, "n_vocab - 1");
+    tok[0] = -1;
+    CHECK(rule_rows_invalid(tok.data(), nt, pl, 2, V, T).row == 0, "a negative id");
+    CHECK(rule_rows_invalid(tok.data(), nt, pl, 0, V, T).row == -1, "no rows");
+}
+
+// the pass mask separates exactly the passes that differ in what their step graphs bake, restated as the triple (logit_rules_kernel runs, phrase_rules_kernel
+// runs, 0 or - a set-aware pass - 1 | 2: its own logit table is handed to rule_sets_kernel | 4: its own phrase table is)
+static void check_pass_mask() {
+    int mask[8], old_key[8][3];
+    for (int c = 0; c < 8; ++c) {
+        const bool logit_on = c & 1, phrase_on = c & 2, set_aware = c & 4;
+        mask[c] = rules_pass_mask(logit_on, phrase_on, set_aware);
+        old_key[c][0] = (logit_on && !set_aware) ? 1 : 0;
+        old_key[c][1] = (phrase_on && !set_aware) ? 1 : 0;
+        old_key[c][2] = set_aware ? (1 | (logit_on ? 2 : 0) | (phrase_on ? 4 : 0)) : 0;
+        // what each bit says
+        CHECK(((mask[c] & kRulesPassLogitKernel) != 0) == (old_key[c][0] != 0) && ((mask[c] & kRulesPassPhraseKernel) != 0) == (old_key[c][1] != 0), "case %d: kernels", c);
+        CHECK(((mask[c] & kRulesPassSetAware) != 0) == set_aware && ((mask[c] & kRulesPassOwnLogit) != 0) == (set_aware && logit_on) &&
+              ((mask[c] & kRulesPassOwnPhrase) != 0) == (set_aware && phrase_on), "case %d: the set-aware bits", c);
+        CHECK((mask[c] == 0) == (!logit_on && !phrase_on && !set_aware), "case %d: 0 is the pass without rules", c);
+    }
+    for (int a = 0; a < 8; ++a)
+        for (int b = 0; b < 8; ++b)
+            CHECK((mask[a] == mask[b]) == (memcmp(old_key[a], old_key[b], sizeof(old_key[a])) == 0), "cases %d and %d: masks %d and %d", a, b, mask[a], mask[b]);
+}
+
 int main() {
     std::mt19937 rng(20);
     check_geometry();
     check_set_aware();
+    check_debug_rows();
+    check_pass_mask();
     check_grouping(rng);
     check_arithmetic(rng);
     if (g_failed) { printf("FAILED %d of %d\n", g_failed, g_checks); return 1; }

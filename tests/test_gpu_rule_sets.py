@@ -248,6 +248,69 @@ def test_kernel_alone_equals_the_restatement_as_bytes(own_on):
         sess.setPhraseRules(); sess.setLogitRules()
 
 
+def test_the_three_kernels_give_one_set_the_same_bytes():
+    """The three kernels share their phases (csrc/rules_phases.h): one set - phrases "mixed", p = 1.3, n = 2, three biases on phrase targets - over the histories
+    |H| = 0, 1 and 223, row 1 not live, (1) session-level through phrase_rules_kernel then logit_rules_kernel, (2) through rule_sets_kernel as set 0, (3) through
+    rule_sets_kernel as banked set 1 with the session's own rules off.  Each against the numpy restatement, as bytes; the match counters against its count.
+    (wh_debug_logit_rules_apply takes no live flags - every row it gets is live - so in (1) it gets the live rows, one call each.)"""
+    model = _model("test-micro", 0)
+    V = model.dims.n_vocab
+    st = model.specialTokens
+    special = int(st.special_token_begin)
+    phrases = PC.tables(V, special)["mixed"]
+    lg = dict(p=1.3, n=2, bias=[(9, 0.5), (8, -0.75), (4, 2.0)])
+    lists = PC.token_lists(special, int(st.start_of_transcript_token), int(st.end_token), int(st.time_token_begin))
+    picked = [next((tk, pl) for tk, pl in lists if len(PC.history(tk, pl, special)) == n) for n in (0, 1, 223)]
+    rng = np.random.default_rng(17)
+    rows = np.stack([PC.row(rng, V) for _ in range(3)])
+    tokens = np.zeros((3, L.MAX_TOKEN_CONTEXT), np.int32)
+    n_tok, p_len, live = np.zeros(3, np.int32), np.zeros(3, np.int32), np.array([1, 0, 1], np.int32)
+    want, n_want = [], 0
+    for r, (tk, pl) in enumerate(picked):
+        tokens[r, :len(tk)] = tk
+        n_tok[r], p_len[r] = len(tk), pl
+        if not live[r]:
+            want.append(rows[r])
+            continue
+        H = PC.history(tk, pl, special)
+        out, n = PC.apply_phrases(rows[r], H, phrases)
+        want.append(RC.apply_rules(out, H, **lg))
+        n_want += n
+    want = np.stack(want)
+    assert n_want > 0 and want[0].tobytes() != rows[0].tobytes() and want[2].tobytes() != rows[2].tobytes()
+    PI, PF = L.PI32, L.PF
+
+    def args(a, r0=0, n=3):
+        return (a[r0:].ctypes.data_as(PF), n, tokens[r0:].ctypes.data_as(PI), n_tok[r0:].ctypes.data_as(PI), p_len[r0:].ctypes.data_as(PI))
+
+    sess = api.Session(model, 3)
+    try:
+        lib = sess.lib
+        _define(sess, 1, (phrases, lg))
+        sess.setPhraseRules(phrases); sess.setLogitRules(repetitionPenalty=lg["p"], noRepeatNgramSize=lg["n"], tokenBias=lg["bias"])
+        # (1) the two session-level kernels, one behind the other
+        got = np.ascontiguousarray(rows.copy())
+        m0 = sess.phraseRulesStats()[2]
+        api._check(lib.wh_debug_phrase_rules_apply(sess.handle, *args(got), live.ctypes.data_as(PI)))
+        for r in (0, 2):
+            api._check(lib.wh_debug_logit_rules_apply(sess.handle, *args(got, r, 1)))
+        assert got.tobytes() == want.tobytes() and sess.phraseRulesStats()[2] - m0 == n_want
+        # (2) rule_sets_kernel with every row under set 0, (3) the same set from the bank with the session's own rules off
+        for k in (0, 1):
+            if k == 1:
+                sess.setPhraseRules(); sess.setLogitRules()
+            got = np.ascontiguousarray(rows.copy())
+            set_of = np.full(3, k, np.int32)
+            m0 = sess.ruleSetStats()[2]
+            api._check(lib.wh_debug_rule_sets_apply(sess.handle, *args(got), live.ctypes.data_as(PI), set_of.ctypes.data_as(PI)))
+            m1 = sess.ruleSetStats()[2]
+            assert got.tobytes() == want.tobytes(), k
+            assert [a - b for a, b in zip(m1, m0)] == [n_want if j == k else 0 for j in range(16)], k
+        assert got[1].tobytes() == rows[1].tobytes()
+    finally:
+        sess.close()
+
+
 # ---------------------------------------------------------------------------------------------- 2. a slot decodes to the bits of a pass of its own set alone
 @pytest.mark.parametrize("rig", list(RIGS))
 @pytest.mark.parametrize("temperature,seed", [(0.0, 0), (0.6, 5)], ids=["T0", "T0.6"])

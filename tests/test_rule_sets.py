@@ -97,7 +97,7 @@ def test_the_definition_checks_with_both_planners_before_it_writes():
     body = host[host.index('extern "C" int wh_session_define_rule_set'):host.index('extern "C" int wh_session_rule_set(')]
     for check in ("plan::rule_set_banked(index)", "plan::logit_rules_invalid(logit_rules, s->m->dims.n_vocab)", "plan::phrase_rules_invalid(phrase_rules, s->m->dims.n_vocab)"):
         assert check in body
-        for later in ("rule_sets_ensure", "rule_set_build", "hipMemcpyAsync", "c.defined =", "c.lr =", "c.pr ="):
+        for later in ("rule_sets_ensure", "rule_set_build", "hipMemcpyAsync", "c.defined =", "keep_logit_half(c,", "keep_phrase_half(c,"):
             assert body.index(check) < body.index(later), (check, later)
     src = open(os.path.join(ROOT, "whisperkit_amd", "csrc", "rule_sets.hip")).read() + open(os.path.join(ROOT, "whisperkit_amd", "csrc", "rule_sets_plan.h")).read() + body
     assert "getenv" not in src and "knob::" not in src                           # no launch decision from the environment: no new WH_* variable

@@ -485,6 +485,42 @@ def xabsSupports(nState: int, nHead: int) -> bool:
     return bool(L.load().wh_xabs_supports(int(nState), int(nHead)))
 
 
+# ---- device rules (setLogitRules / setPhraseRules / defineRuleSet): the two structs from the Python arguments and back.  A builder returns the struct
+# together with the arrays its pointers name: the caller holds both until the call has returned
+def _logit_rules_struct(repetitionPenalty, noRepeatNgramSize, tokenBias):
+    pairs = list(tokenBias.items()) if isinstance(tokenBias, dict) else list(tokenBias or [])
+    ids = np.ascontiguousarray([int(t) for t, _ in pairs], dtype=np.int32)
+    vals = np.ascontiguousarray([float(b) for _, b in pairs], dtype=np.float32)
+    r = L.WhLogitRules(float(repetitionPenalty), int(noRepeatNgramSize), len(pairs), 0,
+                       ids.ctypes.data_as(L.PI32) if len(pairs) else None, vals.ctypes.data_as(L.PF) if len(pairs) else None)
+    return r, (ids, vals)
+
+
+def _phrase_rules_struct(sequences):
+    pairs = list(sequences.items()) if isinstance(sequences, dict) else list(sequences or [])
+    seqs = [[int(t) for t in seq] for seq, _ in pairs]
+    flat = np.ascontiguousarray([t for seq in seqs for t in seq], dtype=np.int32)
+    lens = np.ascontiguousarray([len(seq) for seq in seqs], dtype=np.int32)
+    vals = np.ascontiguousarray([float(b) for _, b in pairs], dtype=np.float32)
+    r = L.WhPhraseRules(len(pairs), 0, flat.ctypes.data_as(L.PI32) if len(flat) else None, lens.ctypes.data_as(L.PI32) if len(pairs) else None,
+                        vals.ctypes.data_as(L.PF) if len(pairs) else None)
+    return r, (flat, lens, vals)
+
+
+def _logit_rules_dict(r) -> dict:
+    return {"repetitionPenalty": float(r.repetition_penalty), "noRepeatNgramSize": int(r.no_repeat_ngram_size),
+            "tokenBias": [(int(r.bias_tokens[i]), float(r.bias_values[i])) for i in range(r.n_bias)]}
+
+
+def _phrase_rules_list(r) -> list:
+    out, at = [], 0
+    for i in range(r.n_sequences):
+        n = int(r.lengths[i])
+        out.append((tuple(int(r.tokens[at + k]) for k in range(n)), float(r.biases[i])))
+        at += n
+    return out
+
+
 class Session:
     """Per-task state for up to `maxBatch` windows in flight (= DecodingInputs x maxBatch, one HIP stream)."""
 
@@ -1050,19 +1086,14 @@ class Session:
         (every temperature rung, compacted, narrowed and mixed passes) under the unfused sampler; decodeTextCustom, detectLanguage, noSpeechProbs and
         the forced pass do not run the rules; decodeTextBeam / decodeTextGuided / decodeTextSpeculative and beamSize > 1 in transcribe* are refused
         while rules are set, and transcribe* ignores an attached draft."""
-        pairs = list(tokenBias.items()) if isinstance(tokenBias, dict) else list(tokenBias or [])
-        ids = np.ascontiguousarray([int(t) for t, _ in pairs], dtype=np.int32)
-        vals = np.ascontiguousarray([float(b) for _, b in pairs], dtype=np.float32)
-        r = L.WhLogitRules(float(repetitionPenalty), int(noRepeatNgramSize), len(pairs), 0,
-                           ids.ctypes.data_as(L.PI32) if len(pairs) else None, vals.ctypes.data_as(L.PF) if len(pairs) else None)
+        r, _alive = _logit_rules_struct(repetitionPenalty, noRepeatNgramSize, tokenBias)
         _check(self.lib.wh_session_set_logit_rules(self.handle, C.byref(r)))
 
     def logitRules(self) -> dict:
         """the session's rule set: {"repetitionPenalty", "noRepeatNgramSize", "tokenBias": [(id, bias), ...]} - the neutral set when the mode is off"""
         r = L.WhLogitRules()
         _check(self.lib.wh_session_logit_rules(self.handle, C.byref(r)))
-        return {"repetitionPenalty": float(r.repetition_penalty), "noRepeatNgramSize": int(r.no_repeat_ngram_size),
-                "tokenBias": [(int(r.bias_tokens[i]), float(r.bias_values[i])) for i in range(r.n_bias)]}
+        return _logit_rules_dict(r)
 
     def logitRulesStats(self) -> Tuple[int, int]:
         """(decode passes that ran under rules, launches of logit_rules_kernel in them) since the session was created"""
@@ -1086,25 +1117,14 @@ class Session:
         and the forced pass do not run the rules; decodeTextBeam / decodeTextGuided / decodeTextSpeculative and beamSize > 1 in transcribe* are refused while
         rules are set, and transcribe* ignores an attached draft.  Out of scope: text in place of ids, beam search under rules, retraction of a bias when
         a partial match breaks, more than 4096 sequences.  (A rule set per audio: defineRuleSet.)"""
-        pairs = list(sequences.items()) if isinstance(sequences, dict) else list(sequences or [])
-        seqs = [[int(t) for t in seq] for seq, _ in pairs]
-        flat = np.ascontiguousarray([t for seq in seqs for t in seq], dtype=np.int32)
-        lens = np.ascontiguousarray([len(seq) for seq in seqs], dtype=np.int32)
-        vals = np.ascontiguousarray([float(b) for _, b in pairs], dtype=np.float32)
-        r = L.WhPhraseRules(len(pairs), 0, flat.ctypes.data_as(L.PI32) if len(flat) else None, lens.ctypes.data_as(L.PI32) if len(pairs) else None,
-                            vals.ctypes.data_as(L.PF) if len(pairs) else None)
+        r, _alive = _phrase_rules_struct(sequences)
         _check(self.lib.wh_session_set_phrase_rules(self.handle, C.byref(r)))
 
     def phraseRules(self) -> list:
         """the session's phrase rules, in the caller's order: [((id, ...), bias), ...] - empty when the mode is off"""
         r = L.WhPhraseRules()
         _check(self.lib.wh_session_phrase_rules(self.handle, C.byref(r)))
-        out, at = [], 0
-        for i in range(r.n_sequences):
-            n = int(r.lengths[i])
-            out.append((tuple(int(r.tokens[at + k]) for k in range(n)), float(r.biases[i])))
-            at += n
-        return out
+        return _phrase_rules_list(r)
 
     def phraseRulesStats(self) -> Tuple[int, int, int]:
         """(decode passes that ran under phrase rules, launches of phrase_rules_kernel in them, (slot, step, sequence of two or more ids) matches counted on
@@ -1124,18 +1144,8 @@ class Session:
         unfused sampler with one kernel per step in front of it (csrc/rule_sets.hip).  decodeTextBeam / decodeTextGuided /
         decodeTextSpeculative and beamSize > 1 are refused for slots and audios under a set other than 0; an attached draft is ignored for a group that
         carries sets.  The bank (about 5 MB) is allocated by the first definition."""
-        pairs = list(tokenBias.items()) if isinstance(tokenBias, dict) else list(tokenBias or [])
-        ids = np.ascontiguousarray([int(t) for t, _ in pairs], dtype=np.int32)
-        vals = np.ascontiguousarray([float(b) for _, b in pairs], dtype=np.float32)
-        lr = L.WhLogitRules(float(repetitionPenalty), int(noRepeatNgramSize), len(pairs), 0,
-                            ids.ctypes.data_as(L.PI32) if len(pairs) else None, vals.ctypes.data_as(L.PF) if len(pairs) else None)
-        seqp = list(phrases.items()) if isinstance(phrases, dict) else list(phrases or [])
-        seqs = [[int(t) for t in seq] for seq, _ in seqp]
-        flat = np.ascontiguousarray([t for seq in seqs for t in seq], dtype=np.int32)
-        lens = np.ascontiguousarray([len(seq) for seq in seqs], dtype=np.int32)
-        bias = np.ascontiguousarray([float(b) for _, b in seqp], dtype=np.float32)
-        pr = L.WhPhraseRules(len(seqp), 0, flat.ctypes.data_as(L.PI32) if len(flat) else None, lens.ctypes.data_as(L.PI32) if len(seqp) else None,
-                             bias.ctypes.data_as(L.PF) if len(seqp) else None)
+        lr, _alive_lr = _logit_rules_struct(repetitionPenalty, noRepeatNgramSize, tokenBias)
+        pr, _alive_pr = _phrase_rules_struct(phrases)
         _check(self.lib.wh_session_define_rule_set(self.handle, int(index), C.byref(lr), C.byref(pr)))
 
     def ruleSet(self, index: int) -> dict:
@@ -1143,13 +1153,7 @@ class Session:
         bias), ...]} - the neutral values when the index is not defined"""
         lr, pr = L.WhLogitRules(), L.WhPhraseRules()
         _check(self.lib.wh_session_rule_set(self.handle, int(index), C.byref(lr), C.byref(pr)))
-        phrases, at = [], 0
-        for i in range(pr.n_sequences):
-            n = int(pr.lengths[i])
-            phrases.append((tuple(int(pr.tokens[at + k]) for k in range(n)), float(pr.biases[i])))
-            at += n
-        return {"repetitionPenalty": float(lr.repetition_penalty), "noRepeatNgramSize": int(lr.no_repeat_ngram_size),
-                "tokenBias": [(int(lr.bias_tokens[i]), float(lr.bias_values[i])) for i in range(lr.n_bias)], "phrases": phrases}
+        return {**_logit_rules_dict(lr), "phrases": _phrase_rules_list(pr)}
 
     def setSlotRuleSets(self, setOfSlot=None):
         """Step-level assignment by home slot: slot b of decodeText / decodeTextMixed decodes under rule set setOfSlot[b] (0 .. 15), every other slot and None

@@ -776,7 +776,7 @@ DecodeBuffers decode_buffers(wh_session* s, int batch, int max_position) {
         if (s->use_xabs) { s->xabs_pass = s->xabs; s->xabs_pass.spw = s->pass_spw; db.xabs = &s->xabs_pass; }
     }
     if (s->pass_owner) { db.self_owner = s->inpass_dev + s->B; db.owner_slots = s->B; }       // a pass that narrowed (host.hip inpass_narrow)
-    db.rule_sets = s->pass_rs ? &s->rs_args : nullptr;      // a set-aware pass (host.hip decode_text_impl, rule_sets_plan.h)
+    db.rule_sets = (s->pass_rules & plan::kRulesPassSetAware) ? &s->rs_args : nullptr;     // a set-aware pass (host.hip decode_text_impl, rule_sets_plan.h)
     if (s->pass_alt) { db.alt_ids = s->alt_ids; db.alt_lp = s->alt_f32; db.alt_n = s->pass_alt; }      // a pass that records token alternatives (alternatives_plan.h)
     // cross-attention gate: WH_XATT_GATE=0 never, 1 always, unset: while the model carries more than one session (dec_shared.h)
     const int gate_mode = knob::once<knob::WH_XATT_GATE>();

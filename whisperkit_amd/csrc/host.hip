@@ -261,6 +261,28 @@ constexpr int kStepsPerGraph = 8;
 
 static bool use_graphs() { return !knob::once<knob::WH_NO_GRAPH>(); }
 
+// one sampled decode step of the running pass, with what the pass state arms for it: the no-speech kernel at its steps, the rules kernels (pass_rules)
+static void launch_pass_step(wh_session* s, const DecodeBuffers& db, int step) {
+    launch_decoder_step(db, s->cfg_dev, s->suppress_dev, true, s->st, whi::nospeech_step_args(s, step), whi::logit_rules_step_args(s), whi::phrase_rules_step_args(s));
+}
+
+// The history's cut-off of the device rules: word 2 of a table (special_token_begin) is the caller's, so every pass and every wh_debug_*_apply entry writes it,
+// stream-ordered in front of its launches.  Always into the session's own tables that are on; with `bank` (a set-aware pass, wh_debug_rule_sets_apply) also
+// into both halves of every defined banked set whose device copy holds another value.
+static int rules_write_special_begin(wh_session* s, int special_begin, bool bank) {
+    if (s->logit_rules_on) { s->lr_host[2] = special_begin; WH_HIP(hipMemcpyAsync(s->lr_dev + 2, s->lr_host + 2, sizeof(int32_t), hipMemcpyHostToDevice, s->st)); }
+    if (s->phrase_rules_on) { s->pr_host[2] = special_begin; WH_HIP(hipMemcpyAsync(s->pr_dev + 2, s->pr_host + 2, sizeof(int32_t), hipMemcpyHostToDevice, s->st)); }
+    for (int k = 1; bank && k < plan::kMaxRuleSets; ++k) {
+        wh_session::RuleSetCopy& c = s->rs_sets[k];
+        if (!c.defined || c.special_begin == special_begin) continue;
+        int32_t* base = s->rs_dev + whi::kRsOffBank + plan::rule_set_offset(k);
+        WH_HIP(hipMemsetD32Async(base + plan::kRuleSetOffPhrase + 2, special_begin, 1, s->st));
+        WH_HIP(hipMemsetD32Async(base + plan::kRuleSetOffLogit + 2, special_begin, 1, s->st));
+        c.special_begin = special_begin;
+    }
+    return WH_OK;
+}
+
 // Step graphs live in the session (a session is driven by one host thread at a time): no process-wide cache, no lock.
 // `first_step`: token_index of the live slots at the graph's first step (decodeText starts every slot at 0 and advances them in
 // lock step): the graph's self-attention launches fetch only the cache rows its 8 steps can reach, so there is one graph per
@@ -270,7 +292,7 @@ static int get_step_graph(wh_session* s, int batch, int first_step, hipGraphExec
     // (a compacted pass bakes the slot table's address, the mapped kernel instantiations and its own slots per workgroup into its launches)
     const WhGraphKey key{batch, s->align_enabled ? 1 : 0, s->fused_greedy ? 1 : 0, s->align_enabled ? s->n_align_alloc : 0, db.self_rows, db.xattn_gate ? 1 : 0,
                          db.slot_home ? 1 : 0, db.slot_home ? s->pass_spw : 0, db.self_owner ? 1 : 0, db.mixed,
-                         (int)plan::nospeech_step_mask(first_step, kStepsPerGraph, s->pass_ns), s->pass_lr ? 1 : 0, s->pass_pr ? 1 : 0, s->pass_rs ? s->pass_rs_key : 0, s->pass_alt};
+                         (int)plan::nospeech_step_mask(first_step, kStepsPerGraph, s->pass_ns), s->pass_rules, s->pass_alt};
     auto it = s->graphs.find(key);
     if (it != s->graphs.end()) { s->graph_use[key] = ++s->graph_tick; *out = it->second; return WH_OK; }
     // The cache is capped (a large-v3 step graph holds ~2.5 k kernel nodes; a configuration = everything of the key but the row bound has up
@@ -279,7 +301,7 @@ static int get_step_graph(wh_session* s, int batch, int first_step, hipGraphExec
     const size_t cap = (size_t)knob::once<knob::WH_GRAPH_CAP>();
     while (s->graphs.size() >= cap) {
         auto same_cfg = [](const WhGraphKey& a, const WhGraphKey& b) {
-            return a.batch == b.batch && a.align == b.align && a.fused == b.fused && a.n_align == b.n_align && a.gate == b.gate && a.mapped == b.mapped && a.spw == b.spw && a.owner == b.owner && a.mixed == b.mixed && a.ns_mask == b.ns_mask && a.logit_rules == b.logit_rules && a.phrase_rules == b.phrase_rules && a.rule_sets == b.rule_sets && a.alternatives == b.alternatives;
+            return a.batch == b.batch && a.align == b.align && a.fused == b.fused && a.n_align == b.n_align && a.gate == b.gate && a.mapped == b.mapped && a.spw == b.spw && a.owner == b.owner && a.mixed == b.mixed && a.ns_mask == b.ns_mask && a.rules == b.rules && a.alternatives == b.alternatives;
         };
         const WhGraphKey* victim = nullptr;
         unsigned long long victim_last = ~0ull;
@@ -298,7 +320,7 @@ static int get_step_graph(wh_session* s, int batch, int first_step, hipGraphExec
     }
     hipGraph_t graph;
     WH_HIP(hipStreamBeginCapture(s->st, hipStreamCaptureModeThreadLocal));
-    for (int i = 0; i < kStepsPerGraph; ++i) launch_decoder_step(db, s->cfg_dev, s->suppress_dev, true, s->st, whi::nospeech_step_args(s, first_step + i), whi::logit_rules_step_args(s), whi::phrase_rules_step_args(s));
+    for (int i = 0; i < kStepsPerGraph; ++i) launch_pass_step(s, db, first_step + i);
     WH_HIP(hipStreamEndCapture(s->st, &graph));
     hipGraphExec_t exec;
     WH_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
@@ -489,7 +511,7 @@ static int run_token_loop(wh_session* s, int batch, int loop_count, PassLayout* 
     int width = batch;                                   // (changes only through inpass_narrow)
     auto all_done_in = [](const SeqState* q, int n) { for (int b = 0; b < n; ++b) if (q[b].active && !q[b].done) return false; return true; };
     auto all_done = [&]() { return all_done_in(s->seq_host, width); };
-    auto count_steps = [&](int steps) { s->slot_steps += (long long)width * steps; if (L) s->inpass_slot_steps_saved += (long long)(L->width0 - width) * steps; if (s->pass_lr) s->lr_launches += steps; if (s->pass_pr) s->pr_launches += steps; if (s->pass_rs) s->rs_launches += steps; };
+    auto count_steps = [&](int steps) { s->slot_steps += (long long)width * steps; if (L) s->inpass_slot_steps_saved += (long long)(L->width0 - width) * steps; if (s->pass_rules & plan::kRulesPassLogitKernel) s->lr_launches += steps; if (s->pass_rules & plan::kRulesPassPhraseKernel) s->pr_launches += steps; if (s->pass_rules & plan::kRulesPassSetAware) s->rs_launches += steps; };
     // the last read of the pass: the compact slots, or - after a narrowing - every state by home slot (parked once more)
     auto final_read = [&]() -> int {
         if (L && L->switches > 0) {
@@ -509,7 +531,7 @@ static int run_token_loop(wh_session* s, int batch, int loop_count, PassLayout* 
             if (exec) { WH_HIP(hipGraphLaunch(exec, s->st)); count_steps(kStepsPerGraph); }
             else for (int i = 0; i < kStepsPerGraph && step + i < loop_count; ++i) {
                 DecodeBuffers db = whi::decode_buffers(s, width, step + i);
-                launch_decoder_step(db, s->cfg_dev, s->suppress_dev, true, s->st, whi::nospeech_step_args(s, step + i), whi::logit_rules_step_args(s), whi::phrase_rules_step_args(s)); WH_CHECK_LAUNCH();
+                launch_pass_step(s, db, step + i); WH_CHECK_LAUNCH();
                 count_steps(1);
             }
             WH_HIP(hipMemcpyAsync(s->seq_host, s->seq, sizeof(SeqState) * width, hipMemcpyDeviceToHost, s->st));
@@ -567,7 +589,7 @@ static int run_token_loop(wh_session* s, int batch, int loop_count, PassLayout* 
     } else {
         for (int step = 0; step < loop_count; ++step) {
             DecodeBuffers db = whi::decode_buffers(s, width, step);
-            launch_decoder_step(db, s->cfg_dev, s->suppress_dev, true, s->st, whi::nospeech_step_args(s, step), whi::logit_rules_step_args(s), whi::phrase_rules_step_args(s));
+            launch_pass_step(s, db, step);
             WH_CHECK_LAUNCH();
             count_steps(1);
             if ((step & 7) == 7 && step + 1 < loop_count) {
@@ -669,7 +691,7 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
     for (int b = 0; b < batch; ++b) n_live += (active ? active[b] != 0 : 1);
     plan::CompactPassPlan cp{false, batch, s->use_xabs ? s->xabs.spw : 1};
     if (s->fallback_compaction == 1 && active) cp = plan::compact_pass_plan(n_live, batch, s->B, s->use_xabs ? s->xabs.spw : 1);
-    struct PassScope { wh_session* s; ~PassScope() { s->pass_mapped = false; s->pass_owner = false; s->pass_mixed = false; s->pass_ns = plan::NoSpeechRange{-1, -1}; s->pass_lr = false; s->pass_pr = false; s->pass_rs = false; s->pass_alt = 0; } } pass_scope{s};      // (every exit: the next caller of decode_buffers sees a plain pass)
+    struct PassScope { wh_session* s; ~PassScope() { s->pass_mapped = false; s->pass_owner = false; s->pass_mixed = false; s->pass_ns = plan::NoSpeechRange{-1, -1}; s->pass_rules = 0; s->pass_alt = 0; } } pass_scope{s};      // (every exit: the next caller of decode_buffers sees a plain pass)
     const int width = cp.compact ? cp.width : batch;
     if (cp.compact) {
         if (!s->slot_home_dev) WH_HIP(s->mem.alloc(&s->slot_home_dev, (size_t)s->B, false));
@@ -708,42 +730,27 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
     s->fused_greedy = true;
     for (int b = 0; b < width; ++b) if (s->seq_host[b].active && s->seq_host[b].temperature != 0.0f) s->fused_greedy = false;
     if (knob::now<knob::WH_NO_FUSED_SAMPLER>()) s->fused_greedy = false;
-    // ---- device logit rules (wh_session_set_logit_rules; NO REFERENCE BEHAVIOUR): the unfused sampler with logit_rules_kernel in front of it at every
-    // step.  The setter wrote the rule set; the history's cut-off is this call's special_token_begin
-    if (s->logit_rules_on) {
+    // ---- device rules (NO REFERENCE BEHAVIOUR): the unfused sampler with, at every step, the kernels the pass's mask names in front of it
+    // (rule_sets_plan.h rules_pass_mask) - phrase_rules_kernel, then logit_rules_kernel (wh_session_set_phrase_rules / wh_session_set_logit_rules), or in a
+    // set-aware pass rule_sets_kernel alone: set 0 is the session's own two tables (as far as they are on), set k >= 1 lies in the bank.  The setters wrote the
+    // tables; the history's cut-off is this call's special_token_begin
+    const int rules = plan::rules_pass_mask(s->logit_rules_on, s->phrase_rules_on, set_aware);
+    if (rules) {
         s->fused_greedy = false;
-        s->lr_host[2] = st->special_token_begin;
-        WH_HIP(hipMemcpyAsync(s->lr_dev + 2, s->lr_host + 2, sizeof(int32_t), hipMemcpyHostToDevice, s->st));
-        if (!set_aware) { s->pass_lr = true; s->lr_passes += 1; }      // (a set-aware pass hands the table to rule_sets_kernel as set 0's)
+        r = rules_write_special_begin(s, st->special_token_begin, set_aware);
+        if (r) return r;
+        if (rules & plan::kRulesPassLogitKernel) s->lr_passes += 1;
+        if (rules & plan::kRulesPassPhraseKernel) s->pr_passes += 1;
     }
-    // ---- device phrase rules (wh_session_set_phrase_rules; NO REFERENCE BEHAVIOUR): likewise, phrase_rules_kernel directly in front of logit_rules_kernel
-    if (s->phrase_rules_on) {
-        s->fused_greedy = false;
-        s->pr_host[2] = st->special_token_begin;
-        WH_HIP(hipMemcpyAsync(s->pr_dev + 2, s->pr_host + 2, sizeof(int32_t), hipMemcpyHostToDevice, s->st));
-        if (!set_aware) { s->pass_pr = true; s->pr_passes += 1; }
-    }
-    // ---- per-audio rule sets: a set-aware pass runs the unfused sampler with rule_sets_kernel alone in front of it - set 0 is the session's own two tables (as far
-    // as they are on), set k >= 1 lies in the bank.  Every defined set gets this call's special_token_begin (written when it differs from what the set holds);
-    // the slot table goes up by home slot, so compacted, narrowed and mixed passes need nothing else
-    if (set_aware) {
-        s->fused_greedy = false;
-        for (int k = 1; k < plan::kMaxRuleSets; ++k) {
-            wh_session::RuleSetCopy& c = s->rs_sets[k];
-            if (!c.defined || c.special_begin == st->special_token_begin) continue;
-            int32_t* base = s->rs_dev + whi::kRsOffBank + plan::rule_set_offset(k);
-            WH_HIP(hipMemsetD32Async(base + plan::kRuleSetOffPhrase + 2, st->special_token_begin, 1, s->st));
-            WH_HIP(hipMemsetD32Async(base + plan::kRuleSetOffLogit + 2, st->special_token_begin, 1, s->st));
-            c.special_begin = st->special_token_begin;
-        }
+    if (set_aware) {      // the slot table goes up by home slot, so compacted, narrowed and mixed passes need nothing else
         memset(s->rs_host, 0, sizeof(int32_t) * (size_t)s->B);
         for (int b = 0; b < batch; ++b) if (plan::slot_is_live(active, b)) s->rs_host[b] = set_of_slot[b];
         WH_HIP(hipMemcpyAsync(s->rs_dev + whi::kRsOffSlots, s->rs_host, sizeof(int32_t) * (size_t)s->B, hipMemcpyHostToDevice, s->st));
-        s->rs_args.own_logit = s->logit_rules_on ? s->lr_dev : nullptr;
-        s->rs_args.own_phrase = s->phrase_rules_on ? s->pr_dev : nullptr;
-        s->pass_rs_key = 1 | (s->logit_rules_on ? 2 : 0) | (s->phrase_rules_on ? 4 : 0);
-        s->pass_rs = true; s->rs_passes += 1;
+        s->rs_args.own_logit = (rules & plan::kRulesPassOwnLogit) ? s->lr_dev : nullptr;
+        s->rs_args.own_phrase = (rules & plan::kRulesPassOwnPhrase) ? s->pr_dev : nullptr;
+        s->rs_passes += 1;
     }
+    s->pass_rules = rules;
     // ---- token alternatives (wh_session_set_token_alternatives; NO REFERENCE BEHAVIOUR): the unfused sampler's recording instantiation.  The rows of
     // the home slots this pass decodes start from "nothing recorded"; a fallback rung so overwrites only the windows it decodes again
     if (s->token_alternatives > 0) {
@@ -1104,6 +1111,72 @@ extern "C" int wh_debug_token_alternatives_apply(wh_session* s, const float* row
     return WH_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ device rules: what the three features share
+// The session's copy of one half of a rule set (rs_sets[k]: what the getters hand out).  Null or neutral rules: the neutral half.  The new arrays are
+// complete before the old ones go: the caller may pass what a getter handed out, and an allocation that fails leaves the copy as it was
+static void keep_logit_half(wh_session::RuleSetCopy& c, const wh_logit_rules* r) {
+    std::vector<int32_t> ids;
+    std::vector<float> vals;
+    const bool on = !plan::logit_rules_neutral(r);
+    if (on) { ids.assign(r->bias_tokens, r->bias_tokens + r->n_bias); vals.assign(r->bias_values, r->bias_values + r->n_bias); }
+    c.bias_tokens.swap(ids); c.bias_values.swap(vals);
+    c.lr = on ? wh_logit_rules{r->repetition_penalty, r->no_repeat_ngram_size, r->n_bias, 0, c.bias_tokens.data(), c.bias_values.data()}
+              : wh_logit_rules{1.0f, 0, 0, 0, nullptr, nullptr};
+}
+static void keep_phrase_half(wh_session::RuleSetCopy& c, const wh_phrase_rules* r) {
+    std::vector<int32_t> ids, lens;
+    std::vector<float> vals;
+    const bool on = !plan::phrase_rules_neutral(r);
+    if (on) {
+        size_t n_ids = 0;
+        for (int i = 0; i < r->n_sequences; ++i) n_ids += (size_t)r->lengths[i];
+        ids.assign(r->tokens, r->tokens + n_ids); lens.assign(r->lengths, r->lengths + r->n_sequences); vals.assign(r->biases, r->biases + r->n_sequences);
+    }
+    c.tokens.swap(ids); c.lengths.swap(lens); c.biases.swap(vals);
+    c.pr = on ? wh_phrase_rules{r->n_sequences, 0, c.tokens.data(), c.lengths.data(), c.biases.data()} : wh_phrase_rules{0, 0, nullptr, nullptr, nullptr};
+}
+// n device match counters (64-bit; null: never allocated, all 0) into out, one copy behind a drained stream
+static int read_match_counters(const wh_session* s, const char* entry, const void* dev, int n, int64_t* out) {
+    unsigned long long v[plan::kMaxRuleSets] = {};
+    if (dev) {
+        if (hipSetDevice(s->m->device) != hipSuccess) return set_error(WH_ERR_HIP, "%s: hipSetDevice(%d) failed", entry, s->m->device);
+        WH_HIP(hipStreamSynchronize(s->st));
+        WH_HIP(hipMemcpy(v, dev, sizeof(unsigned long long) * (size_t)n, hipMemcpyDeviceToHost));
+    }
+    for (int k = 0; k < n; ++k) out[k] = (int64_t)v[k];
+    return WH_OK;
+}
+// The wh_debug_*_apply entries, around their one launch.  Stage: n_rows (<= max_batch) rows of the model's vocabulary go into the session's logits buffer (row i
+// where a launch leaves slot i's row), slot i's decode state gets tokens [i][WH_MAX_TOKEN_CONTEXT], n_tokens[i] and prompt_lens[i] and is live iff live is null
+// or live[i] != 0 (row i is home slot i).  The history's cut-off is the special_token_begin of wh_special_tokens_default (bank: rules_write_special_begin).
+// Fetch: the rows come back behind the launch.
+static int debug_rows_stage(wh_session* s, const char* entry, const float* rows, int n_rows, const int32_t* tokens, const int32_t* n_tokens, const int32_t* prompt_lens,
+                            const int32_t* live, bool bank) {
+    const int V = s->m->dims.n_vocab;
+    const plan::RuleRowsFault bad = plan::rule_rows_invalid(tokens, n_tokens, prompt_lens, n_rows, V, kMaxTok);
+    if (bad.row >= 0) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: row %d: %s", entry, bad.row, bad.why);
+    wh_special_tokens st;
+    memset(&st, 0, sizeof(st));
+    if (wh_special_tokens_default(s->m, &st) != WH_OK) st.special_token_begin = V;
+    WH_HIP(hipStreamSynchronize(s->st));                  // nothing in flight reads the staging the host writes next
+    for (int i = 0; i < n_rows; ++i) {
+        SeqState& q = s->seq_host[i];
+        memset(&q, 0, sizeof(q));
+        for (int k = 0; k < n_tokens[i]; ++k) q.tokens[k] = tokens[(size_t)i * kMaxTok + k];
+        q.n_tokens = n_tokens[i]; q.prompt_len = prompt_lens[i]; q.active = (!live || live[i]) ? 1 : 0; q.rng_lane = i;
+    }
+    if (int r = rules_write_special_begin(s, st.special_token_begin, bank)) return r;
+    WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * n_rows, hipMemcpyHostToDevice, s->st));
+    WH_HIP(hipMemcpyAsync(s->logits, rows, sizeof(float) * (size_t)n_rows * V, hipMemcpyHostToDevice, s->st));
+    return WH_OK;
+}
+static int debug_rows_fetch(wh_session* s, float* rows, int n_rows) {
+    WH_CHECK_LAUNCH();
+    WH_HIP(hipMemcpyAsync(rows, s->logits, sizeof(float) * (size_t)n_rows * s->m->dims.n_vocab, hipMemcpyDeviceToHost, s->st));
+    WH_HIP(hipStreamSynchronize(s->st));
+    return WH_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ device logit rules
 // NO REFERENCE BEHAVIOUR: the semantics are transformers' `SequenceBiasLogitsProcessor` (single-token sequences), `RepetitionPenaltyLogitsProcessor` and
 // `NoRepeatNGramLogitsProcessor`, applied in the order `generate` applies them (logit_rules_plan.h, logit_rules.hip).
@@ -1116,29 +1189,29 @@ extern "C" void wh_logit_rules_default(wh_logit_rules* r) {
 // through the address its graphs captured.
 extern "C" int wh_session_set_logit_rules(wh_session* s, const wh_logit_rules* rules) {
     if (!s || !s->m) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_logit_rules: null session");
+    WH_TRY
     if (const char* why = plan::logit_rules_invalid(rules, s->m->dims.n_vocab)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_logit_rules: %s", why);
     if (plan::logit_rules_neutral(rules)) {
         s->logit_rules_on = false;
-        s->lr_rules = wh_logit_rules{1.0f, 0, 0, 0, nullptr, nullptr};
+        keep_logit_half(s->rs_sets[0], nullptr);
         return WH_OK;
     }
     if (hipSetDevice(s->m->device) != hipSuccess) return set_error(WH_ERR_HIP, "wh_session_set_logit_rules: hipSetDevice(%d) failed", s->m->device);
     if (!s->lr_dev) WH_HIP(s->mem.alloc(&s->lr_dev, (size_t)plan::kLogitRulesWords, false));      // (not zeroed: a memset on the null stream could land behind the copy below, which writes every word)
     if (!s->lr_host) WH_HIP(s->mem.alloc_pinned(&s->lr_host, (size_t)plan::kLogitRulesWords));
     WH_HIP(hipStreamSynchronize(s->st));
-    int32_t* h = s->lr_host;
-    plan::logit_table_build(rules, s->m->dims.n_vocab, h);      // (h[2], the history's cut-off: every pass writes its own special_token_begin)
-    for (int i = 0; i < rules->n_bias; ++i) { s->lr_bias_tokens[i] = rules->bias_tokens[i]; s->lr_bias_values[i] = rules->bias_values[i]; }
-    WH_HIP(hipMemcpyAsync(s->lr_dev, h, sizeof(int32_t) * plan::kLogitRulesWords, hipMemcpyHostToDevice, s->st));
+    plan::logit_table_build(rules, s->m->dims.n_vocab, s->lr_host);      // (word 2, the history's cut-off: every pass writes its own special_token_begin)
+    WH_HIP(hipMemcpyAsync(s->lr_dev, s->lr_host, sizeof(int32_t) * plan::kLogitRulesWords, hipMemcpyHostToDevice, s->st));
     WH_HIP(hipStreamSynchronize(s->st));
-    s->lr_rules = wh_logit_rules{rules->repetition_penalty, rules->no_repeat_ngram_size, rules->n_bias, 0, s->lr_bias_tokens, s->lr_bias_values};
+    keep_logit_half(s->rs_sets[0], rules);
     s->logit_rules_on = true;
     return WH_OK;
+    WH_CATCH("wh_session_set_logit_rules")
 }
 // The session's copy; its arrays stay valid until the next setter call.  The neutral set when the mode is off
 extern "C" int wh_session_logit_rules(const wh_session* s, wh_logit_rules* out) {
     if (!s || !out) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_logit_rules: null argument");
-    *out = s->lr_rules;
+    *out = s->rs_sets[0].lr;
     return WH_OK;
 }
 extern "C" int wh_session_logit_rules_stats(const wh_session* s, int64_t* passes, int64_t* launches) {
@@ -1148,40 +1221,14 @@ extern "C" int wh_session_logit_rules_stats(const wh_session* s, int64_t* passes
     return WH_OK;
 }
 
-// Development aid: logit_rules_kernel alone over caller-supplied rows and histories - n_rows (<= max_batch) rows of the model's vocabulary go into the session's
-// logits buffer (row i where a launch leaves slot i's row), slot i's decode state gets tokens [i][WH_MAX_TOKEN_CONTEXT], n_tokens[i] and prompt_lens[i],
-// one launch under the session's rule set, the rows come back.  The history's cut-off is the special_token_begin of wh_special_tokens_default.
+// Development aid: logit_rules_kernel alone over caller-supplied rows and histories (debug_rows_stage; every row is live), one launch under the session's rule set.
 extern "C" int wh_debug_logit_rules_apply(wh_session* s, float* rows_inout, int n_rows, const int32_t* tokens, const int32_t* n_tokens, const int32_t* prompt_lens) {
     CHECK_SESSION(s); CHECK_BATCH(s, n_rows);
     if (!rows_inout || !tokens || !n_tokens || !prompt_lens) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_logit_rules_apply: null argument");
     if (!s->logit_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_logit_rules_apply: the session has no logit rules set (wh_session_set_logit_rules)");
-    const int V = s->m->dims.n_vocab;
-    for (int i = 0; i < n_rows; ++i) {
-        if (n_tokens[i] < 0 || n_tokens[i] > kMaxTok || prompt_lens[i] < 0 || prompt_lens[i] > n_tokens[i])
-            return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_logit_rules_apply: row %d has %d tokens, prompt length %d (0 <= prompt <= tokens <= %d)", i, n_tokens[i], prompt_lens[i], kMaxTok);
-        for (int k = 0; k < n_tokens[i]; ++k)
-            if (tokens[(size_t)i * kMaxTok + k] < 0 || tokens[(size_t)i * kMaxTok + k] >= V)
-                return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_logit_rules_apply: row %d token %d out of vocabulary", i, tokens[(size_t)i * kMaxTok + k]);
-    }
-    wh_special_tokens st;
-    memset(&st, 0, sizeof(st));
-    if (wh_special_tokens_default(s->m, &st) != WH_OK) st.special_token_begin = V;
-    WH_HIP(hipStreamSynchronize(s->st));                  // nothing in flight reads the staging the host writes next
-    for (int i = 0; i < n_rows; ++i) {
-        SeqState& q = s->seq_host[i];
-        memset(&q, 0, sizeof(q));
-        for (int k = 0; k < n_tokens[i]; ++k) q.tokens[k] = tokens[(size_t)i * kMaxTok + k];
-        q.n_tokens = n_tokens[i]; q.prompt_len = prompt_lens[i]; q.active = 1; q.rng_lane = i;
-    }
-    s->lr_host[2] = st.special_token_begin;
-    WH_HIP(hipMemcpyAsync(s->lr_dev + 2, s->lr_host + 2, sizeof(int32_t), hipMemcpyHostToDevice, s->st));
-    WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * n_rows, hipMemcpyHostToDevice, s->st));
-    WH_HIP(hipMemcpyAsync(s->logits, rows_inout, sizeof(float) * (size_t)n_rows * V, hipMemcpyHostToDevice, s->st));
-    launch_logit_rules(s->lr_dev, s->seq, s->logits, n_rows, V, s->st);
-    WH_CHECK_LAUNCH();
-    WH_HIP(hipMemcpyAsync(rows_inout, s->logits, sizeof(float) * (size_t)n_rows * V, hipMemcpyDeviceToHost, s->st));
-    WH_HIP(hipStreamSynchronize(s->st));
-    return WH_OK;
+    if (int r = debug_rows_stage(s, "wh_debug_logit_rules_apply", rows_inout, n_rows, tokens, n_tokens, prompt_lens, nullptr, false)) return r;
+    launch_logit_rules(s->lr_dev, s->seq, s->logits, n_rows, s->m->dims.n_vocab, s->st);
+    return debug_rows_fetch(s, rows_inout, n_rows);
 }
 
 // ------------------------------------------------------------------------------------------------ device phrase rules
@@ -1195,7 +1242,7 @@ extern "C" int wh_session_set_phrase_rules(wh_session* s, const wh_phrase_rules*
     if (const char* why = plan::phrase_rules_invalid(rules, s->m->dims.n_vocab)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_phrase_rules: %s", why);
     if (plan::phrase_rules_neutral(rules)) {
         s->phrase_rules_on = false;
-        s->pr_rules = wh_phrase_rules{0, 0, nullptr, nullptr, nullptr};
+        keep_phrase_half(s->rs_sets[0], nullptr);
         return WH_OK;
     }
     if (hipSetDevice(s->m->device) != hipSuccess) return set_error(WH_ERR_HIP, "wh_session_set_phrase_rules: hipSetDevice(%d) failed", s->m->device);
@@ -1209,12 +1256,7 @@ extern "C" int wh_session_set_phrase_rules(wh_session* s, const wh_phrase_rules*
     WH_HIP(hipStreamSynchronize(s->st));
     plan::phrase_table_build(*rules, s->m->dims.n_vocab, s->pr_host);
     WH_HIP(hipMemcpyAsync(s->pr_dev, s->pr_host, sizeof(int32_t) * plan::kPhraseTableWords, hipMemcpyHostToDevice, s->st));
-    size_t n_ids = 0;
-    for (int i = 0; i < rules->n_sequences; ++i) n_ids += (size_t)rules->lengths[i];
-    s->pr_tokens.assign(rules->tokens, rules->tokens + n_ids);
-    s->pr_lengths.assign(rules->lengths, rules->lengths + rules->n_sequences);
-    s->pr_biases.assign(rules->biases, rules->biases + rules->n_sequences);
-    s->pr_rules = wh_phrase_rules{rules->n_sequences, 0, s->pr_tokens.data(), s->pr_lengths.data(), s->pr_biases.data()};
+    keep_phrase_half(s->rs_sets[0], rules);
     s->phrase_rules_on = true;
     return WH_OK;
     WH_CATCH("wh_session_set_phrase_rules")
@@ -1222,61 +1264,28 @@ extern "C" int wh_session_set_phrase_rules(wh_session* s, const wh_phrase_rules*
 // The session's copy; its arrays stay valid until the next setter call.  The empty set when the mode is off
 extern "C" int wh_session_phrase_rules(const wh_session* s, wh_phrase_rules* out) {
     if (!s || !out) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_phrase_rules: null argument");
-    *out = s->pr_rules;
+    *out = s->rs_sets[0].pr;
     return WH_OK;
 }
-// matches: the device counter, one 8-byte copy behind a drained stream
+// matches: the device counter (read_match_counters)
 extern "C" int wh_session_phrase_rules_stats(const wh_session* s, int64_t* passes, int64_t* launches, int64_t* matches) {
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_phrase_rules_stats: null session");
     if (passes) *passes = s->pr_passes;
     if (launches) *launches = s->pr_launches;
-    if (matches) {
-        unsigned long long v = 0;
-        if (s->pr_args.matches) {
-            if (hipSetDevice(s->m->device) != hipSuccess) return set_error(WH_ERR_HIP, "wh_session_phrase_rules_stats: hipSetDevice(%d) failed", s->m->device);
-            WH_HIP(hipStreamSynchronize(s->st));
-            WH_HIP(hipMemcpy(&v, s->pr_args.matches, sizeof(v), hipMemcpyDeviceToHost));
-        }
-        *matches = (int64_t)v;
-    }
-    return WH_OK;
+    return matches ? read_match_counters(s, "wh_session_phrase_rules_stats", s->pr_args.matches, 1, matches) : WH_OK;
 }
 
-// Development aid: phrase_rules_kernel alone over caller-supplied rows and histories, in the shape of wh_debug_logit_rules_apply.  live (or null): row i is a
-// live slot iff live[i] != 0 - the others are inactive slots, whose rows the kernel must leave alone.
+// Development aid: phrase_rules_kernel alone over caller-supplied rows and histories (debug_rows_stage).  live (or null): row i is a live slot iff live[i] != 0 -
+// the others are inactive slots, whose rows the kernel must leave alone.
 extern "C" int wh_debug_phrase_rules_apply(wh_session* s, float* rows_inout, int n_rows, const int32_t* tokens, const int32_t* n_tokens, const int32_t* prompt_lens,
                                            const int32_t* live) {
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_phrase_rules_apply: null session");
     CHECK_SESSION(s); CHECK_BATCH(s, n_rows);
     if (!rows_inout || !tokens || !n_tokens || !prompt_lens) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_phrase_rules_apply: null argument");
     if (!s->phrase_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_phrase_rules_apply: the session has no phrase rules set (wh_session_set_phrase_rules)");
-    const int V = s->m->dims.n_vocab;
-    for (int i = 0; i < n_rows; ++i) {
-        if (n_tokens[i] < 0 || n_tokens[i] > kMaxTok || prompt_lens[i] < 0 || prompt_lens[i] > n_tokens[i])
-            return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_phrase_rules_apply: row %d has %d tokens, prompt length %d (0 <= prompt <= tokens <= %d)", i, n_tokens[i], prompt_lens[i], kMaxTok);
-        for (int k = 0; k < n_tokens[i]; ++k)
-            if (tokens[(size_t)i * kMaxTok + k] < 0 || tokens[(size_t)i * kMaxTok + k] >= V)
-                return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_phrase_rules_apply: row %d token %d out of vocabulary", i, tokens[(size_t)i * kMaxTok + k]);
-    }
-    wh_special_tokens st;
-    memset(&st, 0, sizeof(st));
-    if (wh_special_tokens_default(s->m, &st) != WH_OK) st.special_token_begin = V;
-    WH_HIP(hipStreamSynchronize(s->st));                  // nothing in flight reads the staging the host writes next
-    for (int i = 0; i < n_rows; ++i) {
-        SeqState& q = s->seq_host[i];
-        memset(&q, 0, sizeof(q));
-        for (int k = 0; k < n_tokens[i]; ++k) q.tokens[k] = tokens[(size_t)i * kMaxTok + k];
-        q.n_tokens = n_tokens[i]; q.prompt_len = prompt_lens[i]; q.active = (!live || live[i]) ? 1 : 0; q.rng_lane = i;
-    }
-    s->pr_host[2] = st.special_token_begin;
-    WH_HIP(hipMemcpyAsync(s->pr_dev + 2, s->pr_host + 2, sizeof(int32_t), hipMemcpyHostToDevice, s->st));
-    WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * n_rows, hipMemcpyHostToDevice, s->st));
-    WH_HIP(hipMemcpyAsync(s->logits, rows_inout, sizeof(float) * (size_t)n_rows * V, hipMemcpyHostToDevice, s->st));
-    launch_phrase_rules(s->pr_args, s->seq, s->logits, n_rows, V, s->st);
-    WH_CHECK_LAUNCH();
-    WH_HIP(hipMemcpyAsync(rows_inout, s->logits, sizeof(float) * (size_t)n_rows * V, hipMemcpyDeviceToHost, s->st));
-    WH_HIP(hipStreamSynchronize(s->st));
-    return WH_OK;
+    if (int r = debug_rows_stage(s, "wh_debug_phrase_rules_apply", rows_inout, n_rows, tokens, n_tokens, prompt_lens, live, false)) return r;
+    launch_phrase_rules(s->pr_args, s->seq, s->logits, n_rows, s->m->dims.n_vocab, s->st);
+    return debug_rows_fetch(s, rows_inout, n_rows);
 }
 
 // ------------------------------------------------------------------------------------------------ per-audio rule sets
@@ -1316,22 +1325,8 @@ extern "C" int wh_session_define_rule_set(wh_session* s, int index, const wh_log
     WH_HIP(hipStreamSynchronize(s->st));
     c.defined = !(lr_off && pr_off);
     c.special_begin = s->m->dims.n_vocab;
-    c.bias_tokens.clear(); c.bias_values.clear(); c.tokens.clear(); c.lengths.clear(); c.biases.clear();
-    c.lr = wh_logit_rules{1.0f, 0, 0, 0, nullptr, nullptr};
-    c.pr = wh_phrase_rules{0, 0, nullptr, nullptr, nullptr};
-    if (!lr_off) {
-        c.bias_tokens.assign(logit_rules->bias_tokens, logit_rules->bias_tokens + logit_rules->n_bias);
-        c.bias_values.assign(logit_rules->bias_values, logit_rules->bias_values + logit_rules->n_bias);
-        c.lr = wh_logit_rules{logit_rules->repetition_penalty, logit_rules->no_repeat_ngram_size, logit_rules->n_bias, 0, c.bias_tokens.data(), c.bias_values.data()};
-    }
-    if (!pr_off) {
-        size_t n_ids = 0;
-        for (int i = 0; i < phrase_rules->n_sequences; ++i) n_ids += (size_t)phrase_rules->lengths[i];
-        c.tokens.assign(phrase_rules->tokens, phrase_rules->tokens + n_ids);
-        c.lengths.assign(phrase_rules->lengths, phrase_rules->lengths + phrase_rules->n_sequences);
-        c.biases.assign(phrase_rules->biases, phrase_rules->biases + phrase_rules->n_sequences);
-        c.pr = wh_phrase_rules{phrase_rules->n_sequences, 0, c.tokens.data(), c.lengths.data(), c.biases.data()};
-    }
+    keep_logit_half(c, logit_rules);
+    keep_phrase_half(c, phrase_rules);
     return WH_OK;
     WH_CATCH("wh_session_define_rule_set")
 }
@@ -1339,8 +1334,8 @@ extern "C" int wh_session_define_rule_set(wh_session* s, int index, const wh_log
 extern "C" int wh_session_rule_set(const wh_session* s, int index, wh_logit_rules* logit_rules_out, wh_phrase_rules* phrase_rules_out) {
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_rule_set: null session");
     if (!plan::rule_set_index_valid(index)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_rule_set: index %d (0 .. %d)", index, plan::kMaxRuleSets - 1);
-    if (logit_rules_out) *logit_rules_out = index == 0 ? s->lr_rules : s->rs_sets[index].lr;
-    if (phrase_rules_out) *phrase_rules_out = index == 0 ? s->pr_rules : s->rs_sets[index].pr;
+    if (logit_rules_out) *logit_rules_out = s->rs_sets[index].lr;
+    if (phrase_rules_out) *phrase_rules_out = s->rs_sets[index].pr;
     return WH_OK;
 }
 // Step-level assignment by home slot: slots n .. max_batch - 1 and a null table name set 0.  Any index of 0 .. 15 is accepted here; a decode call whose
@@ -1364,73 +1359,32 @@ extern "C" int wh_session_slot_rule_sets(const wh_session* s, int32_t* set_of_sl
     for (int b = 0; b < n; ++b) set_of_slot_out[b] = b < (int)s->rs_slot.size() ? s->rs_slot[(size_t)b] : 0;
     return WH_OK;
 }
-// matches [WH_MAX_RULE_SETS]: the device counters, one copy behind a drained stream
+// matches [WH_MAX_RULE_SETS]: the device counters (read_match_counters)
 extern "C" int wh_session_rule_set_stats(const wh_session* s, int64_t* passes, int64_t* launches, int64_t* matches) {
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_rule_set_stats: null session");
     if (passes) *passes = s->rs_passes;
     if (launches) *launches = s->rs_launches;
-    if (matches) {
-        unsigned long long v[plan::kMaxRuleSets] = {};
-        if (s->rs_dev) {
-            if (hipSetDevice(s->m->device) != hipSuccess) return set_error(WH_ERR_HIP, "wh_session_rule_set_stats: hipSetDevice(%d) failed", s->m->device);
-            WH_HIP(hipStreamSynchronize(s->st));
-            WH_HIP(hipMemcpy(v, s->rs_dev, sizeof(v), hipMemcpyDeviceToHost));
-        }
-        for (int k = 0; k < plan::kMaxRuleSets; ++k) matches[k] = (int64_t)v[k];
-    }
-    return WH_OK;
+    return matches ? read_match_counters(s, "wh_session_rule_set_stats", s->rs_dev, plan::kMaxRuleSets, matches) : WH_OK;
 }
 
-// Development aid: rule_sets_kernel alone over caller-supplied rows and histories, in the shape of wh_debug_phrase_rules_apply.  set_of_row[i]: the set of row i
-// (row i is home slot i) - ANY value: the kernel must leave a row under an index that is out of range or undefined alone.  At least one banked set must have
-// been defined (the bank exists).  The launch's matches go into the session's counters.
+// Development aid: rule_sets_kernel alone over caller-supplied rows and histories (debug_rows_stage), in the shape of wh_debug_phrase_rules_apply.  set_of_row[i]:
+// the set of row i (row i is home slot i) - ANY value: the kernel must leave a row under an index that is out of range or undefined alone.  At least one banked
+// set must have been defined (the bank exists).  The launch's matches go into the session's counters.
 extern "C" int wh_debug_rule_sets_apply(wh_session* s, float* rows_inout, int n_rows, const int32_t* tokens, const int32_t* n_tokens, const int32_t* prompt_lens,
                                         const int32_t* live, const int32_t* set_of_row) {
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_rule_sets_apply: null session");
     CHECK_SESSION(s); CHECK_BATCH(s, n_rows);
     if (!rows_inout || !tokens || !n_tokens || !prompt_lens || !set_of_row) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_rule_sets_apply: null argument");
     if (!s->rs_dev) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_rule_sets_apply: the session has no rule set defined (wh_session_define_rule_set)");
-    const int V = s->m->dims.n_vocab;
-    for (int i = 0; i < n_rows; ++i) {
-        if (n_tokens[i] < 0 || n_tokens[i] > kMaxTok || prompt_lens[i] < 0 || prompt_lens[i] > n_tokens[i])
-            return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_rule_sets_apply: row %d has %d tokens, prompt length %d (0 <= prompt <= tokens <= %d)", i, n_tokens[i], prompt_lens[i], kMaxTok);
-        for (int k = 0; k < n_tokens[i]; ++k)
-            if (tokens[(size_t)i * kMaxTok + k] < 0 || tokens[(size_t)i * kMaxTok + k] >= V)
-                return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_rule_sets_apply: row %d token %d out of vocabulary", i, tokens[(size_t)i * kMaxTok + k]);
-    }
-    wh_special_tokens st;
-    memset(&st, 0, sizeof(st));
-    if (wh_special_tokens_default(s->m, &st) != WH_OK) st.special_token_begin = V;
-    WH_HIP(hipStreamSynchronize(s->st));                  // nothing in flight reads the staging the host writes next
-    for (int i = 0; i < n_rows; ++i) {
-        SeqState& q = s->seq_host[i];
-        memset(&q, 0, sizeof(q));
-        for (int k = 0; k < n_tokens[i]; ++k) q.tokens[k] = tokens[(size_t)i * kMaxTok + k];
-        q.n_tokens = n_tokens[i]; q.prompt_len = prompt_lens[i]; q.active = (!live || live[i]) ? 1 : 0; q.rng_lane = i;
-    }
-    if (s->logit_rules_on) { s->lr_host[2] = st.special_token_begin; WH_HIP(hipMemcpyAsync(s->lr_dev + 2, s->lr_host + 2, sizeof(int32_t), hipMemcpyHostToDevice, s->st)); }
-    if (s->phrase_rules_on) { s->pr_host[2] = st.special_token_begin; WH_HIP(hipMemcpyAsync(s->pr_dev + 2, s->pr_host + 2, sizeof(int32_t), hipMemcpyHostToDevice, s->st)); }
-    for (int k = 1; k < plan::kMaxRuleSets; ++k) {
-        wh_session::RuleSetCopy& c = s->rs_sets[k];
-        if (!c.defined || c.special_begin == st.special_token_begin) continue;
-        int32_t* base = s->rs_dev + whi::kRsOffBank + plan::rule_set_offset(k);
-        WH_HIP(hipMemsetD32Async(base + plan::kRuleSetOffPhrase + 2, st.special_token_begin, 1, s->st));
-        WH_HIP(hipMemsetD32Async(base + plan::kRuleSetOffLogit + 2, st.special_token_begin, 1, s->st));
-        c.special_begin = st.special_token_begin;
-    }
+    if (int r = debug_rows_stage(s, "wh_debug_rule_sets_apply", rows_inout, n_rows, tokens, n_tokens, prompt_lens, live, true)) return r;
     memset(s->rs_host, 0, sizeof(int32_t) * (size_t)s->B);
     for (int i = 0; i < n_rows; ++i) s->rs_host[i] = set_of_row[i];
     WH_HIP(hipMemcpyAsync(s->rs_dev + whi::kRsOffSlots, s->rs_host, sizeof(int32_t) * (size_t)s->B, hipMemcpyHostToDevice, s->st));
     RuleSetsArgs a = s->rs_args;
     a.own_logit = s->logit_rules_on ? s->lr_dev : nullptr;
     a.own_phrase = s->phrase_rules_on ? s->pr_dev : nullptr;
-    WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * n_rows, hipMemcpyHostToDevice, s->st));
-    WH_HIP(hipMemcpyAsync(s->logits, rows_inout, sizeof(float) * (size_t)n_rows * V, hipMemcpyHostToDevice, s->st));
-    launch_rule_sets(a, s->seq, s->logits, n_rows, V, s->st);
-    WH_CHECK_LAUNCH();
-    WH_HIP(hipMemcpyAsync(rows_inout, s->logits, sizeof(float) * (size_t)n_rows * V, hipMemcpyDeviceToHost, s->st));
-    WH_HIP(hipStreamSynchronize(s->st));
-    return WH_OK;
+    launch_rule_sets(a, s->seq, s->logits, n_rows, s->m->dims.n_vocab, s->st);
+    return debug_rows_fetch(s, rows_inout, n_rows);
 }
 
 // ------------------------------------------------------------------------------------------------ speculative greedy decode

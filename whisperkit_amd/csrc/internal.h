@@ -90,14 +90,12 @@ struct WhGraphKey {
     int owner;            // 1: a pass that narrowed in flight - the self-attention reads the session's row -> owner table (dec_self_attn_owner_kernel); 0 otherwise
     int mixed;            // 1: a mixed pass (option_mix.h) - the logits epilogue and the samplers run their *_mixed instantiations; 0 otherwise
     int ns_mask;          // bit i: step i of the graph stores its logits rows and runs nospeech_kernel (nospeech_plan.h nospeech_step_mask); 0 with the mode off
-    int logit_rules;      // 1: every step runs logit_rules_kernel before the (unfused) sampler (wh_session_set_logit_rules); 0 with no rules set
-    int phrase_rules;     // 1: every step runs phrase_rules_kernel in front of that (wh_session_set_phrase_rules); 0 with no phrase rules set
-    int rule_sets;        // 0, or a set-aware pass (rule_sets_plan.h): 1 | 2 (the session's own logit rules are handed to rule_sets_kernel) | 4 (its phrase rules are) -
-                          // the launch bakes those two pointers or null; logit_rules and phrase_rules are 0 then
+    int rules;            // the pass's rules mask (rule_sets_plan.h rules_pass_mask): which of logit_rules_kernel / phrase_rules_kernel every step runs before the
+                          // (unfused) sampler, or - a set-aware pass - rule_sets_kernel with the session's own tables it is handed (the launch bakes those two pointers or null); 0 with no rules
     int alternatives;     // 0, or the n of a pass that records token alternatives (alternatives_plan.h): the unfused sampler's recording instantiation with n baked in
     bool operator<(const WhGraphKey& o) const {
-        return std::tie(batch, align, fused, n_align, self_rows, gate, mapped, spw, owner, mixed, ns_mask, logit_rules, phrase_rules, rule_sets, alternatives) <
-               std::tie(o.batch, o.align, o.fused, o.n_align, o.self_rows, o.gate, o.mapped, o.spw, o.owner, o.mixed, o.ns_mask, o.logit_rules, o.phrase_rules, o.rule_sets, o.alternatives);
+        return std::tie(batch, align, fused, n_align, self_rows, gate, mapped, spw, owner, mixed, ns_mask, rules, alternatives) <
+               std::tie(o.batch, o.align, o.fused, o.n_align, o.self_rows, o.gate, o.mapped, o.spw, o.owner, o.mixed, o.ns_mask, o.rules, o.alternatives);
     }
 };
 
@@ -212,35 +210,12 @@ struct wh_session {
     wh::plan::NoSpeechRange pass_ns{-1, -1};
     wh::SeqState* ns_seq_keep = nullptr; f16* ns_kv_keep = nullptr;      // wh_no_speech_probs: the decode states and the cache rows 0 ([2][L][B][H][64]) the probe puts back
     long long ns_rows_scored = 0, ns_windows_over = 0, ns_windows_stopped = 0;      // wh_session_no_speech_stats
-    // device logit rules (wh_session_set_logit_rules: host.hip, logit_rules_plan.h, logit_rules.hip).  logit_rules_on: a set other than the neutral one is
-    // installed; lr_rules is the session's copy (its arrays are lr_bias_tokens / lr_bias_values).  lr_dev (device, kLogitRulesWords words at a fixed address,
-    // so that captured step graphs stay valid when values change) and its pinned mirror lr_host are allocated by the first setter that installs rules.
-    // pass_lr holds only while decode_text_impl runs a pass under the rules (the unfused sampler, the kernel in front of it).
-    bool logit_rules_on = false;
-    wh_logit_rules lr_rules{1.0f, 0, 0, 0, nullptr, nullptr};
-    int32_t lr_bias_tokens[wh::plan::kLogitRulesMaxBias] = {};
-    float lr_bias_values[wh::plan::kLogitRulesMaxBias] = {};
-    int32_t *lr_dev = nullptr, *lr_host = nullptr;
-    bool pass_lr = false;
-    long long lr_passes = 0, lr_launches = 0;      // wh_session_logit_rules_stats
-    // device phrase rules (wh_session_set_phrase_rules: host.hip, phrase_rules_plan.h, phrase_rules.hip).  phrase_rules_on: a non-empty set is installed;
-    // pr_rules is the session's copy (its arrays are the three vectors).  pr_args.table (device, kPhraseTableWords words at a fixed address, so that captured
-    // step graphs stay valid when values change), its pinned mirror pr_host and the 64-bit match counter pr_args.matches are allocated by the first setter
-    // that installs rules.  pass_pr holds only while decode_text_impl runs a pass under the rules, as pass_lr does.
-    bool phrase_rules_on = false;
-    wh_phrase_rules pr_rules{0, 0, nullptr, nullptr, nullptr};
-    std::vector<int32_t> pr_tokens, pr_lengths;
-    std::vector<float> pr_biases;
-    int32_t *pr_dev = nullptr, *pr_host = nullptr;
-    wh::PhraseRulesArgs pr_args{nullptr, nullptr};
-    bool pass_pr = false;
-    long long pr_passes = 0, pr_launches = 0;      // wh_session_phrase_rules_stats (matches: the device counter)
-    // per-audio rule sets (wh_session_define_rule_set: host.hip, rule_sets_plan.h, rule_sets.hip).  rs_sets[k], k = 1 .. 15: the session's copy of banked set k
-    // (entry 0 is never used: set 0 is lr_rules / pr_rules above).  rs_slot: the set index of every home slot, empty = all 0; the step-level setter writes it,
-    // every wh_transcribe* call owns it for its duration and leaves it all 0.  Everything on the device is ONE allocation made by the first definition:
-    // rs_dev = match counters [kMaxRuleSets] (64-bit) | slot table [kMaxSessionSlots] | bank [15][kRuleSetStride], at fixed addresses so that captured step
-    // graphs stay valid; rs_host (pinned) = slot table mirror [kMaxSessionSlots] | the staging of one set [kRuleSetStride].  pass_rs holds only while
-    // decode_text_impl runs a set-aware pass; rs_args is what its launches bake, pass_rs_key the graph key's field.
+    // device rules (host.hip).  rs_sets[k]: the session's copy of rule set k, what the getters hand out.  Entry 0 is the session's own
+    // set (wh_session_set_logit_rules / wh_session_set_phrase_rules: its two halves; defined / special_begin belong to the bank and stay unused there), entries
+    // 1 .. 15 are the banked sets (wh_session_define_rule_set).  A half's arrays stay valid until the next setter call for that set.
+    // pass_rules: the rules mask (rule_sets_plan.h rules_pass_mask) of the pass decode_text_impl is running - the unfused sampler, with logit_rules_kernel /
+    // phrase_rules_kernel or, in a set-aware pass, rule_sets_kernel in front of it; 0 otherwise.  The graph key's `rules`, the *_step_args helpers below and
+    // decode_buffers read it.
     struct RuleSetCopy {
         bool defined = false;
         int special_begin = -1;                    // the special_token_begin word the device copy holds (-1: not known)
@@ -250,10 +225,28 @@ struct wh_session {
         std::vector<float> bias_values, biases;
     };
     RuleSetCopy rs_sets[wh::plan::kMaxRuleSets];
+    int pass_rules = 0;
+    // device logit rules (wh_session_set_logit_rules: host.hip, logit_rules_plan.h, logit_rules.hip).  logit_rules_on: a set other than the neutral one is
+    // installed.  lr_dev (device, kLogitRulesWords words at a fixed address, so that captured step graphs stay valid when values change) and its pinned
+    // mirror lr_host are allocated by the first setter that installs rules.
+    bool logit_rules_on = false;
+    int32_t *lr_dev = nullptr, *lr_host = nullptr;
+    long long lr_passes = 0, lr_launches = 0;      // wh_session_logit_rules_stats
+    // device phrase rules (wh_session_set_phrase_rules: host.hip, phrase_rules_plan.h, phrase_rules.hip).  phrase_rules_on: a non-empty set is installed.
+    // pr_args.table (device, kPhraseTableWords words at a fixed address, so that captured step graphs stay valid when values change), its pinned mirror
+    // pr_host and the 64-bit match counter pr_args.matches are allocated by the first setter that installs rules.
+    bool phrase_rules_on = false;
+    int32_t *pr_dev = nullptr, *pr_host = nullptr;
+    wh::PhraseRulesArgs pr_args{nullptr, nullptr};
+    long long pr_passes = 0, pr_launches = 0;      // wh_session_phrase_rules_stats (matches: the device counter)
+    // per-audio rule sets (wh_session_define_rule_set: host.hip, rule_sets_plan.h, rule_sets.hip).  rs_slot: the set index of every home slot, empty = all 0;
+    // the step-level setter writes it, every wh_transcribe* call owns it for its duration and leaves it all 0.  Everything on the device is ONE allocation
+    // made by the first definition: rs_dev = match counters [kMaxRuleSets] (64-bit) | slot table [kMaxSessionSlots] | bank [15][kRuleSetStride], at fixed
+    // addresses so that captured step graphs stay valid; rs_host (pinned) = slot table mirror [kMaxSessionSlots] | the staging of one set [kRuleSetStride].
+    // rs_args is what a set-aware pass's launches bake.
     std::vector<int32_t> rs_slot;
     int32_t *rs_dev = nullptr, *rs_host = nullptr;
     wh::RuleSetsArgs rs_args{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-    bool pass_rs = false; int pass_rs_key = 0;
     long long rs_passes = 0, rs_launches = 0;      // wh_session_rule_set_stats (matches: the device counters)
     // token alternatives (wh_session_set_token_alternatives: host.hip alternatives_arm / alternatives_collect, alternatives_plan.h, the recording instantiations of
     // sampler_kernel).  token_alternatives: 0 = off, n = 1 .. 8.  Everything is allocated by the first setter call that turns the mode on: alt_ids (device, int32
@@ -338,9 +331,9 @@ inline const wh::NoSpeechArgs* nospeech_step_args(const wh_session* s, int step)
 int alternatives_arm(wh_session* s, int n, const int32_t* active);
 int alternatives_collect(wh_session* s, int n, const int32_t* active);
 // device logit rules: the rule set a step of the running pass hands to launch_decoder_step, or null (no rules set, or a pass that does not run them)
-inline const int* logit_rules_step_args(const wh_session* s) { return s->pass_lr ? s->lr_dev : nullptr; }
+inline const int* logit_rules_step_args(const wh_session* s) { return (s->pass_rules & wh::plan::kRulesPassLogitKernel) ? s->lr_dev : nullptr; }
 // device phrase rules: likewise
-inline const wh::PhraseRulesArgs* phrase_rules_step_args(const wh_session* s) { return s->pass_pr ? &s->pr_args : nullptr; }
+inline const wh::PhraseRulesArgs* phrase_rules_step_args(const wh_session* s) { return (s->pass_rules & wh::plan::kRulesPassPhraseKernel) ? &s->pr_args : nullptr; }
 // per-audio rule sets: does any of the home slots 0 .. n - 1 name a set other than 0?  (the passes that do not run rule sets refuse such a call)
 inline bool rule_sets_assigned(const wh_session* s, int n) {
     for (int b = 0; b < n && b < (int)s->rs_slot.size(); ++b) if (s->rs_slot[(size_t)b] != 0) return true;

@@ -369,6 +369,8 @@ struct NoSpeechArgs {
 // one workgroup per slot of `batch`: a live slot whose token_index equals its scoring position scores its row of logits ([batch][n_vocab], as the step's
 // logits launch wrote it) - between the logits launch and the sampler launch of a step
 void launch_nospeech(const NoSpeechArgs& a, SeqState* seq, const float* logits, int batch, int n_vocab, hipStream_t st);
+// The three device rules kernels below are built from one set of phases (rules_phases.h: the history, the phrase phase, the logit phase); which of them a
+// pass runs is its rules mask (rule_sets_plan.h rules_pass_mask; host.hip decode_text_impl).
 // device logit rules (logit_rules.hip, logit_rules_plan.h; NO REFERENCE BEHAVIOUR: transformers' SequenceBias / RepetitionPenalty / NoRepeatNGram processors):
 // one workgroup per slot of `batch`: a live slot applies the session's rule set (`rules`: logit_rules_plan.h kLogitRulesWords words of device memory) to its
 // row of logits ([batch][n_vocab], as the step's logits launch wrote it) from the history in its SeqState - between the logits launch and the sampler launch

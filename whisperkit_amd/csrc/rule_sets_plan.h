@@ -1,8 +1,10 @@
 // Per-audio rule sets (wh_session_define_rule_set): the geometry of the bank of rule sets, which passes are set-aware, the grouping
 // partition of wh_transcribe_batch_with_rule_sets and the arithmetic of one slot's row, as pure functions.  NO REFERENCE BEHAVIOUR: a set is one
 // wh_phrase_rules plus one wh_logit_rules with the semantics, limits and arithmetic of phrase_rules_plan.h and logit_rules_plan.h, unchanged.
+// Also what the three kinds of rules pass share on the host: the pass's rules mask and the row check of the wh_debug_*_apply entries.
 // Plain C++17 (no HIP headers, no environment, no statics): host.hip follows these, rule_sets_kernel (rule_sets.hip) restates rule_set_apply_row with
-// one workgroup per slot, tests/native/rule_sets_check.cpp runs them under g++ (tests/test_rule_sets.py).
+// one workgroup per slot - composed, as here, from the phases of the other two kernels (rules_phases.h) -, tests/native/rule_sets_check.cpp runs them
+// under g++ (tests/test_rule_sets.py).
 //
 // A session holds kMaxRuleSets numbered sets.  Index 0 is the session's own (wh_session_set_phrase_rules / wh_session_set_logit_rules: its two tables
 // live where they always have, outside the bank); indices 1 .. 15 are the bank, one allocation of 15 x kRuleSetStride words at a fixed address.  Every
@@ -65,6 +67,29 @@ inline bool rule_sets_pass_aware(const int32_t* set_of_slot, const int32_t* acti
     for (int b = 0; set_of_slot && b < n; ++b) if (slot_is_live(active, b) && set_of_slot[b] != 0) return true;
     return false;
 }
+// ---- the rules mask of a decode pass: which kernel every step runs in front of the unfused sampler, and with which of the session's own tables.  A pass
+// that is not set-aware runs logit_rules_kernel and / or phrase_rules_kernel, each iff its rules are on; a set-aware pass runs rule_sets_kernel alone and
+// hands it, as set 0's halves, the own tables that are on (the launch bakes those pointers or null).  0: no rules, the pass it has always been.  The mask
+// is a field of the step-graph key: two passes share a graph only if their masks are equal.
+constexpr int kRulesPassLogitKernel = 1, kRulesPassPhraseKernel = 2, kRulesPassSetAware = 4, kRulesPassOwnLogit = 8, kRulesPassOwnPhrase = 16;
+inline int rules_pass_mask(bool logit_rules_on, bool phrase_rules_on, bool set_aware) {
+    if (set_aware) return kRulesPassSetAware | (logit_rules_on ? kRulesPassOwnLogit : 0) | (phrase_rules_on ? kRulesPassOwnPhrase : 0);
+    return (logit_rules_on ? kRulesPassLogitKernel : 0) | (phrase_rules_on ? kRulesPassPhraseKernel : 0);
+}
+
+// ---- the rows of the wh_debug_*_apply entries: row i carries n_tokens[i] ids of tokens [i][max_tokens], the first prompt_lens[i] of them the prompt.
+// The first row that breaks 0 <= prompt <= tokens <= max_tokens or holds an id outside the vocabulary, with the reason; row -1: none does.
+struct RuleRowsFault { int row; const char* why; };
+inline RuleRowsFault rule_rows_invalid(const int32_t* tokens, const int32_t* n_tokens, const int32_t* prompt_lens, int n_rows, int n_vocab, int max_tokens) {
+    for (int i = 0; i < n_rows; ++i) {
+        if (n_tokens[i] < 0 || n_tokens[i] > max_tokens || prompt_lens[i] < 0 || prompt_lens[i] > n_tokens[i])
+            return {i, "token count and prompt length outside 0 <= prompt <= tokens <= the token context"};
+        for (int k = 0; k < n_tokens[i]; ++k)
+            if (tokens[(size_t)i * max_tokens + k] < 0 || tokens[(size_t)i * max_tokens + k] >= n_vocab) return {i, "a token outside the vocabulary"};
+    }
+    return {-1, nullptr};
+}
+
 // the first live slot that names an index outside 0 .. 15 or a banked set that is not defined (bit k of defined_mask: set k is), or -1
 inline int rule_sets_first_undefined(const int32_t* set_of_slot, const int32_t* active, int n, unsigned defined_mask) {
     for (int b = 0; set_of_slot && b < n; ++b) {
