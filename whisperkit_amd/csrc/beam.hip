@@ -240,7 +240,7 @@ int beam_loop_device(wh_session* s, int n_audio, int beam_size, int max_candidat
             const whi::BeamSeq& bq = A[a].beams[j];
             std::copy(bq.tok.begin(), bq.tok.end(), q.tokens);
             q.n_tokens = (int)bq.tok.size(); q.token_index = first; q.next_token = bq.tok.back(); q.prompt_len = n_prompt; q.active = 1;
-            if (s->pass_ns.lo == first) q.rng_lane = a * beam_size + j;      // no-speech detection, scoring step = the loop's first: the audio's first beam scores (lane / beam_size)
+            if (s->pass.ns.lo == first) q.rng_lane = a * beam_size + j;      // no-speech detection, scoring step = the loop's first: the audio's first beam scores (lane / beam_size)
         }
     }
     WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * n_slots, hipMemcpyHostToDevice, s->st));
@@ -348,8 +348,7 @@ static int wh_decode_text_beam_impl(wh_session* s, int n_audio, int beam_size, f
     if (whi::rule_sets_assigned(s, n_audio * beam_size)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text_beam: a slot of the call is assigned a rule set (wh_session_set_slot_rule_sets), which the beam pass does not run");
     const int V = s->m->dims.n_vocab, H = s->m->dims.n_text_head;
     (void)H;
-    for (int i = 0; i < n_prompt; ++i)
-        if (prompt[i] < 0 || prompt[i] >= V) return set_error(WH_ERR_PREFILL_FAILED, "wh_decode_text_beam: prompt token %d out of vocabulary", prompt[i]);
+    if (int r = whi::check_prompt_tokens("wh_decode_text_beam", prompt, n_prompt, V, WH_ERR_PREFILL_FAILED)) return r;
     // a finished list longer than the device list's capacity is ranked on the host (kernels.h kBeamFinishedCap; same results by definition)
     const bool device_ranking = s->beam_ranking == 1 && max_candidates <= kBeamFinishedCap;
     int r = ensure_beam_buffers(s, device_ranking);
@@ -362,25 +361,21 @@ static int wh_decode_text_beam_impl(wh_session* s, int n_audio, int beam_size, f
     // ---- no-speech detection (NO REFERENCE BEHAVIOUR): the value comes from the audio's own slot at a scoring step inside the pre-fill, from its
     // first beam (slot a * beam_size, lane_div = beam_size) when the scoring step is the beam loop's first.  The host loops do not read `done`: mode 2 never stops a beam pass
     const bool ns_on = s->no_speech_detection != plan::kNoSpeechOff;
-    struct NsScope { wh_session* s; ~NsScope() { s->pass_ns = plan::NoSpeechRange{-1, -1}; } } ns_scope{s};
+    whi::PassGuard guard{s};
     if (ns_on) {
         const int p = plan::nospeech_position(prompt, n_prompt, st->start_of_transcript_token);
         const std::vector<int> pos((size_t)n_audio, p);
         r = whi::nospeech_arm(s, n_audio, pos.data(), nullptr, st->no_speech_token, p == n_prompt - 1 ? beam_size : 1);
         if (r) return r;
     }
-    int lang_pos = -1;
-    if (language_tokens && wh_is_model_multilingual(s->m))
-        for (int i = 0; i + 1 < n_prompt; ++i) if (prompt[i] == st->start_of_transcript_token) { lang_pos = i + 1; break; }
+    const int lang_pos = whi::prompt_language_position(prompt, n_prompt, st->start_of_transcript_token, language_tokens && wh_is_model_multilingual(s->m));
 
     // ---- 1. pre-fill on the audios' own slots: decodeText's greedy steps for tokenIndex < n_prompt - 1 (TextDecoder.swift:573-757 on the
     // device state machine), which also resolve the "last prompt timestamp is replaced by the prediction" rule for position n_prompt - 1
     for (int b = 0; b < n_audio; ++b) {
         SeqState& q = s->seq_host[b];
-        memset(&q, 0, sizeof(q));
-        for (int i = 0; i < n_prompt; ++i) q.tokens[i] = prompt[i];
-        if (lang_pos >= 0 && language_tokens[b] >= 0 && language_tokens[b] < V) q.tokens[lang_pos] = language_tokens[b];
-        q.n_tokens = n_prompt; q.token_index = prefilled_index; q.next_token = q.tokens[0]; q.prompt_len = n_prompt; q.active = 1; q.temperature = 0.0f;
+        whi::seq_init_prompt(q, prompt, n_prompt, lang_pos, lang_pos >= 0 ? language_tokens[b] : -1, V);
+        q.active = 1; q.temperature = 0.0f;
         if (ns_on) q.rng_lane = b;      // the home slot nospeech_kernel writes to (T = 0: no other reader)
     }
     s->fused_greedy = false;
@@ -441,7 +436,7 @@ static int wh_decode_text_beam_impl(wh_session* s, int n_audio, int beam_size, f
                 const whi::BeamSeq& bq = A[a].beams[j];
                 std::copy(bq.tok.begin(), bq.tok.end(), q.tokens);
                 q.n_tokens = (int)bq.tok.size(); q.token_index = token_index; q.next_token = bq.tok.back(); q.prompt_len = n_prompt; q.active = 1;
-                if (s->pass_ns.lo == token_index) q.rng_lane = a * beam_size + j;      // (no-speech detection: the scoring step, see above)
+                if (s->pass.ns.lo == token_index) q.rng_lane = a * beam_size + j;      // (no-speech detection: the scoring step, see above)
             }
         WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * n_slots, hipMemcpyHostToDevice, s->st));
         for (int j = 0; j < n_slots; ++j) owner[(size_t)j * kMaxTok + token_index] = j;      // the row this step writes is the slot's own

@@ -767,17 +767,18 @@ DecodeBuffers decode_buffers(wh_session* s, int batch, int max_position) {
     db.emb = m->emb; db.pos = m->dec_pos; db.layers_host = m->dec.data(); db.lnf_g = m->lnf_g; db.lnf_b = m->lnf_b;
     db.self_k = s->self_k; db.self_v = s->self_v; db.cross_k_hi = s->cross_k_hi; db.cross_v_hi = s->cross_v_hi; db.cross_k_lo = s->cross_k_lo; db.cross_v_lo = s->cross_v_lo;
     db.part = s->part; db.ticket = s->ticket; db.logits = s->logits; db.seq = s->seq;
-    db.mixed = s->pass_mixed ? 1 : 0; db.stats = s->stats; db.sup_mask = s->sup_mask_dev; db.fused_greedy = s->fused_greedy ? 1 : 0;
+    db.stats = s->stats; db.sup_mask = s->sup_mask_dev; db.fused_greedy = s->fused_greedy ? 1 : 0;
     db.align = s->align_enabled ? s->align : nullptr; db.align_slot = m->align_slot_dev; db.n_align = s->n_align_alloc;
     db.d32 = &s->d32; db.x = s->d32.x; db.q = s->d32.q;
     if (s->use_xabs) { s->xabs.enc = s->enc16; db.xabs = &s->xabs; }
-    if (s->pass_mapped) {       // compacted pass (host.hip decode_text_impl)
+    const PassState& p = s->pass; db.mixed = p.mixed ? 1 : 0;      // what the running pass switches on (pass_state.h)
+    if (p.mapped) {             // compacted pass (host.hip decode_text_impl)
         db.slot_home = s->slot_home_dev;
-        if (s->use_xabs) { s->xabs_pass = s->xabs; s->xabs_pass.spw = s->pass_spw; db.xabs = &s->xabs_pass; }
+        if (s->use_xabs) { s->xabs_pass = s->xabs; s->xabs_pass.spw = p.spw; db.xabs = &s->xabs_pass; }
     }
-    if (s->pass_owner) { db.self_owner = s->inpass_dev + s->B; db.owner_slots = s->B; }       // a pass that narrowed (host.hip inpass_narrow)
-    db.rule_sets = (s->pass_rules & plan::kRulesPassSetAware) ? &s->rs_args : nullptr;     // a set-aware pass (host.hip decode_text_impl, rule_sets_plan.h)
-    if (s->pass_alt) { db.alt_ids = s->alt_ids; db.alt_lp = s->alt_f32; db.alt_n = s->pass_alt; }      // a pass that records token alternatives (alternatives_plan.h)
+    if (p.owner) { db.self_owner = s->inpass_dev + s->B; db.owner_slots = s->B; }       // a pass that narrowed (host.hip inpass_narrow)
+    db.rule_sets = (p.rules & plan::kRulesPassSetAware) ? &s->rs_args : nullptr;     // a set-aware pass (host.hip decode_text_impl, rule_sets_plan.h)
+    if (p.alt) { db.alt_ids = s->alt_ids; db.alt_lp = s->alt_f32; db.alt_n = p.alt; }      // a pass that records token alternatives (alternatives_plan.h)
     // cross-attention gate: WH_XATT_GATE=0 never, 1 always, unset: while the model carries more than one session (dec_shared.h)
     const int gate_mode = knob::once<knob::WH_XATT_GATE>();
     const bool gate_on = gate_mode < 0 ? kXattnGateDefault && m->n_sessions.load() > 1 : gate_mode != 0;

@@ -261,7 +261,7 @@ constexpr int kStepsPerGraph = 8;
 
 static bool use_graphs() { return !knob::once<knob::WH_NO_GRAPH>(); }
 
-// one sampled decode step of the running pass, with what the pass state arms for it: the no-speech kernel at its steps, the rules kernels (pass_rules)
+// one sampled decode step of the running pass, with what the pass state arms for it: the no-speech kernel at its steps, the rules kernels (pass.rules)
 static void launch_pass_step(wh_session* s, const DecodeBuffers& db, int step) {
     launch_decoder_step(db, s->cfg_dev, s->suppress_dev, true, s->st, whi::nospeech_step_args(s, step), whi::logit_rules_step_args(s), whi::phrase_rules_step_args(s));
 }
@@ -290,9 +290,8 @@ static int rules_write_special_begin(wh_session* s, int special_begin, bool bank
 static int get_step_graph(wh_session* s, int batch, int first_step, hipGraphExec_t* out) {
     DecodeBuffers db = whi::decode_buffers(s, batch, first_step + kStepsPerGraph - 1);
     // (a compacted pass bakes the slot table's address, the mapped kernel instantiations and its own slots per workgroup into its launches)
-    const WhGraphKey key{batch, s->align_enabled ? 1 : 0, s->fused_greedy ? 1 : 0, s->align_enabled ? s->n_align_alloc : 0, db.self_rows, db.xattn_gate ? 1 : 0,
-                         db.slot_home ? 1 : 0, db.slot_home ? s->pass_spw : 0, db.self_owner ? 1 : 0, db.mixed,
-                         (int)plan::nospeech_step_mask(first_step, kStepsPerGraph, s->pass_ns), s->pass_rules, s->pass_alt};
+    const WhGraphKey key = whi::step_graph_key(s->pass, batch, s->align_enabled, s->n_align_alloc, s->fused_greedy, db.self_rows, db.xattn_gate != nullptr,
+                                               (int)plan::nospeech_step_mask(first_step, kStepsPerGraph, s->pass.ns));
     auto it = s->graphs.find(key);
     if (it != s->graphs.end()) { s->graph_use[key] = ++s->graph_tick; *out = it->second; return WH_OK; }
     // The cache is capped (a large-v3 step graph holds ~2.5 k kernel nodes; a configuration = everything of the key but the row bound has up
@@ -300,22 +299,19 @@ static int get_step_graph(wh_session* s, int batch, int first_step, hipGraphExec
     // drained first: no executable graph is destroyed while a launch of it may still be running.
     const size_t cap = (size_t)knob::once<knob::WH_GRAPH_CAP>();
     while (s->graphs.size() >= cap) {
-        auto same_cfg = [](const WhGraphKey& a, const WhGraphKey& b) {
-            return a.batch == b.batch && a.align == b.align && a.fused == b.fused && a.n_align == b.n_align && a.gate == b.gate && a.mapped == b.mapped && a.spw == b.spw && a.owner == b.owner && a.mixed == b.mixed && a.ns_mask == b.ns_mask && a.rules == b.rules && a.alternatives == b.alternatives;
-        };
         const WhGraphKey* victim = nullptr;
         unsigned long long victim_last = ~0ull;
         for (const auto& kv : s->graphs) {
-            if (same_cfg(kv.first, key)) continue;
+            if (kv.first.same_cfg(key)) continue;
             unsigned long long last = 0;                       // a configuration's age = its most recent use
-            for (const auto& u : s->graph_use) if (same_cfg(u.first, kv.first)) last = std::max(last, u.second);
+            for (const auto& u : s->graph_use) if (u.first.same_cfg(kv.first)) last = std::max(last, u.second);
             if (last < victim_last) { victim_last = last; victim = &kv.first; }
         }
         if (!victim) break;                                    // only the current configuration is cached: let it grow to its 28
         const WhGraphKey v = *victim;
         WH_HIP(hipStreamSynchronize(s->st));
         for (auto g = s->graphs.begin(); g != s->graphs.end();) {
-            if (same_cfg(g->first, v)) { hipGraphExecDestroy(g->second); s->graph_use.erase(g->first); g = s->graphs.erase(g); } else ++g;
+            if (g->first.same_cfg(v)) { hipGraphExecDestroy(g->second); s->graph_use.erase(g->first); g = s->graphs.erase(g); } else ++g;
         }
     }
     hipGraph_t graph;
@@ -350,7 +346,7 @@ static int report_progress(wh_session* s, int batch) {
         SeqState& q = s->seq_host[b];
         if (!q.active || q.done || q.n_tokens <= 0) continue;
         wh_progress p{};
-        p.slot = s->pass_mapped ? s->slot_home_host[b] : b;      // a compacted pass reports the window's home slot
+        p.slot = s->pass.mapped ? s->slot_home_host[b] : b;      // a compacted pass reports the window's home slot
         p.n_tokens = q.n_tokens; p.tokens = q.tokens;
         float sum = 0;
         for (int i = 0; i < q.n_tokens; ++i) sum += q.logprobs[i];
@@ -399,7 +395,7 @@ int nospeech_arm(wh_session* s, int n, const int* pos, const float* stop, int to
     }
     h[4 * (size_t)B] = token; h[4 * (size_t)B + 1] = lane_div;
     WH_HIP(hipMemcpyAsync(s->ns_dev, h, sizeof(int32_t) * (4 * (size_t)B + 2), hipMemcpyHostToDevice, s->st));
-    s->pass_ns = plan::nospeech_step_range(pos, n);
+    s->pass.ns = plan::nospeech_step_range(pos, n);
     return WH_OK;
 }
 // behind the pass: prob | stopped by home slot into the pinned mirror (an unscored slot reads 0), the counters.  opts: null, or [n] the options whose
@@ -438,7 +434,7 @@ int alternatives_arm(wh_session* s, int n, const int32_t* active) {
         WH_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s->alt_f32 + b0 * row), ninf_bits, nb * row, s->st));
         WH_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ent + b0 * plan::kAltPositions), 0, nb * plan::kAltPositions, s->st));
     }
-    s->pass_alt = s->token_alternatives;
+    s->pass.alt = s->token_alternatives;
     s->alt_passes += 1;
     return WH_OK;
 }
@@ -490,7 +486,7 @@ static int inpass_narrow(wh_session* s, PassLayout& L, const SeqState* snap, con
     const int n = plan::inpass_compose(L.home.data(), L.live.data(), L.switches ? L.owner.data() : nullptr, L.width, keep.data(), p.width, steps_done, kMaxTok, B,
                                        home, live, owner);
     if (n != n_live) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text: the narrowed pass does not hold its live slots");
-    launch_seq_park(s->seq, s->seq_home, s->pass_mapped ? s->slot_home_dev : nullptr, L.width, B, s->st);
+    launch_seq_park(s->seq, s->seq_home, s->pass.mapped ? s->slot_home_dev : nullptr, L.width, B, s->st);
     WH_HIP(hipMemcpyAsync(s->slot_home_dev, home, sizeof(int32_t) * p.width, hipMemcpyHostToDevice, s->st));
     WH_HIP(hipMemcpyAsync(s->inpass_dev, live, sizeof(int32_t) * p.width, hipMemcpyHostToDevice, s->st));
     WH_HIP(hipMemcpyAsync(s->inpass_dev + B, owner, sizeof(int32_t) * (size_t)p.width * kMaxTok, hipMemcpyHostToDevice, s->st));
@@ -499,7 +495,7 @@ static int inpass_narrow(wh_session* s, PassLayout& L, const SeqState* snap, con
     L.width = p.width; L.switches += 1;
     L.home.assign(home, home + p.width); L.live.assign(live, live + p.width); L.owner.assign(owner, owner + (size_t)p.width * kMaxTok);
     memcpy(s->slot_home_host, home, sizeof(int32_t) * p.width);      // report_progress: compact slot -> home slot
-    s->pass_mapped = true; s->pass_spw = p.spw; s->pass_owner = true;
+    s->pass.mapped = true; s->pass.spw = p.spw; s->pass.owner = true;
     s->inpass_switches += 1;
     return WH_OK;
 }
@@ -511,7 +507,7 @@ static int run_token_loop(wh_session* s, int batch, int loop_count, PassLayout* 
     int width = batch;                                   // (changes only through inpass_narrow)
     auto all_done_in = [](const SeqState* q, int n) { for (int b = 0; b < n; ++b) if (q[b].active && !q[b].done) return false; return true; };
     auto all_done = [&]() { return all_done_in(s->seq_host, width); };
-    auto count_steps = [&](int steps) { s->slot_steps += (long long)width * steps; if (L) s->inpass_slot_steps_saved += (long long)(L->width0 - width) * steps; if (s->pass_rules & plan::kRulesPassLogitKernel) s->lr_launches += steps; if (s->pass_rules & plan::kRulesPassPhraseKernel) s->pr_launches += steps; if (s->pass_rules & plan::kRulesPassSetAware) s->rs_launches += steps; };
+    auto count_steps = [&](int steps) { s->slot_steps += (long long)width * steps; if (L) s->inpass_slot_steps_saved += (long long)(L->width0 - width) * steps; if (s->pass.rules & plan::kRulesPassLogitKernel) s->lr_launches += steps; if (s->pass.rules & plan::kRulesPassPhraseKernel) s->pr_launches += steps; if (s->pass.rules & plan::kRulesPassSetAware) s->rs_launches += steps; };
     // the last read of the pass: the compact slots, or - after a narrowing - every state by home slot (parked once more)
     auto final_read = [&]() -> int {
         if (L && L->switches > 0) {
@@ -626,6 +622,8 @@ extern "C" int wh_decode_text_languages(wh_session* s, int batch, const wh_decod
                                         wh_decoding_result* out) {
     return decode_text_impl(s, batch, opt, st, prompt, n_prompt, language_tokens, temperatures, active, seed, out);
 }
+// The steps, in the order they run: 1 validate (from here), 2 stage the slots, 3 arm the modes, 4 run, 5 back to the home layout, 6 collect.  They share the
+// call's arguments and the class view (cls_*, init_slot, finalise_options), so they are the sections of one function; the pass state they switch on is s->pass
 static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options* opt, const wh_special_tokens* st, const int32_t* prompt,
                             int n_prompt, const int32_t* language_tokens, const float* temperatures, const int32_t* active, uint64_t seed,
                             wh_decoding_result* out, const MixClasses* mix) {
@@ -633,7 +631,7 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
     if (mix) { opt = mix->opts[0]; prompt = mix->prompts[0]; n_prompt = mix->n_prompts[0]; }
     if (!opt || !st || !prompt || !out) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text: null argument");
     const int V = s->m->dims.n_vocab;
-    // ---- per-audio rule sets (wh_session_define_rule_set; NO REFERENCE BEHAVIOUR): a pass is set-aware iff a live slot names a set other than 0; a
+    // per-audio rule sets (wh_session_define_rule_set; NO REFERENCE BEHAVIOUR): a pass is set-aware iff a live slot names a set other than 0; a
     // live slot that names an undefined set fails the call before anything is launched
     const int32_t* const set_of_slot = s->rs_slot.empty() ? nullptr : s->rs_slot.data();
     const bool set_aware = plan::rule_sets_pass_aware(set_of_slot, active, batch);
@@ -649,14 +647,14 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
     auto cls_n_prompt = [&](int c) { return mix ? mix->n_prompts[c] : n_prompt; };
     auto cls_opt = [&](int c) { return mix ? mix->opts[c] : opt; };
     auto cls_of = [&](int hb) { return mix ? mix->class_of_slot[hb] : 0; };
+    auto is_live = [&](int b) { return plan::slot_is_live(active, b); };
+    auto finalise_options = [&](int b) { return (mix && mix->slot_opts && mix->slot_opts[b]) ? mix->slot_opts[b] : cls_opt(cls_of(b)); };      // home slot b's result: the audio's own thresholds (see MixClasses), or its class's options
     int r = WH_OK;
     for (int c = 0; c < n_cls; ++c) {
-        const int32_t* pr = cls_prompt(c);
         const int np = cls_n_prompt(c);
-        if (!pr || !cls_opt(c)) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text: null argument");
+        if (!cls_prompt(c) || !cls_opt(c)) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text: null argument");
         if (np < 1 || np >= kMaxTok) return set_error(WH_ERR_PREFILL_FAILED, "wh_decode_text: prompt length %d out of range [1,%d)", np, kMaxTok);
-        for (int i = 0; i < np; ++i)
-            if (pr[i] < 0 || pr[i] >= V) return set_error(WH_ERR_PREFILL_FAILED, "wh_decode_text: prompt token %d out of vocabulary", pr[i]);
+        if ((r = whi::check_prompt_tokens("wh_decode_text", cls_prompt(c), np, V, WH_ERR_PREFILL_FAILED))) return r;
     }
     // (an unmixed pass: entry 0 of the tables, as ever; a mixed one: every class's entries behind one synchronisation)
     r = mix ? whi::upload_sampler_cfg_classes(s, mix->opts, mix->n_prompts, n_cls, st, prefilled_index, seed)
@@ -664,34 +662,26 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
     if (r) return r;
     if (opt->word_timestamps && s->m->n_align > 0) { r = whi::ensure_align(s); if (r) return r; }
     s->align_enabled = opt->word_timestamps && s->align;
-    // per-slot language token (batched windows of different audios, each with its own detected language): it replaces the
+    // ---- 2. stage the slots.  Per-slot language token (batched windows of different audios, each with its own detected language): it replaces the
     // token that follows <|startoftranscript|> in the shared prompt (prefillDecoderInputs, TextDecoder.swift:183-188)
     int lang_pos_of[kMaxOptionClasses];
-    for (int c = 0; c < n_cls; ++c) {
-        lang_pos_of[c] = -1;
-        if (language_tokens && wh_is_model_multilingual(s->m))
-            for (int i = 0; i + 1 < cls_n_prompt(c); ++i) if (cls_prompt(c)[i] == st->start_of_transcript_token) { lang_pos_of[c] = i + 1; break; }
-    }
+    for (int c = 0; c < n_cls; ++c) lang_pos_of[c] = whi::prompt_language_position(cls_prompt(c), cls_n_prompt(c), st->start_of_transcript_token, language_tokens && wh_is_model_multilingual(s->m));
     // the decode state of home slot hb as the pass starts it
     auto init_slot = [&](SeqState& q, int hb, bool act) {
-        const int c = cls_of(hb), np = cls_n_prompt(c), lang_pos = lang_pos_of[c];
-        const int32_t* pr = cls_prompt(c);
-        memset(&q, 0, sizeof(q));
-        for (int i = 0; i < np; ++i) q.tokens[i] = pr[i];
-        if (lang_pos >= 0 && language_tokens[hb] >= 0 && language_tokens[hb] < V) q.tokens[lang_pos] = language_tokens[hb];
-        q.n_tokens = np; q.token_index = prefilled_index; q.next_token = q.tokens[0]; q.prompt_len = np;
+        const int c = cls_of(hb), lang_pos = lang_pos_of[c];
+        whi::seq_init_prompt(q, cls_prompt(c), cls_n_prompt(c), lang_pos, lang_pos >= 0 ? language_tokens[hb] : -1, V);
         q.active = act ? 1 : 0;
         q.temperature = f16_round(temperatures ? temperatures[hb] : opt->temperature);
         q.rng_lane = seq_pack_lane(hb, c);      // the slot's random stream (T > 0) does not depend on where the slot is decoded; its option class (0 unless mixed)
     };
-    // ---- compacted pass (wh_session_set_fallback_compaction 1): a sparse `active` mask decodes at the width compact_pass_plan gives; compact
+    // Compacted pass (wh_session_set_fallback_compaction 1): a sparse `active` mask decodes at the width compact_pass_plan gives; compact
     // slot i stands for home slot slot_home_host[i] - its encoder output / cross K / V rows, its alignment rows, its language token,
-    // temperature and random stream.  Everything below this block is in home-slot terms again.
+    // temperature and random stream.  Steps 3 and 6 are in home-slot terms again.
     int n_live = 0;
-    for (int b = 0; b < batch; ++b) n_live += (active ? active[b] != 0 : 1);
+    for (int b = 0; b < batch; ++b) n_live += is_live(b);
     plan::CompactPassPlan cp{false, batch, s->use_xabs ? s->xabs.spw : 1};
     if (s->fallback_compaction == 1 && active) cp = plan::compact_pass_plan(n_live, batch, s->B, s->use_xabs ? s->xabs.spw : 1);
-    struct PassScope { wh_session* s; ~PassScope() { s->pass_mapped = false; s->pass_owner = false; s->pass_mixed = false; s->pass_ns = plan::NoSpeechRange{-1, -1}; s->pass_rules = 0; s->pass_alt = 0; } } pass_scope{s};      // (every exit: the next caller of decode_buffers sees a plain pass)
+    whi::PassGuard guard{s};      // (every exit: the next caller of decode_buffers sees a plain pass)
     const int width = cp.compact ? cp.width : batch;
     if (cp.compact) {
         if (!s->slot_home_dev) WH_HIP(s->mem.alloc(&s->slot_home_dev, (size_t)s->B, false));
@@ -700,13 +690,13 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
         if (plan::compact_slot_map(active, batch, width, home, live) != n_live) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text: the compacted pass does not hold its live slots");
         for (int i = 0; i < width; ++i) init_slot(s->seq_host[i], home[i], live[i] != 0);
         WH_HIP(hipMemcpyAsync(s->slot_home_dev, home, sizeof(int32_t) * width, hipMemcpyHostToDevice, s->st));
-        s->pass_mapped = true; s->pass_spw = cp.spw;
+        s->pass.mapped = true; s->pass.spw = cp.spw;
         s->compacted_passes += 1;
     } else {
-        for (int b = 0; b < batch; ++b) init_slot(s->seq_host[b], b, active ? active[b] != 0 : true);
+        for (int b = 0; b < batch; ++b) init_slot(s->seq_host[b], b, is_live(b));
     }
-    // ---- no-speech detection (wh_session_set_no_speech_detection; NO REFERENCE BEHAVIOUR): every decoded slot's scoring position - the first
-    // <|startoftranscript|> of its class's prompt - and, in mode 2, its stop threshold from the options its result is finalised under, by home slot
+    // ---- 3. arm the modes.  No-speech detection (wh_session_set_no_speech_detection; NO REFERENCE BEHAVIOUR): every decoded slot's scoring position -
+    // the first <|startoftranscript|> of its class's prompt - and, in mode 2, its stop threshold from the options its result is finalised under, by home slot
     std::vector<const wh_decoding_options*> ns_opts;
     if (s->no_speech_detection != plan::kNoSpeechOff) {
         int cpos[kMaxOptionClasses];
@@ -715,8 +705,8 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
         std::vector<float> stop((size_t)batch);
         ns_opts.assign((size_t)batch, nullptr);
         for (int b = 0; b < batch; ++b) {
-            const bool act = active ? active[b] != 0 : true;
-            const wh_decoding_options* fo = (mix && mix->slot_opts && mix->slot_opts[b]) ? mix->slot_opts[b] : cls_opt(cls_of(b));
+            const bool act = is_live(b);
+            const wh_decoding_options* fo = finalise_options(b);
             pos[b] = act ? cpos[cls_of(b)] : -1;
             stop[b] = plan::nospeech_stop_threshold(s->no_speech_detection, fo);
             if (act) ns_opts[b] = fo;
@@ -725,7 +715,7 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
         if (r) return r;
     }
     s->decode_passes += 1;
-    if (mix) { s->pass_mixed = true; s->mix_mixed_passes += 1; s->mix_max_classes = std::max<long long>(s->mix_max_classes, n_cls); }
+    if (mix) { s->pass.mixed = true; s->mix_mixed_passes += 1; s->mix_max_classes = std::max<long long>(s->mix_max_classes, n_cls); }
     // fused greedy path: every active slot samples at T = 0 (filters + softmax statistics in the logits epilogue)
     s->fused_greedy = true;
     for (int b = 0; b < width; ++b) if (s->seq_host[b].active && s->seq_host[b].temperature != 0.0f) s->fused_greedy = false;
@@ -744,13 +734,13 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
     }
     if (set_aware) {      // the slot table goes up by home slot, so compacted, narrowed and mixed passes need nothing else
         memset(s->rs_host, 0, sizeof(int32_t) * (size_t)s->B);
-        for (int b = 0; b < batch; ++b) if (plan::slot_is_live(active, b)) s->rs_host[b] = set_of_slot[b];
+        for (int b = 0; b < batch; ++b) if (is_live(b)) s->rs_host[b] = set_of_slot[b];
         WH_HIP(hipMemcpyAsync(s->rs_dev + whi::kRsOffSlots, s->rs_host, sizeof(int32_t) * (size_t)s->B, hipMemcpyHostToDevice, s->st));
         s->rs_args.own_logit = (rules & plan::kRulesPassOwnLogit) ? s->lr_dev : nullptr;
         s->rs_args.own_phrase = (rules & plan::kRulesPassOwnPhrase) ? s->pr_dev : nullptr;
         s->rs_passes += 1;
     }
-    s->pass_rules = rules;
+    s->pass.rules = rules;
     // ---- token alternatives (wh_session_set_token_alternatives; NO REFERENCE BEHAVIOUR): the unfused sampler's recording instantiation.  The rows of
     // the home slots this pass decodes start from "nothing recorded"; a fallback rung so overwrites only the windows it decodes again
     if (s->token_alternatives > 0) {
@@ -758,13 +748,14 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
         r = whi::alternatives_arm(s, batch, active);
         if (r) return r;
     }
+    // ---- 4. run: the states go up and the token loop runs
     WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * width, hipMemcpyHostToDevice, s->st));
     launch_rules_init(s->cfg_dev, s->seq, width, s->st, mix != nullptr);
     int loop_count = 0;       // a slot finishes at its class's count (SamplerCfg.loop_count); the host loop runs to the largest
     for (int c = 0; c < n_cls; ++c) loop_count = std::max(loop_count, std::min(cls_opt(c)->sample_length, kMaxTok - 1));
     s->skip_special_in_progress = opt->skip_special_tokens != 0;
     s->special_begin_in_progress = st->special_token_begin;
-    // ---- in-pass compaction (wh_session_set_inpass_compaction 1): the pass may narrow between step graphs as its slots finish (run_token_loop)
+    // in-pass compaction (wh_session_set_inpass_compaction 1): the pass may narrow between step graphs as its slots finish (run_token_loop)
     PassLayout lay;
     if (s->inpass_compaction == 1) {
         if (!s->seq_snap) WH_HIP(s->mem.alloc_pinned(&s->seq_snap, (size_t)s->B));
@@ -775,56 +766,43 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
             lay.live[i] = s->seq_host[i].active;
         }
     }
-    // a pass that narrowed, back to home-slot terms on the device: seq_host holds the decoded windows' states by home slot; every other slot as a
-    // plain pass leaves it (initialised, inactive)
-    auto upload_home_layout = [&]() -> int {
-        for (int b = 0; b < batch; ++b) if (!(active ? active[b] != 0 : true)) init_slot(s->seq_host[b], b, false);
-        s->pass_mapped = false; s->pass_owner = false;
+    // ---- 5. a pass that narrowed or a compacted one, back to home-slot terms on the host and on the device: the decoded windows' final states at their home slots, every other
+    // slot as a plain pass leaves it (initialised, inactive).  A pass that narrowed ends with seq_host by home slot (run_token_loop); a compacted one that did not, with its live slots in front
+    auto home_layout = [&]() -> int {
+        std::vector<SeqState> fin(s->seq_host, s->seq_host + (lay.switches == 0 ? n_live : 0));
+        for (int b = 0; b < batch; ++b) if (lay.switches == 0 || !is_live(b)) init_slot(s->seq_host[b], b, false);
+        for (size_t i = 0; i < fin.size(); ++i) s->seq_host[s->slot_home_host[i]] = fin[i];
+        s->pass.mapped = false; s->pass.owner = false;
         WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * batch, hipMemcpyHostToDevice, s->st));
         WH_HIP(hipStreamSynchronize(s->st));
         return WH_OK;
     };
     r = run_token_loop(s, width, std::max(loop_count, 0), s->inpass_compaction == 1 ? &lay : nullptr);
-    if (r) {
+    if (r && lay.switches > 0) {
         // an error (a cancel, a failed capture) behind a switch: the device states lie in the compact layout with the finished windows parked.  Put
         // them back by home slot as far as the device still answers, so that a step-API or wh_measure_kernels call that follows sees every slot in
         // its place; the error of the loop is the one reported.
-        if (lay.switches > 0) {
-            const std::string msg = wh_last_error();
-            launch_seq_park(s->seq, s->seq_home, s->slot_home_dev, lay.width, s->B, s->st);
-            if (hipMemcpyAsync(s->seq_host, s->seq_home, sizeof(SeqState) * batch, hipMemcpyDeviceToHost, s->st) == hipSuccess &&
-                hipStreamSynchronize(s->st) == hipSuccess) (void)upload_home_layout();
-            set_error(r, "%s", msg.c_str());
-        }
-        return r;
+        const std::string msg = wh_last_error();
+        launch_seq_park(s->seq, s->seq_home, s->slot_home_dev, lay.width, s->B, s->st);
+        if (hipMemcpyAsync(s->seq_host, s->seq_home, sizeof(SeqState) * batch, hipMemcpyDeviceToHost, s->st) == hipSuccess &&
+            hipStreamSynchronize(s->st) == hipSuccess) (void)home_layout();
+        set_error(r, "%s", msg.c_str());
     }
-    if (lay.switches > 0) {
-        int r2 = upload_home_layout();
-        if (r2) return r2;
-    } else if (cp.compact) {
-        // back to home-slot terms, on the host and on the device: the live slots' final states at their home slots, every other slot as
-        // an uncompacted pass leaves it (initialised, inactive)
-        const int32_t* home = s->slot_home_host;
-        std::vector<SeqState> fin(s->seq_host, s->seq_host + n_live);
-        for (int b = 0; b < batch; ++b) init_slot(s->seq_host[b], b, false);
-        for (int i = 0; i < n_live; ++i) s->seq_host[home[i]] = fin[i];
-        s->pass_mapped = false;
-        WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * batch, hipMemcpyHostToDevice, s->st));
-        WH_HIP(hipStreamSynchronize(s->st));
-    }
+    if (r) return r;
+    if (lay.switches > 0 || cp.compact) { r = home_layout(); if (r) return r; }
+    // ---- 6. collect what the modes recorded, and every decoded slot's result
     const bool ns_on = !ns_opts.empty();
     if (ns_on) { r = whi::nospeech_collect(s, batch, ns_opts.data()); if (r) return r; }
-    const bool alt_on = s->pass_alt > 0;
+    const bool alt_on = s->pass.alt > 0;
     if (alt_on) { r = whi::alternatives_collect(s, batch, active); if (r) return r; }
     for (int b = 0; b < batch; ++b) {
         if (!s->seq_host[b].active) { memset(&out[b], 0, sizeof(out[b])); continue; }
-        const wh_decoding_options* fo = (mix && mix->slot_opts && mix->slot_opts[b]) ? mix->slot_opts[b] : cls_opt(cls_of(b));      // the audio's own thresholds
-        whi::finalize_decoding_result(s->seq_host[b], fo, st, s->seq_host[b].temperature, &out[b], ns_on ? whi::nospeech_prob(s, b) : 0.0f);
+        whi::finalize_decoding_result(s->seq_host[b], finalise_options(b), st, s->seq_host[b].temperature, &out[b], ns_on ? whi::nospeech_prob(s, b) : 0.0f);
         if (alt_on) {      // result token i is the list's token start + i (finalize_decoding_result's slice): where wh_decode_alternatives finds its row
             const SeqState& q = s->seq_host[b];
             int start = 0;
             for (int i = 0; i < q.n_tokens; ++i) if (q.tokens[i] == st->start_of_transcript_token) { start = i; break; }
-            s->alt_start[(size_t)b] = start; s->alt_count[(size_t)b] = out[b].n_tokens; s->alt_nrec[(size_t)b] = s->pass_alt;
+            s->alt_start[(size_t)b] = start; s->alt_count[(size_t)b] = out[b].n_tokens; s->alt_nrec[(size_t)b] = s->pass.alt;
             for (int i = q.prompt_len; i < q.n_tokens; ++i) s->alt_positions += s->alt_ids_host[((size_t)b * plan::kAltPositions + i) * plan::kMaxAlternatives] != plan::kAltNoId;
         }
     }
@@ -869,8 +847,7 @@ extern "C" int wh_decode_text_custom(wh_session* s, const wh_decoding_options* o
     if (n_prompt < 1 || n_prompt >= kMaxTok) return set_error(WH_ERR_PREFILL_FAILED, "wh_decode_text_custom: prompt length %d out of range [1,%d)", n_prompt, kMaxTok);
     if (n_filters < 0 || (n_filters > 0 && !filters)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text_custom: %d filters but no filter table", n_filters);
     const int V = s->m->dims.n_vocab;
-    for (int i = 0; i < n_prompt; ++i)
-        if (prompt[i] < 0 || prompt[i] >= V) return set_error(WH_ERR_PREFILL_FAILED, "wh_decode_text_custom: prompt token %d out of vocabulary", prompt[i]);
+    if (int r = whi::check_prompt_tokens("wh_decode_text_custom", prompt, n_prompt, V, WH_ERR_PREFILL_FAILED)) return r;
     try {
         int r = wh_reset_decoder_inputs(s, 1);
         if (r) return r;
@@ -991,7 +968,7 @@ extern "C" int wh_no_speech_probs(wh_session* s, int batch, const wh_special_tok
     WH_HIP(hipMemcpyAsync(s->ns_seq_keep, s->seq, sizeof(SeqState) * batch, hipMemcpyDeviceToDevice, s->st));
     WH_HIP(hipMemcpy2DAsync(s->ns_kv_keep, row_bytes, s->self_k, pitch, row_bytes, kv_rows, hipMemcpyDeviceToDevice, s->st));
     WH_HIP(hipMemcpy2DAsync(s->ns_kv_keep + kv_rows * kHeadDim, row_bytes, s->self_v, pitch, row_bytes, kv_rows, hipMemcpyDeviceToDevice, s->st));
-    struct Scope { wh_session* s; ~Scope() { s->pass_ns = plan::NoSpeechRange{-1, -1}; } } scope{s};
+    whi::PassGuard guard{s};
     const std::vector<int> pos((size_t)batch, 0);
     int r = whi::nospeech_arm(s, batch, pos.data(), nullptr, st->no_speech_token, 1);
     if (r) return r;
@@ -1087,7 +1064,7 @@ extern "C" int wh_debug_token_alternatives_apply(wh_session* s, const float* row
         memset(&q, 0, sizeof(q));
         q.active = 1; q.rng_lane = i; q.temperature = temperatures ? temperatures[i] : 0.0f;
     }
-    struct Scope { wh_session* s; ~Scope() { s->pass_alt = 0; } } scope{s};
+    whi::PassGuard guard{s};
     r = whi::alternatives_arm(s, n_rows, nullptr);
     if (r) return r;
     s->alt_passes -= 1;                                   // (not a decode pass)
@@ -1488,21 +1465,15 @@ static int spec_pass_impl(wh_session* s, int n_audio, int K, const wh_decoding_o
     r = whi::upload_sampler_cfg(s, opt, st, 0, n_prompt, 0, opt->seed);
     if (r) return r;
     if (opt->word_timestamps && s->m->n_align > 0) { r = whi::ensure_align(s); if (r) return r; }
-    // every exit: the next caller of decode_buffers sees a plain session
-    struct Scope { wh_session* s; ~Scope() { s->pass_mapped = false; s->pass_owner = false; s->pass_mixed = false; s->pass_spw = 1; } } scope{s};
+    whi::PassGuard guard{s};      // every exit: the next caller of decode_buffers sees a plain session
     s->align_enabled = opt->word_timestamps && s->align;
     s->fused_greedy = !knob::now<knob::WH_NO_FUSED_SAMPLER>();
-    s->pass_mixed = false; s->pass_owner = false;
     const int limit = std::max(std::min(opt->sample_length, kMaxTok - 1), 0);      // SamplerCfg.loop_count: positions 0 .. limit - 1 exist
-    int lang_pos = -1;
-    if (language_tokens && wh_is_model_multilingual(s->m))
-        for (int i = 0; i + 1 < n_prompt; ++i) if (prompt[i] == st->start_of_transcript_token) { lang_pos = i + 1; break; }
+    const int lang_pos = whi::prompt_language_position(prompt, n_prompt, st->start_of_transcript_token, language_tokens && wh_is_model_multilingual(s->m));
     for (int a = 0; a < n_audio; ++a) {                                            // the master states, as decode_text_impl starts a slot
         SeqState& q = s->seq_host[a];
-        memset(&q, 0, sizeof(q));
-        for (int i = 0; i < n_prompt; ++i) q.tokens[i] = prompt[i];
-        if (lang_pos >= 0 && language_tokens[a] >= 0 && language_tokens[a] < V) q.tokens[lang_pos] = language_tokens[a];
-        q.n_tokens = n_prompt; q.token_index = 0; q.next_token = q.tokens[0]; q.prompt_len = n_prompt; q.active = 1; q.temperature = 0.0f; q.rng_lane = a;
+        whi::seq_init_prompt(q, prompt, n_prompt, lang_pos, lang_pos >= 0 ? language_tokens[a] : -1, V);
+        q.active = 1; q.temperature = 0.0f; q.rng_lane = a;
     }
     WH_HIP(hipMemcpyAsync(s->spec_master, s->seq_host, sizeof(SeqState) * (size_t)n_audio, hipMemcpyHostToDevice, s->st));
     launch_rules_init(s->cfg_dev, s->spec_master, n_audio, s->st);
@@ -1529,7 +1500,7 @@ static int spec_pass_impl(wh_session* s, int n_audio, int K, const wh_decoding_o
         for (int a = 0; a < n_audio; ++a) if (live[a]) top = std::max(top, p0[a] + pr.upper_k(a, p0[a], K, n_prompt, limit, st->end_token));
         WH_HIP(hipMemcpyAsync(d_dev, d, sizeof(SpecDesc) * (size_t)n_audio, hipMemcpyHostToDevice, s->st));
         launch_spec_arm(s->cfg_dev, s->spec_master, d_dev, dev_src, s->seq, s->spec_owner, s->slot_home_dev, s->spec_io, n_audio, K, s->st);
-        s->pass_mapped = true; s->pass_spw = spw;
+        s->pass.mapped = true; s->pass.spw = spw;
         DecodeBuffers db = whi::decode_buffers(s, width, std::min(top, kMaxTok - 1));
         db.self_owner = s->spec_owner; db.owner_slots = B;
         launch_decoder_step(db, s->cfg_dev, s->suppress_dev, true, s->st);
@@ -1580,8 +1551,7 @@ static int spec_check_args(const char* who, int n_audio, int K, const wh_decodin
     return WH_OK;
 }
 static int spec_check_tokens(const char* who, int n_audio, const int32_t* prompt, int n_prompt, const int32_t* const* proposals, const int32_t* n_proposals, int n_vocab) {
-    for (int i = 0; i < n_prompt; ++i)
-        if (prompt[i] < 0 || prompt[i] >= n_vocab) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: prompt token %d out of vocabulary", who, prompt[i]);
+    if (int r = whi::check_prompt_tokens(who, prompt, n_prompt, n_vocab, WH_ERR_INVALID_ARGUMENT)) return r;
     if (!proposals) return WH_OK;
     if (!n_proposals) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: proposals without their counts", who);
     for (int a = 0; a < n_audio; ++a) {
@@ -1641,7 +1611,7 @@ extern "C" int wh_decode_text_speculative(wh_session* s, wh_session* draft, int 
     int r = whi::upload_sampler_cfg(draft, opt, st, 0, n_prompt, 0, opt->seed);
     if (r) return r;
     WH_HIP(hipStreamSynchronize(draft->st));
-    struct DraftScope { wh_session* d; bool fused, align; ~DraftScope() { d->fused_greedy = fused; d->align_enabled = align; } } draft_scope{draft, draft->fused_greedy, draft->align_enabled};
+    whi::PassGuard draft_guard{draft, true};      // for the two switches only: nothing writes draft->pass, its reset has no effect
     draft->fused_greedy = !knob::now<knob::WH_NO_FUSED_SAMPLER>(); draft->align_enabled = false;
     DraftProposer pr;
     pr.draft = draft; pr.resume.assign((size_t)n_audio, 0);
@@ -2314,16 +2284,14 @@ static int forced_pass_impl(wh_session* s, int n_audio, const int32_t* const* to
     const int B = s->B, V = s->m->dims.n_vocab;
     int r = forced_ensure(s);
     if (r) return r;
-    // every exit: the next caller of decode_buffers sees a plain session, with the sampler / alignment switches the last decode left
-    struct Scope { wh_session* s; bool fused, align; ~Scope() { s->pass_mapped = false; s->pass_owner = false; s->pass_mixed = false; s->fused_greedy = fused; s->align_enabled = align; } }
-        scope{s, s->fused_greedy, s->align_enabled};
+    whi::PassGuard guard{s, true};      // every exit: the next caller of decode_buffers sees a plain session, with the sampler / alignment switches the last decode left
     if (record_alignment && s->m->n_align > 0) {
         r = whi::ensure_align(s);
         if (r) return r;
         WH_HIP(hipMemsetAsync(s->align, 0, (size_t)n_audio * kMaxTok * s->n_align_alloc * kCtx * sizeof(float), s->st));      // home slots 0 .. n_audio - 1
     }
     s->align_enabled = record_alignment && s->align;
-    s->fused_greedy = false; s->pass_mixed = false; s->pass_owner = false;
+    s->fused_greedy = false;
     const size_t cap = (size_t)B * (kMaxTok - 1);
     float* const lp_dev = s->forced_out;
     int* const best_dev = reinterpret_cast<int*>(s->forced_out + cap);
@@ -2345,7 +2313,7 @@ static int forced_pass_impl(wh_session* s, int n_audio, const int32_t* const* to
         WH_HIP(hipMemcpyAsync(s->forced_desc_dev + base, d, sizeof(ForcedDesc) * (size_t)n, hipMemcpyHostToDevice, s->st));
         launch_forced_arm(s->forced_desc_dev + base, s->seq, s->forced_owner, s->slot_home_dev, n, B, V, s->st);
         const plan::CompactPassPlan cp = plan::compact_pass_plan(n, B, B, spw0);      // slots per absorbed-attention workgroup: the value of the ladder rung that holds n slots (results do not depend on it)
-        s->pass_mapped = true; s->pass_spw = cp.compact ? cp.spw : spw0;
+        s->pass.mapped = true; s->pass.spw = cp.compact ? cp.spw : spw0;
         DecodeBuffers db = whi::decode_buffers(s, n, l.self_rows - 1);
         db.self_owner = s->forced_owner; db.owner_slots = B;
         launch_decoder_step(db, nullptr, nullptr, false, s->st);

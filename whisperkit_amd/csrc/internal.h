@@ -5,7 +5,6 @@
 #include <new>
 #include <stdexcept>
 #include <string>
-#include <tuple>
 #include <unordered_map>
 #include <vector>
 
@@ -14,6 +13,7 @@
 #include "kernels.h"
 #include "logit_rules_plan.h"
 #include "nospeech_plan.h"
+#include "pass_state.h"
 #include "phrase_rules_plan.h"
 #include "rule_sets_plan.h"
 #include "text.h"
@@ -83,22 +83,6 @@ struct wh_model {
     std::atomic<int> n_sessions{0};
 };
 
-// step graphs are keyed by everything their captured launches bake in
-struct WhGraphKey {
-    int batch, align, fused, n_align, self_rows, gate;
-    int mapped, spw;      // compacted pass (slot table + mapped cross-attention instantiations) and its slots per absorbed-attention workgroup; 0, 0 otherwise
-    int owner;            // 1: a pass that narrowed in flight - the self-attention reads the session's row -> owner table (dec_self_attn_owner_kernel); 0 otherwise
-    int mixed;            // 1: a mixed pass (option_mix.h) - the logits epilogue and the samplers run their *_mixed instantiations; 0 otherwise
-    int ns_mask;          // bit i: step i of the graph stores its logits rows and runs nospeech_kernel (nospeech_plan.h nospeech_step_mask); 0 with the mode off
-    int rules;            // the pass's rules mask (rule_sets_plan.h rules_pass_mask): which of logit_rules_kernel / phrase_rules_kernel every step runs before the
-                          // (unfused) sampler, or - a set-aware pass - rule_sets_kernel with the session's own tables it is handed (the launch bakes those two pointers or null); 0 with no rules
-    int alternatives;     // 0, or the n of a pass that records token alternatives (alternatives_plan.h): the unfused sampler's recording instantiation with n baked in
-    bool operator<(const WhGraphKey& o) const {
-        return std::tie(batch, align, fused, n_align, self_rows, gate, mapped, spw, owner, mixed, ns_mask, rules, alternatives) <
-               std::tie(o.batch, o.align, o.fused, o.n_align, o.self_rows, o.gate, o.mapped, o.spw, o.owner, o.mixed, o.ns_mask, o.rules, o.alternatives);
-    }
-};
-
 struct wh_session {
     DevMem mem;                       // owns every device and pinned allocation below, the lazily allocated ones included
     wh_model* m = nullptr;
@@ -127,6 +111,7 @@ struct wh_session {
     int* dtw_dev = nullptr;                // rows [B] | lengths [B] | text_idx [B][kDtwPathCap] | time_idx [B][kDtwPathCap], allocated on first use
     int32_t* dtw_host = nullptr;           // pinned mirror of lengths | text_idx | time_idx
     long long dtw_launches = 0, align_d2h_bytes = 0;   // wh_session_word_alignment_stats
+    PassState pass;                       // what the running pass switches on (pass_state.h); written by the pass kinds of host.hip / beam.hip under a PassGuard, plain otherwise
     std::map<WhGraphKey, hipGraphExec_t> graphs;   // captured 8-step decode graphs of THIS session (no process-wide state)
     std::map<WhGraphKey, unsigned long long> graph_use;   // last use (a counter) per graph: the cache is capped, least recently used configuration first
     unsigned long long graph_tick = 0;
@@ -142,12 +127,11 @@ struct wh_session {
     int* suppress_dev = nullptr;
     unsigned char* sup_mask_dev = nullptr;   // SuppressTokensFilter byte masks (fused greedy sampler)
     // option mixing (wh_session_set_option_mixing): 0 = off, 1 = wh_transcribe_batch_with_options groups its audios by batch key (option_mix_plan) and
-    // decodes a group's classes in one pass.  pass_mixed holds only while decode_text_impl runs a pass with classes (host.hip MixClasses; wh_decode_text_mixed works whatever the mode).
+    // decodes a group's classes in one pass.  pass.mixed is set by a pass with classes (host.hip MixClasses; wh_decode_text_mixed works whatever the mode).
     int option_mixing = 0;
-    bool pass_mixed = false;
     long long mix_groups_run = 0, mix_mixed_passes = 0, mix_max_classes = 0;   // wh_session_option_mixing_stats: groups that ran mixed, passes with classes, largest class count
     float* stats = nullptr;                  // [B][kStatBlocks][8]
-    bool fused_greedy = false;
+    bool fused_greedy = false;               // NOT pass state (nor is align_enabled below): the step API (wh_predict_logits, wh_measure_kernels) reads what the last decode left
     int *tok_out_dev = nullptr; float* lp_out_dev = nullptr;
     float* scratch_logits = nullptr;       // [V] for the filter / sample KAT entry points
     // beam search (wh_decode_text_beam, allocated on first use): row -> owning slot table of the self-attention cache, top-k outputs
@@ -164,10 +148,9 @@ struct wh_session {
     long long beam_rank_launches = 0, beam_loop_syncs = 0;   // wh_session_beam_stats
     // compacted fallback passes (wh_session_set_fallback_compaction): 0 = off, 1 = a decode pass with a sparse `active` mask runs at the
     // width launch_plan.h compact_pass_plan gives.  The table is allocated by the first compacted pass: slot_home_dev [B] on the device,
-    // slot_home_host [2][B] pinned (home slots | live flags).  pass_mapped / pass_spw hold only while decode_text_impl runs such a pass.
+    // slot_home_host [2][B] pinned (home slots | live flags).  pass.mapped / pass.spw are set by such a pass (and by the forced and speculative passes, whose virtual slots read the table).
     int fallback_compaction = 0;
     int32_t *slot_home_dev = nullptr, *slot_home_host = nullptr;
-    bool pass_mapped = false; int pass_spw = 1;
     wh::Xabs xabs_pass{};                 // the session's xabs with the pass's slots per workgroup
     long long decode_passes = 0, compacted_passes = 0, slot_steps = 0;   // wh_session_decode_pass_stats
     // in-pass compaction (wh_session_set_inpass_compaction): 0 = off, 1 = a wh_decode_text* pass narrows between step graphs as its slots finish
@@ -175,11 +158,9 @@ struct wh_session {
     // with the option on: seq_home [B] (device, the decode states by home slot), seq_snap [B] (pinned, the second snapshot buffer of the run-ahead
     // loop), inpass_dev = live flags [B] | owner rows [B][kMaxTok] (device), inpass_stage = kInpassMaxSwitches regions of home [B] | live [B] |
     // owner rows [B][kMaxTok] (pinned: one region per switch of a pass, so the host never writes a region the stream has not consumed).
-    // pass_owner holds only while decode_text_impl runs a pass that has narrowed.
     int inpass_compaction = 0;
     wh::SeqState *seq_home = nullptr, *seq_snap = nullptr;
     int32_t *inpass_dev = nullptr, *inpass_stage = nullptr;
-    bool pass_owner = false;
     long long inpass_switches = 0, inpass_slot_steps_saved = 0;          // wh_session_inpass_compaction_stats
     // forced-transcript pass (wh_score_tokens / wh_align_tokens_batch: host.hip forced_pass_impl, forced_plan.h, forced.hip).  Everything is allocated by
     // the first pass: forced_owner [B][kMaxTok] (device, the row -> owner rows of the virtual slots), forced_desc [B * (kMaxTok - 1)] (pinned staging:
@@ -202,20 +183,16 @@ struct wh_session {
     long long spec_passes = 0, spec_rounds = 0, spec_positions = 0, spec_accepted = 0;      // wh_session_speculative_stats
     // no-speech detection (wh_session_set_no_speech_detection: host.hip nospeech_arm, nospeech_plan.h, nospeech.hip): 0 = off, 1 = on, 2 = on + stop.  Everything is
     // allocated by the first pass that runs with the mode on: ns_dev = pos [B] | stop [B] (float) | prob [B] (float) | stopped [B] | cfg [2] (device, by home slot;
-    // what ns_args points into, at fixed addresses so that captured step graphs stay valid) and its pinned mirror ns_host.  pass_ns holds only while a pass
+    // what ns_args points into, at fixed addresses so that captured step graphs stay valid) and its pinned mirror ns_host.  pass.ns holds while a pass
     // runs whose steps lo .. hi carry the logits store and the kernel; (-1, -1) otherwise, and always with the mode off.
     int no_speech_detection = 0;
     int32_t *ns_dev = nullptr, *ns_host = nullptr;
     wh::NoSpeechArgs ns_args{};
-    wh::plan::NoSpeechRange pass_ns{-1, -1};
     wh::SeqState* ns_seq_keep = nullptr; f16* ns_kv_keep = nullptr;      // wh_no_speech_probs: the decode states and the cache rows 0 ([2][L][B][H][64]) the probe puts back
     long long ns_rows_scored = 0, ns_windows_over = 0, ns_windows_stopped = 0;      // wh_session_no_speech_stats
     // device rules (host.hip).  rs_sets[k]: the session's copy of rule set k, what the getters hand out.  Entry 0 is the session's own
     // set (wh_session_set_logit_rules / wh_session_set_phrase_rules: its two halves; defined / special_begin belong to the bank and stay unused there), entries
     // 1 .. 15 are the banked sets (wh_session_define_rule_set).  A half's arrays stay valid until the next setter call for that set.
-    // pass_rules: the rules mask (rule_sets_plan.h rules_pass_mask) of the pass decode_text_impl is running - the unfused sampler, with logit_rules_kernel /
-    // phrase_rules_kernel or, in a set-aware pass, rule_sets_kernel in front of it; 0 otherwise.  The graph key's `rules`, the *_step_args helpers below and
-    // decode_buffers read it.
     struct RuleSetCopy {
         bool defined = false;
         int special_begin = -1;                    // the special_token_begin word the device copy holds (-1: not known)
@@ -225,7 +202,6 @@ struct wh_session {
         std::vector<float> bias_values, biases;
     };
     RuleSetCopy rs_sets[wh::plan::kMaxRuleSets];
-    int pass_rules = 0;
     // device logit rules (wh_session_set_logit_rules: host.hip, logit_rules_plan.h, logit_rules.hip).  logit_rules_on: a set other than the neutral one is
     // installed.  lr_dev (device, kLogitRulesWords words at a fixed address, so that captured step graphs stay valid when values change) and its pinned
     // mirror lr_host are allocated by the first setter that installs rules.
@@ -252,12 +228,11 @@ struct wh_session {
     // sampler_kernel).  token_alternatives: 0 = off, n = 1 .. 8.  Everything is allocated by the first setter call that turns the mode on: alt_ids (device, int32
     // [B][224][8]) and alt_f32 (device, float: log-probabilities [B][224][8] | entropies [B][224]), both by home slot at fixed addresses so that captured step
     // graphs stay valid, and their pinned mirrors.  alt_start / alt_count / alt_nrec: per home slot, the list index of result token 0, the result's token count and the n of the
-    // last pass that decoded the slot (wh_decode_alternatives).  pass_alt holds only while decode_text_impl runs a pass under the mode.
+    // last pass that decoded the slot (wh_decode_alternatives).  pass.alt is set by a pass under the mode.
     int token_alternatives = 0;
     int32_t *alt_ids = nullptr, *alt_ids_host = nullptr;
     float *alt_f32 = nullptr, *alt_f32_host = nullptr;
     std::vector<int32_t> alt_start, alt_count, alt_nrec;
-    int pass_alt = 0;
     long long alt_passes = 0, alt_positions = 0, alt_d2h_bytes = 0;      // wh_session_token_alternatives_stats
     hipEvent_t ev[8]{};
     bool align_enabled = false;
@@ -309,6 +284,13 @@ int vad_chunks_device(wh_device_audio* a, int max_chunk, const wh_decoding_optio
 #define WH_CATCH(name) } catch (const std::bad_alloc&) { return whi::set_error(WH_ERR_OUT_OF_MEMORY, "%s: out of host memory", name); } \
                          catch (const std::exception& e_) { return whi::set_error(WH_ERR_INVALID_ARGUMENT, "%s: %s", name, e_.what()); }
 
+// Every pass kind holds one from before it first writes s->pass to its last exit: s->pass is plain at both ends.  restore_switches: also put back the sampler /
+// alignment switches the last decode left (the forced pass and the speculative pass's draft session, which the step API must not notice); fused / align are unused otherwise
+struct PassGuard {
+    wh_session* s; bool restore_switches, fused = s->fused_greedy, align = s->align_enabled;
+    explicit PassGuard(wh_session* s_, bool restore_switches_ = false) : s(s_), restore_switches(restore_switches_) { s->pass = PassState{}; }
+    ~PassGuard() { s->pass = PassState{}; if (restore_switches) { s->fused_greedy = fused; s->align_enabled = align; } }
+};
 wh::DecodeBuffers decode_buffers(wh_session* s, int batch, int max_position = wh::kMaxTok - 1);
 void drop_session_graphs(wh_session* s);
 int ensure_align(wh_session* s);          // (re)allocate the raw alignment-head score buffer for the model's current head set
@@ -321,19 +303,19 @@ void transcription_truncate_segments(wh_transcription* t, int n_keep);     // re
 void finalize_decoding_result(const wh::SeqState& sq, const wh_decoding_options* opt, const wh_special_tokens* st,
                               float temperature, wh_decoding_result* out, float no_speech_prob = 0.0f);
 // no-speech detection (host.hip): allocate the tables; arm them for a pass over the home slots 0 .. n - 1 (pos / stop by home slot, null stop: never) and set
-// pass_ns; read prob | stopped back behind the pass (the stream is drained) and count.  prob of home slot b: nospeech_prob(s, b)
+// pass.ns; read prob | stopped back behind the pass (the stream is drained) and count.  prob of home slot b: nospeech_prob(s, b)
 int nospeech_arm(wh_session* s, int n, const int* pos, const float* stop, int token, int lane_div);
 int nospeech_collect(wh_session* s, int n, const wh_decoding_options* const* opts);
 inline float nospeech_prob(const wh_session* s, int b) { float v; memcpy(&v, s->ns_host + 2 * (size_t)s->B + b, sizeof(v)); return v; }
-inline const wh::NoSpeechArgs* nospeech_step_args(const wh_session* s, int step) { return wh::plan::nospeech_step_in_range(step, s->pass_ns) ? &s->ns_args : nullptr; }
-// token alternatives (host.hip): reset the rows of the live home slots among 0 .. n - 1 and set pass_alt; behind the pass (the stream is drained) bring those rows
+inline const wh::NoSpeechArgs* nospeech_step_args(const wh_session* s, int step) { return wh::plan::nospeech_step_in_range(step, s->pass.ns) ? &s->ns_args : nullptr; }
+// token alternatives (host.hip): reset the rows of the live home slots among 0 .. n - 1 and set pass.alt; behind the pass (the stream is drained) bring those rows
 // down into the pinned mirrors and count.  The rows of home slot b: alternatives_rows
 int alternatives_arm(wh_session* s, int n, const int32_t* active);
 int alternatives_collect(wh_session* s, int n, const int32_t* active);
 // device logit rules: the rule set a step of the running pass hands to launch_decoder_step, or null (no rules set, or a pass that does not run them)
-inline const int* logit_rules_step_args(const wh_session* s) { return (s->pass_rules & wh::plan::kRulesPassLogitKernel) ? s->lr_dev : nullptr; }
+inline const int* logit_rules_step_args(const wh_session* s) { return (s->pass.rules & wh::plan::kRulesPassLogitKernel) ? s->lr_dev : nullptr; }
 // device phrase rules: likewise
-inline const wh::PhraseRulesArgs* phrase_rules_step_args(const wh_session* s) { return (s->pass_rules & wh::plan::kRulesPassPhraseKernel) ? &s->pr_args : nullptr; }
+inline const wh::PhraseRulesArgs* phrase_rules_step_args(const wh_session* s) { return (s->pass.rules & wh::plan::kRulesPassPhraseKernel) ? &s->pr_args : nullptr; }
 // per-audio rule sets: does any of the home slots 0 .. n - 1 name a set other than 0?  (the passes that do not run rule sets refuse such a call)
 inline bool rule_sets_assigned(const wh_session* s, int n) {
     for (int b = 0; b < n && b < (int)s->rs_slot.size(); ++b) if (s->rs_slot[(size_t)b] != 0) return true;
