@@ -476,6 +476,49 @@ int wh_decode_text_mixed(wh_session* s, int batch, const wh_decoding_options* op
                          const int32_t* class_of_slot /* [batch] */, const wh_special_tokens* st, const int32_t* const* prompts /* [n_classes] */,
                          const int32_t* n_prompts /* [n_classes] */, const int32_t* language_tokens /* [batch] or NULL */, const float* temperatures,
                          const int32_t* active, uint64_t seed, wh_decoding_result* out /* [batch] */);
+/* ---- per-slot prompts and previous-text conditioning ----
+ * wh_decode_text_mixed with the prompt per SLOT instead of per class: slot b decodes under opts[class_of_slot[b]] with ITS prompt prompts[b]
+ * (n_prompts[b] tokens).  There is no limit on the distinct prompts of a pass other than the session's slots; the class keeps everything
+ * else (sampler configuration, suppress list and mask, sample_length, top_k).  The timestamp rules' sampleBegin, the language-token position
+ * (language_tokens replaces the token behind each slot's own <|startoftranscript|>) and the no-speech scoring position are the slot's own.
+ * A slot decodes to the bits it has in wh_decode_text with its prompt as the shared one (same slot, same seed).  Composes with everything
+ * wh_decode_text_mixed composes with: both compaction options, no-speech detection, logit / phrase rules and rule sets, token alternatives,
+ * device word alignment, the progress callback.  Arguments are validated as in wh_decode_text_mixed, before the session is looked at; a NULL
+ * prompts / n_prompts table or a NULL prompt of a slot that decodes (active NULL: every slot) is WH_ERR_INVALID_ARGUMENT; a prompt length
+ * outside [1, WH_MAX_TOKEN_CONTEXT) or an id outside the vocabulary is WH_ERR_PREFILL_FAILED. */
+int wh_decode_text_slot_prompts(wh_session* s, int batch, const wh_decoding_options* opts /* [n_classes] */, int n_classes,
+                                const int32_t* class_of_slot /* [batch] */, const wh_special_tokens* st, const int32_t* const* prompts /* [batch] */,
+                                const int32_t* n_prompts /* [batch] */, const int32_t* language_tokens /* [batch] or NULL */, const float* temperatures,
+                                const int32_t* active, uint64_t seed, wh_decoding_result* out /* [batch] */);
+/* Prompt mixing.  0 = off (default).  1 = on: it has an effect only while option mixing is on - prompt_tokens and prefix_tokens then leave
+ * the CLASS of wh_transcribe_batch_with_options: audios that differ in them alone share one class, each audio's prompt is built by
+ * wh_prefill_prompt from its own options and goes to its slot (wh_decode_text_slot_prompts' pass), so 256 audios with 256 prompts are one
+ * group instead of 16.  Everything else in the class definition is unchanged; audios with beam_size > 1 group as ever.  A prompt that does
+ * not fit fails ITS audio with WH_ERR_PREFILL_FAILED (wh_session_item_status / wh_session_item_error), not its group.  Results equal the off
+ * mode's (at T > 0: for windows that land in the same slots).
+ * Returns WH_ERR_INVALID_ARGUMENT for a NULL session or a mode other than 0 / 1; the getter returns the mode, -1 for NULL. */
+int wh_session_set_prompt_mixing(wh_session* s, int mode);
+int wh_session_prompt_mixing(const wh_session* s);
+/* Previous-text conditioning: NO REFERENCE BEHAVIOUR (the reference accumulates allTokens and never feeds them back); the semantics are
+ * openai/whisper transcribe.py's condition_on_previous_text / prompt_reset_on_temperature.  0 = off (default).  1 = on: TURNING IT ON CHANGES
+ * THE RESULTS OF MULTI-WINDOW AUDIOS.  Every audio of wh_transcribe* keeps a carry (csrc/prompt_carry_plan.h): it starts as the options'
+ * prompt_tokens; a window that added segments appends their tokens (after any window_postprocess truncation); a window whose kept result was
+ * decoded above reset_temperature empties it, the initial prompt included (openai's value is 0.5; NAN = never); a window without segments
+ * leaves it alone; only the last WH_MAX_TOKEN_CONTEXT / 2 - 1 ids below special_token_begin are kept.  The next window's prompt is
+ * wh_prefill_prompt of the audio's options with prompt_tokens = the carry (an empty carry: nil).  While on, every non-beam group that uses the
+ * prefill prompt decodes with per-slot prompts, whatever the option / prompt mixing modes; audios without use_prefill_prompt are unaffected;
+ * beam_size > 1 is WH_ERR_INVALID_ARGUMENT while the mode is on, whether or not the audio prefills; an attached draft is ignored.  Limit: the chunks of wh_transcribe_chunked
+ * are separate audios that decode side by side - nothing is carried between chunks.  wh_align_tokens, wh_decode_text_custom, guided and
+ * speculative decode are untouched.
+ * Returns WH_ERR_INVALID_ARGUMENT for a NULL session or a mode other than 0 / 1; the getter returns the mode (-1 for NULL) and, when
+ * reset_temperature is not NULL, the reset temperature. */
+int wh_session_set_previous_text(wh_session* s, int mode, float reset_temperature);
+int wh_session_previous_text(const wh_session* s, float* reset_temperature);
+/* Counters of the session since its creation: decode passes with per-slot prompts, the largest number of distinct prompts among the decoding
+ * slots of one such pass, the prompt positions those slots stepped through (the sum of their prompt lengths, per pass), windows that decoded
+ * under a non-empty carry (the options' own prompt_tokens included, counted once per window), and carry resets.  Any pointer may be NULL. */
+int wh_session_slot_prompt_stats(const wh_session* s, int64_t* passes, int64_t* max_distinct_prompts, int64_t* prompt_positions,
+                                 int64_t* windows_carried, int64_t* resets);
 /* ---- user-pluggable LogitsFiltering / TokenSampling (Core/Text/LogitsFilter.swift:8-10, Core/Text/TokenSampler.swift:8-11) ----
  * The reference runs `logitsFilters` (custom filters first, Core/TextDecoder.swift:857-899) and the `TokenSampling` object on the
  * host once per token (:641-652).  The fused device loop of wh_decode_text knows the four built-in filters and the greedy /

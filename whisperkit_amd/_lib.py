@@ -209,6 +209,12 @@ SYMBOLS = {
     "wh_session_option_mixing": (I, [VP]),
     "wh_session_option_mixing_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "wh_decode_text_mixed": (I, [VP, I, VP, I, VP, VP, VP, VP, VP, VP, VP, C.c_uint64, VP]),
+    "wh_decode_text_slot_prompts": (I, [VP, I, VP, I, VP, VP, VP, VP, VP, VP, VP, C.c_uint64, VP]),
+    "wh_session_set_prompt_mixing": (I, [VP, I]),
+    "wh_session_prompt_mixing": (I, [VP]),
+    "wh_session_set_previous_text": (I, [VP, I, C.c_float]),
+    "wh_session_previous_text": (I, [VP, C.POINTER(C.c_float)]),
+    "wh_session_slot_prompt_stats": (I, [VP] + [C.POINTER(C.c_int64)] * 5),
     "wh_session_set_beam_ranking": (I, [VP, I]),
     "wh_session_beam_ranking": (I, [VP]),
     "wh_session_beam_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -1222,6 +1222,67 @@ class Session:
                       None if lt is None else lt.ctypes.data, temps.ctypes.data, None if act is None else act.ctypes.data, seed, res)
         return self._with_alternatives([DecodingResult.from_c(r) for r in res[:batch]], act)
 
+    def decodeTextSlotPrompts(self, prompts: Sequence[Optional[Sequence[int]]], optionsList: Sequence[DecodingOptions], classOfSlot: Sequence[int],
+                              temperatures: Optional[Sequence[float]] = None, active: Optional[Sequence[int]] = None, seed: int = 0, specialTokens=None,
+                              languageTokens: Optional[Sequence[int]] = None) -> List[DecodingResult]:
+        """decodeTextMixed with the prompt per SLOT (wh_decode_text_slot_prompts): slot b decodes under optionsList[classOfSlot[b]] with ITS prompt
+        prompts[b] (None: a slot outside `active` may bring none).  Any number of distinct prompts; a slot decodes to the bits decodeText gives it
+        with its prompt as the shared one."""
+        st = specialTokens if specialTokens is not None else self.model.specialTokens
+        n, batch = len(optionsList), len(classOfSlot)
+        if len(prompts) != batch:
+            raise ValueError("decodeTextSlotPrompts: one prompt per slot")
+        cos = [o.to_c() for o in optionsList]
+        opts = (L.WhDecodingOptions * max(n, 1))(*cos)
+        ps = [None if p is None else np.ascontiguousarray(list(p), dtype=np.int32) for p in prompts]
+        pp = (C.c_void_p * max(batch, 1))(*[None if p is None else p.ctypes.data for p in ps])
+        npr = np.ascontiguousarray([0 if p is None else len(p) for p in ps], dtype=np.int32)
+        cls = np.ascontiguousarray(classOfSlot, dtype=np.int32)
+        temps = np.ascontiguousarray(temperatures if temperatures is not None else [optionsList[0].temperature] * batch, dtype=np.float32)
+        act = None if active is None else np.ascontiguousarray(active, dtype=np.int32)
+        lt = None if languageTokens is None else np.ascontiguousarray(languageTokens, dtype=np.int32)
+        res = (L.WhDecodingResult * max(batch, 1))()
+        self._guarded(self.lib.wh_decode_text_slot_prompts, self.handle, batch, opts, n, cls.ctypes.data, C.byref(st), pp, npr.ctypes.data,
+                      None if lt is None else lt.ctypes.data, temps.ctypes.data, None if act is None else act.ctypes.data, seed, res)
+        return self._with_alternatives([DecodingResult.from_c(r) for r in res[:batch]], act)
+
+    PROMPT_MIXINGS = {"off": 0, "on": 1}
+    PREVIOUS_TEXT_MODES = {"off": 0, "on": 1}
+
+    def setPromptMixing(self, mode: str):
+        """Whether, WHILE OPTION MIXING IS ON, promptTokens and prefixTokens leave the option class of transcribeWithOptions: "off" (default) - each
+        distinct prompt is a class, 16 to a group; "on" - every audio's prompt goes to its own slot, so audios that differ only in their prompts are
+        one class.  A prompt that does not fit fails its audio alone.  Results equal the off mode's."""
+        if mode not in self.PROMPT_MIXINGS:
+            raise ValueError(f"promptMixing {mode!r}: expected 'on' or 'off'")
+        _check(self.lib.wh_session_set_prompt_mixing(self.handle, self.PROMPT_MIXINGS[mode]))
+
+    def promptMixing(self) -> str:
+        return {0: "off", 1: "on"}[int(self.lib.wh_session_prompt_mixing(self.handle))]
+
+    def setPreviousTextConditioning(self, mode: str, resetTemperature: Optional[float] = 0.5):
+        """Previous-text conditioning of transcribe* (no reference behaviour; openai/whisper condition_on_previous_text): "off" (default), or "on" - every
+        audio carries the text of its decoded windows into the prompt of its next one (the last 111 text tokens), emptied behind a window that was kept
+        above resetTemperature (None: never).  TURNING IT ON CHANGES THE RESULTS OF MULTI-WINDOW AUDIOS.  Needs usePrefillPrompt; beamSize > 1 is
+        refused; nothing is carried between the chunks of transcribeChunked."""
+        if mode not in self.PREVIOUS_TEXT_MODES:
+            raise ValueError(f"previousTextConditioning {mode!r}: expected 'on' or 'off'")
+        reset = float("nan") if resetTemperature is None else float(resetTemperature)
+        _check(self.lib.wh_session_set_previous_text(self.handle, self.PREVIOUS_TEXT_MODES[mode], reset))
+
+    def previousTextConditioning(self) -> Tuple[str, Optional[float]]:
+        """(mode, resetTemperature or None)"""
+        t = C.c_float()
+        mode = int(self.lib.wh_session_previous_text(self.handle, C.byref(t)))
+        return {0: "off", 1: "on"}[mode], (None if t.value != t.value else float(t.value))
+
+    def slotPromptStats(self) -> Tuple[int, int, int, int, int]:
+        """(decode passes with per-slot prompts, largest number of distinct prompts in one of them, prompt positions their slots stepped through, windows
+        decoded under a non-empty carry, carry resets) since the session was created"""
+        v = [C.c_int64() for _ in range(5)]
+        _check(self.lib.wh_session_slot_prompt_stats(self.handle, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
     BEAM_RANKINGS = {"host": 0, "device": 1}
 
     def setBeamRanking(self, mode: str):

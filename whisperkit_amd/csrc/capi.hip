@@ -771,7 +771,7 @@ DecodeBuffers decode_buffers(wh_session* s, int batch, int max_position) {
     db.align = s->align_enabled ? s->align : nullptr; db.align_slot = m->align_slot_dev; db.n_align = s->n_align_alloc;
     db.d32 = &s->d32; db.x = s->d32.x; db.q = s->d32.q;
     if (s->use_xabs) { s->xabs.enc = s->enc16; db.xabs = &s->xabs; }
-    const PassState& p = s->pass; db.mixed = p.mixed ? 1 : 0;      // what the running pass switches on (pass_state.h)
+    const PassState& p = s->pass; db.mixed = p.mixed;      // what the running pass switches on (pass_state.h)
     if (p.mapped) {             // compacted pass (host.hip decode_text_impl)
         db.slot_home = s->slot_home_dev;
         if (s->use_xabs) { s->xabs_pass = s->xabs; s->xabs_pass.spw = p.spw; db.xabs = &s->xabs_pass; }
@@ -1000,6 +1000,35 @@ extern "C" int wh_session_option_mixing_stats(const wh_session* s, int64_t* grou
     if (groups_run) *groups_run = s->mix_groups_run;
     if (mixed_passes) *mixed_passes = s->mix_mixed_passes;
     if (max_classes_in_a_pass) *max_classes_in_a_pass = s->mix_max_classes;
+    return WH_OK;
+}
+// per-slot prompts (host.hip decode_text_impl, transcribe_jobs)
+extern "C" int wh_session_set_prompt_mixing(wh_session* s, int mode) {
+    if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_prompt_mixing: null session");
+    if (mode != 0 && mode != 1) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_prompt_mixing: mode %d (0 = off, 1 = on)", mode);
+    s->prompt_mixing = mode;
+    return WH_OK;
+}
+extern "C" int wh_session_prompt_mixing(const wh_session* s) { return s ? s->prompt_mixing : -1; }
+extern "C" int wh_session_set_previous_text(wh_session* s, int mode, float reset_temperature) {
+    if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_previous_text: null session");
+    if (!plan::previous_text_mode_valid(mode)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_previous_text: mode %d (0 = off, 1 = on)", mode);
+    s->previous_text = mode; s->previous_text_reset = reset_temperature;
+    return WH_OK;
+}
+extern "C" int wh_session_previous_text(const wh_session* s, float* reset_temperature) {
+    if (!s) return -1;
+    if (reset_temperature) *reset_temperature = s->previous_text_reset;
+    return s->previous_text;
+}
+extern "C" int wh_session_slot_prompt_stats(const wh_session* s, int64_t* passes, int64_t* max_distinct_prompts, int64_t* prompt_positions,
+                                            int64_t* windows_carried, int64_t* resets) {
+    if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_slot_prompt_stats: null session");
+    if (passes) *passes = s->sp_passes;
+    if (max_distinct_prompts) *max_distinct_prompts = s->sp_max_distinct;
+    if (prompt_positions) *prompt_positions = s->sp_positions;
+    if (windows_carried) *windows_carried = s->sp_windows_carried;
+    if (resets) *resets = s->sp_resets;
     return WH_OK;
 }
 extern "C" int wh_session_inpass_compaction_stats(const wh_session* s, int64_t* switches, int64_t* slot_steps_saved) {

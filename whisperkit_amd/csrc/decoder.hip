@@ -453,6 +453,14 @@ __device__ __forceinline__ float uniform01(unsigned long long seed, int counter)
 // log-softmax the token was drawn from and the entropy of that distribution, from the registers that hold the filtered, scaled row.  token_out / logprob_out are
 // the buffers by home slot (ids; log-probabilities with the entropies behind them), counter_override carries n and the buffers' slot count.  Again a value of an
 // existing parameter: <1, 2, 1, 0> (a plain pass), <1, 2, 2, 0> (a mixed pass) and <0, 2, 0, 0> (the kernel-alone entry point) are the only ones launched.
+// DO_ADVANCE == 3 (a per-slot-prompt pass): the mixed form, with the timestamp rules' sampleBegin taken from the slot's own prompt_len
+// (slot_prompt_cfg) - the class entry's initial_prompt_index is not read.  <1, 1, 3, 0> and <1, 2, 3, 0> are the ones launched.
+// the SamplerCfg of a slot that brings its own prompt: its class's entry with the slot's prompt length as the timestamp rules' sampleBegin
+__device__ __forceinline__ SamplerCfg slot_prompt_cfg(const SamplerCfg& cls_cfg, const SeqState* sq) {
+    SamplerCfg c = cls_cfg;
+    c.initial_prompt_index = sq->prompt_len;
+    return c;
+}
 template <int DO_FILTER, int DO_SAMPLE, int DO_ADVANCE, int WRITE_BACK, int TOPK = 0>
 __global__ __launch_bounds__(SAMP_T) void sampler_kernel(const SamplerCfg* __restrict__ cfgp, const int* __restrict__ suppress,
                                                         SeqState* __restrict__ seqs, float* __restrict__ logits_all,
@@ -462,8 +470,9 @@ __global__ __launch_bounds__(SAMP_T) void sampler_kernel(const SamplerCfg* __res
     const int b = blockIdx.x, tid = threadIdx.x;
     SeqState* sq = seqs + b;
     if ((DO_ADVANCE || TOPK) && !slot_live(sq)) return;
-    constexpr bool kMix = DO_ADVANCE == 2;
+    constexpr bool kMix = DO_ADVANCE >= 2;
     if constexpr (kMix) { const int cls = seq_class(sq->rng_lane); cfgp += cls; suppress += cls * kMaxSuppress; }
+    constexpr bool kSlotPrompt = DO_ADVANCE == 3;
     const SamplerCfg cfg = *cfgp;
     const int V = cfg.n_vocab;
     float* logits = logits_all + (size_t)b * V;
@@ -474,7 +483,11 @@ __global__ __launch_bounds__(SAMP_T) void sampler_kernel(const SamplerCfg* __res
     // sh_i: 0 blank_active, 1 ts_active, 2 r1_lo, 3 r1_hi, 4 r2_lo, 5 r2_hi
     if (tid == 0) {
         int r[6] = {0, 0, 0, 0, 0, 0};
-        if (DO_FILTER) compute_filter_rules(cfg, sq, n_tok, V, r);
+        if constexpr (kSlotPrompt) {
+            if (DO_FILTER) compute_filter_rules(slot_prompt_cfg(cfg, sq), sq, n_tok, V, r);
+        } else {
+            if (DO_FILTER) compute_filter_rules(cfg, sq, n_tok, V, r);
+        }
 #pragma unroll
         for (int i = 0; i < 6; ++i) sh_i[i] = r[i];
     }
@@ -670,7 +683,11 @@ __global__ __launch_bounds__(SAMP_T) void sampler_kernel(const SamplerCfg* __res
     }
     if (tid == 0) {
         if (DO_SAMPLE != 2 && token_out) { token_out[b] = tok; logprob_out[b] = lp; }
-        if (DO_ADVANCE) advance_decode_state(cfg, sq, tok, lp, n_tok);
+        if constexpr (kSlotPrompt) {
+            advance_decode_state(slot_prompt_cfg(cfg, sq), sq, tok, lp, n_tok);
+        } else {
+            if (DO_ADVANCE) advance_decode_state(cfg, sq, tok, lp, n_tok);
+        }
     }
 }
 
@@ -697,6 +714,11 @@ __device__ __forceinline__ void stat_wave_reduce(SoftStat& a) {
 #include "sampler_final.inc"
 #undef SAMPLER_FINAL_NAME
 #undef SAMPLER_FINAL_MIXED
+#define SAMPLER_FINAL_NAME sampler_final_slot_prompt_kernel
+#define SAMPLER_FINAL_MIXED 2
+#include "sampler_final.inc"
+#undef SAMPLER_FINAL_NAME
+#undef SAMPLER_FINAL_MIXED
 
 __global__ void rules_init_kernel(const SamplerCfg* __restrict__ cfgp, SeqState* __restrict__ seqs) {
     if (threadIdx.x != 0) return;
@@ -710,8 +732,15 @@ __global__ void rules_init_mixed_kernel(const SamplerCfg* __restrict__ cfgp, Seq
     const SamplerCfg cfg = cfgp[seq_class(sq->rng_lane)];
     compute_filter_rules(cfg, sq, sq->n_tokens, cfg.n_vocab, sq->f_rules);
 }
-void launch_rules_init(const SamplerCfg* cfg_dev, SeqState* seq, int batch, hipStream_t st, bool mixed) {
-    if (mixed) rules_init_mixed_kernel<<<batch, 64, 0, st>>>(cfg_dev, seq);
+__global__ void rules_init_slot_prompt_kernel(const SamplerCfg* __restrict__ cfgp, SeqState* __restrict__ seqs) {      // the mixed form, sampleBegin from the slot's own prompt
+    if (threadIdx.x != 0) return;
+    SeqState* sq = seqs + blockIdx.x;
+    const SamplerCfg cfg = slot_prompt_cfg(cfgp[seq_class(sq->rng_lane)], sq);
+    compute_filter_rules(cfg, sq, sq->n_tokens, cfg.n_vocab, sq->f_rules);
+}
+void launch_rules_init(const SamplerCfg* cfg_dev, SeqState* seq, int batch, hipStream_t st, int mixed) {
+    if (mixed == 2) rules_init_slot_prompt_kernel<<<batch, 64, 0, st>>>(cfg_dev, seq);
+    else if (mixed) rules_init_mixed_kernel<<<batch, 64, 0, st>>>(cfg_dev, seq);
     else rules_init_kernel<<<batch, 64, 0, st>>>(cfg_dev, seq);
 }
 
@@ -852,6 +881,7 @@ void launch_decoder_step(const DecodeBuffers& db, const SamplerCfg* cfg_dev, con
     if (sample) a.cfg = cfg_dev;                 // Float16-logits switch
     if (fused) { a.stats = db.stats; a.sup_mask = db.sup_mask; }
     const bool mixed = sample && db.mixed;       // a mixed pass (option_mix.h): the per-class tables, the mixed instantiations
+    const bool slot_prompts = sample && db.mixed == 2;      // a per-slot-prompt pass: the mixed logits epilogue (it reads no prompt index), the slot-prompt samplers
     launch_dec32_proj(P32_LOGITS, a, n_bt, st, mixed && fused);
     if (ns) launch_nospeech(*ns, db.seq, db.logits, B, V, st);      // before any sampler: the unfused one filters the rows in place, every one advances token_index
     if (db.rule_sets && sample && !fused) launch_rule_sets(*db.rule_sets, db.seq, db.logits, B, V, st);      // a set-aware pass: every slot under the set its home slot names
@@ -859,16 +889,19 @@ void launch_decoder_step(const DecodeBuffers& db, const SamplerCfg* cfg_dev, con
     if (logit_rules && sample && !fused) launch_logit_rules(logit_rules, db.seq, db.logits, B, V, st);      // the raw rows, behind the no-speech kernel's read of them
     if (fused) {
         ProfScope ps_(KK_SAMPLER, st);
-        if (mixed) sampler_final_mixed_kernel<<<B, 256, 0, st>>>(cfg_dev, db.seq, db.stats, (V + 31) / 32);
+        if (slot_prompts) sampler_final_slot_prompt_kernel<<<B, 256, 0, st>>>(cfg_dev, db.seq, db.stats, (V + 31) / 32);
+        else if (mixed) sampler_final_mixed_kernel<<<B, 256, 0, st>>>(cfg_dev, db.seq, db.stats, (V + 31) / 32);
         else sampler_final_kernel<<<B, 256, 0, st>>>(cfg_dev, db.seq, db.stats, (V + 31) / 32);
     } else if (sample) {
         ProfScope ps_(KK_SAMPLER, st);
         if (db.alt_n > 0) {      // token alternatives: the recording instantiations, the buffers by home slot
             const int arg = plan::alternatives_pack_arg(db.alt_n, db.max_batch);
-            if (mixed) sampler_kernel<1, 2, 2, 0><<<B, SAMP_T, 0, st>>>(cfg_dev, suppress_dev, db.seq, db.logits, arg, db.alt_ids, db.alt_lp);
+            if (slot_prompts) sampler_kernel<1, 2, 3, 0><<<B, SAMP_T, 0, st>>>(cfg_dev, suppress_dev, db.seq, db.logits, arg, db.alt_ids, db.alt_lp);
+            else if (mixed) sampler_kernel<1, 2, 2, 0><<<B, SAMP_T, 0, st>>>(cfg_dev, suppress_dev, db.seq, db.logits, arg, db.alt_ids, db.alt_lp);
             else sampler_kernel<1, 2, 1, 0><<<B, SAMP_T, 0, st>>>(cfg_dev, suppress_dev, db.seq, db.logits, arg, db.alt_ids, db.alt_lp);
         } else
-        if (mixed) sampler_kernel<1, 1, 2, 0><<<B, SAMP_T, 0, st>>>(cfg_dev, suppress_dev, db.seq, db.logits, 0, nullptr, nullptr);
+        if (slot_prompts) sampler_kernel<1, 1, 3, 0><<<B, SAMP_T, 0, st>>>(cfg_dev, suppress_dev, db.seq, db.logits, 0, nullptr, nullptr);
+        else if (mixed) sampler_kernel<1, 1, 2, 0><<<B, SAMP_T, 0, st>>>(cfg_dev, suppress_dev, db.seq, db.logits, 0, nullptr, nullptr);
         else sampler_kernel<1, 1, 1, 0><<<B, SAMP_T, 0, st>>>(cfg_dev, suppress_dev, db.seq, db.logits, 0, nullptr, nullptr);
     }
 }

@@ -609,6 +609,9 @@ struct MixClasses {
     // null, or [batch] by home slot: the options each slot's RESULT is finalised under (wh_decoding_fallback reads the compression-ratio, log-prob and
     // no-speech thresholds, which belong to the audio, not to its class: two audios of one class may fall back differently).  Null: the class's options
     const wh_decoding_options* const* slot_opts;
+    // null, or [batch] by home slot (a per-slot-prompt pass): home slot b decodes under ITS prompt slot_prompts[b] of slot_n_prompts[b] tokens; the
+    // class keeps everything else, `prompts` / `n_prompts` are not read.  A slot outside `active` may name no prompt
+    const int32_t* const* slot_prompts = nullptr; const int32_t* slot_n_prompts = nullptr;
 };
 static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options* opt, const wh_special_tokens* st, const int32_t* prompt,
                             int n_prompt, const int32_t* language_tokens, const float* temperatures, const int32_t* active, uint64_t seed,
@@ -628,8 +631,9 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
                             int n_prompt, const int32_t* language_tokens, const float* temperatures, const int32_t* active, uint64_t seed,
                             wh_decoding_result* out, const MixClasses* mix) {
     CHECK_SESSION(s); CHECK_BATCH(s, batch);
-    if (mix) { opt = mix->opts[0]; prompt = mix->prompts[0]; n_prompt = mix->n_prompts[0]; }
-    if (!opt || !st || !prompt || !out) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text: null argument");
+    const bool own_prompts = mix && mix->slot_prompts;      // a per-slot-prompt pass
+    if (mix) { opt = mix->opts[0]; if (!own_prompts) { prompt = mix->prompts[0]; n_prompt = mix->n_prompts[0]; } }
+    if (!opt || !st || (!prompt && !own_prompts) || !out || (own_prompts && !mix->slot_n_prompts)) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text: null argument");
     const int V = s->m->dims.n_vocab;
     // per-audio rule sets (wh_session_define_rule_set; NO REFERENCE BEHAVIOUR): a pass is set-aware iff a live slot names a set other than 0; a
     // live slot that names an undefined set fails the call before anything is launched
@@ -648,28 +652,44 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
     auto cls_opt = [&](int c) { return mix ? mix->opts[c] : opt; };
     auto cls_of = [&](int hb) { return mix ? mix->class_of_slot[hb] : 0; };
     auto is_live = [&](int b) { return plan::slot_is_live(active, b); };
+    static const int32_t kNoPrompt[1] = {0};
+    auto slot_prompt = [&](int hb) { return !own_prompts ? cls_prompt(cls_of(hb)) : mix->slot_prompts[hb] ? mix->slot_prompts[hb] : kNoPrompt; };      // (a slot outside `active` without a prompt: an empty one)
+    auto slot_n_prompt = [&](int hb) { return !own_prompts ? cls_n_prompt(cls_of(hb)) : mix->slot_prompts[hb] ? mix->slot_n_prompts[hb] : 0; };
     auto finalise_options = [&](int b) { return (mix && mix->slot_opts && mix->slot_opts[b]) ? mix->slot_opts[b] : cls_opt(cls_of(b)); };      // home slot b's result: the audio's own thresholds (see MixClasses), or its class's options
     int r = WH_OK;
     for (int c = 0; c < n_cls; ++c) {
+        if (!cls_opt(c)) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text: null argument");
+        if (own_prompts) continue;
         const int np = cls_n_prompt(c);
-        if (!cls_prompt(c) || !cls_opt(c)) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text: null argument");
+        if (!cls_prompt(c)) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text: null argument");
         if (np < 1 || np >= kMaxTok) return set_error(WH_ERR_PREFILL_FAILED, "wh_decode_text: prompt length %d out of range [1,%d)", np, kMaxTok);
         if ((r = whi::check_prompt_tokens("wh_decode_text", cls_prompt(c), np, V, WH_ERR_PREFILL_FAILED))) return r;
     }
-    // (an unmixed pass: entry 0 of the tables, as ever; a mixed one: every class's entries behind one synchronisation)
-    r = mix ? whi::upload_sampler_cfg_classes(s, mix->opts, mix->n_prompts, n_cls, st, prefilled_index, seed)
+    for (int b = 0; own_prompts && b < batch; ++b) {      // per slot: a slot that decodes brings its prompt; one that does not may bring none (a bad one is still refused)
+        if (!mix->slot_prompts[b]) {
+            if (is_live(b)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text: slot %d decodes and has no prompt", b);
+            continue;
+        }
+        const int np = mix->slot_n_prompts[b];
+        if (np < 1 || np >= kMaxTok) return set_error(WH_ERR_PREFILL_FAILED, "wh_decode_text: slot %d: prompt length %d out of range [1,%d)", b, np, kMaxTok);
+        if ((r = whi::check_prompt_tokens("wh_decode_text", mix->slot_prompts[b], np, V, WH_ERR_PREFILL_FAILED))) return r;
+    }
+    // (an unmixed pass: entry 0 of the tables, as ever; a mixed one: every class's entries behind one synchronisation.  A per-slot-prompt pass: its samplers take
+    // the timestamp rules' sampleBegin from the slot's prompt_len, the entries' initial_prompt_index is not read)
+    const int32_t no_np[kMaxOptionClasses] = {};
+    r = mix ? whi::upload_sampler_cfg_classes(s, mix->opts, own_prompts ? no_np : mix->n_prompts, n_cls, st, prefilled_index, seed)
             : whi::upload_sampler_cfg(s, opt, st, prefilled_index, n_prompt, 0, seed);
     if (r) return r;
     if (opt->word_timestamps && s->m->n_align > 0) { r = whi::ensure_align(s); if (r) return r; }
     s->align_enabled = opt->word_timestamps && s->align;
     // ---- 2. stage the slots.  Per-slot language token (batched windows of different audios, each with its own detected language): it replaces the
-    // token that follows <|startoftranscript|> in the shared prompt (prefillDecoderInputs, TextDecoder.swift:183-188)
-    int lang_pos_of[kMaxOptionClasses];
-    for (int c = 0; c < n_cls; ++c) lang_pos_of[c] = whi::prompt_language_position(cls_prompt(c), cls_n_prompt(c), st->start_of_transcript_token, language_tokens && wh_is_model_multilingual(s->m));
+    // token that follows <|startoftranscript|> in the slot's prompt (prefillDecoderInputs, TextDecoder.swift:183-188).  The position is the slot's own: its class's
+    // slots share it unless each brings its prompt
+    const bool replace_lang = language_tokens && wh_is_model_multilingual(s->m);
     // the decode state of home slot hb as the pass starts it
     auto init_slot = [&](SeqState& q, int hb, bool act) {
-        const int c = cls_of(hb), lang_pos = lang_pos_of[c];
-        whi::seq_init_prompt(q, cls_prompt(c), cls_n_prompt(c), lang_pos, lang_pos >= 0 ? language_tokens[hb] : -1, V);
+        const int c = cls_of(hb), lang_pos = whi::prompt_language_position(slot_prompt(hb), slot_n_prompt(hb), st->start_of_transcript_token, replace_lang);
+        whi::seq_init_prompt(q, slot_prompt(hb), slot_n_prompt(hb), lang_pos, lang_pos >= 0 ? language_tokens[hb] : -1, V);
         q.active = act ? 1 : 0;
         q.temperature = f16_round(temperatures ? temperatures[hb] : opt->temperature);
         q.rng_lane = seq_pack_lane(hb, c);      // the slot's random stream (T > 0) does not depend on where the slot is decoded; its option class (0 unless mixed)
@@ -696,18 +716,16 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
         for (int b = 0; b < batch; ++b) init_slot(s->seq_host[b], b, is_live(b));
     }
     // ---- 3. arm the modes.  No-speech detection (wh_session_set_no_speech_detection; NO REFERENCE BEHAVIOUR): every decoded slot's scoring position -
-    // the first <|startoftranscript|> of its class's prompt - and, in mode 2, its stop threshold from the options its result is finalised under, by home slot
+    // the first <|startoftranscript|> of its prompt - and, in mode 2, its stop threshold from the options its result is finalised under, by home slot
     std::vector<const wh_decoding_options*> ns_opts;
     if (s->no_speech_detection != plan::kNoSpeechOff) {
-        int cpos[kMaxOptionClasses];
-        for (int c = 0; c < n_cls; ++c) cpos[c] = plan::nospeech_position(cls_prompt(c), cls_n_prompt(c), st->start_of_transcript_token);
         std::vector<int> pos((size_t)batch);
         std::vector<float> stop((size_t)batch);
         ns_opts.assign((size_t)batch, nullptr);
         for (int b = 0; b < batch; ++b) {
             const bool act = is_live(b);
             const wh_decoding_options* fo = finalise_options(b);
-            pos[b] = act ? cpos[cls_of(b)] : -1;
+            pos[b] = act ? plan::nospeech_position(slot_prompt(b), slot_n_prompt(b), st->start_of_transcript_token) : -1;
             stop[b] = plan::nospeech_stop_threshold(s->no_speech_detection, fo);
             if (act) ns_opts[b] = fo;
         }
@@ -715,7 +733,18 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
         if (r) return r;
     }
     s->decode_passes += 1;
-    if (mix) { s->pass.mixed = true; s->mix_mixed_passes += 1; s->mix_max_classes = std::max<long long>(s->mix_max_classes, n_cls); }
+    if (mix) { s->pass.mixed = own_prompts ? 2 : 1; s->mix_mixed_passes += 1; s->mix_max_classes = std::max<long long>(s->mix_max_classes, n_cls); }
+    if (own_prompts) {      // wh_session_slot_prompt_stats: the pass, its distinct prompts, the prompt positions its slots step through
+        std::vector<std::vector<int32_t>> seen;
+        for (int b = 0; b < batch; ++b) {
+            if (!is_live(b)) continue;
+            seen.emplace_back(slot_prompt(b), slot_prompt(b) + slot_n_prompt(b));
+            s->sp_positions += slot_n_prompt(b);
+        }
+        std::sort(seen.begin(), seen.end());
+        s->sp_passes += 1;
+        s->sp_max_distinct = std::max<long long>(s->sp_max_distinct, (long long)(std::unique(seen.begin(), seen.end()) - seen.begin()));
+    }
     // fused greedy path: every active slot samples at T = 0 (filters + softmax statistics in the logits epilogue)
     s->fused_greedy = true;
     for (int b = 0; b < width; ++b) if (s->seq_host[b].active && s->seq_host[b].temperature != 0.0f) s->fused_greedy = false;
@@ -750,7 +779,7 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
     }
     // ---- 4. run: the states go up and the token loop runs
     WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * width, hipMemcpyHostToDevice, s->st));
-    launch_rules_init(s->cfg_dev, s->seq, width, s->st, mix != nullptr);
+    launch_rules_init(s->cfg_dev, s->seq, width, s->st, s->pass.mixed);
     int loop_count = 0;       // a slot finishes at its class's count (SamplerCfg.loop_count); the host loop runs to the largest
     for (int c = 0; c < n_cls; ++c) loop_count = std::max(loop_count, std::min(cls_opt(c)->sample_length, kMaxTok - 1));
     s->skip_special_in_progress = opt->skip_special_tokens != 0;
@@ -831,6 +860,37 @@ extern "C" int wh_decode_text_mixed(wh_session* s, int batch, const wh_decoding_
     for (int c = 0; c < n_classes; ++c) po[c] = &opts[c];
     for (int b = 0; b < batch; ++b) skip[b] = opts[class_of_slot[b]].skip_special_tokens != 0;
     const MixClasses mix{n_classes, po, class_of_slot, prompts, n_prompts, nullptr};
+    struct SkipScope { wh_session* s; const int32_t* keep; ~SkipScope() { s->skip_special_by_slot = keep; } } skip_scope{s, s->skip_special_by_slot};
+    s->skip_special_by_slot = skip;
+    return decode_text_impl(s, batch, nullptr, st, nullptr, 0, language_tokens, temperatures, active, seed, out, &mix);
+}
+
+// wh_decode_text_mixed with the prompt per SLOT.  The same checks in the same order, then the prompts: all before the session is looked at.
+extern "C" int wh_decode_text_slot_prompts(wh_session* s, int batch, const wh_decoding_options* opts, int n_classes, const int32_t* class_of_slot,
+                                           const wh_special_tokens* st, const int32_t* const* prompts, const int32_t* n_prompts, const int32_t* language_tokens,
+                                           const float* temperatures, const int32_t* active, uint64_t seed, wh_decoding_result* out) {
+    if (n_classes < 1 || n_classes > kMaxOptionClasses)
+        return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text_slot_prompts: %d option classes (1 .. %d)", n_classes, kMaxOptionClasses);
+    if (!opts || !class_of_slot) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text_slot_prompts: null class table");
+    for (int c = 1; c < n_classes; ++c)
+        if (!plan::option_batch_key_equal(opts[0], opts[c]))
+            return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text_slot_prompts: class %d differs from class 0 in a field that belongs to the pass (temperature ladder, seed, "
+                             "use_prefill_prompt, detect_language, word_timestamps, float16_logits, beam search)", c);
+    if (!prompts || !n_prompts) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text_slot_prompts: null prompt table");
+    if (batch >= 1 && batch <= kMaxSessionSlots)
+        for (int b = 0; b < batch; ++b) {
+            if (class_of_slot[b] < 0 || class_of_slot[b] >= n_classes)
+                return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text_slot_prompts: slot %d names class %d of %d", b, class_of_slot[b], n_classes);
+            if (!prompts[b] && plan::slot_is_live(active, b))
+                return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text_slot_prompts: slot %d decodes and has no prompt", b);
+        }
+    CHECK_SESSION(s); CHECK_BATCH(s, batch);
+    if (!st || !out) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text_slot_prompts: null argument");
+    const wh_decoding_options* po[kMaxOptionClasses];
+    int32_t skip[kMaxSessionSlots];
+    for (int c = 0; c < n_classes; ++c) po[c] = &opts[c];
+    for (int b = 0; b < batch; ++b) skip[b] = opts[class_of_slot[b]].skip_special_tokens != 0;
+    const MixClasses mix{n_classes, po, class_of_slot, nullptr, nullptr, nullptr, prompts, n_prompts};
     struct SkipScope { wh_session* s; const int32_t* keep; ~SkipScope() { s->skip_special_by_slot = keep; } } skip_scope{s, s->skip_special_by_slot};
     s->skip_special_by_slot = skip;
     return decode_text_impl(s, batch, nullptr, st, nullptr, 0, language_tokens, temperatures, active, seed, out, &mix);
@@ -1712,6 +1772,10 @@ struct AudioJob {
     int rule_set = 0;                               // the rule set this audio decodes under (wh_transcribe_batch_with_rule_sets; 0 = the session's own)
     wh_transcription* tr;
     int cur_seek = 0, cur_size = 0;   // window in flight
+    // per-slot prompts: the text carried into the next window's prompt (prompt_carry_plan.h; previous-text conditioning), and the prompt the window
+    // in flight decodes under - built from the audio's own options (with the carry as their prompt_tokens) before the window takes a slot
+    std::vector<int32_t> carry; bool carry_started = false;
+    std::vector<int32_t> cur_prompt;
 };
 
 static bool job_next_window(AudioJob& j, const wh_decoding_options* opt) {
@@ -1733,10 +1797,19 @@ static bool job_next_window(AudioJob& j, const wh_decoding_options* opt) {
 // classes: null, or (option mixing) the options that stand for the option classes of this group - job j decodes under class j.cls and everything the
 // host reads per audio (windowing, thresholds, text) comes from the job's own options; `opt` is then class 0 and serves the batch-key fields, which are
 // equal over the group (option_mix.h).  Null: every job runs under `opt`, as ever.
+// slot_prompts (a mixed group under wh_session_set_prompt_mixing 1): the classes do not hold the prompt - every window decodes under its audio's own prompt.
+// Previous-text conditioning (wh_session_set_previous_text 1, a group that prefills and does not beam-search) switches the same route on for any group, with
+// the audio's carry as its prompt_tokens; a group without classes is then one class.
 static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_decoding_options* opt, const wh_special_tokens* st,
-                           const std::vector<const wh_decoding_options*>* classes = nullptr) {
+                           const std::vector<const wh_decoding_options*>* classes = nullptr, bool slot_prompts = false) {
     const wh_model* m = s->m;
     const bool mixed = classes != nullptr;
+    if (s->previous_text == plan::kPreviousTextOn && opt->beam_size > 1)
+        return set_error(WH_ERR_INVALID_ARGUMENT, "beam_size > 1 cannot be combined with previous-text conditioning (wh_session_set_previous_text)");
+    const bool carrying = s->previous_text == plan::kPreviousTextOn && opt->use_prefill_prompt != 0;
+    slot_prompts = (slot_prompts && mixed) || carrying;
+    const std::vector<const wh_decoding_options*> one_class{opt};
+    const std::vector<const wh_decoding_options*>& sp_classes = mixed ? *classes : one_class;
     auto jopt = [&](const AudioJob& j) { return mixed ? j.opt : opt; };
     struct SkipScope { wh_session* s; ~SkipScope() { s->skip_special_by_slot = nullptr; } } skip_scope{s};
     const bool multilingual = wh_is_model_multilingual(m) != 0;
@@ -1775,6 +1848,25 @@ static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_
             AudioJob& j = jobs[ji];
             if (j.finished || j.status != WH_OK || !job_next_window(j, jopt(j))) continue;
             const int b = (int)slot_job.size();
+            bool carried = false;      // the window's prompt holds carried text: counted once the window has its slot
+            if (slot_prompts) {      // the window's own prompt, before it takes a slot: one that does not fit fails ITS audio
+                wh_decoding_options po = *jopt(j);
+                if (carrying) {
+                    if (!j.carry_started) { plan::carry_start(j.carry, po.prompt_tokens, po.n_prompt_tokens, st->special_token_begin); j.carry_started = true; }
+                    po.prompt_tokens = plan::carry_prompt(j.carry, &po.n_prompt_tokens);
+                }
+                j.cur_prompt.assign(1, st->start_of_transcript_token);
+                if (po.use_prefill_prompt) {
+                    j.cur_prompt.resize(kMaxPrompt);
+                    const int np = wh_prefill_prompt(m, &po, st, po.language_token, j.cur_prompt.data(), (int)j.cur_prompt.size());
+                    if (np <= 0 || np >= kMaxTok) {
+                        j.status = set_error(WH_ERR_PREFILL_FAILED, "audio %d: prefill prompt does not fit", j.index); j.error = wh_last_error(); j.finished = true;
+                        continue;
+                    }
+                    j.cur_prompt.resize((size_t)np);
+                }
+                carried = carrying && po.prompt_tokens;
+            }
             // a window without samples: the reference slices audioArray[seek ..< seek + segmentSize], AudioProcessor.padOrTrimAudio returns nil for
             // the empty slice ("startIndex is outside the buffer size", Core/Audio/AudioProcessor.swift:151-155) and the task throws
             // transcriptionFailed("Audio samples are nil") (Core/TranscribeTask.swift:126-129) - a clip that ends beyond the samples gets here
@@ -1783,6 +1875,7 @@ static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_
             if (r == WH_ERR_HIP) return r;                                 // the device is gone: every audio of the group fails
             if (r) { j.status = r; j.error = wh_last_error(); j.finished = true; continue; }
             slot_job.push_back((int)ji);
+            if (carried) s->sp_windows_carried += 1;
             if (s->hooks.window_preprocess) {                              // TranscribeTask.windowPreprocess (:130)
                 const float* win = j.pcm + j.cur_seek;
                 std::vector<float> copy;
@@ -1827,6 +1920,11 @@ static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_
         std::vector<std::vector<int32_t>> mix_prompt;
         std::vector<const int32_t*> mix_pp;
         bool any_detects = opt->language_token < 0;
+        std::vector<const int32_t*> sp_pp; std::vector<int32_t> sp_np;      // (per-slot prompts) the prompt of every slot's window
+        if (slot_prompts) {
+            cls_slot.assign(nb, 0);
+            for (int b = 0; b < nb; ++b) { sp_pp.push_back(jobs[slot_job[b]].cur_prompt.data()); sp_np.push_back((int32_t)jobs[slot_job[b]].cur_prompt.size()); }
+        }
         if (mixed) {
             cls_slot.resize(nb); skip_slot.resize(nb); opt_slot.resize(nb);
             any_detects = false;
@@ -1857,7 +1955,7 @@ static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_
                 n_prompt = wh_prefill_prompt(m, opt, st, opt->language_token, prompt.data(), (int)prompt.size());
                 if (n_prompt <= 0) return set_error(WH_ERR_PREFILL_FAILED, "prefill prompt does not fit");
             }
-            if (mixed && mix_prompt.empty()) {
+            if (mixed && !slot_prompts && mix_prompt.empty()) {
                 for (const wh_decoding_options* co : *classes) {
                     std::vector<int32_t> pr(kMaxPrompt);
                     int np = 1;
@@ -1882,6 +1980,13 @@ static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_
                 bool again = false;
                 for (int b = 0; b < nb; ++b) again |= tmp[b].needs_fallback != 0;
                 if (again && ti + 1 < temps.size()) { r = wh_prepare_decoder_inputs(s, nb); if (r) return r; }   // the beam slots overwrote the windows' cross K/V
+            } else if (slot_prompts) {
+                // (an attached draft is ignored: the speculative pass reads one prompt).  Language tokens as in the branch this one stands in for
+                std::vector<int32_t> ml(lang_slot);
+                for (int b = 0; mixed && b < nb; ++b) if (jobs[slot_job[b]].opt->language_token >= 0) ml[b] = -1;
+                const MixClasses mix{(int)sp_classes.size(), sp_classes.data(), cls_slot.data(), nullptr, nullptr, mixed ? opt_slot.data() : nullptr, sp_pp.data(), sp_np.data()};
+                r = decode_text_impl(s, nb, nullptr, st, nullptr, 0, langs ? ml.data() : nullptr, tv.data(), active.data(), seed, tmp.data(), &mix);
+                if (r) return r;
             } else if (mixed) {
                 // a slot whose audio states its language keeps its class's prompt (-1: no replacement), a detected one gets its own token
                 std::vector<int32_t> ml(lang_slot);
@@ -1973,6 +2078,12 @@ static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_
                 }
                 if (s->hooks.segment_discovery) s->hooks.segment_discovery(s->hooks.user, j.index, tr, seg_before, n_new);   // segmentDiscoveryCallback (:260)
             }
+            if (carrying) {      // the segments the window added, as they stand now, go into the audio's carry
+                const int n_seg = tr->timings.total_decoding_windows > windows_before ? (int)tr->segments.size() - seg_before : 0;
+                const int tok0 = n_seg > 0 ? tr->segments[(size_t)seg_before].token_offset : 0;
+                const int tok1 = n_seg > 0 ? tr->segments.back().token_offset + tr->segments.back().n_tokens : 0;
+                if (plan::carry_after_window(j.carry, n_seg, tr->tokens.data() + tok0, tok1 - tok0, res[b].temperature, s->previous_text_reset, st->special_token_begin)) s->sp_resets += 1;
+            }
             if (tr->timings.total_decoding_windows > windows_before) j.windows += 1;
             tr->timings.audio_processing += (t1 - t0) / nb; tr->timings.logmels += (t2 - t1) / nb; tr->timings.encoding += (t3 - t2) / nb;
             tr->timings.decoding_loop += (t4 - t3) / nb; tr->timings.total_logmel_runs += 1; tr->timings.total_encoding_runs += 1;
@@ -2061,7 +2172,7 @@ static int transcribe_items(wh_session* s, const float* const* pcm, const int32_
     if (mixing) {
         std::vector<const wh_decoding_options*> po((size_t)n_audio, nullptr);
         for (int i = 0; i < n_audio; ++i) if (group_of[(size_t)i] >= 0) po[(size_t)i] = all[(size_t)i].opt;
-        mixp = plan::rule_sets_mix_plan(po.data(), rule_sets ? ruled.data() : nullptr, n_audio);
+        mixp = plan::rule_sets_mix_plan(po.data(), rule_sets ? ruled.data() : nullptr, n_audio, kMaxOptionClasses, s->prompt_mixing == 1);
         group_of = mixp.group;
         group_opt.clear();
         for (const auto& cl : mixp.classes) group_opt.push_back(cl[0]);
@@ -2073,7 +2184,7 @@ static int transcribe_items(wh_session* s, const float* const* pcm, const int32_
         for (int i = 0; i < n_audio; ++i) if (group_of[(size_t)i] == (int)g) { jobs.push_back(all[(size_t)i]); jobs.back().tr = new wh_transcription(); }
         const bool mix_group = mixing && plan::option_mixable(*group_opt[g]);      // (beam search groups run as without the option)
         if (mix_group && !hard) s->mix_groups_run += 1;
-        const int r = hard ? hard : transcribe_jobs(s, jobs, group_opt[g], st, mix_group ? &mixp.classes[g] : nullptr);       // after a device error nothing else can run
+        const int r = hard ? hard : transcribe_jobs(s, jobs, group_opt[g], st, mix_group ? &mixp.classes[g] : nullptr, mix_group && s->prompt_mixing == 1);       // after a device error nothing else can run
         const std::string why = r ? wh_last_error() : "";
         if (r == WH_ERR_HIP || r == WH_ERR_CANCELLED) hard = r;
         for (auto& j : jobs) {

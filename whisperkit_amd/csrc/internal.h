@@ -15,6 +15,7 @@
 #include "nospeech_plan.h"
 #include "pass_state.h"
 #include "phrase_rules_plan.h"
+#include "prompt_carry_plan.h"
 #include "rule_sets_plan.h"
 #include "text.h"
 #include "whisperhip.h"
@@ -130,6 +131,12 @@ struct wh_session {
     // decodes a group's classes in one pass.  pass.mixed is set by a pass with classes (host.hip MixClasses; wh_decode_text_mixed works whatever the mode).
     int option_mixing = 0;
     long long mix_groups_run = 0, mix_mixed_passes = 0, mix_max_classes = 0;   // wh_session_option_mixing_stats: groups that ran mixed, passes with classes, largest class count
+    // per-slot prompts.  prompt_mixing (wh_session_set_prompt_mixing): 1 = while option mixing is on, the prompt leaves the class and every audio's own
+    // prompt goes to its slot.  previous_text (wh_session_set_previous_text; NO REFERENCE BEHAVIOUR): 1 = every audio of wh_transcribe* carries its decoded text into the
+    // prompt of its next window (prompt_carry_plan.h), emptied behind a window kept above previous_text_reset (NaN: never).  pass.mixed == 2 is set by a pass with slot prompts
+    int prompt_mixing = 0, previous_text = 0;
+    float previous_text_reset = 0.5f;
+    long long sp_passes = 0, sp_max_distinct = 0, sp_positions = 0, sp_windows_carried = 0, sp_resets = 0;   // wh_session_slot_prompt_stats
     float* stats = nullptr;                  // [B][kStatBlocks][8]
     bool fused_greedy = false;               // NOT pass state (nor is align_enabled below): the step API (wh_predict_logits, wh_measure_kernels) reads what the last decode left
     int *tok_out_dev = nullptr; float* lp_out_dev = nullptr;

@@ -232,7 +232,7 @@ struct DecodeBuffers {
     const struct Xabs* xabs; // non-null: weight-absorbed cross-attention over the encoder output (xabs.hip) instead of the cross K / V stream
     const int* slot_home;    // null, or [batch] (device): a compacted pass (launch_plan.h compact_pass_plan) - slot b attends over the encoder output / cross
                              // K / V rows of slot slot_home[b] and writes that slot's alignment rows; everything else is indexed by b
-    int mixed;               // 1: a mixed pass (launch_decoder_step below).  Host-side only
+    int mixed;               // 1: a mixed pass, 2: a per-slot-prompt pass (launch_decoder_step below).  Host-side only
     int owner_slots;         // 0, or the slot count self_owner's entries are clamped to instead of `batch`: a pass that narrowed (compact.hip) reads history
                              // rows from the caches of slots beyond its present width.  Host-side only: the kernels' arguments keep their layout
     const struct RuleSetsArgs* rule_sets;   // null, or a set-aware pass (rule_sets.hip, launch_decoder_step below): rule_sets_kernel runs in front of the unfused
@@ -405,7 +405,7 @@ void launch_rule_sets(const RuleSetsArgs& a, const SeqState* seq, float* logits,
 void launch_decoder_step(const DecodeBuffers& db, const SamplerCfg* cfg_dev, const int* suppress_dev, bool sample, hipStream_t st, const NoSpeechArgs* ns = nullptr,
                          const int* logit_rules = nullptr, const PhraseRulesArgs* phrase_rules = nullptr);
 // filter rules of the first sampling step of a decodeText call (later steps: computed by the sampler itself)
-void launch_rules_init(const SamplerCfg* cfg_dev, SeqState* seq, int batch, hipStream_t st, bool mixed = false);
+void launch_rules_init(const SamplerCfg* cfg_dev, SeqState* seq, int batch, hipStream_t st, int mixed = 0);      // mixed: DecodeBuffers.mixed
 // in-pass compaction (compact.hip): the decode state of a narrowing pass moves through a home-indexed array [n_slots].  park: seq_home[home[i]] = seq[i]
 // for the active slots i < width (home null: i); gather: seq[i] = seq_home[home[i]] where live[i], an inactive zero state elsewhere.
 void launch_seq_park(const SeqState* seq, SeqState* seq_home, const int* home, int width, int n_slots, hipStream_t st);

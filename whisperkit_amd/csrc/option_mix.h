@@ -39,13 +39,17 @@ inline bool option_batch_key_equal(const wh_decoding_options& a, const wh_decodi
            a.float16_logits == b.float16_logits &&                                                      // the logits epilogue reads it uniformly
            a.beam_size == b.beam_size && opt_float_eq(a.beam_patience, b.beam_patience);
 }
-inline bool option_class_equal(const wh_decoding_options& a, const wh_decoding_options& b) {
+// the class of a per-slot-prompt pass (wh_session_set_prompt_mixing): the prompt - prompt_tokens, prefix_tokens - travels with the slot, the rest of the class stays
+inline bool option_class_equal_sans_prompt(const wh_decoding_options& a, const wh_decoding_options& b) {
     return a.task == b.task && a.language_token == b.language_token &&
-           opt_list_eq(a.prompt_tokens, a.n_prompt_tokens, b.prompt_tokens, b.n_prompt_tokens) &&
-           opt_list_eq(a.prefix_tokens, a.n_prefix_tokens, b.prefix_tokens, b.n_prefix_tokens) &&
            a.without_timestamps == b.without_timestamps && a.suppress_blank == b.suppress_blank &&
            opt_list_eq(a.suppress_tokens, a.n_suppress_tokens, b.suppress_tokens, b.n_suppress_tokens) &&
            opt_float_eq(a.first_token_log_prob_threshold, b.first_token_log_prob_threshold) && a.sample_length == b.sample_length && a.top_k == b.top_k;
+}
+inline bool option_class_equal(const wh_decoding_options& a, const wh_decoding_options& b) {
+    return option_class_equal_sans_prompt(a, b) &&
+           opt_list_eq(a.prompt_tokens, a.n_prompt_tokens, b.prompt_tokens, b.n_prompt_tokens) &&
+           opt_list_eq(a.prefix_tokens, a.n_prefix_tokens, b.prefix_tokens, b.n_prefix_tokens);
 }
 // (clip_timestamps: positions inside ONE audio, never compared)
 inline bool option_per_audio_equal(const wh_decoding_options& a, const wh_decoding_options& b) {
@@ -66,8 +70,8 @@ struct OptionMixPlan {
 };
 // Deterministic: an audio joins the FIRST group of its batch key that holds its class or has room for one more; groups and classes are numbered in
 // order of first appearance, so caller order is kept inside a group.  Audios with beam_size > 1 group as without the option (option_same_group, one
-// class).  opts[i] == nullptr: the audio takes no part.
-inline OptionMixPlan option_mix_plan(const wh_decoding_options* const* opts, int n, int max_classes = kMaxOptionClasses) {
+// class).  opts[i] == nullptr: the audio takes no part.  slot_prompts: the prompt is no part of the class (option_class_equal_sans_prompt).
+inline OptionMixPlan option_mix_plan(const wh_decoding_options* const* opts, int n, int max_classes = kMaxOptionClasses, bool slot_prompts = false) {
     OptionMixPlan p;
     p.group.assign((size_t)(n > 0 ? n : 0), -1);
     p.cls.assign((size_t)(n > 0 ? n : 0), -1);
@@ -82,7 +86,7 @@ inline OptionMixPlan option_mix_plan(const wh_decoding_options* const* opts, int
                 continue;
             }
             if (!option_batch_key_equal(*cl[0], o)) continue;
-            for (size_t q = 0; q < cl.size() && c < 0; ++q) if (option_class_equal(*cl[q], o)) c = (int)q;
+            for (size_t q = 0; q < cl.size() && c < 0; ++q) if (slot_prompts ? option_class_equal_sans_prompt(*cl[q], o) : option_class_equal(*cl[q], o)) c = (int)q;
             if (c < 0 && (int)cl.size() < max_classes) { c = (int)cl.size(); p.classes[k].push_back(&o); }
             if (c >= 0) g = (int)k;
         }

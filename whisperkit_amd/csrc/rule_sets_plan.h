@@ -104,15 +104,16 @@ inline int rule_sets_first_undefined(const int32_t* set_of_slot, const int32_t* 
 inline bool rule_set_ruled(int set, bool session_rules_on) { return set != 0 || session_rules_on; }
 // option_mix_plan inside each part of that partition, the un-ruled part first: groups are numbered on, classes stay per group.
 // opts[i] == nullptr: the audio takes no part.  ruled null: one part, option_mix_plan itself.
-inline OptionMixPlan rule_sets_mix_plan(const wh_decoding_options* const* opts, const unsigned char* ruled, int n, int max_classes = kMaxOptionClasses) {
-    if (!ruled) return option_mix_plan(opts, n, max_classes);
+inline OptionMixPlan rule_sets_mix_plan(const wh_decoding_options* const* opts, const unsigned char* ruled, int n, int max_classes = kMaxOptionClasses,
+                                        bool slot_prompts = false) {
+    if (!ruled) return option_mix_plan(opts, n, max_classes, slot_prompts);
     OptionMixPlan out;
     out.group.assign((size_t)(n > 0 ? n : 0), -1);
     out.cls.assign((size_t)(n > 0 ? n : 0), -1);
     std::vector<const wh_decoding_options*> po((size_t)(n > 0 ? n : 0));
     for (int part = 0; part < 2; ++part) {
         for (int i = 0; i < n; ++i) po[(size_t)i] = (opts[i] && (ruled[i] != 0) == (part != 0)) ? opts[i] : nullptr;
-        const OptionMixPlan p = option_mix_plan(po.data(), n, max_classes);
+        const OptionMixPlan p = option_mix_plan(po.data(), n, max_classes, slot_prompts);
         const int base = (int)out.classes.size();
         for (int i = 0; i < n; ++i) if (p.group[(size_t)i] >= 0) { out.group[(size_t)i] = base + p.group[(size_t)i]; out.cls[(size_t)i] = p.cls[(size_t)i]; }
         for (const auto& cl : p.classes) out.classes.push_back(cl);

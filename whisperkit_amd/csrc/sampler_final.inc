@@ -1,6 +1,7 @@
 // The body of sampler_final_kernel (decoder.hip), included once per form: SAMPLER_FINAL_NAME = the kernel's name, SAMPLER_FINAL_MIXED = 0: the one
 // SamplerCfg at cfgp, the kernel as it has always been (same text, same instructions: tools/device_code_hash.py); 1 (a mixed pass, option_mix.h): cfgp is
-// the session's per-class table and the slot reads the entry of its class.  (tbeg is a model constant: entry 0 serves every class.)
+// the session's per-class table and the slot reads the entry of its class; 2 (a per-slot-prompt pass, DESIGN 3.5.16): the mixed form with the timestamp rules'
+// sampleBegin taken from the slot's own prompt_len.  (tbeg is a model constant: entry 0 serves every class.)
 __global__ __launch_bounds__(256) void SAMPLER_FINAL_NAME(const SamplerCfg* __restrict__ cfgp, SeqState* __restrict__ seqs,
                                                             const float* __restrict__ stats, int nblk) {
     __shared__ float sm[4][4];
@@ -43,7 +44,9 @@ __global__ __launch_bounds__(256) void SAMPLER_FINAL_NAME(const SamplerCfg* __re
     __syncthreads();
     if (tid == 0) {
         for (int w = 1; w < 4; ++w) { stat_merge(t, sm[w][0], sm[w][1], si[w][0]); stat_merge(u, sm[w][2], sm[w][3], si[w][1]); last_ts = max(last_ts, si[w][2]); }
-#if SAMPLER_FINAL_MIXED
+#if SAMPLER_FINAL_MIXED == 2
+        const SamplerCfg cfg = slot_prompt_cfg(cfgp[seq_class(sq_l.rng_lane)], &sq_l);
+#elif SAMPLER_FINAL_MIXED
         const SamplerCfg cfg = cfgp[seq_class(sq_l.rng_lane)];
 #else
         const SamplerCfg cfg = *cfgp;
