@@ -7,7 +7,7 @@ bit for bit - tokens, log-probabilities as bit patterns, steps, flags.  Nothing 
 tests/test_gpu_parity.py; that is how this reference reaches the oracle.
 
 T > 0 passes are not compared at the transcribe level: a grouped call and a mixed call place the windows in different slots, and the random stream
-follows the slot (SeqState.rng_lane, the seed line of host.hip transcribe_jobs).
+follows the slot (SeqState.rng_lane; the pass's seed is transcribe_plan.h pass_seed, taken in host.hip round_decode).
 
 Run on the MI355X box with `pytest -m gpu`.  The planner and the ABI: tests/test_option_mixing.py."""
 import json

@@ -14,12 +14,14 @@
 #include <algorithm>
 #include <chrono>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <tuple>
 
 #include "forced_plan.h"
 #include "internal.h"
 #include "knobs.h"
+#include "transcribe_plan.h"
 
 using namespace wh;
 using whi::set_error;
@@ -218,6 +220,16 @@ extern "C" int wh_prefill_prompt(const wh_model* m, const wh_decoding_options* o
     if ((int)p.size() > capacity) return -(int)p.size();
     for (size_t i = 0; i < p.size(); ++i) out[i] = p[i];
     return (int)p.size();
+}
+// The prompt a pass decodes under: <|startoftranscript|> alone, or the prefill of the options.  Returns its length; <= 0: it does not fit kMaxPrompt tokens (out is
+// then empty).  What that means is the caller's: an error of the call for a group's or a class's prompt, of the audio for a window's
+static int build_prompt(const wh_model* m, const wh_decoding_options& o, const wh_special_tokens* st, std::vector<int32_t>& out) {
+    out.assign(1, st->start_of_transcript_token);
+    if (!o.use_prefill_prompt) return 1;
+    out.resize(kMaxPrompt);
+    const int np = wh_prefill_prompt(m, &o, st, o.language_token, out.data(), (int)out.size());
+    out.resize(np > 0 ? (size_t)np : 0);
+    return np;
 }
 
 // ------------------------------------------------------------------------------------------------ decodeText
@@ -599,41 +611,46 @@ static int run_token_loop(wh_session* s, int batch, int loop_count, PassLayout* 
     return final_read();
 }
 
-// A mixed pass (option_mix.h): slot b decodes under class_of_slot[b]'s options and prompt.  The batch-key fields are equal over the classes (the caller has
-// checked); everything per pass is read from class 0.
-struct MixClasses {
-    int n;
-    const wh_decoding_options* const* opts;      // [n]
-    const int32_t* class_of_slot;                // [batch], home-slot terms
-    const int32_t* const* prompts; const int32_t* n_prompts;      // [n]
+// What a decode pass is asked to do, in the session's home-slot terms: the option classes, each slot's class, the prompts at their granularity and what the
+// caller gives per slot.  The batch-key fields (option_mix.h) are equal over the classes - the caller has checked - and everything per pass is read from class 0.
+enum class PromptGrain { Shared, PerClass, PerSlot };      // the pass runs as pass.mixed 0 / 1 / 2: one prompt, one per class, one per home slot
+struct PassRequest {
+    int batch = 0;
+    int n = 1; const wh_decoding_options* const* opts = nullptr;      // [n] the option classes
+    const int32_t* class_of_slot = nullptr;                           // [batch] by home slot; null: every slot is class 0
+    PromptGrain grain = PromptGrain::Shared;
+    // Shared: [1]; PerClass: [n]; PerSlot: [batch] by home slot - home slot b decodes under ITS prompt, the class keeps everything else; a slot outside `active` may name none
+    const int32_t* const* prompts = nullptr; const int32_t* n_prompts = nullptr;
     // null, or [batch] by home slot: the options each slot's RESULT is finalised under (wh_decoding_fallback reads the compression-ratio, log-prob and
-    // no-speech thresholds, which belong to the audio, not to its class: two audios of one class may fall back differently).  Null: the class's options
-    const wh_decoding_options* const* slot_opts;
-    // null, or [batch] by home slot (a per-slot-prompt pass): home slot b decodes under ITS prompt slot_prompts[b] of slot_n_prompts[b] tokens; the
-    // class keeps everything else, `prompts` / `n_prompts` are not read.  A slot outside `active` may name no prompt
-    const int32_t* const* slot_prompts = nullptr; const int32_t* slot_n_prompts = nullptr;
+    // no-speech thresholds, which belong to the audio, not to its class: two audios of one class may fall back differently).  Null (entry): the class's options
+    const wh_decoding_options* const* slot_opts = nullptr;
+    const int32_t* language_tokens = nullptr; const float* temperatures = nullptr; const int32_t* active = nullptr;      // null, or [batch] by home slot
+    uint64_t seed = 0;
 };
-static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options* opt, const wh_special_tokens* st, const int32_t* prompt,
-                            int n_prompt, const int32_t* language_tokens, const float* temperatures, const int32_t* active, uint64_t seed,
-                            wh_decoding_result* out, const MixClasses* mix = nullptr);
+static int decode_text_impl(wh_session* s, const wh_special_tokens* st, const PassRequest& rq, wh_decoding_result* out);
 extern "C" int wh_decode_text(wh_session* s, int batch, const wh_decoding_options* opt, const wh_special_tokens* st, const int32_t* prompt,
                               int n_prompt, const float* temperatures, const int32_t* active, uint64_t seed, wh_decoding_result* out) {
-    return decode_text_impl(s, batch, opt, st, prompt, n_prompt, nullptr, temperatures, active, seed, out);
+    return wh_decode_text_languages(s, batch, opt, st, prompt, n_prompt, nullptr, temperatures, active, seed, out);
 }
+// one option set and one prompt for every slot (also the plain rung of transcribe_jobs)
 extern "C" int wh_decode_text_languages(wh_session* s, int batch, const wh_decoding_options* opt, const wh_special_tokens* st, const int32_t* prompt,
                                         int n_prompt, const int32_t* language_tokens, const float* temperatures, const int32_t* active, uint64_t seed,
                                         wh_decoding_result* out) {
-    return decode_text_impl(s, batch, opt, st, prompt, n_prompt, language_tokens, temperatures, active, seed, out);
+    PassRequest rq;
+    rq.batch = batch; rq.opts = &opt; rq.prompts = &prompt; rq.n_prompts = &n_prompt;
+    rq.language_tokens = language_tokens; rq.temperatures = temperatures; rq.active = active; rq.seed = seed;
+    return decode_text_impl(s, st, rq, out);
 }
 // The steps, in the order they run: 1 validate (from here), 2 stage the slots, 3 arm the modes, 4 run, 5 back to the home layout, 6 collect.  They share the
-// call's arguments and the class view (cls_*, init_slot, finalise_options), so they are the sections of one function; the pass state they switch on is s->pass
-static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options* opt, const wh_special_tokens* st, const int32_t* prompt,
-                            int n_prompt, const int32_t* language_tokens, const float* temperatures, const int32_t* active, uint64_t seed,
-                            wh_decoding_result* out, const MixClasses* mix) {
+// request and its view by home slot (prompt_of, options_of, init_slot), so they are the sections of one function; the pass state they switch on is s->pass
+static int decode_text_impl(wh_session* s, const wh_special_tokens* st, const PassRequest& rq, wh_decoding_result* out) {
+    const int batch = rq.batch;
     CHECK_SESSION(s); CHECK_BATCH(s, batch);
-    const bool own_prompts = mix && mix->slot_prompts;      // a per-slot-prompt pass
-    if (mix) { opt = mix->opts[0]; if (!own_prompts) { prompt = mix->prompts[0]; n_prompt = mix->n_prompts[0]; } }
-    if (!opt || !st || (!prompt && !own_prompts) || !out || (own_prompts && !mix->slot_n_prompts)) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text: null argument");
+    const bool mix = rq.grain != PromptGrain::Shared, own_prompts = rq.grain == PromptGrain::PerSlot;
+    const wh_decoding_options* const opt = rq.opts ? rq.opts[0] : nullptr;
+    const int32_t* const language_tokens = rq.language_tokens; const float* const temperatures = rq.temperatures; const int32_t* const active = rq.active;
+    const uint64_t seed = rq.seed;
+    if (!opt || !st || !rq.prompts || !rq.n_prompts || (!own_prompts && !rq.prompts[0]) || !out) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text: null argument");
     const int V = s->m->dims.n_vocab;
     // per-audio rule sets (wh_session_define_rule_set; NO REFERENCE BEHAVIOUR): a pass is set-aware iff a live slot names a set other than 0; a
     // live slot that names an undefined set fails the call before anything is launched
@@ -646,39 +663,37 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
         if (bad >= 0) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text: slot %d is assigned rule set %d, which is not defined (wh_session_define_rule_set)", bad, set_of_slot[bad]);
     }
     const int prefilled_index = 0;   // decoderInputs.cacheLength after reset (Core/Models.swift:313)
-    const int n_cls = mix ? mix->n : 1;
-    auto cls_prompt = [&](int c) { return mix ? mix->prompts[c] : prompt; };
-    auto cls_n_prompt = [&](int c) { return mix ? mix->n_prompts[c] : n_prompt; };
-    auto cls_opt = [&](int c) { return mix ? mix->opts[c] : opt; };
-    auto cls_of = [&](int hb) { return mix ? mix->class_of_slot[hb] : 0; };
+    const int n_cls = rq.n;
+    auto cls_of = [&](int hb) { return rq.class_of_slot ? rq.class_of_slot[hb] : 0; };
     auto is_live = [&](int b) { return plan::slot_is_live(active, b); };
+    // home slot hb's prompt, at the request's granularity (a slot outside `active` without a prompt: an empty one), and the options its RESULT is finalised
+    // under: the audio's own thresholds (PassRequest.slot_opts), or its class's options
+    struct Prompt { const int32_t* tokens; int n; };
     static const int32_t kNoPrompt[1] = {0};
-    auto slot_prompt = [&](int hb) { return !own_prompts ? cls_prompt(cls_of(hb)) : mix->slot_prompts[hb] ? mix->slot_prompts[hb] : kNoPrompt; };      // (a slot outside `active` without a prompt: an empty one)
-    auto slot_n_prompt = [&](int hb) { return !own_prompts ? cls_n_prompt(cls_of(hb)) : mix->slot_prompts[hb] ? mix->slot_n_prompts[hb] : 0; };
-    auto finalise_options = [&](int b) { return (mix && mix->slot_opts && mix->slot_opts[b]) ? mix->slot_opts[b] : cls_opt(cls_of(b)); };      // home slot b's result: the audio's own thresholds (see MixClasses), or its class's options
+    auto prompt_of = [&](int hb) -> Prompt {
+        const int i = own_prompts ? hb : mix ? cls_of(hb) : 0;
+        return rq.prompts[i] ? Prompt{rq.prompts[i], rq.n_prompts[i]} : Prompt{kNoPrompt, 0};
+    };
+    auto options_of = [&](int hb) { return (rq.slot_opts && rq.slot_opts[hb]) ? rq.slot_opts[hb] : rq.opts[cls_of(hb)]; };
     int r = WH_OK;
-    for (int c = 0; c < n_cls; ++c) {
-        if (!cls_opt(c)) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text: null argument");
-        if (own_prompts) continue;
-        const int np = cls_n_prompt(c);
-        if (!cls_prompt(c)) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text: null argument");
-        if (np < 1 || np >= kMaxTok) return set_error(WH_ERR_PREFILL_FAILED, "wh_decode_text: prompt length %d out of range [1,%d)", np, kMaxTok);
-        if ((r = whi::check_prompt_tokens("wh_decode_text", cls_prompt(c), np, V, WH_ERR_PREFILL_FAILED))) return r;
-    }
-    for (int b = 0; own_prompts && b < batch; ++b) {      // per slot: a slot that decodes brings its prompt; one that does not may bring none (a bad one is still refused)
-        if (!mix->slot_prompts[b]) {
-            if (is_live(b)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text: slot %d decodes and has no prompt", b);
+    for (int c = 0; c < n_cls; ++c) if (!rq.opts[c]) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text: null argument");
+    // the prompt table.  Per slot: a slot that decodes brings its prompt; one that does not may bring none (a bad one is still refused)
+    for (int i = 0, n_tab = own_prompts ? batch : n_cls; i < n_tab; ++i) {
+        if (!rq.prompts[i]) {
+            if (!own_prompts) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text: null argument");
+            if (is_live(i)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text: slot %d decodes and has no prompt", i);
             continue;
         }
-        const int np = mix->slot_n_prompts[b];
-        if (np < 1 || np >= kMaxTok) return set_error(WH_ERR_PREFILL_FAILED, "wh_decode_text: slot %d: prompt length %d out of range [1,%d)", b, np, kMaxTok);
-        if ((r = whi::check_prompt_tokens("wh_decode_text", mix->slot_prompts[b], np, V, WH_ERR_PREFILL_FAILED))) return r;
+        const int np = rq.n_prompts[i];
+        if ((np < 1 || np >= kMaxTok) && own_prompts) return set_error(WH_ERR_PREFILL_FAILED, "wh_decode_text: slot %d: prompt length %d out of range [1,%d)", i, np, kMaxTok);
+        if (np < 1 || np >= kMaxTok) return set_error(WH_ERR_PREFILL_FAILED, "wh_decode_text: prompt length %d out of range [1,%d)", np, kMaxTok);
+        if ((r = whi::check_prompt_tokens("wh_decode_text", rq.prompts[i], np, V, WH_ERR_PREFILL_FAILED))) return r;
     }
     // (an unmixed pass: entry 0 of the tables, as ever; a mixed one: every class's entries behind one synchronisation.  A per-slot-prompt pass: its samplers take
     // the timestamp rules' sampleBegin from the slot's prompt_len, the entries' initial_prompt_index is not read)
     const int32_t no_np[kMaxOptionClasses] = {};
-    r = mix ? whi::upload_sampler_cfg_classes(s, mix->opts, own_prompts ? no_np : mix->n_prompts, n_cls, st, prefilled_index, seed)
-            : whi::upload_sampler_cfg(s, opt, st, prefilled_index, n_prompt, 0, seed);
+    r = mix ? whi::upload_sampler_cfg_classes(s, rq.opts, own_prompts ? no_np : rq.n_prompts, n_cls, st, prefilled_index, seed)
+            : whi::upload_sampler_cfg(s, opt, st, prefilled_index, rq.n_prompts[0], 0, seed);
     if (r) return r;
     if (opt->word_timestamps && s->m->n_align > 0) { r = whi::ensure_align(s); if (r) return r; }
     s->align_enabled = opt->word_timestamps && s->align;
@@ -688,8 +703,9 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
     const bool replace_lang = language_tokens && wh_is_model_multilingual(s->m);
     // the decode state of home slot hb as the pass starts it
     auto init_slot = [&](SeqState& q, int hb, bool act) {
-        const int c = cls_of(hb), lang_pos = whi::prompt_language_position(slot_prompt(hb), slot_n_prompt(hb), st->start_of_transcript_token, replace_lang);
-        whi::seq_init_prompt(q, slot_prompt(hb), slot_n_prompt(hb), lang_pos, lang_pos >= 0 ? language_tokens[hb] : -1, V);
+        const Prompt p = prompt_of(hb);
+        const int c = cls_of(hb), lang_pos = whi::prompt_language_position(p.tokens, p.n, st->start_of_transcript_token, replace_lang);
+        whi::seq_init_prompt(q, p.tokens, p.n, lang_pos, lang_pos >= 0 ? language_tokens[hb] : -1, V);
         q.active = act ? 1 : 0;
         q.temperature = f16_round(temperatures ? temperatures[hb] : opt->temperature);
         q.rng_lane = seq_pack_lane(hb, c);      // the slot's random stream (T > 0) does not depend on where the slot is decoded; its option class (0 unless mixed)
@@ -724,8 +740,8 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
         ns_opts.assign((size_t)batch, nullptr);
         for (int b = 0; b < batch; ++b) {
             const bool act = is_live(b);
-            const wh_decoding_options* fo = finalise_options(b);
-            pos[b] = act ? plan::nospeech_position(slot_prompt(b), slot_n_prompt(b), st->start_of_transcript_token) : -1;
+            const wh_decoding_options* fo = options_of(b);
+            pos[b] = act ? plan::nospeech_position(prompt_of(b).tokens, prompt_of(b).n, st->start_of_transcript_token) : -1;
             stop[b] = plan::nospeech_stop_threshold(s->no_speech_detection, fo);
             if (act) ns_opts[b] = fo;
         }
@@ -738,8 +754,9 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
         std::vector<std::vector<int32_t>> seen;
         for (int b = 0; b < batch; ++b) {
             if (!is_live(b)) continue;
-            seen.emplace_back(slot_prompt(b), slot_prompt(b) + slot_n_prompt(b));
-            s->sp_positions += slot_n_prompt(b);
+            const Prompt p = prompt_of(b);
+            seen.emplace_back(p.tokens, p.tokens + p.n);
+            s->sp_positions += p.n;
         }
         std::sort(seen.begin(), seen.end());
         s->sp_passes += 1;
@@ -781,7 +798,7 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
     WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * width, hipMemcpyHostToDevice, s->st));
     launch_rules_init(s->cfg_dev, s->seq, width, s->st, s->pass.mixed);
     int loop_count = 0;       // a slot finishes at its class's count (SamplerCfg.loop_count); the host loop runs to the largest
-    for (int c = 0; c < n_cls; ++c) loop_count = std::max(loop_count, std::min(cls_opt(c)->sample_length, kMaxTok - 1));
+    for (int c = 0; c < n_cls; ++c) loop_count = std::max(loop_count, std::min(rq.opts[c]->sample_length, kMaxTok - 1));
     s->skip_special_in_progress = opt->skip_special_tokens != 0;
     s->special_begin_in_progress = st->special_token_begin;
     // in-pass compaction (wh_session_set_inpass_compaction 1): the pass may narrow between step graphs as its slots finish (run_token_loop)
@@ -826,7 +843,7 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
     if (alt_on) { r = whi::alternatives_collect(s, batch, active); if (r) return r; }
     for (int b = 0; b < batch; ++b) {
         if (!s->seq_host[b].active) { memset(&out[b], 0, sizeof(out[b])); continue; }
-        whi::finalize_decoding_result(s->seq_host[b], finalise_options(b), st, s->seq_host[b].temperature, &out[b], ns_on ? whi::nospeech_prob(s, b) : 0.0f);
+        whi::finalize_decoding_result(s->seq_host[b], options_of(b), st, s->seq_host[b].temperature, &out[b], ns_on ? whi::nospeech_prob(s, b) : 0.0f);
         if (alt_on) {      // result token i is the list's token start + i (finalize_decoding_result's slice): where wh_decode_alternatives finds its row
             const SeqState& q = s->seq_host[b];
             int start = 0;
@@ -838,62 +855,61 @@ static int decode_text_impl(wh_session* s, int batch, const wh_decoding_options*
     return WH_OK;
 }
 
-// wh_decode_text with an option class per slot.  What needs no session is checked first: a caller learns about a bad class table without a device.
-extern "C" int wh_decode_text_mixed(wh_session* s, int batch, const wh_decoding_options* opts, int n_classes, const int32_t* class_of_slot,
-                                    const wh_special_tokens* st, const int32_t* const* prompts, const int32_t* n_prompts, const int32_t* language_tokens,
-                                    const float* temperatures, const int32_t* active, uint64_t seed, wh_decoding_result* out) {
-    if (n_classes < 1 || n_classes > kMaxOptionClasses)
-        return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text_mixed: %d option classes (1 .. %d)", n_classes, kMaxOptionClasses);
-    if (!opts || !class_of_slot) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text_mixed: null class table");
+// The class table of wh_decode_text_mixed / wh_decode_text_slot_prompts.  What needs no session is checked first: a caller learns about a bad table without a device.
+// per_slot: prompts / n_prompts are [batch] by home slot (checked here); else [n_classes] (checked behind the session, as ever)
+static int check_class_table(const char* who, bool per_slot, int batch, const wh_decoding_options* opts, int n_classes, const int32_t* class_of_slot,
+                             const int32_t* const* prompts, const int32_t* n_prompts, const int32_t* active) {
+    if (n_classes < 1 || n_classes > kMaxOptionClasses) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: %d option classes (1 .. %d)", who, n_classes, kMaxOptionClasses);
+    if (!opts || !class_of_slot) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: null class table", who);
     for (int c = 1; c < n_classes; ++c)
         if (!plan::option_batch_key_equal(opts[0], opts[c]))
-            return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text_mixed: class %d differs from class 0 in a field that belongs to the pass (temperature ladder, seed, "
-                             "use_prefill_prompt, detect_language, word_timestamps, float16_logits, beam search)", c);
+            return set_error(WH_ERR_INVALID_ARGUMENT, "%s: class %d differs from class 0 in a field that belongs to the pass (temperature ladder, seed, "
+                             "use_prefill_prompt, detect_language, word_timestamps, float16_logits, beam search)", who, c);
+    if (per_slot && (!prompts || !n_prompts)) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: null prompt table", who);
     if (batch >= 1 && batch <= kMaxSessionSlots)
-        for (int b = 0; b < batch; ++b)
+        for (int b = 0; b < batch; ++b) {
             if (class_of_slot[b] < 0 || class_of_slot[b] >= n_classes)
-                return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text_mixed: slot %d names class %d of %d", b, class_of_slot[b], n_classes);
-    CHECK_SESSION(s); CHECK_BATCH(s, batch);
-    if (!st || !prompts || !n_prompts || !out) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text_mixed: null argument");
+                return set_error(WH_ERR_INVALID_ARGUMENT, "%s: slot %d names class %d of %d", who, b, class_of_slot[b], n_classes);
+            if (per_slot && !prompts[b] && plan::slot_is_live(active, b)) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: slot %d decodes and has no prompt", who, b);
+        }
+    return WH_OK;
+}
+// the progress callback's skip_special_tokens by home slot, for the duration of a pass or a group over slots with options of their own
+struct SkipScope { wh_session* s; const int32_t* keep; ~SkipScope() { s->skip_special_by_slot = keep; } };
+// the pass of a checked class table
+static int decode_class_table(wh_session* s, PromptGrain grain, int batch, const wh_decoding_options* opts, int n_classes, const int32_t* class_of_slot,
+                              const wh_special_tokens* st, const int32_t* const* prompts, const int32_t* n_prompts, const int32_t* language_tokens,
+                              const float* temperatures, const int32_t* active, uint64_t seed, wh_decoding_result* out) {
     const wh_decoding_options* po[kMaxOptionClasses];
     int32_t skip[kMaxSessionSlots];
     for (int c = 0; c < n_classes; ++c) po[c] = &opts[c];
     for (int b = 0; b < batch; ++b) skip[b] = opts[class_of_slot[b]].skip_special_tokens != 0;
-    const MixClasses mix{n_classes, po, class_of_slot, prompts, n_prompts, nullptr};
-    struct SkipScope { wh_session* s; const int32_t* keep; ~SkipScope() { s->skip_special_by_slot = keep; } } skip_scope{s, s->skip_special_by_slot};
+    PassRequest rq;
+    rq.batch = batch; rq.n = n_classes; rq.opts = po; rq.class_of_slot = class_of_slot; rq.grain = grain; rq.prompts = prompts; rq.n_prompts = n_prompts;
+    rq.language_tokens = language_tokens; rq.temperatures = temperatures; rq.active = active; rq.seed = seed;
+    SkipScope skip_scope{s, s->skip_special_by_slot};
     s->skip_special_by_slot = skip;
-    return decode_text_impl(s, batch, nullptr, st, nullptr, 0, language_tokens, temperatures, active, seed, out, &mix);
+    return decode_text_impl(s, st, rq, out);
+}
+
+// wh_decode_text with an option class per slot, one prompt per class
+extern "C" int wh_decode_text_mixed(wh_session* s, int batch, const wh_decoding_options* opts, int n_classes, const int32_t* class_of_slot,
+                                    const wh_special_tokens* st, const int32_t* const* prompts, const int32_t* n_prompts, const int32_t* language_tokens,
+                                    const float* temperatures, const int32_t* active, uint64_t seed, wh_decoding_result* out) {
+    if (int r = check_class_table("wh_decode_text_mixed", false, batch, opts, n_classes, class_of_slot, prompts, n_prompts, active)) return r;
+    CHECK_SESSION(s); CHECK_BATCH(s, batch);
+    if (!st || !prompts || !n_prompts || !out) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text_mixed: null argument");
+    return decode_class_table(s, PromptGrain::PerClass, batch, opts, n_classes, class_of_slot, st, prompts, n_prompts, language_tokens, temperatures, active, seed, out);
 }
 
 // wh_decode_text_mixed with the prompt per SLOT.  The same checks in the same order, then the prompts: all before the session is looked at.
 extern "C" int wh_decode_text_slot_prompts(wh_session* s, int batch, const wh_decoding_options* opts, int n_classes, const int32_t* class_of_slot,
                                            const wh_special_tokens* st, const int32_t* const* prompts, const int32_t* n_prompts, const int32_t* language_tokens,
                                            const float* temperatures, const int32_t* active, uint64_t seed, wh_decoding_result* out) {
-    if (n_classes < 1 || n_classes > kMaxOptionClasses)
-        return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text_slot_prompts: %d option classes (1 .. %d)", n_classes, kMaxOptionClasses);
-    if (!opts || !class_of_slot) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text_slot_prompts: null class table");
-    for (int c = 1; c < n_classes; ++c)
-        if (!plan::option_batch_key_equal(opts[0], opts[c]))
-            return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text_slot_prompts: class %d differs from class 0 in a field that belongs to the pass (temperature ladder, seed, "
-                             "use_prefill_prompt, detect_language, word_timestamps, float16_logits, beam search)", c);
-    if (!prompts || !n_prompts) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text_slot_prompts: null prompt table");
-    if (batch >= 1 && batch <= kMaxSessionSlots)
-        for (int b = 0; b < batch; ++b) {
-            if (class_of_slot[b] < 0 || class_of_slot[b] >= n_classes)
-                return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text_slot_prompts: slot %d names class %d of %d", b, class_of_slot[b], n_classes);
-            if (!prompts[b] && plan::slot_is_live(active, b))
-                return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text_slot_prompts: slot %d decodes and has no prompt", b);
-        }
+    if (int r = check_class_table("wh_decode_text_slot_prompts", true, batch, opts, n_classes, class_of_slot, prompts, n_prompts, active)) return r;
     CHECK_SESSION(s); CHECK_BATCH(s, batch);
     if (!st || !out) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text_slot_prompts: null argument");
-    const wh_decoding_options* po[kMaxOptionClasses];
-    int32_t skip[kMaxSessionSlots];
-    for (int c = 0; c < n_classes; ++c) po[c] = &opts[c];
-    for (int b = 0; b < batch; ++b) skip[b] = opts[class_of_slot[b]].skip_special_tokens != 0;
-    const MixClasses mix{n_classes, po, class_of_slot, nullptr, nullptr, nullptr, prompts, n_prompts};
-    struct SkipScope { wh_session* s; const int32_t* keep; ~SkipScope() { s->skip_special_by_slot = keep; } } skip_scope{s, s->skip_special_by_slot};
-    s->skip_special_by_slot = skip;
-    return decode_text_impl(s, batch, nullptr, st, nullptr, 0, language_tokens, temperatures, active, seed, out, &mix);
+    return decode_class_table(s, PromptGrain::PerSlot, batch, opts, n_classes, class_of_slot, st, prompts, n_prompts, language_tokens, temperatures, active, seed, out);
 }
 
 // decodeText with caller-supplied LogitsFiltering / TokenSampling objects: the reference's host loop (Core/TextDecoder.swift:573-757)
@@ -1794,336 +1810,368 @@ static bool job_next_window(AudioJob& j, const wh_decoding_options* opt) {
     return false;
 }
 
+// the window in flight of job j into slot b of session s: the main session and, on a speculative rung, the draft
+static int job_set_window(wh_session* s, int b, const AudioJob& j) {
+    return j.dev ? wh_set_audio_device(s, b, j.pcm + j.cur_seek, j.cur_size) : wh_set_audio(s, b, j.pcm + j.cur_seek, j.cur_size);
+}
+
+// What transcribe_jobs settles once for its group; the stages of a round read it
+struct GroupPlan {
+    const wh_decoding_options* opt; const wh_special_tokens* st;
+    const std::vector<const wh_decoding_options*>* classes;      // the option classes; a group without classes is its one option set
+    bool mixed, slot_prompts, carrying;                          // the group has classes; every window brings its prompt; ... with the audio's carry in it
+    bool multilingual, detect, job_sets;                         // (job_sets: an audio of the group names a rule set other than 0)
+    int beam;
+    std::vector<float> temps;                                    // the fallback ladder
+    double t_start, cf_start;
+    const wh_decoding_options* options_of(const AudioJob& j) const { return mixed ? j.opt : opt; }      // what the host reads per audio: windowing, thresholds, text
+};
+// temperature ladder in FloatType (TranscribeTask.swift:327)
+static std::vector<float> temperature_ladder(const wh_decoding_options* opt) {
+    std::vector<float> temps;
+    for (int i = 0; i <= opt->temperature_fallback_count; ++i)
+        temps.push_back(f16_round(f16_round(opt->temperature) + f16_round(f16_round((float)i) * f16_round(opt->temperature_increment_on_fallback))));
+    return temps;
+}
+
+// One round: one window from every job that still has one, in the slot its position gives, from gathering to windowing
+struct Round {
+    std::vector<int> slot_job;                             // job index per slot
+    double t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0;         // stage timestamps: gather, log-mel, encoder, decode begin; decode ends
+    std::vector<wh_decoding_result> res, tmp;              // the result kept per slot; the rung's
+    // language token per slot: every audio of the batch detects (and is prompted with) its own language, like the reference's
+    // one TranscribeTask per audio (WhisperKit.swift:735-792); -1 = the options' language / English default of prefillDecoderInputs
+    std::vector<int32_t> lang_slot;
+    // (a group with classes) per slot: its class, its skip_special_tokens for the progress callback, its audio's stated language (-1: it detects) and its own
+    // options: its result's fallback decision (finalize_decoding_result)
+    std::vector<int32_t> cls_slot, skip_slot, stated_lang;
+    std::vector<const wh_decoding_options*> opt_slot;
+    std::vector<const int32_t*> slot_prompt; std::vector<int32_t> slot_n_prompt;      // (per-slot prompts) the prompt of every slot's window
+    std::vector<std::vector<int32_t>> prompt;              // the group's prompt [1], or (classes without per-slot prompts) one per class
+    std::vector<const int32_t*> prompt_p; std::vector<int32_t> prompt_n;
+    // word alignment on the device: the batch's DTW paths (whi::alignment_paths), the seconds they took
+    bool device_paths = false; const int32_t *path_len = nullptr, *path_ti = nullptr, *path_tj = nullptr; double device_align_s = 0;
+    int nb() const { return (int)slot_job.size(); }
+};
+
+// Gather up to round_cap jobs that still have a window (each job contributes one window per round: windows of one audio are sequential).
+// A window whose padOrTrim fails (TranscribeTask.swift:126-127 throws audioProcessingFailed) fails ITS audio only: the audio leaves the
+// batch with its status and message, its neighbours go on (the reference wraps every audio in its own Result, WhisperKit.swift:786-790).
+static int round_gather(wh_session* s, std::vector<AudioJob>& jobs, Round& R, const GroupPlan& G, int round_cap) {
+    const wh_special_tokens* st = G.st;
+    R.t0 = now_s();
+    for (size_t ji = 0; ji < jobs.size() && R.nb() < round_cap; ++ji) {
+        AudioJob& j = jobs[ji];
+        if (j.finished || j.status != WH_OK || !job_next_window(j, G.options_of(j))) continue;
+        const int b = R.nb();
+        bool carried = false;      // the window's prompt holds carried text: counted once the window has its slot
+        if (G.slot_prompts) {      // the window's own prompt, before it takes a slot: one that does not fit fails ITS audio
+            wh_decoding_options po = *G.options_of(j);
+            if (G.carrying) {
+                if (!j.carry_started) { plan::carry_start(j.carry, po.prompt_tokens, po.n_prompt_tokens, st->special_token_begin); j.carry_started = true; }
+                po.prompt_tokens = plan::carry_prompt(j.carry, &po.n_prompt_tokens);
+            }
+            const int np = build_prompt(s->m, po, st, j.cur_prompt);
+            if (np <= 0 || np >= kMaxTok) {
+                j.status = set_error(WH_ERR_PREFILL_FAILED, "audio %d: prefill prompt does not fit", j.index); j.error = wh_last_error(); j.finished = true;
+                continue;
+            }
+            carried = G.carrying && po.prompt_tokens;
+        }
+        // a window without samples: the reference slices audioArray[seek ..< seek + segmentSize], AudioProcessor.padOrTrimAudio returns nil for
+        // the empty slice ("startIndex is outside the buffer size", Core/Audio/AudioProcessor.swift:151-155) and the task throws
+        // transcriptionFailed("Audio samples are nil") (Core/TranscribeTask.swift:126-129) - a clip that ends beyond the samples gets here
+        int r = j.cur_size > 0 ? job_set_window(s, b, j)
+                               : set_error(WH_ERR_TRANSCRIPTION_FAILED, "audio %d: Audio samples are nil (window start %d is outside the buffer size %d)", j.index, j.cur_seek, j.n);
+        if (r == WH_ERR_HIP) return r;                                 // the device is gone: every audio of the group fails
+        if (r) { j.status = r; j.error = wh_last_error(); j.finished = true; continue; }
+        R.slot_job.push_back((int)ji);
+        if (carried) s->sp_windows_carried += 1;
+        if (s->hooks.window_preprocess) {                              // TranscribeTask.windowPreprocess (:130)
+            const float* win = j.pcm + j.cur_seek;
+            std::vector<float> copy;
+            if (j.dev) {                                               // the hook expects host samples: it gets a copy of its window
+                copy.resize((size_t)j.cur_size);
+                WH_HIP(hipMemcpyAsync(copy.data(), win, sizeof(float) * (size_t)j.cur_size, hipMemcpyDeviceToHost, s->st));
+                WH_HIP(hipStreamSynchronize(s->st));
+                j.dev->d2h_bytes += (long long)sizeof(float) * j.cur_size;
+                win = copy.data();
+            }
+            s->hooks.window_preprocess(s->hooks.user, j.index, win, j.cur_seek, j.cur_size);
+        }
+        j.tr->seeks.push_back(j.cur_seek);
+    }
+    return WH_OK;
+}
+
+// log-mel, encoder and the decoder's inputs for the round's windows
+static int round_encode(wh_session* s, const std::vector<AudioJob>& jobs, Round& R, const GroupPlan& G) {
+    const int nb = R.nb();
+    // per-audio rule sets: the round's windows name their audios' sets by home slot (decode_text_impl uploads the table for every set-aware pass)
+    if (G.job_sets) {
+        s->rs_slot.assign((size_t)s->B, 0);
+        for (int b = 0; b < nb; ++b) s->rs_slot[(size_t)b] = jobs[R.slot_job[b]].rule_set;
+    }
+    R.t1 = now_s();
+    int r = wh_log_mel_spectrogram(s, nb); if (r) return r;
+    hipStreamSynchronize(s->st);
+    R.t2 = now_s();
+    r = wh_encode_features(s, nb); if (r) return r;
+    r = wh_prepare_decoder_inputs(s, nb); if (r) return r;
+    hipStreamSynchronize(s->st);
+    R.t3 = now_s();
+    return WH_OK;
+}
+
+// The prompt table of the round's passes, once per round: the group's prompt, or one per class.  A prompt that does not fit is an error of the call
+static int round_prompts(const wh_session* s, Round& R, const GroupPlan& G) {
+    if (!R.prompt.empty() || (G.mixed && G.slot_prompts)) return WH_OK;      // (classes whose windows bring their prompts: no table)
+    for (const wh_decoding_options* co : *G.classes) {
+        std::vector<int32_t> pr;
+        if (build_prompt(s->m, *co, G.st, pr) <= 0) return set_error(WH_ERR_PREFILL_FAILED, "prefill prompt does not fit");
+        R.prompt.push_back(std::move(pr));
+    }
+    for (const auto& pr : R.prompt) { R.prompt_p.push_back(pr.data()); R.prompt_n.push_back((int32_t)pr.size()); }
+    return WH_OK;
+}
+
+// decodeWithFallback (TranscribeTask.swift:316-411), all slots in lock step per temperature: R.res holds every slot's kept result
+static int round_decode(wh_session* s, std::vector<AudioJob>& jobs, Round& R, const GroupPlan& G) {
+    const wh_decoding_options* opt = G.opt;
+    const wh_special_tokens* st = G.st;
+    const int nb = R.nb();
+    R.res.resize(nb); R.tmp.resize(nb);
+    std::vector<int32_t> active(nb, 1);
+    R.lang_slot.assign(nb, opt->language_token);
+    bool any_detects = opt->language_token < 0;
+    if (G.slot_prompts)
+        for (int b = 0; b < nb; ++b) { R.slot_prompt.push_back(jobs[R.slot_job[b]].cur_prompt.data()); R.slot_n_prompt.push_back((int32_t)jobs[R.slot_job[b]].cur_prompt.size()); }
+    if (G.mixed) {
+        R.cls_slot.resize(nb); R.skip_slot.resize(nb); R.opt_slot.resize(nb); R.stated_lang.resize(nb);
+        any_detects = false;
+        for (int b = 0; b < nb; ++b) {
+            const AudioJob& j = jobs[R.slot_job[b]];
+            R.cls_slot[b] = j.cls; R.opt_slot[b] = j.opt; R.skip_slot[b] = j.opt->skip_special_tokens != 0; R.lang_slot[b] = R.stated_lang[b] = j.opt->language_token;
+            any_detects |= j.opt->language_token < 0;
+        }
+        s->skip_special_by_slot = R.skip_slot.data();      // (transcribe_jobs puts it back)
+    }
+    for (size_t ti = 0; ti < G.temps.size(); ++ti) {
+        CHECK_CANCEL(s);
+        std::vector<float> tv(nb, G.temps[ti]);
+        bool per_slot_lang = false;
+        int r;
+        if (G.multilingual && any_detects && G.detect) {
+            std::vector<int32_t> lt(nb); std::vector<float> ll(nb);
+            r = wh_detect_language(s, nb, st, lt.data(), ll.data()); if (r) return r;
+            for (int b = 0; b < nb; ++b) {
+                if (!active[b]) continue;
+                if (G.mixed && R.stated_lang[b] >= 0) continue;      // this audio states its language
+                R.lang_slot[b] = lt[b];
+                wh_transcription* t = jobs[R.slot_job[b]].tr;
+                if (!t->language_set) { t->language_token = lt[b]; t->language_set = true; }
+            }
+            per_slot_lang = true;
+        }
+        r = round_prompts(s, R, G); if (r) return r;
+        r = whi::reset_decoder_inputs_masked(s, nb, active.data()); if (r) return r;     // accepted slots keep their alignment rows
+        const uint64_t seed = plan::pass_seed(opt->seed, jobs[R.slot_job[0]].windows, ti);
+        const int32_t* langs = (per_slot_lang && opt->use_prefill_prompt) ? R.lang_slot.data() : nullptr;
+        plan::PassRouteInput in;
+        in.beam_size = opt->beam_size; in.temperature = G.temps[ti]; in.rung = (int)ti;
+        for (int b = 0; b < nb; ++b) in.all_active &= active[b] != 0;
+        in.slot_prompts = G.slot_prompts; in.mixed = G.mixed; in.draft = s->draft != nullptr;
+        in.no_speech = s->no_speech_detection != plan::kNoSpeechOff; in.alternatives = s->token_alternatives != 0;
+        in.logit_rules = s->logit_rules_on; in.phrase_rules = s->phrase_rules_on; in.job_sets = G.job_sets;
+        in.progress_cb = s->progress_cb != nullptr; in.spec_fits = plan::spec_fits(nb, s->draft_k, s->B);
+        plan::PassRoute route = plan::pass_route(in);
+        if (route == plan::PassRoute::Speculative && spec_check_draft("wh_transcribe", s, s->draft, nb)) route = plan::PassRoute::Plain;
+        switch (route) {
+        case plan::PassRoute::Beam: {      // (no reference behaviour, wh_decode_text_beam): the T = 0 pass expands every window into beam_size slots
+            r = wh_decode_text_beam(s, nb, G.beam, opt->beam_patience, opt, st, R.prompt_p[0], R.prompt_n[0], langs, R.tmp.data());
+            if (r) return r;
+            bool again = false;
+            for (int b = 0; b < nb; ++b) again |= R.tmp[b].needs_fallback != 0;
+            if (again && ti + 1 < G.temps.size()) { r = wh_prepare_decoder_inputs(s, nb); if (r) return r; }   // the beam slots overwrote the windows' cross K/V
+            break;
+        }
+        case plan::PassRoute::SlotPrompts: case plan::PassRoute::Mixed: {
+            const bool per_slot = route == plan::PassRoute::SlotPrompts;
+            std::vector<int32_t> ml(nb);
+            plan::slot_language_overrides(R.lang_slot.data(), G.mixed ? R.stated_lang.data() : nullptr, nb, ml.data());
+            PassRequest rq;
+            rq.batch = nb; rq.n = (int)G.classes->size(); rq.opts = G.classes->data(); rq.class_of_slot = G.mixed ? R.cls_slot.data() : nullptr;
+            rq.grain = per_slot ? PromptGrain::PerSlot : PromptGrain::PerClass;
+            rq.prompts = per_slot ? R.slot_prompt.data() : R.prompt_p.data(); rq.n_prompts = per_slot ? R.slot_n_prompt.data() : R.prompt_n.data();
+            rq.slot_opts = G.mixed ? R.opt_slot.data() : nullptr;
+            rq.language_tokens = langs ? ml.data() : nullptr; rq.temperatures = tv.data(); rq.active = active.data(); rq.seed = seed;
+            r = decode_text_impl(s, st, rq, R.tmp.data());
+            if (r) return r;
+            break;
+        }
+        case plan::PassRoute::Speculative: {
+            // first rung with a draft attached (wh_session_set_draft) and room for the rings: the speculative pass (results are the ordinary pass's).  The
+            // draft gets the same windows through its own log-mel and encoder
+            wh_session* const dr = s->draft;
+            for (int b = 0; b < nb; ++b) { r = job_set_window(dr, b, jobs[R.slot_job[b]]); if (r) return r; }
+            r = wh_log_mel_spectrogram(dr, nb); if (r) return r;
+            r = wh_encode_features(dr, nb); if (r) return r;
+            r = wh_prepare_decoder_inputs(dr, nb); if (r) return r;
+            r = wh_decode_text_speculative(s, dr, nb, s->draft_k, opt, st, R.prompt_p[0], R.prompt_n[0], langs, R.tmp.data());
+            if (r) return r;
+            break;
+        }
+        case plan::PassRoute::Plain:
+            r = wh_decode_text_languages(s, nb, opt, st, R.prompt_p[0], R.prompt_n[0], langs, tv.data(), active.data(), seed, R.tmp.data());
+            if (r) return r;
+            break;
+        }
+        bool any = false;
+        for (int b = 0; b < nb; ++b) {
+            if (!active[b]) continue;
+            R.res[b] = R.tmp[b];
+            AudioJob& j = jobs[R.slot_job[b]];
+            j.tr->timings.total_decoding_loops += R.tmp[b].steps;
+            if (R.tmp[b].needs_fallback && ti + 1 < G.temps.size()) { any = true; j.tr->timings.total_decoding_fallbacks += 1; }
+            else active[b] = 0;
+        }
+        if (!any) break;
+    }
+    R.t4 = now_s();
+    return WH_OK;
+}
+
+// Word alignment on the device (wh_session_set_word_alignment 1): every slot's DTW row count is known from its result alone
+// (wh_word_alignment_rows), so the whole batch is aligned by one head-mean launch, one DTW launch and one copy of the paths
+static int round_align(wh_session* s, const std::vector<AudioJob>& jobs, Round& R, const GroupPlan& G) {
+    R.device_paths = s->word_alignment == 1 && G.opt->word_timestamps && s->align;
+    if (!R.device_paths) return WH_OK;
+    const int nb = R.nb();
+    std::vector<int32_t> rows(nb);
+    for (int b = 0; b < nb; ++b) { rows[b] = wh_word_alignment_rows(&R.res[b], G.options_of(jobs[R.slot_job[b]]), G.st, s->tok != nullptr); if (rows[b] < 0) return WH_ERR_SEGMENTING_FAILED; }
+    int r = whi::alignment_paths(s, nb, rows.data(), &R.path_len, &R.path_ti, &R.path_tj); if (r) return r;
+    R.device_align_s = now_s() - R.t4;
+    return WH_OK;
+}
+
+// Windowing (TranscribeTask.swift:175-278) of slot b's kept result: its segments, alternatives, the hooks, the carry, the audio's seek and timings
+static int round_window(wh_session* s, std::vector<AudioJob>& jobs, Round& R, const GroupPlan& G, int b) {
+    const wh_special_tokens* st = G.st;
+    const int nb = R.nb();
+    AudioJob& j = jobs[R.slot_job[b]];
+    wh_transcription* tr = j.tr;
+    const wh_decoding_options* const jo = G.options_of(j);
+    const wh_decoding_result& res = R.res[b];
+    int r;
+    // "Windowing" (TranscribeTask.swift:175-265) is host-only code shared with the CPU tests: wh_transcription_add_window
+    std::vector<float> full;
+    const float* alignment = nullptr;
+    if (G.opt->word_timestamps && s->align && !R.device_paths) {
+        full.resize((size_t)kMaxTok * kCtx);
+        r = wh_get_alignment_weights(s, b, full.data()); if (r) return r;
+        alignment = full.data();
+    }
+    const double windows_before = tr->timings.total_decoding_windows;
+    int32_t seek = j.seek;
+    const int seg_before = (int)tr->segments.size();
+    if (R.device_paths) {
+        r = wh_transcription_add_window_path(tr, s->tok, jo, st, &res, R.path_ti + (size_t)b * kDtwPathCap, R.path_tj + (size_t)b * kDtwPathCap,
+                                             R.path_len[b], R.lang_slot[b], j.cur_size, &seek);
+        tr->timings.decoding_word_timestamps += R.device_align_s / nb;      // the batch's device stage, shared out like the other stages
+    } else {
+        r = wh_transcription_add_window(tr, s->tok, jo, st, &res, alignment, R.lang_slot[b], j.cur_size, &seek);
+    }
+    if (r) return r;
+    j.seek = seek;
+    const bool had_segments = tr->timings.total_decoding_windows > windows_before;      // (`guard let currentSegments`, :239-242)
+    // token alternatives: the rows of the rung whose result is kept (its pass was the last to decode home slot b), sliced by the segments just cut
+    if (s->token_alternatives > 0 && had_segments) {
+        int n_alt = 0, n_rows = 0;
+        std::vector<int32_t> aid((size_t)WH_MAX_RESULT_TOKENS * plan::kMaxAlternatives);
+        std::vector<float> alp((size_t)WH_MAX_RESULT_TOKENS * plan::kMaxAlternatives), aen((size_t)WH_MAX_RESULT_TOKENS);
+        r = wh_decode_alternatives(s, b, aid.data(), alp.data(), aen.data(), &n_alt, &n_rows); if (r) return r;
+        if (n_alt > 0 && n_rows == res.n_tokens) { r = wh_transcription_set_window_alternatives(tr, n_alt, aid.data(), alp.data(), aen.data(), n_rows); if (r) return r; }
+    }
+    if (had_segments) {
+        int n_new = (int)tr->segments.size() - seg_before;
+        if (s->hooks.window_postprocess) {                         // TranscribeTask.windowPostProcess (:246-250)
+            const int keep = s->hooks.window_postprocess(s->hooks.user, j.index, j.cur_seek, j.cur_size, tr, seg_before, n_new);
+            if (keep >= 0 && keep < n_new) { whi::transcription_truncate_segments(tr, seg_before + keep); n_new = keep; }
+        }
+        if (s->hooks.segment_discovery) s->hooks.segment_discovery(s->hooks.user, j.index, tr, seg_before, n_new);   // segmentDiscoveryCallback (:260)
+    }
+    if (G.carrying) {      // the segments the window added, as they stand now, go into the audio's carry
+        const int n_seg = had_segments ? (int)tr->segments.size() - seg_before : 0;
+        const int tok0 = n_seg > 0 ? tr->segments[(size_t)seg_before].token_offset : 0;
+        const int tok1 = n_seg > 0 ? tr->segments.back().token_offset + tr->segments.back().n_tokens : 0;
+        if (plan::carry_after_window(j.carry, n_seg, tr->tokens.data() + tok0, tok1 - tok0, res.temperature, s->previous_text_reset, st->special_token_begin)) s->sp_resets += 1;
+    }
+    if (had_segments) j.windows += 1;
+    tr->timings.audio_processing += (R.t1 - R.t0) / nb; tr->timings.logmels += (R.t2 - R.t1) / nb; tr->timings.encoding += (R.t3 - R.t2) / nb;
+    tr->timings.decoding_loop += (R.t4 - R.t3) / nb; tr->timings.total_logmel_runs += 1; tr->timings.total_encoding_runs += 1;
+    tr->timings.total_audio_processing_runs += 1;
+    tr->timings.decoding_windowing += (now_s() - R.t4) / nb;
+    if (tr->timings.first_token_time == 0) tr->timings.first_token_time = G.cf_start + (R.t4 - G.t_start);   // first decode of this audio done
+    return WH_OK;
+}
+
 // classes: null, or (option mixing) the options that stand for the option classes of this group - job j decodes under class j.cls and everything the
 // host reads per audio (windowing, thresholds, text) comes from the job's own options; `opt` is then class 0 and serves the batch-key fields, which are
 // equal over the group (option_mix.h).  Null: every job runs under `opt`, as ever.
 // slot_prompts (a mixed group under wh_session_set_prompt_mixing 1): the classes do not hold the prompt - every window decodes under its audio's own prompt.
 // Previous-text conditioning (wh_session_set_previous_text 1, a group that prefills and does not beam-search) switches the same route on for any group, with
 // the audio's carry as its prompt_tokens; a group without classes is then one class.
+// The group-level checks and the ladder are here; a round's work is in its stages: round_gather, round_encode, round_decode, round_align, round_window.
 static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_decoding_options* opt, const wh_special_tokens* st,
                            const std::vector<const wh_decoding_options*>* classes = nullptr, bool slot_prompts = false) {
-    const wh_model* m = s->m;
-    const bool mixed = classes != nullptr;
     if (s->previous_text == plan::kPreviousTextOn && opt->beam_size > 1)
         return set_error(WH_ERR_INVALID_ARGUMENT, "beam_size > 1 cannot be combined with previous-text conditioning (wh_session_set_previous_text)");
-    const bool carrying = s->previous_text == plan::kPreviousTextOn && opt->use_prefill_prompt != 0;
-    slot_prompts = (slot_prompts && mixed) || carrying;
     const std::vector<const wh_decoding_options*> one_class{opt};
-    const std::vector<const wh_decoding_options*>& sp_classes = mixed ? *classes : one_class;
-    auto jopt = [&](const AudioJob& j) { return mixed ? j.opt : opt; };
-    struct SkipScope { wh_session* s; ~SkipScope() { s->skip_special_by_slot = nullptr; } } skip_scope{s};
-    const bool multilingual = wh_is_model_multilingual(m) != 0;
-    const int detect = opt->detect_language < 0 ? !opt->use_prefill_prompt : opt->detect_language;
-    const double t_start = now_s();
-    const double cf_start = cf_absolute_time();
+    GroupPlan G;
+    G.opt = opt; G.st = st; G.mixed = classes != nullptr; G.classes = G.mixed ? classes : &one_class;
+    G.carrying = plan::carrying(s->previous_text, opt->use_prefill_prompt);
+    G.slot_prompts = plan::slot_prompts_route(slot_prompts, G.mixed, G.carrying);
+    G.multilingual = wh_is_model_multilingual(s->m) != 0;
+    G.detect = plan::detects_language(opt->detect_language, opt->use_prefill_prompt);
+    G.t_start = now_s(); G.cf_start = cf_absolute_time();
+    SkipScope skip_scope{s, nullptr};
     for (auto& j : jobs) { const wh_decoding_options* jo = j.opt ? j.opt : opt;      // clip timestamps belong to the audio, not to its group
                           j.clips = prepare_seek_clips(jo, j.n); j.tr->timings.input_audio_seconds = (double)j.n / WH_SAMPLE_RATE - (double)(jo->n_clip_timestamps > 0 && jo->clip_timestamps ? jo->clip_timestamps[0] : 0.0f);
-                          j.tr->timings.pipeline_start = cf_start; }
-    // temperature ladder in FloatType (TranscribeTask.swift:327)
-    std::vector<float> temps;
-    for (int i = 0; i <= opt->temperature_fallback_count; ++i)
-        temps.push_back(f16_round(f16_round(opt->temperature) + f16_round(f16_round((float)i) * f16_round(opt->temperature_increment_on_fallback))));
-
+                          j.tr->timings.pipeline_start = G.cf_start; }
+    G.temps = temperature_ladder(opt);
     // beam search (no reference behaviour, wh_decode_text_beam): the T = 0 pass expands every window into beam_size slots
-    const int beam = opt->beam_size > 1 ? opt->beam_size : 1;
+    const int beam = G.beam = opt->beam_size > 1 ? opt->beam_size : 1;
     if (beam > 1 && opt->word_timestamps) return set_error(WH_ERR_INVALID_ARGUMENT, "beam_size > 1 cannot be combined with word_timestamps");
     if (beam > 1 && s->token_alternatives > 0) return set_error(WH_ERR_INVALID_ARGUMENT, "beam_size > 1 cannot be combined with token alternatives (wh_session_set_token_alternatives)");
     if (beam > 1 && s->logit_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "beam_size > 1 cannot be combined with the session's logit rules (wh_session_set_logit_rules)");
     if (beam > 1 && s->phrase_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "beam_size > 1 cannot be combined with the session's phrase rules (wh_session_set_phrase_rules)");
-    bool job_sets = false;      // per-audio rule sets: does an audio of this group name a set other than 0?  (the set never splits a group: rule_sets_plan.h)
-    for (const auto& j : jobs) job_sets |= j.rule_set != 0;
+    G.job_sets = false;      // per-audio rule sets: does an audio of this group name a set other than 0?  (the set never splits a group: rule_sets_plan.h)
+    for (const auto& j : jobs) G.job_sets |= j.rule_set != 0;
     s->rs_slot.clear();         // (a group before this one may have carried sets: this one starts with every slot under 0)
-    if (beam > 1 && job_sets) return set_error(WH_ERR_INVALID_ARGUMENT, "beam_size > 1 cannot be combined with a rule set (wh_transcribe_batch_with_rule_sets)");
+    if (beam > 1 && G.job_sets) return set_error(WH_ERR_INVALID_ARGUMENT, "beam_size > 1 cannot be combined with a rule set (wh_transcribe_batch_with_rule_sets)");
     if (beam > s->B) return set_error(WH_ERR_INVALID_ARGUMENT, "beam_size %d exceeds the session's %d slots", beam, s->B);
-    const int round_cap = s->B / beam;
-    std::vector<int> slot_job;   // job index per slot for the current round
     while (true) {
-        // gather up to B jobs that still have a window (each job contributes one window per round: windows of one audio are sequential)
-        // A window whose padOrTrim fails (TranscribeTask.swift:126-127 throws audioProcessingFailed) fails ITS audio only: the audio leaves the
-        // batch with its status and message, its neighbours go on (the reference wraps every audio in its own Result, WhisperKit.swift:786-790).
-        slot_job.clear();
         CHECK_CANCEL(s);
-        double t0 = now_s();
-        for (size_t ji = 0; ji < jobs.size() && (int)slot_job.size() < round_cap; ++ji) {
-            AudioJob& j = jobs[ji];
-            if (j.finished || j.status != WH_OK || !job_next_window(j, jopt(j))) continue;
-            const int b = (int)slot_job.size();
-            bool carried = false;      // the window's prompt holds carried text: counted once the window has its slot
-            if (slot_prompts) {      // the window's own prompt, before it takes a slot: one that does not fit fails ITS audio
-                wh_decoding_options po = *jopt(j);
-                if (carrying) {
-                    if (!j.carry_started) { plan::carry_start(j.carry, po.prompt_tokens, po.n_prompt_tokens, st->special_token_begin); j.carry_started = true; }
-                    po.prompt_tokens = plan::carry_prompt(j.carry, &po.n_prompt_tokens);
-                }
-                j.cur_prompt.assign(1, st->start_of_transcript_token);
-                if (po.use_prefill_prompt) {
-                    j.cur_prompt.resize(kMaxPrompt);
-                    const int np = wh_prefill_prompt(m, &po, st, po.language_token, j.cur_prompt.data(), (int)j.cur_prompt.size());
-                    if (np <= 0 || np >= kMaxTok) {
-                        j.status = set_error(WH_ERR_PREFILL_FAILED, "audio %d: prefill prompt does not fit", j.index); j.error = wh_last_error(); j.finished = true;
-                        continue;
-                    }
-                    j.cur_prompt.resize((size_t)np);
-                }
-                carried = carrying && po.prompt_tokens;
-            }
-            // a window without samples: the reference slices audioArray[seek ..< seek + segmentSize], AudioProcessor.padOrTrimAudio returns nil for
-            // the empty slice ("startIndex is outside the buffer size", Core/Audio/AudioProcessor.swift:151-155) and the task throws
-            // transcriptionFailed("Audio samples are nil") (Core/TranscribeTask.swift:126-129) - a clip that ends beyond the samples gets here
-            int r = j.cur_size > 0 ? (j.dev ? wh_set_audio_device(s, b, j.pcm + j.cur_seek, j.cur_size) : wh_set_audio(s, b, j.pcm + j.cur_seek, j.cur_size))
-                                   : set_error(WH_ERR_TRANSCRIPTION_FAILED, "audio %d: Audio samples are nil (window start %d is outside the buffer size %d)", j.index, j.cur_seek, j.n);
-            if (r == WH_ERR_HIP) return r;                                 // the device is gone: every audio of the group fails
-            if (r) { j.status = r; j.error = wh_last_error(); j.finished = true; continue; }
-            slot_job.push_back((int)ji);
-            if (carried) s->sp_windows_carried += 1;
-            if (s->hooks.window_preprocess) {                              // TranscribeTask.windowPreprocess (:130)
-                const float* win = j.pcm + j.cur_seek;
-                std::vector<float> copy;
-                if (j.dev) {                                               // the hook expects host samples: it gets a copy of its window
-                    copy.resize((size_t)j.cur_size);
-                    WH_HIP(hipMemcpyAsync(copy.data(), win, sizeof(float) * (size_t)j.cur_size, hipMemcpyDeviceToHost, s->st));
-                    WH_HIP(hipStreamSynchronize(s->st));
-                    j.dev->d2h_bytes += (long long)sizeof(float) * j.cur_size;
-                    win = copy.data();
-                }
-                s->hooks.window_preprocess(s->hooks.user, j.index, win, j.cur_seek, j.cur_size);
-            }
-            j.tr->seeks.push_back(j.cur_seek);
-        }
-        if (slot_job.empty()) break;
-        const int nb = (int)slot_job.size();
-        // per-audio rule sets: the round's windows name their audios' sets by home slot (decode_text_impl uploads the table for every set-aware pass)
-        if (job_sets) {
-            s->rs_slot.assign((size_t)s->B, 0);
-            for (int b = 0; b < nb; ++b) s->rs_slot[(size_t)b] = jobs[slot_job[b]].rule_set;
-        }
-        double t1 = now_s();
-        int r = wh_log_mel_spectrogram(s, nb); if (r) return r;
-        hipStreamSynchronize(s->st);
-        double t2 = now_s();
-        r = wh_encode_features(s, nb); if (r) return r;
-        r = wh_prepare_decoder_inputs(s, nb); if (r) return r;
-        hipStreamSynchronize(s->st);
-        double t3 = now_s();
-        // ---- decodeWithFallback (TranscribeTask.swift:316-411), all slots in lock step per temperature
-        std::vector<wh_decoding_result> res(nb), tmp(nb);
-        std::vector<int32_t> active(nb, 1);
-        std::vector<int32_t> prompt(kMaxPrompt);
-        int n_prompt = 1;
-        prompt[0] = st->start_of_transcript_token;
-        // language token per slot: every audio of the batch detects (and is prompted with) its own language, like the reference's
-        // one TranscribeTask per audio (WhisperKit.swift:735-792); -1 = the options' language / English default of prefillDecoderInputs
-        std::vector<int32_t> lang_slot(nb, opt->language_token);
-        // (option mixing) the class of every slot, the prompt of every class, each slot's skip_special_tokens for the progress callback
-        std::vector<int32_t> cls_slot, skip_slot, mix_np;
-        std::vector<const wh_decoding_options*> opt_slot;      // each slot's own options: its result's fallback decision (finalize_decoding_result)
-        std::vector<std::vector<int32_t>> mix_prompt;
-        std::vector<const int32_t*> mix_pp;
-        bool any_detects = opt->language_token < 0;
-        std::vector<const int32_t*> sp_pp; std::vector<int32_t> sp_np;      // (per-slot prompts) the prompt of every slot's window
-        if (slot_prompts) {
-            cls_slot.assign(nb, 0);
-            for (int b = 0; b < nb; ++b) { sp_pp.push_back(jobs[slot_job[b]].cur_prompt.data()); sp_np.push_back((int32_t)jobs[slot_job[b]].cur_prompt.size()); }
-        }
-        if (mixed) {
-            cls_slot.resize(nb); skip_slot.resize(nb); opt_slot.resize(nb);
-            any_detects = false;
-            for (int b = 0; b < nb; ++b) {
-                const AudioJob& j = jobs[slot_job[b]];
-                cls_slot[b] = j.cls; opt_slot[b] = j.opt; skip_slot[b] = j.opt->skip_special_tokens != 0; lang_slot[b] = j.opt->language_token;
-                any_detects |= j.opt->language_token < 0;
-            }
-            s->skip_special_by_slot = skip_slot.data();
-        }
-        for (size_t ti = 0; ti < temps.size(); ++ti) {
-            CHECK_CANCEL(s);
-            std::vector<float> tv(nb, temps[ti]);
-            bool per_slot_lang = false;
-            if (multilingual && any_detects && detect) {
-                std::vector<int32_t> lt(nb); std::vector<float> ll(nb);
-                r = wh_detect_language(s, nb, st, lt.data(), ll.data()); if (r) return r;
-                for (int b = 0; b < nb; ++b) {
-                    if (!active[b]) continue;
-                    if (mixed && jobs[slot_job[b]].opt->language_token >= 0) continue;      // this audio states its language
-                    lang_slot[b] = lt[b];
-                    wh_transcription* t = jobs[slot_job[b]].tr;
-                    if (!t->language_set) { t->language_token = lt[b]; t->language_set = true; }
-                }
-                per_slot_lang = true;
-            }
-            if (opt->use_prefill_prompt && !mixed) {
-                n_prompt = wh_prefill_prompt(m, opt, st, opt->language_token, prompt.data(), (int)prompt.size());
-                if (n_prompt <= 0) return set_error(WH_ERR_PREFILL_FAILED, "prefill prompt does not fit");
-            }
-            if (mixed && !slot_prompts && mix_prompt.empty()) {
-                for (const wh_decoding_options* co : *classes) {
-                    std::vector<int32_t> pr(kMaxPrompt);
-                    int np = 1;
-                    pr[0] = st->start_of_transcript_token;
-                    if (co->use_prefill_prompt) {
-                        np = wh_prefill_prompt(m, co, st, co->language_token, pr.data(), (int)pr.size());
-                        if (np <= 0) return set_error(WH_ERR_PREFILL_FAILED, "prefill prompt does not fit");
-                    }
-                    pr.resize((size_t)np);
-                    mix_prompt.push_back(std::move(pr)); mix_np.push_back(np);
-                }
-                for (const auto& pr : mix_prompt) mix_pp.push_back(pr.data());
-            }
-            r = whi::reset_decoder_inputs_masked(s, nb, active.data()); if (r) return r;     // accepted slots keep their alignment rows
-            uint64_t seed = opt->seed + 1000003ull * (uint64_t)jobs[slot_job[0]].windows + ti;
-            const int32_t* langs = (per_slot_lang && opt->use_prefill_prompt) ? lang_slot.data() : nullptr;
-            bool all_active = true;
-            for (int b = 0; b < nb; ++b) all_active &= active[b] != 0;
-            if (beam > 1 && temps[ti] == 0.0f && all_active) {
-                r = wh_decode_text_beam(s, nb, beam, opt->beam_patience, opt, st, prompt.data(), n_prompt, langs, tmp.data());
-                if (r) return r;
-                bool again = false;
-                for (int b = 0; b < nb; ++b) again |= tmp[b].needs_fallback != 0;
-                if (again && ti + 1 < temps.size()) { r = wh_prepare_decoder_inputs(s, nb); if (r) return r; }   // the beam slots overwrote the windows' cross K/V
-            } else if (slot_prompts) {
-                // (an attached draft is ignored: the speculative pass reads one prompt).  Language tokens as in the branch this one stands in for
-                std::vector<int32_t> ml(lang_slot);
-                for (int b = 0; mixed && b < nb; ++b) if (jobs[slot_job[b]].opt->language_token >= 0) ml[b] = -1;
-                const MixClasses mix{(int)sp_classes.size(), sp_classes.data(), cls_slot.data(), nullptr, nullptr, mixed ? opt_slot.data() : nullptr, sp_pp.data(), sp_np.data()};
-                r = decode_text_impl(s, nb, nullptr, st, nullptr, 0, langs ? ml.data() : nullptr, tv.data(), active.data(), seed, tmp.data(), &mix);
-                if (r) return r;
-            } else if (mixed) {
-                // a slot whose audio states its language keeps its class's prompt (-1: no replacement), a detected one gets its own token
-                std::vector<int32_t> ml(lang_slot);
-                for (int b = 0; b < nb; ++b) if (jobs[slot_job[b]].opt->language_token >= 0) ml[b] = -1;
-                const MixClasses mix{(int)classes->size(), classes->data(), cls_slot.data(), mix_pp.data(), mix_np.data(), opt_slot.data()};
-                r = decode_text_impl(s, nb, nullptr, st, nullptr, 0, langs ? ml.data() : nullptr, tv.data(), active.data(), seed, tmp.data(), &mix);
-                if (r) return r;
-            } else if (s->draft && s->no_speech_detection == plan::kNoSpeechOff && s->token_alternatives == 0 && !s->logit_rules_on && !s->phrase_rules_on && !job_sets && ti == 0 && temps[ti] == 0.0f && all_active && beam == 1 && !s->progress_cb && plan::spec_fits(nb, s->draft_k, s->B) &&
-                       !spec_check_draft("wh_transcribe", s, s->draft, nb)) {
-                // first rung with a draft attached (wh_session_set_draft) and room for the rings: the speculative pass (results are the ordinary pass's).  The
-                // speculative pass reports no no-speech value and runs neither logit nor phrase rules nor rule sets, so a session with any of them on (or a group that carries sets) runs the ordinary pass below instead.  The
-                // draft gets the same windows through its own log-mel and encoder
-                wh_session* const dr = s->draft;
-                for (int b = 0; b < nb; ++b) {
-                    const AudioJob& j = jobs[slot_job[b]];
-                    r = j.dev ? wh_set_audio_device(dr, b, j.pcm + j.cur_seek, j.cur_size) : wh_set_audio(dr, b, j.pcm + j.cur_seek, j.cur_size);
-                    if (r) return r;
-                }
-                r = wh_log_mel_spectrogram(dr, nb); if (r) return r;
-                r = wh_encode_features(dr, nb); if (r) return r;
-                r = wh_prepare_decoder_inputs(dr, nb); if (r) return r;
-                r = wh_decode_text_speculative(s, dr, nb, s->draft_k, opt, st, prompt.data(), n_prompt, langs, tmp.data());
-                if (r) return r;
-            } else {
-                r = decode_text_impl(s, nb, opt, st, prompt.data(), n_prompt, langs, tv.data(), active.data(), seed, tmp.data());
-                if (r) return r;
-            }
-            bool any = false;
-            for (int b = 0; b < nb; ++b) {
-                if (!active[b]) continue;
-                res[b] = tmp[b];
-                AudioJob& j = jobs[slot_job[b]];
-                j.tr->timings.total_decoding_loops += tmp[b].steps;
-                if (tmp[b].needs_fallback && ti + 1 < temps.size()) { any = true; j.tr->timings.total_decoding_fallbacks += 1; }
-                else active[b] = 0;
-            }
-            if (!any) break;
-        }
-        double t4 = now_s();
-        // ---- word alignment on the device (wh_session_set_word_alignment 1): every slot's DTW row count is known from its result alone
-        // (wh_word_alignment_rows), so the whole batch is aligned by one head-mean launch, one DTW launch and one copy of the paths
-        const bool device_paths = s->word_alignment == 1 && opt->word_timestamps && s->align;
-        const int32_t *path_len = nullptr, *path_ti = nullptr, *path_tj = nullptr;
-        double device_align_s = 0;
-        if (device_paths) {
-            std::vector<int32_t> rows(nb);
-            for (int b = 0; b < nb; ++b) { rows[b] = wh_word_alignment_rows(&res[b], jopt(jobs[slot_job[b]]), st, s->tok != nullptr); if (rows[b] < 0) return WH_ERR_SEGMENTING_FAILED; }
-            r = whi::alignment_paths(s, nb, rows.data(), &path_len, &path_ti, &path_tj); if (r) return r;
-            device_align_s = now_s() - t4;
-        }
-        // ---- windowing (TranscribeTask.swift:175-278)
-        for (int b = 0; b < nb; ++b) {
-            AudioJob& j = jobs[slot_job[b]];
-            wh_transcription* tr = j.tr;
-            const wh_decoding_options* const jo = jopt(j);
-            // "Windowing" (TranscribeTask.swift:175-265) is host-only code shared with the CPU tests: wh_transcription_add_window
-            std::vector<float> full;
-            const float* alignment = nullptr;
-            if (opt->word_timestamps && s->align && !device_paths) {
-                full.resize((size_t)kMaxTok * kCtx);
-                r = wh_get_alignment_weights(s, b, full.data()); if (r) return r;
-                alignment = full.data();
-            }
-            const double windows_before = tr->timings.total_decoding_windows;
-            int32_t seek = j.seek;
-            const int seg_before = (int)tr->segments.size();
-            if (device_paths) {
-                r = wh_transcription_add_window_path(tr, s->tok, jo, st, &res[b], path_ti + (size_t)b * kDtwPathCap, path_tj + (size_t)b * kDtwPathCap,
-                                                     path_len[b], lang_slot[b], j.cur_size, &seek);
-                tr->timings.decoding_word_timestamps += device_align_s / nb;      // the batch's device stage, shared out like the other stages
-            } else {
-                r = wh_transcription_add_window(tr, s->tok, jo, st, &res[b], alignment, lang_slot[b], j.cur_size, &seek);
-            }
-            if (r) return r;
-            j.seek = seek;
-            // token alternatives: the rows of the rung whose result is kept (its pass was the last to decode home slot b), sliced by the segments just cut
-            if (s->token_alternatives > 0 && tr->timings.total_decoding_windows > windows_before) {
-                int n_alt = 0, n_rows = 0;
-                std::vector<int32_t> aid((size_t)WH_MAX_RESULT_TOKENS * plan::kMaxAlternatives);
-                std::vector<float> alp((size_t)WH_MAX_RESULT_TOKENS * plan::kMaxAlternatives), aen((size_t)WH_MAX_RESULT_TOKENS);
-                r = wh_decode_alternatives(s, b, aid.data(), alp.data(), aen.data(), &n_alt, &n_rows); if (r) return r;
-                if (n_alt > 0 && n_rows == res[b].n_tokens) { r = wh_transcription_set_window_alternatives(tr, n_alt, aid.data(), alp.data(), aen.data(), n_rows); if (r) return r; }
-            }
-            if (tr->timings.total_decoding_windows > windows_before) {      // the window had segments (`guard let currentSegments`, :239-242)
-                int n_new = (int)tr->segments.size() - seg_before;
-                if (s->hooks.window_postprocess) {                         // TranscribeTask.windowPostProcess (:246-250)
-                    const int keep = s->hooks.window_postprocess(s->hooks.user, j.index, j.cur_seek, j.cur_size, tr, seg_before, n_new);
-                    if (keep >= 0 && keep < n_new) { whi::transcription_truncate_segments(tr, seg_before + keep); n_new = keep; }
-                }
-                if (s->hooks.segment_discovery) s->hooks.segment_discovery(s->hooks.user, j.index, tr, seg_before, n_new);   // segmentDiscoveryCallback (:260)
-            }
-            if (carrying) {      // the segments the window added, as they stand now, go into the audio's carry
-                const int n_seg = tr->timings.total_decoding_windows > windows_before ? (int)tr->segments.size() - seg_before : 0;
-                const int tok0 = n_seg > 0 ? tr->segments[(size_t)seg_before].token_offset : 0;
-                const int tok1 = n_seg > 0 ? tr->segments.back().token_offset + tr->segments.back().n_tokens : 0;
-                if (plan::carry_after_window(j.carry, n_seg, tr->tokens.data() + tok0, tok1 - tok0, res[b].temperature, s->previous_text_reset, st->special_token_begin)) s->sp_resets += 1;
-            }
-            if (tr->timings.total_decoding_windows > windows_before) j.windows += 1;
-            tr->timings.audio_processing += (t1 - t0) / nb; tr->timings.logmels += (t2 - t1) / nb; tr->timings.encoding += (t3 - t2) / nb;
-            tr->timings.decoding_loop += (t4 - t3) / nb; tr->timings.total_logmel_runs += 1; tr->timings.total_encoding_runs += 1;
-            tr->timings.total_audio_processing_runs += 1;
-            tr->timings.decoding_windowing += (now_s() - t4) / nb;
-            if (tr->timings.first_token_time == 0) tr->timings.first_token_time = cf_start + (t4 - t_start);   // first decode of this audio done
-        }
+        Round R;
+        int r = round_gather(s, jobs, R, G, s->B / beam); if (r) return r;
+        if (R.slot_job.empty()) break;
+        r = round_encode(s, jobs, R, G); if (r) return r;
+        r = round_decode(s, jobs, R, G); if (r) return r;
+        r = round_align(s, jobs, R, G); if (r) return r;
+        for (int b = 0; b < R.nb(); ++b) { r = round_window(s, jobs, R, G, b); if (r) return r; }
     }
     for (auto& j : jobs) {
         if (j.status != WH_OK) continue;
         wh_transcription* tr = j.tr;
-        tr->timings.full_pipeline = now_s() - t_start;
-        int fr = wh_transcription_finalize(tr, s->tok, jopt(j), st);
+        tr->timings.full_pipeline = now_s() - G.t_start;
+        int fr = wh_transcription_finalize(tr, s->tok, G.options_of(j), st);
         if (fr) { j.status = fr; j.error = wh_last_error(); }
     }
     return WH_OK;
 }
 
-// Two option sets may share a device batch when everything the lock-stepped loop reads is equal: all scalars and the prompt / prefix /
-// suppress token lists (NaN == NaN: both nil).  Clip timestamps are positions inside ONE audio and are applied per audio.
-static bool same_group_options(const wh_decoding_options& a, const wh_decoding_options& b) {
-    auto fe = [](float x, float y) { return (isnan(x) && isnan(y)) || x == y; };
-    auto le = [](const int32_t* x, int nx, const int32_t* y, int ny) {
-        const int ex = x ? nx : 0, ey = y ? ny : 0;
-        return (x == nullptr) == (y == nullptr) && ex == ey && (ex == 0 || memcmp(x, y, sizeof(int32_t) * (size_t)ex) == 0);
-    };
-    return a.task == b.task && a.language_token == b.language_token && fe(a.temperature, b.temperature) &&
-           fe(a.temperature_increment_on_fallback, b.temperature_increment_on_fallback) && a.temperature_fallback_count == b.temperature_fallback_count &&
-           a.sample_length == b.sample_length && a.top_k == b.top_k && a.use_prefill_prompt == b.use_prefill_prompt && a.detect_language == b.detect_language &&
-           a.skip_special_tokens == b.skip_special_tokens && a.without_timestamps == b.without_timestamps && a.word_timestamps == b.word_timestamps &&
-           fe(a.max_initial_timestamp, b.max_initial_timestamp) && a.max_window_seek == b.max_window_seek && fe(a.window_clip_time, b.window_clip_time) &&
-           le(a.prompt_tokens, a.n_prompt_tokens, b.prompt_tokens, b.n_prompt_tokens) && le(a.prefix_tokens, a.n_prefix_tokens, b.prefix_tokens, b.n_prefix_tokens) &&
-           a.suppress_blank == b.suppress_blank && le(a.suppress_tokens, a.n_suppress_tokens, b.suppress_tokens, b.n_suppress_tokens) &&
-           fe(a.compression_ratio_threshold, b.compression_ratio_threshold) && fe(a.log_prob_threshold, b.log_prob_threshold) &&
-           fe(a.first_token_log_prob_threshold, b.first_token_log_prob_threshold) && fe(a.no_speech_threshold, b.no_speech_threshold) && a.seed == b.seed &&
-           a.float16_logits == b.float16_logits && a.beam_size == b.beam_size && fe(a.beam_patience, b.beam_patience);
-}
-
 // WhisperKit.transcribeWithOptions(audioArrays:decodeOptionsArray:) (Core/WhisperKit.swift:716-812): one DecodingOptions and one
-// Result<[TranscriptionResult], Error> per audio.  Audios whose options can share a lock-stepped device batch (same_group_options) form
+// Result<[TranscriptionResult], Error> per audio.  Audios whose options can share a lock-stepped device batch (option_mix.h option_same_group) form
 // a group; groups run one after the other (the reference runs one TranscribeTask per audio: grouping changes the batching, not a result).
 // A failure that belongs to one audio (bad buffer, a window outside the samples) fails that audio; a failure of a group's shared state
 // (invalid option combination, a device error) fails the group's audios; the other groups still run.
@@ -2162,7 +2210,7 @@ static int transcribe_items(wh_session* s, const float* const* pcm, const int32_
         }
         ruled[(size_t)i] = plan::rule_set_ruled(j.rule_set, session_rules_on) ? 1 : 0;
         int g = -1;
-        for (size_t k = 0; k < group_opt.size() && g < 0; ++k) if (group_ruled[k] == ruled[(size_t)i] && same_group_options(*group_opt[k], *j.opt)) g = (int)k;
+        for (size_t k = 0; k < group_opt.size() && g < 0; ++k) if (group_ruled[k] == ruled[(size_t)i] && plan::option_same_group(*group_opt[k], *j.opt)) g = (int)k;
         if (g < 0) { g = (int)group_opt.size(); group_opt.push_back(j.opt); group_ruled.push_back(ruled[(size_t)i]); }
         group_of[(size_t)i] = g;
     }
@@ -2181,17 +2229,19 @@ static int transcribe_items(wh_session* s, const float* const* pcm, const int32_
     int hard = WH_OK;
     for (size_t g = 0; g < group_opt.size(); ++g) {
         std::vector<AudioJob> jobs;
-        for (int i = 0; i < n_audio; ++i) if (group_of[(size_t)i] == (int)g) { jobs.push_back(all[(size_t)i]); jobs.back().tr = new wh_transcription(); }
+        std::vector<std::unique_ptr<wh_transcription>> owned;      // the jobs' transcriptions, until they are published into out[]
+        for (int i = 0; i < n_audio; ++i) if (group_of[(size_t)i] == (int)g) { owned.emplace_back(new wh_transcription()); jobs.push_back(all[(size_t)i]); jobs.back().tr = owned.back().get(); }
         const bool mix_group = mixing && plan::option_mixable(*group_opt[g]);      // (beam search groups run as without the option)
         if (mix_group && !hard) s->mix_groups_run += 1;
         const int r = hard ? hard : transcribe_jobs(s, jobs, group_opt[g], st, mix_group ? &mixp.classes[g] : nullptr, mix_group && s->prompt_mixing == 1);       // after a device error nothing else can run
         const std::string why = r ? wh_last_error() : "";
         if (r == WH_ERR_HIP || r == WH_ERR_CANCELLED) hard = r;
-        for (auto& j : jobs) {
+        for (size_t k = 0; k < jobs.size(); ++k) {
+            const AudioJob& j = jobs[k];
             AudioJob& a = all[(size_t)j.index];
             a.status = r ? r : j.status;
             a.error = r ? why : j.error;
-            if (a.status == WH_OK) out[j.index] = j.tr; else delete j.tr;
+            if (a.status == WH_OK) out[j.index] = owned[k].release();
         }
     }
     int n_ok = 0, first_bad = WH_OK;
@@ -2246,6 +2296,21 @@ extern "C" int wh_transcribe(wh_session* s, const float* pcm, int n, const wh_de
     return wh_transcribe_batch(s, p, nn, 1, opt, st, out);          // one audio: its failure is the call's failure
 }
 
+// behind a chunked call: a chunk that failed is logged and skipped (AudioChunker.swift:19-37: `case .failure`); the others move to the front of out[] with
+// their seek offsets applied (updateSeekOffsetsForResults).  Returns how many are kept
+static int keep_transcribed_chunks(wh_transcription** out, int nc, const std::vector<int32_t>& chunk_start, int32_t* seek_offsets_out) {
+    int kept = 0;
+    for (int i = 0; i < nc; ++i) {
+        if (!out[i]) continue;
+        wh_transcription_apply_seek_offset(out[i], chunk_start[(size_t)i]);
+        wh_transcription* t = out[i];
+        out[i] = nullptr; out[kept] = t;
+        if (seek_offsets_out) seek_offsets_out[kept] = chunk_start[(size_t)i];
+        ++kept;
+    }
+    return kept;
+}
+
 extern "C" int wh_transcribe_chunked(wh_session* s, const float* pcm, int n, const wh_decoding_options* opt, const wh_special_tokens* st,
                                      wh_transcription** out, int capacity, int32_t* seek_offsets_out, int* n_out) {
     CHECK_SESSION(s);
@@ -2272,16 +2337,7 @@ extern "C" int wh_transcribe_chunked(wh_session* s, const float* pcm, int n, con
     for (int i = 0; i < nc; ++i) { ptrs[i] = pcm + cs[i]; lens[i] = ce[i] - cs[i]; }
     int r = wh_transcribe_batch(s, ptrs.data(), lens.data(), nc, &chunked, st, out);
     if (r) return r;
-    int kept = 0;                                             // a chunk that failed is logged and skipped (AudioChunker.swift:19-37: `case .failure`)
-    for (int i = 0; i < nc; ++i) {
-        if (!out[i]) continue;
-        wh_transcription_apply_seek_offset(out[i], cs[i]);   // updateSeekOffsetsForResults
-        wh_transcription* t = out[i];
-        out[i] = nullptr; out[kept] = t;
-        if (seek_offsets_out) seek_offsets_out[kept] = cs[i];
-        ++kept;
-    }
-    *n_out = kept;
+    *n_out = keep_transcribed_chunks(out, nc, cs, seek_offsets_out);
     return WH_OK;
 }
 
@@ -2292,17 +2348,22 @@ static int check_device_audios(const wh_session* s, const wh_device_audio* const
             return set_error(WH_ERR_INVALID_ARGUMENT, "%s: audio %d lives on device %d, the session on device %d", who, i, audios[i]->device, s->m->device);
     return WH_OK;
 }
+// transcribe_items over checked device audios: the samples' device addresses and lengths (a null audio: "invalid buffer", alone)
+static int transcribe_device_items(wh_session* s, const wh_device_audio* const* audios, int n_audio, const wh_decoding_options* const* opts, const wh_special_tokens* st,
+                                   wh_transcription** out, int32_t* statuses, const int32_t* rule_sets, const char* who) {
+    if (int r = check_device_audios(s, audios, n_audio, who)) return r;
+    std::vector<const float*> ptrs((size_t)n_audio);
+    std::vector<int32_t> lens((size_t)n_audio);
+    for (int i = 0; i < n_audio; ++i) { ptrs[(size_t)i] = audios[i] ? audios[i]->data : nullptr; lens[(size_t)i] = audios[i] ? audios[i]->n : -1; }
+    return transcribe_items(s, ptrs.data(), lens.data(), n_audio, opts, nullptr, st, out, statuses, audios, rule_sets);
+}
 
 extern "C" int wh_transcribe_device_batch_with_options(wh_session* s, const wh_device_audio* const* audios, int n_audio, const wh_decoding_options* const* opts,
                                                        const wh_special_tokens* st, wh_transcription** out, int32_t* statuses) {
     CHECK_SESSION(s);
     if (!audios || n_audio < 1 || !st || !out) return set_error(WH_ERR_TRANSCRIPTION_FAILED, "wh_transcribe_device_batch_with_options: null argument");
     WH_TRY
-    if (int r = check_device_audios(s, audios, n_audio, "wh_transcribe_device_batch_with_options")) return r;
-    std::vector<const float*> ptrs((size_t)n_audio);
-    std::vector<int32_t> lens((size_t)n_audio);
-    for (int i = 0; i < n_audio; ++i) { ptrs[(size_t)i] = audios[i] ? audios[i]->data : nullptr; lens[(size_t)i] = audios[i] ? audios[i]->n : -1; }    // a null audio: "invalid buffer", alone
-    return transcribe_items(s, ptrs.data(), lens.data(), n_audio, opts, nullptr, st, out, statuses, audios);
+    return transcribe_device_items(s, audios, n_audio, opts, st, out, statuses, nullptr, "wh_transcribe_device_batch_with_options");
     WH_CATCH("wh_transcribe_device_batch_with_options")
 }
 
@@ -2320,11 +2381,7 @@ extern "C" int wh_transcribe_device_batch_with_rule_sets(wh_session* s, const wh
     CHECK_SESSION(s);
     if (!audios || n_audio < 1 || !st || !out) return set_error(WH_ERR_TRANSCRIPTION_FAILED, "wh_transcribe_device_batch_with_rule_sets: null argument");
     WH_TRY
-    if (int r = check_device_audios(s, audios, n_audio, "wh_transcribe_device_batch_with_rule_sets")) return r;
-    std::vector<const float*> ptrs((size_t)n_audio);
-    std::vector<int32_t> lens((size_t)n_audio);
-    for (int i = 0; i < n_audio; ++i) { ptrs[(size_t)i] = audios[i] ? audios[i]->data : nullptr; lens[(size_t)i] = audios[i] ? audios[i]->n : -1; }    // a null audio: "invalid buffer", alone
-    return transcribe_items(s, ptrs.data(), lens.data(), n_audio, opts, nullptr, st, out, statuses, audios, rule_set_of_audio);
+    return transcribe_device_items(s, audios, n_audio, opts, st, out, statuses, rule_set_of_audio, "wh_transcribe_device_batch_with_rule_sets");
     WH_CATCH("wh_transcribe_device_batch_with_rule_sets")
 }
 
@@ -2353,21 +2410,12 @@ extern "C" int wh_transcribe_chunked_device(wh_session* s, wh_device_audio* a, c
     chunked.clip_timestamps = nullptr;
     chunked.n_clip_timestamps = 0;
     std::vector<const float*> ptrs((size_t)nc);
-    std::vector<int32_t> lens((size_t)nc);
+    std::vector<int32_t> lens((size_t)nc), cs((size_t)nc);
     std::vector<const wh_device_audio*> devs((size_t)nc, a);
-    for (int i = 0; i < nc; ++i) { ptrs[(size_t)i] = a->data + chunks[(size_t)i].first; lens[(size_t)i] = chunks[(size_t)i].second - chunks[(size_t)i].first; }
+    for (int i = 0; i < nc; ++i) { cs[(size_t)i] = chunks[(size_t)i].first; ptrs[(size_t)i] = a->data + cs[(size_t)i]; lens[(size_t)i] = chunks[(size_t)i].second - cs[(size_t)i]; }
     int r = transcribe_items(s, ptrs.data(), lens.data(), nc, nullptr, &chunked, st, out, nullptr, devs.data());
     if (r) return r;
-    int kept = 0;
-    for (int i = 0; i < nc; ++i) {
-        if (!out[i]) continue;
-        wh_transcription_apply_seek_offset(out[i], chunks[(size_t)i].first);
-        wh_transcription* t = out[i];
-        out[i] = nullptr; out[kept] = t;
-        if (seek_offsets_out) seek_offsets_out[kept] = chunks[(size_t)i].first;
-        ++kept;
-    }
-    *n_out = kept;
+    *n_out = keep_transcribed_chunks(out, nc, cs, seek_offsets_out);
     return WH_OK;
     WH_CATCH("wh_transcribe_chunked_device")
 }
@@ -2548,13 +2596,10 @@ extern "C" int wh_align_tokens_batch(wh_session* s, const float* const* pcm_host
         if (n_samples[a] < 1 || !pcm_host[a]) { fail(a, set_error(WH_ERR_AUDIO_PROCESSING_FAILED, "audio %d: invalid buffer", a)); continue; }
         if (n_samples[a] > kWindowSamples) { fail(a, set_error(WH_ERR_INVALID_ARGUMENT, "audio %d: %d samples exceed one window of %d (long-form alignment is out of scope)", a, n_samples[a], kWindowSamples)); continue; }
         if (n_text[a] < 0 || (n_text[a] > 0 && !text_tokens[a])) { fail(a, set_error(WH_ERR_INVALID_ARGUMENT, "audio %d: invalid token list", a)); continue; }
-        std::vector<int32_t> p(kMaxPrompt);
-        int np = 1;
-        p[0] = st->start_of_transcript_token;
-        if (opts[a].use_prefill_prompt) np = wh_prefill_prompt(s->m, &opts[a], st, opts[a].language_token, p.data(), (int)p.size());
+        std::vector<int32_t> p;
+        const int np = build_prompt(s->m, opts[a], st, p);
         if (np <= 0) { fail(a, set_error(WH_ERR_PREFILL_FAILED, "audio %d: prefill prompt does not fit", a)); continue; }
         if (np + n_text[a] + 1 > kMaxTok) { fail(a, set_error(WH_ERR_INVALID_ARGUMENT, "audio %d: prompt (%d) + text (%d) + end token exceed %d tokens", a, np, n_text[a], kMaxTok)); continue; }
-        p.resize((size_t)np);
         p.insert(p.end(), text_tokens[a], text_tokens[a] + n_text[a]);
         p.push_back(st->end_token);
         const int32_t* pp = p.data(); const int32_t pn = (int32_t)p.size();

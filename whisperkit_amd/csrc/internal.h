@@ -128,7 +128,7 @@ struct wh_session {
     int* suppress_dev = nullptr;
     unsigned char* sup_mask_dev = nullptr;   // SuppressTokensFilter byte masks (fused greedy sampler)
     // option mixing (wh_session_set_option_mixing): 0 = off, 1 = wh_transcribe_batch_with_options groups its audios by batch key (option_mix_plan) and
-    // decodes a group's classes in one pass.  pass.mixed is set by a pass with classes (host.hip MixClasses; wh_decode_text_mixed works whatever the mode).
+    // decodes a group's classes in one pass.  pass.mixed is set by a pass with classes (host.hip PassRequest with a prompt per class or per slot; wh_decode_text_mixed works whatever the mode).
     int option_mixing = 0;
     long long mix_groups_run = 0, mix_mixed_passes = 0, mix_max_classes = 0;   // wh_session_option_mixing_stats: groups that ran mixed, passes with classes, largest class count
     // per-slot prompts.  prompt_mixing (wh_session_set_prompt_mixing): 1 = while option mixing is on, the prompt leaves the class and every audio's own
