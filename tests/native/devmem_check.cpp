@@ -2,6 +2,10 @@
 // (once more with -fsanitize=address,undefined).  One query per line on stdin, one answer line per query:
 //   dec32 <d> <L> <V>   | mxabs <d> <L> | sxabs <d> <H> <B> | d32 <d> <B>
 //        -> <measured size> <end of the carving pass> | region offsets of the measuring pass | region offsets of the carving pass
+//   pack <what> <B> [<heads>]   what = nospeech | slots | forced | altf32 | inpassdev | inpassregion | rsdev | rshost | dtwdev | dtwhost | beamsum |
+//                               aligntmp: a packed session buffer at B slots (aligntmp: <heads> alignment heads), with the library's own constants
+//        -> <measured size> <end of the device pass> <end of the pinned pass> | region offsets measuring | against the device base | against the pinned base
+//   ring <regions> <stride> <n> <n> ...   -> the element offset each take(n) of one StageRing returned, `full` where it refused
 //   owner <k> <what>    -> a session-like sequence of allocations against a counting backend whose k-th allocation (what = alloc) or k-th
 //                          zero-fill (what = fill) fails, k = 0: nothing fails; the sequence stops at the first error, the owner is destroyed:
 //        -> <backend allocations tried> <error seen 0/1> <held before destruction> <live in the backend after> <freed twice or unknown>
@@ -10,9 +14,12 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <string>
 #include <vector>
 
+#include "alternatives_plan.h"
 #include "devmem.h"
+#include "rule_sets_plan.h"
 
 namespace {
 // destinations with the field names and element widths of kernels.h Dec32LayerW / Dec32 / XabsLayerW / Xabs and of wh_model
@@ -46,6 +53,61 @@ void print_layout(size_t measured, size_t carved, size_t n_regions) {
     for (size_t i = 0; i < g_off.size(); ++i) printf("%s %zu", i == n_regions ? " |" : "", g_off[i]);
     printf("\n");
     g_off.clear();
+}
+
+// ---- the packed session buffers.  The constants the library passes: kernels.h / common.h cannot be included here (HIP), the plan headers can
+constexpr size_t kMaxTok = 224, kCtx = 1500, kDtwPathCap = 256 + 1500, kMaxSessionSlots = 256;
+static_assert(wh::plan::kAltPositions == kMaxTok, "one alternatives row per decoder position");
+char* const kBasePinned = reinterpret_cast<char*>(uintptr_t(0x5000) << 24);      // never dereferenced
+template <class V, class Pack, class Note> void pack_query(Pack pack, Note note_view) {
+    V v{};
+    const size_t measured = pack(nullptr, v); note_view(v, nullptr);
+    const size_t n_regions = g_off.size();
+    const size_t dev = pack(kBase, v); note_view(v, kBase);
+    const size_t pinned = pack(kBasePinned, v); note_view(v, kBasePinned);
+    printf("%zu %zu %zu |", measured, dev, pinned);
+    for (size_t i = 0; i < g_off.size(); ++i) printf("%s %zu", (i && i % n_regions == 0) ? " |" : "", g_off[i]);
+    printf("\n");
+    g_off.clear();
+}
+bool pack_dispatch(const char* what, size_t B, size_t H) {
+    using namespace wh::mem;
+    const std::string w = what;
+    if (w == "nospeech") pack_query<NoSpeechView>([&](void* b, NoSpeechView& v) { return pack_nospeech(b, B, v); },
+        [](const NoSpeechView& v, const void* b) { note(v.pos, b); note(v.stop, b); note(v.prob, b); note(v.stopped, b); note(v.cfg, b); });
+    else if (w == "slots") pack_query<SlotTableView>([&](void* b, SlotTableView& v) { return pack_slot_table(b, B, v); },
+        [](const SlotTableView& v, const void* b) { note(v.home, b); note(v.live, b); });
+    else if (w == "forced") pack_query<ForcedOutView>([&](void* b, ForcedOutView& v) { return pack_forced_out(b, B, kMaxTok, v); },
+        [](const ForcedOutView& v, const void* b) { note(v.lp, b); note(v.best, b); note(v.best_lp, b); });
+    else if (w == "altf32") pack_query<AltF32View>([&](void* b, AltF32View& v) { return pack_alternatives_f32(b, B, wh::plan::kAltPositions, wh::plan::kMaxAlternatives, v); },
+        [](const AltF32View& v, const void* b) { note(v.lp, b); note(v.entropy, b); });
+    else if (w == "inpassdev") pack_query<InpassDevView>([&](void* b, InpassDevView& v) { return pack_inpass_dev(b, B, kMaxTok, v); },
+        [](const InpassDevView& v, const void* b) { note(v.live, b); note(v.owner, b); });
+    else if (w == "inpassregion") pack_query<InpassRegionView>([&](void* b, InpassRegionView& v) { return pack_inpass_region(b, B, kMaxTok, v); },
+        [](const InpassRegionView& v, const void* b) { note(v.home, b); note(v.live, b); note(v.owner, b); });
+    else if (w == "rsdev") pack_query<RuleSetsDevView>([&](void* b, RuleSetsDevView& v) { return pack_rule_sets_dev(b, wh::plan::kMaxRuleSets, kMaxSessionSlots, (size_t)wh::plan::kRuleSetBankWords, v); },
+        [](const RuleSetsDevView& v, const void* b) { note(v.matches, b); note(v.slots, b); note(v.bank, b); });
+    else if (w == "rshost") pack_query<RuleSetsHostView>([&](void* b, RuleSetsHostView& v) { return pack_rule_sets_host(b, kMaxSessionSlots, wh::plan::kRuleSetStride, v); },
+        [](const RuleSetsHostView& v, const void* b) { note(v.slots, b); note(v.stage, b); });
+    else if (w == "dtwdev" || w == "dtwhost") pack_query<DtwView>([&](void* b, DtwView& v) { return pack_dtw(b, B, kDtwPathCap, w == "dtwdev", v); },
+        [](const DtwView& v, const void* b) { note(v.rows, b); note(v.len, b); note(v.ti, b); note(v.tj, b); });
+    else if (w == "beamsum") pack_query<BeamSumView>([&](void* b, BeamSumView& v) { return pack_beam_sums(b, B, v); },
+        [](const BeamSumView& v, const void* b) { note(v.half[0], b); note(v.half[1], b); });
+    else if (w == "aligntmp") pack_query<AlignTmpView>([&](void* b, AlignTmpView& v) { return pack_align_tmp(b, kMaxTok, H, kCtx, v); },
+        [](const AlignTmpView& v, const void* b) { note(v.rows, b); note(v.stat, b); note(v.flags, b); });
+    else return false;
+    return true;
+}
+void ring_query(const char* line) {
+    size_t regions, stride; int used = 0;
+    if (sscanf(line, "ring %zu %zu%n", &regions, &stride, &used) != 2) { printf("bad query\n"); return; }
+    wh::mem::StageRing ring(regions, stride);
+    size_t n; int more = 0;
+    for (const char* p = line + used; sscanf(p, "%zu%n", &n, &more) == 1; p += more) {
+        const size_t at = ring.take(n);
+        if (at == wh::mem::StageRing::kFull) printf("full "); else printf("%zu ", at);
+    }
+    printf("| %zu\n", ring.taken());
 }
 
 // ---- the counting backend
@@ -122,7 +184,7 @@ void owner_query(long k, bool fill) {
 }  // namespace
 
 int main() {
-    char line[256];
+    char line[4096];      // (a ring query lists every take)
     while (fgets(line, sizeof(line), stdin)) {
         size_t d, a, b;
         long k;
@@ -155,6 +217,10 @@ int main() {
             const size_t carved = wh::mem::carve_session_d32(kBase, d, a, q);
             note_d32(q, kBase);
             print_layout(measured, carved, 11);
+        } else if (sscanf(line, "pack %15s %zu %zu", what, &a, &b) >= 2) {
+            if (!pack_dispatch(what, a, b)) printf("bad query\n");
+        } else if (!strncmp(line, "ring ", 5)) {
+            ring_query(line);
         } else if (sscanf(line, "owner %ld %15s", &k, what) == 2) {
             owner_query(k, !strcmp(what, "fill"));
         } else {

@@ -198,23 +198,26 @@ struct AudioBeams {
     int first_token_too_low = 0;
 };
 
+// the only place that allocates the beam pass's memory
 int ensure_beam_buffers(wh_session* s, bool device_ranking) {
     const size_t B = (size_t)s->B;
+    mem::BeamSumView measure{};
     // (not zero-filled; a call that fails part way keeps what it got and asks for the rest next time)
-    if (!s->beam_owner) WH_HIP(s->mem.alloc(&s->beam_owner, kMaxTok * B, false));
-    if (!s->beam_lp) WH_HIP(s->mem.alloc(&s->beam_lp, kBeamTopK * B, false));
-    if (!s->beam_tok) WH_HIP(s->mem.alloc(&s->beam_tok, kBeamTopK * B, false));
+    if (!s->beam.owner) WH_HIP(s->mem.alloc(&s->beam.owner, kMaxTok * B, false));
+    if (!s->beam.lp) WH_HIP(s->mem.alloc(&s->beam.lp, kBeamTopK * B, false));
+    if (!s->beam.tok) WH_HIP(s->mem.alloc(&s->beam.tok, kBeamTopK * B, false));
     if (!device_ranking) return WH_OK;
     // the second half of the ping-pong, the per-audio state and the finished lists (an audio per slot at beam size 1: sized by max_batch)
-    if (!s->beam_seq_alt) WH_HIP(s->mem.alloc(&s->beam_seq_alt, B, false));
-    if (!s->beam_owner_alt) WH_HIP(s->mem.alloc(&s->beam_owner_alt, kMaxTok * B, false));
-    if (!s->beam_sum) WH_HIP(s->mem.alloc(&s->beam_sum, 2 * B, false));
-    if (!s->beam_audio) WH_HIP(s->mem.alloc(&s->beam_audio, B, false));
-    if (!s->beam_audio_host) WH_HIP(s->mem.alloc_pinned(&s->beam_audio_host, B));
-    if (!s->beam_fin_tok) WH_HIP(s->mem.alloc(&s->beam_fin_tok, (size_t)kBeamSeqStride * kBeamFinishedCap * B, false));
-    if (!s->beam_fin_lp) WH_HIP(s->mem.alloc(&s->beam_fin_lp, (size_t)kBeamSeqStride * kBeamFinishedCap * B, false));
-    if (!s->beam_fin_sum) WH_HIP(s->mem.alloc(&s->beam_fin_sum, kBeamFinishedCap * B, false));
-    if (!s->beam_fin_len) WH_HIP(s->mem.alloc(&s->beam_fin_len, kBeamFinishedCap * B, false));
+    if (!s->beam.seq_alt) WH_HIP(s->mem.alloc(&s->beam.seq_alt, B, false));
+    if (!s->beam.owner_alt) WH_HIP(s->mem.alloc(&s->beam.owner_alt, kMaxTok * B, false));
+    if (!s->beam.sum_dev) WH_HIP(s->mem.alloc(&s->beam.sum_dev, mem::pack_beam_sums(nullptr, B, measure) / sizeof(float), false));
+    mem::pack_beam_sums(s->beam.sum_dev, B, s->beam.sum);
+    if (!s->beam.audio) WH_HIP(s->mem.alloc(&s->beam.audio, B, false));
+    if (!s->beam.audio_host) WH_HIP(s->mem.alloc_pinned(&s->beam.audio_host, B));
+    if (!s->beam.fin_tok) WH_HIP(s->mem.alloc(&s->beam.fin_tok, (size_t)kBeamSeqStride * kBeamFinishedCap * B, false));
+    if (!s->beam.fin_lp) WH_HIP(s->mem.alloc(&s->beam.fin_lp, (size_t)kBeamSeqStride * kBeamFinishedCap * B, false));
+    if (!s->beam.fin_sum) WH_HIP(s->mem.alloc(&s->beam.fin_sum, kBeamFinishedCap * B, false));
+    if (!s->beam.fin_len) WH_HIP(s->mem.alloc(&s->beam.fin_len, kBeamFinishedCap * B, false));
     return WH_OK;
 }
 
@@ -228,7 +231,8 @@ int beam_loop_device(wh_session* s, int n_audio, int beam_size, int max_candidat
                      std::vector<SeqState>& greedy) {
     const int n_slots = n_audio * beam_size, B = s->B, first = n_prompt - 1;
     constexpr int kPoll = 8;
-    BeamAudioState* ah = s->beam_audio_host;
+    BeamAudioState* ah = s->beam.audio_host;
+    mem::BeamSumView measure{};
     for (int a = 0; a < n_audio; ++a) {
         ah[a] = BeamAudioState{};
         ah[a].live = A[a].live ? 1 : 0; ah[a].n_beams = A[a].live ? beam_size : 0;
@@ -244,13 +248,13 @@ int beam_loop_device(wh_session* s, int n_audio, int beam_size, int max_candidat
         }
     }
     WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * n_slots, hipMemcpyHostToDevice, s->st));
-    WH_HIP(hipMemsetAsync(s->beam_seq_alt, 0, sizeof(SeqState) * n_slots, s->st));
-    WH_HIP(hipMemcpyAsync(s->beam_owner, owner.data(), sizeof(int) * owner.size(), hipMemcpyHostToDevice, s->st));
-    WH_HIP(hipMemsetAsync(s->beam_sum, 0, sizeof(float) * 2 * (size_t)B, s->st));
-    WH_HIP(hipMemcpyAsync(s->beam_audio, ah, sizeof(BeamAudioState) * n_audio, hipMemcpyHostToDevice, s->st));
-    SeqState* seqs[2] = {s->seq, s->beam_seq_alt};
-    int* owners[2] = {s->beam_owner, s->beam_owner_alt};
-    float* sums[2] = {s->beam_sum, s->beam_sum + B};
+    WH_HIP(hipMemsetAsync(s->beam.seq_alt, 0, sizeof(SeqState) * n_slots, s->st));
+    WH_HIP(hipMemcpyAsync(s->beam.owner, owner.data(), sizeof(int) * owner.size(), hipMemcpyHostToDevice, s->st));
+    WH_HIP(hipMemsetAsync(s->beam.sum_dev, 0, mem::pack_beam_sums(nullptr, (size_t)B, measure), s->st));      // both halves
+    WH_HIP(hipMemcpyAsync(s->beam.audio, ah, sizeof(BeamAudioState) * n_audio, hipMemcpyHostToDevice, s->st));
+    SeqState* seqs[2] = {s->seq, s->beam.seq_alt};
+    int* owners[2] = {s->beam.owner, s->beam.owner_alt};
+    float* const* sums = s->beam.sum.half;
     bool any_live = true;       // (the caller checked)
     for (int token_index = first; any_live && token_index < loop_count; ++token_index) {
         const int in = (token_index - first) & 1, out = in ^ 1;
@@ -259,16 +263,16 @@ int beam_loop_device(wh_session* s, int n_audio, int beam_size, int max_candidat
         db.cross_div = beam_size;
         db.self_owner = owners[in];
         launch_decoder_step(db, nullptr, nullptr, false, s->st, whi::nospeech_step_args(s, token_index));
-        launch_beam_filter_topk(s->cfg_dev, s->suppress_dev, seqs[in], s->logits, n_slots, beam_size + 1, s->beam_lp, s->beam_tok, s->st);
+        launch_beam_filter_topk(s->cfg_dev, s->suppress_dev, seqs[in], s->logits, n_slots, beam_size + 1, s->beam.lp, s->beam.tok, s->st);
         WH_CHECK_LAUNCH();
         BeamRankArgs k{};
         k.n_audio = n_audio; k.beam_size = beam_size; k.max_candidates = max_candidates; k.eot = st->end_token; k.len = token_index + 1;
-        k.topk_stride = kBeamTopK; k.topk_lp = s->beam_lp; k.topk_tok = s->beam_tok;
+        k.topk_stride = kBeamTopK; k.topk_lp = s->beam.lp; k.topk_tok = s->beam.tok;
         k.tok_in = seqs[in]->tokens; k.lp_in = seqs[in]->logprobs; k.sum_in = sums[in];
         k.tok_out = seqs[out]->tokens; k.lp_out = seqs[out]->logprobs; k.sum_out = sums[out];
         k.in_stride = k.out_stride = (long long)(sizeof(SeqState) / sizeof(int));
-        k.audio = s->beam_audio;
-        k.fin_tok = s->beam_fin_tok; k.fin_lp = s->beam_fin_lp; k.fin_sum = s->beam_fin_sum; k.fin_len = s->beam_fin_len;
+        k.audio = s->beam.audio;
+        k.fin_tok = s->beam.fin_tok; k.fin_lp = s->beam.fin_lp; k.fin_sum = s->beam.fin_sum; k.fin_len = s->beam.fin_len;
         k.fin_cap = kBeamFinishedCap; k.fin_stride = kBeamSeqStride; k.fin_append = 1;
         k.seq_in = seqs[in]; k.seq_out = seqs[out]; k.owner_in = owners[in]; k.owner_out = owners[out];
         k.token_index = token_index; k.prompt_len = n_prompt; k.parity_out = out;
@@ -276,11 +280,11 @@ int beam_loop_device(wh_session* s, int n_audio, int beam_size, int max_candidat
         k.threshold_position = prefilled_index; k.first_token_log_prob_threshold = opt->first_token_log_prob_threshold;
         int r = launch_beam_rank(k, s->st);
         if (r) return r;
-        s->beam_rank_launches += 1;
+        s->beam.rank_launches += 1;
         if ((token_index - first + 1) % kPoll == 0 && token_index + 1 < loop_count) {
-            WH_HIP(hipMemcpyAsync(ah, s->beam_audio, sizeof(BeamAudioState) * n_audio, hipMemcpyDeviceToHost, s->st));
+            WH_HIP(hipMemcpyAsync(ah, s->beam.audio, sizeof(BeamAudioState) * n_audio, hipMemcpyDeviceToHost, s->st));
             WH_HIP(hipStreamSynchronize(s->st));
-            s->beam_loop_syncs += 1;
+            s->beam.loop_syncs += 1;
             if (s->cancel_flag && *s->cancel_flag) return set_error(WH_ERR_CANCELLED, "wh_decode_text_beam: cancelled through the session's cancel flag");
             any_live = false;
             for (int a = 0; a < n_audio; ++a) any_live |= ah[a].live != 0;
@@ -290,15 +294,15 @@ int beam_loop_device(wh_session* s, int n_audio, int beam_size, int max_candidat
     std::vector<SeqState> hseq((size_t)2 * n_slots);
     std::vector<float> hsum((size_t)2 * n_slots), fsum((size_t)n_audio * kBeamFinishedCap), flp(fsum.size() * kBeamSeqStride);
     std::vector<int> ftok(flp.size()), flen(fsum.size());
-    WH_HIP(hipMemcpyAsync(ah, s->beam_audio, sizeof(BeamAudioState) * n_audio, hipMemcpyDeviceToHost, s->st));
+    WH_HIP(hipMemcpyAsync(ah, s->beam.audio, sizeof(BeamAudioState) * n_audio, hipMemcpyDeviceToHost, s->st));
     for (int h = 0; h < 2; ++h) {
         WH_HIP(hipMemcpyAsync(hseq.data() + (size_t)h * n_slots, seqs[h], sizeof(SeqState) * n_slots, hipMemcpyDeviceToHost, s->st));
         WH_HIP(hipMemcpyAsync(hsum.data() + (size_t)h * n_slots, sums[h], sizeof(float) * n_slots, hipMemcpyDeviceToHost, s->st));
     }
-    WH_HIP(hipMemcpyAsync(ftok.data(), s->beam_fin_tok, sizeof(int) * ftok.size(), hipMemcpyDeviceToHost, s->st));
-    WH_HIP(hipMemcpyAsync(flp.data(), s->beam_fin_lp, sizeof(float) * flp.size(), hipMemcpyDeviceToHost, s->st));
-    WH_HIP(hipMemcpyAsync(flen.data(), s->beam_fin_len, sizeof(int) * flen.size(), hipMemcpyDeviceToHost, s->st));
-    WH_HIP(hipMemcpyAsync(fsum.data(), s->beam_fin_sum, sizeof(float) * fsum.size(), hipMemcpyDeviceToHost, s->st));
+    WH_HIP(hipMemcpyAsync(ftok.data(), s->beam.fin_tok, sizeof(int) * ftok.size(), hipMemcpyDeviceToHost, s->st));
+    WH_HIP(hipMemcpyAsync(flp.data(), s->beam.fin_lp, sizeof(float) * flp.size(), hipMemcpyDeviceToHost, s->st));
+    WH_HIP(hipMemcpyAsync(flen.data(), s->beam.fin_len, sizeof(int) * flen.size(), hipMemcpyDeviceToHost, s->st));
+    WH_HIP(hipMemcpyAsync(fsum.data(), s->beam.fin_sum, sizeof(float) * fsum.size(), hipMemcpyDeviceToHost, s->st));
     WH_HIP(hipStreamSynchronize(s->st));
     for (int a = 0; a < n_audio; ++a) {
         AudioBeams& ab = A[a];
@@ -342,7 +346,7 @@ static int wh_decode_text_beam_impl(wh_session* s, int n_audio, int beam_size, f
                          n_audio * beam_size, s->B);
     if (n_prompt < 1 || n_prompt >= kMaxTok) return set_error(WH_ERR_PREFILL_FAILED, "wh_decode_text_beam: prompt length %d out of range [1,%d)", n_prompt, kMaxTok);
     if (opt->word_timestamps) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text_beam: word timestamps are not recorded along beams (decode the chosen tokens again with wh_decode_text and prefixTokens to align them)");
-    if (s->token_alternatives > 0) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text_beam: the session records token alternatives (wh_session_set_token_alternatives), which the beam pass does not do");
+    if (s->alt.n > 0) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text_beam: the session records token alternatives (wh_session_set_token_alternatives), which the beam pass does not do");
     if (s->logit_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text_beam: the session has logit rules set (wh_session_set_logit_rules), which the beam pass does not run");
     if (s->phrase_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text_beam: the session has phrase rules set (wh_session_set_phrase_rules), which the beam pass does not run");
     if (whi::rule_sets_assigned(s, n_audio * beam_size)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text_beam: a slot of the call is assigned a rule set (wh_session_set_slot_rule_sets), which the beam pass does not run");
@@ -350,7 +354,7 @@ static int wh_decode_text_beam_impl(wh_session* s, int n_audio, int beam_size, f
     (void)H;
     if (int r = whi::check_prompt_tokens("wh_decode_text_beam", prompt, n_prompt, V, WH_ERR_PREFILL_FAILED)) return r;
     // a finished list longer than the device list's capacity is ranked on the host (kernels.h kBeamFinishedCap; same results by definition)
-    const bool device_ranking = s->beam_ranking == 1 && max_candidates <= kBeamFinishedCap;
+    const bool device_ranking = s->beam.ranking == 1 && max_candidates <= kBeamFinishedCap;
     int r = ensure_beam_buffers(s, device_ranking);
     if (r) return r;
     const int prefilled_index = 0;
@@ -360,7 +364,7 @@ static int wh_decode_text_beam_impl(wh_session* s, int n_audio, int beam_size, f
     const int loop_count = std::max(std::min(opt->sample_length, kMaxTok - 1), 0);
     // ---- no-speech detection (NO REFERENCE BEHAVIOUR): the value comes from the audio's own slot at a scoring step inside the pre-fill, from its
     // first beam (slot a * beam_size, lane_div = beam_size) when the scoring step is the beam loop's first.  The host loops do not read `done`: mode 2 never stops a beam pass
-    const bool ns_on = s->no_speech_detection != plan::kNoSpeechOff;
+    const bool ns_on = s->ns.mode != plan::kNoSpeechOff;
     whi::PassGuard guard{s};
     if (ns_on) {
         const int p = plan::nospeech_position(prompt, n_prompt, st->start_of_transcript_token);
@@ -440,17 +444,17 @@ static int wh_decode_text_beam_impl(wh_session* s, int n_audio, int beam_size, f
             }
         WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * n_slots, hipMemcpyHostToDevice, s->st));
         for (int j = 0; j < n_slots; ++j) owner[(size_t)j * kMaxTok + token_index] = j;      // the row this step writes is the slot's own
-        WH_HIP(hipMemcpyAsync(s->beam_owner, owner.data(), sizeof(int) * owner.size(), hipMemcpyHostToDevice, s->st));
+        WH_HIP(hipMemcpyAsync(s->beam.owner, owner.data(), sizeof(int) * owner.size(), hipMemcpyHostToDevice, s->st));
         DecodeBuffers db = whi::decode_buffers(s, n_slots, token_index);
         db.cross_div = beam_size;
-        db.self_owner = s->beam_owner;
+        db.self_owner = s->beam.owner;
         launch_decoder_step(db, nullptr, nullptr, false, s->st, whi::nospeech_step_args(s, token_index));
-        launch_beam_filter_topk(s->cfg_dev, s->suppress_dev, s->seq, s->logits, n_slots, beam_size + 1, s->beam_lp, s->beam_tok, s->st);
+        launch_beam_filter_topk(s->cfg_dev, s->suppress_dev, s->seq, s->logits, n_slots, beam_size + 1, s->beam.lp, s->beam.tok, s->st);
         WH_CHECK_LAUNCH();
-        WH_HIP(hipMemcpyAsync(h_lp.data(), s->beam_lp, sizeof(float) * h_lp.size(), hipMemcpyDeviceToHost, s->st));
-        WH_HIP(hipMemcpyAsync(h_tok.data(), s->beam_tok, sizeof(int) * h_tok.size(), hipMemcpyDeviceToHost, s->st));
+        WH_HIP(hipMemcpyAsync(h_lp.data(), s->beam.lp, sizeof(float) * h_lp.size(), hipMemcpyDeviceToHost, s->st));
+        WH_HIP(hipMemcpyAsync(h_tok.data(), s->beam.tok, sizeof(int) * h_tok.size(), hipMemcpyDeviceToHost, s->st));
         WH_HIP(hipStreamSynchronize(s->st));      // (also: `owner` / seq_host may be rewritten now)
-        s->beam_loop_syncs += 1;
+        s->beam.loop_syncs += 1;
         std::vector<int> pairs;
         any_live = false;
         for (int a = 0; a < n_audio; ++a) {

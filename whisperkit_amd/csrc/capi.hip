@@ -426,7 +426,7 @@ extern "C" int wh_session_create_with_options(wh_model* m, int max_batch, const 
     // a split session resolves the automatic cross-attention choice to the K / V rows (their projection reads the split encoder output)
     const int r = session_create_impl(m, max_batch, opt->encoder_precision == 1 ? 0 : cross_attention_mode, cross_attention_splits,
                                       opt->cross_attention_slots_per_workgroup, out, opt->encoder_precision);
-    if (r == WH_OK) (*out)->fallback_compaction = opt->fallback_compaction;
+    if (r == WH_OK) (*out)->slots.fallback_compaction = opt->fallback_compaction;
     return r;
 }
 extern "C" int wh_session_create_with_mode(wh_model* m, int max_batch, int cross_attention_mode, wh_session** out) {
@@ -773,12 +773,12 @@ DecodeBuffers decode_buffers(wh_session* s, int batch, int max_position) {
     if (s->use_xabs) { s->xabs.enc = s->enc16; db.xabs = &s->xabs; }
     const PassState& p = s->pass; db.mixed = p.mixed;      // what the running pass switches on (pass_state.h)
     if (p.mapped) {             // compacted pass (host.hip decode_text_impl)
-        db.slot_home = s->slot_home_dev;
+        db.slot_home = s->slots.home_dev;
         if (s->use_xabs) { s->xabs_pass = s->xabs; s->xabs_pass.spw = p.spw; db.xabs = &s->xabs_pass; }
     }
-    if (p.owner) { db.self_owner = s->inpass_dev + s->B; db.owner_slots = s->B; }       // a pass that narrowed (host.hip inpass_narrow)
-    db.rule_sets = (p.rules & plan::kRulesPassSetAware) ? &s->rs_args : nullptr;     // a set-aware pass (host.hip decode_text_impl, rule_sets_plan.h)
-    if (p.alt) { db.alt_ids = s->alt_ids; db.alt_lp = s->alt_f32; db.alt_n = p.alt; }      // a pass that records token alternatives (alternatives_plan.h)
+    if (p.owner) { db.self_owner = s->inpass.d.owner; db.owner_slots = s->B; }       // a pass that narrowed (host.hip inpass_narrow)
+    db.rule_sets = (p.rules & plan::kRulesPassSetAware) ? &s->rules.rs_args : nullptr;     // a set-aware pass (host.hip decode_text_impl, rule_sets_plan.h)
+    if (p.alt) { db.alt_ids = s->alt.ids; db.alt_lp = s->alt.f32; db.alt_n = p.alt; }      // a pass that records token alternatives (alternatives_plan.h)
     // cross-attention gate: WH_XATT_GATE=0 never, 1 always, unset: while the model carries more than one session (dec_shared.h)
     const int gate_mode = knob::once<knob::WH_XATT_GATE>();
     const bool gate_on = gate_mode < 0 ? kXattnGateDefault && m->n_sessions.load() > 1 : gate_mode != 0;
@@ -866,20 +866,34 @@ extern "C" int wh_predict_logits(wh_session* s, int batch, const int32_t* tokens
 
 // scratch of the optional alignment post-processing (one slot at a time), sized for the session's current alignment-head count
 static int ensure_align_tmp(wh_session* s) {
+    wh_session::WordAlign& f = s->walign;
     const size_t H = (size_t)s->n_align_alloc;
-    if (s->align_tmp && s->align_tmp_heads != s->n_align_alloc) { WH_HIP(hipStreamSynchronize(s->st)); s->mem.release(s->align_tmp); s->align_tmp = nullptr; }
-    if (!s->align_tmp) {
-        WH_HIP(s->mem.alloc(&s->align_tmp, (size_t)kMaxTok * H * kCtx + 2 * H * kCtx + 256, false));
-        s->align_tmp_heads = s->n_align_alloc;
+    if (f.tmp && f.tmp_heads != s->n_align_alloc) { WH_HIP(hipStreamSynchronize(s->st)); s->mem.release(f.tmp); f.tmp = nullptr; }
+    if (!f.tmp) {
+        mem::AlignTmpView measure{};
+        WH_HIP(s->mem.alloc(&f.tmp, mem::pack_align_tmp(nullptr, kMaxTok, H, kCtx, measure) / sizeof(float), false));
+        mem::pack_align_tmp(f.tmp, kMaxTok, H, kCtx, f.t);
+        f.tmp_heads = s->n_align_alloc;
     }
+    return WH_OK;
+}
+// the only place that allocates the batched DTW's tables (the first call of alignment_paths)
+static int dtw_ensure(wh_session* s) {
+    wh_session::WordAlign& f = s->walign;
+    const size_t B = (size_t)s->B, cap = (size_t)kDtwPathCap;
+    mem::DtwView measure{};
+    if (!f.dev) WH_HIP(s->mem.alloc(&f.dev, mem::pack_dtw(nullptr, B, cap, true, measure) / sizeof(int32_t), false));
+    if (!f.host && s->mem.alloc_pinned(&f.host, mem::pack_dtw(nullptr, B, cap, false, measure) / sizeof(int32_t)) != hipSuccess)
+        return set_error(WH_ERR_HIP, "hipHostMalloc of the alignment path buffer failed");
+    mem::pack_dtw(f.dev, B, cap, true, f.d); mem::pack_dtw(f.host, B, cap, false, f.h);
     return WH_OK;
 }
 // slot b's [224][1500] alignment weights into align_mean: the optional post-processing, else the plain head mean
 static void launch_alignment_slot(wh_session* s, int b, bool postprocess) {
     const size_t n = (size_t)kMaxTok * kCtx, H = (size_t)s->n_align_alloc;
     if (postprocess) {
-        float* stat = s->align_tmp + (size_t)kMaxTok * H * kCtx;
-        launch_alignment_postprocess(s->align + (size_t)b * n * H, s->n_align_alloc, s->align_tmp, stat, reinterpret_cast<int*>(stat + 2 * H * kCtx),
+        const mem::AlignTmpView& t = s->walign.t;
+        launch_alignment_postprocess(s->align + (size_t)b * n * H, s->n_align_alloc, t.rows, t.stat, t.flags,
                                      s->align_znorm, s->align_median, s->align_mean + b * n, s->st);
     } else {
         launch_alignment_mean(s->align + (size_t)b * n * H, 1, s->n_align_alloc, s->align_mean + b * n, s->st);   // this slot only
@@ -897,7 +911,7 @@ extern "C" int wh_get_alignment_weights(wh_session* s, int b, float* out) {
     WH_CHECK_LAUNCH();
     WH_HIP(hipMemcpyAsync(out, s->align_mean + b * n, n * 4, hipMemcpyDeviceToHost, s->st));
     WH_HIP(hipStreamSynchronize(s->st));
-    s->align_d2h_bytes += (long long)(n * 4);
+    s->walign.d2h_bytes += (long long)(n * 4);
     return WH_OK;
 }
 
@@ -911,15 +925,11 @@ int alignment_paths(wh_session* s, int batch, const int32_t* rows, const int32_t
         if (rows[b] < 0 || rows[b] > kDtwMaxRows) return set_error(WH_ERR_INVALID_ARGUMENT, "alignment paths: rows[%d] = %d outside [0, %d]", b, rows[b], kDtwMaxRows);
         max_rows = std::max(max_rows, (int)rows[b]);
     }
-    if (!s->dtw_dev) WH_HIP(s->mem.alloc(&s->dtw_dev, 2 * B + 2 * B * cap, false));
-    if (!s->dtw_host && s->mem.alloc_pinned(&s->dtw_host, B + 2 * B * cap) != hipSuccess)
-        return set_error(WH_ERR_HIP, "hipHostMalloc of the alignment path buffer failed");
-    int* rows_dev = s->dtw_dev;
-    int* len_dev = rows_dev + B;                      // lengths | text_idx | time_idx are contiguous: one copy brings them back
-    int *ti_dev = len_dev + B, *tj_dev = ti_dev + B * cap;
-    *len = s->dtw_host; *ti = s->dtw_host + B; *tj = s->dtw_host + B + B * cap;
+    if (int r = dtw_ensure(s)) return r;
+    const mem::DtwView &d = s->walign.d, &h = s->walign.h;      // lengths | text_idx | time_idx are contiguous on both sides: one copy brings them back
+    *len = h.len; *ti = h.ti; *tj = h.tj;
     if (max_rows == 0) {                              // no slot has a token row: nothing to launch
-        memset(s->dtw_host, 0, B * sizeof(int32_t));
+        memset(h.len, 0, B * sizeof(int32_t));
         return WH_OK;
     }
     const bool postprocess = s->align_znorm || s->align_median > 1;
@@ -930,15 +940,15 @@ int alignment_paths(wh_session* s, int batch, const int32_t* rows, const int32_t
         launch_alignment_mean(s->align, batch, s->n_align_alloc, s->align_mean, s->st);
     }
     WH_CHECK_LAUNCH();
-    WH_HIP(hipMemcpyAsync(rows_dev, rows, sizeof(int) * (size_t)batch, hipMemcpyHostToDevice, s->st));
-    int r = launch_dtw_batch(s->align_mean, rows_dev, batch, max_rows, kMaxTok, kCtx, ti_dev, tj_dev, len_dev, kDtwPathCap, s->st);
+    WH_HIP(hipMemcpyAsync(d.rows, rows, sizeof(int) * (size_t)batch, hipMemcpyHostToDevice, s->st));
+    int r = launch_dtw_batch(s->align_mean, d.rows, batch, max_rows, kMaxTok, kCtx, d.ti, d.tj, d.len, kDtwPathCap, s->st);
     if (r) return r;
-    s->dtw_launches += 1;
+    s->walign.dtw_launches += 1;
     // slots [0, batch) of the three arrays: lengths, then the two index arrays up to the last slot in use
-    const size_t nbytes = (B + B * cap + (size_t)batch * cap) * sizeof(int32_t);
-    WH_HIP(hipMemcpyAsync(s->dtw_host, len_dev, nbytes, hipMemcpyDeviceToHost, s->st));
+    const size_t nbytes = (size_t)(d.tj + (size_t)batch * cap - d.len) * sizeof(int32_t);
+    WH_HIP(hipMemcpyAsync(h.len, d.len, nbytes, hipMemcpyDeviceToHost, s->st));
     WH_HIP(hipStreamSynchronize(s->st));
-    s->align_d2h_bytes += (long long)nbytes;
+    s->walign.d2h_bytes += (long long)nbytes;
     return WH_OK;
 }
 }  // namespace whi
@@ -963,99 +973,99 @@ extern "C" int wh_alignment_paths(wh_session* s, int batch, const int32_t* rows,
 extern "C" int wh_session_set_word_alignment(wh_session* s, int mode) {
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_word_alignment: null session");
     if (mode != 0 && mode != 1) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_word_alignment: mode %d (0 = host, 1 = device)", mode);
-    s->word_alignment = mode;
+    s->walign.mode = mode;
     return WH_OK;
 }
-extern "C" int wh_session_word_alignment(const wh_session* s) { return s ? s->word_alignment : -1; }
+extern "C" int wh_session_word_alignment(const wh_session* s) { return s ? s->walign.mode : -1; }
 extern "C" int wh_session_word_alignment_stats(const wh_session* s, int64_t* dtw_launches, int64_t* alignment_d2h_bytes) {
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_word_alignment_stats: null session");
-    if (dtw_launches) *dtw_launches = s->dtw_launches;
-    if (alignment_d2h_bytes) *alignment_d2h_bytes = s->align_d2h_bytes;
+    whi::store_stat(dtw_launches, s->walign.dtw_launches);
+    whi::store_stat(alignment_d2h_bytes, s->walign.d2h_bytes);
     return WH_OK;
 }
 
 extern "C" int wh_session_set_fallback_compaction(wh_session* s, int mode) {
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_fallback_compaction: null session");
     if (mode != 0 && mode != 1) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_fallback_compaction: mode %d (0 = off, 1 = on)", mode);
-    s->fallback_compaction = mode;
+    s->slots.fallback_compaction = mode;
     return WH_OK;
 }
-extern "C" int wh_session_fallback_compaction(const wh_session* s) { return s ? s->fallback_compaction : -1; }
+extern "C" int wh_session_fallback_compaction(const wh_session* s) { return s ? s->slots.fallback_compaction : -1; }
 extern "C" int wh_session_set_inpass_compaction(wh_session* s, int mode) {
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_inpass_compaction: null session");
     if (mode != 0 && mode != 1) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_inpass_compaction: mode %d (0 = off, 1 = on)", mode);
-    s->inpass_compaction = mode;
+    s->inpass.mode = mode;
     return WH_OK;
 }
-extern "C" int wh_session_inpass_compaction(const wh_session* s) { return s ? s->inpass_compaction : -1; }
+extern "C" int wh_session_inpass_compaction(const wh_session* s) { return s ? s->inpass.mode : -1; }
 extern "C" int wh_session_set_option_mixing(wh_session* s, int mode) {
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_option_mixing: null session");
     if (mode != 0 && mode != 1) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_option_mixing: mode %d (0 = off, 1 = on)", mode);
-    s->option_mixing = mode;
+    s->mix.mode = mode;
     return WH_OK;
 }
-extern "C" int wh_session_option_mixing(const wh_session* s) { return s ? s->option_mixing : -1; }
+extern "C" int wh_session_option_mixing(const wh_session* s) { return s ? s->mix.mode : -1; }
 extern "C" int wh_session_option_mixing_stats(const wh_session* s, int64_t* groups_run, int64_t* mixed_passes, int64_t* max_classes_in_a_pass) {
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_option_mixing_stats: null session");
-    if (groups_run) *groups_run = s->mix_groups_run;
-    if (mixed_passes) *mixed_passes = s->mix_mixed_passes;
-    if (max_classes_in_a_pass) *max_classes_in_a_pass = s->mix_max_classes;
+    whi::store_stat(groups_run, s->mix.groups_run);
+    whi::store_stat(mixed_passes, s->mix.mixed_passes);
+    whi::store_stat(max_classes_in_a_pass, s->mix.max_classes);
     return WH_OK;
 }
 // per-slot prompts (host.hip decode_text_impl, transcribe_jobs)
 extern "C" int wh_session_set_prompt_mixing(wh_session* s, int mode) {
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_prompt_mixing: null session");
     if (mode != 0 && mode != 1) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_prompt_mixing: mode %d (0 = off, 1 = on)", mode);
-    s->prompt_mixing = mode;
+    s->mix.prompt_mixing = mode;
     return WH_OK;
 }
-extern "C" int wh_session_prompt_mixing(const wh_session* s) { return s ? s->prompt_mixing : -1; }
+extern "C" int wh_session_prompt_mixing(const wh_session* s) { return s ? s->mix.prompt_mixing : -1; }
 extern "C" int wh_session_set_previous_text(wh_session* s, int mode, float reset_temperature) {
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_previous_text: null session");
     if (!plan::previous_text_mode_valid(mode)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_previous_text: mode %d (0 = off, 1 = on)", mode);
-    s->previous_text = mode; s->previous_text_reset = reset_temperature;
+    s->mix.previous_text = mode; s->mix.previous_text_reset = reset_temperature;
     return WH_OK;
 }
 extern "C" int wh_session_previous_text(const wh_session* s, float* reset_temperature) {
     if (!s) return -1;
-    if (reset_temperature) *reset_temperature = s->previous_text_reset;
-    return s->previous_text;
+    if (reset_temperature) *reset_temperature = s->mix.previous_text_reset;
+    return s->mix.previous_text;
 }
 extern "C" int wh_session_slot_prompt_stats(const wh_session* s, int64_t* passes, int64_t* max_distinct_prompts, int64_t* prompt_positions,
                                             int64_t* windows_carried, int64_t* resets) {
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_slot_prompt_stats: null session");
-    if (passes) *passes = s->sp_passes;
-    if (max_distinct_prompts) *max_distinct_prompts = s->sp_max_distinct;
-    if (prompt_positions) *prompt_positions = s->sp_positions;
-    if (windows_carried) *windows_carried = s->sp_windows_carried;
-    if (resets) *resets = s->sp_resets;
+    whi::store_stat(passes, s->mix.sp_passes);
+    whi::store_stat(max_distinct_prompts, s->mix.sp_max_distinct);
+    whi::store_stat(prompt_positions, s->mix.sp_positions);
+    whi::store_stat(windows_carried, s->mix.sp_windows_carried);
+    whi::store_stat(resets, s->mix.sp_resets);
     return WH_OK;
 }
 extern "C" int wh_session_inpass_compaction_stats(const wh_session* s, int64_t* switches, int64_t* slot_steps_saved) {
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_inpass_compaction_stats: null session");
-    if (switches) *switches = s->inpass_switches;
-    if (slot_steps_saved) *slot_steps_saved = s->inpass_slot_steps_saved;
+    whi::store_stat(switches, s->inpass.switches);
+    whi::store_stat(slot_steps_saved, s->inpass.slot_steps_saved);
     return WH_OK;
 }
 extern "C" int wh_session_decode_pass_stats(const wh_session* s, int64_t* passes, int64_t* compacted_passes, int64_t* slot_steps) {
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_decode_pass_stats: null session");
-    if (passes) *passes = s->decode_passes;
-    if (compacted_passes) *compacted_passes = s->compacted_passes;
-    if (slot_steps) *slot_steps = s->slot_steps;
+    whi::store_stat(passes, s->count.decode_passes);
+    whi::store_stat(compacted_passes, s->count.compacted_passes);
+    whi::store_stat(slot_steps, s->count.slot_steps);
     return WH_OK;
 }
 
 extern "C" int wh_session_set_beam_ranking(wh_session* s, int mode) {
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_beam_ranking: null session");
     if (mode != 0 && mode != 1) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_beam_ranking: mode %d (0 = host, 1 = device)", mode);
-    s->beam_ranking = mode;
+    s->beam.ranking = mode;
     return WH_OK;
 }
-extern "C" int wh_session_beam_ranking(const wh_session* s) { return s ? s->beam_ranking : -1; }
+extern "C" int wh_session_beam_ranking(const wh_session* s) { return s ? s->beam.ranking : -1; }
 extern "C" int wh_session_beam_stats(const wh_session* s, int64_t* rank_launches, int64_t* loop_synchronisations) {
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_beam_stats: null session");
-    if (rank_launches) *rank_launches = s->beam_rank_launches;
-    if (loop_synchronisations) *loop_synchronisations = s->beam_loop_syncs;
+    whi::store_stat(rank_launches, s->beam.rank_launches);
+    whi::store_stat(loop_synchronisations, s->beam.loop_syncs);
     return WH_OK;
 }
 

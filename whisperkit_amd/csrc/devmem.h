@@ -1,6 +1,7 @@
 // Who owns device and pinned memory, and how one allocation is carved into regions.  Plain C++17 (no HIP headers), like launch_plan.h:
-// the library instantiates Owned with the HIP calls (internal.h HipMem), tests/native/devmem_check.cpp with a counting fake, and the four
-// layout functions below run there under g++ with the SAME code the library carves with (tests/test_devmem.py).
+// the library instantiates Owned with the HIP calls (internal.h HipMem), tests/native/devmem_check.cpp with a counting fake, and the layout
+// functions below (carve_*: blobs of 256-byte aligned regions; pack_*: the packed tables of the session's opt-in features) and the staging
+// ring run there under g++ with the SAME code the library cuts its buffers with (tests/test_devmem.py).
 #pragma once
 #include <atomic>
 #include <cstddef>
@@ -127,6 +128,127 @@ size_t carve_session_d32(void* base, size_t d, size_t B, Q& q) {
     c.take(q.ticket, n_bt * 4096);
     return c.size();
 }
+
+// ---------------------------------------------------------------------------------------------- packed allocations
+// The sibling of Carve for the small tables of the session's opt-in features: regions back to back at their natural alignment, nothing
+// rounded, because single copies span several regions (the no-speech tables go up in one copy, the DTW lengths and paths come down in
+// one).  Same discipline: a pack_* function lists the regions ONCE, runs against a null base to measure and against the device and the
+// pinned allocation to fill a typed view of each; the session keeps the views and nothing else cuts these buffers.
+class Pack {
+public:
+    explicit Pack(void* base) : base_(reinterpret_cast<uintptr_t>(base)) {}
+    template <class T> void take(T*& p, size_t n) {
+        off_ = (off_ + alignof(T) - 1) / alignof(T) * alignof(T);
+        p = reinterpret_cast<T*>(base_ + off_);
+        off_ += n * sizeof(T);
+    }
+    size_t size() const { return off_; }
+private:
+    uintptr_t base_;
+    size_t off_ = 0;
+};
+
+// The views.  The pack_* functions take the destination as a template parameter like the carve_* ones; these are what the library passes.
+struct NoSpeechView { int32_t* pos; float *stop, *prob; int32_t *stopped, *cfg; };
+struct SlotTableView { int32_t *home, *live; };
+struct ForcedOutView { float* lp; int32_t* best; float* best_lp; };
+struct AltF32View { float *lp, *entropy; };
+struct InpassDevView { int32_t *live, *owner; };
+struct InpassRegionView { int32_t *home, *live, *owner; };
+struct RuleSetsDevView { unsigned long long* matches; int32_t *slots, *bank; };
+struct RuleSetsHostView { int32_t *slots, *stage; };
+struct DtwView { int32_t *rows, *len, *ti, *tj; };
+struct BeamSumView { float* half[2]; };
+struct AlignTmpView { float *rows, *stat; int32_t* flags; };
+
+// no-speech detection, by home slot: scoring position | stop threshold | probability | stopped flag | (token, lane divisor)
+template <class V> size_t pack_nospeech(void* base, size_t B, V& v) {
+    Pack c(base);
+    c.take(v.pos, B); c.take(v.stop, B); c.take(v.prob, B); c.take(v.stopped, B); c.take(v.cfg, 2);
+    return c.size();
+}
+// the pinned side of the compacted-pass slot table: home slot | live flag of every compact slot
+template <class V> size_t pack_slot_table(void* base, size_t B, V& v) {
+    Pack c(base);
+    c.take(v.home, B); c.take(v.live, B);
+    return c.size();
+}
+// forced pass, one entry per position of a call (at most B sequences of max_tok tokens): log p(target) | argmax | log p(argmax)
+template <class V> size_t pack_forced_out(void* base, size_t B, size_t max_tok, V& v) {
+    const size_t cap = B * (max_tok - 1);
+    Pack c(base);
+    c.take(v.lp, cap); c.take(v.best, cap); c.take(v.best_lp, cap);
+    return c.size();
+}
+// token alternatives, the fp32 buffer: log-probabilities [B][positions][n_max] | entropies [B][positions] (the kernel indexes both from one base)
+template <class V> size_t pack_alternatives_f32(void* base, size_t B, size_t positions, size_t n_max, V& v) {
+    Pack c(base);
+    c.take(v.lp, B * positions * n_max); c.take(v.entropy, B * positions);
+    return c.size();
+}
+// in-pass compaction on the device: live flags [B] | row -> owner rows [B][max_tok]
+template <class V> size_t pack_inpass_dev(void* base, size_t B, size_t max_tok, V& v) {
+    Pack c(base);
+    c.take(v.live, B); c.take(v.owner, B * max_tok);
+    return c.size();
+}
+// ... and one region of its pinned staging (a StageRing of them): home slots [B] | live flags [B] | owner rows [B][max_tok]
+template <class V> size_t pack_inpass_region(void* base, size_t B, size_t max_tok, V& v) {
+    Pack c(base);
+    c.take(v.home, B); c.take(v.live, B); c.take(v.owner, B * max_tok);
+    return c.size();
+}
+// per-audio rule sets on the device: 64-bit match counters [n_sets] | set of every home slot [n_slots] | the banked sets [bank_words]
+template <class V> size_t pack_rule_sets_dev(void* base, size_t n_sets, size_t n_slots, size_t bank_words, V& v) {
+    Pack c(base);
+    c.take(v.matches, n_sets); c.take(v.slots, n_slots); c.take(v.bank, bank_words);
+    return c.size();
+}
+// ... and pinned: the slot table's mirror [n_slots] | the staging of one set [set_words]
+template <class V> size_t pack_rule_sets_host(void* base, size_t n_slots, size_t set_words, V& v) {
+    Pack c(base);
+    c.take(v.slots, n_slots); c.take(v.stage, set_words);
+    return c.size();
+}
+// batched DTW: token rows [B] (the device buffer only: with_rows) | path lengths [B] | text indices [B][cap] | time indices [B][cap]
+template <class V> size_t pack_dtw(void* base, size_t B, size_t cap, bool with_rows, V& v) {
+    Pack c(base);
+    c.take(v.rows, with_rows ? B : 0); c.take(v.len, B); c.take(v.ti, B * cap); c.take(v.tj, B * cap);
+    return c.size();
+}
+// device beam ranking: the cumulative log-probabilities of both halves of the ping-pong, [B] each
+template <class V> size_t pack_beam_sums(void* base, size_t B, V& v) {
+    Pack c(base);
+    c.take(v.half[0], B); c.take(v.half[1], B);
+    return c.size();
+}
+// alignment post-processing scratch of one slot: softmax rows [max_tok][heads][ctx] | statistics [2][heads][ctx] | 256 row flags
+template <class V> size_t pack_align_tmp(void* base, size_t max_tok, size_t heads, size_t ctx, V& v) {
+    Pack c(base);
+    c.take(v.rows, max_tok * heads * ctx); c.take(v.stat, 2 * heads * ctx); c.take(v.flags, 256);
+    return c.size();
+}
+
+// ---------------------------------------------------------------------------------------------- staging ring
+// A pinned buffer of `regions` regions of `stride` elements whose region k is uploaded stream-ordered (to the same offset of a device twin,
+// or to tables of its own): every launch of a pass takes the next regions, so the host never writes one the stream has not consumed.  One
+// ring per pass, on the caller's stack; what a full ring means is the caller's business.
+class StageRing {
+public:
+    static constexpr size_t kFull = ~(size_t)0;
+    StageRing(size_t regions, size_t stride) : regions_(regions), stride_(stride) {}
+    // the element offset of the next n regions, or kFull (nothing is taken then)
+    size_t take(size_t n) {
+        if (n > regions_ - next_) return kFull;
+        const size_t off = next_ * stride_;
+        next_ += n;
+        return off;
+    }
+    size_t taken() const { return next_; }
+    size_t stride() const { return stride_; }
+private:
+    size_t regions_, stride_, next_ = 0;
+};
 
 }  // namespace mem
 }  // namespace wh

@@ -282,12 +282,12 @@ static void launch_pass_step(wh_session* s, const DecodeBuffers& db, int step) {
 // stream-ordered in front of its launches.  Always into the session's own tables that are on; with `bank` (a set-aware pass, wh_debug_rule_sets_apply) also
 // into both halves of every defined banked set whose device copy holds another value.
 static int rules_write_special_begin(wh_session* s, int special_begin, bool bank) {
-    if (s->logit_rules_on) { s->lr_host[2] = special_begin; WH_HIP(hipMemcpyAsync(s->lr_dev + 2, s->lr_host + 2, sizeof(int32_t), hipMemcpyHostToDevice, s->st)); }
-    if (s->phrase_rules_on) { s->pr_host[2] = special_begin; WH_HIP(hipMemcpyAsync(s->pr_dev + 2, s->pr_host + 2, sizeof(int32_t), hipMemcpyHostToDevice, s->st)); }
+    if (s->logit_rules_on) { s->rules.lr_host[2] = special_begin; WH_HIP(hipMemcpyAsync(s->rules.lr_dev + 2, s->rules.lr_host + 2, sizeof(int32_t), hipMemcpyHostToDevice, s->st)); }
+    if (s->phrase_rules_on) { s->rules.pr_host[2] = special_begin; WH_HIP(hipMemcpyAsync(s->rules.pr_dev + 2, s->rules.pr_host + 2, sizeof(int32_t), hipMemcpyHostToDevice, s->st)); }
     for (int k = 1; bank && k < plan::kMaxRuleSets; ++k) {
-        wh_session::RuleSetCopy& c = s->rs_sets[k];
+        wh_session::RuleSetCopy& c = s->rules.rs_sets[k];
         if (!c.defined || c.special_begin == special_begin) continue;
-        int32_t* base = s->rs_dev + whi::kRsOffBank + plan::rule_set_offset(k);
+        int32_t* base = s->rules.rs.bank + plan::rule_set_offset(k);
         WH_HIP(hipMemsetD32Async(base + plan::kRuleSetOffPhrase + 2, special_begin, 1, s->st));
         WH_HIP(hipMemsetD32Async(base + plan::kRuleSetOffLogit + 2, special_begin, 1, s->st));
         c.special_begin = special_begin;
@@ -358,7 +358,7 @@ static int report_progress(wh_session* s, int batch) {
         SeqState& q = s->seq_host[b];
         if (!q.active || q.done || q.n_tokens <= 0) continue;
         wh_progress p{};
-        p.slot = s->pass.mapped ? s->slot_home_host[b] : b;      // a compacted pass reports the window's home slot
+        p.slot = s->pass.mapped ? s->slots.h.home[b] : b;      // a compacted pass reports the window's home slot
         p.n_tokens = q.n_tokens; p.tokens = q.tokens;
         float sum = 0;
         for (int i = 0; i < q.n_tokens; ++i) sum += q.logprobs[i];
@@ -383,46 +383,51 @@ static int report_progress(wh_session* s, int batch) {
 
 // ---- no-speech detection (wh_session_set_no_speech_detection; NO REFERENCE BEHAVIOUR: openai/whisper decoding.py no_speech_prob semantics)
 namespace whi {
-static int nospeech_ensure(wh_session* s) {
-    const size_t n = 4 * (size_t)s->B + 2;
-    if (!s->ns_dev) WH_HIP(s->mem.alloc(&s->ns_dev, n, true));
-    if (!s->ns_host) WH_HIP(s->mem.alloc_pinned(&s->ns_host, n));
-    NoSpeechArgs& a = s->ns_args;
-    a.pos = s->ns_dev; a.stop = reinterpret_cast<const float*>(s->ns_dev + s->B); a.prob = reinterpret_cast<float*>(s->ns_dev + 2 * (size_t)s->B);
-    a.stopped = s->ns_dev + 3 * (size_t)s->B; a.cfg = s->ns_dev + 4 * (size_t)s->B; a.n_slots = s->B;
+// the only place that allocates the feature's memory.  probe: also what wh_no_speech_probs puts back (the decode states, the cache rows 0)
+static int nospeech_ensure(wh_session* s, bool probe = false) {
+    wh_session::NoSpeech& f = s->ns;
+    mem::NoSpeechView measure{};
+    const size_t n = mem::pack_nospeech(nullptr, (size_t)s->B, measure) / sizeof(int32_t);
+    if (!f.dev) WH_HIP(s->mem.alloc(&f.dev, n, true));
+    if (!f.host) WH_HIP(s->mem.alloc_pinned(&f.host, n));
+    mem::pack_nospeech(f.dev, (size_t)s->B, f.d); mem::pack_nospeech(f.host, (size_t)s->B, f.h);
+    f.args = NoSpeechArgs{f.d.pos, f.d.stop, f.d.prob, f.d.stopped, f.d.cfg, s->B};
+    if (!probe) return WH_OK;
+    const wh_dims& dm = s->m->dims;
+    if (!f.seq_keep) WH_HIP(s->mem.alloc(&f.seq_keep, (size_t)s->B, false));
+    if (!f.kv_keep) WH_HIP(s->mem.alloc(&f.kv_keep, 2 * (size_t)dm.n_text_layer * s->B * dm.n_text_head * kHeadDim, false));
     return WH_OK;
 }
 // The caller's stream holds no launch that reads the tables (every pass ends drained).  prob starts at -1, "not scored": a probability is never negative
 int nospeech_arm(wh_session* s, int n, const int* pos, const float* stop, int token, int lane_div) {
     int r = nospeech_ensure(s);
     if (r) return r;
-    const int B = s->B;
-    int32_t* h = s->ns_host;
-    const float never = INFINITY, unscored = -1.0f;
-    for (int b = 0; b < B; ++b) {
-        h[b] = b < n ? pos[b] : -1;
-        memcpy(h + B + b, (b < n && stop) ? &stop[b] : &never, sizeof(float));
-        memcpy(h + 2 * (size_t)B + b, &unscored, sizeof(float));
-        h[3 * (size_t)B + b] = 0;
+    mem::NoSpeechView measure{};
+    const mem::NoSpeechView& h = s->ns.h;
+    for (int b = 0; b < s->B; ++b) {
+        h.pos[b] = b < n ? pos[b] : -1;
+        h.stop[b] = (b < n && stop) ? stop[b] : INFINITY;
+        h.prob[b] = -1.0f;      // "not scored"
+        h.stopped[b] = 0;
     }
-    h[4 * (size_t)B] = token; h[4 * (size_t)B + 1] = lane_div;
-    WH_HIP(hipMemcpyAsync(s->ns_dev, h, sizeof(int32_t) * (4 * (size_t)B + 2), hipMemcpyHostToDevice, s->st));
+    h.cfg[0] = token; h.cfg[1] = lane_div;
+    WH_HIP(hipMemcpyAsync(s->ns.dev, s->ns.host, mem::pack_nospeech(nullptr, (size_t)s->B, measure), hipMemcpyHostToDevice, s->st));      // every region, one copy
     s->pass.ns = plan::nospeech_step_range(pos, n);
     return WH_OK;
 }
 // behind the pass: prob | stopped by home slot into the pinned mirror (an unscored slot reads 0), the counters.  opts: null, or [n] the options whose
 // noSpeechThreshold a scored slot is counted against (null entries: not counted)
 int nospeech_collect(wh_session* s, int n, const wh_decoding_options* const* opts) {
-    const size_t B = (size_t)s->B;
-    WH_HIP(hipMemcpyAsync(s->ns_host + 2 * B, s->ns_dev + 2 * B, sizeof(int32_t) * 2 * B, hipMemcpyDeviceToHost, s->st));
+    const mem::NoSpeechView &d = s->ns.d, &h = s->ns.h;
+    // prob | stopped are adjacent (pack_nospeech): one copy brings both down
+    WH_HIP(hipMemcpyAsync(h.prob, d.prob, (size_t)s->B * (sizeof(*d.prob) + sizeof(*d.stopped)), hipMemcpyDeviceToHost, s->st));
     WH_HIP(hipStreamSynchronize(s->st));
     for (int b = 0; b < n; ++b) {
-        float p;
-        memcpy(&p, s->ns_host + 2 * B + b, sizeof(p));
-        if (p < 0.0f) { p = 0.0f; memcpy(s->ns_host + 2 * B + b, &p, sizeof(p)); continue; }
-        s->ns_rows_scored += 1;
-        if (opts && opts[b] && !isnan(opts[b]->no_speech_threshold) && p > opts[b]->no_speech_threshold) s->ns_windows_over += 1;
-        if (s->ns_host[3 * B + b]) s->ns_windows_stopped += 1;
+        const float p = h.prob[b];
+        if (p < 0.0f) { h.prob[b] = 0.0f; continue; }
+        s->ns.rows_scored += 1;
+        if (opts && opts[b] && !isnan(opts[b]->no_speech_threshold) && p > opts[b]->no_speech_threshold) s->ns.windows_over += 1;
+        if (h.stopped[b]) s->ns.windows_stopped += 1;
     }
     return WH_OK;
 }
@@ -430,37 +435,49 @@ int nospeech_collect(wh_session* s, int n, const wh_decoding_options* const* opt
 
 // ---- token alternatives (wh_session_set_token_alternatives; NO REFERENCE BEHAVIOUR: torch.topk(log_softmax(row / T)) and the entropy of that distribution)
 namespace whi {
+// the only place that allocates the feature's memory (wh_session_set_token_alternatives, the first call that turns the mode on)
+static int alternatives_ensure(wh_session* s) {
+    wh_session::TokenAlternatives& f = s->alt;
+    const size_t B = (size_t)s->B, ids = plan::alternatives_id_words(s->B);
+    mem::AltF32View measure{};
+    const size_t f32 = mem::pack_alternatives_f32(nullptr, B, plan::kAltPositions, plan::kMaxAlternatives, measure) / sizeof(float);
+    if (!f.f32) WH_HIP(s->mem.alloc(&f.f32, f32, false));
+    if (!f.ids_host) WH_HIP(s->mem.alloc_pinned(&f.ids_host, ids));
+    if (!f.f32_host) WH_HIP(s->mem.alloc_pinned(&f.f32_host, f32));
+    mem::pack_alternatives_f32(f.f32, B, plan::kAltPositions, plan::kMaxAlternatives, f.d);
+    mem::pack_alternatives_f32(f.f32_host, B, plan::kAltPositions, plan::kMaxAlternatives, f.h);
+    if (!f.ids) WH_HIP(s->mem.alloc(&f.ids, ids, false));      // (last: ids set = everything is there; every pass resets the rows it decodes)
+    return WH_OK;
+}
 // The caller's stream holds no launch that writes the buffers (every pass ends drained).  Runs of live home slots: one memset triple for a full pass
 int alternatives_arm(wh_session* s, int n, const int32_t* active) {
-    if (!s->alt_ids || !s->alt_f32) return set_error(WH_ERR_INVALID_ARGUMENT, "token alternatives: the buffers are not allocated (wh_session_set_token_alternatives)");
+    if (!s->alt.ids || !s->alt.f32) return set_error(WH_ERR_INVALID_ARGUMENT, "token alternatives: the buffers are not allocated (wh_session_set_token_alternatives)");
     const size_t row = (size_t)plan::kAltPositions * plan::kMaxAlternatives;
     const float ninf = -INFINITY;
     int32_t ninf_bits;
     memcpy(&ninf_bits, &ninf, sizeof(ninf_bits));
     std::vector<int32_t> begin((size_t)n), count((size_t)n);
     const int runs = plan::alternatives_live_runs(active, n, begin.data(), count.data());
-    float* const ent = s->alt_f32 + plan::alternatives_lp_floats(s->B);
     for (int k = 0; k < runs; ++k) {
         const size_t b0 = (size_t)begin[(size_t)k], nb = (size_t)count[(size_t)k];
-        WH_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s->alt_ids + b0 * row), plan::kAltNoId, nb * row, s->st));
-        WH_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s->alt_f32 + b0 * row), ninf_bits, nb * row, s->st));
-        WH_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ent + b0 * plan::kAltPositions), 0, nb * plan::kAltPositions, s->st));
+        WH_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s->alt.ids + b0 * row), plan::kAltNoId, nb * row, s->st));
+        WH_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s->alt.d.lp + b0 * row), ninf_bits, nb * row, s->st));
+        WH_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s->alt.d.entropy + b0 * plan::kAltPositions), 0, nb * plan::kAltPositions, s->st));
     }
-    s->pass.alt = s->token_alternatives;
-    s->alt_passes += 1;
+    s->pass.alt = s->alt.n;
+    s->alt.passes += 1;
     return WH_OK;
 }
 int alternatives_collect(wh_session* s, int n, const int32_t* active) {
     const size_t row = (size_t)plan::kAltPositions * plan::kMaxAlternatives;
     std::vector<int32_t> begin((size_t)n), count((size_t)n);
     const int runs = plan::alternatives_live_runs(active, n, begin.data(), count.data());
-    const size_t ent_off = plan::alternatives_lp_floats(s->B);
     for (int k = 0; k < runs; ++k) {
         const size_t b0 = (size_t)begin[(size_t)k], nb = (size_t)count[(size_t)k];
-        WH_HIP(hipMemcpyAsync(s->alt_ids_host + b0 * row, s->alt_ids + b0 * row, sizeof(int32_t) * nb * row, hipMemcpyDeviceToHost, s->st));
-        WH_HIP(hipMemcpyAsync(s->alt_f32_host + b0 * row, s->alt_f32 + b0 * row, sizeof(float) * nb * row, hipMemcpyDeviceToHost, s->st));
-        WH_HIP(hipMemcpyAsync(s->alt_f32_host + ent_off + b0 * plan::kAltPositions, s->alt_f32 + ent_off + b0 * plan::kAltPositions, sizeof(float) * nb * plan::kAltPositions, hipMemcpyDeviceToHost, s->st));
-        s->alt_d2h_bytes += (long long)(nb * (2 * row + plan::kAltPositions) * 4);
+        WH_HIP(hipMemcpyAsync(s->alt.ids_host + b0 * row, s->alt.ids + b0 * row, sizeof(int32_t) * nb * row, hipMemcpyDeviceToHost, s->st));
+        WH_HIP(hipMemcpyAsync(s->alt.h.lp + b0 * row, s->alt.d.lp + b0 * row, sizeof(float) * nb * row, hipMemcpyDeviceToHost, s->st));
+        WH_HIP(hipMemcpyAsync(s->alt.h.entropy + b0 * plan::kAltPositions, s->alt.d.entropy + b0 * plan::kAltPositions, sizeof(float) * nb * plan::kAltPositions, hipMemcpyDeviceToHost, s->st));
+        s->alt.d2h_bytes += (long long)(nb * (2 * row + plan::kAltPositions) * 4);
     }
     WH_HIP(hipStreamSynchronize(s->st));
     return WH_OK;
@@ -468,7 +485,40 @@ int alternatives_collect(wh_session* s, int n, const int32_t* active) {
 }  // namespace whi
 
 // ---- in-pass compaction (wh_session_set_inpass_compaction): the layout of the pass run_token_loop drives, in the session's home-slot terms
+// The slot table of a pass under pass.mapped: the device half the kernels read and the pinned half report_progress reads (internal.h SlotTable).  The only place
+// that allocates either; every pass that sets pass.mapped comes through here first
+static int slot_table_ensure(wh_session* s) {
+    wh_session::SlotTable& f = s->slots;
+    mem::SlotTableView measure{};
+    if (!f.home_dev) WH_HIP(s->mem.alloc(&f.home_dev, (size_t)s->B, false));
+    if (!f.host) WH_HIP(s->mem.alloc_pinned(&f.host, mem::pack_slot_table(nullptr, (size_t)s->B, measure) / sizeof(int32_t)));
+    mem::pack_slot_table(f.host, (size_t)s->B, f.h);
+    return WH_OK;
+}
+// words of one region of the in-pass staging
+static size_t inpass_region_words(const wh_session* s) {
+    mem::InpassRegionView region{};
+    return mem::pack_inpass_region(nullptr, (size_t)s->B, kMaxTok, region) / sizeof(int32_t);
+}
+// the only place that allocates in-pass compaction's memory.  narrowing false: what a pass under the option needs before it runs (the second snapshot buffer);
+// true: what its first narrowing needs
+static int inpass_ensure(wh_session* s, bool narrowing) {
+    wh_session::Inpass& f = s->inpass;
+    const size_t B = (size_t)s->B;
+    if (!narrowing) {
+        if (!f.seq_snap) WH_HIP(s->mem.alloc_pinned(&f.seq_snap, B));
+        return WH_OK;
+    }
+    mem::InpassDevView measure{};
+    if (!f.seq_home) WH_HIP(s->mem.alloc(&f.seq_home, B, true));
+    if (!f.dev) WH_HIP(s->mem.alloc(&f.dev, mem::pack_inpass_dev(nullptr, B, kMaxTok, measure) / sizeof(int32_t), false));
+    if (!f.stage) WH_HIP(s->mem.alloc_pinned(&f.stage, (size_t)plan::kInpassMaxSwitches * inpass_region_words(s)));
+    mem::pack_inpass_dev(f.dev, B, kMaxTok, f.d);
+    return WH_OK;
+}
+
 struct PassLayout {
+    mem::StageRing ring{0, 0};               // the staging regions of this pass's narrowings (inpass.stage)
     int width = 0, width0 = 0;               // compact slots now / when the pass began
     int n_home = 0;                          // home slots of the call (its `batch`): what is read back by home slot after a narrowing
     int switches = 0;                        // narrowings of this pass so far
@@ -487,28 +537,28 @@ static int inpass_narrow(wh_session* s, PassLayout& L, const SeqState* snap, con
     int n_live = 0;
     for (int i = 0; i < L.width; ++i) if (L.live[i] && alive[L.home[i]]) { keep[i] = 1; ++n_live; }
     const plan::CompactPassPlan p = plan::inpass_compact_plan(n_live, L.width, B, s->use_xabs ? s->xabs.spw : 1, loop_count - steps_done);
-    if (!p.compact || L.switches >= plan::kInpassMaxSwitches) return WH_OK;
-    const size_t region = 2 * (size_t)B + (size_t)B * kMaxTok;
-    if (!s->slot_home_dev) WH_HIP(s->mem.alloc(&s->slot_home_dev, (size_t)B, false));
-    if (!s->slot_home_host) WH_HIP(s->mem.alloc_pinned(&s->slot_home_host, 2 * (size_t)B));
-    if (!s->seq_home) WH_HIP(s->mem.alloc(&s->seq_home, (size_t)B, true));
-    if (!s->inpass_dev) WH_HIP(s->mem.alloc(&s->inpass_dev, (size_t)B + (size_t)B * kMaxTok, false));
-    if (!s->inpass_stage) WH_HIP(s->mem.alloc_pinned(&s->inpass_stage, (size_t)plan::kInpassMaxSwitches * region));
-    int32_t* home = s->inpass_stage + (size_t)L.switches * region, *live = home + B, *owner = live + B;
+    if (!p.compact) return WH_OK;
+    const size_t at = L.ring.take(1);
+    if (at == mem::StageRing::kFull) return WH_OK;      // (as many switches as the ladder has rungs: the pass stays at its width)
+    if (int r = slot_table_ensure(s)) return r;
+    if (int r = inpass_ensure(s, true)) return r;
+    mem::InpassRegionView stage{};
+    mem::pack_inpass_region(s->inpass.stage + at, (size_t)B, kMaxTok, stage);
+    int32_t *const home = stage.home, *const live = stage.live, *const owner = stage.owner;
     const int n = plan::inpass_compose(L.home.data(), L.live.data(), L.switches ? L.owner.data() : nullptr, L.width, keep.data(), p.width, steps_done, kMaxTok, B,
                                        home, live, owner);
     if (n != n_live) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text: the narrowed pass does not hold its live slots");
-    launch_seq_park(s->seq, s->seq_home, s->pass.mapped ? s->slot_home_dev : nullptr, L.width, B, s->st);
-    WH_HIP(hipMemcpyAsync(s->slot_home_dev, home, sizeof(int32_t) * p.width, hipMemcpyHostToDevice, s->st));
-    WH_HIP(hipMemcpyAsync(s->inpass_dev, live, sizeof(int32_t) * p.width, hipMemcpyHostToDevice, s->st));
-    WH_HIP(hipMemcpyAsync(s->inpass_dev + B, owner, sizeof(int32_t) * (size_t)p.width * kMaxTok, hipMemcpyHostToDevice, s->st));
-    launch_seq_gather(s->seq_home, s->seq, s->slot_home_dev, s->inpass_dev, p.width, B, s->st);
+    launch_seq_park(s->seq, s->inpass.seq_home, s->pass.mapped ? s->slots.home_dev : nullptr, L.width, B, s->st);
+    WH_HIP(hipMemcpyAsync(s->slots.home_dev, home, sizeof(int32_t) * p.width, hipMemcpyHostToDevice, s->st));
+    WH_HIP(hipMemcpyAsync(s->inpass.d.live, live, sizeof(int32_t) * p.width, hipMemcpyHostToDevice, s->st));
+    WH_HIP(hipMemcpyAsync(s->inpass.d.owner, owner, sizeof(int32_t) * (size_t)p.width * kMaxTok, hipMemcpyHostToDevice, s->st));
+    launch_seq_gather(s->inpass.seq_home, s->seq, s->slots.home_dev, s->inpass.d.live, p.width, B, s->st);
     WH_CHECK_LAUNCH();
     L.width = p.width; L.switches += 1;
     L.home.assign(home, home + p.width); L.live.assign(live, live + p.width); L.owner.assign(owner, owner + (size_t)p.width * kMaxTok);
-    memcpy(s->slot_home_host, home, sizeof(int32_t) * p.width);      // report_progress: compact slot -> home slot
+    memcpy(s->slots.h.home, home, sizeof(int32_t) * p.width);      // report_progress: compact slot -> home slot
     s->pass.mapped = true; s->pass.spw = p.spw; s->pass.owner = true;
-    s->inpass_switches += 1;
+    s->inpass.switches += 1;
     return WH_OK;
 }
 
@@ -519,13 +569,13 @@ static int run_token_loop(wh_session* s, int batch, int loop_count, PassLayout* 
     int width = batch;                                   // (changes only through inpass_narrow)
     auto all_done_in = [](const SeqState* q, int n) { for (int b = 0; b < n; ++b) if (q[b].active && !q[b].done) return false; return true; };
     auto all_done = [&]() { return all_done_in(s->seq_host, width); };
-    auto count_steps = [&](int steps) { s->slot_steps += (long long)width * steps; if (L) s->inpass_slot_steps_saved += (long long)(L->width0 - width) * steps; if (s->pass.rules & plan::kRulesPassLogitKernel) s->lr_launches += steps; if (s->pass.rules & plan::kRulesPassPhraseKernel) s->pr_launches += steps; if (s->pass.rules & plan::kRulesPassSetAware) s->rs_launches += steps; };
+    auto count_steps = [&](int steps) { s->count.slot_steps += (long long)width * steps; if (L) s->inpass.slot_steps_saved += (long long)(L->width0 - width) * steps; if (s->pass.rules & plan::kRulesPassLogitKernel) s->rules.lr_launches += steps; if (s->pass.rules & plan::kRulesPassPhraseKernel) s->rules.pr_launches += steps; if (s->pass.rules & plan::kRulesPassSetAware) s->rules.rs_launches += steps; };
     // the last read of the pass: the compact slots, or - after a narrowing - every state by home slot (parked once more)
     auto final_read = [&]() -> int {
         if (L && L->switches > 0) {
-            launch_seq_park(s->seq, s->seq_home, s->slot_home_dev, width, s->B, s->st);
+            launch_seq_park(s->seq, s->inpass.seq_home, s->slots.home_dev, width, s->B, s->st);
             WH_CHECK_LAUNCH();
-            WH_HIP(hipMemcpyAsync(s->seq_host, s->seq_home, sizeof(SeqState) * L->n_home, hipMemcpyDeviceToHost, s->st));
+            WH_HIP(hipMemcpyAsync(s->seq_host, s->inpass.seq_home, sizeof(SeqState) * L->n_home, hipMemcpyDeviceToHost, s->st));
         } else WH_HIP(hipMemcpyAsync(s->seq_host, s->seq, sizeof(SeqState) * width, hipMemcpyDeviceToHost, s->st));
         WH_HIP(hipStreamSynchronize(s->st));
         return WH_OK;
@@ -563,7 +613,7 @@ static int run_token_loop(wh_session* s, int batch, int loop_count, PassLayout* 
         struct Report { bool on; double *l, *w, t0; int n; decltype(now)* clk; ~Report() { if (on) fprintf(stderr, "[wh host] decode loop: %d graph launches, %.2f ms inside hipGraphLaunch, %.2f ms waiting for the device, %.2f ms total\n", n, *l * 1e3, *w * 1e3, ((*clk)() - t0) * 1e3); } } report{dbg_host, &t_launch, &t_wait, t_begin, n_graphs, &now};
         // A pass that may narrow alternates between two snapshot buffers and remembers the layout each snapshot was taken in: the copy behind graph g
         // can be of another layout than the one behind graph g - 1 that the host is looking at.  Otherwise one buffer, as ever.
-        SeqState* const snap[2] = {s->seq_host, L ? s->seq_snap : s->seq_host};
+        SeqState* const snap[2] = {s->seq_host, L ? s->inpass.seq_snap : s->seq_host};
         std::vector<int32_t> snap_home[2];
         int snap_width[2] = {width, width};
         for (int g = 0; g < n_graphs; ++g) {
@@ -654,11 +704,11 @@ static int decode_text_impl(wh_session* s, const wh_special_tokens* st, const Pa
     const int V = s->m->dims.n_vocab;
     // per-audio rule sets (wh_session_define_rule_set; NO REFERENCE BEHAVIOUR): a pass is set-aware iff a live slot names a set other than 0; a
     // live slot that names an undefined set fails the call before anything is launched
-    const int32_t* const set_of_slot = s->rs_slot.empty() ? nullptr : s->rs_slot.data();
+    const int32_t* const set_of_slot = s->rules.rs_slot.empty() ? nullptr : s->rules.rs_slot.data();
     const bool set_aware = plan::rule_sets_pass_aware(set_of_slot, active, batch);
     if (set_aware) {
         unsigned defined = 0;
-        for (int k = 1; k < plan::kMaxRuleSets; ++k) if (s->rs_sets[k].defined) defined |= 1u << k;
+        for (int k = 1; k < plan::kMaxRuleSets; ++k) if (s->rules.rs_sets[k].defined) defined |= 1u << k;
         const int bad = plan::rule_sets_first_undefined(set_of_slot, active, batch, defined);
         if (bad >= 0) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text: slot %d is assigned rule set %d, which is not defined (wh_session_define_rule_set)", bad, set_of_slot[bad]);
     }
@@ -711,30 +761,29 @@ static int decode_text_impl(wh_session* s, const wh_special_tokens* st, const Pa
         q.rng_lane = seq_pack_lane(hb, c);      // the slot's random stream (T > 0) does not depend on where the slot is decoded; its option class (0 unless mixed)
     };
     // Compacted pass (wh_session_set_fallback_compaction 1): a sparse `active` mask decodes at the width compact_pass_plan gives; compact
-    // slot i stands for home slot slot_home_host[i] - its encoder output / cross K / V rows, its alignment rows, its language token,
+    // slot i stands for home slot slots.h.home[i] - its encoder output / cross K / V rows, its alignment rows, its language token,
     // temperature and random stream.  Steps 3 and 6 are in home-slot terms again.
     int n_live = 0;
     for (int b = 0; b < batch; ++b) n_live += is_live(b);
     plan::CompactPassPlan cp{false, batch, s->use_xabs ? s->xabs.spw : 1};
-    if (s->fallback_compaction == 1 && active) cp = plan::compact_pass_plan(n_live, batch, s->B, s->use_xabs ? s->xabs.spw : 1);
+    if (s->slots.fallback_compaction == 1 && active) cp = plan::compact_pass_plan(n_live, batch, s->B, s->use_xabs ? s->xabs.spw : 1);
     whi::PassGuard guard{s};      // (every exit: the next caller of decode_buffers sees a plain pass)
     const int width = cp.compact ? cp.width : batch;
     if (cp.compact) {
-        if (!s->slot_home_dev) WH_HIP(s->mem.alloc(&s->slot_home_dev, (size_t)s->B, false));
-        if (!s->slot_home_host) WH_HIP(s->mem.alloc_pinned(&s->slot_home_host, 2 * (size_t)s->B));
-        int32_t* home = s->slot_home_host, *live = s->slot_home_host + s->B;
+        if ((r = slot_table_ensure(s))) return r;
+        int32_t *const home = s->slots.h.home, *const live = s->slots.h.live;
         if (plan::compact_slot_map(active, batch, width, home, live) != n_live) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text: the compacted pass does not hold its live slots");
         for (int i = 0; i < width; ++i) init_slot(s->seq_host[i], home[i], live[i] != 0);
-        WH_HIP(hipMemcpyAsync(s->slot_home_dev, home, sizeof(int32_t) * width, hipMemcpyHostToDevice, s->st));
+        WH_HIP(hipMemcpyAsync(s->slots.home_dev, home, sizeof(int32_t) * width, hipMemcpyHostToDevice, s->st));
         s->pass.mapped = true; s->pass.spw = cp.spw;
-        s->compacted_passes += 1;
+        s->count.compacted_passes += 1;
     } else {
         for (int b = 0; b < batch; ++b) init_slot(s->seq_host[b], b, is_live(b));
     }
     // ---- 3. arm the modes.  No-speech detection (wh_session_set_no_speech_detection; NO REFERENCE BEHAVIOUR): every decoded slot's scoring position -
     // the first <|startoftranscript|> of its prompt - and, in mode 2, its stop threshold from the options its result is finalised under, by home slot
     std::vector<const wh_decoding_options*> ns_opts;
-    if (s->no_speech_detection != plan::kNoSpeechOff) {
+    if (s->ns.mode != plan::kNoSpeechOff) {
         std::vector<int> pos((size_t)batch);
         std::vector<float> stop((size_t)batch);
         ns_opts.assign((size_t)batch, nullptr);
@@ -742,25 +791,25 @@ static int decode_text_impl(wh_session* s, const wh_special_tokens* st, const Pa
             const bool act = is_live(b);
             const wh_decoding_options* fo = options_of(b);
             pos[b] = act ? plan::nospeech_position(prompt_of(b).tokens, prompt_of(b).n, st->start_of_transcript_token) : -1;
-            stop[b] = plan::nospeech_stop_threshold(s->no_speech_detection, fo);
+            stop[b] = plan::nospeech_stop_threshold(s->ns.mode, fo);
             if (act) ns_opts[b] = fo;
         }
         r = whi::nospeech_arm(s, batch, pos.data(), stop.data(), st->no_speech_token, 1);
         if (r) return r;
     }
-    s->decode_passes += 1;
-    if (mix) { s->pass.mixed = own_prompts ? 2 : 1; s->mix_mixed_passes += 1; s->mix_max_classes = std::max<long long>(s->mix_max_classes, n_cls); }
+    s->count.decode_passes += 1;
+    if (mix) { s->pass.mixed = own_prompts ? 2 : 1; s->mix.mixed_passes += 1; s->mix.max_classes = std::max<long long>(s->mix.max_classes, n_cls); }
     if (own_prompts) {      // wh_session_slot_prompt_stats: the pass, its distinct prompts, the prompt positions its slots step through
         std::vector<std::vector<int32_t>> seen;
         for (int b = 0; b < batch; ++b) {
             if (!is_live(b)) continue;
             const Prompt p = prompt_of(b);
             seen.emplace_back(p.tokens, p.tokens + p.n);
-            s->sp_positions += p.n;
+            s->mix.sp_positions += p.n;
         }
         std::sort(seen.begin(), seen.end());
-        s->sp_passes += 1;
-        s->sp_max_distinct = std::max<long long>(s->sp_max_distinct, (long long)(std::unique(seen.begin(), seen.end()) - seen.begin()));
+        s->mix.sp_passes += 1;
+        s->mix.sp_max_distinct = std::max<long long>(s->mix.sp_max_distinct, (long long)(std::unique(seen.begin(), seen.end()) - seen.begin()));
     }
     // fused greedy path: every active slot samples at T = 0 (filters + softmax statistics in the logits epilogue)
     s->fused_greedy = true;
@@ -775,21 +824,21 @@ static int decode_text_impl(wh_session* s, const wh_special_tokens* st, const Pa
         s->fused_greedy = false;
         r = rules_write_special_begin(s, st->special_token_begin, set_aware);
         if (r) return r;
-        if (rules & plan::kRulesPassLogitKernel) s->lr_passes += 1;
-        if (rules & plan::kRulesPassPhraseKernel) s->pr_passes += 1;
+        if (rules & plan::kRulesPassLogitKernel) s->rules.lr_passes += 1;
+        if (rules & plan::kRulesPassPhraseKernel) s->rules.pr_passes += 1;
     }
     if (set_aware) {      // the slot table goes up by home slot, so compacted, narrowed and mixed passes need nothing else
-        memset(s->rs_host, 0, sizeof(int32_t) * (size_t)s->B);
-        for (int b = 0; b < batch; ++b) if (is_live(b)) s->rs_host[b] = set_of_slot[b];
-        WH_HIP(hipMemcpyAsync(s->rs_dev + whi::kRsOffSlots, s->rs_host, sizeof(int32_t) * (size_t)s->B, hipMemcpyHostToDevice, s->st));
-        s->rs_args.own_logit = (rules & plan::kRulesPassOwnLogit) ? s->lr_dev : nullptr;
-        s->rs_args.own_phrase = (rules & plan::kRulesPassOwnPhrase) ? s->pr_dev : nullptr;
-        s->rs_passes += 1;
+        memset(s->rules.rs_h.slots, 0, sizeof(int32_t) * (size_t)s->B);
+        for (int b = 0; b < batch; ++b) if (is_live(b)) s->rules.rs_h.slots[b] = set_of_slot[b];
+        WH_HIP(hipMemcpyAsync(s->rules.rs.slots, s->rules.rs_h.slots, sizeof(int32_t) * (size_t)s->B, hipMemcpyHostToDevice, s->st));
+        s->rules.rs_args.own_logit = (rules & plan::kRulesPassOwnLogit) ? s->rules.lr_dev : nullptr;
+        s->rules.rs_args.own_phrase = (rules & plan::kRulesPassOwnPhrase) ? s->rules.pr_dev : nullptr;
+        s->rules.rs_passes += 1;
     }
     s->pass.rules = rules;
     // ---- token alternatives (wh_session_set_token_alternatives; NO REFERENCE BEHAVIOUR): the unfused sampler's recording instantiation.  The rows of
     // the home slots this pass decodes start from "nothing recorded"; a fallback rung so overwrites only the windows it decodes again
-    if (s->token_alternatives > 0) {
+    if (s->alt.n > 0) {
         s->fused_greedy = false;
         r = whi::alternatives_arm(s, batch, active);
         if (r) return r;
@@ -803,12 +852,13 @@ static int decode_text_impl(wh_session* s, const wh_special_tokens* st, const Pa
     s->special_begin_in_progress = st->special_token_begin;
     // in-pass compaction (wh_session_set_inpass_compaction 1): the pass may narrow between step graphs as its slots finish (run_token_loop)
     PassLayout lay;
-    if (s->inpass_compaction == 1) {
-        if (!s->seq_snap) WH_HIP(s->mem.alloc_pinned(&s->seq_snap, (size_t)s->B));
+    if (s->inpass.mode == 1) {
+        if ((r = inpass_ensure(s, false))) return r;
+        lay.ring = mem::StageRing((size_t)plan::kInpassMaxSwitches, inpass_region_words(s));
         lay.width = lay.width0 = width; lay.n_home = batch;
         lay.home.resize((size_t)width); lay.live.resize((size_t)width);
         for (int i = 0; i < width; ++i) {
-            lay.home[i] = cp.compact ? s->slot_home_host[i] : i;
+            lay.home[i] = cp.compact ? s->slots.h.home[i] : i;
             lay.live[i] = s->seq_host[i].active;
         }
     }
@@ -817,20 +867,20 @@ static int decode_text_impl(wh_session* s, const wh_special_tokens* st, const Pa
     auto home_layout = [&]() -> int {
         std::vector<SeqState> fin(s->seq_host, s->seq_host + (lay.switches == 0 ? n_live : 0));
         for (int b = 0; b < batch; ++b) if (lay.switches == 0 || !is_live(b)) init_slot(s->seq_host[b], b, false);
-        for (size_t i = 0; i < fin.size(); ++i) s->seq_host[s->slot_home_host[i]] = fin[i];
+        for (size_t i = 0; i < fin.size(); ++i) s->seq_host[s->slots.h.home[i]] = fin[i];
         s->pass.mapped = false; s->pass.owner = false;
         WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * batch, hipMemcpyHostToDevice, s->st));
         WH_HIP(hipStreamSynchronize(s->st));
         return WH_OK;
     };
-    r = run_token_loop(s, width, std::max(loop_count, 0), s->inpass_compaction == 1 ? &lay : nullptr);
+    r = run_token_loop(s, width, std::max(loop_count, 0), s->inpass.mode == 1 ? &lay : nullptr);
     if (r && lay.switches > 0) {
         // an error (a cancel, a failed capture) behind a switch: the device states lie in the compact layout with the finished windows parked.  Put
         // them back by home slot as far as the device still answers, so that a step-API or wh_measure_kernels call that follows sees every slot in
         // its place; the error of the loop is the one reported.
         const std::string msg = wh_last_error();
-        launch_seq_park(s->seq, s->seq_home, s->slot_home_dev, lay.width, s->B, s->st);
-        if (hipMemcpyAsync(s->seq_host, s->seq_home, sizeof(SeqState) * batch, hipMemcpyDeviceToHost, s->st) == hipSuccess &&
+        launch_seq_park(s->seq, s->inpass.seq_home, s->slots.home_dev, lay.width, s->B, s->st);
+        if (hipMemcpyAsync(s->seq_host, s->inpass.seq_home, sizeof(SeqState) * batch, hipMemcpyDeviceToHost, s->st) == hipSuccess &&
             hipStreamSynchronize(s->st) == hipSuccess) (void)home_layout();
         set_error(r, "%s", msg.c_str());
     }
@@ -848,8 +898,8 @@ static int decode_text_impl(wh_session* s, const wh_special_tokens* st, const Pa
             const SeqState& q = s->seq_host[b];
             int start = 0;
             for (int i = 0; i < q.n_tokens; ++i) if (q.tokens[i] == st->start_of_transcript_token) { start = i; break; }
-            s->alt_start[(size_t)b] = start; s->alt_count[(size_t)b] = out[b].n_tokens; s->alt_nrec[(size_t)b] = s->pass.alt;
-            for (int i = q.prompt_len; i < q.n_tokens; ++i) s->alt_positions += s->alt_ids_host[((size_t)b * plan::kAltPositions + i) * plan::kMaxAlternatives] != plan::kAltNoId;
+            s->alt.start[(size_t)b] = start; s->alt.count[(size_t)b] = out[b].n_tokens; s->alt.nrec[(size_t)b] = s->pass.alt;
+            for (int i = q.prompt_len; i < q.n_tokens; ++i) s->alt.positions += s->alt.ids_host[((size_t)b * plan::kAltPositions + i) * plan::kMaxAlternatives] != plan::kAltNoId;
         }
     }
     return WH_OK;
@@ -1020,15 +1070,15 @@ extern "C" int wh_detect_language(wh_session* s, int batch, const wh_special_tok
 extern "C" int wh_session_set_no_speech_detection(wh_session* s, int mode) {
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_no_speech_detection: null session");
     if (!plan::nospeech_mode_valid(mode)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_no_speech_detection: mode %d (0 = off, 1 = on, 2 = on + stop)", mode);
-    s->no_speech_detection = mode;
+    s->ns.mode = mode;
     return WH_OK;
 }
-extern "C" int wh_session_no_speech_detection(const wh_session* s) { return s ? s->no_speech_detection : -1; }
+extern "C" int wh_session_no_speech_detection(const wh_session* s) { return s ? s->ns.mode : -1; }
 extern "C" int wh_session_no_speech_stats(const wh_session* s, int64_t* rows_scored, int64_t* windows_over_threshold, int64_t* windows_stopped) {
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_no_speech_stats: null session");
-    if (rows_scored) *rows_scored = s->ns_rows_scored;
-    if (windows_over_threshold) *windows_over_threshold = s->ns_windows_over;
-    if (windows_stopped) *windows_stopped = s->ns_windows_stopped;
+    whi::store_stat(rows_scored, s->ns.rows_scored);
+    whi::store_stat(windows_over_threshold, s->ns.windows_over);
+    whi::store_stat(windows_stopped, s->ns.windows_stopped);
     return WH_OK;
 }
 
@@ -1039,11 +1089,10 @@ extern "C" int wh_no_speech_probs(wh_session* s, int batch, const wh_special_tok
     if (!st || !probs_out) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_no_speech_probs: null argument");
     const wh_dims& dm = s->m->dims;
     const size_t kv_rows = (size_t)dm.n_text_layer * s->B * dm.n_text_head, row_bytes = sizeof(f16) * kHeadDim, pitch = row_bytes * kMaxTok;
-    if (!s->ns_seq_keep) WH_HIP(s->mem.alloc(&s->ns_seq_keep, (size_t)s->B, false));
-    if (!s->ns_kv_keep) WH_HIP(s->mem.alloc(&s->ns_kv_keep, 2 * kv_rows * kHeadDim, false));
-    WH_HIP(hipMemcpyAsync(s->ns_seq_keep, s->seq, sizeof(SeqState) * batch, hipMemcpyDeviceToDevice, s->st));
-    WH_HIP(hipMemcpy2DAsync(s->ns_kv_keep, row_bytes, s->self_k, pitch, row_bytes, kv_rows, hipMemcpyDeviceToDevice, s->st));
-    WH_HIP(hipMemcpy2DAsync(s->ns_kv_keep + kv_rows * kHeadDim, row_bytes, s->self_v, pitch, row_bytes, kv_rows, hipMemcpyDeviceToDevice, s->st));
+    if (int r = whi::nospeech_ensure(s, true)) return r;
+    WH_HIP(hipMemcpyAsync(s->ns.seq_keep, s->seq, sizeof(SeqState) * batch, hipMemcpyDeviceToDevice, s->st));
+    WH_HIP(hipMemcpy2DAsync(s->ns.kv_keep, row_bytes, s->self_k, pitch, row_bytes, kv_rows, hipMemcpyDeviceToDevice, s->st));
+    WH_HIP(hipMemcpy2DAsync(s->ns.kv_keep + kv_rows * kHeadDim, row_bytes, s->self_v, pitch, row_bytes, kv_rows, hipMemcpyDeviceToDevice, s->st));
     whi::PassGuard guard{s};
     const std::vector<int> pos((size_t)batch, 0);
     int r = whi::nospeech_arm(s, batch, pos.data(), nullptr, st->no_speech_token, 1);
@@ -1058,11 +1107,11 @@ extern "C" int wh_no_speech_probs(wh_session* s, int batch, const wh_special_tok
     s->align_enabled = false;
     DecodeBuffers db = whi::decode_buffers(s, batch, 0);
     s->align_enabled = keep;
-    launch_decoder_step(db, nullptr, nullptr, false, s->st, &s->ns_args);
+    launch_decoder_step(db, nullptr, nullptr, false, s->st, &s->ns.args);
     WH_CHECK_LAUNCH();
-    WH_HIP(hipMemcpyAsync(s->seq, s->ns_seq_keep, sizeof(SeqState) * batch, hipMemcpyDeviceToDevice, s->st));
-    WH_HIP(hipMemcpy2DAsync(s->self_k, pitch, s->ns_kv_keep, row_bytes, row_bytes, kv_rows, hipMemcpyDeviceToDevice, s->st));
-    WH_HIP(hipMemcpy2DAsync(s->self_v, pitch, s->ns_kv_keep + kv_rows * kHeadDim, row_bytes, row_bytes, kv_rows, hipMemcpyDeviceToDevice, s->st));
+    WH_HIP(hipMemcpyAsync(s->seq, s->ns.seq_keep, sizeof(SeqState) * batch, hipMemcpyDeviceToDevice, s->st));
+    WH_HIP(hipMemcpy2DAsync(s->self_k, pitch, s->ns.kv_keep, row_bytes, row_bytes, kv_rows, hipMemcpyDeviceToDevice, s->st));
+    WH_HIP(hipMemcpy2DAsync(s->self_v, pitch, s->ns.kv_keep + kv_rows * kHeadDim, row_bytes, row_bytes, kv_rows, hipMemcpyDeviceToDevice, s->st));
     r = whi::nospeech_collect(s, batch, nullptr);
     if (r) return r;
     for (int b = 0; b < batch; ++b) probs_out[b] = whi::nospeech_prob(s, b);
@@ -1076,43 +1125,39 @@ extern "C" int wh_no_speech_probs(wh_session* s, int batch, const wh_special_tok
 extern "C" int wh_session_set_token_alternatives(wh_session* s, int n) {
     if (!s || !s->m) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_token_alternatives: null session");
     if (!plan::alternatives_n_valid(n)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_token_alternatives: n %d (0 = off, 1 .. %d)", n, plan::kMaxAlternatives);
-    if (n > 0 && !s->alt_ids) {
+    if (n > 0 && !s->alt.ids) {
         if (hipSetDevice(s->m->device) != hipSuccess) return set_error(WH_ERR_HIP, "wh_session_set_token_alternatives: hipSetDevice(%d) failed", s->m->device);
         WH_TRY
-        s->alt_start.assign((size_t)s->B, 0); s->alt_count.assign((size_t)s->B, 0); s->alt_nrec.assign((size_t)s->B, 0);
+        s->alt.start.assign((size_t)s->B, 0); s->alt.count.assign((size_t)s->B, 0); s->alt.nrec.assign((size_t)s->B, 0);
         WH_CATCH("wh_session_set_token_alternatives")
-        if (!s->alt_f32) WH_HIP(s->mem.alloc(&s->alt_f32, plan::alternatives_f32_floats(s->B), false));
-        if (!s->alt_ids_host) WH_HIP(s->mem.alloc_pinned(&s->alt_ids_host, plan::alternatives_id_words(s->B)));
-        if (!s->alt_f32_host) WH_HIP(s->mem.alloc_pinned(&s->alt_f32_host, plan::alternatives_f32_floats(s->B)));
-        WH_HIP(s->mem.alloc(&s->alt_ids, plan::alternatives_id_words(s->B), false));      // (last: alt_ids set = everything is there; every pass resets the rows it decodes)
+        if (int r = whi::alternatives_ensure(s)) return r;
     }
-    s->token_alternatives = n;
+    s->alt.n = n;
     return WH_OK;
 }
-extern "C" int wh_session_token_alternatives(const wh_session* s) { return s ? s->token_alternatives : -1; }
+extern "C" int wh_session_token_alternatives(const wh_session* s) { return s ? s->alt.n : -1; }
 extern "C" int wh_session_token_alternatives_stats(const wh_session* s, int64_t* passes, int64_t* positions_recorded, int64_t* d2h_bytes) {
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_token_alternatives_stats: null session");
-    if (passes) *passes = s->alt_passes;
-    if (positions_recorded) *positions_recorded = s->alt_positions;
-    if (d2h_bytes) *d2h_bytes = s->alt_d2h_bytes;
+    whi::store_stat(passes, s->alt.passes);
+    whi::store_stat(positions_recorded, s->alt.positions);
+    whi::store_stat(d2h_bytes, s->alt.d2h_bytes);
     return WH_OK;
 }
 // The rows of home slot `slot` as the last pass that decoded it left them, aligned with that pass's wh_decoding_result.tokens: n_tokens rows of n_alt pairs
 extern "C" int wh_decode_alternatives(const wh_session* s, int slot, int32_t* ids_out, float* logprobs_out, float* entropy_out, int* n_alt_out, int* n_tokens_out) {
     if (!s || !s->m) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_alternatives: null session");
     if (slot < 0 || slot >= s->B) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_alternatives: slot %d out of range [0,%d)", slot, s->B);
-    const int n = s->alt_ids ? s->alt_nrec[(size_t)slot] : 0, count = n > 0 ? s->alt_count[(size_t)slot] : 0;
+    const int n = s->alt.ids ? s->alt.nrec[(size_t)slot] : 0, count = n > 0 ? s->alt.count[(size_t)slot] : 0;
     if (n_alt_out) *n_alt_out = n;
     if (n_tokens_out) *n_tokens_out = count;
-    const size_t ent_off = plan::alternatives_lp_floats(s->B);
     for (int i = 0; i < count; ++i) {
-        const int row = plan::alternatives_result_row(s->alt_start[(size_t)slot], i);
+        const int row = plan::alternatives_result_row(s->alt.start[(size_t)slot], i);
         for (int k = 0; k < n; ++k) {
             const long long o = row >= 0 ? plan::alternatives_pair_offset(slot, row, k, s->B) : -1;
-            if (ids_out) ids_out[(size_t)i * n + k] = o >= 0 ? s->alt_ids_host[o] : plan::kAltNoId;
-            if (logprobs_out) logprobs_out[(size_t)i * n + k] = o >= 0 ? s->alt_f32_host[o] : -INFINITY;
+            if (ids_out) ids_out[(size_t)i * n + k] = o >= 0 ? s->alt.ids_host[o] : plan::kAltNoId;
+            if (logprobs_out) logprobs_out[(size_t)i * n + k] = o >= 0 ? s->alt.h.lp[o] : -INFINITY;
         }
-        if (entropy_out) entropy_out[i] = row >= 0 ? s->alt_f32_host[ent_off + (size_t)plan::alternatives_entropy_offset(slot, row, s->B)] : 0.0f;
+        if (entropy_out) entropy_out[i] = row >= 0 ? s->alt.h.entropy[plan::alternatives_entropy_offset(slot, row, s->B)] : 0.0f;
     }
     return WH_OK;
 }
@@ -1124,9 +1169,9 @@ extern "C" int wh_debug_token_alternatives_apply(wh_session* s, const float* row
     CHECK_SESSION(s); CHECK_BATCH(s, n_rows);
     if (!rows || !ids_out || !logprobs_out || !entropy_out) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_token_alternatives_apply: null argument");
     if (n < 1 || !plan::alternatives_n_valid(n)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_token_alternatives_apply: n %d (1 .. %d)", n, plan::kMaxAlternatives);
-    const int keep = s->token_alternatives;
+    const int keep = s->alt.n;
     int r = wh_session_set_token_alternatives(s, n);      // (allocates on first use)
-    s->token_alternatives = keep;
+    s->alt.n = keep;
     if (r) return r;
     const int V = s->m->dims.n_vocab;
     wh_decoding_options o;
@@ -1143,23 +1188,22 @@ extern "C" int wh_debug_token_alternatives_apply(wh_session* s, const float* row
     whi::PassGuard guard{s};
     r = whi::alternatives_arm(s, n_rows, nullptr);
     if (r) return r;
-    s->alt_passes -= 1;                                   // (not a decode pass)
+    s->alt.passes -= 1;                                   // (not a decode pass)
     WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * n_rows, hipMemcpyHostToDevice, s->st));
     WH_HIP(hipMemcpyAsync(s->logits, rows, sizeof(float) * (size_t)n_rows * V, hipMemcpyHostToDevice, s->st));
-    launch_alternatives_only(s->cfg_dev, s->seq, s->logits, n_rows, n, s->B, s->alt_ids, s->alt_f32, s->st);
+    launch_alternatives_only(s->cfg_dev, s->seq, s->logits, n_rows, n, s->B, s->alt.ids, s->alt.f32, s->st);
     WH_CHECK_LAUNCH();
-    const long long bytes_before = s->alt_d2h_bytes;
+    const long long bytes_before = s->alt.d2h_bytes;
     r = whi::alternatives_collect(s, n_rows, nullptr);
-    s->alt_d2h_bytes = bytes_before;
+    s->alt.d2h_bytes = bytes_before;
     if (r) return r;
-    const size_t ent_off = plan::alternatives_lp_floats(s->B);
     for (int i = 0; i < n_rows; ++i) {
         for (int k = 0; k < n; ++k) {
             const long long po = plan::alternatives_pair_offset(i, 0, k, s->B);
-            ids_out[(size_t)i * n + k] = s->alt_ids_host[po]; logprobs_out[(size_t)i * n + k] = s->alt_f32_host[po];
+            ids_out[(size_t)i * n + k] = s->alt.ids_host[po]; logprobs_out[(size_t)i * n + k] = s->alt.h.lp[po];
         }
-        entropy_out[i] = s->alt_f32_host[ent_off + (size_t)plan::alternatives_entropy_offset(i, 0, s->B)];
-        s->alt_nrec[(size_t)i] = 0;                       // (what wh_decode_alternatives knew about these slots is gone)
+        entropy_out[i] = s->alt.h.entropy[plan::alternatives_entropy_offset(i, 0, s->B)];
+        s->alt.nrec[(size_t)i] = 0;                       // (what wh_decode_alternatives knew about these slots is gone)
     }
     return WH_OK;
 }
@@ -1233,6 +1277,12 @@ static int debug_rows_fetch(wh_session* s, float* rows, int n_rows) {
 // ------------------------------------------------------------------------------------------------ device logit rules
 // NO REFERENCE BEHAVIOUR: the semantics are transformers' `SequenceBiasLogitsProcessor` (single-token sequences), `RepetitionPenaltyLogitsProcessor` and
 // `NoRepeatNGramLogitsProcessor`, applied in the order `generate` applies them (logit_rules_plan.h, logit_rules.hip).
+// the only place that allocates the logit rules' memory (the first setter that installs rules)
+static int logit_rules_ensure(wh_session* s) {
+    if (!s->rules.lr_dev) WH_HIP(s->mem.alloc(&s->rules.lr_dev, (size_t)plan::kLogitRulesWords, false));      // (not zeroed: a memset on the null stream could land behind the setter's copy, which writes every word)
+    if (!s->rules.lr_host) WH_HIP(s->mem.alloc_pinned(&s->rules.lr_host, (size_t)plan::kLogitRulesWords));
+    return WH_OK;
+}
 extern "C" void wh_logit_rules_default(wh_logit_rules* r) {
     if (!r) return;
     memset(r, 0, sizeof(*r));
@@ -1246,17 +1296,16 @@ extern "C" int wh_session_set_logit_rules(wh_session* s, const wh_logit_rules* r
     if (const char* why = plan::logit_rules_invalid(rules, s->m->dims.n_vocab)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_logit_rules: %s", why);
     if (plan::logit_rules_neutral(rules)) {
         s->logit_rules_on = false;
-        keep_logit_half(s->rs_sets[0], nullptr);
+        keep_logit_half(s->rules.rs_sets[0], nullptr);
         return WH_OK;
     }
     if (hipSetDevice(s->m->device) != hipSuccess) return set_error(WH_ERR_HIP, "wh_session_set_logit_rules: hipSetDevice(%d) failed", s->m->device);
-    if (!s->lr_dev) WH_HIP(s->mem.alloc(&s->lr_dev, (size_t)plan::kLogitRulesWords, false));      // (not zeroed: a memset on the null stream could land behind the copy below, which writes every word)
-    if (!s->lr_host) WH_HIP(s->mem.alloc_pinned(&s->lr_host, (size_t)plan::kLogitRulesWords));
+    if (int r = logit_rules_ensure(s)) return r;
     WH_HIP(hipStreamSynchronize(s->st));
-    plan::logit_table_build(rules, s->m->dims.n_vocab, s->lr_host);      // (word 2, the history's cut-off: every pass writes its own special_token_begin)
-    WH_HIP(hipMemcpyAsync(s->lr_dev, s->lr_host, sizeof(int32_t) * plan::kLogitRulesWords, hipMemcpyHostToDevice, s->st));
+    plan::logit_table_build(rules, s->m->dims.n_vocab, s->rules.lr_host);      // (word 2, the history's cut-off: every pass writes its own special_token_begin)
+    WH_HIP(hipMemcpyAsync(s->rules.lr_dev, s->rules.lr_host, sizeof(int32_t) * plan::kLogitRulesWords, hipMemcpyHostToDevice, s->st));
     WH_HIP(hipStreamSynchronize(s->st));
-    keep_logit_half(s->rs_sets[0], rules);
+    keep_logit_half(s->rules.rs_sets[0], rules);
     s->logit_rules_on = true;
     return WH_OK;
     WH_CATCH("wh_session_set_logit_rules")
@@ -1264,13 +1313,13 @@ extern "C" int wh_session_set_logit_rules(wh_session* s, const wh_logit_rules* r
 // The session's copy; its arrays stay valid until the next setter call.  The neutral set when the mode is off
 extern "C" int wh_session_logit_rules(const wh_session* s, wh_logit_rules* out) {
     if (!s || !out) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_logit_rules: null argument");
-    *out = s->rs_sets[0].lr;
+    *out = s->rules.rs_sets[0].lr;
     return WH_OK;
 }
 extern "C" int wh_session_logit_rules_stats(const wh_session* s, int64_t* passes, int64_t* launches) {
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_logit_rules_stats: null session");
-    if (passes) *passes = s->lr_passes;
-    if (launches) *launches = s->lr_launches;
+    whi::store_stat(passes, s->rules.lr_passes);
+    whi::store_stat(launches, s->rules.lr_launches);
     return WH_OK;
 }
 
@@ -1280,7 +1329,7 @@ extern "C" int wh_debug_logit_rules_apply(wh_session* s, float* rows_inout, int 
     if (!rows_inout || !tokens || !n_tokens || !prompt_lens) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_logit_rules_apply: null argument");
     if (!s->logit_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_logit_rules_apply: the session has no logit rules set (wh_session_set_logit_rules)");
     if (int r = debug_rows_stage(s, "wh_debug_logit_rules_apply", rows_inout, n_rows, tokens, n_tokens, prompt_lens, nullptr, false)) return r;
-    launch_logit_rules(s->lr_dev, s->seq, s->logits, n_rows, s->m->dims.n_vocab, s->st);
+    launch_logit_rules(s->rules.lr_dev, s->seq, s->logits, n_rows, s->m->dims.n_vocab, s->st);
     return debug_rows_fetch(s, rows_inout, n_rows);
 }
 
@@ -1289,27 +1338,33 @@ extern "C" int wh_debug_logit_rules_apply(wh_session* s, float* rows_inout, int 
 // the special case bias = -inf), on input_ids = [sentinel] + H (phrase_rules_plan.h, phrase_rules.hip).
 // The setter builds the table in the pinned staging and uploads it stream-ordered on the session's stream: the stream is drained first, so no copy in flight
 // reads a half-written staging; every later launch of the stream reads the new table through the address its graphs captured.
+// the only place that allocates the phrase rules' memory (the first setter that installs rules); the match counter starts at 0, stream-ordered
+static int phrase_rules_ensure(wh_session* s) {
+    wh_session::Rules& f = s->rules;
+    if (!f.pr_dev) WH_HIP(s->mem.alloc(&f.pr_dev, (size_t)plan::kPhraseTableWords, false));      // (not zeroed: the setter's copy writes every word)
+    if (!f.pr_host) WH_HIP(s->mem.alloc_pinned(&f.pr_host, (size_t)plan::kPhraseTableWords));
+    if (!f.pr_args.matches) {
+        WH_HIP(s->mem.alloc(&f.pr_args.matches, (size_t)1, false));
+        WH_HIP(hipMemsetAsync(f.pr_args.matches, 0, sizeof(unsigned long long), s->st));
+    }
+    f.pr_args.table = f.pr_dev;
+    return WH_OK;
+}
 extern "C" int wh_session_set_phrase_rules(wh_session* s, const wh_phrase_rules* rules) {
     if (!s || !s->m) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_phrase_rules: null session");
     WH_TRY
     if (const char* why = plan::phrase_rules_invalid(rules, s->m->dims.n_vocab)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_phrase_rules: %s", why);
     if (plan::phrase_rules_neutral(rules)) {
         s->phrase_rules_on = false;
-        keep_phrase_half(s->rs_sets[0], nullptr);
+        keep_phrase_half(s->rules.rs_sets[0], nullptr);
         return WH_OK;
     }
     if (hipSetDevice(s->m->device) != hipSuccess) return set_error(WH_ERR_HIP, "wh_session_set_phrase_rules: hipSetDevice(%d) failed", s->m->device);
-    if (!s->pr_dev) WH_HIP(s->mem.alloc(&s->pr_dev, (size_t)plan::kPhraseTableWords, false));      // (not zeroed: the copy below writes every word)
-    if (!s->pr_host) WH_HIP(s->mem.alloc_pinned(&s->pr_host, (size_t)plan::kPhraseTableWords));
-    if (!s->pr_args.matches) {
-        WH_HIP(s->mem.alloc(&s->pr_args.matches, (size_t)1, false));
-        WH_HIP(hipMemsetAsync(s->pr_args.matches, 0, sizeof(unsigned long long), s->st));
-    }
-    s->pr_args.table = s->pr_dev;
+    if (int r = phrase_rules_ensure(s)) return r;
     WH_HIP(hipStreamSynchronize(s->st));
-    plan::phrase_table_build(*rules, s->m->dims.n_vocab, s->pr_host);
-    WH_HIP(hipMemcpyAsync(s->pr_dev, s->pr_host, sizeof(int32_t) * plan::kPhraseTableWords, hipMemcpyHostToDevice, s->st));
-    keep_phrase_half(s->rs_sets[0], rules);
+    plan::phrase_table_build(*rules, s->m->dims.n_vocab, s->rules.pr_host);
+    WH_HIP(hipMemcpyAsync(s->rules.pr_dev, s->rules.pr_host, sizeof(int32_t) * plan::kPhraseTableWords, hipMemcpyHostToDevice, s->st));
+    keep_phrase_half(s->rules.rs_sets[0], rules);
     s->phrase_rules_on = true;
     return WH_OK;
     WH_CATCH("wh_session_set_phrase_rules")
@@ -1317,15 +1372,15 @@ extern "C" int wh_session_set_phrase_rules(wh_session* s, const wh_phrase_rules*
 // The session's copy; its arrays stay valid until the next setter call.  The empty set when the mode is off
 extern "C" int wh_session_phrase_rules(const wh_session* s, wh_phrase_rules* out) {
     if (!s || !out) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_phrase_rules: null argument");
-    *out = s->rs_sets[0].pr;
+    *out = s->rules.rs_sets[0].pr;
     return WH_OK;
 }
 // matches: the device counter (read_match_counters)
 extern "C" int wh_session_phrase_rules_stats(const wh_session* s, int64_t* passes, int64_t* launches, int64_t* matches) {
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_phrase_rules_stats: null session");
-    if (passes) *passes = s->pr_passes;
-    if (launches) *launches = s->pr_launches;
-    return matches ? read_match_counters(s, "wh_session_phrase_rules_stats", s->pr_args.matches, 1, matches) : WH_OK;
+    whi::store_stat(passes, s->rules.pr_passes);
+    whi::store_stat(launches, s->rules.pr_launches);
+    return matches ? read_match_counters(s, "wh_session_phrase_rules_stats", s->rules.pr_args.matches, 1, matches) : WH_OK;
 }
 
 // Development aid: phrase_rules_kernel alone over caller-supplied rows and histories (debug_rows_stage).  live (or null): row i is a live slot iff live[i] != 0 -
@@ -1337,7 +1392,7 @@ extern "C" int wh_debug_phrase_rules_apply(wh_session* s, float* rows_inout, int
     if (!rows_inout || !tokens || !n_tokens || !prompt_lens) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_phrase_rules_apply: null argument");
     if (!s->phrase_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_phrase_rules_apply: the session has no phrase rules set (wh_session_set_phrase_rules)");
     if (int r = debug_rows_stage(s, "wh_debug_phrase_rules_apply", rows_inout, n_rows, tokens, n_tokens, prompt_lens, live, false)) return r;
-    launch_phrase_rules(s->pr_args, s->seq, s->logits, n_rows, s->m->dims.n_vocab, s->st);
+    launch_phrase_rules(s->rules.pr_args, s->seq, s->logits, n_rows, s->m->dims.n_vocab, s->st);
     return debug_rows_fetch(s, rows_inout, n_rows);
 }
 
@@ -1346,18 +1401,24 @@ extern "C" int wh_debug_phrase_rules_apply(wh_session* s, float* rows_inout, int
 // wh_logit_rules plus one wh_phrase_rules with the limits, validation and arithmetic of the two setters above; every home slot names the set it decodes under.
 // The first definition allocates everything in one piece and fills it with neutral sets; a definition rewrites its set in place, stream-ordered on the
 // session's stream behind a drained stream, so captured step graphs stay valid.
+// (the only place that allocates the rule sets' memory)
 static int rule_sets_ensure(wh_session* s) {
-    if (s->rs_dev) return WH_OK;
-    const size_t words = (size_t)whi::kRsOffBank + (size_t)plan::kRuleSetBankWords;
-    if (!s->rs_host) WH_HIP(s->mem.alloc_pinned(&s->rs_host, (size_t)kMaxSessionSlots + (size_t)plan::kRuleSetStride));
+    wh_session::Rules& f = s->rules;
+    if (f.rs_dev) return WH_OK;
+    mem::RuleSetsHostView host{};
+    mem::RuleSetsDevView d{};
+    const size_t bytes = mem::pack_rule_sets_dev(nullptr, plan::kMaxRuleSets, kMaxSessionSlots, (size_t)plan::kRuleSetBankWords, d);
+    if (!f.rs_host) WH_HIP(s->mem.alloc_pinned(&f.rs_host, mem::pack_rule_sets_host(nullptr, kMaxSessionSlots, plan::kRuleSetStride, host) / sizeof(int32_t)));
+    mem::pack_rule_sets_host(f.rs_host, kMaxSessionSlots, plan::kRuleSetStride, f.rs_h);
     int32_t* dev = nullptr;
-    WH_HIP(s->mem.alloc(&dev, words, false));      // (filled on the session's stream: counters 0, every slot under set 0, every set neutral - p = 1.0f)
-    WH_HIP(hipMemsetAsync(dev, 0, sizeof(int32_t) * words, s->st));
+    WH_HIP(s->mem.alloc(&dev, bytes / sizeof(int32_t), false));      // (filled on the session's stream: counters 0, every slot under set 0, every set neutral - p = 1.0f)
+    mem::pack_rule_sets_dev(dev, plan::kMaxRuleSets, kMaxSessionSlots, (size_t)plan::kRuleSetBankWords, d);
+    WH_HIP(hipMemsetAsync(dev, 0, bytes, s->st));
     for (int k = 1; k < plan::kMaxRuleSets; ++k)
-        WH_HIP(hipMemsetD32Async(dev + whi::kRsOffBank + plan::rule_set_offset(k) + plan::kRuleSetOffLogit, 0x3f800000, 1, s->st));
+        WH_HIP(hipMemsetD32Async(d.bank + plan::rule_set_offset(k) + plan::kRuleSetOffLogit, 0x3f800000, 1, s->st));
     WH_HIP(hipStreamSynchronize(s->st));
-    s->rs_dev = dev;
-    s->rs_args = RuleSetsArgs{dev + whi::kRsOffBank, dev + whi::kRsOffSlots, nullptr, nullptr, reinterpret_cast<unsigned long long*>(dev), s->B};
+    f.rs_dev = dev; f.rs = d;
+    f.rs_args = RuleSetsArgs{d.bank, d.slots, nullptr, nullptr, d.matches, s->B};
     return WH_OK;
 }
 extern "C" int wh_session_define_rule_set(wh_session* s, int index, const wh_logit_rules* logit_rules, const wh_phrase_rules* phrase_rules) {
@@ -1367,14 +1428,14 @@ extern "C" int wh_session_define_rule_set(wh_session* s, int index, const wh_log
     if (const char* why = plan::logit_rules_invalid(logit_rules, s->m->dims.n_vocab)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_define_rule_set: %s", why);
     if (const char* why = plan::phrase_rules_invalid(phrase_rules, s->m->dims.n_vocab)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_define_rule_set: %s", why);
     const bool lr_off = plan::logit_rules_neutral(logit_rules), pr_off = plan::phrase_rules_neutral(phrase_rules);
-    wh_session::RuleSetCopy& c = s->rs_sets[index];
+    wh_session::RuleSetCopy& c = s->rules.rs_sets[index];
     if (lr_off && pr_off && !c.defined) return WH_OK;      // (undefining what is not defined: nothing to write, nothing to allocate)
     if (hipSetDevice(s->m->device) != hipSuccess) return set_error(WH_ERR_HIP, "wh_session_define_rule_set: hipSetDevice(%d) failed", s->m->device);
     if (int r = rule_sets_ensure(s)) return r;
     WH_HIP(hipStreamSynchronize(s->st));                    // nothing in flight reads the staging the host writes next
-    int32_t* stage = s->rs_host + kMaxSessionSlots;
+    int32_t* const stage = s->rules.rs_h.stage;
     plan::rule_set_build(logit_rules, phrase_rules, s->m->dims.n_vocab, stage);
-    WH_HIP(hipMemcpyAsync(s->rs_dev + whi::kRsOffBank + plan::rule_set_offset(index), stage, sizeof(int32_t) * (size_t)plan::kRuleSetStride, hipMemcpyHostToDevice, s->st));
+    WH_HIP(hipMemcpyAsync(s->rules.rs.bank + plan::rule_set_offset(index), stage, sizeof(int32_t) * (size_t)plan::kRuleSetStride, hipMemcpyHostToDevice, s->st));
     WH_HIP(hipStreamSynchronize(s->st));
     c.defined = !(lr_off && pr_off);
     c.special_begin = s->m->dims.n_vocab;
@@ -1387,8 +1448,8 @@ extern "C" int wh_session_define_rule_set(wh_session* s, int index, const wh_log
 extern "C" int wh_session_rule_set(const wh_session* s, int index, wh_logit_rules* logit_rules_out, wh_phrase_rules* phrase_rules_out) {
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_rule_set: null session");
     if (!plan::rule_set_index_valid(index)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_rule_set: index %d (0 .. %d)", index, plan::kMaxRuleSets - 1);
-    if (logit_rules_out) *logit_rules_out = s->rs_sets[index].lr;
-    if (phrase_rules_out) *phrase_rules_out = s->rs_sets[index].pr;
+    if (logit_rules_out) *logit_rules_out = s->rules.rs_sets[index].lr;
+    if (phrase_rules_out) *phrase_rules_out = s->rules.rs_sets[index].pr;
     return WH_OK;
 }
 // Step-level assignment by home slot: slots n .. max_batch - 1 and a null table name set 0.  Any index of 0 .. 15 is accepted here; a decode call whose
@@ -1396,28 +1457,28 @@ extern "C" int wh_session_rule_set(const wh_session* s, int index, wh_logit_rule
 extern "C" int wh_session_set_slot_rule_sets(wh_session* s, const int32_t* set_of_slot, int n) {
     if (!s || !s->m) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_slot_rule_sets: null session");
     WH_TRY
-    if (!set_of_slot) { s->rs_slot.clear(); return WH_OK; }
+    if (!set_of_slot) { s->rules.rs_slot.clear(); return WH_OK; }
     if (n < 0 || n > s->B) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_slot_rule_sets: %d slots (0 .. %d)", n, s->B);
     for (int b = 0; b < n; ++b)
         if (!plan::rule_set_index_valid(set_of_slot[b])) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_slot_rule_sets: slot %d names rule set %d (0 .. %d)", b, set_of_slot[b], plan::kMaxRuleSets - 1);
     std::vector<int32_t> next((size_t)s->B, 0);
     for (int b = 0; b < n; ++b) next[(size_t)b] = set_of_slot[b];
-    s->rs_slot.swap(next);
+    s->rules.rs_slot.swap(next);
     return WH_OK;
     WH_CATCH("wh_session_set_slot_rule_sets")
 }
 extern "C" int wh_session_slot_rule_sets(const wh_session* s, int32_t* set_of_slot_out, int n) {
     if (!s || !set_of_slot_out) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_slot_rule_sets: null argument");
     if (n < 0 || n > s->B) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_slot_rule_sets: %d slots (0 .. %d)", n, s->B);
-    for (int b = 0; b < n; ++b) set_of_slot_out[b] = b < (int)s->rs_slot.size() ? s->rs_slot[(size_t)b] : 0;
+    for (int b = 0; b < n; ++b) set_of_slot_out[b] = b < (int)s->rules.rs_slot.size() ? s->rules.rs_slot[(size_t)b] : 0;
     return WH_OK;
 }
 // matches [WH_MAX_RULE_SETS]: the device counters (read_match_counters)
 extern "C" int wh_session_rule_set_stats(const wh_session* s, int64_t* passes, int64_t* launches, int64_t* matches) {
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_rule_set_stats: null session");
-    if (passes) *passes = s->rs_passes;
-    if (launches) *launches = s->rs_launches;
-    return matches ? read_match_counters(s, "wh_session_rule_set_stats", s->rs_dev, plan::kMaxRuleSets, matches) : WH_OK;
+    whi::store_stat(passes, s->rules.rs_passes);
+    whi::store_stat(launches, s->rules.rs_launches);
+    return matches ? read_match_counters(s, "wh_session_rule_set_stats", s->rules.rs.matches, plan::kMaxRuleSets, matches) : WH_OK;
 }
 
 // Development aid: rule_sets_kernel alone over caller-supplied rows and histories (debug_rows_stage), in the shape of wh_debug_phrase_rules_apply.  set_of_row[i]:
@@ -1428,14 +1489,14 @@ extern "C" int wh_debug_rule_sets_apply(wh_session* s, float* rows_inout, int n_
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_rule_sets_apply: null session");
     CHECK_SESSION(s); CHECK_BATCH(s, n_rows);
     if (!rows_inout || !tokens || !n_tokens || !prompt_lens || !set_of_row) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_rule_sets_apply: null argument");
-    if (!s->rs_dev) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_rule_sets_apply: the session has no rule set defined (wh_session_define_rule_set)");
+    if (!s->rules.rs_dev) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_rule_sets_apply: the session has no rule set defined (wh_session_define_rule_set)");
     if (int r = debug_rows_stage(s, "wh_debug_rule_sets_apply", rows_inout, n_rows, tokens, n_tokens, prompt_lens, live, true)) return r;
-    memset(s->rs_host, 0, sizeof(int32_t) * (size_t)s->B);
-    for (int i = 0; i < n_rows; ++i) s->rs_host[i] = set_of_row[i];
-    WH_HIP(hipMemcpyAsync(s->rs_dev + whi::kRsOffSlots, s->rs_host, sizeof(int32_t) * (size_t)s->B, hipMemcpyHostToDevice, s->st));
-    RuleSetsArgs a = s->rs_args;
-    a.own_logit = s->logit_rules_on ? s->lr_dev : nullptr;
-    a.own_phrase = s->phrase_rules_on ? s->pr_dev : nullptr;
+    memset(s->rules.rs_h.slots, 0, sizeof(int32_t) * (size_t)s->B);
+    for (int i = 0; i < n_rows; ++i) s->rules.rs_h.slots[i] = set_of_row[i];
+    WH_HIP(hipMemcpyAsync(s->rules.rs.slots, s->rules.rs_h.slots, sizeof(int32_t) * (size_t)s->B, hipMemcpyHostToDevice, s->st));
+    RuleSetsArgs a = s->rules.rs_args;
+    a.own_logit = s->logit_rules_on ? s->rules.lr_dev : nullptr;
+    a.own_phrase = s->phrase_rules_on ? s->rules.pr_dev : nullptr;
     launch_rule_sets(a, s->seq, s->logits, n_rows, s->m->dims.n_vocab, s->st);
     return debug_rows_fetch(s, rows_inout, n_rows);
 }
@@ -1447,15 +1508,18 @@ extern "C" int wh_debug_rule_sets_apply(wh_session* s, float* rows_inout, int n_
 // its own next token.  T = 0 only: tokens, log-probabilities and stop reasons are the ordinary loop's.  Eager launches, one synchronisation per round.
 constexpr int kSpecStageRegions = 2 * kMaxTok;      // a round confirms at least one position (<= 223 rounds) and stages at most two descriptor sets
 
+// descriptors of one region of the staging: an audio takes at least two slots
+static size_t spec_region_descs(const wh_session* s) { return std::max<size_t>((size_t)s->B / 2, 1); }
+// the only place that allocates the speculative pass's memory; its virtual slots read the slot table
 static int spec_ensure(wh_session* s) {
-    const size_t B = (size_t)s->B, half = std::max<size_t>(B / 2, 1);
-    if (!s->spec_master) WH_HIP(s->mem.alloc(&s->spec_master, B, true));
-    if (!s->spec_owner) WH_HIP(s->mem.alloc(&s->spec_owner, B * kMaxTok, false));
-    if (!s->slot_home_dev) WH_HIP(s->mem.alloc(&s->slot_home_dev, B, false));
-    if (!s->spec_desc) WH_HIP(s->mem.alloc_pinned(&s->spec_desc, (size_t)kSpecStageRegions * half));
-    if (!s->spec_desc_dev) WH_HIP(s->mem.alloc(&s->spec_desc_dev, (size_t)kSpecStageRegions * half, false));
-    if (!s->spec_io) WH_HIP(s->mem.alloc(&s->spec_io, half, true));
-    if (!s->spec_io_host) WH_HIP(s->mem.alloc_pinned(&s->spec_io_host, half));
+    const size_t B = (size_t)s->B, half = spec_region_descs(s);
+    if (int r = slot_table_ensure(s)) return r;
+    if (!s->spec.master) WH_HIP(s->mem.alloc(&s->spec.master, B, true));
+    if (!s->spec.owner) WH_HIP(s->mem.alloc(&s->spec.owner, B * kMaxTok, false));
+    if (!s->spec.desc) WH_HIP(s->mem.alloc_pinned(&s->spec.desc, (size_t)kSpecStageRegions * half));
+    if (!s->spec.desc_dev) WH_HIP(s->mem.alloc(&s->spec.desc_dev, (size_t)kSpecStageRegions * half, false));
+    if (!s->spec.io) WH_HIP(s->mem.alloc(&s->spec.io, half, true));
+    if (!s->spec.io_host) WH_HIP(s->mem.alloc_pinned(&s->spec.io_host, half));
     return WH_OK;
 }
 
@@ -1514,7 +1578,7 @@ struct DraftProposer : SpecProposer {
         *dev_src = draft->seq;
         if (steps <= 0) return WH_OK;
         WH_HIP(hipMemcpyAsync(stage2_dev, stage2, sizeof(SpecDesc) * (size_t)n_audio, hipMemcpyHostToDevice, s->st));
-        launch_spec_arm_draft(draft->cfg_dev, s->spec_master, stage2_dev, draft->seq, n_audio, s->st);
+        launch_spec_arm_draft(draft->cfg_dev, s->spec.master, stage2_dev, draft->seq, n_audio, s->st);
         for (int i = 0; i < steps; ++i) {
             int top = 0;
             for (int a = 0; a < n_audio; ++a) if (stage2[a].n) top = std::max(top, resume[(size_t)a] + i);
@@ -1522,7 +1586,7 @@ struct DraftProposer : SpecProposer {
             launch_decoder_step(db, draft->cfg_dev, draft->suppress_dev, true, s->st);
         }
         WH_CHECK_LAUNCH();
-        draft->slot_steps += (long long)n_audio * steps;
+        draft->count.slot_steps += (long long)n_audio * steps;
         for (int a = 0; a < n_audio; ++a) if (stage2[a].n) resume[(size_t)a] += steps;   // (an upper bound: confirmed() brings it down to what the target kept)
         return WH_OK;
     }
@@ -1551,46 +1615,44 @@ static int spec_pass_impl(wh_session* s, int n_audio, int K, const wh_decoding_o
         whi::seq_init_prompt(q, prompt, n_prompt, lang_pos, lang_pos >= 0 ? language_tokens[a] : -1, V);
         q.active = 1; q.temperature = 0.0f; q.rng_lane = a;
     }
-    WH_HIP(hipMemcpyAsync(s->spec_master, s->seq_host, sizeof(SeqState) * (size_t)n_audio, hipMemcpyHostToDevice, s->st));
-    launch_rules_init(s->cfg_dev, s->spec_master, n_audio, s->st);
+    WH_HIP(hipMemcpyAsync(s->spec.master, s->seq_host, sizeof(SeqState) * (size_t)n_audio, hipMemcpyHostToDevice, s->st));
+    launch_rules_init(s->cfg_dev, s->spec.master, n_audio, s->st);
     WH_CHECK_LAUNCH();
-    s->decode_passes += 1; s->spec_passes += 1;
-    const size_t half = std::max<size_t>((size_t)B / 2, 1);
+    s->count.decode_passes += 1; s->spec.passes += 1;
+    mem::StageRing ring((size_t)kSpecStageRegions, spec_region_descs(s));
     const plan::CompactPassPlan cp = plan::compact_pass_plan(width, B, B, s->use_xabs ? s->xabs.spw : 1);      // slots per absorbed-attention workgroup of the rung that holds `width` slots (results do not depend on it)
     const int spw = cp.compact ? cp.spw : (s->use_xabs ? s->xabs.spw : 1);
     std::vector<int> p0((size_t)n_audio, 0), p0_next((size_t)n_audio, 0);
     std::vector<char> live((size_t)n_audio, limit > 0 ? 1 : 0);
     int n_live = limit > 0 ? n_audio : 0;
-    size_t region = 0;
     while (n_live > 0) {
         if (cancelled(s)) { hipStreamSynchronize(s->st); return set_error(WH_ERR_CANCELLED, "speculative pass: cancelled through the session's cancel flag"); }
-        if (region + 2 > (size_t)kSpecStageRegions) return set_error(WH_ERR_DECODING_FAILED, "speculative pass: more rounds than positions");
-        // this round's own regions of the pinned staging (uploaded stream-ordered): the stream has consumed nothing the host writes here
-        SpecDesc* d = s->spec_desc + region * half;
-        SpecDesc* d_dev = s->spec_desc_dev + region * half;
+        // this round's own two regions of the pinned staging (uploaded stream-ordered): the stream has consumed nothing the host writes here
+        const size_t at = ring.take(2);
+        if (at == mem::StageRing::kFull) return set_error(WH_ERR_DECODING_FAILED, "speculative pass: more rounds than positions");
+        SpecDesc *const d = s->spec.desc + at, *const d_dev = s->spec.desc_dev + at;
         const SeqState* dev_src = nullptr;
-        r = pr.propose(s, n_audio, K, n_prompt, limit, p0.data(), live.data(), d, d + half, d_dev + half, &dev_src);
+        r = pr.propose(s, n_audio, K, n_prompt, limit, p0.data(), live.data(), d, d + ring.stride(), d_dev + ring.stride(), &dev_src);
         if (r) return r;
-        region += 2;
         int top = 0;                                          // the largest position the round can run
         for (int a = 0; a < n_audio; ++a) if (live[a]) top = std::max(top, p0[a] + pr.upper_k(a, p0[a], K, n_prompt, limit, st->end_token));
         WH_HIP(hipMemcpyAsync(d_dev, d, sizeof(SpecDesc) * (size_t)n_audio, hipMemcpyHostToDevice, s->st));
-        launch_spec_arm(s->cfg_dev, s->spec_master, d_dev, dev_src, s->seq, s->spec_owner, s->slot_home_dev, s->spec_io, n_audio, K, s->st);
+        launch_spec_arm(s->cfg_dev, s->spec.master, d_dev, dev_src, s->seq, s->spec.owner, s->slots.home_dev, s->spec.io, n_audio, K, s->st);
         s->pass.mapped = true; s->pass.spw = spw;
         DecodeBuffers db = whi::decode_buffers(s, width, std::min(top, kMaxTok - 1));
-        db.self_owner = s->spec_owner; db.owner_slots = B;
+        db.self_owner = s->spec.owner; db.owner_slots = B;
         launch_decoder_step(db, s->cfg_dev, s->suppress_dev, true, s->st);
-        launch_spec_accept(s->spec_master, s->seq, s->spec_io, n_audio, K, s->st);
+        launch_spec_accept(s->spec.master, s->seq, s->spec.io, n_audio, K, s->st);
         WH_CHECK_LAUNCH();
-        WH_HIP(hipMemcpyAsync(s->spec_io_host, s->spec_io, sizeof(SpecRound) * (size_t)n_audio, hipMemcpyDeviceToHost, s->st));
+        WH_HIP(hipMemcpyAsync(s->spec.io_host, s->spec.io, sizeof(SpecRound) * (size_t)n_audio, hipMemcpyDeviceToHost, s->st));
         WH_HIP(hipStreamSynchronize(s->st));
-        s->spec_rounds += 1; s->slot_steps += width;
+        s->spec.rounds += 1; s->count.slot_steps += width;
         for (int a = 0; a < n_audio; ++a) {
             p0_next[(size_t)a] = p0[(size_t)a];
             if (!live[a]) continue;
-            const SpecRound& o = s->spec_io_host[a];
+            const SpecRound& o = s->spec.io_host[a];
             if (o.k < 0 || o.k > K || o.accepted < 0 || o.accepted > o.k) return set_error(WH_ERR_DECODING_FAILED, "speculative pass: audio %d: the round reports %d of %d positions", a, o.accepted, o.k);
-            s->spec_positions += 1 + o.k; s->spec_accepted += o.accepted;
+            s->spec.positions += 1 + o.k; s->spec.accepted += o.accepted;
             p0[(size_t)a] = p0_next[(size_t)a] = p0[(size_t)a] + o.accepted + (o.done ? 0 : 1);      // a finished audio stays at the last position it ran
             if (o.done) { live[a] = 0; --n_live; }
             else if (o.token_index != p0[(size_t)a]) return set_error(WH_ERR_DECODING_FAILED, "speculative pass: audio %d stands at position %d, the host at %d", a, o.token_index, p0[(size_t)a]);
@@ -1607,8 +1669,8 @@ static int spec_pass_impl(wh_session* s, int n_audio, int K, const wh_decoding_o
         }
     }
     WH_HIP(hipMemsetAsync(s->seq, 0, sizeof(SeqState) * (size_t)width, s->st));
-    WH_HIP(hipMemcpyAsync(s->seq, s->spec_master, sizeof(SeqState) * (size_t)n_audio, hipMemcpyDeviceToDevice, s->st));
-    WH_HIP(hipMemcpyAsync(s->seq_host, s->spec_master, sizeof(SeqState) * (size_t)n_audio, hipMemcpyDeviceToHost, s->st));
+    WH_HIP(hipMemcpyAsync(s->seq, s->spec.master, sizeof(SeqState) * (size_t)n_audio, hipMemcpyDeviceToDevice, s->st));
+    WH_HIP(hipMemcpyAsync(s->seq_host, s->spec.master, sizeof(SeqState) * (size_t)n_audio, hipMemcpyDeviceToHost, s->st));
     WH_HIP(hipStreamSynchronize(s->st));
     for (int a = 0; a < n_audio; ++a) whi::finalize_decoding_result(s->seq_host[a], opt, st, s->seq_host[a].temperature, &out[a]);
     return WH_OK;
@@ -1648,7 +1710,7 @@ extern "C" int wh_decode_text_guided(wh_session* s, int n_audio, int K, const wh
     CHECK_SESSION(s);
     if (int r = spec_check_args(who, n_audio, K, opt, st, prompt, n_prompt, out, s->B)) return r;
     if (int r = spec_check_tokens(who, n_audio, prompt, n_prompt, proposals, n_proposals, s->m->dims.n_vocab)) return r;
-    if (s->token_alternatives > 0) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: the session records token alternatives (wh_session_set_token_alternatives), which the speculative pass does not do", who);
+    if (s->alt.n > 0) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: the session records token alternatives (wh_session_set_token_alternatives), which the speculative pass does not do", who);
     if (s->logit_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: the session has logit rules set (wh_session_set_logit_rules), which the speculative pass does not run", who);
     if (s->phrase_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: the session has phrase rules set (wh_session_set_phrase_rules), which the speculative pass does not run", who);
     if (whi::rule_sets_assigned(s, n_audio)) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: a slot of the call is assigned a rule set (wh_session_set_slot_rule_sets), which the speculative pass does not run", who);
@@ -1678,7 +1740,7 @@ extern "C" int wh_decode_text_speculative(wh_session* s, wh_session* draft, int 
     if (int r = spec_check_args(who, n_audio, K, opt, st, prompt, n_prompt, out, s->B)) return r;
     if (int r = spec_check_tokens(who, n_audio, prompt, n_prompt, nullptr, nullptr, s->m->dims.n_vocab)) return r;
     if (int r = spec_check_draft(who, s, draft, n_audio)) return r;
-    if (s->token_alternatives > 0) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: the session records token alternatives (wh_session_set_token_alternatives), which the speculative pass does not do", who);
+    if (s->alt.n > 0) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: the session records token alternatives (wh_session_set_token_alternatives), which the speculative pass does not do", who);
     if (s->logit_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: the session has logit rules set (wh_session_set_logit_rules), which the speculative pass does not run", who);
     if (s->phrase_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: the session has phrase rules set (wh_session_set_phrase_rules), which the speculative pass does not run", who);
     if (whi::rule_sets_assigned(s, n_audio)) return set_error(WH_ERR_INVALID_ARGUMENT, "%s: a slot of the call is assigned a rule set (wh_session_set_slot_rule_sets), which the speculative pass does not run", who);
@@ -1697,20 +1759,20 @@ extern "C" int wh_decode_text_speculative(wh_session* s, wh_session* draft, int 
 
 extern "C" int wh_session_set_draft(wh_session* s, wh_session* draft, int K) {
     if (!s || !s->m) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_draft: null session");
-    if (!draft) { s->draft = nullptr; s->draft_k = 0; return WH_OK; }
+    if (!draft) { s->spec.draft = nullptr; s->spec.draft_k = 0; return WH_OK; }
     if (!plan::spec_k_valid(K)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_draft: K = %d (1 .. %d)", K, plan::kSpecMaxK);
     if (int r = spec_check_draft("wh_session_set_draft", s, draft, 1)) return r;
-    s->draft = draft; s->draft_k = K;
+    s->spec.draft = draft; s->spec.draft_k = K;
     return WH_OK;
 }
-extern "C" int wh_session_draft_k(const wh_session* s) { return s ? (s->draft ? s->draft_k : 0) : -1; }
+extern "C" int wh_session_draft_k(const wh_session* s) { return s ? (s->spec.draft ? s->spec.draft_k : 0) : -1; }
 
 extern "C" int wh_session_speculative_stats(const wh_session* s, int64_t* passes, int64_t* rounds, int64_t* positions_run, int64_t* tokens_accepted) {
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_speculative_stats: null session");
-    if (passes) *passes = s->spec_passes;
-    if (rounds) *rounds = s->spec_rounds;
-    if (positions_run) *positions_run = s->spec_positions;
-    if (tokens_accepted) *tokens_accepted = s->spec_accepted;
+    whi::store_stat(passes, s->spec.passes);
+    whi::store_stat(rounds, s->spec.rounds);
+    whi::store_stat(positions_run, s->spec.positions);
+    whi::store_stat(tokens_accepted, s->spec.accepted);
     return WH_OK;
 }
 
@@ -1886,7 +1948,7 @@ static int round_gather(wh_session* s, std::vector<AudioJob>& jobs, Round& R, co
         if (r == WH_ERR_HIP) return r;                                 // the device is gone: every audio of the group fails
         if (r) { j.status = r; j.error = wh_last_error(); j.finished = true; continue; }
         R.slot_job.push_back((int)ji);
-        if (carried) s->sp_windows_carried += 1;
+        if (carried) s->mix.sp_windows_carried += 1;
         if (s->hooks.window_preprocess) {                              // TranscribeTask.windowPreprocess (:130)
             const float* win = j.pcm + j.cur_seek;
             std::vector<float> copy;
@@ -1909,8 +1971,8 @@ static int round_encode(wh_session* s, const std::vector<AudioJob>& jobs, Round&
     const int nb = R.nb();
     // per-audio rule sets: the round's windows name their audios' sets by home slot (decode_text_impl uploads the table for every set-aware pass)
     if (G.job_sets) {
-        s->rs_slot.assign((size_t)s->B, 0);
-        for (int b = 0; b < nb; ++b) s->rs_slot[(size_t)b] = jobs[R.slot_job[b]].rule_set;
+        s->rules.rs_slot.assign((size_t)s->B, 0);
+        for (int b = 0; b < nb; ++b) s->rules.rs_slot[(size_t)b] = jobs[R.slot_job[b]].rule_set;
     }
     R.t1 = now_s();
     int r = wh_log_mel_spectrogram(s, nb); if (r) return r;
@@ -1980,12 +2042,12 @@ static int round_decode(wh_session* s, std::vector<AudioJob>& jobs, Round& R, co
         plan::PassRouteInput in;
         in.beam_size = opt->beam_size; in.temperature = G.temps[ti]; in.rung = (int)ti;
         for (int b = 0; b < nb; ++b) in.all_active &= active[b] != 0;
-        in.slot_prompts = G.slot_prompts; in.mixed = G.mixed; in.draft = s->draft != nullptr;
-        in.no_speech = s->no_speech_detection != plan::kNoSpeechOff; in.alternatives = s->token_alternatives != 0;
+        in.slot_prompts = G.slot_prompts; in.mixed = G.mixed; in.draft = s->spec.draft != nullptr;
+        in.no_speech = s->ns.mode != plan::kNoSpeechOff; in.alternatives = s->alt.n != 0;
         in.logit_rules = s->logit_rules_on; in.phrase_rules = s->phrase_rules_on; in.job_sets = G.job_sets;
-        in.progress_cb = s->progress_cb != nullptr; in.spec_fits = plan::spec_fits(nb, s->draft_k, s->B);
+        in.progress_cb = s->progress_cb != nullptr; in.spec_fits = plan::spec_fits(nb, s->spec.draft_k, s->B);
         plan::PassRoute route = plan::pass_route(in);
-        if (route == plan::PassRoute::Speculative && spec_check_draft("wh_transcribe", s, s->draft, nb)) route = plan::PassRoute::Plain;
+        if (route == plan::PassRoute::Speculative && spec_check_draft("wh_transcribe", s, s->spec.draft, nb)) route = plan::PassRoute::Plain;
         switch (route) {
         case plan::PassRoute::Beam: {      // (no reference behaviour, wh_decode_text_beam): the T = 0 pass expands every window into beam_size slots
             r = wh_decode_text_beam(s, nb, G.beam, opt->beam_patience, opt, st, R.prompt_p[0], R.prompt_n[0], langs, R.tmp.data());
@@ -2012,12 +2074,12 @@ static int round_decode(wh_session* s, std::vector<AudioJob>& jobs, Round& R, co
         case plan::PassRoute::Speculative: {
             // first rung with a draft attached (wh_session_set_draft) and room for the rings: the speculative pass (results are the ordinary pass's).  The
             // draft gets the same windows through its own log-mel and encoder
-            wh_session* const dr = s->draft;
+            wh_session* const dr = s->spec.draft;
             for (int b = 0; b < nb; ++b) { r = job_set_window(dr, b, jobs[R.slot_job[b]]); if (r) return r; }
             r = wh_log_mel_spectrogram(dr, nb); if (r) return r;
             r = wh_encode_features(dr, nb); if (r) return r;
             r = wh_prepare_decoder_inputs(dr, nb); if (r) return r;
-            r = wh_decode_text_speculative(s, dr, nb, s->draft_k, opt, st, R.prompt_p[0], R.prompt_n[0], langs, R.tmp.data());
+            r = wh_decode_text_speculative(s, dr, nb, s->spec.draft_k, opt, st, R.prompt_p[0], R.prompt_n[0], langs, R.tmp.data());
             if (r) return r;
             break;
         }
@@ -2044,7 +2106,7 @@ static int round_decode(wh_session* s, std::vector<AudioJob>& jobs, Round& R, co
 // Word alignment on the device (wh_session_set_word_alignment 1): every slot's DTW row count is known from its result alone
 // (wh_word_alignment_rows), so the whole batch is aligned by one head-mean launch, one DTW launch and one copy of the paths
 static int round_align(wh_session* s, const std::vector<AudioJob>& jobs, Round& R, const GroupPlan& G) {
-    R.device_paths = s->word_alignment == 1 && G.opt->word_timestamps && s->align;
+    R.device_paths = s->walign.mode == 1 && G.opt->word_timestamps && s->align;
     if (!R.device_paths) return WH_OK;
     const int nb = R.nb();
     std::vector<int32_t> rows(nb);
@@ -2085,7 +2147,7 @@ static int round_window(wh_session* s, std::vector<AudioJob>& jobs, Round& R, co
     j.seek = seek;
     const bool had_segments = tr->timings.total_decoding_windows > windows_before;      // (`guard let currentSegments`, :239-242)
     // token alternatives: the rows of the rung whose result is kept (its pass was the last to decode home slot b), sliced by the segments just cut
-    if (s->token_alternatives > 0 && had_segments) {
+    if (s->alt.n > 0 && had_segments) {
         int n_alt = 0, n_rows = 0;
         std::vector<int32_t> aid((size_t)WH_MAX_RESULT_TOKENS * plan::kMaxAlternatives);
         std::vector<float> alp((size_t)WH_MAX_RESULT_TOKENS * plan::kMaxAlternatives), aen((size_t)WH_MAX_RESULT_TOKENS);
@@ -2104,7 +2166,7 @@ static int round_window(wh_session* s, std::vector<AudioJob>& jobs, Round& R, co
         const int n_seg = had_segments ? (int)tr->segments.size() - seg_before : 0;
         const int tok0 = n_seg > 0 ? tr->segments[(size_t)seg_before].token_offset : 0;
         const int tok1 = n_seg > 0 ? tr->segments.back().token_offset + tr->segments.back().n_tokens : 0;
-        if (plan::carry_after_window(j.carry, n_seg, tr->tokens.data() + tok0, tok1 - tok0, res.temperature, s->previous_text_reset, st->special_token_begin)) s->sp_resets += 1;
+        if (plan::carry_after_window(j.carry, n_seg, tr->tokens.data() + tok0, tok1 - tok0, res.temperature, s->mix.previous_text_reset, st->special_token_begin)) s->mix.sp_resets += 1;
     }
     if (had_segments) j.windows += 1;
     tr->timings.audio_processing += (R.t1 - R.t0) / nb; tr->timings.logmels += (R.t2 - R.t1) / nb; tr->timings.encoding += (R.t3 - R.t2) / nb;
@@ -2124,12 +2186,12 @@ static int round_window(wh_session* s, std::vector<AudioJob>& jobs, Round& R, co
 // The group-level checks and the ladder are here; a round's work is in its stages: round_gather, round_encode, round_decode, round_align, round_window.
 static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_decoding_options* opt, const wh_special_tokens* st,
                            const std::vector<const wh_decoding_options*>* classes = nullptr, bool slot_prompts = false) {
-    if (s->previous_text == plan::kPreviousTextOn && opt->beam_size > 1)
+    if (s->mix.previous_text == plan::kPreviousTextOn && opt->beam_size > 1)
         return set_error(WH_ERR_INVALID_ARGUMENT, "beam_size > 1 cannot be combined with previous-text conditioning (wh_session_set_previous_text)");
     const std::vector<const wh_decoding_options*> one_class{opt};
     GroupPlan G;
     G.opt = opt; G.st = st; G.mixed = classes != nullptr; G.classes = G.mixed ? classes : &one_class;
-    G.carrying = plan::carrying(s->previous_text, opt->use_prefill_prompt);
+    G.carrying = plan::carrying(s->mix.previous_text, opt->use_prefill_prompt);
     G.slot_prompts = plan::slot_prompts_route(slot_prompts, G.mixed, G.carrying);
     G.multilingual = wh_is_model_multilingual(s->m) != 0;
     G.detect = plan::detects_language(opt->detect_language, opt->use_prefill_prompt);
@@ -2142,12 +2204,12 @@ static int transcribe_jobs(wh_session* s, std::vector<AudioJob>& jobs, const wh_
     // beam search (no reference behaviour, wh_decode_text_beam): the T = 0 pass expands every window into beam_size slots
     const int beam = G.beam = opt->beam_size > 1 ? opt->beam_size : 1;
     if (beam > 1 && opt->word_timestamps) return set_error(WH_ERR_INVALID_ARGUMENT, "beam_size > 1 cannot be combined with word_timestamps");
-    if (beam > 1 && s->token_alternatives > 0) return set_error(WH_ERR_INVALID_ARGUMENT, "beam_size > 1 cannot be combined with token alternatives (wh_session_set_token_alternatives)");
+    if (beam > 1 && s->alt.n > 0) return set_error(WH_ERR_INVALID_ARGUMENT, "beam_size > 1 cannot be combined with token alternatives (wh_session_set_token_alternatives)");
     if (beam > 1 && s->logit_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "beam_size > 1 cannot be combined with the session's logit rules (wh_session_set_logit_rules)");
     if (beam > 1 && s->phrase_rules_on) return set_error(WH_ERR_INVALID_ARGUMENT, "beam_size > 1 cannot be combined with the session's phrase rules (wh_session_set_phrase_rules)");
     G.job_sets = false;      // per-audio rule sets: does an audio of this group name a set other than 0?  (the set never splits a group: rule_sets_plan.h)
     for (const auto& j : jobs) G.job_sets |= j.rule_set != 0;
-    s->rs_slot.clear();         // (a group before this one may have carried sets: this one starts with every slot under 0)
+    s->rules.rs_slot.clear();         // (a group before this one may have carried sets: this one starts with every slot under 0)
     if (beam > 1 && G.job_sets) return set_error(WH_ERR_INVALID_ARGUMENT, "beam_size > 1 cannot be combined with a rule set (wh_transcribe_batch_with_rule_sets)");
     if (beam > s->B) return set_error(WH_ERR_INVALID_ARGUMENT, "beam_size %d exceeds the session's %d slots", beam, s->B);
     while (true) {
@@ -2183,8 +2245,8 @@ static int transcribe_items(wh_session* s, const float* const* pcm, const int32_
     wh_decoding_options_default(&dflt);
     // per-audio rule sets (rule_sets: [n_audio] or null = all 0): the call owns the session's slot assignment for its duration and leaves it all 0, so a
     // step-level assignment never reaches a window.  An audio is `ruled` iff it decodes under any rules at all: that bit splits groups, the set index does not
-    struct SlotSetScope { wh_session* s; ~SlotSetScope() { s->rs_slot.clear(); } } slot_set_scope{s};
-    s->rs_slot.clear();
+    struct SlotSetScope { wh_session* s; ~SlotSetScope() { s->rules.rs_slot.clear(); } } slot_set_scope{s};
+    s->rules.rs_slot.clear();
     const bool session_rules_on = s->logit_rules_on || s->phrase_rules_on;
     std::vector<unsigned char> ruled((size_t)n_audio, session_rules_on ? 1 : 0);
     s->item_status.assign((size_t)n_audio, WH_OK);
@@ -2204,7 +2266,7 @@ static int transcribe_items(wh_session* s, const float* const* pcm, const int32_
             continue;
         }
         j.rule_set = rule_sets ? rule_sets[i] : 0;
-        if (j.rule_set != 0 && (!plan::rule_set_banked(j.rule_set) || !s->rs_sets[j.rule_set].defined)) {
+        if (j.rule_set != 0 && (!plan::rule_set_banked(j.rule_set) || !s->rules.rs_sets[j.rule_set].defined)) {
             j.status = set_error(WH_ERR_INVALID_ARGUMENT, "audio %d: rule set %d is not defined (wh_session_define_rule_set: 1 .. %d)", i, j.rule_set, plan::kMaxRuleSets - 1); j.error = wh_last_error();
             continue;
         }
@@ -2216,11 +2278,11 @@ static int transcribe_items(wh_session* s, const float* const* pcm, const int32_
     }
     // option mixing (wh_session_set_option_mixing 1): the groups are the batch keys (option_mix.h option_mix_plan); a group's audios carry their class
     plan::OptionMixPlan mixp;
-    const bool mixing = s->option_mixing == 1;
+    const bool mixing = s->mix.mode == 1;
     if (mixing) {
         std::vector<const wh_decoding_options*> po((size_t)n_audio, nullptr);
         for (int i = 0; i < n_audio; ++i) if (group_of[(size_t)i] >= 0) po[(size_t)i] = all[(size_t)i].opt;
-        mixp = plan::rule_sets_mix_plan(po.data(), rule_sets ? ruled.data() : nullptr, n_audio, kMaxOptionClasses, s->prompt_mixing == 1);
+        mixp = plan::rule_sets_mix_plan(po.data(), rule_sets ? ruled.data() : nullptr, n_audio, kMaxOptionClasses, s->mix.prompt_mixing == 1);
         group_of = mixp.group;
         group_opt.clear();
         for (const auto& cl : mixp.classes) group_opt.push_back(cl[0]);
@@ -2232,8 +2294,8 @@ static int transcribe_items(wh_session* s, const float* const* pcm, const int32_
         std::vector<std::unique_ptr<wh_transcription>> owned;      // the jobs' transcriptions, until they are published into out[]
         for (int i = 0; i < n_audio; ++i) if (group_of[(size_t)i] == (int)g) { owned.emplace_back(new wh_transcription()); jobs.push_back(all[(size_t)i]); jobs.back().tr = owned.back().get(); }
         const bool mix_group = mixing && plan::option_mixable(*group_opt[g]);      // (beam search groups run as without the option)
-        if (mix_group && !hard) s->mix_groups_run += 1;
-        const int r = hard ? hard : transcribe_jobs(s, jobs, group_opt[g], st, mix_group ? &mixp.classes[g] : nullptr, mix_group && s->prompt_mixing == 1);       // after a device error nothing else can run
+        if (mix_group && !hard) s->mix.groups_run += 1;
+        const int r = hard ? hard : transcribe_jobs(s, jobs, group_opt[g], st, mix_group ? &mixp.classes[g] : nullptr, mix_group && s->mix.prompt_mixing == 1);       // after a device error nothing else can run
         const std::string why = r ? wh_last_error() : "";
         if (r == WH_ERR_HIP || r == WH_ERR_CANCELLED) hard = r;
         for (size_t k = 0; k < jobs.size(); ++k) {
@@ -2424,14 +2486,21 @@ extern "C" int wh_transcribe_chunked_device(wh_session* s, wh_device_audio* a, c
 // NO REFERENCE BEHAVIOUR: openai/whisper timing.find_alignment semantics.  The tokens are given, so every position of every audio is a
 // virtual slot of a decoder launch (forced_plan.h): forced_arm_kernel writes the slots' positions, owner rows and home slots, the step kernels run as they
 // are at width = positions of the launch, forced_score_kernel reads the logits rows.  Eager launches, like the beam loop.
+// positions of one call at most: n_audio <= B sequences of <= kMaxTok tokens
+static size_t forced_capacity(const wh_session* s) { return (size_t)s->B * (kMaxTok - 1); }
+// the only place that allocates the forced pass's memory; its virtual slots read the slot table
 static int forced_ensure(wh_session* s) {
-    const size_t cap = (size_t)s->B * (kMaxTok - 1);      // positions of one call at most: n_audio <= B sequences of <= kMaxTok tokens
-    if (!s->forced_owner) WH_HIP(s->mem.alloc(&s->forced_owner, (size_t)s->B * kMaxTok, false));
-    if (!s->slot_home_dev) WH_HIP(s->mem.alloc(&s->slot_home_dev, (size_t)s->B, false));
-    if (!s->forced_desc) WH_HIP(s->mem.alloc_pinned(&s->forced_desc, cap));
-    if (!s->forced_desc_dev) WH_HIP(s->mem.alloc(&s->forced_desc_dev, cap, false));
-    if (!s->forced_out) WH_HIP(s->mem.alloc(&s->forced_out, 3 * cap, false));
-    if (!s->forced_out_host) WH_HIP(s->mem.alloc_pinned(&s->forced_out_host, 3 * cap));
+    wh_session::Forced& f = s->forced;
+    const size_t B = (size_t)s->B, cap = forced_capacity(s);
+    mem::ForcedOutView measure{};
+    const size_t out = mem::pack_forced_out(nullptr, B, kMaxTok, measure) / sizeof(float);
+    if (int r = slot_table_ensure(s)) return r;
+    if (!f.owner) WH_HIP(s->mem.alloc(&f.owner, B * kMaxTok, false));
+    if (!f.desc) WH_HIP(s->mem.alloc_pinned(&f.desc, cap));
+    if (!f.desc_dev) WH_HIP(s->mem.alloc(&f.desc_dev, cap, false));
+    if (!f.out) WH_HIP(s->mem.alloc(&f.out, out, false));
+    if (!f.out_host) WH_HIP(s->mem.alloc_pinned(&f.out_host, out));
+    mem::pack_forced_out(f.out, B, kMaxTok, f.d); mem::pack_forced_out(f.out_host, B, kMaxTok, f.h);
     return WH_OK;
 }
 
@@ -2451,42 +2520,39 @@ static int forced_pass_impl(wh_session* s, int n_audio, const int32_t* const* to
     }
     s->align_enabled = record_alignment && s->align;
     s->fused_greedy = false;
-    const size_t cap = (size_t)B * (kMaxTok - 1);
-    float* const lp_dev = s->forced_out;
-    int* const best_dev = reinterpret_cast<int*>(s->forced_out + cap);
-    float* const best_lp_dev = s->forced_out + 2 * cap;
+    const mem::ForcedOutView &od = s->forced.d, &oh = s->forced.h;
+    mem::StageRing ring(forced_capacity(s), 1);
     const std::vector<plan::ForcedLaunch> launches = plan::forced_pass_plan(n_tokens, n_audio, B);
     const int spw0 = s->use_xabs ? s->xabs.spw : 1;
-    size_t base = 0;
-    s->forced_passes += 1;
+    s->forced.passes += 1;
     for (const plan::ForcedLaunch& l : launches) {
         if (cancelled(s)) { hipStreamSynchronize(s->st); return set_error(WH_ERR_CANCELLED, "forced pass: cancelled through the session's cancel flag"); }
         const int n = (int)l.slots.size();
-        if (base + (size_t)n > cap) return set_error(WH_ERR_DECODING_FAILED, "forced pass: the plan holds more positions than the session's staging");
-        // this launch's own region of the pinned staging (uploaded stream-ordered below, like inpass_stage): the stream has consumed nothing the host writes here
-        ForcedDesc* d = s->forced_desc + base;
+        // this launch's own descriptors of the pinned staging (uploaded stream-ordered below): the stream has consumed nothing the host writes here
+        const size_t base = ring.take((size_t)n);
+        if (base == mem::StageRing::kFull) return set_error(WH_ERR_DECODING_FAILED, "forced pass: the plan holds more positions than the session's staging");
+        ForcedDesc* d = s->forced.desc + base;
         for (int i = 0; i < n; ++i) {
             const plan::ForcedSlot& v = l.slots[(size_t)i];
             d[i] = ForcedDesc{v.audio, v.position, tokens[v.audio][v.position], v.first, v.len, tokens[v.audio][v.position + 1], {0, 0}};
         }
-        WH_HIP(hipMemcpyAsync(s->forced_desc_dev + base, d, sizeof(ForcedDesc) * (size_t)n, hipMemcpyHostToDevice, s->st));
-        launch_forced_arm(s->forced_desc_dev + base, s->seq, s->forced_owner, s->slot_home_dev, n, B, V, s->st);
+        WH_HIP(hipMemcpyAsync(s->forced.desc_dev + base, d, sizeof(ForcedDesc) * (size_t)n, hipMemcpyHostToDevice, s->st));
+        launch_forced_arm(s->forced.desc_dev + base, s->seq, s->forced.owner, s->slots.home_dev, n, B, V, s->st);
         const plan::CompactPassPlan cp = plan::compact_pass_plan(n, B, B, spw0);      // slots per absorbed-attention workgroup: the value of the ladder rung that holds n slots (results do not depend on it)
         s->pass.mapped = true; s->pass.spw = cp.compact ? cp.spw : spw0;
         DecodeBuffers db = whi::decode_buffers(s, n, l.self_rows - 1);
-        db.self_owner = s->forced_owner; db.owner_slots = B;
+        db.self_owner = s->forced.owner; db.owner_slots = B;
         launch_decoder_step(db, nullptr, nullptr, false, s->st);
-        launch_forced_score(s->logits, s->forced_desc_dev + base, n, V, lp_dev + base, best_dev + base, best_lp_dev + base, s->st);
+        launch_forced_score(s->logits, s->forced.desc_dev + base, n, V, od.lp + base, od.best + base, od.best_lp + base, s->st);
         WH_CHECK_LAUNCH();
-        if (s->forced_capture && (base + (size_t)n) * V <= s->forced_capture_floats)       // wh_debug_forced_capture: the rows before the next launch rewrites them
-            WH_HIP(hipMemcpyAsync(s->forced_capture + base * V, s->logits, sizeof(float) * (size_t)n * V, hipMemcpyDeviceToHost, s->st));
-        s->forced_launches += 1; s->forced_positions += n;
-        base += (size_t)n;
+        if (s->forced.capture && (base + (size_t)n) * V <= s->forced.capture_floats)       // wh_debug_forced_capture: the rows before the next launch rewrites them
+            WH_HIP(hipMemcpyAsync(s->forced.capture + base * V, s->logits, sizeof(float) * (size_t)n * V, hipMemcpyDeviceToHost, s->st));
+        s->forced.launches += 1; s->forced.positions += n;
     }
-    if (base) {
-        WH_HIP(hipMemcpyAsync(s->forced_out_host, lp_dev, sizeof(float) * base, hipMemcpyDeviceToHost, s->st));
-        WH_HIP(hipMemcpyAsync(s->forced_out_host + cap, best_dev, sizeof(int) * base, hipMemcpyDeviceToHost, s->st));
-        WH_HIP(hipMemcpyAsync(s->forced_out_host + 2 * cap, best_lp_dev, sizeof(float) * base, hipMemcpyDeviceToHost, s->st));
+    if (const size_t total = ring.taken()) {
+        WH_HIP(hipMemcpyAsync(oh.lp, od.lp, sizeof(float) * total, hipMemcpyDeviceToHost, s->st));
+        WH_HIP(hipMemcpyAsync(oh.best, od.best, sizeof(int32_t) * total, hipMemcpyDeviceToHost, s->st));
+        WH_HIP(hipMemcpyAsync(oh.best_lp, od.best_lp, sizeof(float) * total, hipMemcpyDeviceToHost, s->st));
     }
     WH_HIP(hipStreamSynchronize(s->st));
     for (int a = 0; a < n_audio; ++a) {
@@ -2496,12 +2562,11 @@ static int forced_pass_impl(wh_session* s, int n_audio, const int32_t* const* to
         if (best_lp_out && best_lp_out[a]) best_lp_out[a][0] = 0.0f;
     }
     size_t k = 0;
-    const int* const best_host = reinterpret_cast<const int*>(s->forced_out_host + cap);
     for (const plan::ForcedLaunch& l : launches)
         for (const plan::ForcedSlot& v : l.slots) {
-            if (lp_out && lp_out[v.audio]) lp_out[v.audio][v.position + 1] = s->forced_out_host[k];
-            if (best_out && best_out[v.audio]) best_out[v.audio][v.position + 1] = best_host[k];
-            if (best_lp_out && best_lp_out[v.audio]) best_lp_out[v.audio][v.position + 1] = s->forced_out_host[2 * cap + k];
+            if (lp_out && lp_out[v.audio]) lp_out[v.audio][v.position + 1] = oh.lp[k];
+            if (best_out && best_out[v.audio]) best_out[v.audio][v.position + 1] = oh.best[k];
+            if (best_lp_out && best_lp_out[v.audio]) best_lp_out[v.audio][v.position + 1] = oh.best_lp[k];
             ++k;
         }
     return WH_OK;
@@ -2534,9 +2599,9 @@ extern "C" int wh_score_tokens(wh_session* s, int n_audio, const int32_t* const*
 
 extern "C" int wh_session_forced_pass_stats(const wh_session* s, int64_t* passes, int64_t* launches, int64_t* positions) {
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_forced_pass_stats: null session");
-    if (passes) *passes = s->forced_passes;
-    if (launches) *launches = s->forced_launches;
-    if (positions) *positions = s->forced_positions;
+    whi::store_stat(passes, s->forced.passes);
+    whi::store_stat(launches, s->forced.launches);
+    whi::store_stat(positions, s->forced.positions);
     return WH_OK;
 }
 
@@ -2545,8 +2610,8 @@ extern "C" int wh_session_forced_pass_stats(const wh_session* s, int64_t* passes
 // NULL switches it off.  The buffer must stay valid while it is installed.
 extern "C" int wh_debug_forced_capture(wh_session* s, float* logits_out, size_t capacity_floats) {
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_forced_capture: null session");
-    s->forced_capture = logits_out;
-    s->forced_capture_floats = logits_out ? capacity_floats : 0;
+    s->forced.capture = logits_out;
+    s->forced.capture_floats = logits_out ? capacity_floats : 0;
     return WH_OK;
 }
 
@@ -2559,16 +2624,16 @@ extern "C" int wh_debug_forced_score(wh_session* s, const float* logits_rows, in
     const int V = s->m->dims.n_vocab;
     int r = forced_ensure(s);
     if (r) return r;
-    const size_t cap = (size_t)s->B * (kMaxTok - 1);
+    const mem::ForcedOutView& od = s->forced.d;
     WH_HIP(hipStreamSynchronize(s->st));                  // nothing in flight reads the staging the host writes next
-    for (int i = 0; i < n_rows; ++i) s->forced_desc[i] = ForcedDesc{0, 0, 0, 0, 1, targets[i], {0, 0}};
-    WH_HIP(hipMemcpyAsync(s->forced_desc_dev, s->forced_desc, sizeof(ForcedDesc) * (size_t)n_rows, hipMemcpyHostToDevice, s->st));
+    for (int i = 0; i < n_rows; ++i) s->forced.desc[i] = ForcedDesc{0, 0, 0, 0, 1, targets[i], {0, 0}};
+    WH_HIP(hipMemcpyAsync(s->forced.desc_dev, s->forced.desc, sizeof(ForcedDesc) * (size_t)n_rows, hipMemcpyHostToDevice, s->st));
     WH_HIP(hipMemcpyAsync(s->logits, logits_rows, sizeof(float) * (size_t)n_rows * V, hipMemcpyHostToDevice, s->st));
-    launch_forced_score(s->logits, s->forced_desc_dev, n_rows, V, s->forced_out, reinterpret_cast<int*>(s->forced_out + cap), s->forced_out + 2 * cap, s->st);
+    launch_forced_score(s->logits, s->forced.desc_dev, n_rows, V, od.lp, od.best, od.best_lp, s->st);
     WH_CHECK_LAUNCH();
-    WH_HIP(hipMemcpyAsync(logprobs_out, s->forced_out, sizeof(float) * n_rows, hipMemcpyDeviceToHost, s->st));
-    WH_HIP(hipMemcpyAsync(best_tokens_out, s->forced_out + cap, sizeof(int) * n_rows, hipMemcpyDeviceToHost, s->st));
-    WH_HIP(hipMemcpyAsync(best_logprobs_out, s->forced_out + 2 * cap, sizeof(float) * n_rows, hipMemcpyDeviceToHost, s->st));
+    WH_HIP(hipMemcpyAsync(logprobs_out, od.lp, sizeof(float) * n_rows, hipMemcpyDeviceToHost, s->st));
+    WH_HIP(hipMemcpyAsync(best_tokens_out, od.best, sizeof(int) * n_rows, hipMemcpyDeviceToHost, s->st));
+    WH_HIP(hipMemcpyAsync(best_logprobs_out, od.best_lp, sizeof(float) * n_rows, hipMemcpyDeviceToHost, s->st));
     WH_HIP(hipStreamSynchronize(s->st));
     return WH_OK;
 }
@@ -2654,7 +2719,7 @@ extern "C" int wh_align_tokens_batch(wh_session* s, const float* const* pcm_host
             o.n_tokens = n; o.avg_logprob = sum / (float)n; o.compression_ratio = wh_compression_ratio(words.data(), (int)words.size());
             o.steps = (int)q.size() - 1;
         }
-        const bool device_paths = s->word_alignment == 1;
+        const bool device_paths = s->walign.mode == 1;
         const int32_t *path_len = nullptr, *path_ti = nullptr, *path_tj = nullptr;
         if (device_paths) {
             std::vector<int32_t> rows((size_t)nb);

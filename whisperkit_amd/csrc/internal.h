@@ -106,12 +106,18 @@ struct wh_session {
     float *align = nullptr, *align_mean = nullptr;
     int n_align_alloc = 0;                // alignment heads the `align` allocation was sized for
     int align_znorm = 0, align_median = 0;   // optional openai/whisper-style post-processing (wh_session_set_alignment_postprocess)
-    float* align_tmp = nullptr; int align_tmp_heads = 0;   // [224][n_align][1500] softmax rows + [2][n_align][1500] statistics + 224 flags
-    // word-timestamp alignment (wh_session_set_word_alignment): 0 = per slot on the host, 1 = one batched DTW launch per device batch (align.hip)
-    int word_alignment = 0;
-    int* dtw_dev = nullptr;                // rows [B] | lengths [B] | text_idx [B][kDtwPathCap] | time_idx [B][kDtwPathCap], allocated on first use
-    int32_t* dtw_host = nullptr;           // pinned mirror of lengths | text_idx | time_idx
-    long long dtw_launches = 0, align_d2h_bytes = 0;   // wh_session_word_alignment_stats
+    // word-timestamp alignment beyond the raw rows (wh_session_set_word_alignment): mode 0 = DTW per slot on the host, 1 = one batched DTW launch per device batch
+    // (align.hip).  tmp: the scratch of the optional post-processing, one slot at a time, (re)sized for the session's alignment-head count by capi.hip
+    // ensure_align_tmp and cut by devmem.h pack_align_tmp.  dev / host (pinned): the batched DTW's tables, allocated by the first call of alignment_paths and cut by
+    // pack_dtw - the device buffer has the token rows in front of what the pinned mirror holds.
+    struct WordAlign {
+        int mode = 0;
+        float* tmp = nullptr; int tmp_heads = 0;
+        wh::mem::AlignTmpView t{};
+        int32_t *dev = nullptr, *host = nullptr;
+        wh::mem::DtwView d{}, h{};
+        long long dtw_launches = 0, d2h_bytes = 0;   // wh_session_word_alignment_stats
+    } walign;
     PassState pass;                       // what the running pass switches on (pass_state.h); written by the pass kinds of host.hip / beam.hip under a PassGuard, plain otherwise
     std::map<WhGraphKey, hipGraphExec_t> graphs;   // captured 8-step decode graphs of THIS session (no process-wide state)
     std::map<WhGraphKey, unsigned long long> graph_use;   // last use (a counter) per graph: the cache is capped, least recently used configuration first
@@ -119,6 +125,7 @@ struct wh_session {
     const volatile int32_t* cancel_flag = nullptr; // polled between step graphs and pipeline stages (Task.checkCancellation)
     bool use_xabs = false;                // cross-attention path of this session (fixed at creation: never a function of the live batch)
     wh::Xabs xabs{};                      // absorbed queries + split partials (one allocation: devmem.h carve_session_xabs)
+    wh::Xabs xabs_pass{};                 // the session's xabs with the running pass's slots per workgroup
     wh::Dec32 d32{};                      // decode-step activations: residual, planes, split-K scratch (one allocation: devmem.h carve_session_d32)
     wh::SeqState* seq = nullptr;
     wh::SeqState* seq_host = nullptr;     // pinned
@@ -127,76 +134,96 @@ struct wh_session {
     wh::SamplerCfg* cfg_dev = nullptr;
     int* suppress_dev = nullptr;
     unsigned char* sup_mask_dev = nullptr;   // SuppressTokensFilter byte masks (fused greedy sampler)
-    // option mixing (wh_session_set_option_mixing): 0 = off, 1 = wh_transcribe_batch_with_options groups its audios by batch key (option_mix_plan) and
-    // decodes a group's classes in one pass.  pass.mixed is set by a pass with classes (host.hip PassRequest with a prompt per class or per slot; wh_decode_text_mixed works whatever the mode).
-    int option_mixing = 0;
-    long long mix_groups_run = 0, mix_mixed_passes = 0, mix_max_classes = 0;   // wh_session_option_mixing_stats: groups that ran mixed, passes with classes, largest class count
-    // per-slot prompts.  prompt_mixing (wh_session_set_prompt_mixing): 1 = while option mixing is on, the prompt leaves the class and every audio's own
-    // prompt goes to its slot.  previous_text (wh_session_set_previous_text; NO REFERENCE BEHAVIOUR): 1 = every audio of wh_transcribe* carries its decoded text into the
-    // prompt of its next window (prompt_carry_plan.h), emptied behind a window kept above previous_text_reset (NaN: never).  pass.mixed == 2 is set by a pass with slot prompts
-    int prompt_mixing = 0, previous_text = 0;
-    float previous_text_reset = 0.5f;
-    long long sp_passes = 0, sp_max_distinct = 0, sp_positions = 0, sp_windows_carried = 0, sp_resets = 0;   // wh_session_slot_prompt_stats
     float* stats = nullptr;                  // [B][kStatBlocks][8]
     bool fused_greedy = false;               // NOT pass state (nor is align_enabled below): the step API (wh_predict_logits, wh_measure_kernels) reads what the last decode left
     int *tok_out_dev = nullptr; float* lp_out_dev = nullptr;
     float* scratch_logits = nullptr;       // [V] for the filter / sample KAT entry points
-    // beam search (wh_decode_text_beam, allocated on first use): row -> owning slot table of the self-attention cache, top-k outputs
-    int *beam_owner = nullptr, *beam_tok = nullptr; float* beam_lp = nullptr;
-    // candidate ranking of the beam loop (wh_session_set_beam_ranking): 0 = on the host, one round trip per position; 1 = beam_rank_kernel
-    // (beamrank.hip).  Device mode ping-pongs the decode state, the owner table and the sums between positions: buffer 0 is seq / beam_owner /
-    // beam_sum, buffer 1 is beam_seq_alt / beam_owner_alt / beam_sum + B.  All of it is allocated on first use.
-    int beam_ranking = 0;
-    wh::SeqState* beam_seq_alt = nullptr; int* beam_owner_alt = nullptr; float* beam_sum = nullptr;
-    wh::BeamAudioState* beam_audio = nullptr;      // [B]
-    wh::BeamAudioState* beam_audio_host = nullptr; // pinned mirror (the live flags every 8 positions, the whole state after the loop)
-    int* beam_fin_tok = nullptr; float *beam_fin_lp = nullptr, *beam_fin_sum = nullptr;   // [B][kBeamFinishedCap][kBeamSeqStride] / [B][kBeamFinishedCap]
-    int* beam_fin_len = nullptr;           // [B][kBeamFinishedCap] tokens per finished sequence
-    long long beam_rank_launches = 0, beam_loop_syncs = 0;   // wh_session_beam_stats
-    // compacted fallback passes (wh_session_set_fallback_compaction): 0 = off, 1 = a decode pass with a sparse `active` mask runs at the
-    // width launch_plan.h compact_pass_plan gives.  The table is allocated by the first compacted pass: slot_home_dev [B] on the device,
-    // slot_home_host [2][B] pinned (home slots | live flags).  pass.mapped / pass.spw are set by such a pass (and by the forced and speculative passes, whose virtual slots read the table).
-    int fallback_compaction = 0;
-    int32_t *slot_home_dev = nullptr, *slot_home_host = nullptr;
-    wh::Xabs xabs_pass{};                 // the session's xabs with the pass's slots per workgroup
-    long long decode_passes = 0, compacted_passes = 0, slot_steps = 0;   // wh_session_decode_pass_stats
-    // in-pass compaction (wh_session_set_inpass_compaction): 0 = off, 1 = a wh_decode_text* pass narrows between step graphs as its slots finish
-    // (host.hip inpass_narrow, launch_plan.h inpass_compact_plan / inpass_compose, compact.hip).  Everything is allocated by the first pass that runs
-    // with the option on: seq_home [B] (device, the decode states by home slot), seq_snap [B] (pinned, the second snapshot buffer of the run-ahead
-    // loop), inpass_dev = live flags [B] | owner rows [B][kMaxTok] (device), inpass_stage = kInpassMaxSwitches regions of home [B] | live [B] |
-    // owner rows [B][kMaxTok] (pinned: one region per switch of a pass, so the host never writes a region the stream has not consumed).
-    int inpass_compaction = 0;
-    wh::SeqState *seq_home = nullptr, *seq_snap = nullptr;
-    int32_t *inpass_dev = nullptr, *inpass_stage = nullptr;
-    long long inpass_switches = 0, inpass_slot_steps_saved = 0;          // wh_session_inpass_compaction_stats
-    // forced-transcript pass (wh_score_tokens / wh_align_tokens_batch: host.hip forced_pass_impl, forced_plan.h, forced.hip).  Everything is allocated by
-    // the first pass: forced_owner [B][kMaxTok] (device, the row -> owner rows of the virtual slots), forced_desc [B * (kMaxTok - 1)] (pinned staging:
-    // a call's launches take consecutive regions of it, one descriptor per position, so the host never writes a region the stream has not consumed;
-    // each region is uploaded to the same offset of forced_desc_dev, which the kernels read), forced_out = log p(target) | argmax | log p(argmax), [B * (kMaxTok - 1)] each (device) and its pinned mirror.
-    int32_t* forced_owner = nullptr;
-    wh::ForcedDesc *forced_desc = nullptr, *forced_desc_dev = nullptr;
-    float *forced_out = nullptr, *forced_out_host = nullptr;
-    long long forced_passes = 0, forced_launches = 0, forced_positions = 0;      // wh_session_forced_pass_stats
-    float* forced_capture = nullptr; size_t forced_capture_floats = 0;            // wh_debug_forced_capture: host buffer the launches' logits rows are copied to, or null
-    // speculative greedy decode (wh_decode_text_guided / wh_decode_text_speculative: host.hip spec_pass_impl, spec_plan.h, spec.hip).  Everything is allocated by
-    // the first pass: spec_master [B] (device, the audios' master states), spec_owner [B][kMaxTok] (device, the row -> owner rows of the virtual slots),
-    // spec_desc [kSpecStageRounds][B / 2] (pinned staging: a pass's rounds take consecutive regions of it, so the host never writes a region the stream has
-    // not consumed; each is uploaded to the same offset of spec_desc_dev), spec_io [B / 2] (device, what a round leaves per audio) and its pinned mirror.
-    wh::SeqState* spec_master = nullptr;
-    int32_t* spec_owner = nullptr;
-    wh::SpecDesc *spec_desc = nullptr, *spec_desc_dev = nullptr;
-    wh::SpecRound *spec_io = nullptr, *spec_io_host = nullptr;
-    wh_session* draft = nullptr; int draft_k = 0;      // wh_session_set_draft: not owned
-    long long spec_passes = 0, spec_rounds = 0, spec_positions = 0, spec_accepted = 0;      // wh_session_speculative_stats
-    // no-speech detection (wh_session_set_no_speech_detection: host.hip nospeech_arm, nospeech_plan.h, nospeech.hip): 0 = off, 1 = on, 2 = on + stop.  Everything is
-    // allocated by the first pass that runs with the mode on: ns_dev = pos [B] | stop [B] (float) | prob [B] (float) | stopped [B] | cfg [2] (device, by home slot;
-    // what ns_args points into, at fixed addresses so that captured step graphs stay valid) and its pinned mirror ns_host.  pass.ns holds while a pass
-    // runs whose steps lo .. hi carry the logits store and the kernel; (-1, -1) otherwise, and always with the mode off.
-    int no_speech_detection = 0;
-    int32_t *ns_dev = nullptr, *ns_host = nullptr;
-    wh::NoSpeechArgs ns_args{};
-    wh::SeqState* ns_seq_keep = nullptr; f16* ns_kv_keep = nullptr;      // wh_no_speech_probs: the decode states and the cache rows 0 ([2][L][B][H][64]) the probe puts back
-    long long ns_rows_scored = 0, ns_windows_over = 0, ns_windows_stopped = 0;      // wh_session_no_speech_stats
+    // ---- the opt-in features.  Each owns its mode word, its buffers with their typed views (devmem.h pack_*), its pinned mirrors and its counters; the memory is
+    // allocated on first use by the feature's one ensure function (named with each struct) and stays at fixed addresses, so captured step graphs stay valid.
+    // option mixing (wh_session_set_option_mixing): mode 0 = off, 1 = wh_transcribe_batch_with_options groups its audios by batch key (option_mix_plan) and decodes a
+    // group's classes in one pass.  pass.mixed is set by a pass with classes (host.hip PassRequest with a prompt per class or per slot; wh_decode_text_mixed works whatever the mode).
+    // Per-slot prompts.  prompt_mixing (wh_session_set_prompt_mixing): 1 = while option mixing is on, the prompt leaves the class and every audio's own
+    // prompt goes to its slot.  previous_text (wh_session_set_previous_text; NO REFERENCE BEHAVIOUR): 1 = every audio of wh_transcribe* carries its decoded text into the
+    // prompt of its next window (prompt_carry_plan.h), emptied behind a window kept above previous_text_reset (NaN: never).  pass.mixed == 2 is set by a pass with slot prompts.
+    // No device memory of its own.
+    struct Mixing {
+        int mode = 0;
+        long long groups_run = 0, mixed_passes = 0, max_classes = 0;   // wh_session_option_mixing_stats: groups that ran mixed, passes with classes, largest class count
+        int prompt_mixing = 0, previous_text = 0;
+        float previous_text_reset = 0.5f;
+        long long sp_passes = 0, sp_max_distinct = 0, sp_positions = 0, sp_windows_carried = 0, sp_resets = 0;   // wh_session_slot_prompt_stats
+    } mix;
+    // beam search (wh_decode_text_beam; beam.hip ensure_beam_buffers): owner = the row -> owning slot table of the self-attention cache, tok / lp = the top-k outputs.
+    // ranking (wh_session_set_beam_ranking): 0 = candidates ranked on the host, one round trip per position; 1 = beam_rank_kernel (beamrank.hip).  Device mode
+    // ping-pongs the decode state, the owner table and the sums between positions: buffer 0 is seq / owner / sum.half[0], buffer 1 is seq_alt / owner_alt /
+    // sum.half[1] (one allocation: pack_beam_sums); its buffers are allocated by the first pass that ranks on the device.
+    struct Beam {
+        int ranking = 0;
+        int *owner = nullptr, *tok = nullptr; float* lp = nullptr;
+        wh::SeqState* seq_alt = nullptr; int* owner_alt = nullptr;
+        float* sum_dev = nullptr; wh::mem::BeamSumView sum{};
+        wh::BeamAudioState* audio = nullptr;      // [B]
+        wh::BeamAudioState* audio_host = nullptr; // pinned mirror (the live flags every 8 positions, the whole state after the loop)
+        int* fin_tok = nullptr; float *fin_lp = nullptr, *fin_sum = nullptr;   // [B][kBeamFinishedCap][kBeamSeqStride] / [B][kBeamFinishedCap]
+        int* fin_len = nullptr;           // [B][kBeamFinishedCap] tokens per finished sequence
+        long long rank_launches = 0, loop_syncs = 0;   // wh_session_beam_stats
+    } beam;
+    // the slot table of a pass that decodes at compact or virtual slots (host.hip slot_table_ensure): home_dev [B] on the device, what the kernels of a pass under
+    // pass.mapped read; host (pinned) = home slots [B] | live flags [B] (pack_slot_table), what report_progress reads under pass.mapped.  EVERY pass that sets
+    // pass.mapped calls slot_table_ensure first - the compacted and the narrowing decode passes, the forced pass, the speculative pass - and it allocates both.
+    // fallback_compaction (wh_session_set_fallback_compaction): 0 = off, 1 = a decode pass with a sparse `active` mask runs at the width launch_plan.h compact_pass_plan gives.
+    struct SlotTable {
+        int fallback_compaction = 0;
+        int32_t *home_dev = nullptr, *host = nullptr;
+        wh::mem::SlotTableView h{};
+    } slots;
+    struct PassCounters { long long decode_passes = 0, compacted_passes = 0, slot_steps = 0; } count;   // wh_session_decode_pass_stats
+    // in-pass compaction (wh_session_set_inpass_compaction; host.hip inpass_ensure, inpass_narrow, launch_plan.h inpass_compact_plan / inpass_compose, compact.hip):
+    // mode 0 = off, 1 = a wh_decode_text* pass narrows between step graphs as its slots finish.  seq_snap [B] (pinned, the second snapshot buffer of the run-ahead
+    // loop) is allocated by the first pass that runs with the option on, the rest by the first narrowing: seq_home [B] (device, the decode states by home slot),
+    // dev = live flags | owner rows (pack_inpass_dev), stage (pinned) = a StageRing of kInpassMaxSwitches regions (pack_inpass_region), one per switch of a pass.
+    struct Inpass {
+        int mode = 0;
+        wh::SeqState *seq_home = nullptr, *seq_snap = nullptr;
+        int32_t *dev = nullptr, *stage = nullptr;
+        wh::mem::InpassDevView d{};
+        long long switches = 0, slot_steps_saved = 0;          // wh_session_inpass_compaction_stats
+    } inpass;
+    // forced-transcript pass (wh_score_tokens / wh_align_tokens_batch: host.hip forced_ensure, forced_pass_impl, forced_plan.h, forced.hip).  Everything is allocated by
+    // the first pass: owner [B][kMaxTok] (device, the row -> owner rows of the virtual slots), desc [B * (kMaxTok - 1)] (pinned, a StageRing of single descriptors:
+    // a call's launches take consecutive ones, each uploaded to the same offset of desc_dev, which the kernels read), out (device) and its pinned mirror, both cut by pack_forced_out.
+    struct Forced {
+        int32_t* owner = nullptr;
+        wh::ForcedDesc *desc = nullptr, *desc_dev = nullptr;
+        float *out = nullptr, *out_host = nullptr;
+        wh::mem::ForcedOutView d{}, h{};
+        long long passes = 0, launches = 0, positions = 0;      // wh_session_forced_pass_stats
+        float* capture = nullptr; size_t capture_floats = 0;    // wh_debug_forced_capture: host buffer the launches' logits rows are copied to, or null
+    } forced;
+    // speculative greedy decode (wh_decode_text_guided / wh_decode_text_speculative: host.hip spec_ensure, spec_pass_impl, spec_plan.h, spec.hip).  Everything is allocated by
+    // the first pass: master [B] (device, the audios' master states), owner [B][kMaxTok] (device, the row -> owner rows of the virtual slots), desc (pinned, a StageRing
+    // of kSpecStageRegions regions of B / 2 descriptors: a round takes two, each uploaded to the same offset of desc_dev), io [B / 2] (device, what a round leaves per audio)
+    // and its pinned mirror.
+    struct Spec {
+        wh::SeqState* master = nullptr;
+        int32_t* owner = nullptr;
+        wh::SpecDesc *desc = nullptr, *desc_dev = nullptr;
+        wh::SpecRound *io = nullptr, *io_host = nullptr;
+        wh_session* draft = nullptr; int draft_k = 0;      // wh_session_set_draft: not owned
+        long long passes = 0, rounds = 0, positions = 0, accepted = 0;      // wh_session_speculative_stats
+    } spec;
+    // no-speech detection (wh_session_set_no_speech_detection: host.hip nospeech_ensure, nospeech_arm, nospeech_plan.h, nospeech.hip): mode 0 = off, 1 = on, 2 = on + stop.
+    // dev (device, zero-filled, by home slot; what args points into) and its pinned mirror host are allocated by the first pass that runs with the mode on and cut
+    // by pack_nospeech.  pass.ns holds while a pass runs whose steps lo .. hi carry the logits store and the kernel; (-1, -1) otherwise, and always with the mode off.
+    // seq_keep / kv_keep: the decode states and the cache rows 0 ([2][L][B][H][64]) that wh_no_speech_probs puts back, allocated by the first probe.
+    struct NoSpeech {
+        int mode = 0;
+        int32_t *dev = nullptr, *host = nullptr;
+        wh::mem::NoSpeechView d{}, h{};
+        wh::NoSpeechArgs args{};
+        wh::SeqState* seq_keep = nullptr; f16* kv_keep = nullptr;
+        long long rows_scored = 0, windows_over = 0, windows_stopped = 0;      // wh_session_no_speech_stats
+    } ns;
     // device rules (host.hip).  rs_sets[k]: the session's copy of rule set k, what the getters hand out.  Entry 0 is the session's own
     // set (wh_session_set_logit_rules / wh_session_set_phrase_rules: its two halves; defined / special_begin belong to the bank and stay unused there), entries
     // 1 .. 15 are the banked sets (wh_session_define_rule_set).  A half's arrays stay valid until the next setter call for that set.
@@ -208,39 +235,41 @@ struct wh_session {
         std::vector<int32_t> bias_tokens, tokens, lengths;
         std::vector<float> bias_values, biases;
     };
-    RuleSetCopy rs_sets[wh::plan::kMaxRuleSets];
-    // device logit rules (wh_session_set_logit_rules: host.hip, logit_rules_plan.h, logit_rules.hip).  logit_rules_on: a set other than the neutral one is
-    // installed.  lr_dev (device, kLogitRulesWords words at a fixed address, so that captured step graphs stay valid when values change) and its pinned
-    // mirror lr_host are allocated by the first setter that installs rules.
-    bool logit_rules_on = false;
-    int32_t *lr_dev = nullptr, *lr_host = nullptr;
-    long long lr_passes = 0, lr_launches = 0;      // wh_session_logit_rules_stats
-    // device phrase rules (wh_session_set_phrase_rules: host.hip, phrase_rules_plan.h, phrase_rules.hip).  phrase_rules_on: a non-empty set is installed.
-    // pr_args.table (device, kPhraseTableWords words at a fixed address, so that captured step graphs stay valid when values change), its pinned mirror
-    // pr_host and the 64-bit match counter pr_args.matches are allocated by the first setter that installs rules.
-    bool phrase_rules_on = false;
-    int32_t *pr_dev = nullptr, *pr_host = nullptr;
-    wh::PhraseRulesArgs pr_args{nullptr, nullptr};
-    long long pr_passes = 0, pr_launches = 0;      // wh_session_phrase_rules_stats (matches: the device counter)
-    // per-audio rule sets (wh_session_define_rule_set: host.hip, rule_sets_plan.h, rule_sets.hip).  rs_slot: the set index of every home slot, empty = all 0;
-    // the step-level setter writes it, every wh_transcribe* call owns it for its duration and leaves it all 0.  Everything on the device is ONE allocation
-    // made by the first definition: rs_dev = match counters [kMaxRuleSets] (64-bit) | slot table [kMaxSessionSlots] | bank [15][kRuleSetStride], at fixed
-    // addresses so that captured step graphs stay valid; rs_host (pinned) = slot table mirror [kMaxSessionSlots] | the staging of one set [kRuleSetStride].
-    // rs_args is what a set-aware pass's launches bake.
-    std::vector<int32_t> rs_slot;
-    int32_t *rs_dev = nullptr, *rs_host = nullptr;
-    wh::RuleSetsArgs rs_args{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-    long long rs_passes = 0, rs_launches = 0;      // wh_session_rule_set_stats (matches: the device counters)
-    // token alternatives (wh_session_set_token_alternatives: host.hip alternatives_arm / alternatives_collect, alternatives_plan.h, the recording instantiations of
-    // sampler_kernel).  token_alternatives: 0 = off, n = 1 .. 8.  Everything is allocated by the first setter call that turns the mode on: alt_ids (device, int32
-    // [B][224][8]) and alt_f32 (device, float: log-probabilities [B][224][8] | entropies [B][224]), both by home slot at fixed addresses so that captured step
-    // graphs stay valid, and their pinned mirrors.  alt_start / alt_count / alt_nrec: per home slot, the list index of result token 0, the result's token count and the n of the
-    // last pass that decoded the slot (wh_decode_alternatives).  pass.alt is set by a pass under the mode.
-    int token_alternatives = 0;
-    int32_t *alt_ids = nullptr, *alt_ids_host = nullptr;
-    float *alt_f32 = nullptr, *alt_f32_host = nullptr;
-    std::vector<int32_t> alt_start, alt_count, alt_nrec;
-    long long alt_passes = 0, alt_positions = 0, alt_d2h_bytes = 0;      // wh_session_token_alternatives_stats
+    // logit_rules_on / phrase_rules_on: a set other than the neutral / the empty one is installed (wh_session_set_logit_rules / wh_session_set_phrase_rules)
+    bool logit_rules_on = false, phrase_rules_on = false;
+    // Logit rules (logit_rules_plan.h, logit_rules.hip): lr_dev (device, kLogitRulesWords words) and its pinned mirror lr_host, allocated by the first setter that
+    // installs rules (host.hip logit_rules_ensure).  Phrase rules (phrase_rules_plan.h, phrase_rules.hip): pr_dev = pr_args.table (device, kPhraseTableWords words), its
+    // pinned mirror pr_host and the 64-bit match counter pr_args.matches, likewise (phrase_rules_ensure).  Per-audio rule sets (wh_session_define_rule_set: rule_sets_plan.h,
+    // rule_sets.hip).  rs_slot: the set index of every home slot, empty = all 0; the step-level setter writes it, every wh_transcribe* call owns it for its duration and leaves
+    // it all 0.  rs_dev is ONE device allocation made by the first definition (rule_sets_ensure) and cut by pack_rule_sets_dev into rs; rs_host (pinned) is cut by
+    // pack_rule_sets_host into rs_h.  rs_args is what a set-aware pass's launches bake.
+    struct Rules {
+        __attribute__((always_inline)) ~Rules() = default;      // (part of the session's destructor, as when the fields lay in the session)
+        RuleSetCopy rs_sets[wh::plan::kMaxRuleSets];
+        int32_t *lr_dev = nullptr, *lr_host = nullptr;
+        long long lr_passes = 0, lr_launches = 0;      // wh_session_logit_rules_stats
+        int32_t *pr_dev = nullptr, *pr_host = nullptr;
+        wh::PhraseRulesArgs pr_args{nullptr, nullptr};
+        long long pr_passes = 0, pr_launches = 0;      // wh_session_phrase_rules_stats (matches: the device counter)
+        std::vector<int32_t> rs_slot;
+        int32_t *rs_dev = nullptr, *rs_host = nullptr;
+        wh::mem::RuleSetsDevView rs{};
+        wh::mem::RuleSetsHostView rs_h{};
+        wh::RuleSetsArgs rs_args{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
+        long long rs_passes = 0, rs_launches = 0;      // wh_session_rule_set_stats (matches: the device counters)
+    } rules;
+    // token alternatives (wh_session_set_token_alternatives: host.hip alternatives_ensure, alternatives_arm / alternatives_collect, alternatives_plan.h, the recording
+    // instantiations of sampler_kernel).  n: 0 = off, 1 .. 8.  Everything is allocated by the first setter call that turns the mode on: ids (device, int32 [B][224][8])
+    // and f32 (device, cut by pack_alternatives_f32), both by home slot, and their pinned mirrors.  start / count / nrec: per home slot, the list index of result token 0,
+    // the result's token count and the n of the last pass that decoded the slot (wh_decode_alternatives).  pass.alt is set by a pass under the mode.
+    struct TokenAlternatives {
+        int n = 0;
+        int32_t *ids = nullptr, *ids_host = nullptr;
+        float *f32 = nullptr, *f32_host = nullptr;
+        wh::mem::AltF32View d{}, h{};
+        std::vector<int32_t> start, count, nrec;
+        long long passes = 0, positions = 0, d2h_bytes = 0;      // wh_session_token_alternatives_stats
+    } alt;
     hipEvent_t ev[8]{};
     bool align_enabled = false;
     wh_timings last_timings{};
@@ -309,25 +338,25 @@ void transcription_truncate_segments(wh_transcription* t, int n_keep);     // re
 // no_speech_prob: the window's value (no-speech detection, nospeech.hip), or 0 - the reference's constant
 void finalize_decoding_result(const wh::SeqState& sq, const wh_decoding_options* opt, const wh_special_tokens* st,
                               float temperature, wh_decoding_result* out, float no_speech_prob = 0.0f);
-// no-speech detection (host.hip): allocate the tables; arm them for a pass over the home slots 0 .. n - 1 (pos / stop by home slot, null stop: never) and set
+// no-speech detection (host.hip): arm the tables (allocated on first use) for a pass over the home slots 0 .. n - 1 (pos / stop by home slot, null stop: never) and set
 // pass.ns; read prob | stopped back behind the pass (the stream is drained) and count.  prob of home slot b: nospeech_prob(s, b)
 int nospeech_arm(wh_session* s, int n, const int* pos, const float* stop, int token, int lane_div);
 int nospeech_collect(wh_session* s, int n, const wh_decoding_options* const* opts);
-inline float nospeech_prob(const wh_session* s, int b) { float v; memcpy(&v, s->ns_host + 2 * (size_t)s->B + b, sizeof(v)); return v; }
-inline const wh::NoSpeechArgs* nospeech_step_args(const wh_session* s, int step) { return wh::plan::nospeech_step_in_range(step, s->pass.ns) ? &s->ns_args : nullptr; }
+inline float nospeech_prob(const wh_session* s, int b) { return s->ns.h.prob[b]; }
+inline const wh::NoSpeechArgs* nospeech_step_args(const wh_session* s, int step) { return wh::plan::nospeech_step_in_range(step, s->pass.ns) ? &s->ns.args : nullptr; }
 // token alternatives (host.hip): reset the rows of the live home slots among 0 .. n - 1 and set pass.alt; behind the pass (the stream is drained) bring those rows
 // down into the pinned mirrors and count.  The rows of home slot b: alternatives_rows
 int alternatives_arm(wh_session* s, int n, const int32_t* active);
 int alternatives_collect(wh_session* s, int n, const int32_t* active);
 // device logit rules: the rule set a step of the running pass hands to launch_decoder_step, or null (no rules set, or a pass that does not run them)
-inline const int* logit_rules_step_args(const wh_session* s) { return (s->pass.rules & wh::plan::kRulesPassLogitKernel) ? s->lr_dev : nullptr; }
+inline const int* logit_rules_step_args(const wh_session* s) { return (s->pass.rules & wh::plan::kRulesPassLogitKernel) ? s->rules.lr_dev : nullptr; }
 // device phrase rules: likewise
-inline const wh::PhraseRulesArgs* phrase_rules_step_args(const wh_session* s) { return (s->pass.rules & wh::plan::kRulesPassPhraseKernel) ? &s->pr_args : nullptr; }
+inline const wh::PhraseRulesArgs* phrase_rules_step_args(const wh_session* s) { return (s->pass.rules & wh::plan::kRulesPassPhraseKernel) ? &s->rules.pr_args : nullptr; }
 // per-audio rule sets: does any of the home slots 0 .. n - 1 name a set other than 0?  (the passes that do not run rule sets refuse such a call)
 inline bool rule_sets_assigned(const wh_session* s, int n) {
-    for (int b = 0; b < n && b < (int)s->rs_slot.size(); ++b) if (s->rs_slot[(size_t)b] != 0) return true;
+    for (int b = 0; b < n && b < (int)s->rules.rs_slot.size(); ++b) if (s->rules.rs_slot[(size_t)b] != 0) return true;
     return false;
 }
-// the device regions of rs_dev, in 32-bit words
-constexpr int kRsOffSlots = 2 * wh::plan::kMaxRuleSets, kRsOffBank = kRsOffSlots + wh::kMaxSessionSlots;
+// the stats getters: a null destination is not wanted
+inline void store_stat(int64_t* out, long long v) { if (out) *out = v; }
 }  // namespace whi
