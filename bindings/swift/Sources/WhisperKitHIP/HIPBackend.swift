@@ -547,6 +547,24 @@ public final class HIPTokenizer /* : WhisperTokenizer */ {
         wh_tokenizer_decode(handle, ids, Int32(ids.count), 0, &buf, n + 1)
         return String(decoding: buf.prefix(Int(n)).map(UInt8.init(bitPattern:)), as: UTF8.self)
     }
+    // WhisperTokenizer.encode(text:) (Core/Models.swift:1153).  The protocol's method does not throw: a tokenizer.json outside the implemented shape
+    // (canEncode false) and ill-formed text give [] - a caller that must tell them apart asks canEncode first.
+    public var canEncode: Bool { wh_tokenizer_can_encode(handle) == 1 }
+    public func encode(text: String) -> [Int] {
+        let n = wh_tokenizer_encode(handle, text, 0, nil, 0)
+        guard n > 0 else { return [] }
+        var ids = [Int32](repeating: 0, count: Int(n))
+        wh_tokenizer_encode(handle, text, 0, &ids, n)
+        return ids.map(Int.init)
+    }
+    // the CLI's prompt rule (TranscribeCLI.swift:135,146) for DecodingOptions.promptTokens / prefixTokens
+    public func encodePrompt(text: String) -> [Int] {
+        let n = wh_tokenizer_encode_prompt(handle, text, nil, 0)
+        guard n > 0 else { return [] }
+        var ids = [Int32](repeating: 0, count: Int(n))
+        wh_tokenizer_encode_prompt(handle, text, &ids, n)
+        return ids.map(Int.init)
+    }
     public var specialTokens: SpecialTokens { var st = wh_special_tokens(); wh_tokenizer_special_tokens(handle, &st); return SpecialTokens(hip: st) }
 }
 // wh_session_set_tokenizer(session, tokenizer.handle): transcribe results then carry text, words and the language code

@@ -856,6 +856,34 @@ int wh_tokenizer_special_tokens(const wh_tokenizer* t, wh_special_tokens* out);
 int wh_tokenizer_split_to_word_tokens(const wh_tokenizer* t, const int32_t* tokens, int n, const char* language_code,
                                       int32_t* word_token_counts, int32_t* word_byte_counts, int counts_capacity,
                                       char* words_out, int words_capacity, int* words_bytes);
+/* ---- text -> ids: WhisperTokenizer.encode(text:) (Core/Models.swift:1153, the wrapper's at :1171).  The semantics are those of HF `tokenizers`
+ * on the same tokenizer.json (Tokenizer.from_file(p).encode(text, add_special_tokens).ids), restated for the Whisper shape of the file: added
+ * tokens cut out of the raw text (leftmost, longest), the ByteLevel pre-tokenizer's pattern, the byte-level alphabet, merges by lowest rank.
+ * wh_tokenizer_load parses model.merges in both serialisations ("a b" strings and ["a", "b"] pairs); a merge that names a token outside the
+ * vocabulary fails the load, as it does there.  Functions that write ids follow the size convention of wh_tokenizer_decode: they return the
+ * number of ids needed and write at most `capacity` of them, so a first call with (NULL, 0) sizes the buffer; a failure returns
+ * -(its wh_status) with the message in wh_last_error().  Host only; a tokenizer is immutable after the load, so calls may run concurrently. */
+/* 1 when the file has the shape that is implemented: normalizer null; pre_tokenizer ByteLevel with use_regex true and add_prefix_space false; BPE
+ * with dropout null, empty continuing_subword_prefix and end_of_word_suffix, byte_fallback and ignore_merges false, a token for each of the 256
+ * bytes; every added token with lstrip / rstrip / single_word / normalized false.  0 otherwise: every encoding call below then fails with
+ * WH_ERR_TOKENIZER_UNAVAILABLE and a message that names the field - an encoding that differs from `tokenizers` is never returned - while
+ * decoding and word splitting work as before. */
+int wh_tokenizer_can_encode(const wh_tokenizer* t);
+/* encode(text:) (Core/Models.swift:1153).  text: NUL-terminated UTF-8; ill-formed UTF-8 is WH_ERR_INVALID_ARGUMENT (nothing is repaired), as is a
+ * text of 1 GiB or more; "" gives 0 ids.  add_special_tokens != 0 applies the `single` template of a TemplateProcessing post_processor; a null post_processor adds
+ * nothing and any other type is WH_ERR_TOKENIZER_UNAVAILABLE then.  Cost: O(n log n) in the longest run without a split point. */
+int wh_tokenizer_encode(const wh_tokenizer* t, const char* text, int add_special_tokens, int32_t* out_ids, int capacity);
+/* The rule the reference's front ends build promptTokens / prefixTokens with (WhisperKitCLI/TranscribeCLI.swift:135,146;
+ * Server/OpenAIHandler.swift:217,387): encode(" " + text.trimmingCharacters(in: .whitespaces)).filter { $0 < specialTokenBegin }.
+ * Text that is empty after trimming gives 0 ids. */
+int wh_tokenizer_encode_prompt(const wh_tokenizer* t, const char* text, int32_t* out_ids, int capacity);
+/* NO REFERENCE BEHAVIOUR (the reference hard-codes no such list): openai/whisper's Tokenizer.non_speech_tokens over this vocabulary - its fixed
+ * list of annotation symbols, each encoded bare and behind a space and kept when that is one token (for the musical symbols U+2669 .. U+266F: the
+ * first token in any case), plus the first tokens of " -" and " '"; ascending, unique.  An id list for suppress_tokens or a logit-rule bias. */
+int wh_tokenizer_non_speech_tokens(const wh_tokenizer* t, int32_t* out_ids, int capacity);
+/* Development aid: the pre-tokenizer's split alone (what `pre_tokenizer.pre_tokenize_str` of `tokenizers` shows): the UTF-8 byte count of every
+ * piece of `text`, in order, by the same size convention. */
+int wh_debug_tokenizer_pre_tokenize(const char* text, int32_t* piece_bytes, int capacity);
 /* TextDecoding.tokenizer (Core/TextDecoder.swift:61): with a tokenizer attached the transcribe entry points produce
  * segment / word / result text, group word timestamps by real words and infer the language code.  NULL detaches.
  * The tokenizer must outlive the session's use of it. */

@@ -294,6 +294,12 @@ SYMBOLS = {
     "wh_tokenizer_id_to_token": (I, [VP, I, C.c_char_p, I]),
     "wh_tokenizer_special_tokens": (I, [VP, PST]),
     "wh_tokenizer_split_to_word_tokens": (I, [VP, PI32, I, C.c_char_p, PI32, PI32, I, C.c_char_p, I, C.POINTER(I)]),
+    # text -> ids (csrc/tokenizer.cpp): the count needed, or -(wh_status)
+    "wh_tokenizer_can_encode": (I, [VP]),
+    "wh_tokenizer_encode": (I, [VP, C.c_char_p, I, PI32, I]),
+    "wh_tokenizer_encode_prompt": (I, [VP, C.c_char_p, PI32, I]),
+    "wh_tokenizer_non_speech_tokens": (I, [VP, PI32, I]),
+    "wh_debug_tokenizer_pre_tokenize": (I, [C.c_char_p, PI32, I]),
     "wh_session_set_tokenizer": (I, [VP, VP]),
     "wh_session_set_progress_callback": (I, [VP, PROGRESS_FN, VP]),
     "wh_transcription_has_text": (I, [VP]),

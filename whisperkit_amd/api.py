@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import ctypes as C
 import dataclasses
+import functools
 import math
 import weakref
 from typing import List, Optional, Sequence, Tuple, Union
@@ -70,6 +71,16 @@ class DecodingOptions:
     float16Logits: bool = False   # reference-numerics switch (wh_decoding_options.float16_logits): FloatType logits + Float16 timestamp rule
     beamSize: int = 0             # > 1: the T = 0 pass is a beam search (openai/whisper semantics; NO REFERENCE BEHAVIOUR - fatalError there)
     beamPatience: float = 1.0
+
+    def withText(self, tokenizer: "Tokenizer", prompt: Optional[str] = None, prefix: Optional[str] = None) -> "DecodingOptions":
+        """A copy with promptTokens / prefixTokens built from text the way the reference's CLI builds them (TranscribeCLI.swift:135,146;
+        Tokenizer.encodePrompt); a text left None keeps the field as it is."""
+        changes = {}
+        if prompt is not None:
+            changes["promptTokens"] = tokenizer.encodePrompt(prompt)
+        if prefix is not None:
+            changes["prefixTokens"] = tokenizer.encodePrompt(prefix)
+        return dataclasses.replace(self, **changes)
 
     def to_c(self):
         o = L.WhDecodingOptions()
@@ -307,6 +318,10 @@ def _collect_again(res: TranscriptionResult) -> TranscriptionResult:
     return _collect(out)
 
 
+# CharacterSet.whitespaces (general category Zs and TAB): what wh_tokenizer_encode_prompt trims (csrc/unicode_tables.h kSpaceSeparatorRanges)
+SWIFT_WHITESPACES = "\t \u00a0\u1680" + "".join(chr(c) for c in range(0x2000, 0x200B)) + "\u202f\u205f\u3000"
+
+
 class Tokenizer:
     """WhisperTokenizer (Core/Models.swift:1150-1307) loaded from a HF `tokenizer.json` (ModelUtilities.loadTokenizer)."""
 
@@ -324,6 +339,51 @@ class Tokenizer:
     def decode(self, tokens: Sequence[int], skipSpecialTokens: bool = False) -> str:
         a = np.ascontiguousarray(list(tokens), dtype=np.int32)
         return _string(self.lib.wh_tokenizer_decode, self.handle, a.ctypes.data_as(L.PI32), len(a), int(skipSpecialTokens))
+
+    # ---- text -> ids (csrc/tokenizer.cpp): HF `tokenizers` semantics on the same tokenizer.json, restated
+    def _ids(self, fn, *args) -> List[int]:
+        n = fn(self.handle, *args, None, 0)
+        if n < 0:
+            raise WhisperError(-n, self.lib.wh_last_error().decode())
+        buf = (C.c_int32 * max(n, 1))()
+        fn(self.handle, *args, buf, n)
+        return list(buf[:n])
+
+    @staticmethod
+    def _utf8(text: str) -> bytes:
+        b = text.encode("utf-8", "surrogatepass")      # a lone surrogate stays ill-formed and is refused by the library, not repaired here
+        if b"\0" in b:
+            raise WhisperError(100, "encode: the text holds a NUL character (the C ABI takes NUL-terminated strings)")
+        return b
+
+    canEncode = property(lambda s: bool(s.lib.wh_tokenizer_can_encode(s.handle)))
+
+    def encode(self, text: str, addSpecialTokens: bool = False) -> List[int]:
+        """WhisperTokenizer.encode(text:) (Core/Models.swift:1153): the ids `tokenizers` gives for Tokenizer.from_file(path).encode(text, add_special_tokens).
+        A tokenizer.json outside the implemented Whisper shape (canEncode False) raises WhisperError code 1 naming the field; ill-formed text code 100."""
+        return self._ids(self.lib.wh_tokenizer_encode, self._utf8(text), int(addSpecialTokens))
+
+    def encodePrompt(self, text: str) -> List[int]:
+        """The ids the reference's front ends put into promptTokens / prefixTokens (TranscribeCLI.swift:135,146): encode(" " + text trimmed of whitespaces)
+        without the special tokens; nothing for a text that is empty after trimming."""
+        return self._ids(self.lib.wh_tokenizer_encode_prompt, self._utf8(text))
+
+    def nonSpeechTokens(self) -> List[int]:
+        """NO REFERENCE BEHAVIOUR: openai/whisper's Tokenizer.non_speech_tokens over this vocabulary (ascending) - an id list for
+        DecodingOptions.suppressTokens or Session.setLogitRules(tokenBias=...)."""
+        return self._ids(self.lib.wh_tokenizer_non_speech_tokens)
+
+    def phraseVariants(self, text: str) -> List[Tuple[int, ...]]:
+        """The distinct id tuples a phrase rule must name for `text`: a phrase is tokenized one way at the start of a segment (encode(text)) and another in
+        running text (encode(" " + text)), both after trimming and without special tokens.  A variant that encodes to nothing is left out."""
+        begin = self.specialTokens.special_token_begin
+        spaced = self.encodePrompt(text)
+        bare = [t for t in self.encode(text.strip(SWIFT_WHITESPACES)) if t < begin]
+        out = []
+        for v in (tuple(bare), tuple(spaced)):
+            if v and v not in out:
+                out.append(v)
+        return out
 
     def convertTokenToId(self, token: str) -> Optional[int]:
         i = self.lib.wh_tokenizer_token_to_id(self.handle, token.encode("utf-8"))
@@ -519,6 +579,25 @@ def _phrase_rules_list(r) -> list:
         out.append((tuple(int(r.tokens[at + k]) for k in range(n)), float(r.biases[i])))
         at += n
     return out
+
+
+def _takes_phrases_text(method):
+    """Session.defineRuleSet's own parameter list is fixed (callers and tests/test_rule_sets.py name it positionally), so the text form of its phrases comes in
+    as one keyword in front of it: phrasesText is encoded with the session's tokenizer (Session._phrases_of_text) and appended to `phrases`, given by keyword or
+    as the fifth positional argument, and the call goes on unchanged.  functools.wraps: introspection shows the wrapped function's parameters."""
+    @functools.wraps(method)
+    def call(self, *args, phrasesText=None, **kw):
+        if phrasesText:
+            at = 4                                              # index, repetitionPenalty, noRepeatNgramSize, tokenBias, phrases
+            phrases = args[at] if len(args) > at else kw.get("phrases")
+            given = list(phrases.items()) if isinstance(phrases, dict) else list(phrases or [])
+            merged = given + self._phrases_of_text(method.__name__, phrasesText)
+            if len(args) > at:
+                args = args[:at] + (merged,) + args[at + 1:]
+            else:
+                kw["phrases"] = merged
+        return method(self, *args, **kw)
+    return call
 
 
 class Session:
@@ -1115,10 +1194,29 @@ class Session:
         SETTING RULES CHANGES RESULTS.  No argument or an empty list turns the mode off.  Runs wherever the logit rules run (decodeText / decodeTextMixed /
         transcribe*: every temperature rung, compacted, narrowed and mixed passes) under the unfused sampler; decodeTextCustom, detectLanguage, noSpeechProbs
         and the forced pass do not run the rules; decodeTextBeam / decodeTextGuided / decodeTextSpeculative and beamSize > 1 in transcribe* are refused while
-        rules are set, and transcribe* ignores an attached draft.  Out of scope: text in place of ids, beam search under rules, retraction of a bias when
+        rules are set, and transcribe* ignores an attached draft.  Phrases as text: setPhraseRulesText.  Out of scope: beam search under rules, retraction of a bias when
         a partial match breaks, more than 4096 sequences.  (A rule set per audio: defineRuleSet.)"""
         r, _alive = _phrase_rules_struct(sequences)
         _check(self.lib.wh_session_set_phrase_rules(self.handle, C.byref(r)))
+
+    def _text_tokenizer(self, who: str) -> "Tokenizer":
+        tok = getattr(self, "tokenizer", None)
+        if tok is None:
+            raise WhisperError(1, f"{who}: the session has no tokenizer (setTokenizer)")
+        return tok
+
+    def _phrases_of_text(self, who: str, phrasesText) -> list:
+        """{text: bias} or [(text, bias), ...] as [((id, ...), bias), ...]: the bias of a text goes to each of its variants (Tokenizer.phraseVariants)"""
+        tok = self._text_tokenizer(who)
+        items = phrasesText.items() if hasattr(phrasesText, "items") else phrasesText
+        return [(v, bias) for text, bias in items for v in tok.phraseVariants(text)]
+
+    def setPhraseRulesText(self, phrasesText=None):
+        """setPhraseRules with the phrases given as text, {text: bias} or [(text, bias), ...]: every text becomes its variants under the session's tokenizer
+        (setTokenizer; Tokenizer.phraseVariants: the tokenization at the start of a segment and the one in running text), each with the text's bias, and the
+        list goes through setPhraseRules with its limits and validation - two texts that yield one sequence are a sequence given twice.  Without a tokenizer,
+        or with one that cannot encode: WhisperError code 1.  No argument or an empty list turns the mode off."""
+        self.setPhraseRules(self._phrases_of_text("setPhraseRulesText", phrasesText) if phrasesText else None)
 
     def phraseRules(self) -> list:
         """the session's phrase rules, in the caller's order: [((id, ...), bias), ...] - empty when the mode is off"""
@@ -1135,6 +1233,7 @@ class Session:
 
     MAX_RULE_SETS = 16      # include/whisperhip.h WH_MAX_RULE_SETS (a design constant): index 0 is the session's own rules, 1 .. 15 the bank
 
+    @_takes_phrases_text
     def defineRuleSet(self, index: int, repetitionPenalty: float = 1.0, noRepeatNgramSize: int = 0, tokenBias=None, phrases=None):
         """NO REFERENCE BEHAVIOUR.  Defines rule set `index` (1 .. 15) of the session's bank: one setLogitRules set (repetitionPenalty, noRepeatNgramSize,
         tokenBias) plus one setPhraseRules list (phrases), with their limits, validation and arithmetic.  Every audio of transcribeWithOptions(..., ruleSets=...)
@@ -1143,7 +1242,9 @@ class Session:
         setPhraseRules), possibly none.  Only the index and nothing else undefines it.  A pass whose live slots all name 0 is unchanged; any other pass runs the
         unfused sampler with one kernel per step in front of it (csrc/rule_sets.hip).  decodeTextBeam / decodeTextGuided /
         decodeTextSpeculative and beamSize > 1 are refused for slots and audios under a set other than 0; an attached draft is ignored for a group that
-        carries sets.  The bank (about 5 MB) is allocated by the first definition."""
+        carries sets.  The bank (about 5 MB) is allocated by the first definition.  The keyword phrasesText={text: bias} or [(text, bias), ...] is taken in
+        front of this function (_takes_phrases_text): turned into sequences as setPhraseRulesText turns them (the session's tokenizer; WhisperError code 1
+        without one) and appended to `phrases` before the validation."""
         lr, _alive_lr = _logit_rules_struct(repetitionPenalty, noRepeatNgramSize, tokenBias)
         pr, _alive_pr = _phrase_rules_struct(phrases)
         _check(self.lib.wh_session_define_rule_set(self.handle, int(index), C.byref(lr), C.byref(pr)))
@@ -1393,6 +1494,16 @@ class Session:
         self._guarded(self.lib.wh_align_tokens_batch, self.handle, ptrs, lens, n, optv, C.byref(st), tptr, tlen, outs, stat)
         return [_collect(outs[i]) if stat[i] == 0 else WhisperError(int(stat[i]), self.lib.wh_session_item_error(self.handle, i).decode()) for i in range(n)]
 
+    def alignText(self, audioArrays: Sequence[np.ndarray], texts: Sequence[str],
+                  options: Union[None, DecodingOptions, Sequence[Optional[DecodingOptions]]] = None,
+                  specialTokens=None) -> List[Union[TranscriptionResult, WhisperError]]:
+        """alignTokens for transcripts given as text: texts[a] becomes Tokenizer.encodePrompt(texts[a]) under the session's tokenizer (WhisperError code 1
+        without one, or with one that cannot encode).  A text of more than 224 tokens is that audio's own error, as in alignTokens."""
+        tok = self._text_tokenizer("alignText")
+        if len(texts) != len(audioArrays):
+            raise WhisperError(9, "The number of audio arrays and texts must be balanced.")
+        return self.alignTokens(audioArrays, [tok.encodePrompt(t) for t in texts], options, specialTokens)
+
     def forcedPassStats(self) -> Tuple[int, int, int]:
         """(forced passes, their decoder launches, the positions those launches ran) since the session was created"""
         a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
@@ -1545,6 +1656,11 @@ def phraseBoost(phrases, bias: float) -> List[Tuple[Tuple[int, ...], float]]:
     if len(out) > MAX_PHRASE_SEQUENCES:
         raise ValueError(f"phraseBoost: {len(out)} sequences, more than the {MAX_PHRASE_SEQUENCES} one rule set holds")
     return list(out.items())
+
+
+def phraseBoostText(tokenizer: "Tokenizer", phrases: Sequence[str], bias: float) -> List[Tuple[Tuple[int, ...], float]]:
+    """phraseBoost over every variant (Tokenizer.phraseVariants: at the start of a segment and in running text) of every phrase given as text."""
+    return phraseBoost([v for text in phrases for v in tokenizer.phraseVariants(text)], bias)
 
 
 def compressionRatio(tokens: Sequence[int]) -> float:

@@ -21,6 +21,19 @@ struct wh_tokenizer {
     wh_special_tokens special{};
     std::vector<int> language_tokens;         // allLanguageTokens, ascending
 
+    // encode side (tokenizer.cpp).  encode_refusal names the first field of the file that is outside the implemented Whisper shape
+    // ("" = wh_tokenizer_can_encode); the tables below are filled either way, decode never looks at them.
+    std::string encode_refusal;
+    std::unordered_map<uint64_t, std::pair<int32_t, int32_t>> merges;   // (left id << 32 | right id) -> (rank, merged id)
+    int32_t byte_token[256];                                            // id of the one-character token of each byte, -1 = not in the vocabulary
+    std::unordered_map<uint64_t, int32_t> added_trie;                   // byte trie over the added tokens' contents: (node << 8 | byte) -> node
+    std::vector<int32_t> added_trie_id;                                 // node -> id of the added token that ends there, -1 = none
+    int post_processor = 0;                                             // 0 null, 1 TemplateProcessing, 2 anything else (post_processor_what says what)
+    std::string post_processor_what;
+    std::vector<int32_t> template_single;                               // the `single` template as ids, -1 where the sequence goes
+
+    int encode(const char* text, size_t n, bool add_special_tokens, std::vector<int32_t>& ids) const;   // a wh_status; appends to ids
+
     std::string decode(const int32_t* tokens, int n, bool skip_special) const;
     std::string decode(const std::vector<int>& t, bool skip_special = false) const { return decode(t.data(), (int)t.size(), skip_special); }
     void split_on_unicode(const std::vector<int>& tokens, std::vector<std::string>& words, std::vector<std::vector<int>>& word_tokens) const;
@@ -42,6 +55,9 @@ struct Word {
 // UTF-8 helpers shared by the splitter and the punctuation merge
 std::string utf8_repair(const std::string& bytes);                     // String(decoding:as: UTF8.self)
 std::vector<uint32_t> utf8_scalars(const std::string& s);
+bool utf8_valid(const char* s, size_t n);                              // well formed by the table utf8_repair repairs to
+// the GPT-2 split of the ByteLevel pre-tokenizer over well-formed UTF-8: the end offset of every piece, in order (tokenizer.cpp)
+void byte_level_split(const char* s, size_t n, std::vector<size_t>& ends);
 std::string trim_swift_whitespaces(const std::string& s);             // trimmingCharacters(in: .whitespaces)
 std::string trimming_special_token_characters(const std::string& s);  // "<|>" stripped from both ends
 float rounded2(float x);                                               // Float.rounded(2)

@@ -137,3 +137,113 @@ def write_kat_tokenizer(folder: str, n_vocab: int = 51865, clean_up_tokenization
         json.dump({"tokenizer_class": "WhisperTokenizer", "clean_up_tokenization_spaces": clean_up_tokenization_spaces,
                    "bos_token": "<|endoftext|>", "eos_token": "<|endoftext|>", "unk_token": "<|endoftext|>"}, f)
     return path
+
+
+# ------------------------------------------------------------------------------------------------ tokenizer fixture with merges
+# A few lines per script, so that a small BPE trained on them merges inside multi-byte characters (Cyrillic, Greek, Hebrew, Arabic: two bytes;
+# Devanagari, Thai, kana, CJK, Hangul: three) as well as across letters.  Written for this fixture; the content carries no meaning for the tests.
+BPE_SAMPLE = """
+The quick brown fox jumps over the lazy dog. She said that they're going to the market, and he didn't know what we've done there.
+It's nine o'clock; I'll be there in 15 minutes, or 1500 seconds - isn't that what you'd call "soon"? I'm sure that the weather is fine.
+Speech recognition turns the sound of a voice into text: the thing that was said, the words that were spoken, and the time of every word.
+Thanks for watching! Thank you for listening. In 1999 and in 2024 there were 365 and 366 days; 3.14159 is not 22/7 (but it is close).
+Le cœur a ses raisons que la raison ne connaît point. Où est la bibliothèque? Ça va très bien, merci beaucoup, à bientôt, mon ami.
+Über den Wolken muß die Freiheit wohl grenzenlos sein. Die Straße ist naß; schöne Grüße aus München, Köln und Zürich.
+El niño comió una piña en la montaña. ¿Cómo estás? ¡Qué día tan bonito! Mañana será otro día, señor, señora y señorita.
+Η γλώσσα είναι το σπίτι του ανθρώπου. Καλημέρα σας, τι κάνετε σήμερα; Ευχαριστώ πολύ, όλα καλά. Η θάλασσα και ο ήλιος της Ελλάδας.
+Быстрая коричневая лиса прыгает через ленивую собаку. Привет, как дела? Спасибо за просмотр! Сегодня хорошая погода, и мы идём гулять.
+Распознавание речи превращает звук голоса в текст: то, что было сказано, слова, которые были произнесены, и время каждого слова.
+שלום עולם, מה שלומך היום? תודה רבה על הצפייה. השועל החום המהיר קופץ מעל הכלב העצלן. הלשון היא הבית של האדם.
+مرحبا بالعالم، كيف حالك اليوم؟ شكرا جزيلا على المشاهدة. الثعلب البني السريع يقفز فوق الكلب الكسول. في عام ١٩٩٩ وفي عام ٢٠٢٤.
+नमस्ते दुनिया, आज आप कैसे हैं? देखने के लिए धन्यवाद। तेज़ भूरी लोमड़ी आलसी कुत्ते के ऊपर कूदती है। भाषा मनुष्य का घर है।
+สวัสดีชาวโลก วันนี้คุณเป็นอย่างไรบ้าง ขอบคุณที่รับชม สุนัขจิ้งจอกสีน้ำตาลกระโดดข้ามสุนัขขี้เกียจ ภาษาคือบ้านของมนุษย์
+こんにちは世界、今日はお元気ですか。ご視聴ありがとうございました。すばやい茶色のキツネはのろまな犬を飛び越えます。テストのテキストです。
+音声認識は声の音を文字に変えます。言われたこと、話された言葉、そしてすべての言葉の時間。日本語と中国語の文字は漢字です。
+你好世界，今天你好吗？感谢您的观看。敏捷的棕色狐狸跳过了懒惰的狗。语音识别把声音变成文字：说过的话和每个词的时间。
+안녕하세요 세계, 오늘 어떻게 지내세요? 시청해 주셔서 감사합니다. 빠른 갈색 여우가 게으른 개를 뛰어넘습니다. 음성 인식은 소리를 글자로 바꿉니다.
+$5, €10, £20 and ¥3000 - prices... "quotes", 'single', (brackets), [square] & {curly}; a+b=c, x*y/z, 50% #tag @name <|not a token|> ♪♪ ♪
+"""
+
+
+def _train_bpe(n_merges: int):
+    """A plain BPE trainer over BPE_SAMPLE in the byte-level alphabet: the most frequent adjacent pair is merged, ties broken by the pair's text, until
+    n_merges merges exist or no pair is left.  Deterministic; the words are split at white space with the leading space kept on the word."""
+    import collections, re
+    b2u = bytes_to_unicode()
+    words = collections.Counter(tuple(b2u[b] for b in w.encode("utf-8"))
+                                for w in re.findall(r" ?[^\W\d_]+| ?\d+| ?[^\s\w]+|\s+", BPE_SAMPLE))
+    words = [[list(w), c] for w, c in sorted(words.items())]
+    merges = []
+    while len(merges) < n_merges:
+        pairs = collections.Counter()
+        for w, c in words:
+            for a, b in zip(w, w[1:]):
+                pairs[(a, b)] += c
+        if not pairs:
+            break
+        best = min(pairs.items(), key=lambda kv: (-kv[1], kv[0]))[0]
+        merges.append(best)
+        for item in words:
+            w, out, i = item[0], [], 0
+            while i < len(w):
+                if i + 1 < len(w) and (w[i], w[i + 1]) == best:
+                    out.append(w[i] + w[i + 1]); i += 2
+                else:
+                    out.append(w[i]); i += 1
+            item[0] = out
+    return merges
+
+
+_BPE_MERGES = {}
+
+
+def bpe_fixture_merges(n_merges: int = 1200):
+    """the fixture's merges, [(left, right), ...] in rank order (trained once per process)"""
+    if n_merges not in _BPE_MERGES:
+        _BPE_MERGES[n_merges] = _train_bpe(n_merges)
+    return list(_BPE_MERGES[n_merges])
+
+
+def write_bpe_tokenizer(folder: str, n_vocab: int = 51865, merges_form: str = "strings", clean_up_tokenization_spaces: bool = True) -> str:
+    """Write a merge-closed `tokenizer.json` + `tokenizer_config.json` into `folder` and return the tokenizer.json path: ids 0..255 are the byte tokens, the
+    merged tokens of bpe_fixture_merges() follow in rank order (every merge's parts and result are in the vocabulary, as `tokenizers` requires), filler
+    that no text encodes to runs up to the end token, and the Whisper added tokens sit at the ids kat_tokenizer_vocab(n_vocab) puts them.
+    merges_form: "strings" writes "a b" lines, "pairs" writes ["a", "b"] as newer `tokenizers` serialises them.  Needs no `tokenizers`."""
+    import json, os
+    if merges_form not in ("strings", "pairs"):
+        raise ValueError(f"merges_form {merges_form!r} (strings or pairs)")
+    _, added = kat_tokenizer_vocab(n_vocab)
+    eot = added[0]["id"]
+    merges = bpe_fixture_merges()
+    assert len(merges) >= 1000, len(merges)
+    tokens = list(bytes_to_unicode().values())
+    seen = set(tokens)
+    for a, b in merges:
+        if a + b not in seen:          # two merges may spell one token; it keeps its first id
+            seen.add(a + b)
+            tokens.append(a + b)
+    i = 0
+    while len(tokens) < eot:
+        tok = f"<filler{i}>"
+        i += 1
+        if tok not in seen:
+            seen.add(tok)
+            tokens.append(tok)
+    vocab = {t: k for k, t in enumerate(tokens)}
+    tj = {
+        "version": "1.0", "truncation": None, "padding": None, "added_tokens": added, "normalizer": None,
+        "pre_tokenizer": {"type": "ByteLevel", "add_prefix_space": False, "trim_offsets": True, "use_regex": True},
+        "post_processor": None,
+        "decoder": {"type": "ByteLevel", "add_prefix_space": True, "trim_offsets": True, "use_regex": True},
+        "model": {"type": "BPE", "dropout": None, "unk_token": None, "continuing_subword_prefix": "", "end_of_word_suffix": "",
+                  "fuse_unk": False, "byte_fallback": False, "ignore_merges": False, "vocab": vocab,
+                  "merges": [f"{a} {b}" for a, b in merges] if merges_form == "strings" else [[a, b] for a, b in merges]},
+    }
+    os.makedirs(folder, exist_ok=True)
+    path = os.path.join(folder, "tokenizer.json")
+    with open(path, "w", encoding="utf-8") as f:
+        json.dump(tj, f, ensure_ascii=False)
+    with open(os.path.join(folder, "tokenizer_config.json"), "w", encoding="utf-8") as f:
+        json.dump({"tokenizer_class": "WhisperTokenizer", "clean_up_tokenization_spaces": clean_up_tokenization_spaces,
+                   "bos_token": "<|endoftext|>", "eos_token": "<|endoftext|>", "unk_token": "<|endoftext|>"}, f)
+    return path
