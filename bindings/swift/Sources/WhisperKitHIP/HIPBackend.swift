@@ -71,6 +71,11 @@ public final class HIPSession {
     /// `.on` = it narrows between step graphs (to 32 / 64 / 128 slots, when a 32-slot batch tile is saved) as its windows reach EOT.  Same results, bit for bit.
     public enum InPassCompaction: Int32 { case off = 0, on = 1 }
     public var inPassCompaction: InPassCompaction = .off { didSet { _ = wh_session_set_inpass_compaction(handle, inPassCompaction.rawValue) } }
+    /// Prompt prefill (wh_session_set_prompt_prefill; no reference behaviour): `.off` (default) = a decode pass steps through every prompt position; `.on` = the
+    /// positions in front of <|startoftranscript|> (the previous-text part) run as virtual slots of a few launches before the token loop, in a session at least
+    /// twice as wide as the pass.  Same results, bit for bit, at any temperature.
+    public enum PromptPrefill: Int32 { case off = 0, on = 1 }
+    public var promptPrefill: PromptPrefill = .off { didSet { _ = wh_session_set_prompt_prefill(handle, promptPrefill.rawValue) } }
     /// Option mixing (wh_session_set_option_mixing): `.off` (default) = transcribeWithOptions runs audios whose options differ in separate groups; `.on` = audios
     /// that agree in the pass-level fields share a device batch and each slot decodes under the options of its class (up to 16 classes per batch).
     public enum OptionMixing: Int32 { case off = 0, on = 1 }

@@ -448,6 +448,26 @@ int wh_session_inpass_compaction(const wh_session* s);
 /* Counters of the session since its creation: narrowings, and the slot-steps they saved (width the pass began with minus the width launched, summed
  * over the decoder steps launched).  wh_session_decode_pass_stats keeps its meaning: slot_steps sums the width actually launched.  Any pointer may be NULL. */
 int wh_session_inpass_compaction_stats(const wh_session* s, int64_t* switches, int64_t* slot_steps_saved);
+/* Prompt prefill.  0 = off (default): a decode pass steps through every position of its prompts, one launch chain per position at the pass's width - under
+ * previous-text conditioning up to 116 positions per window before its first sampled token.  1 = on: a pass of wh_decode_text / wh_decode_text_languages /
+ * wh_decode_text_mixed / wh_decode_text_slot_prompts / wh_transcribe* first runs the prompt positions 0 .. P0 - 1 of all its slots as VIRTUAL SLOTS of a few
+ * launches, then its token loop from step P0.  n_pref = the index of the first <|startoftranscript|> of a slot's prompt (0: no previous-text part);
+ * P0 = 8 floor(min(n_pref over the slots that decode, sample_length) / 8); R = ceil(P0 / ceil(P0 / floor(session slots / pass width))) positions per launch,
+ * each in a slot of its own: pass slot i uses the slots i + width j, j < R (their decode states and self-attention caches; their encoder data are not touched).
+ * A pass is NOT prefilled when P0 is 0 (a slot without a previous-text part switches it off for its pass), when it fills more than half of the session, or
+ * while a progress callback is installed.  Every prefilled position runs the pass's real logits launch, rules kernels and sampler, so a window that samples the
+ * end token inside its prompt or fails first_token_log_prob_threshold ends where it would.  Results are identical to the off mode, bit for bit: tokens,
+ * log-probabilities, steps, fallback fields, no-speech probabilities and all alignment rows; at T > 0 too (a position draws from its slot's random stream
+ * at its own index).  What differs, only for a window that ENDS inside its prompt: the positions of its launch behind the end have run too, so the match
+ * counters of phrase rules / rule sets may count them (the alignment rows they wrote are put back), and the one alternatives row of such a window, which no
+ * result reads, holds whichever of them wrote last.  Composes with both compaction options, option mixing, slot prompts, device rules, rule sets, token alternatives, no-speech
+ * detection and device word alignment.  The beam-search, speculative / guided, forced and custom passes, wh_detect_language and the step API are untouched.
+ * Returns WH_ERR_INVALID_ARGUMENT for a NULL session or a mode other than 0 / 1; the getter returns the mode, -1 for NULL. */
+int wh_session_set_prompt_prefill(wh_session* s, int mode);
+int wh_session_prompt_prefill(const wh_session* s);
+/* Counters of the session since its creation: passes that were prefilled, their prefill launches, the prompt positions those ran (P0 per slot that decodes) and
+ * the windows that ended at a prefilled position.  Any pointer may be NULL. */
+int wh_session_prompt_prefill_stats(const wh_session* s, int64_t* passes, int64_t* launches, int64_t* positions, int64_t* windows_ended_in_prompt);
 /* Option mixing.  0 = off (default): wh_transcribe_batch_with_options runs audios whose options differ in any field but the clip timestamps in
  * separate groups, one after the other.  1 = on: audios share a device batch when the fields that belong to the PASS are equal - temperature,
  * temperature_increment_on_fallback, temperature_fallback_count, seed, use_prefill_prompt, detect_language, word_timestamps, float16_logits,

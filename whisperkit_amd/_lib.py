@@ -205,6 +205,9 @@ SYMBOLS = {
     "wh_session_set_inpass_compaction": (I, [VP, I]),
     "wh_session_inpass_compaction": (I, [VP]),
     "wh_session_inpass_compaction_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "wh_session_set_prompt_prefill": (I, [VP, I]),
+    "wh_session_prompt_prefill": (I, [VP]),
+    "wh_session_prompt_prefill_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "wh_session_set_option_mixing": (I, [VP, I]),
     "wh_session_option_mixing": (I, [VP]),
     "wh_session_option_mixing_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -1063,6 +1063,28 @@ class Session:
         _check(self.lib.wh_session_inpass_compaction_stats(self.handle, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
 
+    PROMPT_PREFILLS = {"off": 0, "on": 1}
+
+    def setPromptPrefill(self, mode: str):
+        """NO REFERENCE BEHAVIOUR (the reference steps through its prompt).  "off" (default) - a decode pass steps through every prompt position, one launch
+        chain per position; "on" - a pass of decodeText / decodeTextMixed / decodeTextSlotPrompts / transcribe* first runs the prompt positions in front of
+        <|startoftranscript|> (the previous-text part), as far as all its windows have them and rounded down to a multiple of 8, as virtual slots of a few
+        launches, then its token loop from there.  Needs a session at least twice as wide as the pass; a window without a previous-text part or an installed
+        progress callback switches it off for the pass.  Results are the same in both modes, bit for bit, at any temperature (wh_session_set_prompt_prefill
+        in include/whisperhip.h says what may differ for a window that ends inside its prompt)."""
+        if mode not in self.PROMPT_PREFILLS:
+            raise ValueError(f"promptPrefill {mode!r}: expected 'on' or 'off'")
+        _check(self.lib.wh_session_set_prompt_prefill(self.handle, self.PROMPT_PREFILLS[mode]))
+
+    def promptPrefill(self) -> str:
+        return {0: "off", 1: "on"}[int(self.lib.wh_session_prompt_prefill(self.handle))]
+
+    def promptPrefillStats(self) -> Tuple[int, int, int, int]:
+        """(prefilled passes, their prefill launches, prompt positions those ran, windows that ended at a prefilled position) since the session was created"""
+        a, b, c, d = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int64()
+        _check(self.lib.wh_session_prompt_prefill_stats(self.handle, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return int(a.value), int(b.value), int(c.value), int(d.value)
+
     NO_SPEECH_DETECTIONS = {"off": 0, "on": 1, "stop": 2}
 
     def setNoSpeechDetection(self, mode: str):

@@ -998,6 +998,21 @@ extern "C" int wh_session_set_inpass_compaction(wh_session* s, int mode) {
     return WH_OK;
 }
 extern "C" int wh_session_inpass_compaction(const wh_session* s) { return s ? s->inpass.mode : -1; }
+extern "C" int wh_session_set_prompt_prefill(wh_session* s, int mode) {
+    if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_prompt_prefill: null session");
+    if (mode != 0 && mode != 1) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_prompt_prefill: mode %d (0 = off, 1 = on)", mode);
+    s->prefill.mode = mode;
+    return WH_OK;
+}
+extern "C" int wh_session_prompt_prefill(const wh_session* s) { return s ? s->prefill.mode : -1; }
+extern "C" int wh_session_prompt_prefill_stats(const wh_session* s, int64_t* passes, int64_t* launches, int64_t* positions, int64_t* windows_ended_in_prompt) {
+    if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_prompt_prefill_stats: null session");
+    whi::store_stat(passes, s->prefill.passes);
+    whi::store_stat(launches, s->prefill.launches);
+    whi::store_stat(positions, s->prefill.positions);
+    whi::store_stat(windows_ended_in_prompt, s->prefill.ended_in_prompt);
+    return WH_OK;
+}
 extern "C" int wh_session_set_option_mixing(wh_session* s, int mode) {
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_option_mixing: null session");
     if (mode != 0 && mode != 1) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_option_mixing: mode %d (0 = off, 1 = on)", mode);

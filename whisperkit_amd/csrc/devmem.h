@@ -160,6 +160,8 @@ struct RuleSetsHostView { int32_t *slots, *stage; };
 struct DtwView { int32_t *rows, *len, *ti, *tj; };
 struct BeamSumView { float* half[2]; };
 struct AlignTmpView { float *rows, *stat; int32_t* flags; };
+template <class Seq> struct PrefillSeqView { Seq *master, *fin; };
+struct PrefillTabView { int32_t *ended, *home, *owner; };
 
 // no-speech detection, by home slot: scoring position | stop threshold | probability | stopped flag | (token, lane divisor)
 template <class V> size_t pack_nospeech(void* base, size_t B, V& v) {
@@ -226,6 +228,19 @@ template <class V> size_t pack_beam_sums(void* base, size_t B, V& v) {
 template <class V> size_t pack_align_tmp(void* base, size_t max_tok, size_t heads, size_t ctx, V& v) {
     Pack c(base);
     c.take(v.rows, max_tok * heads * ctx); c.take(v.stat, 2 * heads * ctx); c.take(v.flags, 256);
+    return c.size();
+}
+
+// prompt prefill, the decode states: master states [B] | finished states [B]
+template <class V> size_t pack_prefill_seq(void* base, size_t B, V& v) {
+    Pack c(base);
+    c.take(v.master, B); c.take(v.fin, B);
+    return c.size();
+}
+// ... and its tables: ended flags [B] | home slot of every virtual slot [B] | row -> owner rows [B][max_tok]
+template <class V> size_t pack_prefill_tab(void* base, size_t B, size_t max_tok, V& v) {
+    Pack c(base);
+    c.take(v.ended, B); c.take(v.home, B); c.take(v.owner, B * max_tok);
     return c.size();
 }
 

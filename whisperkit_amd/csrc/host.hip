@@ -21,6 +21,7 @@
 #include "forced_plan.h"
 #include "internal.h"
 #include "knobs.h"
+#include "prefill_plan.h"
 #include "transcribe_plan.h"
 
 using namespace wh;
@@ -270,6 +271,7 @@ void finalize_decoding_result(const SeqState& sq, const wh_decoding_options* opt
 }  // namespace whi
 
 constexpr int kStepsPerGraph = 8;
+static_assert(kStepsPerGraph == plan::kPrefillStepsPerGraph, "a prefilled pass resumes on a step-graph boundary (prefill_plan.h)");
 
 static bool use_graphs() { return !knob::once<knob::WH_NO_GRAPH>(); }
 
@@ -564,7 +566,8 @@ static int inpass_narrow(wh_session* s, PassLayout& L, const SeqState* snap, con
 
 // L: the pass may narrow (decode_text_impl with the option on), or null.  A pass that narrowed ends with seq_host in HOME-slot terms (entry b = the final
 // state of home slot b, for the home slots the pass decoded; the caller fills in the others); otherwise seq_host holds the `batch` compact slots as ever.
-static int run_token_loop(wh_session* s, int batch, int loop_count, PassLayout* L = nullptr) {
+// first_step: the step the loop begins at - 0, or the P0 of a prefilled pass (prefill_run below: a multiple of kStepsPerGraph; every live slot stands there).
+static int run_token_loop(wh_session* s, int batch, int loop_count, PassLayout* L = nullptr, int first_step = 0) {
     // every slot's state lives on the device; the host only replays step graphs and polls the done flags
     int width = batch;                                   // (changes only through inpass_narrow)
     auto all_done_in = [](const SeqState* q, int n) { for (int b = 0; b < n; ++b) if (q[b].active && !q[b].done) return false; return true; };
@@ -582,7 +585,7 @@ static int run_token_loop(wh_session* s, int batch, int loop_count, PassLayout* 
     };
     if (s->progress_cb) {
         // with a callback installed the host needs whole snapshots: no run-ahead, one synchronisation per 8 steps
-        for (int step = 0; step < loop_count; step += kStepsPerGraph) {
+        for (int step = first_step; step < loop_count; step += kStepsPerGraph) {
             CHECK_CANCEL(s);
             hipGraphExec_t exec = nullptr;
             if (use_graphs()) { int r = get_step_graph(s, width, step, &exec); if (r) return r; }
@@ -604,19 +607,19 @@ static int run_token_loop(wh_session* s, int batch, int loop_count, PassLayout* 
         return final_read();
     }
     if (use_graphs()) {
-        const int n_graphs = (loop_count + kStepsPerGraph - 1) / kStepsPerGraph;
+        const int n_graphs = (loop_count + kStepsPerGraph - 1) / kStepsPerGraph, g0 = first_step / kStepsPerGraph;
         // WH_DBG_HOST=1: host-side cost of the replay loop (time inside hipGraphLaunch vs waiting for the device), one line per decode
         const bool dbg_host = knob::once<knob::WH_DBG_HOST>();
         double t_launch = 0.0, t_wait = 0.0;
         auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
         const double t_begin = dbg_host ? now() : 0.0;
-        struct Report { bool on; double *l, *w, t0; int n; decltype(now)* clk; ~Report() { if (on) fprintf(stderr, "[wh host] decode loop: %d graph launches, %.2f ms inside hipGraphLaunch, %.2f ms waiting for the device, %.2f ms total\n", n, *l * 1e3, *w * 1e3, ((*clk)() - t0) * 1e3); } } report{dbg_host, &t_launch, &t_wait, t_begin, n_graphs, &now};
+        struct Report { bool on; double *l, *w, t0; int n; decltype(now)* clk; ~Report() { if (on) fprintf(stderr, "[wh host] decode loop: %d graph launches, %.2f ms inside hipGraphLaunch, %.2f ms waiting for the device, %.2f ms total\n", n, *l * 1e3, *w * 1e3, ((*clk)() - t0) * 1e3); } } report{dbg_host, &t_launch, &t_wait, t_begin, n_graphs - g0, &now};
         // A pass that may narrow alternates between two snapshot buffers and remembers the layout each snapshot was taken in: the copy behind graph g
         // can be of another layout than the one behind graph g - 1 that the host is looking at.  Otherwise one buffer, as ever.
         SeqState* const snap[2] = {s->seq_host, L ? s->inpass.seq_snap : s->seq_host};
         std::vector<int32_t> snap_home[2];
         int snap_width[2] = {width, width};
-        for (int g = 0; g < n_graphs; ++g) {
+        for (int g = g0; g < n_graphs; ++g) {
             if (cancelled(s)) { hipStreamSynchronize(s->st); return set_error(WH_ERR_CANCELLED, "decodeText: cancelled through the session's cancel flag"); }
             hipGraphExec_t exec;
             int r = get_step_graph(s, width, g * kStepsPerGraph, &exec);
@@ -631,7 +634,7 @@ static int run_token_loop(wh_session* s, int batch, int loop_count, PassLayout* 
             WH_HIP(hipEventRecord(s->ev[g & 1], s->st));
             snap_width[g & 1] = width;
             if (L) snap_home[g & 1] = L->home;
-            if (g >= 1) {
+            if (g > g0) {
                 const double tb = dbg_host ? now() : 0.0;
                 WH_HIP(hipEventSynchronize(s->ev[(g - 1) & 1]));
                 if (dbg_host) t_wait += now() - tb;
@@ -645,7 +648,7 @@ static int run_token_loop(wh_session* s, int batch, int loop_count, PassLayout* 
             }
         }
     } else {
-        for (int step = 0; step < loop_count; ++step) {
+        for (int step = first_step; step < loop_count; ++step) {
             DecodeBuffers db = whi::decode_buffers(s, width, step);
             launch_pass_step(s, db, step);
             WH_CHECK_LAUNCH();
@@ -659,6 +662,74 @@ static int run_token_loop(wh_session* s, int batch, int loop_count, PassLayout* 
         }
     }
     return final_read();
+}
+
+// ---- prompt prefill (wh_session_set_prompt_prefill; NO REFERENCE BEHAVIOUR; prefill_plan.h, prefill.hip)
+// the only place that allocates the feature's memory (the first pass that is prefilled)
+static int prefill_ensure(wh_session* s) {
+    wh_session::Prefill& f = s->prefill;
+    const size_t B = (size_t)s->B;
+    mem::PrefillSeqView<SeqState> mq{};
+    mem::PrefillTabView mt{};
+    if (!f.seq) WH_HIP(s->mem.alloc(&f.seq, mem::pack_prefill_seq(nullptr, B, mq) / sizeof(SeqState), false));
+    if (!f.tab) WH_HIP(s->mem.alloc(&f.tab, mem::pack_prefill_tab(nullptr, B, kMaxTok, mt) / sizeof(int32_t), false));
+    mem::pack_prefill_seq(f.seq, B, f.q); mem::pack_prefill_tab(f.tab, B, kMaxTok, f.t);
+    if (s->align_enabled && f.align_heads != s->n_align_alloc) {      // (every pass ends drained: no launch reads the old buffer)
+        s->mem.release(f.align_keep);
+        f.align_keep = nullptr; f.align_heads = 0;
+        WH_HIP(s->mem.alloc(&f.align_keep, B * (size_t)s->n_align_alloc * kCtx, false));
+        f.align_heads = s->n_align_alloc;
+    }
+    return WH_OK;
+}
+// Behind step 4's upload of the states (s->seq holds the pass's `width` slots at step 0, their f_rules computed): the positions 0 .. pp.p0 - 1 of every
+// live slot in pp.launches eager decoder launches under the pass's own sampler, rules kernels and random streams, then the commit.  On return the device holds
+// what the token loop would hold at step pp.p0 - every SeqState, the cache rows and the alignment rows of the pass slots - and s->pass is what it was.
+// Nothing waits: the launch parameters are kernel arguments (no host descriptor, so no staging), and the token loop's first snapshot is the first look.
+static int prefill_run(wh_session* s, const plan::PrefillPlan& pp, int width, int n_live) {
+    if (int r = prefill_ensure(s)) return r;
+    const wh_session::Prefill& f = s->prefill;
+    const int B = s->B, spw0 = s->use_xabs ? s->xabs.spw : 1;
+    const PassState keep = s->pass;
+    const int32_t* const pass_home = keep.mapped ? s->slots.home_dev : nullptr;      // a compacted pass: compact slot i stands for home slot home_dev[i]
+    WH_HIP(hipMemcpyAsync(f.q.master, s->seq, sizeof(SeqState) * (size_t)width, hipMemcpyDeviceToDevice, s->st));
+    WH_HIP(hipMemsetAsync(f.t.ended, 0, sizeof(int32_t) * (size_t)width, s->st));
+    // (a pass that records alignment rows: the rows a launch may write are kept in front of it, and put back where it ran behind a position that ended its window)
+    auto align_rows = [&](int prev_first, int prev_n, int first, int n) {
+        if (s->align_enabled) launch_prefill_align(s->seq, s->align, f.align_keep, pass_home, width, pp.ring, prev_first, prev_n, first, n, B, s->n_align_alloc, s->st);
+    };
+    int prev_first = 0, prev_n = 0;
+    for (int k = 0; k < pp.launches; ++k) {
+        if (cancelled(s)) {
+            // the ring members beyond the pass's width are left as the commit leaves them, inactive zero states: no slot outside the pass stays armed
+            (void)hipMemsetAsync(s->seq + width, 0, sizeof(SeqState) * (size_t)width * (size_t)(pp.ring - 1), s->st);
+            hipStreamSynchronize(s->st); s->pass = keep;
+            return set_error(WH_ERR_CANCELLED, "decodeText: cancelled through the session's cancel flag");
+        }
+        const int first = plan::prefill_launch_first(k, pp.ring), n = plan::prefill_launch_count(k, pp.ring, pp.p0), vwidth = width * n;
+        align_rows(prev_first, prev_n, first, n);
+        launch_prefill_arm(s->cfg_dev, f.q.master, f.q.fin, f.t.ended, s->seq, f.t.owner, f.t.home, pass_home, width, pp.ring, first, n, prev_n, B, keep.mixed, s->st);
+        // the mapped instantiations, as the forced pass: the slots per absorbed-attention workgroup of the ladder rung that holds the virtual width (results do not depend on it)
+        const plan::CompactPassPlan cp = plan::compact_pass_plan(vwidth, B, B, spw0);
+        s->pass.mapped = true; s->pass.spw = cp.compact ? cp.spw : spw0;
+        DecodeBuffers db = whi::decode_buffers(s, vwidth, first + n - 1);
+        db.self_owner = f.t.owner; db.owner_slots = B; db.slot_home = f.t.home;
+        launch_decoder_step(db, s->cfg_dev, s->suppress_dev, true, s->st, nullptr, whi::logit_rules_step_args(s), whi::phrase_rules_step_args(s));
+        WH_CHECK_LAUNCH();
+        s->pass = keep;
+        s->count.slot_steps += vwidth;
+        if (keep.rules & plan::kRulesPassLogitKernel) s->rules.lr_launches += 1;
+        if (keep.rules & plan::kRulesPassPhraseKernel) s->rules.pr_launches += 1;
+        if (keep.rules & plan::kRulesPassSetAware) s->rules.rs_launches += 1;
+        prev_first = first; prev_n = n;
+    }
+    align_rows(prev_first, prev_n, 0, 0);
+    launch_prefill_commit(f.q.master, f.q.fin, f.t.ended, s->seq, s->self_k, s->self_v, width, pp.ring, pp.p0, prev_n, B, s->m->dims.n_text_head, s->m->dims.n_text_layer, s->st);
+    WH_CHECK_LAUNCH();
+    plan::PrefillCounters c;
+    c.pass(pp, n_live);
+    s->prefill.passes += c.passes; s->prefill.launches += c.launches; s->prefill.positions += c.positions;
+    return WH_OK;
 }
 
 // What a decode pass is asked to do, in the session's home-slot terms: the option classes, each slot's class, the prompts at their granularity and what the
@@ -873,7 +944,20 @@ static int decode_text_impl(wh_session* s, const wh_special_tokens* st, const Pa
         WH_HIP(hipStreamSynchronize(s->st));
         return WH_OK;
     };
-    r = run_token_loop(s, width, std::max(loop_count, 0), s->inpass.mode == 1 ? &lay : nullptr);
+    // prompt prefill (wh_session_set_prompt_prefill 1; NO REFERENCE BEHAVIOUR): the prompt positions in front of every live slot's
+    // <|startoftranscript|>, as far as they are common to all of them and end on a graph boundary, run as virtual slots of a few launches; the loop begins at P0.
+    // Not under a progress callback (its snapshots are per 8 steps from step 0), and not where the planner says no (P0 = 0, or the pass fills the session)
+    plan::PrefillPlan pp = plan::prefill_plan(0, width, s->B);
+    if (s->prefill.mode == 1 && !s->progress_cb) {
+        std::vector<int32_t> n_pref((size_t)batch), live((size_t)batch);
+        for (int b = 0; b < batch; ++b) {
+            live[(size_t)b] = is_live(b);
+            n_pref[(size_t)b] = plan::prefill_prompt_range(prompt_of(b).tokens, prompt_of(b).n, st->start_of_transcript_token);
+        }
+        pp = plan::prefill_plan(plan::prefill_range(n_pref.data(), live.data(), batch, std::max(loop_count, 0)), width, s->B);
+    }
+    if (pp.on) r = prefill_run(s, pp, width, n_live);
+    if (!r) r = run_token_loop(s, width, std::max(loop_count, 0), s->inpass.mode == 1 ? &lay : nullptr, pp.p0);
     if (r && lay.switches > 0) {
         // an error (a cancel, a failed capture) behind a switch: the device states lie in the compact layout with the finished windows parked.  Put
         // them back by home slot as far as the device still answers, so that a step-API or wh_measure_kernels call that follows sees every slot in
@@ -886,6 +970,8 @@ static int decode_text_impl(wh_session* s, const wh_special_tokens* st, const Pa
     }
     if (r) return r;
     if (lay.switches > 0 || cp.compact) { r = home_layout(); if (r) return r; }
+    // (a window that ends keeps the token_index it ended at: one below P0 ended at a position the prefill ran)
+    for (int b = 0; pp.on && b < batch; ++b) s->prefill.ended_in_prompt += s->seq_host[b].active && s->seq_host[b].done && s->seq_host[b].token_index < pp.p0;
     // ---- 6. collect what the modes recorded, and every decoded slot's result
     const bool ns_on = !ns_opts.empty();
     if (ns_on) { r = whi::nospeech_collect(s, batch, ns_opts.data()); if (r) return r; }

@@ -212,6 +212,19 @@ struct wh_session {
         wh_session* draft = nullptr; int draft_k = 0;      // wh_session_set_draft: not owned
         long long passes = 0, rounds = 0, positions = 0, accepted = 0;      // wh_session_speculative_stats
     } spec;
+    // prompt prefill (wh_session_set_prompt_prefill: host.hip prefill_ensure, prefill_run, prefill_plan.h, prefill.hip): mode 0 = off, 1 = an ordinary decode pass runs
+    // the first P0 prompt positions of its slots as virtual slots before its token loop.  Everything is allocated by the first pass that is prefilled: seq = master
+    // states [B] | finished states [B] (device; pack_prefill_seq), tab = ended flags [B] | home slots [B] | row -> owner rows [B][kMaxTok] (device; pack_prefill_tab).
+    // The virtual slots read tab's home slots, not the session's slot table: a compacted pass keeps its own.  align_keep [B][align_heads][kCtx] (device): one
+    // alignment row per virtual slot, kept across a launch; allocated by the first prefilled pass that records alignment rows, again when the head count changed.
+    struct Prefill {
+        int mode = 0;
+        wh::SeqState* seq = nullptr; int32_t* tab = nullptr;
+        float* align_keep = nullptr; int align_heads = 0;
+        wh::mem::PrefillSeqView<wh::SeqState> q{};
+        wh::mem::PrefillTabView t{};
+        long long passes = 0, launches = 0, positions = 0, ended_in_prompt = 0;      // wh_session_prompt_prefill_stats
+    } prefill;
     // no-speech detection (wh_session_set_no_speech_detection: host.hip nospeech_ensure, nospeech_arm, nospeech_plan.h, nospeech.hip): mode 0 = off, 1 = on, 2 = on + stop.
     // dev (device, zero-filled, by home slot; what args points into) and its pinned mirror host are allocated by the first pass that runs with the mode on and cut
     // by pack_nospeech.  pass.ns holds while a pass runs whose steps lo .. hi carry the logits store and the kernel; (-1, -1) otherwise, and always with the mode off.

@@ -445,6 +445,21 @@ void launch_spec_arm(const SamplerCfg* cfg_dev, const SeqState* master, const Sp
 void launch_spec_arm_draft(const SamplerCfg* draft_cfg_dev, const SeqState* master, const SpecDesc* desc, SeqState* draft_seq, int n_audio, hipStream_t st);
 // accept: one wave per audio - the longest accepted prefix of the round, master[a] = the virtual slot's state after it
 void launch_spec_accept(SeqState* master, const SeqState* seq, SpecRound* io, int n_audio, int K, hipStream_t st);
+// prompt prefill (prefill.hip, prefill_plan.h): the launch that runs the positions first .. first + n - 1 of every pass slot i < width in the ring members
+// i + width j.  arm: master[i] (the state at position `first`) -> the whole SeqState of the members, their owner rows [slot][kMaxTok] and home slots
+// (pass_home [width], or null: pass slot i is its own home), master[i] advanced to first + n; before that, fin[i] / ended[i] keep what a position of the
+// launch before (prev_n positions; 0: none) left when it ended the window.  mixed: DecodeBuffers.mixed
+void launch_prefill_arm(const SamplerCfg* cfg_dev, SeqState* master, SeqState* fin, int* ended, SeqState* seq, int* owner, int* slot_home, const int* pass_home,
+                        int width, int ring, int first, int n, int prev_n, int n_slots, int mixed, hipStream_t st);
+// align, in front of arm while the pass records alignment rows (align: [n_slots][kMaxTok][n_align][kCtx], keep: [n_slots][n_align][kCtx]): the rows the launch
+// before (prev_n positions from prev_first) wrote behind a position that ended its window are put back, the rows this launch may write (n positions from
+// first; n = 0 behind the last launch) are kept
+void launch_prefill_align(const SeqState* seq, float* align, float* keep, const int* pass_home, int width, int ring, int prev_first, int prev_n, int first, int n,
+                          int n_slots, int n_align, hipStream_t st);
+// commit, behind the last launch (last_n positions): seq[i] = the state the first finished position left, or else the last position's; the cache rows
+// q < p0 the ring members hold move to slot i (self_k / self_v: [n_layer][n_slots][n_head][kMaxTok][kHeadDim])
+void launch_prefill_commit(const SeqState* master, const SeqState* fin, const int* ended, SeqState* seq, f16* self_k, f16* self_v, int width, int ring, int p0,
+                           int last_n, int n_slots, int n_head, int n_layer, hipStream_t st);
 // standalone filter / sampler entry points (KAT surface of the C ABI)
 void launch_filter_only(const SamplerCfg* cfg_dev, const int* suppress_dev, SeqState* seq, float* logits, int n_vocab, hipStream_t st);
 void launch_sample_only(const SamplerCfg* cfg_dev, SeqState* seq, float* logits, int n_vocab, int counter, int* token_out, float* logprob_out, hipStream_t st);
