@@ -33,27 +33,37 @@ struct Seq {      // kernels.h SeqState
 constexpr int32_t SOT = 50258, PREV = 50361, EN = 50259, DE = 50261, V = 51865;
 
 static void check_key() {
-    using whi::step_graph_key;
+    using whi::step_graph_key; using wh::SlotCfg;
     // the plain pass: every pass-derived field is 0 (and n_align with alignment off)
     const WhGraphKey plain = step_graph_key(PassState{}, 8, false, 6, true, 16, false, 0);
     CHECK(plain.batch == 8 && plain.align == 0 && plain.fused == 1 && plain.n_align == 0 && plain.self_rows == 16 && plain.gate == 0);
-    CHECK(plain.mapped == 0 && plain.spw == 0 && plain.owner == 0 && plain.mixed == 0 && plain.ns_mask == 0 && plain.rules == 0 && plain.alternatives == 0);
+    CHECK(plain.mapped == 0 && plain.spw == 0 && plain.owner == 0 && plain.grain == SlotCfg::Shared && plain.ns_mask == 0 && plain.rules == 0 && plain.alternatives == 0);
     CHECK(step_graph_key(PassState{}, 8, true, 6, true, 16, true, 5).n_align == 6);
     // all 13 fields by name: a 14th field stops the compilation here
-    WhGraphKey k = step_graph_key(PassState{true, 2, true, true, {0, 0}, 3, 4}, 40, true, 6, false, 24, true, 1);
-    auto& [batch, align, fused, n_align, self_rows, gate, mapped, spw, owner, mixed, ns_mask, rules, alternatives] = k;
-    int* const field[13] = {&batch, &align, &fused, &n_align, &self_rows, &gate, &mapped, &spw, &owner, &mixed, &ns_mask, &rules, &alternatives};
+    WhGraphKey k = step_graph_key(PassState{true, 2, true, SlotCfg::PerClass, {0, 0}, 3, 4}, 40, true, 6, false, 24, true, 1);
+    auto& [batch, align, fused, n_align, self_rows, gate, mapped, spw, owner, grain, ns_mask, rules, alternatives] = k;
+    static_assert(sizeof(WhGraphKey) == 13 * sizeof(int) && sizeof(grain) == sizeof(int), "the grain is one of 13 words");
+    int* const field[12] = {&batch, &align, &fused, &n_align, &self_rows, &gate, &mapped, &spw, &owner, &ns_mask, &rules, &alternatives};      // (the grain: below)
     CHECK(&self_rows == &k.self_rows && field[4] == &k.self_rows);
-    CHECK(mapped == 1 && spw == 2 && owner == 1 && mixed == 1 && ns_mask == 1 && rules == 3 && alternatives == 4 && n_align == 6 && gate == 1);
+    CHECK(mapped == 1 && spw == 2 && owner == 1 && grain == SlotCfg::PerClass && ns_mask == 1 && rules == 3 && alternatives == 4 && n_align == 6 && gate == 1);
     const WhGraphKey base = k;
     CHECK(!(base < base) && base.same_cfg(base) && !(plain < plain));
-    for (int i = 0; i < 13; ++i) {
+    auto check_differs = [&](const WhGraphKey& other, bool row_bound) {
+        CHECK((base < other) != (other < base));      // unequal, in exactly one direction
+        CHECK(!(other < other));
+        CHECK(base.same_cfg(other) == row_bound && other.same_cfg(base) == row_bound);      // only the row bound stays inside a configuration
+    };
+    for (int i = 0; i < 12; ++i) {
         *field[i] += 1;
         const WhGraphKey other = k;
         *field[i] -= 1;
-        CHECK((base < other) != (other < base));      // unequal, in exactly one direction
-        CHECK(!(other < other));
-        CHECK(base.same_cfg(other) == (i == 4) && other.same_cfg(base) == (i == 4));      // only the row bound stays inside a configuration
+        check_differs(other, i == 4);
+    }
+    for (SlotCfg g : {SlotCfg::Shared, SlotCfg::PerSlotPrompt}) {      // the 13th field, to either side of PerClass
+        grain = g;
+        const WhGraphKey other = k;
+        grain = SlotCfg::PerClass;
+        check_differs(other, false);
     }
     // spw enters only for a mapped pass
     PassState a, b;
@@ -64,14 +74,14 @@ static void check_key() {
     const WhGraphKey ma = step_graph_key(a, 8, false, 0, true, 8, false, 0), mb = step_graph_key(b, 8, false, 0, true, 8, false, 0);
     CHECK(((ma < mb) != (mb < ma)) && !ma.same_cfg(mb) && ma.spw == 1 && mb.spw == 4);
     // every other switch of the state reaches the key
-    for (int f = 0; f < 4; ++f) {
+    for (int f = 0; f < 5; ++f) {
         PassState p;
-        if (f == 0) p.owner = true; else if (f == 1) p.mixed = true; else if (f == 2) p.rules = 2; else p.alt = 3;
+        if (f == 0) p.owner = true; else if (f == 1) p.grain = SlotCfg::PerClass; else if (f == 2) p.rules = 2; else if (f == 3) p.alt = 3; else p.grain = SlotCfg::PerSlotPrompt;
         const WhGraphKey kp = step_graph_key(p, 8, false, 0, true, 8, false, 0);
         CHECK((kp < ka) != (ka < kp));
     }
     const PassState d;
-    CHECK(!d.mapped && d.spw == 1 && !d.owner && !d.mixed && d.ns.lo == -1 && d.ns.hi == -1 && d.rules == 0 && d.alt == 0);
+    CHECK(!d.mapped && d.spw == 1 && !d.owner && d.grain == SlotCfg::Shared && d.ns.lo == -1 && d.ns.hi == -1 && d.rules == 0 && d.alt == 0);
 }
 
 struct Case { std::vector<int32_t> prompt; int lang_pos; };

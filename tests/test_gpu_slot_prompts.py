@@ -180,7 +180,7 @@ def _forty_prompts(sess, words=False):
 @pytest.mark.parametrize("model", ["en", "ml"])
 @pytest.mark.parametrize("temperature", [0.0, 0.6])
 def test_forty_prompts_in_one_pass(model, temperature):
-    """T = 0: the fused sampler (logits epilogue + sampler_final_slot_prompt_kernel); T = 0.6 / top-5: sampler_kernel<1, 1, 3, 0>.  Timestamps are on in both
+    """T = 0: the fused sampler (logits epilogue + sampler_final_kernel<PerSlotPrompt>); T = 0.6 / top-5: sampler_kernel<PassStep<PerSlotPrompt>>.  Timestamps are on in both
     models: the English-only prompt has no task token, so sampleBegin IS the prompt index; the multilingual one takes max(task + 1, prompt index)."""
     sess = _en() if model == "en" else _ml()
     prompts, classes, cls = _forty_prompts(sess)

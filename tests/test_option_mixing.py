@@ -93,7 +93,7 @@ def test_python_surface_and_header_carry_the_option():
 
 def test_library_carries_the_mixed_kernels_and_the_build_tracks_their_sources():
     blob = open(os.path.join(os.path.dirname(L.__file__), "libwhisperhip.so"), "rb").read()
-    assert b"sampler_final_mixed_kernel" in blob and b"rules_init_mixed_kernel" in blob
-    assert b"dec32_proj_kernelILi5E" in blob and b"sampler_kernelILi1ELi1ELi2E" in blob       # P32_LOGITS_MIXED, DO_ADVANCE = 2
+    assert b"sampler_final_kernelILNS_7SlotCfgE1E" in blob and b"rules_init_kernelILNS_7SlotCfgE1E" in blob      # SlotCfg::PerClass
+    assert b"dec32_proj_kernelILi5E" in blob and b"sampler_kernelINS_11SamplerFormILb1ELNS_4DrawE1ELb1ELNS_7SlotCfgE1E" in blob       # P32_LOGITS_MIXED, PassStep<PerClass>
     mk = open(os.path.join(ROOT, "whisperkit_amd", "csrc", "Makefile")).read()
-    assert "option_mix.h" in mk and "sampler_final.inc" in mk
+    assert "option_mix.h" in mk and "decoder.hip" in mk      # the enum's header, the forms' source

@@ -215,7 +215,8 @@ def test_python_surface_lib_and_header_are_in_step():
 
 def test_library_carries_the_slot_prompt_kernels_and_the_build_tracks_their_sources():
     blob = open(os.path.join(os.path.dirname(L.__file__), "libwhisperhip.so"), "rb").read()
-    assert b"sampler_final_slot_prompt_kernel" in blob and b"rules_init_slot_prompt_kernel" in blob
-    assert b"sampler_kernelILi1ELi1ELi3E" in blob and b"sampler_kernelILi1ELi2ELi3E" in blob       # DO_ADVANCE = 3, sampling and recording
+    assert b"sampler_final_kernelILNS_7SlotCfgE2E" in blob and b"rules_init_kernelILNS_7SlotCfgE2E" in blob      # SlotCfg::PerSlotPrompt
+    for draw in (b"1", b"2"):      # PassStep / RecordingPassStep <PerSlotPrompt>
+        assert b"sampler_kernelINS_11SamplerFormILb1ELNS_4DrawE" + draw + b"ELb1ELNS_7SlotCfgE2E" in blob, draw
     mk = open(os.path.join(ROOT, "whisperkit_amd", "csrc", "Makefile")).read()
-    assert "prompt_carry_plan.h" in mk and "sampler_final.inc" in mk
+    assert "prompt_carry_plan.h" in mk and "option_mix.h" in mk and "decoder.hip" in mk      # ..., the enum's header, the forms' source

@@ -172,7 +172,8 @@ def test_python_surface_swift_shim_build_and_documents():
     r = api.DecodingResult([1], [0.0], 0.0, 0.0, 0.0, 1.0, -1, None, False, False, 1)
     assert r.alternatives is None and r.entropies is None
     blob = open(os.path.join(os.path.dirname(L.__file__), "libwhisperhip.so"), "rb").read()
-    for name in (b"sampler_kernelILi1ELi2ELi1ELi0E", b"sampler_kernelILi1ELi2ELi2ELi0E", b"sampler_kernelILi0ELi2ELi0ELi0E"):      # DO_SAMPLE = 2: plain, mixed, alone
+    form = b"sampler_kernelINS_11SamplerFormILb%dELNS_4DrawE2ELb%dELNS_7SlotCfgE%dELb0E"      # Draw::TokenAndAlternatives: (filter, advance, SlotCfg), no write-back
+    for name in (form % (1, 1, 0), form % (1, 1, 1), form % (0, 0, 0)):      # RecordingPassStep<Shared>, <PerClass>, AlternativesOnly
         assert name in blob, name
     assert "alternatives_plan.h" in open(os.path.join(ROOT, "whisperkit_amd", "csrc", "Makefile")).read()
     swift = open(os.path.join(ROOT, "bindings", "swift", "Sources", "WhisperKitHIP", "HIPBackend.swift")).read()

@@ -771,7 +771,7 @@ DecodeBuffers decode_buffers(wh_session* s, int batch, int max_position) {
     db.align = s->align_enabled ? s->align : nullptr; db.align_slot = m->align_slot_dev; db.n_align = s->n_align_alloc;
     db.d32 = &s->d32; db.x = s->d32.x; db.q = s->d32.q;
     if (s->use_xabs) { s->xabs.enc = s->enc16; db.xabs = &s->xabs; }
-    const PassState& p = s->pass; db.mixed = p.mixed;      // what the running pass switches on (pass_state.h)
+    const PassState& p = s->pass; db.grain = p.grain;      // what the running pass switches on (pass_state.h)
     if (p.mapped) {             // compacted pass (host.hip decode_text_impl)
         db.slot_home = s->slots.home_dev;
         if (s->use_xabs) { s->xabs_pass = s->xabs; s->xabs_pass.spw = p.spw; db.xabs = &s->xabs_pass; }

@@ -29,6 +29,7 @@
 // same bits alone or among 31 others (tests/test_gpu_dims.py).
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "alternatives_plan.h"
 #include "dec_shared.h"
@@ -442,38 +443,75 @@ __device__ __forceinline__ float uniform01(unsigned long long seed, int counter)
     return (float)(z >> 40) * (1.0f / 16777216.0f);
 }
 
-// MODE bit 0: apply filters; bit 1: sample; bit 2: advance decodeText state; bit 3: write filtered logits back
-// TOPK > 0 (beam search, BeamSearchTokenSampler.update's device part, no reference behaviour): after the filters, the log-softmax of the
-// row and its TOPK best entries, descending, ties to the lower id (openai/whisper decoding.py:361 logprobs[idx].topk(beam_size + 1)) go to
-// logprob_out / token_out[b * kBeamTopK + k]; the row stays in registers (the two-kernel form re-read it K + 3 times through L2).
-// DO_ADVANCE == 2 (a mixed pass, option_mix.h): advance, with cfgp and suppress the session's per-class tables - the slot reads the entries of its class
-// (seq_class of SeqState.rng_lane) and draws from the lane in the word's low bits.  A value of an existing parameter, so that every other instantiation
-// keeps its name and its instructions (tools/device_code_hash.py): only mixed passes launch <1, 1, 2, 0>.
-// DO_SAMPLE == 2 (token alternatives, alternatives_plan.h): sample, and - when the step appends its token - record the n best entries of the
-// log-softmax the token was drawn from and the entropy of that distribution, from the registers that hold the filtered, scaled row.  token_out / logprob_out are
-// the buffers by home slot (ids; log-probabilities with the entropies behind them), counter_override carries n and the buffers' slot count.  Again a value of an
-// existing parameter: <1, 2, 1, 0> (a plain pass), <1, 2, 2, 0> (a mixed pass) and <0, 2, 0, 0> (the kernel-alone entry point) are the only ones launched.
-// DO_ADVANCE == 3 (a per-slot-prompt pass): the mixed form, with the timestamp rules' sampleBegin taken from the slot's own prompt_len
-// (slot_prompt_cfg) - the class entry's initial_prompt_index is not read.  <1, 1, 3, 0> and <1, 2, 3, 0> are the ones launched.
-// the SamplerCfg of a slot that brings its own prompt: its class's entry with the slot's prompt length as the timestamp rules' sampleBegin
-__device__ __forceinline__ SamplerCfg slot_prompt_cfg(const SamplerCfg& cls_cfg, const SeqState* sq) {
-    SamplerCfg c = cls_cfg;
-    c.initial_prompt_index = sq->prompt_len;
-    return c;
+// The SamplerCfg slot `sq` runs under (SlotCfg, option_mix.h): entry 0 of the table at cfgp, the entry of the slot's class (seq_class of SeqState.rng_lane), or
+// that entry with the slot's own prompt length as the timestamp rules' sampleBegin - the class entry's initial_prompt_index is then not read.
+// In two steps, the table entry and what the slot runs under given its entry, because sampler_kernel reads its row under the entry and takes the second step
+// only for the rules and the state; a kernel without that split writes slot_cfg<G>(slot_entry<G>(cfgp, sq), sq).
+template <SlotCfg G>
+__device__ __forceinline__ const SamplerCfg& slot_entry(const SamplerCfg* cfgp, const SeqState* sq) {
+    return cfgp[G == SlotCfg::Shared ? 0 : seq_class(sq->rng_lane)];
 }
-template <int DO_FILTER, int DO_SAMPLE, int DO_ADVANCE, int WRITE_BACK, int TOPK = 0>
+template <SlotCfg G>
+__device__ __forceinline__ decltype(auto) slot_cfg(const SamplerCfg& entry, const SeqState* sq) {      // (the entry itself, by reference, unless the slot brings its prompt)
+    if constexpr (G == SlotCfg::PerSlotPrompt) {
+        SamplerCfg c = entry;
+        c.initial_prompt_index = sq->prompt_len;
+        return c;
+    } else {
+        return (entry);
+    }
+}
+// host side: f(std::integral_constant<SlotCfg, g>{}) - the one place a run-time SlotCfg picks a kernel's form
+template <class F> static void with_slot_cfg(SlotCfg g, F&& f) {
+    switch (g) {
+        case SlotCfg::Shared: return f(std::integral_constant<SlotCfg, SlotCfg::Shared>{});
+        case SlotCfg::PerClass: return f(std::integral_constant<SlotCfg, SlotCfg::PerClass>{});
+        case SlotCfg::PerSlotPrompt: return f(std::integral_constant<SlotCfg, SlotCfg::PerSlotPrompt>{});
+    }
+}
+
+// The forms of sampler_kernel: what one launch does with a slot's logits row, in the order the kernel does it.
+//   filter      apply the logits filters (LogitsFilter.swift) to the row
+//   write_back  store the filtered row
+//   top_k       beam search (BeamSearchTokenSampler.update's device part, no reference behaviour): after the filters, the log-softmax of the row and its best
+//               entries, descending, ties to the lower id (openai/whisper decoding.py:361 logprobs[idx].topk(beam_size + 1)) go to logprob_out /
+//               token_out[b * kBeamTopK + k]; the row stays in registers.  Nothing is drawn
+//   draw        None; Token: the greedy / top-k multinomial token and its log-probability; TokenAndAlternatives (alternatives_plan.h): also - when
+//               the step appends its token - the n best entries of the log-softmax the token was drawn from and that distribution's entropy, from the registers
+//               that hold the filtered, scaled row, into token_out / logprob_out as the buffers by home slot (ids; log-probabilities, the entropies behind them)
+//   advance     advance the slot's decodeText state by the token; dead slots are skipped, the random counter is the slot's token_index
+//   cfg         where the slot's SamplerCfg and suppress list come from (slot_cfg above); other than Shared, the low bits of rng_lane are the random lane
+enum class Draw { None, Token, TokenAndAlternatives };
+template <bool FILTER, Draw DRAW, bool ADVANCE, SlotCfg CFG = SlotCfg::Shared, bool WRITE_BACK = false, bool TOP_K = false>
+struct SamplerForm {
+    static constexpr bool filter = FILTER, advance = ADVANCE, write_back = WRITE_BACK, top_k = TOP_K;
+    static constexpr Draw draw = DRAW;
+    static constexpr SlotCfg cfg = CFG;
+};
+template <SlotCfg G> using PassStep = SamplerForm<true, Draw::Token, true, G>;                               // the unfused step of a decode pass
+template <SlotCfg G> using RecordingPassStep = SamplerForm<true, Draw::TokenAndAlternatives, true, G>;      // ... of one that records token alternatives
+using FilterOnly = SamplerForm<true, Draw::None, false, SlotCfg::Shared, true>;                              // launch_filter_only
+using SampleOnly = SamplerForm<false, Draw::Token, false>;                                                   // launch_sample_only
+using AlternativesOnly = SamplerForm<false, Draw::TokenAndAlternatives, false>;                              // launch_alternatives_only
+using BeamFilterTopK = SamplerForm<true, Draw::None, false, SlotCfg::Shared, false, true>;                   // launch_beam_filter_topk
+using FilterSample = SamplerForm<true, Draw::Token, false>;                                                  // launch_filter_sample
+// form_arg, the one integer a form reads its own way:
+//   Draw::Token without advance          the random counter of the draw (T > 0)
+//   Draw::TokenAndAlternatives           alternatives_pack_arg(n, slots): the list length and the slot count of the buffers
+//   top_k                                K, the number of entries reported (at most kBeamTopK)
+//   every other form                     not read
+template <class Form>
 __global__ __launch_bounds__(SAMP_T) void sampler_kernel(const SamplerCfg* __restrict__ cfgp, const int* __restrict__ suppress,
                                                         SeqState* __restrict__ seqs, float* __restrict__ logits_all,
-                                                        int counter_override, int* __restrict__ token_out, float* __restrict__ logprob_out) {
+                                                        int form_arg, int* __restrict__ token_out, float* __restrict__ logprob_out) {
     __shared__ BlockRed br;
     __shared__ int sh_i[8];
     const int b = blockIdx.x, tid = threadIdx.x;
     SeqState* sq = seqs + b;
-    if ((DO_ADVANCE || TOPK) && !slot_live(sq)) return;
-    constexpr bool kMix = DO_ADVANCE >= 2;
-    if constexpr (kMix) { const int cls = seq_class(sq->rng_lane); cfgp += cls; suppress += cls * kMaxSuppress; }
-    constexpr bool kSlotPrompt = DO_ADVANCE == 3;
-    const SamplerCfg cfg = *cfgp;
+    if ((Form::advance || Form::top_k) && !slot_live(sq)) return;
+    constexpr bool kMix = Form::cfg != SlotCfg::Shared;
+    if constexpr (kMix) { const int cls = seq_class(sq->rng_lane); cfgp += cls; suppress += cls * kMaxSuppress; }      // (slot_entry, and the class's suppress list)
+    const SamplerCfg cfg = *cfgp;      // the slot's own prompt enters with the rules and the state below (slot_cfg)
     const int V = cfg.n_vocab;
     float* logits = logits_all + (size_t)b * V;
     const int n_tok = sq->n_tokens;
@@ -483,15 +521,11 @@ __global__ __launch_bounds__(SAMP_T) void sampler_kernel(const SamplerCfg* __res
     // sh_i: 0 blank_active, 1 ts_active, 2 r1_lo, 3 r1_hi, 4 r2_lo, 5 r2_hi
     if (tid == 0) {
         int r[6] = {0, 0, 0, 0, 0, 0};
-        if constexpr (kSlotPrompt) {
-            if (DO_FILTER) compute_filter_rules(slot_prompt_cfg(cfg, sq), sq, n_tok, V, r);
-        } else {
-            if (DO_FILTER) compute_filter_rules(cfg, sq, n_tok, V, r);
-        }
+        if (Form::filter) compute_filter_rules(slot_cfg<Form::cfg>(cfg, sq), sq, n_tok, V, r);
 #pragma unroll
         for (int i = 0; i < 6; ++i) sh_i[i] = r[i];
     }
-    if (DO_FILTER && !cfg.language_filter) {
+    if (Form::filter && !cfg.language_filter) {
         for (int i = tid; i < cfg.n_suppress; i += SAMP_T) {                       // SuppressTokensFilter :21-24
             int t = suppress[i];
             if (t >= 0 && t < V) logits[t] = -INFINITY;
@@ -509,7 +543,7 @@ __global__ __launch_bounds__(SAMP_T) void sampler_kernel(const SamplerCfg* __res
         if (n < V) {
             v = logits[n];
             if (cfg.f16_logits) v = (float)(f16)v;          // idempotent for logits the projection kernel already rounded
-            if (DO_FILTER) {
+            if (Form::filter) {
                 if (cfg.language_filter) {                                           // LanguageLogitsFilter :259-265
                     if (n < cfg.language_token_begin || n >= cfg.language_token_begin + cfg.n_language_tokens) v = -INFINITY;
                 } else {
@@ -521,7 +555,7 @@ __global__ __launch_bounds__(SAMP_T) void sampler_kernel(const SamplerCfg* __res
         }
         x[e] = v;
     }
-    if (DO_FILTER && ts_active && !cfg.language_filter) {
+    if (Form::filter && ts_active && !cfg.language_filter) {
         // sumOfProbabilityOverTimestampsIsAboveAnyOtherToken (:144-242): logsumexp(ts) > max(text)
         const float m_text = block_max(mx_text, &br);
         const float m_ts = block_max(mx_ts, &br);
@@ -543,15 +577,15 @@ __global__ __launch_bounds__(SAMP_T) void sampler_kernel(const SamplerCfg* __res
             }
         }
     }
-    if (WRITE_BACK) {
+    if (Form::write_back) {
 #pragma unroll
         for (int e = 0; e < SAMP_E; ++e) {
             int n = tid + SAMP_T * e;
             if (n < V) logits[n] = x[e];
         }
     }
-    if (TOPK) {
-        const int K = min(counter_override, kBeamTopK);      // (the counter argument carries K in this mode)
+    if (Form::top_k) {
+        const int K = min(form_arg, kBeamTopK);
         float lm = -INFINITY;
         int li = 0x7fffffff;
 #pragma unroll
@@ -585,7 +619,7 @@ __global__ __launch_bounds__(SAMP_T) void sampler_kernel(const SamplerCfg* __res
         }
         return;
     }
-    if (!DO_SAMPLE) return;
+    if (Form::draw == Draw::None) return;
 
     // ---- GreedyTokenSampler (TokenSampler.swift:29-252)
     const float temp = sq->temperature;
@@ -632,7 +666,7 @@ __global__ __launch_bounds__(SAMP_T) void sampler_kernel(const SamplerCfg* __res
         }
         float pr[8], total = 0.0f;
         for (int j = 0; j < k; ++j) { pr[j] = expf(tv[j] - lse); total += pr[j]; }
-        const int counter = DO_ADVANCE ? sq->token_index : counter_override;
+        const int counter = Form::advance ? sq->token_index : form_arg;
         const float rnd = uniform01(cfg.seed + (unsigned long long)(kMix ? seq_lane(sq->rng_lane) : sq->rng_lane) * 0x632BE59BD9B4E019ull, counter) * total;
         float accp = 0.0f;
         int chosen = 0;
@@ -643,12 +677,12 @@ __global__ __launch_bounds__(SAMP_T) void sampler_kernel(const SamplerCfg* __res
         tok = ti[chosen];
         lp = tv[chosen] - lse;
     }
-    if constexpr (DO_SAMPLE == 2) {
-        const int n_alt = min(plan::alternatives_arg_n(counter_override), plan::kMaxAlternatives), slots = plan::alternatives_arg_slots(counter_override);
+    if constexpr (Form::draw == Draw::TokenAndAlternatives) {
+        const int n_alt = min(plan::alternatives_arg_n(form_arg), plan::kMaxAlternatives), slots = plan::alternatives_arg_slots(form_arg);
         const int home = kMix ? seq_lane(sq->rng_lane) : sq->rng_lane;
         const int ti_cur = sq->token_index;
         bool rec = gmax != -INFINITY;                        // (a row without a finite entry keeps what the host's reset wrote)
-        if (DO_ADVANCE) rec = rec && plan::alternatives_step_records(ti_cur, sq->prompt_len, n_tok, kMaxTok, tok, cfg.end_token, ti_cur == cfg.prefilled_index,
+        if (Form::advance) rec = rec && plan::alternatives_step_records(ti_cur, sq->prompt_len, n_tok, kMaxTok, tok, cfg.end_token, ti_cur == cfg.prefilled_index,
                                                                     cfg.has_first_token_threshold != 0, cfg.first_token_log_prob_threshold, lp);
         const long long po = plan::alternatives_pair_offset(home, n_tok, 0, slots), eo = plan::alternatives_entropy_offset(home, n_tok, slots);
         rec = rec && po >= 0 && eo >= 0;
@@ -663,7 +697,7 @@ __global__ __launch_bounds__(SAMP_T) void sampler_kernel(const SamplerCfg* __res
             }
             sx = block_sum(sx, &br);
             if (tid == 0) (logprob_out + plan::alternatives_lp_floats(slots))[eo] = lse - sx / se;
-            // the n best, descending, ties to the lower id: the TOPK branch's repeated argmax, on the scaled row and with the sampler's own lse
+            // the n best, descending, ties to the lower id: the top_k branch's repeated argmax, on the scaled row and with the sampler's own lse
             // (nothing reads the row after this: a reported entry is struck out in its register)
             float bv = gmax; int bi = gidx;
             for (int k = 0; k < n_alt; ++k) {
@@ -682,12 +716,8 @@ __global__ __launch_bounds__(SAMP_T) void sampler_kernel(const SamplerCfg* __res
         }
     }
     if (tid == 0) {
-        if (DO_SAMPLE != 2 && token_out) { token_out[b] = tok; logprob_out[b] = lp; }
-        if constexpr (kSlotPrompt) {
-            advance_decode_state(slot_prompt_cfg(cfg, sq), sq, tok, lp, n_tok);
-        } else {
-            if (DO_ADVANCE) advance_decode_state(cfg, sq, tok, lp, n_tok);
-        }
+        if (Form::draw != Draw::TokenAndAlternatives && token_out) { token_out[b] = tok; logprob_out[b] = lp; }
+        if (Form::advance) advance_decode_state(slot_cfg<Form::cfg>(cfg, sq), sq, tok, lp, n_tok);
     }
 }
 
@@ -704,44 +734,76 @@ __device__ __forceinline__ void stat_wave_reduce(SoftStat& a) {
 // One workgroup per slot: merge the per-workgroup (text, timestamp) statistics of the logits kernel, apply the
 // "timestamp mass beats every text token" rule (LogitsFilter.swift:144-242), take the greedy token and its log-prob
 // (TokenSampler.swift:29-252, T = 0) and advance the decodeText state.
-#define SAMPLER_FINAL_NAME sampler_final_kernel
-#define SAMPLER_FINAL_MIXED 0
-#include "sampler_final.inc"
-#undef SAMPLER_FINAL_NAME
-#undef SAMPLER_FINAL_MIXED
-#define SAMPLER_FINAL_NAME sampler_final_mixed_kernel
-#define SAMPLER_FINAL_MIXED 1
-#include "sampler_final.inc"
-#undef SAMPLER_FINAL_NAME
-#undef SAMPLER_FINAL_MIXED
-#define SAMPLER_FINAL_NAME sampler_final_slot_prompt_kernel
-#define SAMPLER_FINAL_MIXED 2
-#include "sampler_final.inc"
-#undef SAMPLER_FINAL_NAME
-#undef SAMPLER_FINAL_MIXED
+// cfgp: the table slot_cfg<G> reads (tbeg is a model constant: entry 0 serves every class)
+template <SlotCfg G>
+__global__ __launch_bounds__(256) void sampler_final_kernel(const SamplerCfg* __restrict__ cfgp, SeqState* __restrict__ seqs,
+                                                            const float* __restrict__ stats, int nblk) {
+    __shared__ float sm[4][4];
+    __shared__ int si[4][3];
+    __shared__ SeqState sq_l;     // the slot's whole decode state: thread 0's bookkeeping (token history scans, appends) runs on
+                                  // this LDS copy instead of a chain of dependent global round trips
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    SeqState* sq = seqs + b;
+    if (!slot_live(sq)) return;
+    constexpr int kWords = sizeof(SeqState) / 4;
+    static_assert(kMaxTok <= 256, "one history token per thread");
+    for (int i = tid; i < kWords; i += 256) reinterpret_cast<int*>(&sq_l)[i] = reinterpret_cast<const int*>(sq)[i];
+    // index of the last timestamp token of the history, found by all threads (the rules of the NEXT step need it: compute_filter_rules)
+    const int n_hist = sq->n_tokens;
+    const int tbeg = cfgp->time_token_begin;
+    int last_ts = (tid < n_hist && tid < kMaxTok && sq->tokens[tid] >= tbeg) ? tid : -1;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) last_ts = max(last_ts, __shfl_xor(last_ts, o, 64));
+    SoftStat t{-INFINITY, 0.0f, 0x7fffffff}, u{-INFINITY, 0.0f, 0x7fffffff};
+    constexpr int NR = kStatBlocks / 256;      // records per thread: all loads are issued before the first merge (one L2 round
+    float4 lo[NR];                             // trip instead of NR dependent ones)
+    float2 hi[NR];
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+        const int i = tid + 256 * k;
+        const float* e = stats + ((size_t)b * kStatBlocks + min(i, nblk - 1)) * 8;
+        lo[k] = *reinterpret_cast<const float4*>(e);
+        hi[k] = *reinterpret_cast<const float2*>(e + 4);
+    }
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+        if (tid + 256 * k < nblk) {
+            stat_merge(t, lo[k].x, lo[k].y, __float_as_int(lo[k].z));
+            stat_merge(u, lo[k].w, hi[k].x, __float_as_int(hi[k].y));
+        }
+    }
+    stat_wave_reduce(t);
+    stat_wave_reduce(u);
+    if (lane == 0) { sm[wave][0] = t.m; sm[wave][1] = t.s; si[wave][0] = t.i; sm[wave][2] = u.m; sm[wave][3] = u.s; si[wave][1] = u.i; si[wave][2] = last_ts; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < 4; ++w) { stat_merge(t, sm[w][0], sm[w][1], si[w][0]); stat_merge(u, sm[w][2], sm[w][3], si[w][1]); last_ts = max(last_ts, si[w][2]); }
+        const SamplerCfg cfg = slot_cfg<G>(slot_entry<G>(cfgp, &sq_l), &sq_l);
+        const bool ts_active = sq_l.f_rules[1] != 0;
+        int tok; float lp;
+        const bool cond = ts_active && timestamp_mass_wins(t, u, cfg.f16_logits != 0);
+        if (cond || t.m == -INFINITY) {          // text ids masked: the candidates are the timestamp ids
+            tok = u.i; lp = -logf(u.s);
+        } else {
+            SoftStat g = t;
+            stat_merge(g, u.m, u.s, u.i);        // equal maxima: the text id (smaller index) wins, like a first-maximum argmax
+            tok = g.i; lp = -logf(g.s);
+        }
+        advance_decode_state(cfg, &sq_l, tok, lp, sq_l.n_tokens, last_ts);
+    }
+    __syncthreads();
+    for (int i = tid; i < kWords; i += 256) reinterpret_cast<int*>(sq)[i] = reinterpret_cast<const int*>(&sq_l)[i];
+}
 
+template <SlotCfg G>
 __global__ void rules_init_kernel(const SamplerCfg* __restrict__ cfgp, SeqState* __restrict__ seqs) {
     if (threadIdx.x != 0) return;
     SeqState* sq = seqs + blockIdx.x;
-    const SamplerCfg cfg = *cfgp;
+    const SamplerCfg cfg = slot_cfg<G>(slot_entry<G>(cfgp, sq), sq);
     compute_filter_rules(cfg, sq, sq->n_tokens, cfg.n_vocab, sq->f_rules);
 }
-__global__ void rules_init_mixed_kernel(const SamplerCfg* __restrict__ cfgp, SeqState* __restrict__ seqs) {      // cfgp: the per-class table (option_mix.h)
-    if (threadIdx.x != 0) return;
-    SeqState* sq = seqs + blockIdx.x;
-    const SamplerCfg cfg = cfgp[seq_class(sq->rng_lane)];
-    compute_filter_rules(cfg, sq, sq->n_tokens, cfg.n_vocab, sq->f_rules);
-}
-__global__ void rules_init_slot_prompt_kernel(const SamplerCfg* __restrict__ cfgp, SeqState* __restrict__ seqs) {      // the mixed form, sampleBegin from the slot's own prompt
-    if (threadIdx.x != 0) return;
-    SeqState* sq = seqs + blockIdx.x;
-    const SamplerCfg cfg = slot_prompt_cfg(cfgp[seq_class(sq->rng_lane)], sq);
-    compute_filter_rules(cfg, sq, sq->n_tokens, cfg.n_vocab, sq->f_rules);
-}
-void launch_rules_init(const SamplerCfg* cfg_dev, SeqState* seq, int batch, hipStream_t st, int mixed) {
-    if (mixed == 2) rules_init_slot_prompt_kernel<<<batch, 64, 0, st>>>(cfg_dev, seq);
-    else if (mixed) rules_init_mixed_kernel<<<batch, 64, 0, st>>>(cfg_dev, seq);
-    else rules_init_kernel<<<batch, 64, 0, st>>>(cfg_dev, seq);
+void launch_rules_init(const SamplerCfg* cfg_dev, SeqState* seq, int batch, hipStream_t st, SlotCfg grain) {
+    with_slot_cfg(grain, [&](auto g) { rules_init_kernel<decltype(g)::value><<<batch, 64, 0, st>>>(cfg_dev, seq); });
 }
 
 // ---------------------------------------------------------------------------------------------- launchers
@@ -880,52 +942,47 @@ void launch_decoder_step(const DecodeBuffers& db, const SamplerCfg* cfg_dev, con
     a.logits = (fused && !ns) ? nullptr : db.logits; a.prof_kind = KK_DEC_LOGITS;      // (a scoring step of the no-speech detection keeps the rows: a runtime argument, the same instantiation)
     if (sample) a.cfg = cfg_dev;                 // Float16-logits switch
     if (fused) { a.stats = db.stats; a.sup_mask = db.sup_mask; }
-    const bool mixed = sample && db.mixed;       // a mixed pass (option_mix.h): the per-class tables, the mixed instantiations
-    const bool slot_prompts = sample && db.mixed == 2;      // a per-slot-prompt pass: the mixed logits epilogue (it reads no prompt index), the slot-prompt samplers
-    launch_dec32_proj(P32_LOGITS, a, n_bt, st, mixed && fused);
+    // other than Shared (option_mix.h): the per-class tables, the mixed logits epilogue (it reads no prompt index: one form serves PerClass and PerSlotPrompt)
+    const SlotCfg grain = sample ? db.grain : SlotCfg::Shared;
+    launch_dec32_proj(P32_LOGITS, a, n_bt, st, grain != SlotCfg::Shared && fused);
     if (ns) launch_nospeech(*ns, db.seq, db.logits, B, V, st);      // before any sampler: the unfused one filters the rows in place, every one advances token_index
     if (db.rule_sets && sample && !fused) launch_rule_sets(*db.rule_sets, db.seq, db.logits, B, V, st);      // a set-aware pass: every slot under the set its home slot names
     if (phrase_rules && sample && !fused) launch_phrase_rules(*phrase_rules, db.seq, db.logits, B, V, st);      // the raw rows too: phrase rules first, then the logit rules
     if (logit_rules && sample && !fused) launch_logit_rules(logit_rules, db.seq, db.logits, B, V, st);      // the raw rows, behind the no-speech kernel's read of them
     if (fused) {
         ProfScope ps_(KK_SAMPLER, st);
-        if (slot_prompts) sampler_final_slot_prompt_kernel<<<B, 256, 0, st>>>(cfg_dev, db.seq, db.stats, (V + 31) / 32);
-        else if (mixed) sampler_final_mixed_kernel<<<B, 256, 0, st>>>(cfg_dev, db.seq, db.stats, (V + 31) / 32);
-        else sampler_final_kernel<<<B, 256, 0, st>>>(cfg_dev, db.seq, db.stats, (V + 31) / 32);
+        with_slot_cfg(grain, [&](auto g) { sampler_final_kernel<decltype(g)::value><<<B, 256, 0, st>>>(cfg_dev, db.seq, db.stats, (V + 31) / 32); });
     } else if (sample) {
         ProfScope ps_(KK_SAMPLER, st);
-        if (db.alt_n > 0) {      // token alternatives: the recording instantiations, the buffers by home slot
+        if (db.alt_n > 0) {      // token alternatives: the recording forms, the buffers by home slot
             const int arg = plan::alternatives_pack_arg(db.alt_n, db.max_batch);
-            if (slot_prompts) sampler_kernel<1, 2, 3, 0><<<B, SAMP_T, 0, st>>>(cfg_dev, suppress_dev, db.seq, db.logits, arg, db.alt_ids, db.alt_lp);
-            else if (mixed) sampler_kernel<1, 2, 2, 0><<<B, SAMP_T, 0, st>>>(cfg_dev, suppress_dev, db.seq, db.logits, arg, db.alt_ids, db.alt_lp);
-            else sampler_kernel<1, 2, 1, 0><<<B, SAMP_T, 0, st>>>(cfg_dev, suppress_dev, db.seq, db.logits, arg, db.alt_ids, db.alt_lp);
-        } else
-        if (slot_prompts) sampler_kernel<1, 1, 3, 0><<<B, SAMP_T, 0, st>>>(cfg_dev, suppress_dev, db.seq, db.logits, 0, nullptr, nullptr);
-        else if (mixed) sampler_kernel<1, 1, 2, 0><<<B, SAMP_T, 0, st>>>(cfg_dev, suppress_dev, db.seq, db.logits, 0, nullptr, nullptr);
-        else sampler_kernel<1, 1, 1, 0><<<B, SAMP_T, 0, st>>>(cfg_dev, suppress_dev, db.seq, db.logits, 0, nullptr, nullptr);
+            with_slot_cfg(grain, [&](auto g) { sampler_kernel<RecordingPassStep<decltype(g)::value>><<<B, SAMP_T, 0, st>>>(cfg_dev, suppress_dev, db.seq, db.logits, arg, db.alt_ids, db.alt_lp); });
+        } else {
+            with_slot_cfg(grain, [&](auto g) { sampler_kernel<PassStep<decltype(g)::value>><<<B, SAMP_T, 0, st>>>(cfg_dev, suppress_dev, db.seq, db.logits, 0, nullptr, nullptr); });
+        }
     }
 }
 
 void launch_filter_only(const SamplerCfg* cfg_dev, const int* suppress_dev, SeqState* seq, float* logits, int n_vocab, hipStream_t st) {
-    sampler_kernel<1, 0, 0, 1><<<1, SAMP_T, 0, st>>>(cfg_dev, suppress_dev, seq, logits, 0, nullptr, nullptr);
+    sampler_kernel<FilterOnly><<<1, SAMP_T, 0, st>>>(cfg_dev, suppress_dev, seq, logits, 0, nullptr, nullptr);
 }
 // token alternatives, the kernel alone: the recording path over `batch` caller-given rows with the filters off (row b: temperature, list length and home slot from seq[b])
 void launch_alternatives_only(const SamplerCfg* cfg_dev, SeqState* seq, float* logits, int batch, int n, int max_batch, int* alt_ids, float* alt_lp, hipStream_t st) {
-    sampler_kernel<0, 2, 0, 0><<<batch, SAMP_T, 0, st>>>(cfg_dev, nullptr, seq, logits, plan::alternatives_pack_arg(n, max_batch), alt_ids, alt_lp);
+    sampler_kernel<AlternativesOnly><<<batch, SAMP_T, 0, st>>>(cfg_dev, nullptr, seq, logits, plan::alternatives_pack_arg(n, max_batch), alt_ids, alt_lp);
 }
 void launch_sample_only(const SamplerCfg* cfg_dev, SeqState* seq, float* logits, int n_vocab, int counter, int* token_out, float* logprob_out, hipStream_t st) {
-    sampler_kernel<0, 1, 0, 0><<<1, SAMP_T, 0, st>>>(cfg_dev, nullptr, seq, logits, counter, token_out, logprob_out);
+    sampler_kernel<SampleOnly><<<1, SAMP_T, 0, st>>>(cfg_dev, nullptr, seq, logits, counter, token_out, logprob_out);
 }
 
 
 // ---------------------------------------------------------------------------------------------- beam search support
 void launch_beam_filter_topk(const SamplerCfg* cfg_dev, const int* suppress_dev, SeqState* seq, float* logits, int batch, int K, float* lp_out,
                              int* tok_out, hipStream_t st) {
-    sampler_kernel<1, 0, 0, 0, 1><<<batch, SAMP_T, 0, st>>>(cfg_dev, suppress_dev, seq, logits, K, tok_out, lp_out);
+    sampler_kernel<BeamFilterTopK><<<batch, SAMP_T, 0, st>>>(cfg_dev, suppress_dev, seq, logits, K, tok_out, lp_out);
 }
 
 void launch_filter_sample(const SamplerCfg* cfg_dev, const int* suppress_dev, SeqState* seq, float* logits, int batch, int* token_out, float* logprob_out, hipStream_t st) {
-    sampler_kernel<1, 1, 0, 0><<<batch, SAMP_T, 0, st>>>(cfg_dev, suppress_dev, seq, logits, 0, token_out, logprob_out);
+    sampler_kernel<FilterSample><<<batch, SAMP_T, 0, st>>>(cfg_dev, suppress_dev, seq, logits, 0, token_out, logprob_out);
 }
 
 // align [B][224][n_align][1500] raw cross-attention score rows of the alignment heads -> out [B][224][1500]:

@@ -140,9 +140,9 @@ __device__ __forceinline__ void chan_merge(float& cn, float& cm, float& cM2, flo
 // the CUs that the cross-attention streams of the other sessions leave can hold at once; on half of the CUs the projection chain takes twice as long
 // (profiles/r06s_cu_partition_sweep.jsonl), i.e. its cost in flight is workgroup ROUNDS, and two row tiles per workgroup halve them.  The k-tiles of a row tile
 // are multiplied by the same wave in the same order as with RT = 1 and meet in LDS in the same order: the same bits (tests/test_gpu_round6.py).
-// MODE P32_LOGITS_MIXED (a mixed pass, option_mix.h) is P32_LOGITS with one suppress mask per option class in a.sup_mask, option_mask_stride(N) bytes
-// apart: a slot reads the mask of its class (seq_class of SeqState.rng_lane).  A mode of its own, so that the instantiations of every other mode keep
-// their names and their instructions (tools/device_code_hash.py): only mixed passes launch it.
+// MODE P32_LOGITS_MIXED (a pass whose SlotCfg, option_mix.h, is not Shared) is P32_LOGITS with one suppress mask per option class in a.sup_mask,
+// option_mask_stride(N) bytes apart: a slot reads the mask of its class (seq_class of SeqState.rng_lane).  The epilogue reads no prompt index, so this kernel
+// has two forms where the samplers have three: PerClass and PerSlotPrompt passes both launch this one.
 template <int MODE, bool HILO, int TC, bool NTW, int RT>
 __global__ __launch_bounds__(256, 2) void dec32_proj_kernel(const P32Args a) {
     constexpr bool kMix = MODE == P32_LOGITS_MIXED, kLogits = MODE == P32_LOGITS || kMix;

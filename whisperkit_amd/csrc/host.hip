@@ -708,7 +708,7 @@ static int prefill_run(wh_session* s, const plan::PrefillPlan& pp, int width, in
         }
         const int first = plan::prefill_launch_first(k, pp.ring), n = plan::prefill_launch_count(k, pp.ring, pp.p0), vwidth = width * n;
         align_rows(prev_first, prev_n, first, n);
-        launch_prefill_arm(s->cfg_dev, f.q.master, f.q.fin, f.t.ended, s->seq, f.t.owner, f.t.home, pass_home, width, pp.ring, first, n, prev_n, B, keep.mixed, s->st);
+        launch_prefill_arm(s->cfg_dev, f.q.master, f.q.fin, f.t.ended, s->seq, f.t.owner, f.t.home, pass_home, width, pp.ring, first, n, prev_n, B, keep.grain, s->st);
         // the mapped instantiations, as the forced pass: the slots per absorbed-attention workgroup of the ladder rung that holds the virtual width (results do not depend on it)
         const plan::CompactPassPlan cp = plan::compact_pass_plan(vwidth, B, B, spw0);
         s->pass.mapped = true; s->pass.spw = cp.compact ? cp.spw : spw0;
@@ -734,13 +734,12 @@ static int prefill_run(wh_session* s, const plan::PrefillPlan& pp, int width, in
 
 // What a decode pass is asked to do, in the session's home-slot terms: the option classes, each slot's class, the prompts at their granularity and what the
 // caller gives per slot.  The batch-key fields (option_mix.h) are equal over the classes - the caller has checked - and everything per pass is read from class 0.
-enum class PromptGrain { Shared, PerClass, PerSlot };      // the pass runs as pass.mixed 0 / 1 / 2: one prompt, one per class, one per home slot
 struct PassRequest {
     int batch = 0;
     int n = 1; const wh_decoding_options* const* opts = nullptr;      // [n] the option classes
     const int32_t* class_of_slot = nullptr;                           // [batch] by home slot; null: every slot is class 0
-    PromptGrain grain = PromptGrain::Shared;
-    // Shared: [1]; PerClass: [n]; PerSlot: [batch] by home slot - home slot b decodes under ITS prompt, the class keeps everything else; a slot outside `active` may name none
+    SlotCfg grain = SlotCfg::Shared;      // the pass runs under it (option_mix.h): one prompt, one per class, one per home slot
+    // Shared: [1]; PerClass: [n]; PerSlotPrompt: [batch] by home slot - home slot b decodes under ITS prompt, the class keeps everything else; a slot outside `active` may name none
     const int32_t* const* prompts = nullptr; const int32_t* n_prompts = nullptr;
     // null, or [batch] by home slot: the options each slot's RESULT is finalised under (wh_decoding_fallback reads the compression-ratio, log-prob and
     // no-speech thresholds, which belong to the audio, not to its class: two audios of one class may fall back differently).  Null (entry): the class's options
@@ -767,11 +766,11 @@ extern "C" int wh_decode_text_languages(wh_session* s, int batch, const wh_decod
 static int decode_text_impl(wh_session* s, const wh_special_tokens* st, const PassRequest& rq, wh_decoding_result* out) {
     const int batch = rq.batch;
     CHECK_SESSION(s); CHECK_BATCH(s, batch);
-    const bool mix = rq.grain != PromptGrain::Shared, own_prompts = rq.grain == PromptGrain::PerSlot;
+    const SlotCfg grain = rq.grain;
     const wh_decoding_options* const opt = rq.opts ? rq.opts[0] : nullptr;
     const int32_t* const language_tokens = rq.language_tokens; const float* const temperatures = rq.temperatures; const int32_t* const active = rq.active;
     const uint64_t seed = rq.seed;
-    if (!opt || !st || !rq.prompts || !rq.n_prompts || (!own_prompts && !rq.prompts[0]) || !out) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text: null argument");
+    if (!opt || !st || !rq.prompts || !rq.n_prompts || (grain != SlotCfg::PerSlotPrompt && !rq.prompts[0]) || !out) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text: null argument");
     const int V = s->m->dims.n_vocab;
     // per-audio rule sets (wh_session_define_rule_set; NO REFERENCE BEHAVIOUR): a pass is set-aware iff a live slot names a set other than 0; a
     // live slot that names an undefined set fails the call before anything is launched
@@ -792,29 +791,29 @@ static int decode_text_impl(wh_session* s, const wh_special_tokens* st, const Pa
     struct Prompt { const int32_t* tokens; int n; };
     static const int32_t kNoPrompt[1] = {0};
     auto prompt_of = [&](int hb) -> Prompt {
-        const int i = own_prompts ? hb : mix ? cls_of(hb) : 0;
+        const int i = grain == SlotCfg::PerSlotPrompt ? hb : grain == SlotCfg::PerClass ? cls_of(hb) : 0;
         return rq.prompts[i] ? Prompt{rq.prompts[i], rq.n_prompts[i]} : Prompt{kNoPrompt, 0};
     };
     auto options_of = [&](int hb) { return (rq.slot_opts && rq.slot_opts[hb]) ? rq.slot_opts[hb] : rq.opts[cls_of(hb)]; };
     int r = WH_OK;
     for (int c = 0; c < n_cls; ++c) if (!rq.opts[c]) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text: null argument");
     // the prompt table.  Per slot: a slot that decodes brings its prompt; one that does not may bring none (a bad one is still refused)
-    for (int i = 0, n_tab = own_prompts ? batch : n_cls; i < n_tab; ++i) {
+    for (int i = 0, n_tab = grain == SlotCfg::PerSlotPrompt ? batch : n_cls; i < n_tab; ++i) {
         if (!rq.prompts[i]) {
-            if (!own_prompts) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text: null argument");
+            if (grain != SlotCfg::PerSlotPrompt) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text: null argument");
             if (is_live(i)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text: slot %d decodes and has no prompt", i);
             continue;
         }
         const int np = rq.n_prompts[i];
-        if ((np < 1 || np >= kMaxTok) && own_prompts) return set_error(WH_ERR_PREFILL_FAILED, "wh_decode_text: slot %d: prompt length %d out of range [1,%d)", i, np, kMaxTok);
+        if ((np < 1 || np >= kMaxTok) && grain == SlotCfg::PerSlotPrompt) return set_error(WH_ERR_PREFILL_FAILED, "wh_decode_text: slot %d: prompt length %d out of range [1,%d)", i, np, kMaxTok);
         if (np < 1 || np >= kMaxTok) return set_error(WH_ERR_PREFILL_FAILED, "wh_decode_text: prompt length %d out of range [1,%d)", np, kMaxTok);
         if ((r = whi::check_prompt_tokens("wh_decode_text", rq.prompts[i], np, V, WH_ERR_PREFILL_FAILED))) return r;
     }
     // (an unmixed pass: entry 0 of the tables, as ever; a mixed one: every class's entries behind one synchronisation.  A per-slot-prompt pass: its samplers take
     // the timestamp rules' sampleBegin from the slot's prompt_len, the entries' initial_prompt_index is not read)
     const int32_t no_np[kMaxOptionClasses] = {};
-    r = mix ? whi::upload_sampler_cfg_classes(s, rq.opts, own_prompts ? no_np : rq.n_prompts, n_cls, st, prefilled_index, seed)
-            : whi::upload_sampler_cfg(s, opt, st, prefilled_index, rq.n_prompts[0], 0, seed);
+    r = grain != SlotCfg::Shared ? whi::upload_sampler_cfg_classes(s, rq.opts, grain == SlotCfg::PerSlotPrompt ? no_np : rq.n_prompts, n_cls, st, prefilled_index, seed)
+                                 : whi::upload_sampler_cfg(s, opt, st, prefilled_index, rq.n_prompts[0], 0, seed);
     if (r) return r;
     if (opt->word_timestamps && s->m->n_align > 0) { r = whi::ensure_align(s); if (r) return r; }
     s->align_enabled = opt->word_timestamps && s->align;
@@ -869,8 +868,9 @@ static int decode_text_impl(wh_session* s, const wh_special_tokens* st, const Pa
         if (r) return r;
     }
     s->count.decode_passes += 1;
-    if (mix) { s->pass.mixed = own_prompts ? 2 : 1; s->mix.mixed_passes += 1; s->mix.max_classes = std::max<long long>(s->mix.max_classes, n_cls); }
-    if (own_prompts) {      // wh_session_slot_prompt_stats: the pass, its distinct prompts, the prompt positions its slots step through
+    s->pass.grain = grain;
+    if (grain != SlotCfg::Shared) { s->mix.mixed_passes += 1; s->mix.max_classes = std::max<long long>(s->mix.max_classes, n_cls); }
+    if (grain == SlotCfg::PerSlotPrompt) {      // wh_session_slot_prompt_stats: the pass, its distinct prompts, the prompt positions its slots step through
         std::vector<std::vector<int32_t>> seen;
         for (int b = 0; b < batch; ++b) {
             if (!is_live(b)) continue;
@@ -916,7 +916,7 @@ static int decode_text_impl(wh_session* s, const wh_special_tokens* st, const Pa
     }
     // ---- 4. run: the states go up and the token loop runs
     WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * width, hipMemcpyHostToDevice, s->st));
-    launch_rules_init(s->cfg_dev, s->seq, width, s->st, s->pass.mixed);
+    launch_rules_init(s->cfg_dev, s->seq, width, s->st, s->pass.grain);
     int loop_count = 0;       // a slot finishes at its class's count (SamplerCfg.loop_count); the host loop runs to the largest
     for (int c = 0; c < n_cls; ++c) loop_count = std::max(loop_count, std::min(rq.opts[c]->sample_length, kMaxTok - 1));
     s->skip_special_in_progress = opt->skip_special_tokens != 0;
@@ -1013,7 +1013,7 @@ static int check_class_table(const char* who, bool per_slot, int batch, const wh
 // the progress callback's skip_special_tokens by home slot, for the duration of a pass or a group over slots with options of their own
 struct SkipScope { wh_session* s; const int32_t* keep; ~SkipScope() { s->skip_special_by_slot = keep; } };
 // the pass of a checked class table
-static int decode_class_table(wh_session* s, PromptGrain grain, int batch, const wh_decoding_options* opts, int n_classes, const int32_t* class_of_slot,
+static int decode_class_table(wh_session* s, SlotCfg grain, int batch, const wh_decoding_options* opts, int n_classes, const int32_t* class_of_slot,
                               const wh_special_tokens* st, const int32_t* const* prompts, const int32_t* n_prompts, const int32_t* language_tokens,
                               const float* temperatures, const int32_t* active, uint64_t seed, wh_decoding_result* out) {
     const wh_decoding_options* po[kMaxOptionClasses];
@@ -1035,7 +1035,7 @@ extern "C" int wh_decode_text_mixed(wh_session* s, int batch, const wh_decoding_
     if (int r = check_class_table("wh_decode_text_mixed", false, batch, opts, n_classes, class_of_slot, prompts, n_prompts, active)) return r;
     CHECK_SESSION(s); CHECK_BATCH(s, batch);
     if (!st || !prompts || !n_prompts || !out) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text_mixed: null argument");
-    return decode_class_table(s, PromptGrain::PerClass, batch, opts, n_classes, class_of_slot, st, prompts, n_prompts, language_tokens, temperatures, active, seed, out);
+    return decode_class_table(s, SlotCfg::PerClass, batch, opts, n_classes, class_of_slot, st, prompts, n_prompts, language_tokens, temperatures, active, seed, out);
 }
 
 // wh_decode_text_mixed with the prompt per SLOT.  The same checks in the same order, then the prompts: all before the session is looked at.
@@ -1045,7 +1045,7 @@ extern "C" int wh_decode_text_slot_prompts(wh_session* s, int batch, const wh_de
     if (int r = check_class_table("wh_decode_text_slot_prompts", true, batch, opts, n_classes, class_of_slot, prompts, n_prompts, active)) return r;
     CHECK_SESSION(s); CHECK_BATCH(s, batch);
     if (!st || !out) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text_slot_prompts: null argument");
-    return decode_class_table(s, PromptGrain::PerSlot, batch, opts, n_classes, class_of_slot, st, prompts, n_prompts, language_tokens, temperatures, active, seed, out);
+    return decode_class_table(s, SlotCfg::PerSlotPrompt, batch, opts, n_classes, class_of_slot, st, prompts, n_prompts, language_tokens, temperatures, active, seed, out);
 }
 
 // decodeText with caller-supplied LogitsFiltering / TokenSampling objects: the reference's host loop (Core/TextDecoder.swift:573-757)
@@ -1206,7 +1206,7 @@ extern "C" int wh_no_speech_probs(wh_session* s, int batch, const wh_special_tok
 
 // ------------------------------------------------------------------------------------------------ token alternatives
 // NO REFERENCE BEHAVIOUR: torch.topk(log_softmax(row / T), n) and the entropy of that distribution, on the row the sampler draws from (DESIGN 3.5.15;
-// alternatives_plan.h, the DO_SAMPLE == 2 instantiations of sampler_kernel).
+// alternatives_plan.h, the Draw::TokenAndAlternatives forms of sampler_kernel).
 // The first call that turns the mode on allocates the buffers; they keep their addresses for the session's life, so graphs captured under the mode stay valid
 extern "C" int wh_session_set_token_alternatives(wh_session* s, int n) {
     if (!s || !s->m) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_token_alternatives: null session");
@@ -2149,7 +2149,7 @@ static int round_decode(wh_session* s, std::vector<AudioJob>& jobs, Round& R, co
             plan::slot_language_overrides(R.lang_slot.data(), G.mixed ? R.stated_lang.data() : nullptr, nb, ml.data());
             PassRequest rq;
             rq.batch = nb; rq.n = (int)G.classes->size(); rq.opts = G.classes->data(); rq.class_of_slot = G.mixed ? R.cls_slot.data() : nullptr;
-            rq.grain = per_slot ? PromptGrain::PerSlot : PromptGrain::PerClass;
+            rq.grain = per_slot ? SlotCfg::PerSlotPrompt : SlotCfg::PerClass;
             rq.prompts = per_slot ? R.slot_prompt.data() : R.prompt_p.data(); rq.n_prompts = per_slot ? R.slot_n_prompt.data() : R.prompt_n.data();
             rq.slot_opts = G.mixed ? R.opt_slot.data() : nullptr;
             rq.language_tokens = langs ? ml.data() : nullptr; rq.temperatures = tv.data(); rq.active = active.data(); rq.seed = seed;

@@ -141,10 +141,10 @@ struct wh_session {
     // ---- the opt-in features.  Each owns its mode word, its buffers with their typed views (devmem.h pack_*), its pinned mirrors and its counters; the memory is
     // allocated on first use by the feature's one ensure function (named with each struct) and stays at fixed addresses, so captured step graphs stay valid.
     // option mixing (wh_session_set_option_mixing): mode 0 = off, 1 = wh_transcribe_batch_with_options groups its audios by batch key (option_mix_plan) and decodes a
-    // group's classes in one pass.  pass.mixed is set by a pass with classes (host.hip PassRequest with a prompt per class or per slot; wh_decode_text_mixed works whatever the mode).
+    // group's classes in one pass.  pass.grain leaves SlotCfg::Shared in a pass with classes (host.hip PassRequest with a prompt per class or per slot; wh_decode_text_mixed works whatever the mode).
     // Per-slot prompts.  prompt_mixing (wh_session_set_prompt_mixing): 1 = while option mixing is on, the prompt leaves the class and every audio's own
     // prompt goes to its slot.  previous_text (wh_session_set_previous_text; NO REFERENCE BEHAVIOUR): 1 = every audio of wh_transcribe* carries its decoded text into the
-    // prompt of its next window (prompt_carry_plan.h), emptied behind a window kept above previous_text_reset (NaN: never).  pass.mixed == 2 is set by a pass with slot prompts.
+    // prompt of its next window (prompt_carry_plan.h), emptied behind a window kept above previous_text_reset (NaN: never).  pass.grain is SlotCfg::PerSlotPrompt in a pass with slot prompts.
     // No device memory of its own.
     struct Mixing {
         int mode = 0;

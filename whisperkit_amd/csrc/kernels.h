@@ -191,8 +191,8 @@ struct SeqState {
                                   // A mixed pass (option_mix.h) keeps the slot's option class in bits 16.. of this word (seq_lane / seq_class below): the
                                   // struct keeps its size and offsets, so every kernel of an unmixed pass - class 0, the word IS the lane - is the device
                                   // code it was, and the class travels with the state through compact.hip and the compacted-pass slot map.
-                                  // Invariant: only the mixed instantiations split the word; every other reader (sampler_kernel) takes it whole.  So whoever
-                                  // starts an unmixed launch writes the lane alone: decode_text_impl / wh_detect_language / the step API / the beam loop
+                                  // Invariant: only the SlotCfg::PerClass / PerSlotPrompt forms split the word; every SlotCfg::Shared reader (sampler_kernel)
+                                  // takes it whole.  So whoever starts a Shared launch writes the lane alone: decode_text_impl / wh_detect_language / the step API / the beam loop
                                   // initialise it, and wh_measure_kernels, the one caller that re-arms states a pass left behind, strips the class
 };
 constexpr int kSeqClassShift = 16;
@@ -232,7 +232,7 @@ struct DecodeBuffers {
     const struct Xabs* xabs; // non-null: weight-absorbed cross-attention over the encoder output (xabs.hip) instead of the cross K / V stream
     const int* slot_home;    // null, or [batch] (device): a compacted pass (launch_plan.h compact_pass_plan) - slot b attends over the encoder output / cross
                              // K / V rows of slot slot_home[b] and writes that slot's alignment rows; everything else is indexed by b
-    int mixed;               // 1: a mixed pass, 2: a per-slot-prompt pass (launch_decoder_step below).  Host-side only
+    SlotCfg grain;           // where a slot's SamplerCfg comes from (option_mix.h; launch_decoder_step below picks the samplers' forms by it).  Host-side only
     int owner_slots;         // 0, or the slot count self_owner's entries are clamped to instead of `batch`: a pass that narrowed (compact.hip) reads history
                              // rows from the caches of slots beyond its present width.  Host-side only: the kernels' arguments keep their layout
     const struct RuleSetsArgs* rule_sets;   // null, or a set-aware pass (rule_sets.hip, launch_decoder_step below): rule_sets_kernel runs in front of the unfused
@@ -352,9 +352,9 @@ void launch_xabs_attn(const XabsArgs& a, hipStream_t st);
 void launch_xabs_vup(const XabsArgs& a, int n_bt, hipStream_t st);
 
 // one decoder forward + (optionally) fused filter/sample/state-advance for all slots
-// db.mixed (a mixed pass, option_mix.h): cfg_dev / suppress_dev / db.sup_mask are the session's per-class tables [kMaxOptionClasses] /
+// db.grain != SlotCfg::Shared (a mixed pass, option_mix.h): cfg_dev / suppress_dev / db.sup_mask are the session's per-class tables [kMaxOptionClasses] /
 // [kMaxOptionClasses][kMaxSuppress] / [kMaxOptionClasses][option_mask_stride(V)] and every slot reads the entry of its class (seq_class) - the
-// *_mixed instantiations; otherwise entry 0 through the instantiations that have always run
+// PerClass / PerSlotPrompt forms of the samplers; otherwise entry 0 through the Shared forms
 // no-speech detection (nospeech.hip, nospeech_plan.h; NO REFERENCE BEHAVIOUR: openai/whisper decoding.py no_speech_prob semantics): what nospeech_kernel reads and
 // writes, session memory at fixed addresses.  Every table is indexed by HOME slot (seq_lane(SeqState.rng_lane) / lane_div): a value survives fallback
 // compaction and in-pass narrowing.  lane_div > 1 (the beam loop, slot = audio x beam_size + beam): only the first beam of an audio scores, into entry audio.
@@ -405,7 +405,7 @@ void launch_rule_sets(const RuleSetsArgs& a, const SeqState* seq, float* logits,
 void launch_decoder_step(const DecodeBuffers& db, const SamplerCfg* cfg_dev, const int* suppress_dev, bool sample, hipStream_t st, const NoSpeechArgs* ns = nullptr,
                          const int* logit_rules = nullptr, const PhraseRulesArgs* phrase_rules = nullptr);
 // filter rules of the first sampling step of a decodeText call (later steps: computed by the sampler itself)
-void launch_rules_init(const SamplerCfg* cfg_dev, SeqState* seq, int batch, hipStream_t st, int mixed = 0);      // mixed: DecodeBuffers.mixed
+void launch_rules_init(const SamplerCfg* cfg_dev, SeqState* seq, int batch, hipStream_t st, SlotCfg grain = SlotCfg::Shared);      // grain: DecodeBuffers.grain
 // in-pass compaction (compact.hip): the decode state of a narrowing pass moves through a home-indexed array [n_slots].  park: seq_home[home[i]] = seq[i]
 // for the active slots i < width (home null: i); gather: seq[i] = seq_home[home[i]] where live[i], an inactive zero state elsewhere.
 void launch_seq_park(const SeqState* seq, SeqState* seq_home, const int* home, int width, int n_slots, hipStream_t st);
@@ -448,9 +448,9 @@ void launch_spec_accept(SeqState* master, const SeqState* seq, SpecRound* io, in
 // prompt prefill (prefill.hip, prefill_plan.h): the launch that runs the positions first .. first + n - 1 of every pass slot i < width in the ring members
 // i + width j.  arm: master[i] (the state at position `first`) -> the whole SeqState of the members, their owner rows [slot][kMaxTok] and home slots
 // (pass_home [width], or null: pass slot i is its own home), master[i] advanced to first + n; before that, fin[i] / ended[i] keep what a position of the
-// launch before (prev_n positions; 0: none) left when it ended the window.  mixed: DecodeBuffers.mixed
+// launch before (prev_n positions; 0: none) left when it ended the window.  grain: DecodeBuffers.grain
 void launch_prefill_arm(const SamplerCfg* cfg_dev, SeqState* master, SeqState* fin, int* ended, SeqState* seq, int* owner, int* slot_home, const int* pass_home,
-                        int width, int ring, int first, int n, int prev_n, int n_slots, int mixed, hipStream_t st);
+                        int width, int ring, int first, int n, int prev_n, int n_slots, SlotCfg grain, hipStream_t st);
 // align, in front of arm while the pass records alignment rows (align: [n_slots][kMaxTok][n_align][kCtx], keep: [n_slots][n_align][kCtx]): the rows the launch
 // before (prev_n positions from prev_first) wrote behind a position that ended its window are put back, the rows this launch may write (n positions from
 // first; n = 0 behind the last launch) are kept

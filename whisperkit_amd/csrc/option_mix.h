@@ -20,6 +20,14 @@ namespace wh {
 
 constexpr int kMaxOptionClasses = 16;   // classes per device batch: a design constant (16 x mask_stride mask bytes + 16 SamplerCfg + 16 suppress lists per session), not a measured value
 
+// Where a pass slot's SamplerCfg comes from - the one switch of a pass's samplers, rule kernels and step graphs (PassState / WhGraphKey in pass_state.h,
+// DecodeBuffers in kernels.h, slot_cfg<> in decoder.hip).  The values are kernel arguments and graph-key fields: they keep their numbers.
+enum class SlotCfg : int {
+    Shared = 0,         // entry 0 of the session's tables: one prompt, one set of options
+    PerClass = 1,       // the entry of the slot's option class (seq_class of SeqState.rng_lane): a mixed pass
+    PerSlotPrompt = 2,  // the class entry, with the slot's own prompt_len as the timestamp rules' sampleBegin
+};
+
 namespace plan {
 
 // bytes between the suppress masks of two classes: the logits epilogue reads a mask four bytes at a time and V = 51865 is odd

@@ -16,10 +16,10 @@ namespace wh {
 constexpr int kPrefillSeqWords = sizeof(SeqState) / 4;
 static_assert(sizeof(SeqState) % 4 == 0, "SeqState is copied word by word");
 
-// the SamplerCfg pass slot `sq` samples under: entry 0, its class's entry (a mixed pass), or that with the slot's own sampleBegin (a per-slot-prompt pass)
-__device__ __forceinline__ SamplerCfg prefill_cfg(const SamplerCfg* cfgp, const SeqState* sq, int mixed) {
-    SamplerCfg c = cfgp[mixed ? seq_class(sq->rng_lane) : 0];
-    if (mixed == 2) c.initial_prompt_index = sq->prompt_len;
+// the SamplerCfg pass slot `sq` samples under: slot_cfg<> of decoder.hip with the grain at run time (one kernel serves the three)
+__device__ __forceinline__ SamplerCfg prefill_cfg(const SamplerCfg* cfgp, const SeqState* sq, SlotCfg grain) {
+    SamplerCfg c = cfgp[grain != SlotCfg::Shared ? seq_class(sq->rng_lane) : 0];
+    if (grain == SlotCfg::PerSlotPrompt) c.initial_prompt_index = sq->prompt_len;
     return c;
 }
 
@@ -50,7 +50,7 @@ __device__ __forceinline__ int prefill_first_done(const SeqState* seq, int i, in
 __global__ __launch_bounds__(256) void prefill_arm_kernel(const SamplerCfg* __restrict__ cfgp, SeqState* __restrict__ master, SeqState* __restrict__ fin,
                                                           int* __restrict__ ended, SeqState* __restrict__ seq, int* __restrict__ owner,
                                                           int* __restrict__ slot_home, const int* __restrict__ pass_home, int width, int ring, int first,
-                                                          int n, int prev_n, int n_slots, int mixed) {
+                                                          int n, int prev_n, int n_slots, SlotCfg grain) {
     __shared__ SeqState sq_l;
     __shared__ int go, keep;
     const int i = blockIdx.x, tid = threadIdx.x;
@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void prefill_arm_kernel(const SamplerCfg* __re
         for (int w = tid; w < kPrefillSeqWords; w += 256) reinterpret_cast<int*>(q)[w] = reinterpret_cast<const int*>(&sq_l)[w];
         __syncthreads();
         if (tid == 0) {
-            advance_decode_state(prefill_cfg(cfgp, &sq_l, mixed), &sq_l, -1, 0.0f, sq_l.n_tokens);
+            advance_decode_state(prefill_cfg(cfgp, &sq_l, grain), &sq_l, -1, 0.0f, sq_l.n_tokens);
             go = sq_l.done == 0 ? 1 : 0;
         }
         __syncthreads();
@@ -180,9 +180,9 @@ __global__ __launch_bounds__(256) void prefill_commit_kernel(const SeqState* __r
 static_assert(kHeadDim * sizeof(f16) % 16 == 0, "prefill_commit_kernel: a cache row is a whole number of 16-byte vectors");
 
 void launch_prefill_arm(const SamplerCfg* cfg_dev, SeqState* master, SeqState* fin, int* ended, SeqState* seq, int* owner, int* slot_home, const int* pass_home,
-                        int width, int ring, int first, int n, int prev_n, int n_slots, int mixed, hipStream_t st) {
+                        int width, int ring, int first, int n, int prev_n, int n_slots, SlotCfg grain, hipStream_t st) {
     if (width < 1 || ring < 1 || n < 1 || n > ring || (long long)width * ring > n_slots || first < 0 || first + n > kMaxTok) return;
-    prefill_arm_kernel<<<width, 256, 0, st>>>(cfg_dev, master, fin, ended, seq, owner, slot_home, pass_home, width, ring, first, n, prev_n, n_slots, mixed);
+    prefill_arm_kernel<<<width, 256, 0, st>>>(cfg_dev, master, fin, ended, seq, owner, slot_home, pass_home, width, ring, first, n, prev_n, n_slots, grain);
 }
 void launch_prefill_align(const SeqState* seq, float* align, float* keep, const int* pass_home, int width, int ring, int prev_first, int prev_n, int first, int n,
                           int n_slots, int n_align, hipStream_t st) {
