@@ -86,7 +86,8 @@ typedef struct wh_decoding_options {
     float temperature_increment_on_fallback;
     int32_t temperature_fallback_count;
     int32_t sample_length;
-    int32_t top_k;
+    int32_t top_k;                /* DecodingOptions.topK.  The device sampler finds its candidates with one arg-max round each and CLAMPS the count at 8:
+                                   * top_k = 40 decodes as top_k = 8.  wh_session_set_wide_top_k(s, 1) lifts the clamp (any k, up to the whole vocabulary) */
     int32_t use_prefill_prompt;
     int32_t detect_language;      /* -1: default (= !use_prefill_prompt) */
     int32_t skip_special_tokens;
@@ -454,8 +455,8 @@ int wh_session_inpass_compaction_stats(const wh_session* s, int64_t* switches, i
  * launches, then its token loop from step P0.  n_pref = the index of the first <|startoftranscript|> of a slot's prompt (0: no previous-text part);
  * P0 = 8 floor(min(n_pref over the slots that decode, sample_length) / 8); R = ceil(P0 / ceil(P0 / floor(session slots / pass width))) positions per launch,
  * each in a slot of its own: pass slot i uses the slots i + width j, j < R (their decode states and self-attention caches; their encoder data are not touched).
- * A pass is NOT prefilled when P0 is 0 (a slot without a previous-text part switches it off for its pass), when it fills more than half of the session, or
- * while a progress callback is installed.  Every prefilled position runs the pass's real logits launch, rules kernels and sampler, so a window that samples the
+ * A pass is NOT prefilled when P0 is 0 (a slot without a previous-text part switches it off for its pass), when it fills more than half of the session,
+ * while a progress callback is installed, or when it samples wide (wh_session_set_wide_top_k).  Every prefilled position runs the pass's real logits launch, rules kernels and sampler, so a window that samples the
  * end token inside its prompt or fails first_token_log_prob_threshold ends where it would.  Results are identical to the off mode, bit for bit: tokens,
  * log-probabilities, steps, fallback fields, no-speech probabilities and all alignment rows; at T > 0 too (a position draws from its slot's random stream
  * at its own index).  What differs, only for a window that ENDS inside its prompt: the positions of its launch behind the end have run too, so the match
@@ -1061,6 +1062,37 @@ int wh_session_token_alternatives_stats(const wh_session* s, int64_t* passes, in
  * entropy_out [n_rows].  It overwrites the rows of home slots 0 .. n_rows - 1. */
 int wh_debug_token_alternatives_apply(wh_session* s, const float* rows, int n_rows, const float* temperatures, int n, int32_t* ids_out,
                                       float* logprobs_out, float* entropy_out);
+
+/* ---- Wide top-k sampling: DecodingOptions.topK above 8 on the device (opt-in).
+ * GreedyTokenSampler draws, at T > 0, from the top_k largest entries of the scaled row (Core/Text/TokenSampler.swift:140-180), for any top_k; openai/whisper and
+ * faster-whisper sample the whole vocabulary on their fallback rungs, which is top_k = n_vocab.  The device sampler clamps top_k at 8 (see wh_decoding_options.top_k).
+ * mode 0 (default) = off: everything as ever, the clamp included.  mode 1 = on: a draw at T > 0 with top_k > 8 - in wh_decode_text / _languages / _mixed /
+ * _slot_prompts, every T > 0 rung of wh_transcribe*, wh_sample_token and through it the NULL-sampler branch of wh_decode_text_custom - runs a selection
+ * kernel of its own (csrc/topk_wide.hip): a pass launches the session's filters alone and then that kernel, which scales by 1 / T, takes
+ * the log-sum-exp the way the sampler does, and draws among the top_k largest entries - value descending, ties to the lower id, -0.0 == +0.0; entries
+ * that are not finite weigh 0; top_k >= n_vocab is the whole row - with the sampler's own random stream (same lane, same counter), so a slot decodes to
+ * the same bytes at any width and in any slot.  Candidate masses are summed in fixed point (units of 2^-40), so rnd * total and the cumulative sums are
+ * exact integers: against the fp32 running sum of the clamped sampler a draw can differ only where rnd falls within a few ulp of a boundary.
+ * With the mode on, top_k <= 8 and every T = 0 pass run the kernels they always ran, bit for bit; a T = 0 slot inside a wide pass takes the arg-max,
+ * also the same bytes.  It composes with both compaction options, no-speech detection, logit / phrase rules, rule sets, per-slot prompts, device word
+ * alignment and the progress callback.  Whether a slot samples wide belongs to the PASS: wh_decode_text_mixed / wh_decode_text_slot_prompts return
+ * WH_ERR_INVALID_ARGUMENT, before anything is launched, when some classes have top_k > 8 and some do not, and wh_transcribe_batch_with_options under option
+ * mixing keeps such audios in different groups (the batching changes, never a result).
+ * Out of scope: token alternatives (wh_session_set_token_alternatives) with top_k > 8 under the mode are WH_ERR_INVALID_ARGUMENT (in batch calls, the
+ * status of the audios concerned); a wide pass is not prefilled (wh_session_set_prompt_prefill); beam, guided and speculative passes are T = 0 and untouched.
+ * WH_ERR_INVALID_ARGUMENT for a NULL session or a mode other than 0 / 1. */
+int wh_session_set_wide_top_k(wh_session* s, int mode);
+int wh_session_wide_top_k(const wh_session* s);   /* the mode; -1 for a NULL session */
+/* Counters of the session since its creation: decode passes that sampled wide, and launches of the selection kernel (one per step of such a pass, one per wide
+ * wh_sample_token draw).  Either pointer may be NULL. */
+int wh_session_wide_top_k_stats(const wh_session* s, int64_t* passes, int64_t* launches);
+/* Development aid: the selection kernel alone, filters off, no state advance, whatever the mode.  rows [n_rows][n_vocab] (n_rows <= max_batch, n_vocab <= the
+ * model's) go into the session's logits buffer; every row is drawn under (k >= 1, temperature - taken as given -, seed) on random lane 0, row i with
+ * counters[i] as its counter (NULL: 0).  tokens_out / logprobs_out [n_rows]; each of the following may be NULL: kth_value_out [n_rows] the k-th largest scaled
+ * value (the min(k, n_vocab)-th), n_selected_out [n_rows] how many candidates sit at that value, total_out [n_rows] the candidates' mass sum exp(x - lse).
+ * temperature 0 takes the first candidate (k-th value = the maximum, one selected, mass reported as 0). */
+int wh_debug_wide_top_k(wh_session* s, const float* rows, int n_rows, int n_vocab, int k, float temperature, uint64_t seed, const int32_t* counters,
+                        int32_t* tokens_out, float* logprobs_out, float* kth_value_out, int32_t* n_selected_out, float* total_out);
 
 void wh_transcription_free(wh_transcription* t);
 int wh_transcription_n_segments(const wh_transcription* t);

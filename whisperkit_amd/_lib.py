@@ -269,6 +269,10 @@ SYMBOLS = {
     "wh_transcription_alternatives": (I, [VP, C.POINTER(PI32), C.POINTER(PF), C.POINTER(PF), C.POINTER(I), C.POINTER(I)]),
     "wh_transcription_set_window_alternatives": (I, [VP, I, PI32, PF, PF, I]),
     "wh_debug_token_alternatives_apply": (I, [VP, PF, I, PF, I, PI32, PF, PF]),
+    "wh_session_set_wide_top_k": (I, [VP, I]),
+    "wh_session_wide_top_k": (I, [VP]),
+    "wh_session_wide_top_k_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "wh_debug_wide_top_k": (I, [VP, PF, I, I, I, C.c_float, C.c_uint64, PI32, PI32, PF, PF, PI32, PF]),
     "wh_prefill_prompt": (I, [VP, POPT, PST, C.c_int32, PI32, I]),
     "wh_transcribe": (I, [VP, VP, I, POPT, PST, PVP]),
     "wh_transcribe_batch": (I, [VP, PVP, PI32, I, POPT, PST, PVP]),

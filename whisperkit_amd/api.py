@@ -1175,6 +1175,38 @@ class Session:
                                                           ids.ctypes.data_as(L.PI32), lps.ctypes.data_as(L.PF), ent.ctypes.data_as(L.PF)))
         return ids, lps, ent
 
+    def setWideTopK(self, mode):
+        """DecodingOptions.topK above 8 on the device (wh_session_set_wide_top_k; csrc/topk_wide.hip).  "off" / 0 (default): the device sampler
+        clamps topK at 8, as ever.  "on" / 1: a draw at T > 0 with topK > 8 - decodeText*, every T > 0 rung of transcribe*, sampleToken - runs the wide
+        selection kernel: any topK, up to the whole vocabulary (topK >= nVocab), with the sampler's own random stream.  topK <= 8 and T = 0 run what they
+        always ran.  decodeTextMixed / decodeTextSlotPrompts refuse classes on both sides of 8; token alternatives with topK > 8 are refused; a wide pass is
+        not prefilled."""
+        m = {"off": 0, "on": 1}.get(mode, mode)
+        _check(self.lib.wh_session_set_wide_top_k(self.handle, int(m)))
+
+    def wideTopK(self) -> int:
+        return int(self.lib.wh_session_wide_top_k(self.handle))
+
+    def wideTopKStats(self) -> Tuple[int, int]:
+        """(decode passes that sampled wide, launches of the selection kernel) since the session was created"""
+        a, b = C.c_int64(), C.c_int64()
+        _check(self.lib.wh_session_wide_top_k_stats(self.handle, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def debugWideTopK(self, rows, k: int, temperature: float, seed: int = 0, counters=None):
+        """Development aid (wh_debug_wide_top_k): the selection kernel alone over rows [nRows][nVocab' <= nVocab], filters off, no state advance, random lane 0,
+        row i under counters[i] -> (tokens, logProbs, kthValues, nSelected, totals), one entry per row."""
+        x = np.ascontiguousarray(rows, dtype=np.float32)
+        assert x.ndim == 2 and x.shape[1] <= self.model.dims.n_vocab
+        n = x.shape[0]
+        c = None if counters is None else np.ascontiguousarray(counters, dtype=np.int32)
+        assert c is None or c.shape == (n,)
+        tok = np.empty((n,), np.int32); lp = np.empty((n,), np.float32); kth = np.empty((n,), np.float32); nsel = np.empty((n,), np.int32); tot = np.empty((n,), np.float32)
+        _check(self.lib.wh_debug_wide_top_k(self.handle, x.ctypes.data_as(L.PF), n, x.shape[1], int(k), float(temperature), int(seed),
+                                            None if c is None else c.ctypes.data_as(L.PI32), tok.ctypes.data_as(L.PI32), lp.ctypes.data_as(L.PF),
+                                            kth.ctypes.data_as(L.PF), nsel.ctypes.data_as(L.PI32), tot.ctypes.data_as(L.PF)))
+        return tok, lp, kth, nsel, tot
+
     def setLogitRules(self, repetitionPenalty: float = 1.0, noRepeatNgramSize: int = 0, tokenBias=None):
         """NO REFERENCE BEHAVIOUR: the semantics are transformers' SequenceBiasLogitsProcessor (single-token sequences), RepetitionPenaltyLogitsProcessor and
         NoRepeatNGramLogitsProcessor, applied in the order `generate` applies them.  An opt-in rule set of the session, applied on the device to the raw

@@ -779,6 +779,7 @@ DecodeBuffers decode_buffers(wh_session* s, int batch, int max_position) {
     if (p.owner) { db.self_owner = s->inpass.d.owner; db.owner_slots = s->B; }       // a pass that narrowed (host.hip inpass_narrow)
     db.rule_sets = (p.rules & plan::kRulesPassSetAware) ? &s->rules.rs_args : nullptr;     // a set-aware pass (host.hip decode_text_impl, rule_sets_plan.h)
     if (p.alt) { db.alt_ids = s->alt.ids; db.alt_lp = s->alt.f32; db.alt_n = p.alt; }      // a pass that records token alternatives (alternatives_plan.h)
+    db.wide_top_k = p.wide ? 1 : 0;      // a wide top-k pass (topk_wide_plan.h)
     // cross-attention gate: WH_XATT_GATE=0 never, 1 always, unset: while the model carries more than one session (dec_shared.h)
     const int gate_mode = knob::once<knob::WH_XATT_GATE>();
     const bool gate_on = gate_mode < 0 ? kXattnGateDefault && m->n_sessions.load() > 1 : gate_mode != 0;
@@ -1259,7 +1260,11 @@ extern "C" int wh_sample_token(wh_session* s, const float* logits, int n_logits,
     q.active = 1; q.temperature = (float)(_Float16)temperature;   // GreedyTokenSampler.temperature is FloatType (TokenSampler.swift:30)
     WH_HIP(hipMemcpyAsync(s->seq, &q, sizeof(SeqState), hipMemcpyHostToDevice, s->st));
     WH_HIP(hipMemcpyAsync(s->scratch_logits, logits, sizeof(float) * n_logits, hipMemcpyHostToDevice, s->st));
-    launch_sample_only(s->cfg_dev, s->seq, s->scratch_logits, n_logits, counter, s->tok_out_dev, s->lp_out_dev, s->st);
+    // wide top-k (wh_session_set_wide_top_k 1): a T > 0 draw with top_k > 8 is topk_wide_kernel's, as in a pass
+    if (plan::wide_top_k_applies(s->wide.mode, top_k) && q.temperature != 0.0f) {
+        launch_wide_top_k_rows(s->cfg_dev, s->seq, s->scratch_logits, 1, nullptr, counter, s->tok_out_dev, s->lp_out_dev, nullptr, nullptr, nullptr, s->st);
+        s->wide.launches += 1;
+    } else launch_sample_only(s->cfg_dev, s->seq, s->scratch_logits, n_logits, counter, s->tok_out_dev, s->lp_out_dev, s->st);
     WH_CHECK_LAUNCH();
     WH_HIP(hipMemcpyAsync(token_out, s->tok_out_dev, sizeof(int), hipMemcpyDeviceToHost, s->st));
     WH_HIP(hipMemcpyAsync(logprob_out, s->lp_out_dev, sizeof(float), hipMemcpyDeviceToHost, s->st));

@@ -2,6 +2,8 @@
 #pragma once
 #include "kernels.h"
 
+#include <type_traits>
+
 namespace wh {
 
 __device__ __forceinline__ bool slot_live(const SeqState* s) { return s->active && !s->done; }
@@ -147,6 +149,94 @@ __device__ __forceinline__ void advance_decode_state(const SamplerCfg& cfg, SeqS
     int hint = last_ts_pre;
     if (hint >= -1 && nt > n_tok && tok >= tb) hint = nt - 1;          // the token appended by this step is the newest timestamp
     compute_filter_rules(cfg, sq, nt, cfg.n_vocab, sq->f_rules, hint);
+}
+
+// ---------------------------------------------------------------------------------------------- what the samplers share (decoder.hip sampler_kernel, topk_wide.hip)
+constexpr int SAMP_T = 1024;
+constexpr int SAMP_E = 51;   // ceil(51866 / 1024)
+static_assert(SAMP_T * SAMP_E >= kMaxVocab, "sampler_kernel keeps the whole logits row in registers");
+
+struct BlockRed {
+    float f[32];
+    int i[32];
+};
+
+__device__ __forceinline__ float block_max(float v, BlockRed* br) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    v = wave_max(v);
+    __syncthreads();
+    if (lane == 0) br->f[wave] = v;
+    __syncthreads();
+    float r = br->f[0];
+    for (int w = 1; w < SAMP_T / 64; ++w) r = fmaxf(r, br->f[w]);
+    return r;
+}
+__device__ __forceinline__ float block_sum(float v, BlockRed* br) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    v = wave_sum(v);
+    __syncthreads();
+    if (lane == 0) br->f[wave] = v;
+    __syncthreads();
+    float r = 0.0f;
+    for (int w = 0; w < SAMP_T / 64; ++w) r += br->f[w];
+    return r;
+}
+// argmax with ties -> smallest index
+__device__ __forceinline__ void block_argmax(float v, int idx, BlockRed* br, float* vout, int* iout) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        float ov = __shfl_xor(v, o, 64);
+        int oi = __shfl_xor(idx, o, 64);
+        if (ov > v || (ov == v && oi < idx)) { v = ov; idx = oi; }
+    }
+    __syncthreads();
+    if (lane == 0) { br->f[wave] = v; br->i[wave] = idx; }
+    __syncthreads();
+    float bv = br->f[0];
+    int bi = br->i[0];
+    for (int w = 1; w < SAMP_T / 64; ++w) {
+        float ov = br->f[w];
+        int oi = br->i[w];
+        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+    }
+    *vout = bv;
+    *iout = bi;
+}
+
+__device__ __forceinline__ float uniform01(unsigned long long seed, int counter) {
+    unsigned long long z = seed + (unsigned long long)(counter + 1) * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z = z ^ (z >> 31);
+    return (float)(z >> 40) * (1.0f / 16777216.0f);
+}
+
+// The SamplerCfg slot `sq` runs under (SlotCfg, option_mix.h): entry 0 of the table at cfgp, the entry of the slot's class (seq_class of SeqState.rng_lane), or
+// that entry with the slot's own prompt length as the timestamp rules' sampleBegin - the class entry's initial_prompt_index is then not read.
+// In two steps, the table entry and what the slot runs under given its entry, because sampler_kernel reads its row under the entry and takes the second step
+// only for the rules and the state; a kernel without that split writes slot_cfg<G>(slot_entry<G>(cfgp, sq), sq).
+template <SlotCfg G>
+__device__ __forceinline__ const SamplerCfg& slot_entry(const SamplerCfg* cfgp, const SeqState* sq) {
+    return cfgp[G == SlotCfg::Shared ? 0 : seq_class(sq->rng_lane)];
+}
+template <SlotCfg G>
+__device__ __forceinline__ decltype(auto) slot_cfg(const SamplerCfg& entry, const SeqState* sq) {      // (the entry itself, by reference, unless the slot brings its prompt)
+    if constexpr (G == SlotCfg::PerSlotPrompt) {
+        SamplerCfg c = entry;
+        c.initial_prompt_index = sq->prompt_len;
+        return c;
+    } else {
+        return (entry);
+    }
+}
+// host side: f(std::integral_constant<SlotCfg, g>{}) - the one place a run-time SlotCfg picks a kernel's form
+template <class F> static void with_slot_cfg(SlotCfg g, F&& f) {
+    switch (g) {
+        case SlotCfg::Shared: return f(std::integral_constant<SlotCfg, SlotCfg::Shared>{});
+        case SlotCfg::PerClass: return f(std::integral_constant<SlotCfg, SlotCfg::PerClass>{});
+        case SlotCfg::PerSlotPrompt: return f(std::integral_constant<SlotCfg, SlotCfg::PerSlotPrompt>{});
+    }
 }
 
 }  // namespace wh

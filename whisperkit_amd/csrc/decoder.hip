@@ -383,92 +383,7 @@ __global__ __launch_bounds__(256) void dec_cross_attn_kernel(const AttnArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------- sampler
-constexpr int SAMP_T = 1024;
-constexpr int SAMP_E = 51;   // ceil(51866 / 1024)
-static_assert(SAMP_T * SAMP_E >= kMaxVocab, "sampler_kernel keeps the whole logits row in registers");
-
-struct BlockRed {
-    float f[32];
-    int i[32];
-};
-
-__device__ __forceinline__ float block_max(float v, BlockRed* br) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    v = wave_max(v);
-    __syncthreads();
-    if (lane == 0) br->f[wave] = v;
-    __syncthreads();
-    float r = br->f[0];
-    for (int w = 1; w < SAMP_T / 64; ++w) r = fmaxf(r, br->f[w]);
-    return r;
-}
-__device__ __forceinline__ float block_sum(float v, BlockRed* br) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    v = wave_sum(v);
-    __syncthreads();
-    if (lane == 0) br->f[wave] = v;
-    __syncthreads();
-    float r = 0.0f;
-    for (int w = 0; w < SAMP_T / 64; ++w) r += br->f[w];
-    return r;
-}
-// argmax with ties -> smallest index
-__device__ __forceinline__ void block_argmax(float v, int idx, BlockRed* br, float* vout, int* iout) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        float ov = __shfl_xor(v, o, 64);
-        int oi = __shfl_xor(idx, o, 64);
-        if (ov > v || (ov == v && oi < idx)) { v = ov; idx = oi; }
-    }
-    __syncthreads();
-    if (lane == 0) { br->f[wave] = v; br->i[wave] = idx; }
-    __syncthreads();
-    float bv = br->f[0];
-    int bi = br->i[0];
-    for (int w = 1; w < SAMP_T / 64; ++w) {
-        float ov = br->f[w];
-        int oi = br->i[w];
-        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-    }
-    *vout = bv;
-    *iout = bi;
-}
-
-__device__ __forceinline__ float uniform01(unsigned long long seed, int counter) {
-    unsigned long long z = seed + (unsigned long long)(counter + 1) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z = z ^ (z >> 31);
-    return (float)(z >> 40) * (1.0f / 16777216.0f);
-}
-
-// The SamplerCfg slot `sq` runs under (SlotCfg, option_mix.h): entry 0 of the table at cfgp, the entry of the slot's class (seq_class of SeqState.rng_lane), or
-// that entry with the slot's own prompt length as the timestamp rules' sampleBegin - the class entry's initial_prompt_index is then not read.
-// In two steps, the table entry and what the slot runs under given its entry, because sampler_kernel reads its row under the entry and takes the second step
-// only for the rules and the state; a kernel without that split writes slot_cfg<G>(slot_entry<G>(cfgp, sq), sq).
-template <SlotCfg G>
-__device__ __forceinline__ const SamplerCfg& slot_entry(const SamplerCfg* cfgp, const SeqState* sq) {
-    return cfgp[G == SlotCfg::Shared ? 0 : seq_class(sq->rng_lane)];
-}
-template <SlotCfg G>
-__device__ __forceinline__ decltype(auto) slot_cfg(const SamplerCfg& entry, const SeqState* sq) {      // (the entry itself, by reference, unless the slot brings its prompt)
-    if constexpr (G == SlotCfg::PerSlotPrompt) {
-        SamplerCfg c = entry;
-        c.initial_prompt_index = sq->prompt_len;
-        return c;
-    } else {
-        return (entry);
-    }
-}
-// host side: f(std::integral_constant<SlotCfg, g>{}) - the one place a run-time SlotCfg picks a kernel's form
-template <class F> static void with_slot_cfg(SlotCfg g, F&& f) {
-    switch (g) {
-        case SlotCfg::Shared: return f(std::integral_constant<SlotCfg, SlotCfg::Shared>{});
-        case SlotCfg::PerClass: return f(std::integral_constant<SlotCfg, SlotCfg::PerClass>{});
-        case SlotCfg::PerSlotPrompt: return f(std::integral_constant<SlotCfg, SlotCfg::PerSlotPrompt>{});
-    }
-}
+// (SAMP_T / SAMP_E, the block reductions, uniform01, slot_entry / slot_cfg / with_slot_cfg: dec_shared.h - topk_wide.hip shares them)
 
 // The forms of sampler_kernel: what one launch does with a slot's logits row, in the order the kernel does it.
 //   filter      apply the logits filters (LogitsFilter.swift) to the row
@@ -495,6 +410,7 @@ using SampleOnly = SamplerForm<false, Draw::Token, false>;                      
 using AlternativesOnly = SamplerForm<false, Draw::TokenAndAlternatives, false>;                              // launch_alternatives_only
 using BeamFilterTopK = SamplerForm<true, Draw::None, false, SlotCfg::Shared, false, true>;                   // launch_beam_filter_topk
 using FilterSample = SamplerForm<true, Draw::Token, false>;                                                  // launch_filter_sample
+template <SlotCfg G> using FilterWriteBack = SamplerForm<true, Draw::None, false, G, true>;                  // launch_filter_write_back: in front of topk_wide_kernel
 // form_arg, the one integer a form reads its own way:
 //   Draw::Token without advance          the random counter of the draw (T > 0)
 //   Draw::TokenAndAlternatives           alternatives_pack_arg(n, slots): the list length and the slot count of the buffers
@@ -954,7 +870,10 @@ void launch_decoder_step(const DecodeBuffers& db, const SamplerCfg* cfg_dev, con
         with_slot_cfg(grain, [&](auto g) { sampler_final_kernel<decltype(g)::value><<<B, 256, 0, st>>>(cfg_dev, db.seq, db.stats, (V + 31) / 32); });
     } else if (sample) {
         ProfScope ps_(KK_SAMPLER, st);
-        if (db.alt_n > 0) {      // token alternatives: the recording forms, the buffers by home slot
+        if (db.wide_top_k) {     // wide top-k (topk_wide.hip): the filters alone, then the selection kernel draws from the stored rows and advances
+            launch_filter_write_back(cfg_dev, suppress_dev, db.seq, db.logits, B, grain, st);
+            launch_wide_top_k_step(cfg_dev, db.seq, db.logits, B, grain, st);
+        } else if (db.alt_n > 0) {      // token alternatives: the recording forms, the buffers by home slot
             const int arg = plan::alternatives_pack_arg(db.alt_n, db.max_batch);
             with_slot_cfg(grain, [&](auto g) { sampler_kernel<RecordingPassStep<decltype(g)::value>><<<B, SAMP_T, 0, st>>>(cfg_dev, suppress_dev, db.seq, db.logits, arg, db.alt_ids, db.alt_lp); });
         } else {
@@ -965,6 +884,9 @@ void launch_decoder_step(const DecodeBuffers& db, const SamplerCfg* cfg_dev, con
 
 void launch_filter_only(const SamplerCfg* cfg_dev, const int* suppress_dev, SeqState* seq, float* logits, int n_vocab, hipStream_t st) {
     sampler_kernel<FilterOnly><<<1, SAMP_T, 0, st>>>(cfg_dev, suppress_dev, seq, logits, 0, nullptr, nullptr);
+}
+void launch_filter_write_back(const SamplerCfg* cfg_dev, const int* suppress_dev, SeqState* seq, float* logits, int batch, SlotCfg grain, hipStream_t st) {
+    with_slot_cfg(grain, [&](auto g) { sampler_kernel<FilterWriteBack<decltype(g)::value>><<<batch, SAMP_T, 0, st>>>(cfg_dev, suppress_dev, seq, logits, 0, nullptr, nullptr); });
 }
 // token alternatives, the kernel alone: the recording path over `batch` caller-given rows with the filters off (row b: temperature, list length and home slot from seq[b])
 void launch_alternatives_only(const SamplerCfg* cfg_dev, SeqState* seq, float* logits, int batch, int n, int max_batch, int* alt_ids, float* alt_lp, hipStream_t st) {

@@ -572,7 +572,7 @@ static int run_token_loop(wh_session* s, int batch, int loop_count, PassLayout* 
     int width = batch;                                   // (changes only through inpass_narrow)
     auto all_done_in = [](const SeqState* q, int n) { for (int b = 0; b < n; ++b) if (q[b].active && !q[b].done) return false; return true; };
     auto all_done = [&]() { return all_done_in(s->seq_host, width); };
-    auto count_steps = [&](int steps) { s->count.slot_steps += (long long)width * steps; if (L) s->inpass.slot_steps_saved += (long long)(L->width0 - width) * steps; if (s->pass.rules & plan::kRulesPassLogitKernel) s->rules.lr_launches += steps; if (s->pass.rules & plan::kRulesPassPhraseKernel) s->rules.pr_launches += steps; if (s->pass.rules & plan::kRulesPassSetAware) s->rules.rs_launches += steps; };
+    auto count_steps = [&](int steps) { s->count.slot_steps += (long long)width * steps; if (L) s->inpass.slot_steps_saved += (long long)(L->width0 - width) * steps; if (s->pass.rules & plan::kRulesPassLogitKernel) s->rules.lr_launches += steps; if (s->pass.rules & plan::kRulesPassPhraseKernel) s->rules.pr_launches += steps; if (s->pass.rules & plan::kRulesPassSetAware) s->rules.rs_launches += steps; if (s->pass.wide) s->wide.launches += steps; };
     // the last read of the pass: the compact slots, or - after a narrowing - every state by home slot (parked once more)
     auto final_read = [&]() -> int {
         if (L && L->switches > 0) {
@@ -797,6 +797,15 @@ static int decode_text_impl(wh_session* s, const wh_special_tokens* st, const Pa
     auto options_of = [&](int hb) { return (rq.slot_opts && rq.slot_opts[hb]) ? rq.slot_opts[hb] : rq.opts[cls_of(hb)]; };
     int r = WH_OK;
     for (int c = 0; c < n_cls; ++c) if (!rq.opts[c]) return set_error(WH_ERR_DECODING_FAILED, "wh_decode_text: null argument");
+    // wide top-k (wh_session_set_wide_top_k): whether a pass samples wide belongs to the pass - it has ONE unfused sampler - so its classes agree
+    // on it, and a pass that would sample wide records no token alternatives.  Nothing is launched before these refusals
+    const bool wide_opts = plan::wide_top_k_applies(s->wide.mode, opt->top_k);
+    for (int c = 1; c < n_cls; ++c)
+        if (plan::wide_top_k_straddles(s->wide.mode, opt->top_k, rq.opts[c]->top_k))
+            return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text: class 0 has top_k %d and class %d has top_k %d: under wh_session_set_wide_top_k the classes of a pass are all above %d or none",
+                             opt->top_k, c, rq.opts[c]->top_k, plan::kWideTopKMin - 1);
+    if (wide_opts && s->alt.n > 0)
+        return set_error(WH_ERR_INVALID_ARGUMENT, "wh_decode_text: top_k %d under wh_session_set_wide_top_k cannot be combined with token alternatives (wh_session_set_token_alternatives)", opt->top_k);
     // the prompt table.  Per slot: a slot that decodes brings its prompt; one that does not may bring none (a bad one is still refused)
     for (int i = 0, n_tab = grain == SlotCfg::PerSlotPrompt ? batch : n_cls; i < n_tab; ++i) {
         if (!rq.prompts[i]) {
@@ -885,6 +894,9 @@ static int decode_text_impl(wh_session* s, const wh_special_tokens* st, const Pa
     // fused greedy path: every active slot samples at T = 0 (filters + softmax statistics in the logits epilogue)
     s->fused_greedy = true;
     for (int b = 0; b < width; ++b) if (s->seq_host[b].active && s->seq_host[b].temperature != 0.0f) s->fused_greedy = false;
+    // wide top-k: a pass with a T > 0 slot whose options ask for more than 8 candidates.  (Its T = 0 slots, if any, take the first candidate in the same kernel, the
+    // bytes sampler_kernel gives them; an all-greedy pass is not wide, whatever its top_k.)  Not prefilled: the virtual slots of a prefill launch run the plain sampler
+    if (wide_opts && !s->fused_greedy) { s->pass.wide = true; s->wide.passes += 1; }
     if (knob::now<knob::WH_NO_FUSED_SAMPLER>()) s->fused_greedy = false;
     // ---- device rules (NO REFERENCE BEHAVIOUR): the unfused sampler with, at every step, the kernels the pass's mask names in front of it
     // (rule_sets_plan.h rules_pass_mask) - phrase_rules_kernel, then logit_rules_kernel (wh_session_set_phrase_rules / wh_session_set_logit_rules), or in a
@@ -948,7 +960,7 @@ static int decode_text_impl(wh_session* s, const wh_special_tokens* st, const Pa
     // <|startoftranscript|>, as far as they are common to all of them and end on a graph boundary, run as virtual slots of a few launches; the loop begins at P0.
     // Not under a progress callback (its snapshots are per 8 steps from step 0), and not where the planner says no (P0 = 0, or the pass fills the session)
     plan::PrefillPlan pp = plan::prefill_plan(0, width, s->B);
-    if (s->prefill.mode == 1 && !s->progress_cb) {
+    if (s->prefill.mode == 1 && !s->progress_cb && !s->pass.wide) {
         std::vector<int32_t> n_pref((size_t)batch), live((size_t)batch);
         for (int b = 0; b < batch; ++b) {
             live[(size_t)b] = is_live(b);
@@ -1291,6 +1303,76 @@ extern "C" int wh_debug_token_alternatives_apply(wh_session* s, const float* row
         entropy_out[i] = s->alt.h.entropy[plan::alternatives_entropy_offset(i, 0, s->B)];
         s->alt.nrec[(size_t)i] = 0;                       // (what wh_decode_alternatives knew about these slots is gone)
     }
+    return WH_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ wide top-k sampling
+// NO REFERENCE BEHAVIOUR beyond DecodingOptions.topK itself: the reference honours any k on the host (TokenSampler.swift:140-180); topk_wide.hip does on the device.
+namespace whi {
+// the only place that allocates the feature's memory (the first wh_debug_wide_top_k call): [6][B] words on the device and pinned
+static int wide_top_k_ensure(wh_session* s) {
+    if (!s->wide.host) WH_HIP(s->mem.alloc_pinned(&s->wide.host, (size_t)6 * s->B));
+    if (!s->wide.dev) WH_HIP(s->mem.alloc(&s->wide.dev, (size_t)6 * s->B, false));
+    return WH_OK;
+}
+}  // namespace whi
+extern "C" int wh_session_set_wide_top_k(wh_session* s, int mode) {
+    if (!s || !s->m) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_wide_top_k: null session");
+    if (!plan::wide_top_k_mode_valid(mode)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_wide_top_k: mode %d (0 = off, 1 = on)", mode);
+    s->wide.mode = mode;
+    return WH_OK;
+}
+extern "C" int wh_session_wide_top_k(const wh_session* s) { return s ? s->wide.mode : -1; }
+extern "C" int wh_session_wide_top_k_stats(const wh_session* s, int64_t* passes, int64_t* launches) {
+    if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_wide_top_k_stats: null session");
+    whi::store_stat(passes, s->wide.passes);
+    whi::store_stat(launches, s->wide.launches);
+    return WH_OK;
+}
+// Development aid: topk_wide_kernel alone, filters off, no state advance - n_rows (<= max_batch) rows of n_vocab (<= the model's) entries go into the session's
+// logits buffer and every row is drawn under (k, temperature - taken as given, not rounded to Float16 -, seed) on random lane 0 with counters[i] as its counter
+// (null: 0).  Per row: the token and its log-probability, and - each may be null - the k-th candidate's scaled value, how many candidates sit at that value, and
+// the candidates' mass.  Works whatever the mode; temperature 0 takes the first candidate.
+extern "C" int wh_debug_wide_top_k(wh_session* s, const float* rows, int n_rows, int n_vocab, int k, float temperature, uint64_t seed, const int32_t* counters,
+                                   int32_t* tokens_out, float* logprobs_out, float* kth_value_out, int32_t* n_selected_out, float* total_out) {
+    CHECK_SESSION(s); CHECK_BATCH(s, n_rows);
+    if (!rows || !tokens_out || !logprobs_out) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_wide_top_k: null argument");
+    if (n_vocab < 1 || n_vocab > s->m->dims.n_vocab || k < 1) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_wide_top_k: n_vocab %d (1 .. %d), k %d (>= 1)", n_vocab, s->m->dims.n_vocab, k);
+    int r = whi::wide_top_k_ensure(s);
+    if (r) return r;
+    wh_decoding_options o;
+    wh_decoding_options_default(&o);
+    o.top_k = k; o.without_timestamps = 1;
+    wh_special_tokens st{};
+    r = whi::upload_sampler_cfg(s, &o, &st, 0, 0, 0, seed);      // (drains the stream: nothing in flight reads the staging the host writes next)
+    if (r) return r;
+    // entry 0's n_vocab is the model's: the rows are n_vocab wide, so the entry goes up once more with the caller's width
+    SamplerCfg c;
+    WH_HIP(hipMemcpy(&c, s->cfg_dev, sizeof(c), hipMemcpyDeviceToHost));
+    c.n_vocab = n_vocab;
+    WH_HIP(hipMemcpy(s->cfg_dev, &c, sizeof(c), hipMemcpyHostToDevice));
+    const size_t B = (size_t)s->B;
+    for (int i = 0; i < n_rows; ++i) {
+        SeqState& q = s->seq_host[i];
+        memset(&q, 0, sizeof(q));
+        q.active = 1; q.temperature = temperature;
+        s->wide.host[i] = counters ? counters[i] : 0;
+    }
+    int32_t* const d = s->wide.dev;
+    WH_HIP(hipMemcpyAsync(s->seq, s->seq_host, sizeof(SeqState) * n_rows, hipMemcpyHostToDevice, s->st));
+    WH_HIP(hipMemcpyAsync(d, s->wide.host, sizeof(int32_t) * n_rows, hipMemcpyHostToDevice, s->st));
+    WH_HIP(hipMemcpyAsync(s->logits, rows, sizeof(float) * (size_t)n_rows * n_vocab, hipMemcpyHostToDevice, s->st));
+    launch_wide_top_k_rows(s->cfg_dev, s->seq, s->logits, n_rows, d, 0, d + B, reinterpret_cast<float*>(d + 2 * B), reinterpret_cast<float*>(d + 3 * B), d + 4 * B,
+                           reinterpret_cast<float*>(d + 5 * B), s->st);
+    WH_CHECK_LAUNCH();
+    WH_HIP(hipMemcpyAsync(s->wide.host, d, sizeof(int32_t) * 6 * B, hipMemcpyDeviceToHost, s->st));
+    WH_HIP(hipStreamSynchronize(s->st));
+    const int32_t* const h = s->wide.host;
+    memcpy(tokens_out, h + B, sizeof(int32_t) * n_rows);
+    memcpy(logprobs_out, h + 2 * B, sizeof(float) * n_rows);
+    if (kth_value_out) memcpy(kth_value_out, h + 3 * B, sizeof(float) * n_rows);
+    if (n_selected_out) memcpy(n_selected_out, h + 4 * B, sizeof(int32_t) * n_rows);
+    if (total_out) memcpy(total_out, h + 5 * B, sizeof(float) * n_rows);
     return WH_OK;
 }
 
@@ -2356,7 +2438,7 @@ static int transcribe_items(wh_session* s, const float* const* pcm, const int32_
             j.status = set_error(WH_ERR_INVALID_ARGUMENT, "audio %d: rule set %d is not defined (wh_session_define_rule_set: 1 .. %d)", i, j.rule_set, plan::kMaxRuleSets - 1); j.error = wh_last_error();
             continue;
         }
-        ruled[(size_t)i] = plan::rule_set_ruled(j.rule_set, session_rules_on) ? 1 : 0;
+        ruled[(size_t)i] = (plan::rule_set_ruled(j.rule_set, session_rules_on) ? 1 : 0) | (plan::wide_top_k_applies(s->wide.mode, j.opt->top_k) ? 2 : 0);      // (the part: rule_sets_plan.h)
         int g = -1;
         for (size_t k = 0; k < group_opt.size() && g < 0; ++k) if (group_ruled[k] == ruled[(size_t)i] && plan::option_same_group(*group_opt[k], *j.opt)) g = (int)k;
         if (g < 0) { g = (int)group_opt.size(); group_opt.push_back(j.opt); group_ruled.push_back(ruled[(size_t)i]); }
@@ -2368,7 +2450,7 @@ static int transcribe_items(wh_session* s, const float* const* pcm, const int32_
     if (mixing) {
         std::vector<const wh_decoding_options*> po((size_t)n_audio, nullptr);
         for (int i = 0; i < n_audio; ++i) if (group_of[(size_t)i] >= 0) po[(size_t)i] = all[(size_t)i].opt;
-        mixp = plan::rule_sets_mix_plan(po.data(), rule_sets ? ruled.data() : nullptr, n_audio, kMaxOptionClasses, s->mix.prompt_mixing == 1);
+        mixp = plan::rule_sets_mix_plan(po.data(), (rule_sets || s->wide.mode == 1) ? ruled.data() : nullptr, n_audio, kMaxOptionClasses, s->mix.prompt_mixing == 1);
         group_of = mixp.group;
         group_opt.clear();
         for (const auto& cl : mixp.classes) group_opt.push_back(cl[0]);

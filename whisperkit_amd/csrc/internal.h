@@ -18,6 +18,7 @@
 #include "prompt_carry_plan.h"
 #include "rule_sets_plan.h"
 #include "text.h"
+#include "topk_wide_plan.h"
 #include "whisperhip.h"
 
 // every device and pinned allocation of a model or a session goes through one of these (devmem.h)
@@ -283,6 +284,14 @@ struct wh_session {
         std::vector<int32_t> start, count, nrec;
         long long passes = 0, positions = 0, d2h_bytes = 0;      // wh_session_token_alternatives_stats
     } alt;
+    // wide top-k sampling (wh_session_set_wide_top_k: topk_wide_plan.h, topk_wide.hip; host.hip wide_top_k_ensure).  mode 0 = off: top_k above 8 decodes as 8, as ever;
+    // 1 = a T > 0 draw with top_k > 8 runs topk_wide_kernel (pass.wide while such a pass runs).  dev (device) and its pinned mirror host, [6][B] words - counters in,
+    // tokens / log-probabilities / k-th values / tie counts / masses out - serve wh_debug_wide_top_k alone and are allocated by its first call.
+    struct WideTopK {
+        int mode = 0;
+        int32_t *dev = nullptr, *host = nullptr;
+        long long passes = 0, launches = 0;      // wh_session_wide_top_k_stats
+    } wide;
     hipEvent_t ev[8]{};
     bool align_enabled = false;
     wh_timings last_timings{};

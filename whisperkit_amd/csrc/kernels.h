@@ -240,6 +240,7 @@ struct DecodeBuffers {
     int* alt_ids;            // token alternatives (alternatives_plan.h, launch_decoder_step below): alt_n > 0 - the unfused sampler runs its recording instantiation
     float* alt_lp;           // and writes ids [max_batch][224][8] / log-probabilities [max_batch][224][8] | entropies [max_batch][224] by home slot.  Host-side only
     int alt_n;
+    int wide_top_k;          // 1: a wide top-k pass (topk_wide.hip, launch_decoder_step below): the unfused sampler is the filter / write-back form + topk_wide_kernel.  Host-side only
 };
 constexpr int kStatBlocks = 1792; // >= workgroups of the logits kernel (V / 64 rows: GEMV path, V / 32 rows: MFMA path), multiple of 256
 // Largest vocabulary the sampling kernels cover: sampler_kernel holds SAMP_T x SAMP_E = 1024 x 51 ids in registers, the fused greedy
@@ -468,6 +469,15 @@ void launch_sample_only(const SamplerCfg* cfg_dev, SeqState* seq, float* logits,
 // (home slot seq[b].rng_lane, position seq[b].n_tokens) of alt_ids / alt_lp, which are laid out for max_batch home slots
 void launch_alternatives_only(const SamplerCfg* cfg_dev, SeqState* seq, float* logits, int batch, int n, int max_batch, int* alt_ids, float* alt_lp, hipStream_t st);
 void launch_filter_sample(const SamplerCfg* cfg_dev, const int* suppress_dev, SeqState* seq, float* logits, int batch, int* token_out, float* logprob_out, hipStream_t st);
+// the filter / write-back form over `batch` slots of a pass (grain: DecodeBuffers.grain): the filtered rows go back to `logits`, nothing is drawn, no state moves
+void launch_filter_write_back(const SamplerCfg* cfg_dev, const int* suppress_dev, SeqState* seq, float* logits, int batch, SlotCfg grain, hipStream_t st);
+// wide top-k sampling (topk_wide.hip, topk_wide_plan.h): the temperature top-k multinomial for any k over already filtered rows, one workgroup per slot.
+// step: a decode pass's form - every live slot draws under its class's top_k and seed with its token_index as the counter, and its decodeText state advances.
+// rows: `batch` rows under entry 0 of cfg_dev (temperature and random lane from seq[b]); the counter of row b is counters[b] (device memory), or `counter` where
+// that is null; token_out / logprob_out [batch], and - each may be null - the k-th candidate's scaled value, the candidates at that value, the candidates' mass
+void launch_wide_top_k_step(const SamplerCfg* cfg_dev, SeqState* seq, const float* logits, int batch, SlotCfg grain, hipStream_t st);
+void launch_wide_top_k_rows(const SamplerCfg* cfg_dev, SeqState* seq, const float* logits, int batch, const int* counters, int counter, int* token_out,
+                            float* logprob_out, float* kth_out, int* nsel_out, float* total_out, hipStream_t st);
 constexpr int kBeamTopK = 16;   // row stride of the top-k outputs: beam sizes up to 15 (topk(beam_size + 1))
 // beam search: the LogitsFiltering rules, log-softmax and the K best entries of every live slot's row in one pass (row in registers)
 void launch_beam_filter_topk(const SamplerCfg* cfg_dev, const int* suppress_dev, SeqState* seq, float* logits, int batch, int K, float* lp_out,

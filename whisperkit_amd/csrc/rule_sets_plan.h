@@ -103,7 +103,8 @@ inline int rule_sets_first_undefined(const int32_t* set_of_slot, const int32_t* 
 // at all - a set other than 0, or set 0 while the session's own rules are on.  Un-ruled audios keep the fused sampler, and with it their bits.
 inline bool rule_set_ruled(int set, bool session_rules_on) { return set != 0 || session_rules_on; }
 // option_mix_plan inside each part of that partition, the un-ruled part first: groups are numbered on, classes stay per group.
-// opts[i] == nullptr: the audio takes no part.  ruled null: one part, option_mix_plan itself.
+// opts[i] == nullptr: the audio takes no part.  ruled null: one part, option_mix_plan itself.  ruled[i] is the audio's part, 0 .. 3: bit 0 the rules bit above, bit 1
+// (wh_session_set_wide_top_k, topk_wide_plan.h) whether the audio's T > 0 rungs sample wide - a pass has one sampler, so that bit splits groups as well.
 inline OptionMixPlan rule_sets_mix_plan(const wh_decoding_options* const* opts, const unsigned char* ruled, int n, int max_classes = kMaxOptionClasses,
                                         bool slot_prompts = false) {
     if (!ruled) return option_mix_plan(opts, n, max_classes, slot_prompts);
@@ -111,8 +112,8 @@ inline OptionMixPlan rule_sets_mix_plan(const wh_decoding_options* const* opts, 
     out.group.assign((size_t)(n > 0 ? n : 0), -1);
     out.cls.assign((size_t)(n > 0 ? n : 0), -1);
     std::vector<const wh_decoding_options*> po((size_t)(n > 0 ? n : 0));
-    for (int part = 0; part < 2; ++part) {
-        for (int i = 0; i < n; ++i) po[(size_t)i] = (opts[i] && (ruled[i] != 0) == (part != 0)) ? opts[i] : nullptr;
+    for (int part = 0; part < 4; ++part) {
+        for (int i = 0; i < n; ++i) po[(size_t)i] = (opts[i] && ruled[i] == part) ? opts[i] : nullptr;
         const OptionMixPlan p = option_mix_plan(po.data(), n, max_classes, slot_prompts);
         const int base = (int)out.classes.size();
         for (int i = 0; i < n; ++i) if (p.group[(size_t)i] >= 0) { out.group[(size_t)i] = base + p.group[(size_t)i]; out.cls[(size_t)i] = p.cls[(size_t)i]; }
