@@ -59,6 +59,10 @@ public final class HIPSession {
     /// (csrc/align.hip) and one copy of the paths.  The paths, and so every word timing, are the same in both, index for index.
     public enum WordAlignment: Int32 { case host = 0, device = 1 }
     public var wordAlignment: WordAlignment = .host { didSet { _ = wh_session_set_word_alignment(handle, wordAlignment.rawValue) } }
+    /// How device alignment runs the openai-style post-processing (wh_session_set_alignment_batching): `.off` (default) = three launches per slot;
+    /// `.on` = two launches per device batch (csrc/align_post.hip).  The weights, paths and word timings are the same in both, byte for byte.
+    public enum AlignmentBatching: Int32 { case off = 0, on = 1 }
+    public var alignmentBatching: AlignmentBatching = .off { didSet { _ = wh_session_set_alignment_batching(handle, alignmentBatching.rawValue) } }
     /// Where beam search (beam_size > 1) ranks its candidates (wh_session_set_beam_ranking): `.host` (default) = one copy of the top-k tables, one
     /// synchronise and one upload of the next decode state per position; `.device` = beam_rank_kernel (csrc/beamrank.hip) per position, the host
     /// looks at the device every 8 positions.  Results are the same in both, bit for bit.

@@ -327,7 +327,8 @@ int wh_session_set_alignment_postprocess(wh_session* s, int z_normalize, int med
 int wh_session_set_word_alignment(wh_session* s, int mode);
 int wh_session_word_alignment(const wh_session* s);
 /* The alignment paths of slots [0, batch) after a decode, whatever the mode: head mean of all slots in one launch (with
- * wh_session_set_alignment_postprocess on: the per-slot post-processing launches back to back), one DTW launch over rows[b] token rows of
+ * wh_session_set_alignment_postprocess on: the per-slot post-processing launches back to back, or the two batched launches of
+ * wh_session_set_alignment_batching 1), one DTW launch over rows[b] token rows of
  * slot b (0 <= rows[b] <= 256; 0 = no path, rows beyond the 224 recorded ones read as zero), one device -> host copy, one synchronise.
  * Slot b's path lands at b * capacity_per_slot, lengths[b] is its length (-length when it exceeds capacity_per_slot: nothing written). */
 int wh_alignment_paths(wh_session* s, int batch, const int32_t* rows, int32_t* text_idx, int32_t* time_idx, int32_t* lengths,
@@ -335,6 +336,22 @@ int wh_alignment_paths(wh_session* s, int batch, const int32_t* rows, int32_t* t
 /* Counters of the session since its creation: launches of the batched DTW kernel, bytes copied device -> host for the alignment
  * (wh_get_alignment_weights, wh_alignment_paths and the word timestamps of wh_transcribe*).  Either pointer may be NULL. */
 int wh_session_word_alignment_stats(const wh_session* s, int64_t* dtw_launches, int64_t* alignment_d2h_bytes);
+/* How wh_alignment_paths (and with it the word timestamps of wh_transcribe* in device mode, wh_align_tokens_batch, wh_align_text*) runs the
+ * post-processing of wh_session_set_alignment_postprocess.  0 = per slot (default): three launches per slot, back to back, through a scratch
+ * copy of the slot's probabilities.  1 = batched (csrc/align_post.hip): two launches per device batch whatever its width -
+ * row statistics, then one fused pass per (slot, tile of 48 frames) that keeps the probabilities in LDS.  The weights, and so the paths and
+ * every word timing, are the same in both modes, byte for byte.  With the post-processing off the switch changes nothing; the scratch of
+ * mode 1 (8 bytes per slot, row and alignment head) is allocated by the first batched call.  Any other mode: WH_ERR_INVALID_ARGUMENT.
+ * wh_session_alignment_batching returns the mode, -1 for NULL.  wh_get_alignment_weights keeps the per-slot kernels in either mode. */
+int wh_session_set_alignment_batching(wh_session* s, int mode);
+int wh_session_alignment_batching(const wh_session* s);
+/* Counters since the session's creation: post-processing kernels wh_alignment_paths launched (either mode), calls that took the batched
+ * path.  Either pointer may be NULL. */
+int wh_session_alignment_batching_stats(const wh_session* s, int64_t* postprocess_launches, int64_t* batched_calls);
+/* development aids (tests of the batched post-processing): slot b's [224][1500] weights as the last wh_alignment_paths left them, without a
+ * launch; overwrite n_rows recorded score rows [n_rows][n_align][1500] of slot b from first_row on (first_row + n_rows <= 224) */
+int wh_debug_alignment_mean(wh_session* s, int b, float* out_host /* [224][1500] */);
+int wh_debug_set_alignment_rows(wh_session* s, int b, int first_row, int n_rows, const float* rows_host);
 
 /* A device-resident stage output as a plain tensor descriptor (what the MLMultiArray results of the CoreML stages,
  * Core/Models.swift:848-1107, become behind a C ABI): row-major, `device` = HIP device ordinal (the session's model device). The

@@ -226,6 +226,12 @@ SYMBOLS = {
     "wh_session_word_alignment": (I, [VP]),
     "wh_alignment_paths": (I, [VP, I, PI32, PI32, PI32, PI32, I]),
     "wh_session_word_alignment_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    # batched alignment post-processing (csrc/align_post.hip, align_post_plan.h)
+    "wh_session_set_alignment_batching": (I, [VP, I]),
+    "wh_session_alignment_batching": (I, [VP]),
+    "wh_session_alignment_batching_stats": (I, [VP, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "wh_debug_alignment_mean": (I, [VP, I, PF]),
+    "wh_debug_set_alignment_rows": (I, [VP, I, I, I, PF]),
     # forced-transcript pass (csrc/forced.hip, forced_plan.h)
     "wh_score_tokens": (I, [VP, I, PVP, PI32, I, PVP, PVP, PVP]),
     "wh_align_tokens_batch": (I, [VP, PVP, PI32, I, POPT, PST, PVP, PI32, PVP, PI32]),

@@ -1477,6 +1477,37 @@ class Session:
     def wordAlignment(self) -> str:
         return {0: "host", 1: "device"}[int(self.lib.wh_session_word_alignment(self.handle))]
 
+    ALIGNMENT_BATCHINGS = {"off": 0, "on": 1}
+
+    def setAlignmentBatching(self, mode: str):
+        """How alignmentPaths (and the word timestamps in "device" wordAlignment, alignTokens, alignText) runs the post-processing of
+        setAlignmentPostprocess: "off" (default) - three launches per slot, back to back; "on" - two launches per device batch whatever its
+        width (csrc/align_post.hip).  The weights, paths and word timings are the same in both modes, byte for byte."""
+        if mode not in self.ALIGNMENT_BATCHINGS:
+            raise ValueError(f"alignmentBatching {mode!r}: expected 'on' or 'off'")
+        _check(self.lib.wh_session_set_alignment_batching(self.handle, self.ALIGNMENT_BATCHINGS[mode]))
+
+    @property
+    def alignmentBatching(self) -> str:
+        return {0: "off", 1: "on"}[int(self.lib.wh_session_alignment_batching(self.handle))]
+
+    def alignmentBatchingStats(self) -> Tuple[int, int]:
+        """(post-processing kernels alignmentPaths launched, calls that took the batched path) since the session was created"""
+        a, b = C.c_int64(), C.c_int64()
+        _check(self.lib.wh_session_alignment_batching_stats(self.handle, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def debugAlignmentMean(self, b: int) -> np.ndarray:
+        """Development aid (wh_debug_alignment_mean): slot b's [224][1500] weights as the last alignmentPaths left them, without a launch"""
+        out = np.zeros((L.MAX_TOKEN_CONTEXT, L.AUDIO_CTX), np.float32)
+        _check(self.lib.wh_debug_alignment_mean(self.handle, int(b), out.ctypes.data_as(L.PF)))
+        return out
+
+    def debugSetAlignmentRows(self, b: int, firstRow: int, rows: np.ndarray):
+        """Development aid (wh_debug_set_alignment_rows): overwrite recorded score rows [nRows][nAlign][1500] of slot b from firstRow on"""
+        r = np.ascontiguousarray(rows, dtype=np.float32)
+        _check(self.lib.wh_debug_set_alignment_rows(self.handle, int(b), int(firstRow), int(r.shape[0]), r.ctypes.data_as(L.PF)))
+
     def alignmentPaths(self, batch: int, rows: Sequence[int]) -> List[Tuple[List[int], List[int]]]:
         """The DTW paths (textIndices, timeIndices) of slots [0, batch) over the first rows[b] alignment rows of slot b, after a decode:
         one head-mean launch, one batched DTW launch, one copy (wh_alignment_paths; works in either wordAlignment mode)."""

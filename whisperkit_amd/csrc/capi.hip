@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "align_post_plan.h"
 #include "internal.h"
 #include "knobs.h"
 
@@ -878,6 +879,18 @@ static int ensure_align_tmp(wh_session* s) {
     }
     return WH_OK;
 }
+// the only place that allocates the batched post-processing's row statistics (the first batched call of alignment_paths; again when the head count moved)
+static int ensure_align_post(wh_session* s) {
+    wh_session::WordAlign& f = s->walign;
+    if (f.post && f.post_heads != s->n_align_alloc) { WH_HIP(hipStreamSynchronize(s->st)); s->mem.release(f.post); f.post = nullptr; }
+    if (!f.post) {
+        mem::AlignPostView measure{};
+        WH_HIP(s->mem.alloc(&f.post, mem::pack_align_post(nullptr, (size_t)s->B, kMaxTok, (size_t)s->n_align_alloc, measure) / sizeof(float), false));
+        mem::pack_align_post(f.post, (size_t)s->B, kMaxTok, (size_t)s->n_align_alloc, f.p);
+        f.post_heads = s->n_align_alloc;
+    }
+    return WH_OK;
+}
 // the only place that allocates the batched DTW's tables (the first call of alignment_paths)
 static int dtw_ensure(wh_session* s) {
     wh_session::WordAlign& f = s->walign;
@@ -934,9 +947,14 @@ int alignment_paths(wh_session* s, int batch, const int32_t* rows, const int32_t
         return WH_OK;
     }
     const bool postprocess = s->align_znorm || s->align_median > 1;
-    if (postprocess) {
+    if (plan::align_post_applies(s->walign.batching, s->align_znorm, s->align_median)) {
+        int r = ensure_align_post(s); if (r) return r;
+        launch_alignment_postprocess_batch(s->align, batch, s->n_align_alloc, s->walign.p.stat, s->walign.p.flags, s->align_znorm, s->align_median, s->align_mean, s->st);
+        s->walign.post_launches += plan::kAlignPostLaunches; s->walign.batched_calls += 1;
+    } else if (postprocess) {
         int r = ensure_align_tmp(s); if (r) return r;
         for (int b = 0; b < batch; ++b) launch_alignment_slot(s, b, true);       // back to back: the scratch is reused in stream order
+        s->walign.post_launches += (long long)batch * (s->align_znorm ? 3 : 2);
     } else {
         launch_alignment_mean(s->align, batch, s->n_align_alloc, s->align_mean, s->st);
     }
@@ -982,6 +1000,40 @@ extern "C" int wh_session_word_alignment_stats(const wh_session* s, int64_t* dtw
     if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_word_alignment_stats: null session");
     whi::store_stat(dtw_launches, s->walign.dtw_launches);
     whi::store_stat(alignment_d2h_bytes, s->walign.d2h_bytes);
+    return WH_OK;
+}
+
+extern "C" int wh_session_set_alignment_batching(wh_session* s, int mode) {
+    if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_alignment_batching: null session");
+    if (!plan::alignment_batching_mode_valid(mode)) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_set_alignment_batching: mode %d (0 = per slot, 1 = batched)", mode);
+    s->walign.batching = mode;
+    return WH_OK;
+}
+extern "C" int wh_session_alignment_batching(const wh_session* s) { return s ? s->walign.batching : -1; }
+extern "C" int wh_session_alignment_batching_stats(const wh_session* s, int64_t* postprocess_launches, int64_t* batched_calls) {
+    if (!s) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_session_alignment_batching_stats: null session");
+    whi::store_stat(postprocess_launches, s->walign.post_launches);
+    whi::store_stat(batched_calls, s->walign.batched_calls);
+    return WH_OK;
+}
+// Development aids.  wh_debug_alignment_mean: slot b's [224][1500] weights as the last wh_alignment_paths (or word-timestamp pass) left them, no launch.
+// wh_debug_set_alignment_rows: overwrite n_rows recorded score rows [n_rows][n_align][1500] of slot b from first_row on.
+extern "C" int wh_debug_alignment_mean(wh_session* s, int b, float* out) {
+    CHECK_SESSION(s); CHECK_SLOT(s, b);
+    if (!out) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_alignment_mean: null output");
+    if (!s->align) return set_error(WH_ERR_SEGMENTING_FAILED, "no alignment weights recorded (run a decode with word timestamps / the step API first)");
+    const size_t n = (size_t)kMaxTok * kCtx;
+    WH_HIP(hipStreamSynchronize(s->st));
+    WH_HIP(hipMemcpy(out, s->align_mean + b * n, n * 4, hipMemcpyDeviceToHost));
+    return WH_OK;
+}
+extern "C" int wh_debug_set_alignment_rows(wh_session* s, int b, int first_row, int n_rows, const float* rows) {
+    CHECK_SESSION(s); CHECK_SLOT(s, b);
+    if (!rows || first_row < 0 || n_rows < 1 || first_row + n_rows > kMaxTok) return set_error(WH_ERR_INVALID_ARGUMENT, "wh_debug_set_alignment_rows: rows [%d, %d) outside [0, %d)", first_row, first_row + n_rows, kMaxTok);
+    if (!s->align) return set_error(WH_ERR_SEGMENTING_FAILED, "no alignment weights recorded (run a decode with word timestamps / the step API first)");
+    const size_t row = (size_t)s->n_align_alloc * kCtx;
+    WH_HIP(hipStreamSynchronize(s->st));
+    WH_HIP(hipMemcpy(s->align + ((size_t)b * kMaxTok + first_row) * row, rows, (size_t)n_rows * row * 4, hipMemcpyHostToDevice));
     return WH_OK;
 }
 

@@ -160,6 +160,7 @@ struct RuleSetsHostView { int32_t *slots, *stage; };
 struct DtwView { int32_t *rows, *len, *ti, *tj; };
 struct BeamSumView { float* half[2]; };
 struct AlignTmpView { float *rows, *stat; int32_t* flags; };
+struct AlignPostView { float* stat; int32_t* flags; };
 template <class Seq> struct PrefillSeqView { Seq *master, *fin; };
 struct PrefillTabView { int32_t *ended, *home, *owner; };
 
@@ -228,6 +229,12 @@ template <class V> size_t pack_beam_sums(void* base, size_t B, V& v) {
 template <class V> size_t pack_align_tmp(void* base, size_t max_tok, size_t heads, size_t ctx, V& v) {
     Pack c(base);
     c.take(v.rows, max_tok * heads * ctx); c.take(v.stat, 2 * heads * ctx); c.take(v.flags, 256);
+    return c.size();
+}
+// batched alignment post-processing, the whole session width: (row maximum, 1 / row sum) [B][max_tok][heads][2] | written flags [B][max_tok]
+template <class V> size_t pack_align_post(void* base, size_t B, size_t max_tok, size_t heads, V& v) {
+    Pack c(base);
+    c.take(v.stat, B * max_tok * heads * 2); c.take(v.flags, B * max_tok);
     return c.size();
 }
 

@@ -110,11 +110,16 @@ struct wh_session {
     // word-timestamp alignment beyond the raw rows (wh_session_set_word_alignment): mode 0 = DTW per slot on the host, 1 = one batched DTW launch per device batch
     // (align.hip).  tmp: the scratch of the optional post-processing, one slot at a time, (re)sized for the session's alignment-head count by capi.hip
     // ensure_align_tmp and cut by devmem.h pack_align_tmp.  dev / host (pinned): the batched DTW's tables, allocated by the first call of alignment_paths and cut by
-    // pack_dtw - the device buffer has the token rows in front of what the pinned mirror holds.
+    // pack_dtw - the device buffer has the token rows in front of what the pinned mirror holds.  batching (wh_session_set_alignment_batching): 1 = alignment_paths
+    // runs the post-processing of the whole batch in two launches (align_post.hip); post / p: its row statistics for the session's width, allocated by the first
+    // batched call (capi.hip ensure_align_post, devmem.h pack_align_post) and by nothing else.  post_launches: post-processing kernels alignment_paths launched.
     struct WordAlign {
-        int mode = 0;
+        int mode = 0, batching = 0;
         float* tmp = nullptr; int tmp_heads = 0;
         wh::mem::AlignTmpView t{};
+        float* post = nullptr; int post_heads = 0;
+        wh::mem::AlignPostView p{};
+        long long post_launches = 0, batched_calls = 0;   // wh_session_alignment_batching_stats
         int32_t *dev = nullptr, *host = nullptr;
         wh::mem::DtwView d{}, h{};
         long long dtw_launches = 0, d2h_bytes = 0;   // wh_session_word_alignment_stats

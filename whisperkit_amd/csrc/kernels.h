@@ -520,6 +520,10 @@ void launch_alignment_mean(const float* align, int batch, int n_align, float* ou
 // openai/whisper-style alignment post-processing of one slot (z-normalise over the token rows, median filter, head mean)
 void launch_alignment_postprocess(const float* align, int n_align, float* prob_tmp, float* stat_tmp, int* row_written, int znorm, int median_width,
                                   float* out, hipStream_t st);
+// the same post-processing for `batch` consecutive slots in two launches (align_post.hip): stat [batch][224][n_align][2] and flags [batch][224] are scratch,
+// out [batch][224][1500] is byte for byte what launch_alignment_postprocess writes slot by slot.  median_width: 0 / 1 (off) or odd and <= 15
+void launch_alignment_postprocess_batch(const float* align, int batch, int n_align, float* stat, int* flags, int znorm, int median_width, float* out,
+                                        hipStream_t st);
 // batched dynamic time warping (align.hip): one workgroup per matrix m[k] = [rows_stride][cols] (rows at or beyond rows_stride read as 0), rows_dev[k]
 // in [0, max_rows] (0: length 0), paths to text_idx / time_idx [n][capacity], lengths [n] (-length when a path exceeds capacity).  Returns WH_OK,
 // WH_ERR_INVALID_ARGUMENT (max_rows outside [1, kDtwMaxRows], cols outside [1, kDtwMaxCols]: nothing is launched) or WH_ERR_HIP.
